@@ -1,10 +1,10 @@
 #!/usr/bin/env python
 """Headline benchmark: sentences/s embedded by text_sonar_basic_encoder
-(fp16, batch 1024, seq_len 128 -- BASELINE.json configs[1]) on N MI355X, plus
-xsim pairs/s at BASELINE configs[2] scale (1M x 1M x 1024), the roofline of the
+(fp16, batch 1024, seq_len 128 -- BASELINE.json configs[1]) on N MI355X.  With --full,
+also xsim pairs/s at BASELINE configs[2] scale (1M x 1M x 1024), the roofline of the
 dominant kernel and the CPU oracle baseline timed on the same box in the same run.
 
-  python bench.py --gpus 1 --steps 10 --warmup 3
+  python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
       --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,10 +14,19 @@ HBM; for N > 1 each rank encodes its own batch (weak scaling, sentences are inde
 SURVEY 8(e)) and the step ends with the RCCL all-gather that assembles the embedding
 matrix.  Rank 0 prints ONE JSON line on stdout; everything else goes to stderr.
 
-Extra objects in the same line (N = 1): `varlen` (C2(b): lengths randint(16,129)), `c1`
-(BASELINE configs[0]: 32 sentences <= 64 tokens -- GPU time, CPU-oracle time and the
-1 - cos between the two on identical weights and inputs), `xsim` (+ its own
-`cpu_baseline`), `decoder` (C5), `speech` (C4).
+A plain run sets up, runs W warm-up steps, times exactly K steps (`ms_per_step`, `value`),
+writes the outputs if asked and prints the line.  --dump-outputs DIR writes what the last
+timed step returned -- the [N * 1024, 1024] sentence-embedding matrix -- as
+DIR/sentence_embeddings.npy (float32); weights and ids are seeded, so two builds given the
+same arguments can be compared output for output.
+
+Everything else needs --full: a second K-step pass with the engine's per-launch profiling
+(`ms_per_step_profiled`, `kernels`, `hbm_kernels`, `roofline`), `cpu_baseline` and
+`parity`, `xsim` (+ its own `cpu_baseline`) and the extra legs (N = 1): `varlen` (C2(b):
+lengths randint(16,129)), `c1` (BASELINE configs[0]: 32 sentences <= 64 tokens -- GPU time,
+CPU-oracle time and the 1 - cos between the two on identical weights and inputs),
+`batch5`, `e2e`, `decoder` (C5), `speech` (C4).  --no-cpu-baseline / --no-xsim /
+--no-extras drop parts of a --full run.
 
 SONAR_BENCH_DRYRUN=1 swaps the engine for a CPU stub and RCCL for gloo: it exists so
 that the N > 1 control flow (process group, the all-gathers inside the timed step, the
@@ -63,6 +72,26 @@ def cpu_threads() -> int:
         avail = os.cpu_count() or 1
     torch.set_num_threads(max(1, min(16, avail)))
     return torch.get_num_threads()
+
+
+DUMP_BYTES = 64 * 10**6   # --dump-outputs writes at most this much
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: each tensor as DIR/<name>.npy in float32.  A tensor above the budget is replaced by a fixed
+    sample of its rows (seed 0, sorted), whose indices go to DIR/<name>_rows.npy (float64)."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        if a.nbytes > DUMP_BYTES:
+            keep = max(1, DUMP_BYTES // (a.nbytes // a.shape[0] + 8) - 1)   # + 8: the float64 row index
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(dirname, f"{name}_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        log(f"[dump] {name}.npy {list(a.shape)} float32 -> {dirname}")
 
 
 def best_of(fn, reps=3):
@@ -378,6 +407,64 @@ def speech_leg(dev, n=64, cpu=True):
     return out
 
 
+def profiled_pass(model, timed, step, steps, batch_n, seq):
+    """The second K-step pass of --full, with the engine's per-launch HIP-event profiling on: returns
+    (ms_per_step_profiled, roofline, kernels, hbm_kernels)."""
+    model.engine.set_profiling(True)
+    elapsed_prof = timed(step, steps, 0)
+    model.engine.set_profiling(False)
+    prof = model.engine.read_profile()
+    ffn1 = prof["gemm_ffn1"]
+    ffn1_ms = ffn1["ms"] / max(ffn1["launches"], 1)
+    achieved = FFN1_FLOPS_PER_LAUNCH / (ffn1_ms * 1e-3) / 1e12 if ffn1_ms > 0 else None
+    traffic, traffic_src = None, None
+    tfile = os.path.join(ROOT, "profiles", "traffic.json")
+    if os.path.exists(tfile):
+        try:
+            tj = json.load(open(tfile))
+            traffic = tj.get("gemm_ffn1_hbm_bytes_per_launch")
+            traffic_src = "profiles/traffic.json (STATIC: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of " + \
+                          str(tj.get("state", "r01m")) + ", not measured in this run)"
+        except Exception:
+            traffic = None
+    roofline = {"bound": "mfma", "kernel": "gemm_v2_kernel<EPI_RELU_F16, LayerNorm-fold consumer> (FFN inner projection, M=131072 N=8192 K=1024; "
+                                           "4-wave 256x256 engine, csrc/gemm_v2.hip; SMI_G2V2=0: gemm_tn256_kernel<EPI_RELU_F16>)",
+                "timed_region": "the second (profiled) K-step pass: HIP events around every launch on the engine's stream",
+                "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": achieved / MFMA_PEAK_TFLOPS if achieved else None, "traffic": traffic,
+                "traffic_source": traffic_src, "avg_launch_ms": ffn1_ms, "launches": ffn1["launches"],
+                "flops_per_launch": FFN1_FLOPS_PER_LAUNCH,
+                "note": "since round 3 this kernel also applies the LayerNorm that precedes it (LayerNorm folded into the GEMMs, "
+                        "DESIGN.md 3.1: +2.6 % of its time, measured same-box, for 48 LayerNorm launches = 4.5 ms less per step; "
+                        "SMI_ENC_LNFOLD=0 restores the separate launches); `achieved` counts the GEMM's flops only"}
+    kernels = {k: {"ms_per_step": v["ms"] / steps, "launches_per_step": v["launches"] / steps} for k, v in prof.items()}
+    # HBM-bound kernels of the step: algorithmic bytes per launch (SURVEY 8(d): fp16 residual stream and operands,
+    # T = 131072 tokens, d = 1024) / mean HIP-event time of the launches inside the timed region
+    HBM_PEAK_GBS = 8000.0
+    tok = batch_n * seq
+    hbm_bytes = {"layernorm": tok * D * 2 * 2,                 # read x, write h
+                 "attention": tok * D * 2 * 4,                 # read q|k|v, write ctx
+                 "ln_pool": tok * D * 2 + batch_n * D * 2,     # read x, write one vector per sentence (the pooling kernel)
+                 "embed": tok * (8 + D * 2 + D * 2)}           # ids + gathered table row + x row (the fp32 position rows are L2 hits)
+    hbm_kernels = {}
+    ln_prof = prof.get("layernorm")
+    if ln_prof and ln_prof["launches"] and ln_prof["launches"] / steps < 2:
+        # LayerNorm folded into the GEMMs (DESIGN.md 3.1): the only launch left in this slot is the row-statistics pass
+        # over the embedding output (reads x once, writes 8 B per row)
+        hbm_bytes["layernorm"] = tok * D * 2 + tok * 8
+        hbm_kernels["layernorm_note"] = "LayerNorm is folded into the QKV / FFN-inner GEMMs; this slot times the one row-statistics pass"
+    for name, nbytes in hbm_bytes.items():
+        p_ = prof.get(name)
+        if p_ and p_["launches"] and p_["ms"] > 0:
+            us = p_["ms"] / p_["launches"] * 1e3
+            hbm_kernels[name] = {"bytes_per_launch": nbytes, "avg_launch_us": us, "achieved_GBs": nbytes / us / 1e3,
+                                 "frac_of_hbm_peak": nbytes / us / 1e3 / HBM_PEAK_GBS,
+                                 "launches_per_step": p_["launches"] / steps}
+    hbm_kernels["note"] = ("single launches per step (embed, ln_pool, the row-statistics pass) are dominated by ramp-up and "
+                           "tail; attention (24 launches per step) is the steady-state figure")
+    return elapsed_prof / steps * 1e3, roofline, kernels, hbm_kernels
+
+
 # ---------------------------------------------------------------------- dry-run stubs (CPU, gloo)
 class _StubEngine:
     device_bytes = 0
@@ -469,6 +556,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the profiled pass (kernels, roofline), CPU baselines and parity, xsim and the "
+                         "extra legs; without it a run only times the headline steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the sentence embeddings of the last one as DIR/sentence_embeddings.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-xsim", action="store_true")
     ap.add_argument("--xsim-ring", action="store_true",
@@ -601,7 +693,7 @@ def main():
         sd = text_encoder_state_dict(dev)
         model = SonarTextTransformerEncoderModel(get_text_encoder_config("basic"), sd, device=dev, dtype=torch.float16,
                                                  max_tokens_hint=BATCH * SEQ, fp16_residual=not args.fp32_residual)
-        want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+        want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
         # the CPU baseline runs the SAME weights (fp16-representable values, fp32 arithmetic)
         sd_cpu = {k: v.float().cpu() for k, v in sd.items()} if want_cpu else None
         del sd
@@ -618,83 +710,37 @@ def main():
     batch = SequenceBatch(ids, None)
     gathered = torch.empty((world * batch_n, D), dtype=torch.float16, device=dev) if use_dist else None
 
+    last = {}
+
     def step():
         emb = model(batch).sentence_embeddings
         if use_dist:
             dist.all_gather_into_tensor(gathered, emb)  # assemble the embedding matrix over RCCL / xGMI
+        last["emb"] = gathered if use_dist else emb     # what a caller of the step receives (--dump-outputs)
         return emb
 
     for _ in range(args.warmup):
         step()
-    # Two timed passes of exactly K steps: the HEADLINE pass runs without the engine's per-launch
-    # HIP-event profiling (~170 event pairs per step); the second pass, with it, supplies the per-kernel table and the
-    # roofline's live launch durations, and is reported beside the headline as `ms_per_step_profiled`.
+    # With --full, two timed passes of exactly K steps: the HEADLINE pass runs without the engine's
+    # per-launch HIP-event profiling (~170 event pairs per step); the second pass, with it, supplies the per-kernel table
+    # and the roofline's live launch durations, and is reported beside the headline as `ms_per_step_profiled`.
     elapsed = timed(step, args.steps, 0)
-    model.engine.set_profiling(True)
-    elapsed_prof = timed(step, args.steps, 0)
-    model.engine.set_profiling(False)
-    prof = model.engine.read_profile()
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * batch_n * args.steps / elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"sentence_embeddings": last["emb"]})
+    if args.full:
+        ms_per_step_profiled, roofline, kernels, hbm_kernels = profiled_pass(model, timed, step, args.steps, batch_n, seq)
 
     c2_gpu = None
-    if not DRYRUN and rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and not DRYRUN and rank == 0 and world == 1 and not args.no_cpu_baseline:
         c2_gpu = step()[: args.cpu_sentences].float().cpu()   # the rows the CPU oracle will encode (untimed extra call)
         c2_ids_cpu = ids[: args.cpu_sentences].cpu()
-    ms_per_step = elapsed / args.steps * 1e3
-    ms_per_step_profiled = elapsed_prof / args.steps * 1e3
-    value = world * batch_n * args.steps / elapsed
-    ffn1 = prof["gemm_ffn1"]
-    ffn1_ms = ffn1["ms"] / max(ffn1["launches"], 1)
-    achieved = FFN1_FLOPS_PER_LAUNCH / (ffn1_ms * 1e-3) / 1e12 if ffn1_ms > 0 else None
-    traffic, traffic_src = None, None
-    tfile = os.path.join(ROOT, "profiles", "traffic.json")
-    if os.path.exists(tfile):
-        try:
-            tj = json.load(open(tfile))
-            traffic = tj.get("gemm_ffn1_hbm_bytes_per_launch")
-            traffic_src = "profiles/traffic.json (STATIC: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of " + \
-                          str(tj.get("state", "r01m")) + ", not measured in this run)"
-        except Exception:
-            traffic = None
-    roofline = {"bound": "mfma", "kernel": "gemm_v2_kernel<EPI_RELU_F16, LayerNorm-fold consumer> (FFN inner projection, M=131072 N=8192 K=1024; "
-                                           "4-wave 256x256 engine, csrc/gemm_v2.hip; SMI_G2V2=0: gemm_tn256_kernel<EPI_RELU_F16>)",
-                "timed_region": "the second (profiled) K-step pass: HIP events around every launch on the engine's stream",
-                "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": achieved / MFMA_PEAK_TFLOPS if achieved else None, "traffic": traffic,
-                "traffic_source": traffic_src, "avg_launch_ms": ffn1_ms, "launches": ffn1["launches"],
-                "flops_per_launch": FFN1_FLOPS_PER_LAUNCH,
-                "note": "since round 3 this kernel also applies the LayerNorm that precedes it (LayerNorm folded into the GEMMs, "
-                        "DESIGN.md 3.1: +2.6 % of its time, measured same-box, for 48 LayerNorm launches = 4.5 ms less per step; "
-                        "SMI_ENC_LNFOLD=0 restores the separate launches); `achieved` counts the GEMM's flops only"}
-    kernels = {k: {"ms_per_step": v["ms"] / args.steps, "launches_per_step": v["launches"] / args.steps} for k, v in prof.items()}
-    # HBM-bound kernels of the step: algorithmic bytes per launch (fp16 residual stream and operands,
-    # T = 131072 tokens, d = 1024) / mean HIP-event time of the launches inside the timed region
-    HBM_PEAK_GBS = 8000.0
-    tok = batch_n * seq
-    hbm_bytes = {"layernorm": tok * D * 2 * 2,                 # read x, write h
-                 "attention": tok * D * 2 * 4,                 # read q|k|v, write ctx
-                 "ln_pool": tok * D * 2 + batch_n * D * 2,     # read x, write one vector per sentence (the pooling kernel)
-                 "embed": tok * (8 + D * 2 + D * 2)}           # ids + gathered table row + x row (the fp32 position rows are L2 hits)
-    hbm_kernels = {}
-    ln_prof = prof.get("layernorm")
-    if ln_prof and ln_prof["launches"] and ln_prof["launches"] / args.steps < 2:
-        # LayerNorm folded into the GEMMs: the only launch left in this slot is the row-statistics pass
-        # over the embedding output (reads x once, writes 8 B per row)
-        hbm_bytes["layernorm"] = tok * D * 2 + tok * 8
-        hbm_kernels["layernorm_note"] = "LayerNorm is folded into the QKV / FFN-inner GEMMs; this slot times the one row-statistics pass"
-    for name, nbytes in hbm_bytes.items():
-        p_ = prof.get(name)
-        if p_ and p_["launches"] and p_["ms"] > 0:
-            us = p_["ms"] / p_["launches"] * 1e3
-            hbm_kernels[name] = {"bytes_per_launch": nbytes, "avg_launch_us": us, "achieved_GBs": nbytes / us / 1e3,
-                                 "frac_of_hbm_peak": nbytes / us / 1e3 / HBM_PEAK_GBS,
-                                 "launches_per_step": p_["launches"] / args.steps}
-    hbm_kernels["note"] = ("single launches per step (embed, ln_pool, the row-statistics pass) are dominated by ramp-up and "
-                           "tail; attention (24 launches per step) is the steady-state figure")
-
     # ------------------------------------------------------------ C2(b) varlen + C1 (N = 1 only)
+    extras = args.full and world == 1 and not args.no_extras and not DRYRUN
     extra = {}
     c1_gpu = None
-    if world == 1 and not args.no_extras and not DRYRUN:
+    if extras:
         lens = torch.randint(16, SEQ + 1, (BATCH,), generator=torch.Generator().manual_seed(0))
         vids = ids.clone()
         for i, n in enumerate(lens.tolist()):
@@ -726,7 +772,7 @@ def main():
                                        "randint(8,65) seed 1, fp16 (text.py:178)",
                            "tokens": int(b5_lens.sum()), "ms": b5_t / 50 * 1e3, "sentences_per_s": 5 * 50 / b5_t}
 
-    if world == 1 and not args.no_extras and not DRYRUN:
+    if extras:
         try:
             extra["e2e"] = e2e_leg(model, dev)
         except Exception as e:  # an extra, never the reason the headline is lost
@@ -737,7 +783,7 @@ def main():
 
     # ------------------------------------------------------------ xsim leg (BASELINE configs[2])
     xs = None
-    if not args.no_xsim:
+    if args.full and not args.no_xsim:
         n_total = args.xsim_n if not DRYRUN else 512 * world
         if n_total % world:
             raise SystemExit(f"--xsim-n {n_total} must divide over {world} ranks")
@@ -800,7 +846,7 @@ def main():
         # xsim as LASER defines it (source/xsim.py, margin "ratio", k = 4): forward top-4 (x -> y), backward top-4
         # (y -> x), margin re-scoring of the forward candidates; N = 1 only.  The error is counted against the
         # constructed neighbours (x_i was built from y_src(i)), so it must be 0.
-        if world == 1 and not args.no_extras and not DRYRUN:
+        if extras:
             def margin_mine():
                 xn = xs_mod.normalize_rows(x_local)
                 yn = xs_mod.normalize_rows(y_local)
@@ -830,7 +876,7 @@ def main():
                 xs["margin"]["cpu_baseline"] = xsim_margin_cpu_baseline()
 
     # ------------------------------------------------- secondary configs (BASELINE C4 / C5), N = 1 only
-    if world == 1 and not args.no_extras and not DRYRUN:
+    if extras:
         del model
         torch.cuda.empty_cache()
         try:
@@ -863,25 +909,35 @@ def main():
             extra["c1"]["speedup_vs_cpu"] = extra["c1"]["sentences_per_s"] / cb["c1"]["value"]
 
     if rank == 0:
+        # the headline fields; the others only in a --full run, in the same places of the line
         out = {
             "metric": "sentences/sec embedded (seq128 b1024)", "value": value, "unit": "sentences/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-            "ms_per_step_profiled": ms_per_step_profiled,   # the second K-step pass, per-launch HIP-event profiling on (kernels / roofline)
+        }
+        if args.full:
+            out["ms_per_step_profiled"] = ms_per_step_profiled   # the second K-step pass, per-launch HIP-event profiling on (kernels / roofline)
+        out.update({
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f16",
-            "data": "synthetic" if not DRYRUN else "dry-run stub",
+            "data": "synthetic" if not DRYRUN else "dry-run stub", "full": args.full,
             "config": {"workload": "text_sonar_basic_encoder fp16, batch 1024 x seq_len 128 per GPU, eng_Latn (BASELINE configs[1])",
                        "global_batch": world * batch_n, "seq_len": seq, "parallelism": f"dp{world}",
                        "weights": "random-init basic arch (24L, d=1024, F=8192, V=256206)"},
-            "roofline": roofline, "cpu_baseline": cb,
-            "parity": {"tolerance_1_minus_cos": 1e-3,
-                       "c2_max_1_minus_cos_vs_cpu_oracle": cb.get("c2_max_1_minus_cos_vs_gpu") if cb else None,
-                       "c1_max_1_minus_cos_vs_cpu_oracle": extra.get("c1", {}).get("max_1_minus_cos_vs_cpu_oracle"),
-                       "xsim_top1_agreement": xs.get("top1_agreement_with_constructed_neighbours") if xs else None},
+        })
+        if args.full:
+            out.update({
+                "roofline": roofline, "cpu_baseline": cb,
+                "parity": {"tolerance_1_minus_cos": 1e-3,
+                           "c2_max_1_minus_cos_vs_cpu_oracle": cb.get("c2_max_1_minus_cos_vs_gpu") if cb else None,
+                           "c1_max_1_minus_cos_vs_cpu_oracle": extra.get("c1", {}).get("max_1_minus_cos_vs_cpu_oracle"),
+                           "xsim_top1_agreement": xs.get("top1_agreement_with_constructed_neighbours") if xs else None},
+            })
+        out.update({
             "collective": _with_rccl_log(collective, rccl_log),
             "encoder_tflops": value * FLOPS_PER_SENTENCE / 1e12,
             "encoder_frac_of_mfma_peak": value * FLOPS_PER_SENTENCE / 1e12 / (MFMA_PEAK_TFLOPS * world),
-            "kernels": kernels, "hbm_kernels": hbm_kernels, "xsim": xs, **extra,
-        }
+        })
+        if args.full:
+            out.update({"kernels": kernels, "hbm_kernels": hbm_kernels, "xsim": xs, **extra})
         print(json.dumps(out), flush=True)
     if use_dist:
         dist.destroy_process_group()

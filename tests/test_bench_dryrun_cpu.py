@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -30,7 +31,7 @@ def test_bench_control_flow_dry_run(world, form):
     env = dict(os.environ, SONAR_BENCH_DRYRUN="1", OMP_NUM_THREADS="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    args = ["--gpus", str(world), "--steps", "3", "--warmup", "1"]
+    args = ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--full"]   # --full: the xsim leg and the roofline too
     ring = form.endswith("-ring")       # --xsim-ring: Y shards rotated around the ranks under the mining
     if ring:
         args.append("--xsim-ring")
@@ -63,6 +64,32 @@ def test_bench_control_flow_dry_run(world, form):
     assert out["parity"]["xsim_top1_agreement"] == xs["top1_agreement_with_constructed_neighbours"]
     for key in ("metric", "unit", "roofline", "cpu_baseline", "vs_baseline", "dtype"):
         assert key in out
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_bench_plain_run_is_lean_and_dumps_outputs(world, tmp_path):
+    """Without --full a run times the headline steps and nothing else; --dump-outputs writes what the last timed step
+    returned (the all-gathered embedding matrix for N > 1) as float32 .npy files."""
+    env = dict(os.environ, SONAR_BENCH_DRYRUN="1", OMP_NUM_THREADS="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dump = tmp_path / "out"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "4", "--warmup", "2",
+           "--dump-outputs", str(dump)]
+    r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    out = json.loads(lines[0])
+    assert out["full"] is False and out["steps"] == 4 and out["warmup"] == 2 and out["n_gpus"] == world
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out
+    assert abs(out["value"] - 8 * world * 4 / (out["ms_per_step"] * 4 / 1e3)) / out["value"] < 1e-6
+    for key in ("ms_per_step_profiled", "roofline", "kernels", "hbm_kernels", "cpu_baseline", "parity", "xsim"):
+        assert key not in out, key
+    emb = np.load(dump / "sentence_embeddings.npy")
+    assert emb.dtype == np.float32 and emb.shape == (8 * world, 1024)
+    assert sorted(p.name for p in dump.iterdir()) == ["sentence_embeddings.npy"]
 
 
 def test_bench_refuses_a_rank_count_that_contradicts_gpus():

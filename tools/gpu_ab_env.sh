@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 OUT=$PWD/gpurun_out; mkdir -p $OUT
 LOG=$OUT/${TAG}_ab.txt
 : > $LOG
-c2() { python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-xsim 2>/dev/null | python -c "
+c2() { python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-extras --no-xsim 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readline())
 print('C2 %.2f ms  %.0f sent/s  ' % (d['ms_per_step'], d['value']) + ' '.join('%s %.2f' % (k, v['ms_per_step']) for k, v in d['kernels'].items() if k.startswith('gemm') or k == 'attention'))"; }
