@@ -142,7 +142,7 @@ const char* smi_version(void);
 /* ABI revision of this header: bumped whenever a struct grows, an argument list changes or a workspace formula
  * changes (round 2 = 2, round 3 = 3, ...).  A binding compares it with SMI_ABI_VERSION at load time and refuses a
  * library built from another revision (the structs carry no size field). */
-#define SMI_ABI_VERSION 6
+#define SMI_ABI_VERSION 7
 int smi_abi_version(void);
 const char* smi_last_error(void);
 /* Tuning registry (round 5).  Every A/B switch of the library -- engine-family thresholds, split-K part counts, storage
@@ -315,6 +315,53 @@ int smi_text_decoder_set_beam_logits_dtype(smi_text_decoder* dec, int32_t dtype)
  * output projection writes and the next kernel reads at 1 280 rows (-3.9 % of a C5 step).  An fp16 model's Python engine
  * (TextDecoderEngine(dtype=float16)) selects it; a C caller gets fp32 partial sums unless it asks. */
 int smi_text_decoder_set_slab_dtype(smi_text_decoder* dec, int32_t dtype);
+
+/* Step processors of smi_text_decoder_generate / smi_text_decoder_sample (fairseq2's NGramRepeatBlockProcessor and
+ * BannedSequenceProcessor, handed over as `step_processors=` by the reference's pipelines).  They act on the FREE steps only
+ * (not on the teacher-forced prompt steps, not on the forced EOS at max_seq_len - 1), on the row's sequence so far, prompt
+ * included:
+ *   ngram_size n >= 1: for every window start i in [0, L - n] whose n - 1 tokens equal the last n - 1 tokens of the
+ *     sequence (length L), the token s[i + n - 1] is banned; n = 1 bans every token present, the prompt's EOS included
+ *     (generation then runs to the length cap); 0 = off.
+ *   banned sequence b (HOST CSR: tokens banned_tokens[banned_offsets[q] .. banned_offsets[q + 1]), num_banned of them, each
+ *     non-empty): b[-1] is banned when the last len(b) - 1 tokens equal b[:-1]; a length-1 sequence is banned always.
+ * Beam search: a banned token's log-probability is -inf AFTER log_softmax (the normaliser is the untouched row's).
+ * Sampling: its probability is 0 before the top-k / top-p filter (not renormalised first). */
+typedef struct smi_step_processors {
+  int32_t ngram_size;
+  int32_t num_banned;
+  const int32_t* banned_tokens;   /* host */
+  const int32_t* banned_offsets;  /* host [num_banned + 1], banned_offsets[0] == 0 */
+} smi_step_processors;
+
+/* Per-handle setting, as smi_text_decoder_set_chains: NULL (or all off) clears it.  The banned-sequence table is copied to
+ * the device here.  Errors: token ids outside the vocabulary, empty sequences, more than 1024 sequences, a sequence or an
+ * ngram_size longer than the decoder's max_seq_len, or a max_seq_len above 1023.  A row whose every token is banned (a
+ * small vocabulary can be covered) gets no candidate in the beam search (its slot goes inert, as when fewer than `beam`
+ * continuations exist) and, when sampling, ends with EOS at log-probability -inf. */
+int smi_text_decoder_set_step_processors(smi_text_decoder* dec, const smi_step_processors* procs);
+
+/* The beam search's vocabulary selection under step processors on given logits, for the parity tests: logits device fp32
+ * [rows, ldl] row-major, or (logits_f16_tm) fp16 in the tile-major layout with K = ldl; tile_max / tile_sum device fp32
+ * [ldl / 256][rows] (per 256-column tile: maximum and sum of exp(v - maximum)); hist device int32 [rows, hist_stride], row r's
+ * sequence so far hist[r][0 .. hist_len); pad_idx (-1 = none) is never a candidate.  Outputs (device): pval fp32 / pidx
+ * int32 [rows, 16], the first k2 (<= 16) entries = the top-k2 of the masked row (value desc, token asc; -inf / INT32_MAX
+ * when fewer remain), and pmax / psum fp32 [rows], the untouched row's softmax normaliser.  With no processor active the
+ * engine's default selection runs, as in smi_text_decoder_generate. */
+int smi_vocab_select_banned(const void* logits, int32_t ldl, int32_t logits_f16_tm, int32_t rows, int32_t vocab,
+                            const float* tile_max, const float* tile_sum, int32_t k2, int32_t pad_idx,
+                            const int32_t* hist, int32_t hist_stride, int32_t hist_len, const smi_step_processors* procs,
+                            float* pval, int32_t* pidx, float* pmax, float* psum, void* stream);
+
+/* smi_sample_rows under step processors, for the parity tests: every row's sequence so far is hist (device int32
+ * [hist_len]), and the ids the processors ban get mass 0 in the filter and the draw.  When the kept set's Q40 mass is 0 (a
+ * banned token holds the row maximum far above every kept one) the most probable kept token is returned, lowest id on a tie,
+ * with its exact log-probability. */
+int smi_sample_rows_banned(const float* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t sampler, int32_t top_k,
+                           float top_p, float temperature, int32_t pad_idx, int32_t eos_idx, int32_t block_eos,
+                           int32_t unk_idx, float unk_penalty, const int32_t* hist, int32_t hist_len,
+                           const smi_step_processors* procs, const uint64_t* z, int32_t* out_token, float* out_logprob,
+                           uint64_t* out_kept_mass, int32_t* out_kept_count, void* stream);
 
 /* Sampling generation (sonar/inference_pipelines/text.py:315-320: a `sampler` makes predict() build
  * fairseq2's SamplingSeq2SeqGenerator instead of the beam search; one hypothesis per sentence).

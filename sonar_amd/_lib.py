@@ -10,7 +10,7 @@ import contextlib
 import ctypes as C
 import os
 from pathlib import Path
-from typing import Optional
+from typing import Optional, Tuple
 
 # SMI_LIB: development override -- load a variant build of the library (tools/README.md) instead of the in-tree one
 LIB_PATH = Path(os.environ["SMI_LIB"]).resolve() if os.environ.get("SMI_LIB") else \
@@ -187,6 +187,28 @@ class smi_sampling_params(C.Structure):
     ]
 
 
+class smi_step_processors(C.Structure):
+    _fields_ = [
+        ("ngram_size", C.c_int32),
+        ("num_banned", C.c_int32),
+        ("banned_tokens", C.POINTER(C.c_int32)),
+        ("banned_offsets", C.POINTER(C.c_int32)),
+    ]
+
+
+def step_processors_struct(ngram_size: int, banned_seqs) -> Tuple["smi_step_processors", list]:
+    """-> (smi_step_processors, keep-alive list of its host arrays) for an n-gram size (0 = off) and banned sequences."""
+    seqs = [list(map(int, b)) for b in banned_seqs]
+    flat = [t for b in seqs for t in b]
+    offs = [0]
+    for b in seqs:
+        offs.append(offs[-1] + len(b))
+    toks = (C.c_int32 * max(len(flat), 1))(*flat)
+    offa = (C.c_int32 * len(offs))(*offs)
+    return smi_step_processors(ngram_size=int(ngram_size), num_banned=len(seqs), banned_tokens=toks,
+                               banned_offsets=offa), [toks, offa]
+
+
 class smi_speech_encoder_config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in (
         "model_dim", "num_layers", "num_heads", "ffn_inner_dim", "conv_kernel", "num_mel_bins",
@@ -235,7 +257,7 @@ class smi_mlp_head_layer(C.Structure):
     _fields_ = [("w", smi_tensor), ("b", smi_tensor), ("out_dim", C.c_int32), ("reserved", C.c_int32)]
 
 
-ABI_VERSION = 6  # SMI_ABI_VERSION of include/sonar_mi355.h
+ABI_VERSION = 7  # SMI_ABI_VERSION of include/sonar_mi355.h
 
 # every symbol include/sonar_mi355.h declares: name -> (restype, argtypes)
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
@@ -268,6 +290,11 @@ SYMBOLS = {
     "smi_text_decoder_set_chains": (C.c_int, [_vp, _i32]),
     "smi_text_decoder_set_beam_logits_dtype": (C.c_int, [_vp, _i32]),
     "smi_text_decoder_set_slab_dtype": (C.c_int, [_vp, _i32]),
+    "smi_text_decoder_set_step_processors": (C.c_int, [_vp, C.POINTER(smi_step_processors)]),
+    "smi_vocab_select_banned": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _i32, _i32,
+                                          C.POINTER(smi_step_processors), _vp, _vp, _vp, _vp, _vp]),
+    "smi_sample_rows_banned": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _i32, _i32, _f32,
+                                         _vp, _i32, C.POINTER(smi_step_processors), _vp, _vp, _vp, _vp, _vp, _vp]),
     "smi_text_decoder_sample": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), _i32,
                                           C.POINTER(smi_sampling_params), _vp, _vp, _vp, _vp]),
     "smi_sample_rows": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _i32, _i32, _f32, _vp,

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "step_proc.hpp"
 
 namespace smi {
 
@@ -507,20 +508,17 @@ __device__ __forceinline__ float logit_at(const float* __restrict__ logits, int 
   return f16_tm ? (float)((const f16*)logits)[tm_offset(row, tok, ldl)] : logits[(size_t)row * ldl + tok];
 }
 
-__global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restrict__ logits, int ldl, int f16_tm, int vocab,
-                                                           const float* __restrict__ tile_max,
-                                                           const float* __restrict__ tile_sum, int ntiles,
-                                                           int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx, int unk_idx,
-                                                           float unk_penalty, int block_eos,
-                                                           float* __restrict__ pmax, float* __restrict__ psum,
-                                                           float* __restrict__ pval, int* __restrict__ pidx) {
-  __shared__ float s_f[4];
-  __shared__ int s_sel[VSEL_SLOTS];
+constexpr int VSEL_TPT = 8;  // tiles per thread: up to 2048 tiles = 524288 tokens
+
+// step 1 of the selection: the row's softmax normaliser (pmax, psum) from its tile statistics; m[] = the thread's tile maxima
+__device__ __forceinline__ void vsel_normaliser(const float* __restrict__ tile_max, const float* __restrict__ tile_sum,
+                                                int ntiles, int stat_rows, float* __restrict__ pmax,
+                                                float* __restrict__ psum, float (&m)[VSEL_TPT], float* s_f) {
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const float* tm = tile_max + row;  // [tile][stat_rows]
   const float* ts = tile_sum + row;
-  constexpr int TPT = 8;  // tiles per thread: up to 2048 tiles = 524288 tokens
-  float m[TPT], sm[TPT];
+  constexpr int TPT = VSEL_TPT;
+  float sm[TPT];
   float lm = -INFINITY;
 #pragma unroll
   for (int j = 0; j < TPT; ++j) {
@@ -546,6 +544,21 @@ __global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restri
     pmax[row] = M;
     psum[row] = (s_f[0] + s_f[1]) + (s_f[2] + s_f[3]);
   }
+}
+
+__global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restrict__ logits, int ldl, int f16_tm, int vocab,
+                                                           const float* __restrict__ tile_max,
+                                                           const float* __restrict__ tile_sum, int ntiles,
+                                                           int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx, int unk_idx,
+                                                           float unk_penalty, int block_eos,
+                                                           float* __restrict__ pmax, float* __restrict__ psum,
+                                                           float* __restrict__ pval, int* __restrict__ pidx) {
+  __shared__ float s_f[4];
+  __shared__ int s_sel[VSEL_SLOTS];
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  constexpr int TPT = VSEL_TPT;
+  float m[TPT];
+  vsel_normaliser(tile_max, tile_sum, ntiles, stat_rows, pmax, psum, m, s_f);
   if (k2 == 0) return;
   // The two selections below are k2 rounds of "workgroup-wide maximum of a sortable key, then retire the winner".  The kernel is
   // VALU-bound (1280 rows x 4 waves on 1024 SIMDs: a round used to rebuild and compare the keys of all of a thread's slots,
@@ -628,6 +641,189 @@ __global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restri
       }
     }
   }
+}
+
+// ------------------------------------------------- vocabulary select under step processors (bans)
+// As vocab_select_kernel, with the ids the row's step processors ban (step_proc.hpp) removed from the candidates; pmax /
+// psum stay those of the untouched row (a ban is -inf AFTER log_softmax).  A banned id is usually its tile's maximum, so
+// the tile argument changes: a tile holding a banned id ("dirty") says nothing through its raw maximum.  The candidates are
+//   tile 0, the k2 best CLEAN tiles >= 1 (value desc, tile asc), and every dirty tile >= 1 whose raw maximum is >= the
+//   k2-th of those (every dirty tile when fewer than k2 clean tiles exist);
+// each of the k2 clean tiles holds an unbanned element >= that maximum which wins every value tie against a later tile, and
+// a dirty tile below it holds nothing that can reach the top-k2.  Their number is not bounded, so the tiles are read in
+// groups of VSEL_SLOTS, each group merged with the running top-k2 (an LDS list, one more slot per thread) by k2 rounds of
+// the workgroup-wide arg-max; banned columns are skipped through a per-group 256-bit mask per tile.
+constexpr int VSB_MAX_BANS = kStepProcMaxLen + kStepProcMaxBanned;
+
+__global__ __launch_bounds__(256) void vocab_select_banned_kernel(
+    const float* __restrict__ logits, int ldl, int f16_tm, int vocab, const float* __restrict__ tile_max,
+    const float* __restrict__ tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx,
+    int unk_idx, float unk_penalty, int block_eos, const int32_t* __restrict__ hist, int hist_stride, int hist_len,
+    StepProcDev proc, float* __restrict__ pmax, float* __restrict__ psum, float* __restrict__ pval, int* __restrict__ pidx) {
+  __shared__ float s_f[4];
+  __shared__ int32_t s_seq[kStepProcMaxLen];
+  __shared__ int32_t s_ban[VSB_MAX_BANS];
+  __shared__ uint32_t s_dirty[2048 / 32];
+  __shared__ int s_tiles[2048];              // candidate tiles: [0] tile 0, [1, nsel) the clean ones, then the dirty ones
+  __shared__ short s_slot[2048];             // tile -> slot in the current group, -1 elsewhere
+  __shared__ uint32_t s_mask[VSEL_SLOTS][8]; // banned columns of the group's tiles
+  __shared__ unsigned long long s_top[VS_K2MAX];
+  __shared__ unsigned long long s_k2[2][4];
+  __shared__ int s_nban, s_ndirty;
+  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  constexpr int TPT = VSEL_TPT;
+  float m[TPT];
+  vsel_normaliser(tile_max, tile_sum, ntiles, stat_rows, pmax, psum, m, s_f);
+  if (k2 == 0) return;
+  // ---- B0. the row's sequence into LDS, empty ban list / dirty bitmap / slot map
+  const int32_t* h = hist + (size_t)row * hist_stride;
+  for (int i = tid; i < hist_len; i += 256) s_seq[i] = h[i];
+  if (tid < 2048 / 32) s_dirty[tid] = 0u;
+  for (int t = tid; t < 2048; t += 256) s_slot[t] = -1;
+  if (tid < VS_K2MAX) s_top[tid] = 0ull;
+  if (tid == 0) {
+    s_nban = 0;
+    s_ndirty = 0;
+  }
+  __syncthreads();
+  // ---- B1. banned ids and dirty tiles
+  step_proc_bans(proc, s_seq, hist_len, tid, 256, [&](int tok) {
+    if (tok < 0 || tok >= vocab) return;
+    const int k = atomicAdd(&s_nban, 1);
+    if (k < VSB_MAX_BANS) s_ban[k] = tok;
+    atomicOr(&s_dirty[tok >> 13], 1u << ((tok >> 8) & 31));
+  });
+  __syncthreads();
+  const int nban = min(s_nban, VSB_MAX_BANS);
+  auto dirty = [&](int t) { return (s_dirty[t >> 5] >> (t & 31)) & 1u; };
+  int rr = 0;  // running round: the wave results alternate between the two halves of s_k2
+  auto wg_max = [&](unsigned long long mine) {
+    const unsigned long long w = wave_max_u64(mine);
+    if (lane == 0) s_k2[rr & 1][wv] = w;
+    __syncthreads();
+    unsigned long long b = s_k2[rr & 1][0];
+#pragma unroll
+    for (int q = 1; q < 4; ++q) b = s_k2[rr & 1][q] > b ? s_k2[rr & 1][q] : b;
+    ++rr;
+    return b;
+  };
+  // ---- B2. the k2 best clean tiles >= 1, and the k2-th one's maximum
+  unsigned long long tk[TPT];
+  unsigned long long tbest = 0ull, last = 0ull;
+#pragma unroll
+  for (int j = 0; j < TPT; ++j) {
+    const int t = tid + 256 * j;
+    tk[j] = (m[j] != -INFINITY && t != 0 && !dirty(t)) ? cand_key(m[j], t) : 0ull;
+    tbest = tk[j] > tbest ? tk[j] : tbest;
+  }
+  if (tid == 0) s_tiles[0] = 0;
+  int nsel = 1;
+  for (int round = 0; round < k2; ++round) {
+    const unsigned long long b = wg_max(tbest);
+    if (b == 0ull) break;  // fewer than k2 clean tiles
+    if (tid == 0) s_tiles[nsel] = (int)(0xffffffffu - (unsigned)(b & 0xffffffffu));
+    ++nsel;
+    last = b;
+    if (b == tbest) {
+      tbest = 0ull;
+#pragma unroll
+      for (int j = 0; j < TPT; ++j) {
+        if (tk[j] == b) tk[j] = 0ull;
+        tbest = tk[j] > tbest ? tk[j] : tbest;
+      }
+    }
+  }
+  // ---- B3. the dirty tiles that can hold a candidate
+  const bool all_dirty = nsel - 1 < k2;
+  float thr = -INFINITY;
+  if (!all_dirty) {  // invert cand_key's value half
+    unsigned u = (unsigned)(last >> 32);
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    thr = __uint_as_float(u);
+  }
+#pragma unroll
+  for (int j = 0; j < TPT; ++j) {
+    const int t = tid + 256 * j;
+    if (t != 0 && t < ntiles && m[j] != -INFINITY && dirty(t) && (all_dirty || m[j] >= thr))
+      s_tiles[nsel + atomicAdd(&s_ndirty, 1)] = t;
+  }
+  __syncthreads();
+  const int ncand = nsel + s_ndirty;
+  // ---- B4. groups of VSEL_SLOTS tiles, each merged with the running top-k2
+  for (int g0 = 0; g0 < ncand; g0 += VSEL_SLOTS) {
+    const int gn = min(VSEL_SLOTS, ncand - g0);
+    if (tid < VSEL_SLOTS * 8) s_mask[tid >> 3][tid & 7] = 0u;
+    if (tid < gn) s_slot[s_tiles[g0 + tid]] = (short)tid;
+    __syncthreads();
+    for (int k = tid; k < nban; k += 256) {
+      const int b = s_ban[k], sl = s_slot[b >> 8];
+      if (sl >= 0) atomicOr(&s_mask[sl][(b & 255) >> 5], 1u << (b & 31));
+    }
+    __syncthreads();
+    unsigned long long ck[VSEL_SLOTS + 1];
+    unsigned long long cbest = 0ull;
+#pragma unroll
+    for (int j = 0; j < VSEL_SLOTS; ++j) {
+      ck[j] = 0ull;
+      if (j < gn) {
+        const int tok = s_tiles[g0 + j] * 256 + tid;
+        const bool banned = (s_mask[j][tid >> 5] >> (tid & 31)) & 1u;
+        if (tok < vocab && !banned && tok != pad_idx && !(block_eos && tok == eos_idx)) {
+          float v = logit_at(logits, ldl, f16_tm, row, tok) * inv_temp;
+          if (tok == unk_idx) v -= unk_penalty;
+          if (v != -INFINITY) ck[j] = cand_key(v, tok);
+        }
+      }
+      cbest = ck[j] > cbest ? ck[j] : cbest;
+    }
+    ck[VSEL_SLOTS] = tid < k2 ? s_top[tid] : 0ull;  // the running list takes part as one more slot
+    cbest = ck[VSEL_SLOTS] > cbest ? ck[VSEL_SLOTS] : cbest;
+    __syncthreads();  // every s_top read before the rounds rewrite it
+    for (int round = 0; round < k2; ++round) {
+      const unsigned long long b = wg_max(cbest);
+      if (tid == 0) s_top[round] = b;
+      if (b != 0ull && b == cbest) {  // keys are unique (the token is part of them): exactly one thread
+        cbest = 0ull;
+#pragma unroll
+        for (int j = 0; j <= VSEL_SLOTS; ++j) {
+          if (ck[j] == b) ck[j] = 0ull;
+          cbest = ck[j] > cbest ? ck[j] : cbest;
+        }
+      }
+    }
+    if (tid < gn) s_slot[s_tiles[g0 + tid]] = -1;
+    __syncthreads();
+  }
+  // ---- B5. the ordered list
+  if (tid < k2) {
+    const unsigned long long b = s_top[tid];
+    float val = -INFINITY;
+    int idx = 0x7fffffff;
+    if (b != 0ull) {
+      unsigned u = (unsigned)(b >> 32);
+      u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+      val = __uint_as_float(u);
+      idx = (int)(0xffffffffu - (unsigned)(b & 0xffffffffu));
+    }
+    pval[(size_t)row * VS_K2MAX + tid] = val;
+    pidx[(size_t)row * VS_K2MAX + tid] = idx;
+  }
+}
+
+hipError_t launch_vocab_select_banned(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
+                                      const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx,
+                                      int eos_idx, int unk_idx, float unk_penalty, int block_eos, const int32_t* hist,
+                                      int hist_stride, int hist_len, const StepProcDev& proc, float* pmax, float* psum,
+                                      float* pval, int* pidx, hipStream_t stream) {
+  if (rows <= 0 || stat_rows < rows || ntiles <= 0 || ntiles > 2048 || k2 < 0 || k2 > VS_K2MAX || (int64_t)ntiles * 256 < vocab)
+    return hipErrorInvalidValue;
+  if (!hist || hist_len < 1 || hist_len > kStepProcMaxLen || hist_stride < hist_len || proc.num_banned < 0 ||
+      proc.num_banned > kStepProcMaxBanned || (proc.num_banned > 0 && (!proc.tokens || !proc.offsets)))
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(vocab_select_banned_kernel, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
+                     tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, hist,
+                     hist_stride, hist_len, proc, pmax, psum, pval, pidx);
+  return hipGetLastError();
 }
 
 hipError_t launch_vocab_select(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,

@@ -51,10 +51,12 @@ struct DecWork {
   DevBuf anc[2], hist[2];
   DevBuf pmax, psum, pval, pidx;
   DevBuf tile_max, tile_sum;  // logits-GEMM tile statistics [rows_pad][vocab_pad / 256]
+  DevBuf prompt_dev;          // sampling under step processors: the prompt, int32
   int kv_positions = 0;       // positions per layer in the current kv allocation
   bool chained = false;       // this call runs next to other chains: per-launch tile choices differ (decoder_step)
   hipStream_t stream = nullptr;  // chains of a split call run on streams of their own
   hipEvent_t done_ev = nullptr;
+  hipEvent_t sp_ev = nullptr;    // end of this workspace's last call that read the step-processor table
 };
 
 constexpr int kMaxChains = 4;
@@ -72,6 +74,12 @@ struct smi_text_decoder {
   int chains = 0;       // smi_text_decoder_set_chains: 0 = SMI_DEC_CHAINS / the default
   int beam_logits_f16 = 0;  // smi_text_decoder_set_beam_logits_dtype: the beam search's logits are stored in fp16
   int beam_slab_f16 = 0;    // smi_text_decoder_set_slab_dtype: the beam search's split-K partial sums are stored in fp16
+  // smi_text_decoder_set_step_processors: n-gram size (0 = off) and the banned sequences (device CSR, read by every chain)
+  int sp_ngram = 0, sp_num_banned = 0;
+  DevBuf sp_tokens, sp_offsets;
+  StepProcDev step_proc() const {
+    return StepProcDev{sp_ngram, sp_num_banned, sp_tokens.as<int32_t>(), sp_offsets.as<int32_t>()};
+  }
   int64_t weight_bytes = 0;
   int ffn_tile_major = 0;  // FFN weights stored tile-major (d, f multiples of 256)
   // Generic-dimension mode (flex.hip): head_dim != 64 or dimensions the MFMA engines do not tile for (the reference's
@@ -83,6 +91,7 @@ struct smi_text_decoder {
     for (auto& w : ws) {
       if (w.stream) (void)hipStreamDestroy(w.stream);
       if (w.done_ev) (void)hipEventDestroy(w.done_ev);
+      if (w.sp_ev) (void)hipEventDestroy(w.sp_ev);
     }
     if (fork_ev) (void)hipEventDestroy(fork_ev);
   }
@@ -349,6 +358,13 @@ int decode_chains(const smi_text_decoder* D, int n, int beam) {
   return std::max(g, 1);
 }
 
+// the step-processor table is read by the work queued so far on `stream` (smi_text_decoder_set_step_processors waits for it)
+int record_table_use(DecWork& S, hipStream_t stream) {
+  if (!S.sp_ev) HIP_TRY(hipEventCreateWithFlags(&S.sp_ev, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(S.sp_ev, stream));
+  return SMI_OK;
+}
+
 // One decode chain: beam search for the n sentences of `emb` on workspace S and stream `stream` (the whole call, or
 // one sentence group of a split call).  margins: device [n][2].
 int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dtype, int n, const int64_t* prompt,
@@ -398,6 +414,7 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
   const int logits_f16 = !D->flex && D->embed_tm.p != nullptr && (lf_env >= 0 ? lf_env != 0 : D->beam_logits_f16 != 0);
   const int sf_env = tune(TUNE_DEC_SLAB_F16, -1);
   const int slab_f16 = !D->flex && (sf_env >= 0 ? sf_env != 0 : D->beam_slab_f16 != 0);
+  const StepProcDev proc = D->step_proc();
 
   // everything one decode step enqueues (position pos; ancestry/history buffer pos & 1)
   auto enqueue_step = [&](int pos, hipStream_t s) -> int {
@@ -409,11 +426,19 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     const bool force_eos = !forced_prompt && step_nr == max_len - 1;
     // forced steps need only the softmax normaliser (the candidate is a given token): k2 = 0
     const bool free_step = !forced_prompt && !force_eos;
-    HIP_TRY(launch_vocab_select(S.logits.as<float>(), (int)D->vocab_pad, logits_f16, rows, (int)c.vocab_size,
-                                S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, rows_pad, free_step ? k2 : 0, inv_temp,
-                                c.pad_idx, c.eos_idx, c.unk_idx, free_step ? bp->unk_penalty : 0.f,
-                                free_step && step_nr < min_len ? 1 : 0, S.pmax.as<float>(), S.psum.as<float>(),
-                                S.pval.as<float>(), S.pidx.as<int>(), s));
+    // step processors act on the free steps only, on the row's sequence so far hist[cur][r][0 .. pos]
+    if (free_step && proc.active())
+      HIP_TRY(launch_vocab_select_banned(S.logits.as<float>(), (int)D->vocab_pad, logits_f16, rows, (int)c.vocab_size,
+                                         S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, rows_pad, k2, inv_temp,
+                                         c.pad_idx, c.eos_idx, c.unk_idx, bp->unk_penalty, step_nr < min_len ? 1 : 0,
+                                         S.hist[cur].as<int32_t>(), stride, pos + 1, proc, S.pmax.as<float>(),
+                                         S.psum.as<float>(), S.pval.as<float>(), S.pidx.as<int>(), s));
+    else
+      HIP_TRY(launch_vocab_select(S.logits.as<float>(), (int)D->vocab_pad, logits_f16, rows, (int)c.vocab_size,
+                                  S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, rows_pad, free_step ? k2 : 0, inv_temp,
+                                  c.pad_idx, c.eos_idx, c.unk_idx, free_step ? bp->unk_penalty : 0.f,
+                                  free_step && step_nr < min_len ? 1 : 0, S.pmax.as<float>(), S.psum.as<float>(),
+                                  S.pval.as<float>(), S.pidx.as<int>(), s));
     BeamStepArgs a{};
     a.tok = S.tok.as<int32_t>(); a.cum = S.cum.as<float>(); a.nactive = S.nactive.as<int32_t>();
     a.done = S.done.as<int32_t>(); a.ndone = S.ndone.as<int32_t>();
@@ -456,6 +481,8 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
   HIP_TRY(launch_beam_output(S.fin_tok.as<int32_t>(), S.fin_len.as<int32_t>(), S.fin_score.as<float>(),
                              S.fin_count.as<int32_t>(), n, beam, stride, max_len, out_tokens, out_lens, out_scores,
                              margins, stream));
+  if (proc.active())
+    if (int rc = record_table_use(S, stream)) return rc;
   return SMI_OK;
 }
 
@@ -750,6 +777,13 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
     HIP_TRY(hipMemcpyAsync(S.tok.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
   }
+  const StepProcDev proc = D->step_proc();
+  if (proc.active()) {  // the bans read the prompt on the device
+    std::vector<int32_t> p32(prompt, prompt + prompt_len);
+    HIP_TRY(S.prompt_dev.reserve((size_t)prompt_len * 4));
+    HIP_TRY(hipMemcpyAsync(S.prompt_dev.p, p32.data(), p32.size() * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+  }
   HIP_TRY(hipMemsetAsync(S.cum.p, 0, (size_t)n * 4, stream));
   HIP_TRY(hipMemsetAsync(S.done.p, 0, (size_t)n * 4, stream));
   HIP_TRY(hipMemsetAsync(S.ndone.p, 0, 4, stream));
@@ -773,6 +807,9 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
     a.forced_tok = forced_prompt ? (int)prompt[step_nr] : (force_eos ? c.eos_idx : -1);
     a.mode = sp->sampler; a.top_k = sp->top_k; a.top_p = sp->top_p; a.z = nullptr; a.seed = sp->seed; a.step = step_nr;
     a.done = S.done.as<int32_t>(); a.out_tok = S.new_tok.as<int32_t>(); a.out_logp = S.new_cum.as<float>();
+    if (a.forced_tok < 0 && proc.active()) {
+      a.proc = proc; a.prompt = S.prompt_dev.as<int32_t>(); a.prompt_len = prompt_len; a.gen = out_tokens; a.gen_stride = max_len;
+    }
     HIP_TRY(launch_sample_rows(a, stream));
     SampleUpdateArgs u{};
     u.samp_tok = S.new_tok.as<int32_t>(); u.samp_logp = S.new_cum.as<float>(); u.tok = S.tok.as<int32_t>();
@@ -788,6 +825,137 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
       if (nd >= n) break;
     }
   }
+  if (proc.active())
+    if (int rc = record_table_use(S, stream)) return rc;
+  return SMI_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// smi_step_processors -> checked host CSR (SMI_OK) or an error
+int check_step_processors(const smi_step_processors* p, int64_t vocab, int max_seq_len) {
+  if (p->ngram_size < 0 || p->ngram_size > max_seq_len)
+    return fail(SMI_ERR_INVALID_ARG, "ngram_size %d outside [0, max_seq_len %d]", p->ngram_size, max_seq_len);
+  if (p->num_banned < 0 || p->num_banned > kStepProcMaxBanned)
+    return fail(SMI_ERR_INVALID_ARG, "num_banned %d outside [0, %d]", p->num_banned, kStepProcMaxBanned);
+  if (p->num_banned == 0) return SMI_OK;
+  if (!p->banned_tokens || !p->banned_offsets) return fail(SMI_ERR_INVALID_ARG, "null banned_tokens / banned_offsets");
+  if (p->banned_offsets[0] != 0) return fail(SMI_ERR_INVALID_ARG, "banned_offsets[0] must be 0");
+  for (int q = 0; q < p->num_banned; ++q) {
+    const int len = p->banned_offsets[q + 1] - p->banned_offsets[q];
+    if (len < 1) return fail(SMI_ERR_INVALID_ARG, "banned sequence %d is empty", q);
+    if (len > max_seq_len) return fail(SMI_ERR_INVALID_ARG, "banned sequence %d is longer than max_seq_len %d", q, max_seq_len);
+  }
+  for (int i = 0; i < p->banned_offsets[p->num_banned]; ++i)
+    if (p->banned_tokens[i] < 0 || p->banned_tokens[i] >= vocab)
+      return fail(SMI_ERR_INVALID_ARG, "banned token %d outside the vocabulary [0, %lld)", p->banned_tokens[i], (long long)vocab);
+  return SMI_OK;
+}
+
+int upload_i32(DevBuf& dst, const int32_t* src, size_t count) {
+  HIP_TRY(dst.reserve(count * 4));
+  HIP_TRY(hipMemcpy(dst.p, src, count * 4, hipMemcpyHostToDevice));
+  return SMI_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int smi_text_decoder_set_step_processors(smi_text_decoder* D, const smi_step_processors* procs) {
+  if (!D) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (!procs || (procs->ngram_size == 0 && procs->num_banned == 0)) {
+    D->sp_ngram = D->sp_num_banned = 0;
+    return SMI_OK;
+  }
+  if (D->cfg.max_seq_len >= kStepProcMaxLen)
+    return fail(SMI_ERR_UNSUPPORTED, "step processors cover max_seq_len up to %d", kStepProcMaxLen - 1);
+  if (int rc = check_step_processors(procs, D->cfg.vocab_size, D->cfg.max_seq_len)) return rc;
+  // stage the new table in buffers of its own: a failed upload leaves the handle's setting as it was
+  DevBuf tok, off;
+  if (procs->num_banned > 0) {
+    if (int rc = upload_i32(off, procs->banned_offsets, (size_t)procs->num_banned + 1)) return rc;
+    if (int rc = upload_i32(tok, procs->banned_tokens, (size_t)procs->banned_offsets[procs->num_banned])) return rc;
+  }
+  // the handle's earlier calls may still read the old table: wait for them (not for the rest of the device)
+  for (auto& w : D->ws)
+    if (w.sp_ev) HIP_TRY(hipEventSynchronize(w.sp_ev));
+  D->sp_offsets = std::move(off);
+  D->sp_tokens = std::move(tok);
+  D->sp_ngram = procs->ngram_size;
+  D->sp_num_banned = procs->num_banned;
+  return SMI_OK;
+}
+
+int smi_vocab_select_banned(const void* logits, int32_t ldl, int32_t logits_f16_tm, int32_t rows, int32_t vocab,
+                            const float* tile_max, const float* tile_sum, int32_t k2, int32_t pad_idx,
+                            const int32_t* hist, int32_t hist_stride, int32_t hist_len, const smi_step_processors* procs,
+                            float* pval, int32_t* pidx, float* pmax, float* psum, void* stream) {
+  if (!logits || !tile_max || !tile_sum || !hist || !procs || !pval || !pidx || !pmax || !psum)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (rows <= 0 || vocab <= 0 || ldl % 256 || ldl < vocab || ldl / 256 > 2048)
+    return fail(SMI_ERR_INVALID_ARG, "ldl %d must be a multiple of 256 >= vocab %d, at most 2048 tiles", ldl, vocab);
+  if (k2 < 1 || k2 > kVocabScanK2Max) return fail(SMI_ERR_INVALID_ARG, "k2 %d outside [1, %d]", k2, kVocabScanK2Max);
+  if (hist_len < 1 || hist_len > kStepProcMaxLen - 1 || hist_stride < hist_len)
+    return fail(SMI_ERR_INVALID_ARG, "hist_len %d outside [1, %d] or above hist_stride %d", hist_len, kStepProcMaxLen - 1,
+                hist_stride);
+  if (logits_f16_tm && rows % 256) return fail(SMI_ERR_INVALID_ARG, "tile-major logits need rows padded to 256");
+  if (int rc = check_step_processors(procs, vocab, kStepProcMaxLen - 1)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  DevBuf tok, off;
+  if (procs->num_banned > 0) {
+    if (int rc = upload_i32(off, procs->banned_offsets, (size_t)procs->num_banned + 1)) return rc;
+    if (int rc = upload_i32(tok, procs->banned_tokens, (size_t)procs->banned_offsets[procs->num_banned])) return rc;
+  }
+  const StepProcDev proc{procs->ngram_size, procs->num_banned, tok.as<int32_t>(), off.as<int32_t>()};
+  if (!proc.active())  // no processor: the engine's default selection, as generate() runs it
+    HIP_TRY(launch_vocab_select((const float*)logits, ldl, logits_f16_tm, rows, vocab, tile_max, tile_sum, ldl / 256, rows, k2,
+                                1.0f, pad_idx, -1, -1, 0.f, 0, pmax, psum, pval, pidx, (hipStream_t)stream));
+  else HIP_TRY(launch_vocab_select_banned((const float*)logits, ldl, logits_f16_tm, rows, vocab, tile_max, tile_sum, ldl / 256,
+                                     rows, k2, 1.0f, pad_idx, -1, -1, 0.f, 0, hist, hist_stride, hist_len, proc, pmax, psum,
+                                     pval, pidx, (hipStream_t)stream));
+  // the CSR copies are freed on return: finish with them first
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_sample_rows_banned(const float* logits, int64_t ld, int32_t rows, int32_t vocab, int32_t sampler, int32_t top_k,
+                           float top_p, float temperature, int32_t pad_idx, int32_t eos_idx, int32_t block_eos,
+                           int32_t unk_idx, float unk_penalty, const int32_t* hist, int32_t hist_len,
+                           const smi_step_processors* procs, const uint64_t* z, int32_t* out_token, float* out_logprob,
+                           uint64_t* out_kept_mass, int32_t* out_kept_count, void* stream) {
+  if (!logits || !hist || !procs || !z || !out_token || !out_logprob) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (rows <= 0 || vocab <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (vocab > (1 << 18)) return fail(SMI_ERR_UNSUPPORTED, "vocab %d: sampling covers up to 2^18 tokens", vocab);
+  if (ld % 4 || ld < (vocab + 3) / 4 * 4) return fail(SMI_ERR_INVALID_ARG, "ld %lld must be a multiple of 4 >= vocab", (long long)ld);
+  if (!(temperature > 0.f)) return fail(SMI_ERR_INVALID_ARG, "temperature must be positive");
+  if (sampler == SMI_SAMPLER_TOP_K) {
+    if (top_k < 1) return fail(SMI_ERR_INVALID_ARG, "top_k must be >= 1");
+  } else if (sampler == SMI_SAMPLER_TOP_P) {
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SMI_ERR_INVALID_ARG, "top_p must be in (0, 1]");
+  } else {
+    return fail(SMI_ERR_INVALID_ARG, "unknown sampler %d", sampler);
+  }
+  if (hist_len < 1 || hist_len > kStepProcMaxLen - 1) return fail(SMI_ERR_INVALID_ARG, "hist_len %d outside [1, %d]", hist_len, kStepProcMaxLen - 1);
+  if (int rc = check_step_processors(procs, vocab, kStepProcMaxLen - 1)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  DevBuf tok, off;
+  if (procs->num_banned > 0) {
+    if (int rc = upload_i32(off, procs->banned_offsets, (size_t)procs->num_banned + 1)) return rc;
+    if (int rc = upload_i32(tok, procs->banned_tokens, (size_t)procs->banned_offsets[procs->num_banned])) return rc;
+  }
+  SampleRowsArgs a{};
+  a.logits = logits; a.ld = ld; a.rows = rows; a.vocab = vocab; a.inv_temp = 1.0f / temperature;
+  a.pad_idx = pad_idx; a.eos_idx = eos_idx; a.block_eos = block_eos; a.forced_tok = -1;
+  a.unk_idx = unk_idx; a.unk_penalty = unk_penalty;
+  a.mode = sampler; a.top_k = top_k; a.top_p = top_p; a.z = (const unsigned long long*)z;
+  a.out_tok = out_token; a.out_logp = out_logprob; a.out_kept_mass = (unsigned long long*)out_kept_mass;
+  a.out_kept_count = out_kept_count;
+  // every row's sequence so far is hist[0 .. hist_len): a prompt with nothing generated yet
+  a.proc = StepProcDev{procs->ngram_size, procs->num_banned, tok.as<int32_t>(), off.as<int32_t>()};
+  a.prompt = hist; a.prompt_len = hist_len; a.gen = hist; a.gen_stride = 0; a.step = hist_len;
+  HIP_TRY(launch_sample_rows(a, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the CSR copies are freed on return
   return SMI_OK;
 }
 

@@ -206,6 +206,24 @@ hipError_t launch_vocab_select(const float* logits, int ldl, int f16_tm, int row
                                const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx,
                                int unk_idx, float unk_penalty, int block_eos, float* pmax, float* psum, float* pval,
                                int* pidx, hipStream_t stream);
+// Step processors (smi_step_processors, device copy): n-gram repeat blocking and banned sequences, CSR on the device
+struct StepProcDev {
+  int ngram;              // 0 = off
+  int num_banned;         // banned sequences
+  const int32_t* tokens;  // [offsets[num_banned]]
+  const int32_t* offsets; // [num_banned + 1]
+  bool active() const { return ngram > 0 || num_banned > 0; }
+};
+constexpr int kStepProcMaxLen = 1024;     // longest sequence a processor reads (LDS copy of it)
+constexpr int kStepProcMaxBanned = 1024;  // banned sequences per handle
+// launch_vocab_select with the bans of `proc` applied to the candidates (not to pmax / psum): row r's sequence so far is
+// hist[r][0 .. hist_len) (stride hist_stride).  The candidates are tile 0, the k2 best tiles without a banned id and every
+// tile with one whose maximum reaches the k2-th of those; the result is the top-k2 of the masked row.
+hipError_t launch_vocab_select_banned(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
+                                      const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx,
+                                      int eos_idx, int unk_idx, float unk_penalty, int block_eos, const int32_t* hist,
+                                      int hist_stride, int hist_len, const StepProcDev& proc, float* pmax, float* psum,
+                                      float* pval, int* pidx, hipStream_t stream);
 struct BeamStepArgs {
   int32_t* tok; float* cum; int32_t* nactive; int32_t* done; int32_t* ndone;
   int32_t* parent; int32_t* new_tok; float* new_cum;
@@ -285,6 +303,12 @@ struct SampleRowsArgs {
   float* out_logp;
   unsigned long long* out_kept_mass;    // optional
   int32_t* out_kept_count;
+  // step processors (proc.active()): row r's sequence so far is prompt[0 .. prompt_len) + gen[r][0 .. step - prompt_len)
+  StepProcDev proc;
+  const int32_t* prompt;  // device
+  int prompt_len;
+  const int32_t* gen;     // [rows][gen_stride]
+  int gen_stride;
 };
 
 struct SampleUpdateArgs {

@@ -17,6 +17,7 @@
 #include "api_common.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
+#include "step_proc.hpp"
 
 using namespace smi;
 using namespace smi_host;
@@ -84,7 +85,12 @@ __device__ __forceinline__ u64 smp_hash(u64 seed, int row, int step) {
   return z ^ (z >> 31);
 }
 
+// BAN: the row's step processors (step_proc.hpp) give the ids of this step mass 0 (an LDS bitmap over the vocabulary) in every
+// histogram pass and in the draw; Z stays the untouched distribution's, as with the UNK penalty
+template <bool BAN>
 __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs a) {
+  __shared__ uint32_t s_banbits[BAN ? (1 << 18) / 32 : 1];
+  __shared__ int32_t s_seq[BAN ? kStepProcMaxLen : 1];
   __shared__ u64 h_mass[SMP_BUCKETS];
   __shared__ uint32_t h_cnt[SMP_BUCKETS];
   __shared__ u64 s_w[SMP_WAVES];
@@ -95,6 +101,17 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs
   if (a.done && a.done[row]) return;
   const float* lg = a.logits + (size_t)row * a.ld;
   const int V = a.vocab;
+  if constexpr (BAN) {  // the row's sequence so far: prompt + generated tokens; step = its length
+    for (int w = tid; w < (V + 31) / 32; w += SMP_THREADS) s_banbits[w] = 0u;
+    const int L = a.step;
+    for (int i = tid; i < L; i += SMP_THREADS)
+      s_seq[i] = i < a.prompt_len ? a.prompt[i] : a.gen[(size_t)row * a.gen_stride + (i - a.prompt_len)];
+    __syncthreads();
+    step_proc_bans(a.proc, s_seq, L, tid, SMP_THREADS, [&](int tok) {
+      if (tok >= 0 && tok < V) atomicOr(&s_banbits[tok >> 5], 1u << (tok & 31));
+    });
+    __syncthreads();
+  }
   const int niter = (V + SMP_THREADS * 4 - 1) / (SMP_THREADS * 4);
   const float it = a.inv_temp;
   // UNK penalty (probs[unk] -= unk_penalty, in the Q40 domain: mass[unk] -= floor(penalty * Z)): the token keeps an exact
@@ -104,7 +121,8 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs
   u64 w_unk = 0;
   uint32_t key_unk = 0;
   auto masked = [&](int idx) {
-    return idx == a.pad_idx || (a.block_eos && idx == a.eos_idx) || (unk_dead && idx == a.unk_idx);
+    return idx == a.pad_idx || (a.block_eos && idx == a.eos_idx) || (unk_dead && idx == a.unk_idx) ||
+           (BAN && ((s_banbits[BAN ? idx >> 5 : 0] >> (idx & 31)) & 1u));
   };
   // element visitor: f(idx, raw logit) for every idx < V this thread owns (iteration-major, coalesced)
   auto for_each = [&](auto&& f) {
@@ -224,7 +242,14 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs
       em += lm[j];
       ec += lc[j];
     }
-    const int rbs = block_max_int(best, s_i);  // >= 0: the first token of the range always fits
+    const int rbs = block_max_int(best, s_i);  // >= 0 while a token is unmasked: the first token of the range always fits
+    if (rbs < 0) {  // every token masked (step processors can cover a small vocabulary): no draw, EOS at -inf
+      if (tid == 0) {
+        a.out_tok[row] = a.eos_idx;
+        a.out_logp[row] = -INFINITY;
+      }
+      return;
+    }
     if (best == rbs) {
       s_bc[0] = bm;
       s_bc[1] = bcn;
@@ -300,12 +325,34 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs
   }
   const float logz = __logf((float)zfull * (1.0f / 1099511627776.0f));
 
-  // ---- F. draw: integer target in [0, kept_mass); order = thread-major over the coalesced ownership
   auto kept = [&](int idx, float v) {
     if (masked(idx)) return false;
     const uint32_t key = key_of(idx, v);
     return key > kstar || (key == kstar && idx <= id_thr);
   };
+  if (kept_mass == 0) {
+    // every kept token's mass is below 2^-40 of exp(M): M belongs to a masked token (a ban, PAD, a blocked EOS) far above
+    // the rest.  Their fp32 probabilities are still > 0, so the reference draws among them; the draw here takes the most
+    // probable kept token (lowest id on a value tie) with its exact log-probability.
+    if (tid == 0) s_bc[3] = 0;
+    __syncthreads();
+    u64 bestk = 0;
+    for_each([&](int idx, float v) {
+      if (!kept(idx, v)) return;
+      const u64 k = ((u64)key_of(idx, v) << 32) | (u64)(0xffffffffu - (uint32_t)idx);
+      bestk = k > bestk ? k : bestk;
+    });
+    if (bestk) atomicMax(&s_bc[3], bestk);
+    __syncthreads();
+    if (tid == 0) {  // s_bc[3] != 0: the kept set is never empty (its first token always fits)
+      const int t = (int)(0xffffffffu - (uint32_t)(s_bc[3] & 0xffffffffu));
+      a.out_tok[row] = t;
+      a.out_logp[row] = (lg[t] * it - M) - logz;
+    }
+    return;
+  }
+
+  // ---- F. draw: integer target in [0, kept_mass); order = thread-major over the coalesced ownership
   const u64 zr = a.z ? a.z[row] : smp_hash(a.seed, row, a.step);
   const u64 target = __umul64hi(zr, kept_mass);
   u64 mine = 0;
@@ -387,7 +434,14 @@ hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t stream) {
     if (a.mode == 1 && !(a.top_p > 0.f && a.top_p <= 1.f)) return hipErrorInvalidValue;
     if (a.mode != 0 && a.mode != 1) return hipErrorInvalidValue;
   }
-  hipLaunchKernelGGL(sample_rows_kernel, dim3(a.rows), dim3(SMP_THREADS), 0, stream, a);
+  if (a.proc.active() && a.forced_tok < 0) {
+    if (!a.prompt || a.prompt_len < 1 || a.step < a.prompt_len || a.step > kStepProcMaxLen || !a.gen ||
+        a.gen_stride < a.step - a.prompt_len || a.proc.num_banned > kStepProcMaxBanned)
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(a.rows), dim3(SMP_THREADS), 0, stream, a);
+  } else {
+    hipLaunchKernelGGL(sample_rows_kernel<false>, dim3(a.rows), dim3(SMP_THREADS), 0, stream, a);
+  }
   return hipGetLastError();
 }
 

@@ -270,7 +270,8 @@ class SpeechToTextModelPipeline(SpeechModelPipelineInterface):
     """sonar/inference_pipelines/speech.py:310-399: audio -> sentence vector (speech engine) -> text
     (decoder engine, beam search).  The generator's length cap follows fairseq2's rule with the fbank
     frame count of the batch as source length (`converter.batch_convert(batch.seqs, batch.padding_mask)`,
-    speech.py:369-372)."""
+    speech.py:369-372).  Other generator arguments, `sampler=` and `step_processors=` included, go to
+    EmbeddingToTextModelPipeline.predict."""
 
     def __init__(self, encoder, decoder, tokenizer, device: torch.device = CPU,
                  fbank_dtype: torch.dtype = torch.float32) -> None:

@@ -243,8 +243,10 @@ class EmbeddingToTextModelPipeline(torch.nn.Module):
     """sonar/inference_pipelines/text.py:270-346 on the MI355X engine: embeddings -> texts by
     beam search (fairseq2 BeamSearchSeq2SeqGenerator defaults; `generator_kwargs` accepts
     beam_size, min_gen_len, max_gen_len, max_seq_len, normalize_scores, len_penalty,
-    unk_penalty, temperature), or -- with `sampler=TopKSampler(k) / TopPSampler(p)` (sonar_amd.generation) -- by
-    fairseq2's SamplingSeq2SeqGenerator (same kwargs minus beam_size)."""
+    unk_penalty, temperature, step_processors), or -- with `sampler=TopKSampler(k) / TopPSampler(p)` (sonar_amd.generation)
+    -- by fairseq2's SamplingSeq2SeqGenerator (same kwargs minus beam_size).  `step_processors=[...]` takes
+    NGramRepeatBlockProcessor / BannedSequenceProcessor (sonar_amd.generation, or fairseq2's objects of those names); they
+    run on the device inside the token selection of both generators."""
 
     def __init__(self, decoder, tokenizer: Union[str, Path, NllbTokenizer], device: torch.device = CPU,
                  dtype: Optional[torch.dtype] = None) -> None:
@@ -293,7 +295,8 @@ class EmbeddingToTextModelPipeline(torch.nn.Module):
 class TextToTextModelPipeline(torch.nn.Module):
     """sonar/inference_pipelines/text.py:56-137: text -> sentence vector (encoder engine) -> text
     (decoder engine, beam search).  `max_seq_len` is clamped to the decoder's positional range as the
-    reference does (text.py:104-107)."""
+    reference does (text.py:104-107); every other generator argument, `sampler=` and `step_processors=` included, goes to
+    EmbeddingToTextModelPipeline.predict."""
 
     def __init__(self, encoder, decoder, tokenizer: Union[str, Path, NllbTokenizer], device: torch.device = CPU,
                  dtype: Optional[torch.dtype] = None) -> None:

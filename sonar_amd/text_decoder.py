@@ -280,6 +280,29 @@ class TextDecoderEngine:
         """Independent decode chains of generate() (smi_text_decoder_set_chains): 0 = the engine's choice."""
         _lib.check(self.lib.smi_text_decoder_set_chains(self._handle, int(chains)))
 
+    def set_step_processors(self, step_processors=None) -> None:
+        """Step processors of the following generate() / sample() calls (smi_text_decoder_set_step_processors): a list of
+        NGramRepeatBlockProcessor / BannedSequenceProcessor (sonar_amd.generation, or fairseq2's own); None or [] clears."""
+        from .generation import resolve_step_processors
+
+        ngram, banned = resolve_step_processors(step_processors)
+        if ngram == 0 and not banned:
+            _lib.check(self.lib.smi_text_decoder_set_step_processors(self._handle, None))
+            return
+        sp, keep = _lib.step_processors_struct(ngram, banned)
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.smi_text_decoder_set_step_processors(self._handle, C.byref(sp)))
+        del keep
+
+    def _with_step_processors(self, step_processors, call):
+        if not step_processors:
+            return call()
+        self.set_step_processors(step_processors)
+        try:
+            return call()
+        finally:
+            self.set_step_processors(None)
+
     def last_margins(self, n: int) -> torch.Tensor:
         """Decision margins fp32 [n, 2] of the last generate() call (smi_text_decoder_last_margins)."""
         out = torch.empty((n, 2), dtype=torch.float32, device=self.device)
@@ -291,11 +314,18 @@ class TextDecoderEngine:
     def generate(self, embeddings: torch.Tensor, prompt: Sequence[int], beam_size: int = 5, min_gen_len: int = 1,
                  max_gen_len: Tuple[int, int] = (1, 128), max_seq_len: Optional[int] = None,
                  normalize_scores: bool = True, len_penalty: float = 1.0, unk_penalty: float = 0.0,
-                 temperature: float = 1.0, source_len: Optional[int] = None):
+                 temperature: float = 1.0, source_len: Optional[int] = None, step_processors=None):
         """Beam search with fairseq2's BeamSearchSeq2SeqGenerator defaults.
         Returns (tokens int32 [n, beam, L] (-1 padded), lens int32 [n, beam], scores fp32 [n, beam]),
         hypotheses best first; tokens are the generated part (after the prompt) incl. the final EOS.
-        `source_len`: see `_length_limits` (None = the sentence-vector case)."""
+        `source_len`: see `_length_limits` (None = the sentence-vector case).  `step_processors`: see
+        `set_step_processors`; a banned token's log-probability is -inf after log_softmax, on the free steps."""
+        return self._with_step_processors(step_processors, lambda: self._generate(
+            embeddings, prompt, beam_size, min_gen_len, max_gen_len, max_seq_len, normalize_scores, len_penalty,
+            unk_penalty, temperature, source_len))
+
+    def _generate(self, embeddings, prompt, beam_size, min_gen_len, max_gen_len, max_seq_len, normalize_scores,
+                  len_penalty, unk_penalty, temperature, source_len):
         e = self._emb(embeddings)
         n = e.shape[0]
         plen = len(prompt)
@@ -318,22 +348,29 @@ class TextDecoderEngine:
                max_gen_len: Tuple[int, int] = (1, 128), max_seq_len: Optional[int] = None,
                normalize_scores: bool = True, len_penalty: float = 1.0, unk_penalty: float = 0.0,
                temperature: float = 1.0, seed: Optional[int] = None, sentence_offset: int = 0,
-               source_len: Optional[int] = None):
+               source_len: Optional[int] = None, step_processors=None):
         """fairseq2's SamplingSeq2SeqGenerator (one hypothesis per sentence) with a TopKSampler /
         TopPSampler (sonar_amd.generation).  Returns (tokens int32 [n, L] (-1 padded), lens int32 [n],
         scores fp32 [n]).  `unk_penalty` is subtracted from the UNK token's probability before the filter, as the
         reference's generator does.  `seed` None draws one from torch's global CPU generator, so
         `torch.manual_seed` makes a run repeatable as it does for the reference; the random stream of a
-        sentence depends on (seed, sentence_offset + its index, step) only, not on the batch."""
+        sentence depends on (seed, sentence_offset + its index, step) only, not on the batch.  `step_processors`: see
+        `set_step_processors`; a banned token's probability is 0 before the filter."""
         from .generation import resolve_sampler
 
         kind, k, p = resolve_sampler(sampler)
+        if seed is None:
+            seed = int(torch.randint(0, 2**62, (1,)).item())
+        return self._with_step_processors(step_processors, lambda: self._sample(
+            embeddings, prompt, kind, k, p, min_gen_len, max_gen_len, max_seq_len, normalize_scores, len_penalty,
+            unk_penalty, temperature, seed, sentence_offset, source_len))
+
+    def _sample(self, embeddings, prompt, kind, k, p, min_gen_len, max_gen_len, max_seq_len, normalize_scores,
+                len_penalty, unk_penalty, temperature, seed, sentence_offset, source_len):
         e = self._emb(embeddings)
         n = e.shape[0]
         plen = len(prompt)
         max_len, min_len = self._length_limits(plen, min_gen_len, max_gen_len, max_seq_len, source_len)
-        if seed is None:
-            seed = int(torch.randint(0, 2**62, (1,)).item())
         seed = (int(seed) + 0x9E3779B97F4A7C15 * 65536 * int(sentence_offset)) & 0xFFFFFFFFFFFFFFFF
         sp = _lib.smi_sampling_params(sampler=kind, top_k=k, top_p=p, temperature=temperature, max_seq_len=max_len,
                                       min_seq_len=min_len, normalize_scores=1 if normalize_scores else 0,

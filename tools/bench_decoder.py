@@ -25,6 +25,19 @@ def main():
         torch.cuda.synchronize()
         dt = time.time() - t0
         print(f"  rep {rep}: {dt*1e3:.1f} ms")
+    if len(sys.argv) > 3 and sys.argv[3] == "ngram":   # A/B: no step processors vs NGramRepeatBlockProcessor(3), alternated
+        from sonar_amd.generation import NGramRepeatBlockProcessor
+        times = {"off": [], "ngram3": []}
+        legs = [("off", None), ("ngram3", [NGramRepeatBlockProcessor(3)])]
+        for rep in range(6):   # A B, B A, ...: neither leg always runs first
+            for name, procs in (legs if rep % 2 == 0 else legs[::-1]):
+                t0 = time.time()
+                eng.generate(emb, [3, 256047], step_processors=procs, **kw)
+                torch.cuda.synchronize()
+                times[name].append(time.time() - t0)
+        for name, ts in times.items():
+            print(f"step processors {name}: " + " ".join(f"{t / (steps + 1) * 1e3:.3f}" for t in ts) +
+                  f" ms/step (min {min(ts) / (steps + 1) * 1e3:.3f})")
     if len(sys.argv) > 3 and sys.argv[3] == "sample":   # the sampling generator on the same shapes
         from sonar_amd.generation import TopKSampler, TopPSampler
         for smp in (TopPSampler(0.9), TopKSampler(50)):
