@@ -557,6 +557,45 @@ int smi_head_featurize(int32_t form, const void* src, const void* mt, const void
 int smi_mlp_head_forward(smi_mlp_head* head, const void* x_f16, int32_t rows, int32_t out_act, float* out,
                          void* stream);
 
+/* LASER2 BiLSTM text encoder -------------------------------------------------
+ * Replaces LaserLstmEncoder.forward(seqs, seq_lens)   sonar/nn/laser_lstm_encoder.py:60-116
+ * for the configurations of Laser2Config              sonar/models/laser2_text/config.py:12-38
+ * (card sonar/cards/laser2_text_encoder.yaml: arch laser2 = 50004 / pad 1 / 320 / 512 / 5 layers / bidirectional / 0.0).
+ * fp16 operands with fp32 accumulation; fp32 cell state, gates and pooling.  Any embed_dim / hidden_size / num_layers, uni- or
+ * bidirectional: widths are zero-padded inside the engine, which is exact (a padded unit's c and h stay 0). */
+typedef struct smi_laser2 smi_laser2; /* opaque */
+typedef struct smi_laser2_config {
+  int64_t vocab_size;    /* vocabulary_size: 50004 */
+  int32_t pad_idx;       /* 1: its embedding row is used as stored; its positions pool as -inf (:105-110) */
+  int32_t embed_dim;     /* model_dim: 320 */
+  int32_t hidden_size;   /* 512 */
+  int32_t num_layers;    /* 5 */
+  int32_t bidirectional; /* 1 */
+  float padding_value;   /* 0.0: pad_packed_sequence's value at positions >= a row's length (:83-85) */
+} smi_laser2_config;
+/* One direction of one nn.LSTM layer: lstm.{weight,bias}_{ih,hh}_l{k}[_reverse], PyTorch gate order i, f, g, o. */
+typedef struct smi_laser2_layer {
+  smi_tensor weight_ih; /* [4*hidden, in]: in = embed_dim (layer 0), hidden_size * (1 + bidirectional) after */
+  smi_tensor weight_hh; /* [4*hidden, hidden] */
+  smi_tensor bias_ih;   /* [4*hidden] */
+  smi_tensor bias_hh;   /* [4*hidden] */
+} smi_laser2_layer;
+/* embed: embed_tokens.weight [vocab, embed_dim]; layers: [num_layers][1 + bidirectional] (forward, then reverse);
+ * max_tokens_hint: workspace to reserve (sum of the lengths of a batch; it grows on demand). */
+int smi_laser2_create(const smi_laser2_config* cfg, const smi_tensor* embed, const smi_laser2_layer* layers,
+                      int64_t max_tokens_hint, smi_laser2** out);
+void smi_laser2_destroy(smi_laser2* h);
+/* ids: device int64 [n, s]; seq_lens: HOST int32 [n], each in [1, s], max == s (the reference asserts it, :86);
+ * out: device fp32 [n, hidden_size * (1 + bidirectional)], forward units first, in the caller's row order (:114-116).
+ * Positions whose token is pad_idx pool as -inf whatever seq_lens says; a row with non-pad tokens at or beyond its length
+ * also pools padding_value (:83-114).  Out-of-vocabulary ids are not read: they raise a flag that smi_laser2_status reports. */
+int smi_laser2_forward(smi_laser2* h, const int64_t* ids, const int32_t* seq_lens, int32_t n, int32_t s, float* out,
+                       void* stream);
+/* Synchronises `stream`; SMI_ERR_INVALID_ARG if a batch since the last call held ids outside [0, vocab_size) (the
+ * reference's nn.Embedding raises IndexError there); clears the flag. */
+int smi_laser2_status(smi_laser2* h, void* stream);
+int64_t smi_laser2_device_bytes(const smi_laser2* h);
+
 /* Host input path ------------------------------------------------------------
  * Replaces the fairseq2n C++ DataPipeline stages between the tokenizer and the model,
  * sonar/inference_pipelines/text.py:226-247 (`.map(truncate)`, `.dynamic_bucket(...)`,

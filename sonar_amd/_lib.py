@@ -257,6 +257,22 @@ class smi_mlp_head_layer(C.Structure):
     _fields_ = [("w", smi_tensor), ("b", smi_tensor), ("out_dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class smi_laser2_config(C.Structure):
+    _fields_ = [
+        ("vocab_size", C.c_int64),
+        ("pad_idx", C.c_int32),
+        ("embed_dim", C.c_int32),
+        ("hidden_size", C.c_int32),
+        ("num_layers", C.c_int32),
+        ("bidirectional", C.c_int32),
+        ("padding_value", C.c_float),
+    ]
+
+
+class smi_laser2_layer(C.Structure):
+    _fields_ = [(n, smi_tensor) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
+
+
 ABI_VERSION = 7  # SMI_ABI_VERSION of include/sonar_mi355.h
 
 # every symbol include/sonar_mi355.h declares: name -> (restype, argtypes)
@@ -319,6 +335,12 @@ SYMBOLS = {
     "smi_mlp_head_destroy": (None, [_vp]),
     "smi_head_featurize": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "smi_mlp_head_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "smi_laser2_create": (C.c_int, [C.POINTER(smi_laser2_config), C.POINTER(smi_tensor), C.POINTER(smi_laser2_layer), _i64,
+                                    C.POINTER(_vp)]),
+    "smi_laser2_destroy": (None, [_vp]),
+    "smi_laser2_forward": (C.c_int, [_vp, _vp, C.POINTER(_i32), _i32, _i32, _vp, _vp]),
+    "smi_laser2_status": (C.c_int, [_vp, _vp]),
+    "smi_laser2_device_bytes": (_i64, [_vp]),
     "smi_host_token_lengths": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, C.POINTER(_i64)]),
     "smi_host_dynamic_bucket": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
     "smi_host_collate_nllb": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp, _i32, _vp, _i32, _i32, _i64, _vp, _i32, _i32]),

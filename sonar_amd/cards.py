@@ -15,6 +15,7 @@ name resolves to the file the card's URL ends in, looked up in `$SONAR_CHECKPOIN
     blaser_2_0_ref / blaser_2_0_qe -> blaser_2_0_ref.pt / blaser_2_0_qe.pt (the cards point at
                                       huggingface `model.pt` files; store them under these names)
     sonar_mutox                   -> mutox.pt
+    laser2_text_encoder           -> laser2.pt, tokenizer laser2.spm   arch laser2
 """
 from __future__ import annotations
 
@@ -25,6 +26,7 @@ from pathlib import Path
 from typing import List, Optional, Union
 
 NLLB_SPM = "sentencepiece.source.256000.model"
+LASER2_SPM = "laser2.spm"
 
 _TEXT_CARDS = {
     "text_sonar_basic_encoder": ("sonar_text_encoder.pt", "basic"),
@@ -35,6 +37,9 @@ _HEAD_CARDS = {
     "blaser_2_0_ref": ("blaser_2_0_ref.pt", "basic_ref"),
     "blaser_2_0_qe": ("blaser_2_0_qe.pt", "basic_qe"),
     "sonar_mutox": ("mutox.pt", "mutox"),
+}
+_LASER2_CARDS = {
+    "laser2_text_encoder": ("laser2.pt", "laser2"),
 }
 _SPEECH_RE = re.compile(r"^sonar_speech_encoder_([a-z]{3})$")
 
@@ -67,7 +72,7 @@ def _find(basenames: List[str]) -> Optional[Path]:
 
 def is_card_name(name: Union[str, Path]) -> bool:
     s = str(name)
-    return s in _TEXT_CARDS or s in _HEAD_CARDS or bool(_SPEECH_RE.match(s))
+    return s in _TEXT_CARDS or s in _HEAD_CARDS or s in _LASER2_CARDS or bool(_SPEECH_RE.match(s))
 
 
 def resolve_card(name: Union[str, Path]) -> ResolvedCard:
@@ -78,6 +83,9 @@ def resolve_card(name: Union[str, Path]) -> ResolvedCard:
         cands = [base]
     elif s in _HEAD_CARDS:
         base, arch = _HEAD_CARDS[s]
+        cands = [base]
+    elif s in _LASER2_CARDS:
+        base, arch = _LASER2_CARDS[s]
         cands = [base]
     else:
         m = _SPEECH_RE.match(s)
@@ -93,7 +101,7 @@ def resolve_card(name: Union[str, Path]) -> ResolvedCard:
         raise FileNotFoundError(
             f"card {s!r}: none of {cands} found in {[str(d) for d in asset_dirs()]} "
             "(set SONAR_CHECKPOINT_DIR to the directory holding the downloaded SONAR files)")
-    tok = _find([NLLB_SPM]) if s in _TEXT_CARDS else None
+    tok = _find([NLLB_SPM]) if s in _TEXT_CARDS else _find([LASER2_SPM]) if s in _LASER2_CARDS else None
     return ResolvedCard(s, ckpt, arch, tok)
 
 
@@ -108,9 +116,10 @@ def resolve_checkpoint(name_or_path: Union[str, Path], default_arch: str):
 def resolve_tokenizer(name_or_path: Union[str, Path]) -> Path:
     """SentencePiece model path for a text card name or a plain path."""
     if is_card_name(name_or_path) and not Path(str(name_or_path)).exists():
-        tok = _find([NLLB_SPM])
+        spm_name = LASER2_SPM if str(name_or_path) in _LASER2_CARDS else NLLB_SPM
+        tok = _find([spm_name])
         if tok is None:
-            raise FileNotFoundError(f"tokenizer of card {name_or_path!r}: {NLLB_SPM} not found in "
+            raise FileNotFoundError(f"tokenizer of card {name_or_path!r}: {spm_name} not found in "
                                     f"{[str(d) for d in asset_dirs()]}")
         return tok
     return Path(str(name_or_path))
