@@ -271,6 +271,18 @@ void smi_text_decoder_destroy(smi_text_decoder* dec);
 int smi_text_decoder_logits(smi_text_decoder* dec, const void* emb, int32_t emb_dtype, int32_t n,
                             const int64_t* prev_tokens, int32_t t, float* out_logits, void* stream);
 
+/* Teacher-forced scoring (forced decoding): log p(text | sentence embedding), token by token, in one parallel forward.
+ * emb device [n, input_dim] (emb_dtype SMI_F32 / SMI_F16); tokens device int64 [n, t], row s's sequence is
+ * tokens[s, 0 .. lens[s]) with the prompt first; lens HOST int32 [n], 1 <= lens[s] <= t <= max_seq_len + 1.
+ * out_logprobs device fp32 [n, t - 1]:
+ *   out[s, j] = log_softmax(logits(emb_s, tokens[s, 0 .. j]))[tokens[s, j + 1]]   for j < lens[s] - 1,   0 beyond.
+ * Plain log-softmax at temperature 1: no PAD / EOS masking, no unk_penalty, no step processors -- the beam search applies
+ * those after its log-softmax, so the normaliser is the same.  Positions >= lens[s] are never read (any value, out-of-range
+ * ids included).  An id outside [0, vocab) inside a length fails the call with SMI_ERR_INVALID_ARG (it is never used as an
+ * index; the handle stays usable).  Synchronises `stream` once, at the end. */
+int smi_text_decoder_score(smi_text_decoder* dec, const void* emb, int32_t emb_dtype, int32_t n, const int64_t* tokens,
+                           int32_t t, const int32_t* lens, float* out_logprobs, void* stream);
+
 /* Beam search for n sentence embeddings.  prompt: HOST int64 [prompt_len] (= [</s>, __lang__]).
  * Outputs (device): out_tokens int32 [n, beam, max_seq_len] generated tokens after the prompt incl. the
  * final EOS, -1 padded; out_lens int32 [n, beam]; out_scores fp32 [n, beam]; hypotheses best first

@@ -17,6 +17,7 @@ LIB_PATH = Path(os.environ["SMI_LIB"]).resolve() if os.environ.get("SMI_LIB") el
     Path(__file__).resolve().parent / "lib" / "libsonar_mi355.so"
 
 SMI_OK = 0
+SMI_ERR_INVALID_ARG = -1
 SMI_F32, SMI_F16, SMI_BF16 = 0, 1, 2
 SMI_POOL = {"mean": 0, "max": 1, "last": 2, "attention": 3}
 SMI_MARGIN = {"ratio": 0, "distance": 1, "cosine": 2}
@@ -300,6 +301,7 @@ SYMBOLS = {
                                           C.POINTER(smi_text_decoder_weights), C.POINTER(_vp)]),
     "smi_text_decoder_destroy": (None, [_vp]),
     "smi_text_decoder_logits": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]),
+    "smi_text_decoder_score": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _vp, _vp]),
     "smi_text_decoder_generate": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), _i32,
                                             C.POINTER(smi_beam_search_params), _vp, _vp, _vp, _vp]),
     "smi_text_decoder_last_margins": (C.c_int, [_vp, _vp, _i32, _vp]),

@@ -48,7 +48,10 @@ __device__ __forceinline__ half4 at_tr_read(unsigned lds_addr) {
 // a transposed copy (keys r, r+2 of a group sit in different halves of the 128-B row: all 64 banks).
 // NTL: the K / V tiles are loaded non-temporally (launcher: every sentence fits ONE 128-query block, so each qkv line
 // is read by exactly one workgroup, once)
-template <bool TM, bool QTM, bool NTL = false>
+// CAUSAL (the decoder's teacher-forced scoring, launch_causal_attention): query i sees keys 0..i only.  The key loop of a
+// 128-query block ends at min(len, q0 + 128) -- one bound for every wave, so the per-tile barrier stays uniform -- and
+// the tiles that reach past q0 mask the keys after each lane's query.
+template <bool TM, bool QTM, bool NTL = false, bool CAUSAL = false>
 __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict__ qkv,
                                                         const int32_t* __restrict__ cu,
                                                         f16* __restrict__ ctx, int d, float sl2e, int order) {
@@ -68,6 +71,7 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
   const int len = cu[n + 1] - start;
   const int q0 = blockIdx.z * AT_QB;
   if (q0 >= len) return;
+  const int kend = CAUSAL ? min(len, q0 + AT_QB) : len;  // keys this block reads
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
@@ -125,10 +129,10 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
     for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
 
   stage(0, 0);
-  for (int kv0 = 0, t = 0; kv0 < len; kv0 += AT_KB, ++t) {
+  for (int kv0 = 0, t = 0; kv0 < kend; kv0 += AT_KB, ++t) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();  // tile t has landed for everyone; everyone is done with the other buffer
-    if (kv0 + AT_KB < len) stage(kv0 + AT_KB, (t + 1) & 1);
+    if (kv0 + AT_KB < kend) stage(kv0 + AT_KB, (t + 1) & 1);
     const char* Ks = lds + (t & 1) * 2 * TILE;
 
     // The tile's two 32-key blocks are taken one after the other, each with its own online-softmax step: only
@@ -151,6 +155,13 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           if (kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= len) sc[r] = -INFINITY;
+      }
+      if constexpr (CAUSAL) {
+        if (kv0 + AT_KB > q0) {  // the tile reaches past the block's first query: keys after the lane's query are out
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi > qi) sc[r] = -INFINITY;
+        }
       }
       float mx = sc[0];
 #pragma unroll
@@ -254,6 +265,17 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
         *(half4*)(op + db * 32 + 8 * q + 4 * hi) = v;
       }
   }
+}
+
+// Causal self-attention of the decoder's teacher-forced rows: cu = [0, seq, 2 seq, ...] (every sequence padded to seq
+// rows, the padding last, so a valid query never sees a padded key); qkv row-major [rows][3d], ctx row-major [rows][d].
+hipError_t launch_causal_attention(const f16* qkv, const int32_t* cu, f16* ctx, int nseq, int seq, int d, int heads,
+                                   hipStream_t stream) {
+  if (heads <= 0 || d != heads * 64 || nseq <= 0 || seq <= 0) return hipErrorInvalidValue;
+  const float sl2e = 0.125f * 1.4426950408889634f;  // Dh^-0.5 * log2(e)
+  hipLaunchKernelGGL((attention_kernel<false, false, false, true>), dim3(nseq, heads, (seq + AT_QB - 1) / AT_QB), dim3(256), 0,
+                     stream, qkv, cu, ctx, d, sl2e, 1);
+  return hipGetLastError();
 }
 
 hipError_t launch_attention(const f16* qkv, const int32_t* cu, f16* ctx, int N, int max_len, int d,

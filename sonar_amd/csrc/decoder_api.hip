@@ -52,6 +52,7 @@ struct DecWork {
   DevBuf pmax, psum, pval, pidx;
   DevBuf tile_max, tile_sum;  // logits-GEMM tile statistics [rows_pad][vocab_pad / 256]
   DevBuf prompt_dev;          // sampling under step processors: the prompt, int32
+  DevBuf sc_lens, sc_tgt, sc_bad, sc_cu;  // teacher-forced scoring: lengths, row targets, bad-id flag, [0, seq, 2 seq, ...]
   int kv_positions = 0;       // positions per layer in the current kv allocation
   bool chained = false;       // this call runs next to other chains: per-launch tile choices differ (decoder_step)
   hipStream_t stream = nullptr;  // chains of a split call run on streams of their own
@@ -486,6 +487,114 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
   return SMI_OK;
 }
 
+// Teacher-forced scoring (smi_text_decoder_score).  A group of ns sentences is ns * seq uniform rows
+// r = s * seq + j (input position j, target tok[s][j + 1]); the whole forward runs once over them.
+constexpr int kScoreRows = 16384;              // rows per sentence group: bounds the activation workspace
+constexpr int64_t kScoreLogitBytes = 2ll << 30;  // fp32 logits of one projection chunk
+
+int score_rows_per_chunk(const smi_text_decoder* D, int rows) {
+  const int64_t fit = kScoreLogitBytes / (D->vocab_pad * 4) / 256 * 256;
+  return (int)std::max<int64_t>(256, std::min<int64_t>(fit, round_up(rows, 256)));
+}
+
+int score_group(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dtype, int ns, const int64_t* tokens, int t,
+                const int32_t* lens_dev, int seq, float* out, hipStream_t stream) {
+  const smi_text_decoder_config& c = D->cfg;
+  const int d = c.model_dim, f = c.ffn_inner_dim, L = c.num_layers;
+  const int rows = ns * seq, n_pad = (int)round_up(ns, 256);
+  // the MFMA GEMMs take 256-row tiles; the flex kernels any row count
+  const int rows_pad = D->flex ? rows : (int)round_up(rows, 256);
+  const size_t es = D->act_bytes();
+  const int chunk = score_rows_per_chunk(D, rows);
+  const int ntiles = (int)(D->vocab_pad / 256);
+  HIP_TRY(S.x.reserve((size_t)rows_pad * d * 4));
+  HIP_TRY(S.h.reserve((size_t)rows_pad * d * es));
+  HIP_TRY(S.ctx.reserve((size_t)rows_pad * d * es));
+  HIP_TRY(S.ffn.reserve((size_t)rows_pad * f * es));
+  HIP_TRY(S.kv.reserve((size_t)rows_pad * 3 * d * es));  // the group's q | k | v rows
+  HIP_TRY(S.logits.reserve((size_t)chunk * D->vocab_pad * 4));
+  HIP_TRY(S.tile_max.reserve((size_t)chunk * ntiles * 4));
+  HIP_TRY(S.tile_sum.reserve((size_t)chunk * ntiles * 4));
+  HIP_TRY(S.sc_tgt.reserve((size_t)rows_pad * 4));
+  if (int rc = compute_cross_constants(D, S, emb, emb_dtype, ns, n_pad, stream)) return rc;
+  // rows past a sentence's length embed the EOS id: finite activations that no scored row reads (causal, padding last)
+  HIP_TRY(launch_score_embed(tokens, t, lens_dev, D->embed.p, D->flex ? 0 : 1, D->pos.as<float>(), c.embed_scale, c.pos_offset,
+                             S.x.as<float>(), S.sc_tgt.as<int32_t>(), ns, seq, rows_pad, d, c.vocab_size, c.eos_idx,
+                             S.sc_bad.as<int32_t>(), stream));
+  float* x = S.x.as<float>();
+  const float* cc = S.cc.as<float>();
+  if (D->flex) {
+    float* h = S.h.as<float>();
+    float* qkv = S.kv.as<float>();
+    float* ctx = S.ctx.as<float>();
+    float* ffn = S.ffn.as<float>();
+    for (int l = 0; l < L; ++l) {
+      DecLayer& Ly = D->layers[l];
+      HIP_TRY(launch_flex_layernorm(x, Ly.ln1_w.as<float>(), Ly.ln1_b.as<float>(), c.ln_eps, h, rows, d, stream));
+      HIP_TRY(launch_flex_linear(h, d, Ly.w_qkv.as<float>(), Ly.b_qkv.as<float>(), qkv, 3 * d, rows, 3 * d, d, 0, nullptr, 0,
+                                 stream));
+      HIP_TRY(launch_flex_attention(qkv, 3 * d, qkv + d, qkv + 2 * d, 3 * d, ctx, d, ns, seq, seq, nullptr, c.num_heads,
+                                    d / c.num_heads, 1, stream));
+      HIP_TRY(launch_flex_linear(ctx, d, Ly.w_o.as<float>(), Ly.b_o.as<float>(), x, d, rows, d, d, 0, x, d, stream));
+      HIP_TRY(launch_flex_add_rows(x, cc + (size_t)l * n_pad * d, rows, d, seq, stream));
+      HIP_TRY(launch_flex_layernorm(x, Ly.ln3_w.as<float>(), Ly.ln3_b.as<float>(), c.ln_eps, h, rows, d, stream));
+      HIP_TRY(launch_flex_linear(h, d, Ly.w_1.as<float>(), Ly.b_1.as<float>(), ffn, f, rows, f, d, 1, nullptr, 0, stream));
+      HIP_TRY(launch_flex_linear(ffn, f, Ly.w_2.as<float>(), Ly.b_2.as<float>(), x, d, rows, d, f, 0, x, d, stream));
+    }
+    HIP_TRY(launch_flex_layernorm(x, D->lnf_w.as<float>(), D->lnf_b.as<float>(), c.ln_eps, h, rows, d, stream));
+    for (int c0 = 0; c0 < rows; c0 += chunk) {
+      const int m = std::min(chunk, rows - c0);
+      HIP_TRY(launch_flex_linear(h + (size_t)c0 * d, d, D->embed.as<float>(), nullptr, S.logits.as<float>(), (int)D->vocab_pad,
+                                 m, (int)c.vocab_size, d, 0, nullptr, 0, stream));
+      HIP_TRY(launch_flex_tile_stats(S.logits.as<float>(), (int)D->vocab_pad, m, (int)c.vocab_size, 1.f,
+                                     S.tile_max.as<float>(), S.tile_sum.as<float>(), m, stream));
+      HIP_TRY(launch_score_gather(S.logits.as<float>(), D->vocab_pad, S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, m,
+                                  S.sc_tgt.as<int32_t>(), c0, m, seq, out, t - 1, stream));
+    }
+    return SMI_OK;
+  }
+  f16* h = S.h.as<f16>();
+  f16* qkv = S.kv.as<f16>();
+  f16* ctx = S.ctx.as<f16>();
+  f16* ffn = S.ffn.as<f16>();
+  // the attention writes the group's rows only: keep the GEMM padding rows of its output finite
+  if (rows_pad > rows) HIP_TRY(hipMemsetAsync(ctx + (size_t)rows * d, 0, (size_t)(rows_pad - rows) * d * 2, stream));
+  const int tm = D->ffn_tile_major;
+  // the layer GEMMs stay on the 128x128 engine family whatever the row count: the automatic choice moves to the 256x256 and
+  // 4-wave engines as M grows, and their fp32 summation orders differ, so a sentence's scores would depend on its company
+  const int fam = 1 << 8;
+  for (int l = 0; l < L; ++l) {
+    DecLayer& Ly = D->layers[l];
+    HIP_TRY(launch_sum_layernorm(x, nullptr, 0, 0, nullptr, 1, Ly.ln1_w.as<float>(), Ly.ln1_b.as<float>(), c.ln_eps, h,
+                                 rows_pad, d, stream));
+    HIP_TRY(launch_gemm_tn(EPI_BIAS_F16 | fam, h, Ly.w_qkv.as<f16>(), Ly.b_qkv.as<float>(), qkv, rows_pad, 3 * d, d, 3 * d, stream));
+    HIP_TRY(launch_causal_attention(qkv, S.sc_cu.as<int32_t>(), ctx, ns, seq, d, c.num_heads, stream));
+    HIP_TRY(launch_gemm_tn(EPI_RESID_F32 | fam, ctx, Ly.w_o.as<f16>(), Ly.b_o.as<float>(), x, rows_pad, d, d, d, stream));
+    // + the sentence's cross-attention constant (row r -> sentence r / seq < ns; the padding rows past ns * seq are not
+    // touched, so they never index past the n_pad reserved constant rows), then LN3
+    HIP_TRY(launch_sum_layernorm(x, nullptr, 0, 0, cc + (size_t)l * n_pad * d, seq, Ly.ln3_w.as<float>(), Ly.ln3_b.as<float>(),
+                                 c.ln_eps, h, rows, d, stream, tm));
+    HIP_TRY(launch_gemm_tn(EPI_RELU_F16 | fam | (tm ? GEMM_IN_TM | GEMM_OUT_TM : 0), h, Ly.w_1.as<f16>(), Ly.b_1.as<float>(), ffn,
+                           rows_pad, f, d, f, stream));
+    HIP_TRY(launch_gemm_tn(EPI_RESID_F32 | fam | (tm ? GEMM_IN_TM : 0), ffn, Ly.w_2.as<f16>(), Ly.b_2.as<float>(), x, rows_pad, d, f,
+                           d, stream));
+  }
+  const int ltm = D->embed_tm.p != nullptr;  // the tied projection reads a tile-major copy of the table
+  HIP_TRY(launch_sum_layernorm(x, nullptr, 0, 0, nullptr, 1, D->lnf_w.as<float>(), D->lnf_b.as<float>(), c.ln_eps, h, rows_pad,
+                               d, stream, ltm));
+  // the logits GEMM in chunks of whole 256-row tiles (a tile-major chunk is contiguous), with the fused per-tile softmax
+  // statistics at scale 1: the gather reads the statistics and the target's single logit, never the 1 MB row
+  GemmTileStats st{S.tile_max.as<float>(), S.tile_sum.as<float>(), 1.f, (int)c.vocab_size};
+  for (int c0 = 0; c0 < rows; c0 += chunk) {
+    const int m = std::min(chunk, rows_pad - c0);
+    HIP_TRY(launch_gemm_tn(EPI_STORE_F32 | (ltm ? GEMM_IN_TM : 0), h + (size_t)c0 * d, (ltm ? D->embed_tm : D->embed).as<f16>(),
+                           nullptr, S.logits.p, m, (int)D->vocab_pad, d, (int)D->vocab_pad, stream, &st));
+    HIP_TRY(launch_score_gather(S.logits.as<float>(), D->vocab_pad, S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, m,
+                                S.sc_tgt.as<int32_t>(), c0, std::min(m, rows - c0), seq, out, t - 1, stream));
+  }
+  return SMI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -612,6 +721,49 @@ int smi_text_decoder_logits(smi_text_decoder* D, const void* emb, int32_t emb_dt
                              S.logits.p, (size_t)D->vocab_pad * 4, (size_t)D->cfg.vocab_size * 4, n,
                              hipMemcpyDeviceToDevice, stream));
   }
+  return SMI_OK;
+}
+
+int smi_text_decoder_score(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n, const int64_t* tokens,
+                           int32_t t, const int32_t* lens, float* out_logprobs, void* stream_v) {
+  if (!D || !emb || !tokens || !lens || !out_logprobs) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (n <= 0 || t <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (emb_dtype != SMI_F32 && emb_dtype != SMI_F16) return fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
+  const smi_text_decoder_config& c = D->cfg;
+  if (t > c.max_seq_len + 1) return fail(SMI_ERR_INVALID_ARG, "t=%d exceeds max_seq_len + 1 = %d", t, c.max_seq_len + 1);
+  int lmax = 1;
+  for (int s = 0; s < n; ++s) {
+    if (lens[s] < 1 || lens[s] > t) return fail(SMI_ERR_INVALID_ARG, "lens[%d] = %d outside [1, t = %d]", s, lens[s], t);
+    lmax = std::max(lmax, (int)lens[s]);
+  }
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (t == 1) return SMI_OK;  // nothing to score
+  HIP_TRY(hipMemsetAsync(out_logprobs, 0, (size_t)n * (t - 1) * 4, stream));
+  if (lmax == 1) return SMI_OK;
+  DecWork& S = D->ws[0];
+  S.chained = false;
+  // every sentence of the call gets the same seq = lmax - 1 input positions; groups of whole sentences bound the workspace
+  const int seq = lmax - 1;
+  const int per = std::max(1, std::min(n, kScoreRows / seq));
+  std::vector<int32_t> cu((size_t)per + 1);  // the causal attention's sequence starts (every group: uniform seq rows)
+  for (int s = 0; s <= per; ++s) cu[s] = s * seq;
+  HIP_TRY(S.sc_lens.reserve((size_t)n * 4));
+  HIP_TRY(S.sc_cu.reserve(cu.size() * 4));
+  HIP_TRY(S.sc_bad.reserve(4));
+  HIP_TRY(hipMemcpyAsync(S.sc_lens.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemcpyAsync(S.sc_cu.p, cu.data(), cu.size() * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipMemsetAsync(S.sc_bad.p, 0, 4, stream));
+  const size_t emb_row = (size_t)c.input_dim * (emb_dtype == SMI_F32 ? 4 : 2);
+  for (int s0 = 0; s0 < n; s0 += per) {
+    const int ns = std::min(per, n - s0);
+    if (int rc = score_group(D, S, (const char*)emb + s0 * emb_row, emb_dtype, ns, tokens + (size_t)s0 * t, t,
+                             S.sc_lens.as<int32_t>() + s0, seq, out_logprobs + (size_t)s0 * (t - 1), stream))
+      return rc;
+  }
+  int32_t bad = 0;
+  HIP_TRY(hipMemcpyAsync(&bad, S.sc_bad.p, 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  if (bad) return fail(SMI_ERR_INVALID_ARG, "a token id inside a sequence's length is outside [0, vocab %d)", (int)c.vocab_size);
   return SMI_OK;
 }
 

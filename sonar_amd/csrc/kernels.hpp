@@ -250,6 +250,21 @@ hipError_t launch_beam_output(const int32_t* fin_tok, const int32_t* fin_len, co
 hipError_t launch_gather_tokens(const int64_t* src, int src_stride, int col, int32_t* tok, int rows,
                                 hipStream_t stream);
 
+// ---- teacher-forced scoring (score.hip, attention.hip) ----
+// Causal self-attention over nseq sequences of `seq` rows each (cu = [0, seq, 2 seq, ..., nseq * seq] on the device):
+// qkv row-major [nseq * seq][3d], ctx [nseq * seq][d], head_dim 64 (attention.hip)
+hipError_t launch_causal_attention(const f16* qkv, const int32_t* cu, f16* ctx, int nseq, int seq, int d, int heads,
+                                   hipStream_t stream);
+// x[r] = E[id] * scale + PE[j + pos_offset] for r = s * seq + j (tok [nseq][ldt], ids past lens[s] read as `fill`),
+// tgt[r] = tok[s][j + 1] or -1, zero rows up to rows_pad; table fp16 (table_f16) or fp32; bad ids raise *bad
+hipError_t launch_score_embed(const int64_t* tok, int ldt, const int32_t* lens, const void* table, int table_f16,
+                              const float* pe, float scale, int pos_offset, float* x, int32_t* tgt, int nseq, int seq,
+                              int rows_pad, int d, int64_t vocab, int fill, int32_t* bad, hipStream_t stream);
+// out[g / seq][g % seq] = logits[g - c0][tgt[g]] - lse(row) for the scored rows g of one logits chunk [c0, c0 + rows)
+hipError_t launch_score_gather(const float* logits, int64_t ldl, const float* tile_max, const float* tile_sum, int ntiles,
+                               int stat_rows, const int32_t* tgt, int c0, int rows, int seq, float* out, int ldo,
+                               hipStream_t stream);
+
 // ---- embedding heads: BLASER / MuTox MLPs (heads.hip) ----
 // form 0: out = f16(x) (src only); 1 QE: [src, mt, src*mt, |mt-src|]; 2 COMET:
 // [ref, mt, src*mt, ref*mt, |mt-src|, |mt-ref|]; inputs optionally L2-normalised first (F.normalize).

@@ -292,6 +292,42 @@ class EmbeddingToTextModelPipeline(torch.nn.Module):
         return texts
 
 
+    @torch.inference_mode()
+    def score(self, inputs: torch.Tensor, texts: Sequence[str], target_lang: str, batch_size: int = 5,
+              progress_bar: bool = False) -> torch.Tensor:
+        """log p(text | sentence embedding) per input, fp32 [n] on the CPU: the sum of the log-probabilities of the text's
+        pieces and its final </s>, given the prompt [</s>, __lang__] (teacher forcing, TextDecoderEngine.score).  The
+        scored sequence is prompt + pieces + [</s>] (`score_sequences`), the shape generate() produces.  Sentences are
+        sorted by length and scored in buckets of `batch_size`; the result is in input order."""
+        if batch_size <= 0:
+            raise ValueError("`batch_size` should be strictly positive")
+        rows, texts = list(inputs), list(texts)
+        if len(rows) != len(texts):
+            raise ValueError(f"{len(rows)} embeddings but {len(texts)} texts")
+        seqs, plen = score_sequences(self.tokenizer, texts, target_lang)
+        order = sorted(range(len(seqs)), key=lambda i: len(seqs[i]))
+        out = torch.zeros(len(seqs), dtype=torch.float32)
+        batches: Iterable = [order[i:i + batch_size] for i in range(0, len(order), batch_size)]
+        if progress_bar:
+            batches = add_progress_bar(batches, inputs=rows, batch_size=batch_size)
+        for idx in batches:
+            emb = torch.stack([rows[i] for i in idx]).to(self.device)
+            lp = self.model.engine.score(emb, [seqs[i] for i in idx]).double().cpu()
+            for k, i in enumerate(idx):   # positions plen - 1 .. L - 2 predict the pieces and </s>
+                out[i] = float(lp[k, plen - 1:len(seqs[i]) - 1].sum())
+        return out
+
+
+def score_sequences(tokenizer: NllbTokenizer, texts: Sequence[str], target_lang: str):
+    """(sequences, prompt length) that EmbeddingToTextModelPipeline.score scores: [</s>, __lang__] + pieces + [</s>] per
+    text -- fairseq2's target-mode encoding of a complete sentence, and what generate() returns after its prompt.
+    (NllbEncoder's own target mode keeps its empty suffix: it builds decoder prompts.)"""
+    enc = tokenizer.create_encoder(task="translation", lang=target_lang, mode="target")
+    eos = tokenizer.vocab_info.eos_idx
+    ids = enc.encode_batch(list(texts)) if hasattr(enc, "encode_batch") else [enc.ids(t) for t in texts]
+    return [list(s) + [eos] for s in ids], len(enc.prefix)
+
+
 class TextToTextModelPipeline(torch.nn.Module):
     """sonar/inference_pipelines/text.py:56-137: text -> sentence vector (encoder engine) -> text
     (decoder engine, beam search).  `max_seq_len` is clamped to the decoder's positional range as the
@@ -332,3 +368,17 @@ class TextToTextModelPipeline(torch.nn.Module):
             out.extend(self.vec2t.predict(emb, target_lang=target_lang, batch_size=len(chunk),
                                           source_len=src_len, **generator_kwargs))
         return out
+
+    @torch.inference_mode()
+    def score(self, input: Union[Path, Sequence[str]], targets: Sequence[str], source_lang: str, target_lang: str,
+              batch_size: int = 5, progress_bar: bool = False) -> torch.Tensor:
+        """log p(target | encode(source)) per pair, fp32 [n] on the CPU: the sources go through `t2vec`, the targets are
+        scored by EmbeddingToTextModelPipeline.score (pieces + final </s> given [</s>, __lang__])."""
+        if isinstance(input, (str, Path)):
+            with open(Path(input), "r", encoding="utf-8") as fh:
+                input = [line.rstrip("\n") for line in fh]
+        sources, targets = list(input), list(targets)
+        if len(sources) != len(targets):
+            raise ValueError(f"{len(sources)} sources but {len(targets)} targets")
+        emb = self.t2vec.predict(sources, source_lang=source_lang, batch_size=batch_size)
+        return self.vec2t.score(emb, targets, target_lang=target_lang, batch_size=batch_size, progress_bar=progress_bar)

@@ -236,6 +236,52 @@ class TextDecoderEngine:
                 prev.data_ptr(), t, out.data_ptr(), _lib.current_stream_ptr()))
         return out
 
+    def score(self, embeddings: torch.Tensor, sequences, lens=None) -> torch.Tensor:
+        """Teacher-forced log-probabilities fp32 [n, t - 1] on the device (smi_text_decoder_score, one parallel forward):
+        out[s, j] = log_softmax(logits(emb_s, seq_s[0 .. j]))[seq_s[j + 1]] for j < len_s - 1, 0 beyond.  Plain log-softmax
+        at temperature 1: no PAD / EOS masking, no unk_penalty, no step processors (the beam search applies those after
+        the same normaliser).  `sequences`: a list of id lists (prompt first), or an int64 [n, t] tensor with `lens`
+        (None = every row is t long); 1 <= len_s <= max_seq_len + 1.  An id outside the vocabulary inside a length raises
+        ValueError."""
+        e = self._emb(embeddings)
+        n = e.shape[0]
+        if isinstance(sequences, torch.Tensor):
+            if sequences.dim() != 2:
+                raise ValueError("sequences must be an int64 [n, t] tensor or a list of id lists")
+            toks = sequences.to(self.device, torch.int64).contiguous()
+            t = toks.shape[1]
+            lens_l = [t] * toks.shape[0] if lens is None else [int(v) for v in torch.as_tensor(lens).reshape(-1).tolist()]
+        else:
+            if lens is not None:
+                raise ValueError("`lens` goes with a tensor of sequences")
+            seqs = [[int(v) for v in s] for s in sequences]
+            lens_l = [len(s) for s in seqs]
+            t = max(lens_l, default=1)
+            host = torch.zeros((len(seqs), t), dtype=torch.int64)
+            for i, s in enumerate(seqs):
+                host[i, :len(s)] = torch.tensor(s, dtype=torch.int64)
+            toks = host.to(self.device)
+        if toks.shape[0] != n or len(lens_l) != n:
+            raise ValueError("one embedding and one length per sequence expected")
+        if t > self.cfg.max_seq_len + 1:
+            raise ValueError(f"sequences of {t} tokens exceed the decoder's max_seq_len + 1 = {self.cfg.max_seq_len + 1}")
+        if any(L < 1 or L > t for L in lens_l):
+            raise ValueError(f"every length must be in [1, {t}]")
+        out = torch.empty((n, max(t - 1, 0)), dtype=torch.float32, device=self.device)
+        if n == 0 or t <= 1:
+            return out.zero_()
+        lens_arr = (C.c_int32 * n)(*lens_l)
+        with torch.cuda.device(self.device):
+            try:
+                _lib.check(self.lib.smi_text_decoder_score(
+                    self._handle, e.data_ptr(), _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16, n,
+                    toks.data_ptr(), t, lens_arr, out.data_ptr(), _lib.current_stream_ptr()))
+            except _lib.SmiError as err:
+                if err.status == _lib.SMI_ERR_INVALID_ARG:
+                    raise ValueError(str(err)) from None
+                raise
+        return out
+
     def _length_limits(self, plen: int, min_gen_len: int, max_gen_len: Tuple[int, int],
                        max_seq_len: Optional[int], source_len: Optional[int]) -> Tuple[int, int]:
         """fairseq2's Seq2SeqGenerator length rule: max_gen_len = a * max_source_len + b, where
