@@ -452,7 +452,6 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
   // The fp16 residual stream itself is tile-major when everything that touches it has that path (d = 1024, no
   // encoded_seqs output): the residual epilogues of the attention-output and FFN-output GEMMs then read-modify-write
   // it straight from the accumulators instead of staging the tile through LDS in 8 barrier-separated passes.
-  const bool x_tm_enabled = tune(TUNE_ENC_X_TM, 1) != 0;  // ENC_X_TM=0: row-major residual stream (A/B measurements)
   // Small batches: the FFN output projection (K = ffn_inner_dim) has (M/256)*(d/256) output tiles -- a handful of
   // CUs would each walk 256 K slices (C1, 1312 tokens: 130 us per layer, 3/4 of the forward).  It is then run as a
   // split-K GEMM into fp32 slabs (ks * tiles units, one round on the chip) that a small kernel folds into x.
@@ -462,19 +461,17 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
     while (ffn2_ks < 8 && tiles * ffn2_ks * 2 <= e->num_cus && f % (ffn2_ks * 2 * 512) == 0) ffn2_ks *= 2;
     if (d % 256 || ffn2_ks < 2) ffn2_ks = 1;
   }
-  // In that mode the whole layer takes the decoder's shape (6 launches instead of 8; SMI_ENC_SB=0 keeps the round-2
-  // schedule for A/B runs): the attention output projection is split-K too (every 128x128 unit on a CU of its own, the
+  // In that mode the whole layer takes the decoder's shape (6 launches instead of 8): the attention output projection is split-K too (every 128x128 unit on a CU of its own, the
   // lone-tile ring engine), and the slabs of both projections are folded into the residual stream by the fused
   // sum + LayerNorm kernel that produces the next GEMM's input -- no separate fold, no separate LayerNorm.
-  const bool sb_env = tune(TUNE_ENC_SB, 1) != 0;
-  const bool sb = sb_env && ffn2_ks > 1 && c.num_layers > 0;
+  const bool sb = ffn2_ks > 1 && c.num_layers > 0;
   const int out_ks = sb ? gemm_splitk_parts((int)rows, d, d, 8) : 1;
   const int max_ks = std::max(ffn2_ks, out_ks);
   if (ffn2_ks > 1 && e->parts.bytes < (size_t)max_ks * rows * d * 4) {
     HIP_TRY(hipStreamSynchronize(stream));
     HIP_TRY(e->parts.alloc((size_t)max_ks * rows * d * 4));
   }
-  const int x_tm = x_tm_enabled && e->tile_major && x16 && d == 1024 && !out_encoded && ffn2_ks == 1;
+  const int x_tm = e->tile_major && x16 && d == 1024 && !out_encoded && ffn2_ks == 1;
   if (rows > total) {
     if (x_tm)  // the rows of the last 256-row panel are interleaved: clear the whole panel, the embedding refills it
       HIP_TRY(hipMemsetAsync((char*)x + (size_t)(rows - 256) * d * xes, 0, (size_t)256 * d * xes, stream));
@@ -508,7 +505,6 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
     ProfScope ps(e, SMI_PROF_LAYERNORM, stream);  // the first LayerNorm's statistics have no producing GEMM
     HIP_TRY(launch_row_stats_tm((const f16*)x, e->rowpart.as<float2>(), M, d, nparts, stream));
   }
-  const bool pf_on = true;  // weight prefetch by the row kernels' surplus workgroups (SMI_PREFETCH=0 disables it: A/B runs)
   for (int l = 0; l < c.num_layers && sb; ++l) {  // small batches: the decoder-shaped layer (see above)
     Layer& L = e->layers[l];
     void* parts = e->parts.p;
@@ -520,7 +516,7 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
     const int sf16 = slab_env && x16;
     { ProfScope ps_(e, SMI_PROF_LAYERNORM, stream);  // x += FFN-output slabs of the previous layer; h = LN1(x)
     HIP_TRY(launch_sum_layernorm(x, l ? parts : nullptr, ffn2_ks, ps, nullptr, 1, L.ln1_w.as<float>(), L.ln1_b.as<float>(),
-                                 c.ln_eps, h, M, d, stream, tm, x16, pf_on ? L.w_1.p : nullptr, (size_t)f * d * 2, sf16)); }
+                                 c.ln_eps, h, M, d, stream, tm, x16, L.w_1.p, (size_t)f * d * 2, sf16)); }
     { ProfScope ps_(e, SMI_PROF_GEMM_QKV, stream);
     HIP_TRY(launch_gemm_tn(EPI_BIAS_F16 | io_tm, h, L.w_qkv.as<f16>(), L.b_qkv.as<float>(), qkv, M, 3 * d, d, 3 * d, stream)); }
     { ProfScope ps_(e, SMI_PROF_ATTENTION, stream);
@@ -529,7 +525,7 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
     HIP_TRY(launch_gemm_tn_splitk(ctx, L.w_o.as<f16>(), L.b_o.as<float>(), parts, M, d, d, out_ks, stream, tm, sf16)); }
     { ProfScope ps_(e, SMI_PROF_LAYERNORM, stream);  // x += attention-output slabs; h = LN2(x)
     HIP_TRY(launch_sum_layernorm(x, parts, out_ks, ps, nullptr, 1, L.ln2_w.as<float>(), L.ln2_b.as<float>(), c.ln_eps, h, M, d,
-                                 stream, tm, x16, pf_on ? L.w_2.p : nullptr, (size_t)f * d * 2, sf16)); }
+                                 stream, tm, x16, L.w_2.p, (size_t)f * d * 2, sf16)); }
     { ProfScope ps_(e, SMI_PROF_GEMM_FFN1, stream);
     HIP_TRY(launch_gemm_tn(EPI_RELU_F16 | io_tm, h, L.w_1.as<f16>(), L.b_1.as<float>(), ffn, M, f, d, f, stream)); }
     { ProfScope ps_(e, SMI_PROF_GEMM_FFN2, stream);
@@ -537,7 +533,7 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
     if (l + 1 == c.num_layers)  // the last layer's slabs meet the stream before the final LayerNorm + pooling
       HIP_TRY(launch_fold_residual(x, x16, parts, ffn2_ks, ps, ps, stream, sf16)); }
   }
-  for (int l = 0; l < c.num_layers && !sb; ++l) {
+  for (int l = 0; l < c.num_layers && !sb; ++l) {  // here ffn2_ks == 1
     Layer& L = e->layers[l];
     if (lnfold) {
       ProfScope ps(e, SMI_PROF_GEMM_QKV, stream);
@@ -569,14 +565,8 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
                            stream)); }
     }
     { ProfScope ps(e, SMI_PROF_GEMM_FFN2, stream);
-    if (ffn2_ks > 1) {
-      HIP_TRY(launch_gemm_tn_splitk(ffn, L.w_2.as<f16>(), L.b_2.as<float>(), e->parts.as<float>(), M, d, f, ffn2_ks,
-                                    stream, tm));
-      HIP_TRY(launch_fold_residual(x, x16, e->parts.as<float>(), ffn2_ks, (size_t)M * d, (size_t)M * d, stream));
-    } else {
-      HIP_TRY(launch_gemm_tn(epi_resid | in_tm | x_out_tm, ffn, L.w_2.as<f16>(), L.b_2.as<float>(), x, M, d, f, d,
-                             stream, nullptr, lnfold ? &fold_prod : nullptr));
-    } }
+    HIP_TRY(launch_gemm_tn(epi_resid | in_tm | x_out_tm, ffn, L.w_2.as<f16>(), L.b_2.as<float>(), x, M, d, f, d,
+                           stream, nullptr, lnfold ? &fold_prod : nullptr)); }
   }
   { ProfScope ps(e, SMI_PROF_LN_POOL, stream);
   HIP_TRY(launch_ln_pool(x, e->lnf_w.as<float>(), e->lnf_b.as<float>(), c.ln_eps, d_cu, out_emb,
@@ -773,7 +763,7 @@ int smi_relpos_attention(const void* qkv, const int32_t* cu, const void* rp, int
   if (n <= 0 || max_len <= 0 || rp_rows <= 0 || rp_zero < 0 || rp_zero >= rp_rows || tile_major < 0 || tile_major > 3)
     return fail(SMI_ERR_INVALID_ARG, "n=%d max_len=%d rp_zero=%d rp_rows=%d tile_major=%d", n, max_len, rp_zero, rp_rows, tile_major);
   if ((tile_major & 2) && !relpos_attention_reads_tile_major())
-    return fail(SMI_ERR_UNSUPPORTED, "tile-major q | k | v needs the LDS-ring kernel (SPEECH_RP_LDS, SPEECH_QKV_TM)");
+    return fail(SMI_ERR_UNSUPPORTED, "tile-major q | k | v needs the LDS-ring kernel (SPEECH_RP_LDS)");
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   HIP_TRY(launch_relpos_attention((const f16*)qkv, cu, (const f16*)rp, rp_zero, rp_rows, u_bias, v_bias, (f16*)ctx, n, max_len, d,
                                   heads, (hipStream_t)stream, tile_major & 1, (tile_major >> 1) & 1));

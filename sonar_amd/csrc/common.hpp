@@ -23,12 +23,6 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds(SMI_GLOBAL_PTR(gsrc), SMI_LDS_PTR(lds_wave_base), 16, 0, 0);
 }
 
-// 4 B per lane (LDS destination = wave-uniform base + lane*4): per-tile constants (bias slices, row statistics) that travel with
-// a tile's pipeline fill instead of through registers
-__device__ __forceinline__ void glds4(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(SMI_GLOBAL_PTR(gsrc), SMI_LDS_PTR(lds_wave_base), 4, 0, 0);
-}
-
 // glds16 with the non-temporal cache policy (aux = 2, `nt`): for lines that exactly ONE workgroup reads, once.
 __device__ __forceinline__ void glds16_nt(const void* gsrc, void* lds_wave_base) {
   __builtin_amdgcn_global_load_lds(SMI_GLOBAL_PTR(gsrc), SMI_LDS_PTR(lds_wave_base), 16, 0, 2);
@@ -52,9 +46,7 @@ __device__ __forceinline__ void fp16_saturate_on() { __builtin_amdgcn_s_setreg(1
 // Cross-lane reductions: the whole wave (wave_sum / wave_max, result in every lane), and for the single-query
 // attention kernels (lane = 8 * pg + c) over the 8 lanes c of a position group and over the 8 position groups pg
 // with the lane's c kept.  DPP row operations and the gfx950 lane-swap
-// instructions run at VALU rate; __shfl_xor compiles to ds_bpermute_b32, an LDS-crossbar round trip per step
-// (-DSMI_SHFL_REDUCE restores the shuffles for A/B builds).
-#ifndef SMI_SHFL_REDUCE
+// instructions run at VALU rate; __shfl_xor compiles to ds_bpermute_b32, an LDS-crossbar round trip per step.
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
   return __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(v), CTRL, 0xf, 0xf, false));
@@ -99,38 +91,8 @@ __device__ __forceinline__ float max_over_groups_of_8(float v) {
   const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
-#else
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float sum_over_8(float v) {
-  v += __shfl_xor(v, 1, 64);
-  v += __shfl_xor(v, 2, 64);
-  v += __shfl_xor(v, 4, 64);
-  return v;
-}
-__device__ __forceinline__ float sum_over_groups_of_8(float v) {
-  v += __shfl_xor(v, 8, 64);
-  v += __shfl_xor(v, 16, 64);
-  v += __shfl_xor(v, 32, 64);
-  return v;
-}
-__device__ __forceinline__ float max_over_groups_of_8(float v) {
-  v = fmaxf(v, __shfl_xor(v, 8, 64));
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  v = fmaxf(v, __shfl_xor(v, 32, 64));
-  return v;
-}
-#endif
 
-// WEIGHT PREFETCH by surplus workgroups (round 4).  A small-batch forward is a chain of latency-bound launches that
+// Weight prefetch by surplus workgroups (round 4).  A small-batch forward is a chain of latency-bound launches that
 // leaves HBM idle most of the time, and then streams a layer's 16.8 MB FFN matrices cold: 18.2 us for the FFN-inner
 // projection at M = 256 against 14.0 us when the matrix was read just before (tools/probe_cold_weights.py).  A row
 // kernel that occupies a quarter of the CUs therefore carries extra workgroups that simply READ the weights a later

@@ -207,8 +207,7 @@ static void launch_sum_ln_np(int blocks, hipStream_t stream, XT* x, const PT* pa
   const int cus = num_cus();  // gemm.hip: per-device, atomically cached (decode chains call this from several host threads)
   // ... when the row work takes at most a quarter of the chip (<= 256 rows: the surplus then streams a 16.8 MB matrix in
   // one round trip; at 512 rows the prefetch cost more than it saved)
-  const bool pf_env = tune(TUNE_PREFETCH, 1) != 0;
-  const int extra = pf_env && pf && pf_bytes && blocks * 4 <= cus ? cus - blocks : 0;
+  const int extra = pf && pf_bytes && blocks * 4 <= cus ? cus - blocks : 0;
   const int main_blocks = blocks;
 #define SMI_SL(NP)                                                                                                     \
   hipLaunchKernelGGL((sum_ln_kernel<NV, XT, NP, PT>), dim3(blocks + extra), dim3(256), 0, stream, x, parts, nparts,    \

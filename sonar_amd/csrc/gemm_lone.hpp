@@ -47,11 +47,7 @@ struct LoneShape {
   static constexpr int MI = BM / 64, NI = BN / 64;             // 32-row MFMA blocks of a wave along m / n
   static constexpr int STAGE_BYTES = (BM + BN) * GT_BK * 2;    // X rows, then W rows, 128 B each
   static constexpr int CPW = (BM + BN) / 32;                   // 1-KiB DMA pieces per wave and stage
-#ifdef SMI_LONE_ST  // probe builds: another ring depth
-  static constexpr int STAGES = SMI_LONE_ST;
-#else
   static constexpr int STAGES = 4;
-#endif
   static constexpr int LDS_BYTES = STAGES * STAGE_BYTES;       // 64 KiB for 64x64
   static constexpr int WG_PER_CU = 160 * 1024 / LDS_BYTES >= 2 ? 2 : 1;
 };
@@ -206,10 +202,6 @@ __device__ __forceinline__ void lone_mainloop(f32x16 (&acc)[NI][MI], const f16* 
     LONE_PH(ph_read, t0)
     if (t + ST < nt) issue(t + ST);
     LONE_PH(ph_dma, t0)
-#ifdef SMI_LONE_SERIAL  // probe build: fragment reads retired BEFORE the MFMAs (no overlap inside a wave)
-    if (t + 2 < nt) lone_wait_stages<CPW>(min(nt - 1, t + ST) - (t + 2));
-    lone_retire(nxt);
-#endif
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
@@ -220,10 +212,8 @@ __device__ __forceinline__ void lone_mainloop(f32x16 (&acc)[NI][MI], const f16* 
           acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_f16(cur.w[ks][ni], cur.x[ks][mi], acc[ni][mi], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     LONE_PH(ph_mfma, t0)
-#ifndef SMI_LONE_SERIAL
     if (t + 2 < nt) lone_wait_stages<CPW>(min(nt - 1, t + ST) - (t + 2));
     lone_retire(nxt);
-#endif
     LONE_PH(ph_wait, t0)
   };
   int t = 0;

@@ -48,17 +48,9 @@ __device__ __forceinline__ void lone16_mainloop(f32x4 (&acc)[4][4], const f16* _
   }
   // Loads in flight per wave: DW / DX k-blocks of W / X, 4 each (32 registers per k-block, 128 KiB in flight per CU).  Measured
   // against ALL of W up front (248 registers) and against X two blocks ahead: the same 1.32-1.34 ms per batch-of-5 forward
-  // (r04 experiment 17) -- the unit is not waiting for operand latency.  Probe builds: -DSMI_L16_DW / -DSMI_L16_DX.
-#ifdef SMI_L16_DW
-  constexpr int DW = NKB < SMI_L16_DW ? NKB : SMI_L16_DW;
-#else
+  // (r04 experiment 17) -- the unit is not waiting for operand latency.
   constexpr int DW = NKB < 4 ? NKB : 4;
-#endif
-#ifdef SMI_L16_DX
-  constexpr int DX = NKB < SMI_L16_DX ? NKB : SMI_L16_DX;
-#else
   constexpr int DX = NKB < 4 ? NKB : 4;
-#endif
   half8 fx[DX][4], fw[DW][4];
   auto load_w = [&](int i, int slot) {  // this wave's i-th k-block = global k-block wave + 4 * i
 #pragma unroll

@@ -20,12 +20,6 @@
 #include "gemm_v2.hpp"
 #include "kernels.hpp"
 
-// -DV2_PROBE=<bits> (measurement builds, wrong results): 1 = no stores under the K loop, 2 = no read-out, 4 = plain (not
-// non-temporal) stores
-#ifndef V2_PROBE
-#define V2_PROBE 0
-#endif
-
 namespace smi {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -121,7 +115,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
     if constexpr (GLU) return (char*)out + ((size_t)tm_ * (N >> 6) + (size_t)tn_ * 4 + wc * 2) * (TM_BLOCK * 2);
     return (char*)out + ((size_t)tm_ * (N >> 5) + (size_t)tn_ * 8 + wc * 4) * (TM_BLOCK * 2);
   };
-  constexpr int NST = (V2_PROBE & 3) ? 0 : (GLU ? 16 : 32);  // stores per wave and tile
+  constexpr int NST = GLU ? 16 : 32;  // stores per wave and tile
 
   bool more = true, first_tile = true;
   while (more) {
@@ -220,12 +214,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
     asm volatile(V2_RDOUT_FIRST_STR);
     auto put = [&](int i, const u32x4& chunk) {  // chunk i = (j, mi)
       u32x4* dst = (u32x4*)(obase + (size_t)(i >> 3) * (TM_BLOCK * 2) + (i & 7) * 1024 + lane_part);
-      if constexpr ((V2_PROBE & 1) != 0)
-        asm volatile("" ::"v"(chunk), "v"(dst));
-      else if constexpr ((V2_PROBE & 4) != 0)
-        *dst = chunk;
-      else
-        store_nt(dst, chunk);
+      store_nt(dst, chunk);
     };
     auto readout = [&](auto mode_tag) {
       constexpr int MODE = decltype(mode_tag)::value;
@@ -355,8 +344,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
 #undef SMI_V2_KBLOCK
 #undef SMI_V2_PAIR
     };
-    if constexpr ((V2_PROBE & 2) != 0) {
-    } else if constexpr (FOLD) {
+    if constexpr (FOLD) {
       if (fold.centered)
         readout(std::integral_constant<int, 2>{});
       else

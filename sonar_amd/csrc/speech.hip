@@ -565,11 +565,7 @@ __device__ __forceinline__ half4 ra_tr_read(unsigned lds_addr) {
 // 3 waves per SIMD (<= 168 registers; 3 workgroups x 48 KiB of LDS per CU): the kernel is a chain of LDS round trips, DMA
 // waits and one barrier per 32-key block, so a third resident workgroup is what hides them (round 4; it took 204 registers =
 // 2 waves before the pad addresses and the first block's second pad half stopped occupying 31 registers across the loop).
-// -DSMI_RELPOS_WAVES=2 restores the two-wave allocation for A/B builds.
-#ifndef SMI_RELPOS_WAVES
-#define SMI_RELPOS_WAVES 3
-#endif
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_WAVES, SMI_RELPOS_WAVES))) void relpos_attention_kernel(const f16* __restrict__ qkv,
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void relpos_attention_kernel(const f16* __restrict__ qkv,
                                                                const int32_t* __restrict__ cu,
                                                                const f16* __restrict__ rp, int rp_zero,
                                                                int rp_rows,
@@ -804,12 +800,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
   }
 }
 
-// -DSMI_RPL_PAD32 (variant builds): fp32 score pad, 68 KiB of LDS = two workgroups per CU
-#ifdef SMI_RPL_PAD32
-typedef float RplPad;
-#else
-typedef f16 RplPad;
-#endif
 // ---------------------------------------------------------------------------------------------------------------------
 // Round 6: the same kernel with the position rows staged ONCE per workgroup through LDS and the score pad in fp16.
 // What bounded the kernel above (profiles/r06_experiments.txt, experiment 14): not its ~250 VALU instructions per key block and
@@ -827,12 +817,12 @@ typedef f16 RplPad;
 //    the content scores) to fp16 before adding them (fairseq2 RelativePositionSDPA: two fp16 matmuls); here only the position
 //    term takes that rounding, the sum and the softmax stay fp32.
 // SMI_SPEECH_RP_LDS=0: the kernel above (A/B runs).
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_WAVES, SMI_RELPOS_WAVES))) void relpos_attention_lds_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void relpos_attention_lds_kernel(
     const f16* __restrict__ qkv, const int32_t* __restrict__ cu, const f16* __restrict__ rp, int rp_zero, int rp_rows,
     const float* __restrict__ u_bias, const float* __restrict__ v_bias, f16* __restrict__ ctx, int d, float sl2e, int ctx_tm,
     int qkv_tm) {
   constexpr int BLK = RA_KB * 128;  // 4 KiB
-  __shared__ __attribute__((aligned(16))) char lds[4 * BLK + 4 * BLK * (int)sizeof(RplPad) / 2 + 5 * BLK];  // K / V x 2 | fp16 pads | position-row ring
+  __shared__ __attribute__((aligned(16))) char lds[4 * BLK + 4 * BLK + 5 * BLK];  // K / V x 2 | fp16 pads | position-row ring
   const int n = blockIdx.x, h = blockIdx.y;
   const int start = cu[n], len = cu[n + 1] - start;
   const int q0 = blockIdx.z * RA_QB;
@@ -840,8 +830,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int l31 = lane & 31, hi = lane >> 5;
   char* const kvb = lds;
-  RplPad* Gs = (RplPad*)(lds + 4 * BLK) + wave * 64 * 32;  // [64 rho][32 queries]
-  char* ring = lds + 4 * BLK + 4 * BLK * (int)sizeof(RplPad) / 2;
+  f16* Gs = (f16*)(lds + 4 * BLK) + wave * 64 * 32;  // [64 rho][32 queries]
+  char* ring = lds + 4 * BLK + 4 * BLK;
   const size_t ld = (size_t)3 * d;
   // qkv_tm: the fused QKV projection leaves q | k | v in the tile-major layout (common.hpp; K = 3 d), which lets that GEMM run on the
   // 4-wave engine: a 16-B chunk of a row is a 16-B chunk there too, the chunks of 8 consecutive rows of a 32-column block are 512
@@ -907,10 +897,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
       vaddr[db] = (unsigned)(size_t)(kvb + BLK + key * 128 + ((chunk ^ (((key >> 1) & 1) << 2)) << 4) + (p16 & 1) * 8);
     }
   }
-  // pad reads: byte (gbase + parity * 2048 - c_r * 64) mod 4096 of the wave's pad (rows of 32 fp16), c_r = (r & 3) + 8 (r >> 2)
-  [[maybe_unused]] const int gbase = (l31 + 31 - 4 * hi) * 64 + l31 * 2;
-  // ... of an even block: rd_base + (27 - c_r) * 64, no wrap; of an odd block: the same xor 2048
-  [[maybe_unused]] const unsigned rd_base = (unsigned)(size_t)Gs + (l31 + 31 - 4 * hi - 27) * 64 + l31 * 2;
+  // pad reads: byte ((l31 + 31 - 4 hi) * 64 + l31 * 2 + parity * 2048 - c_r * 64) mod 4096 of the wave's pad (rows of 32 fp16),
+  // c_r = (r & 3) + 8 (r >> 2).  Of an even block: rd_base + (27 - c_r) * 64, no wrap; of an odd block: the same xor 2048
+  const unsigned rd_base = (unsigned)(size_t)Gs + (l31 + 31 - 4 * hi - 27) * 64 + l31 * 2;
   stage(0, 0);
 #pragma unroll
   for (int b = 0; b < 5; ++b) stage_rp(b, b);
@@ -925,9 +914,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
     for (int r = 0; r < 16; ++r) g[r] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) g = __builtin_amdgcn_mfma_f32_32x32x16_f16(rf_hi[ks], qv[ks], g, 0, 0, 0);
-    RplPad* Gold0 = Gs + 32 * 32;  // block 0 reads rho 32..63 from half 1
+    f16* Gold0 = Gs + 32 * 32;  // block 0 reads rho 32..63 from half 1
 #pragma unroll
-    for (int r = 0; r < 16; ++r) Gold0[((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + l31] = (RplPad)g[r];
+    for (int r = 0; r < 16; ++r) Gold0[((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + l31] = (f16)g[r];
   }
 
   int rslot = wave;  // ring slot of block (wave - kb)
@@ -957,7 +946,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
       for (int ks = 0; ks < 4; ++ks) s = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf[ks], qu[ks], s, 0, 0, 0);
     }
     // ---- position term: G[rho][i] = rp[rel_lo + rho] . (q_i + v), rho = 0..31 new, 32..63 = the previous block's ----
-    RplPad* Gnew = Gs + (kb & 1) * 32 * 32;
+    f16* Gnew = Gs + (kb & 1) * 32 * 32;
     {
       half8 rf[4];
       rp_frags(rslot, rf);
@@ -967,7 +956,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) g = __builtin_amdgcn_mfma_f32_32x32x16_f16(rf[ks], qv[ks], g, 0, 0, 0);
 #pragma unroll
-      for (int r = 0; r < 16; ++r) Gnew[((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + l31] = (RplPad)g[r];
+      for (int r = 0; r < 16; ++r) Gnew[((r & 3) + 8 * (r >> 2) + 4 * hi) * 32 + l31] = (f16)g[r];
     }
     // next block: K / V into the other buffer, the one new block of position rows into the slot that just fell out of use
     if (j0 + RA_KB < len) {
@@ -977,16 +966,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
     rslot = rslot ? rslot - 1 : 4;
     dslot = dslot ? dslot - 1 : 4;
     float bd[16];
-#ifdef SMI_RPL_PAD32
-    {
-      int gb = 2 * gbase + ((kb & 1) << 12);
-      asm volatile("" : "+v"(gb));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) bd[r] = *(const float*)((const char*)Gs + ((gb - ((r & 3) + 8 * (r >> 2)) * 128) & 8191));
-#pragma unroll
-      for (int r = 0; r < 16; ++r) asm volatile("" : "+v"(bd[r]));
-    }
-#else
     {
       // 32-bit destinations: ds_read_u16 zero-extends itself.  With 16-bit asm outputs hipcc masks every result with 0xffff right
       // behind its load -- in front of the wait below, i.e. on a register the data has not reached yet (stale values whenever a
@@ -1012,7 +991,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
 #pragma unroll
       for (int r = 0; r < 16; ++r) bd[r] = (float)__builtin_bit_cast(f16, (unsigned short)raw[r]);
     }
-#endif
 #pragma unroll
     for (int r = 0; r < 16; ++r) s[r] += bd[r];
     if (j0 + RA_KB > len) {
@@ -1106,7 +1084,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SMI_RELPOS_
   }
 }
 
-bool relpos_attention_reads_tile_major() { return tune(TUNE_SPEECH_RP_LDS, 1) != 0 && tune(TUNE_SPEECH_QKV_TM, 1) != 0; }
+bool relpos_attention_reads_tile_major() { return tune(TUNE_SPEECH_RP_LDS, 1) != 0; }
 
 hipError_t launch_relpos_attention(const f16* qkv, const int32_t* cu, const f16* rp, int rp_zero, int rp_rows,
                                    const float* u_bias, const float* v_bias, f16* ctx, int n, int max_len, int d,

@@ -267,11 +267,8 @@ int smi_speech_encoder_create(const smi_speech_encoder_config* cfg, const smi_sp
   E->x16 = (c.flags & SMI_ENC_FP16_RESIDUAL) != 0;
   // Round 4: the per-clip kernels (relative-position attention, depthwise conv) write their outputs tile-major -- any packed
   // row addresses its own 64-B slice of a block, no clip alignment is needed -- so the attention-output and pointwise_conv2
-  // GEMMs (N = K = d, the least efficient shape of the block) read both operands as linear 16 KiB bursts.  SMI_SPEECH_MID_TM=0
-  // restores the row-major operands (A/B, read at create).
-  {
-    E->mid_tm = E->ffn_tile_major && tune(TUNE_SPEECH_MID_TM, 1) != 0;
-  }
+  // GEMMs (N = K = d, the least efficient shape of the block) read both operands as linear 16 KiB bursts.
+  E->mid_tm = E->ffn_tile_major;
   // Round 4: with every GEMM operand of a block tile-major, the fp16 residual stream can be tile-major too (the text
   // encoder's layout): the four residual GEMMs read-modify-write it straight from their accumulators (LAYOUT 3)
   // and leave per-row (sum, sum of squares), and the LayerNorms in front of the fused QKV, pointwise_conv1 and the second
@@ -538,8 +535,8 @@ int smi_speech_encoder_forward(smi_speech_encoder* E, const float* fbank, const 
       HIP_TRY(launch_gemm_tn(EPI_RESID_F16 | io_tm, ctx, L.w_o.as<f16>(), L.b_o.as<float>(), x, R, d, d, d, stream, nullptr,
                              &produce));
       const GemmLnFold cg = consume(L.c1_pw1);
-      // tile-major GLU output where the 4-wave engine takes the launch (its GLU read-out; SPEECH_GLU_TM=0: row-major, 8-wave engine)
-      glu_tm = tune(TUNE_SPEECH_GLU_TM, 1) != 0 && gemm_v2_fits(EPI_GLU_F16, R, 2 * d, d, L.c2_pw1.as<float>(), &cg);
+      // tile-major GLU output where the 4-wave engine takes the launch (its GLU read-out; otherwise row-major, 8-wave engine)
+      glu_tm = gemm_v2_fits(EPI_GLU_F16, R, 2 * d, d, L.c2_pw1.as<float>(), &cg);
       HIP_TRY(launch_gemm_tn(EPI_GLU_F16 | (2 << 8) | GEMM_IN_TM | (glu_tm ? GEMM_OUT_TM : 0), (const f16*)x, L.wf_pw1.as<f16>(),
                              L.c2_pw1.as<float>(), E->glu.p, R, 2 * d, d, d, stream, nullptr, &cg));
     } else {

@@ -2,10 +2,10 @@
 // rows of Y (cosine = dot product of L2-normalised rows).  The reference only
 // names xsim (README.md:5); its in-tree form is F.normalize(x) @ F.normalize(y).T
 // (tests/integration_tests/test_text_sonar.py:42-53).  Here the Nx x Ny score
-// matrix is never materialised: each 128x128 score tile comes out of the
-// shared MFMA tile engine straight into a per-lane running top-k kept in
-// VGPRs, so HBM traffic stays ~(Nx+Ny)*d*2 B and the kernel is MFMA-bound
-// (2*d flop per pair).
+// matrix is never materialised: each 256x256 score tile comes out of the
+// shared MFMA tile engine straight into a running top-k (registers at k = 1,
+// per-row lists in LDS for k >= 2), so HBM traffic stays ~(Nx+Ny)*d*2 B and the
+// kernel is MFMA-bound (2*d flop per pair).
 //
 // Work split: grid = (x tiles) x (y chunks); a workgroup walks the y tiles of
 // its chunk.  The grouped XCD raster makes the ~64 workgroups resident on one
@@ -56,80 +56,8 @@ struct TopK {
   }
 };
 
-// partial results: ps/pi [nchunks][nx_pad][K]
-template <int K>
-__global__ __launch_bounds__(GT_THREADS, 2) void xsim_tile_kernel(const f16* __restrict__ Xn,
-                                                                  const f16* __restrict__ Yn,
-                                                                  int d, int ntx, int nty,
-                                                                  int nchunks, int tiles_per_chunk,
-                                                                  int ny, int nx_pad,
-                                                                  float* __restrict__ ps,
-                                                                  int* __restrict__ pi) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int tile_m, chunk;
-  gt_tile_coords(ntx, nchunks, tile_m, chunk);
-  const int m0 = tile_m * GT_BM;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int l31 = lane & 31, hi = lane >> 5, wm = wave >> 1, wn = wave & 1;
-
-  TopK<K> best[2];
-  best[0].init();
-  best[1].init();
-
-  const int t_begin = chunk * tiles_per_chunk;
-  const int t_end = min(nty, t_begin + tiles_per_chunk);
-  for (int ty = t_begin; ty < t_end; ++ty) {
-    const int n0 = ty * GT_BN;
-    GemmTileAcc acc;
-    gt_mainloop(acc, Xn, Yn, d, m0, n0, smem);
-    __syncthreads();  // all waves done with LDS before the next tile's DMA
-#pragma unroll
-    for (int mi = 0; mi < 2; ++mi) {
-#pragma unroll
-      for (int ni = 0; ni < 2; ++ni) {
-        float vmax = acc.v[ni][mi][0];
-#pragma unroll
-        for (int r = 1; r < 16; ++r) vmax = fmaxf(vmax, acc.v[ni][mi][r]);
-        if (vmax >= best[mi].s[K - 1]) {
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int n = n0 + wn * 64 + ni * 32 + 8 * (r >> 2) + 4 * hi + (r & 3);
-            if (n < ny) best[mi].push(acc.v[ni][mi][r], n);
-          }
-        }
-      }
-    }
-  }
-
-  // merge the 4 lists of every x row (2 lane halves x 2 n-waves) through LDS
-  float* ls = (float*)smem;                        // [128 rows][4][K]
-  int* li = (int*)(smem + 128 * 4 * K * 4);
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi) {
-    const int row = wm * 64 + mi * 32 + l31;
-    const int slot = wn * 2 + hi;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      ls[(row * 4 + slot) * K + j] = best[mi].s[j];
-      li[(row * 4 + slot) * K + j] = best[mi].i[j];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 128) {
-    const int row = threadIdx.x;
-    TopK<K> t;
-    t.init();
-    for (int c = 0; c < 4 * K; ++c) t.push(ls[row * 4 * K + c], li[row * 4 * K + c]);
-    const size_t o = ((size_t)chunk * nx_pad + m0 + row) * K;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      ps[o + j] = t.s[j];
-      pi[o + j] = t.i[j];
-    }
-  }
-}
-
-// 256-row variant on the ping-pong tile engine (gemm_tile256.hpp).  The K slices of
+// Partial results: ps/pi [nchunks][nx_pad][K].
+// 256-row tiles on the ping-pong tile engine (gemm_tile256.hpp).  The K slices of
 // ALL y tiles of the chunk form one continuous DMA stream through the 4-slot LDS ring:
 // the pipeline is filled once per workgroup, not once per y tile; at every tile
 // boundary the accumulators are folded into the running top-k and cleared.
@@ -139,14 +67,13 @@ __global__ __launch_bounds__(GT_THREADS, 2) void xsim_tile_kernel(const f16* __r
 __device__ unsigned long long xs_trace_buf[256 * 2 * 4];
 #endif
 
-// The fold of a finished y tile (n0f = its first y row), as a macro: top-1 calls it through a lambda from two places (below),
-// and a lambda around it costs top-4, which has no register to spare, 76 bytes of spills.
+// The fold of a finished y tile (n0f = its first y row) into the per-lane register lists of top-1.
 #define XS_FOLD(n0f)                                                                                                         \
   do {                                                                                                                       \
     float rowthr[8];                                                                                                         \
     _Pragma("unroll")                                                                                                        \
     for (int mi = 0; mi < 8; ++mi) {                                                                                         \
-      float my = best[mi].s[KR - 1];                                                                                          \
+      float my = best[mi].s[0];                                                                                               \
       my = fmaxf(my, __shfl_xor(my, 16, 64));                                                                                \
       my = fmaxf(my, __shfl_xor(my, 32, 64));                                                                                \
       if (kg == 0) thr[(wr * 128 + mi * 16 + l15) * 4 + wc] = my;                                                            \
@@ -257,11 +184,12 @@ __device__ __forceinline__ void xs_thresholds(unsigned lds_addr, float (&t)[8]) 
     }                                                                                                                        \
   } while (0)
 
-// TM: Xn / Yn are TILE-MAJOR copies (common.hpp; packed into the workspace by xsim_run): a K slice of an operand is one
+// Xn / Yn are TILE-MAJOR copies (common.hpp; packed into the workspace by xsim_run): a K slice of an operand is one
 // contiguous 16 KiB block and the Y stream of a chunk one linear walk, instead of 256 pieces of 64 B a row apart -- the
 // layout that bought the GEMMs +7 % end to end and +26 % on the bare operand stream.
-// LL: the running top-k lists live in LDS (above), one per row; !LL: per-lane lists in registers (rounds 1-3, K <= 4)
-template <int K, bool TM, bool LL>
+// K >= 2: the running top-k lists live in LDS (above), one per row.  K = 1: per-lane lists in registers (16 VGPRs, no
+// pressure there: 436.7 vs 439.6 ms with LDS lists at 262 144 x 1 M; profiles/r04_experiments.txt, experiment 2)
+template <int K>
 __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __restrict__ Xn,
                                                                   const f16* __restrict__ Yn, int d,
                                                                   int ntx, int nty, int nchunks,
@@ -283,8 +211,8 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
   const int nt = d / G2_BK;
   const int S = max(ntiles, 0) * nt;
 
-  constexpr int KR = LL ? 1 : K;  // register lists exist only without LL
-  TopK<KR> best[8];               // one running list per accumulator row block
+  constexpr bool LL = K >= 2;
+  TopK<1> best[8];  // !LL: one running list per accumulator row block
 #pragma unroll
   for (int mi = 0; mi < 8; ++mi) best[mi].init();
   unsigned long long* lists = (unsigned long long*)(smem + G2_LDS_BYTES);  // LL: [256 rows][K] keys
@@ -296,11 +224,10 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
     }
     __syncthreads();  // (before any LDS-DMA is in flight)
   }
-  // Row thresholds shared by the 4 column waves (above the ring): thr[row][wc] = the K-th best score wave wc holds for
-  // that row, a lower bound of the row's K-th best.  Published and read WITHOUT a barrier: the values only grow, so a
-  // stale one is still a valid bound.  A lane's own K-th best is a much weaker test -- with it some lane of nearly
-  // every 16-row block passes and the whole wave walks the insertion path every tile (top-4: 610 ms against 480 for
-  // top-1 at 262 144 x 1 M, r02 experiment 24).
+  // !LL: row thresholds shared by the 4 column waves (above the ring): thr[row][wc] = the best score wave wc holds for
+  // that row, a lower bound of the row's best.  Published and read WITHOUT a barrier: the values only grow, so a
+  // stale one is still a valid bound.  A lane's own best is a much weaker test -- with it some lane of nearly
+  // every 16-row block passes and the whole wave walks the insertion path every tile (r02 experiment 24).
   float* thr = (float*)(smem + G2_LDS_BYTES);
   if constexpr (!LL) {
     if (kg == 0) {
@@ -315,39 +242,23 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
     const f16* yg[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-      if constexpr (TM) {  // piece (wave * 2 + q) of a 16 KiB block: 16 rows x 64 B = 1 KiB, linear
-        xg[q] = Xn + (size_t)tile_m * nt * TM_BLOCK + (wave * 2 + q) * 512 + lane * 8;
-        yg[q] = Yn + (size_t)t_begin * nt * TM_BLOCK + (wave * 2 + q) * 512 + lane * 8;
-      } else {
-        const int row = (wave * 2 + q) * 16 + (lane >> 2);
-        const int chunk16 = (lane & 3) ^ tm_swz(row);
-        xg[q] = Xn + (size_t)(m0 + row) * d + chunk16 * 8;
-        yg[q] = Yn + ((size_t)t_begin * G2_BN + row) * d + chunk16 * 8;
-      }
+      // piece (wave * 2 + q) of a 16 KiB block: 16 rows x 64 B = 1 KiB, linear
+      xg[q] = Xn + (size_t)tile_m * nt * TM_BLOCK + (wave * 2 + q) * 512 + lane * 8;
+      yg[q] = Yn + (size_t)t_begin * nt * TM_BLOCK + (wave * 2 + q) * 512 + lane * 8;
     }
     int ik = 0, is = 0;
     auto issue = [&]() {
       char* slot = smem + (is & 3) * G2_SLOT_BYTES + wave * 2048;
-      const size_t koff = TM ? (size_t)ik * TM_BLOCK : (size_t)ik * G2_BK;
+      const size_t koff = (size_t)ik * TM_BLOCK;
       glds16(xg[0] + koff, slot);
       glds16(xg[1] + koff, slot + 1024);
-      if constexpr (TM) {  // block (tile, k) of Y sits at (tile * nt + k) * TM_BLOCK: the chunk's slices are consecutive
-        glds16(yg[0], slot + G2_BM * G2_BK * 2);
-        glds16(yg[1], slot + G2_BM * G2_BK * 2 + 1024);
-        yg[0] += TM_BLOCK;
-        yg[1] += TM_BLOCK;
-        ++is;
-        if (++ik == nt) ik = 0;
-      } else {
-        glds16(yg[0] + koff, slot + G2_BM * G2_BK * 2);
-        glds16(yg[1] + koff, slot + G2_BM * G2_BK * 2 + 1024);
-        ++is;
-        if (++ik == nt) {
-          ik = 0;
-          yg[0] += (size_t)G2_BN * d;
-          yg[1] += (size_t)G2_BN * d;
-        }
-      }
+      // block (tile, k) of Y sits at (tile * nt + k) * TM_BLOCK: the chunk's slices are consecutive
+      glds16(yg[0], slot + G2_BM * G2_BK * 2);
+      glds16(yg[1], slot + G2_BM * G2_BK * 2 + 1024);
+      yg[0] += TM_BLOCK;
+      yg[1] += TM_BLOCK;
+      ++is;
+      if (++ik == nt) ik = 0;
     };
     const int t_sw = (kg ^ tm_swz(l15)) << 4;
     const int xoff = (wr * 128 + l15) * 64 + t_sw;
@@ -393,12 +304,9 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
     // Group 0 therefore DEFERS its fold by one interval -- it first reads the next tile's first slice, then folds in front
     // of that slice's MFMAs (which start from C = 0 and do not read the accumulators) -- so both groups fold in the same
     // interval and a tile has one long interval instead of two.
-    // top-1 keeps the 12 fragments of the next tile's first slice in registers across the deferred fold; top-2 has no registers
-    // for that (it spills) and reads them AFTER the fold, in the same interval; top-4 (64 list registers) spills either way and
-    // ran 60 % slower deferred: it keeps the two-interval schedule.  Same box, 262 144 x 1 M: top-1 443.5 / 445.6 -> 434.9 /
-    // 434.2 ms, top-2 493.2 / 492.6 -> 474.0 / 473.1 ms (r03 experiment 14).
-    constexpr bool DEFER = LL || K <= 2;    // LL: no list registers, every K runs top-1's schedule
-    constexpr bool LATE_READ = !LL && K == 2;
+    // The 12 fragments of the next tile's first slice stay in registers across the deferred fold (with LDS lists there are no
+    // list registers, so every K runs this schedule).  Same box, 262 144 x 1 M: top-1 443.5 / 445.6 -> 434.9 / 434.2 ms (r03
+    // experiment 14).
     bool pending = false;
     int n0_pending = 0;
     for (int s = 0; s < S; ++s) {
@@ -421,30 +329,11 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
         }
         SMI_LGKM0_BARRIER();
       };
-      if (LATE_READ && pending) {  // group 0, first slice of the next tile: no fragment is live across the fold
-        issue_and_wait();
+      read_frags();
+      issue_and_wait();
+      if (pending) {  // group 0
         fold(n0_pending);
         pending = false;
-        // The reads follow this interval's LDS-DMA issue: as C++ loads each would get `s_waitcnt vmcnt(0)` from hipcc's alias
-        // tracking (gemm.hip) and wait for the slice that was just requested.  One asm statement issues and retires them.
-        const unsigned wa = (unsigned)(size_t)(slot + woff), xa = (unsigned)(size_t)(slot + xoff);
-        asm volatile(
-            "ds_read_b128 %0, %12\n\tds_read_b128 %1, %12 offset:1024\n\tds_read_b128 %2, %12 offset:2048\n\t"
-            "ds_read_b128 %3, %12 offset:3072\n\tds_read_b128 %4, %13\n\tds_read_b128 %5, %13 offset:1024\n\t"
-            "ds_read_b128 %6, %13 offset:2048\n\tds_read_b128 %7, %13 offset:3072\n\tds_read_b128 %8, %13 offset:4096\n\t"
-            "ds_read_b128 %9, %13 offset:5120\n\tds_read_b128 %10, %13 offset:6144\n\tds_read_b128 %11, %13 offset:7168\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(fw[0]), "=&v"(fw[1]), "=&v"(fw[2]), "=&v"(fw[3]), "=&v"(fx[0]), "=&v"(fx[1]), "=&v"(fx[2]), "=&v"(fx[3]),
-              "=&v"(fx[4]), "=&v"(fx[5]), "=&v"(fx[6]), "=&v"(fx[7])
-            : "v"(wa), "v"(xa)
-            : "memory");
-      } else {
-        read_frags();
-        issue_and_wait();
-        if (DEFER && pending) {  // top-1, group 0
-          fold(n0_pending);
-          pending = false;
-        }
       }
       __builtin_amdgcn_sched_barrier(0);
       __builtin_amdgcn_s_setprio(1);
@@ -469,24 +358,16 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
       SMI_BARRIER();
       if (++k == nt) {
         k = 0;
-        if constexpr (DEFER) {
-          if (wr == 0) {
-            pending = true;
-            n0_pending = n0;
-          } else {
-            fold(n0);
-          }
+        if (wr == 0) {
+          pending = true;
+          n0_pending = n0;
         } else {
-#ifdef SMI_XSIM_TRACE
           fold(n0);
-#else
-          XS_FOLD(n0);  // (!LL, K = 4: the macro, not the lambda -- 76 bytes of spills otherwise)
-#endif
         }
         n0 += G2_BN;
       }
     }
-    if (DEFER && pending) fold(n0_pending);
+    if (pending) fold(n0_pending);
 #ifdef SMI_XSIM_TRACE
     if (lane == 0 && (wave == 0 || wave == 4) && blockIdx.x < 256) {
       unsigned long long* o = xs_trace_buf + (blockIdx.x * 2 + wr) * 4;
@@ -510,50 +391,50 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
         pi[o + j] = (int)(0xffffffffu - (uint32_t)key);
       }
     }
-    return;
-  }
-  // a row's candidates sit in the 4 lane groups (kg) of 4 column waves: join the lane groups with
-  // xor-shuffles (both partners end with the merged list), then the 4 waves through LDS
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi) {
-#pragma unroll
-    for (int step = 16; step <= 32; step <<= 1) {
-      float os[KR];
-      int oi[KR];
-#pragma unroll
-      for (int j = 0; j < KR; ++j) {
-        os[j] = __shfl_xor(best[mi].s[j], step, 64);
-        oi[j] = __shfl_xor(best[mi].i[j], step, 64);
-      }
-#pragma unroll
-      for (int j = 0; j < KR; ++j) best[mi].push(os[j], oi[j]);
-    }
-  }
-  __syncthreads();
-  float* ls = (float*)smem;  // [256 rows][4 waves][K]
-  int* li = (int*)(smem + 256 * 4 * K * 4);
-  if (kg == 0) {
+  } else {
+    // a row's candidates sit in the 4 lane groups (kg) of 4 column waves: join the lane groups with
+    // xor-shuffles (both partners end with the merged list), then the 4 waves through LDS
 #pragma unroll
     for (int mi = 0; mi < 8; ++mi) {
-      const int row = wr * 128 + mi * 16 + l15;
 #pragma unroll
-      for (int j = 0; j < KR; ++j) {
-        ls[(row * 4 + wc) * K + j] = best[mi].s[j];
-        li[(row * 4 + wc) * K + j] = best[mi].i[j];
+      for (int step = 16; step <= 32; step <<= 1) {
+        float os[K];
+        int oi[K];
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          os[j] = __shfl_xor(best[mi].s[j], step, 64);
+          oi[j] = __shfl_xor(best[mi].i[j], step, 64);
+        }
+#pragma unroll
+        for (int j = 0; j < K; ++j) best[mi].push(os[j], oi[j]);
       }
     }
-  }
-  __syncthreads();
-  if (threadIdx.x < 256) {
-    const int row = threadIdx.x;
-    TopK<K> t;
-    t.init();
-    for (int c = 0; c < 4 * K; ++c) t.push(ls[row * 4 * K + c], li[row * 4 * K + c]);
-    const size_t o = ((size_t)chunk * nx_pad + m0 + row) * K;
+    __syncthreads();
+    float* ls = (float*)smem;  // [256 rows][4 waves][K]
+    int* li = (int*)(smem + 256 * 4 * K * 4);
+    if (kg == 0) {
 #pragma unroll
-    for (int j = 0; j < K; ++j) {
-      ps[o + j] = t.s[j];
-      pi[o + j] = t.i[j];
+      for (int mi = 0; mi < 8; ++mi) {
+        const int row = wr * 128 + mi * 16 + l15;
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+          ls[(row * 4 + wc) * K + j] = best[mi].s[j];
+          li[(row * 4 + wc) * K + j] = best[mi].i[j];
+        }
+      }
+    }
+    __syncthreads();
+    if (threadIdx.x < 256) {
+      const int row = threadIdx.x;
+      TopK<K> t;
+      t.init();
+      for (int c = 0; c < 4 * K; ++c) t.push(ls[row * 4 * K + c], li[row * 4 * K + c]);
+      const size_t o = ((size_t)chunk * nx_pad + m0 + row) * K;
+#pragma unroll
+      for (int j = 0; j < K; ++j) {
+        ps[o + j] = t.s[j];
+        pi[o + j] = t.i[j];
+      }
     }
   }
 }
@@ -757,28 +638,12 @@ hipError_t launch_margin_select(const float* fs, const int32_t* fi, int64_t nx, 
 static int xsim_chunks(int64_t nty) { return (int)(nty < 8 ? nty : 8); }
 static int round_k(int k) { return k <= 1 ? 1 : (k <= 2 ? 2 : (k <= 4 ? 4 : 8)); }
 
-// SMI_XSIM_TM=0: mine on the row-major normalised matrices (rounds 1-2) instead of tile-major copies -- A/B switch
-static bool xsim_tm() {
-  return tune(TUNE_XSIM_TM, 1) != 0;
-}
-// SMI_XSIM_LL=0: per-lane top-k lists in registers (rounds 1-3; k = 8 then runs on the 128x128 engine) instead of the
-// per-row lists in LDS -- A/B switch (the workspace formula does not depend on it)
-static bool xsim_ll() {
-  return tune(TUNE_XSIM_LL, 1) != 0;
-}
-// top-1 keeps its list in registers (16 VGPRs, no pressure there: 436.7 vs 439.6 ms with LDS lists at 262 144 x 1 M); k >= 2
-// run on LDS lists: 475.1 -> 450.0 ms (k = 2), 545.7 -> 454.3 (k = 4), 657.9 -> 484.2 (k = 8, which the register version could
-// only run on the 128x128 engine) -- same box, identical indices and scores (profiles/r04_experiments.txt, experiment 2)
-static bool xsim_use_ll(int K) { return K >= 2 && xsim_ll(); }
-static bool xsim_on_256(int K) { return K <= 4 || xsim_ll(); }
 // per-chunk partial lists: [chunks][nx_pad][K] scores + indices
 static size_t xsim_lists_bytes(int64_t nx_pad, int64_t ny_pad, int K) {
   return (size_t)xsim_chunks(ny_pad / GT_BN) * nx_pad * K * 8;
 }
-// ... followed (256x256 engine) by the tile-major copies of Xn and Yn
-// The formula does NOT depend on the tuning switches (XSIM_LL decides whether k = 8 runs on the 256x256 engine and therefore
-// whether the copies are written): it is the upper bound over their states, so a switch set by another host thread between a
-// caller's workspace query and its smi_xsim_topk can never make xsim_run write past the size the API validated.
+// ... followed by the tile-major copies of Xn and Yn.  The formula depends on the shapes alone: what a caller queried is what
+// xsim_run writes, whatever another host thread does to the tuning switches in between.
 size_t xsim_workspace_bytes(int64_t nx_pad, int64_t ny_pad, int k, int d) {
   const int K = round_k(k);
   const size_t tm = (size_t)(nx_pad + ny_pad) * d * sizeof(f16);
@@ -789,80 +654,34 @@ template <int K>
 static hipError_t xsim_run(const f16* Xn, int64_t nx, int64_t nx_pad, const f16* Yn, int64_t ny,
                            int64_t ny_pad, int d, int k, int64_t y_off, int32_t* idx, float* score,
                            void* ws, hipStream_t stream) {
+  // 256x256 tiles, continuous slice stream; LDS above the ring: the row lists (K >= 2) or the row thresholds (K = 1)
+  constexpr int lds = G2_LDS_BYTES + (K >= 2 ? 256 * K * 8 : 4096);
   static DeviceOnce attr_done;
   if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)xsim_tile_kernel<K>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, GT_LDS_BYTES);
+    hipError_t e = hipFuncSetAttribute((const void*)xsim_tile256_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return e;
     attr_done.set();
   }
   float* ps = (float*)ws;
-  hipError_t e;
-  int nchunks;
-  if (xsim_on_256(K)) {
-    // 256x256 tiles, continuous slice stream
-    const bool ll = xsim_use_ll(K);
-    constexpr int lds_ll = G2_LDS_BYTES + 256 * K * 8, lds_reg = G2_LDS_BYTES + 4096;
-    static DeviceOnce attr256_done;
-    if (!attr256_done.done()) {
-      e = hipFuncSetAttribute((const void*)xsim_tile256_kernel<K, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_ll);
-      if (e != hipSuccess) return e;
-      e = hipFuncSetAttribute((const void*)xsim_tile256_kernel<K, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_ll);
-      if (e != hipSuccess) return e;
-      if constexpr (K <= 4) {
-        e = hipFuncSetAttribute((const void*)xsim_tile256_kernel<K, true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_reg);
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute((const void*)xsim_tile256_kernel<K, false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_reg);
-        if (e != hipSuccess) return e;
-      }
-      attr256_done.set();
-    }
-    const int ntx = (int)(nx_pad / G2_BM), nty = (int)(ny_pad / G2_BN);
-    nchunks = xsim_chunks(nty);
-    const int tpc = (nty + nchunks - 1) / nchunks;
-    int* pi = (int*)((char*)ws + (size_t)nchunks * nx_pad * K * 4);
-    const f16* xa = Xn;
-    const f16* ya = Yn;
-    const bool tm = xsim_tm();
-    if (tm) {
-      // tile-major copies of both operands behind the partial lists (one pass over each: ~1.5 ms of the 1.8 s at 1 M x 1 M)
-      f16* xtm = (f16*)((char*)ws + xsim_lists_bytes(nx_pad, ny_pad, K));
-      f16* ytm = xtm + (size_t)nx_pad * d;
-      const f16* src[2] = {Xn, Yn};
-      f16* dst[2] = {xtm, ytm};
-      const int64_t rows[2] = {nx_pad, ny_pad};
-      for (int o = 0; o < 2; ++o)
-        for (int64_t r0 = 0; r0 < rows[o]; r0 += 65535LL * TM_ROWS) {  // grid.y limit of the pack kernel
-          const int64_t nr = std::min<int64_t>(rows[o] - r0, 65535LL * TM_ROWS);
-          e = launch_pack_tile_major(src[o] + r0 * d, dst[o] + r0 * d, (int)nr, d, 0, stream);
-          if (e != hipSuccess) return e;
-        }
-      xa = xtm;
-      ya = ytm;
-    }
-#define SMI_XSIM_LAUNCH(TMV, LLV, LDS)                                                                              \
-  hipLaunchKernelGGL((xsim_tile256_kernel<K, TMV, LLV>), dim3(ntx * nchunks), dim3(G2_THREADS), LDS, stream, xa, ya, d, \
-                     ntx, nty, nchunks, tpc, (int)ny, (int)nx_pad, ps, pi)
-    if (ll) {
-      if (tm) SMI_XSIM_LAUNCH(true, true, lds_ll);
-      else SMI_XSIM_LAUNCH(false, true, lds_ll);
-    } else {
-      if constexpr (K <= 4) {
-        if (tm) SMI_XSIM_LAUNCH(true, false, lds_reg);
-        else SMI_XSIM_LAUNCH(false, false, lds_reg);
-      }
-    }
-#undef SMI_XSIM_LAUNCH
-  } else {
-    const int ntx = (int)(nx_pad / GT_BM), nty = (int)(ny_pad / GT_BN);
-    nchunks = xsim_chunks(nty);
-    const int tpc = (nty + nchunks - 1) / nchunks;
-    int* pi = (int*)((char*)ws + (size_t)nchunks * nx_pad * K * 4);
-    hipLaunchKernelGGL(xsim_tile_kernel<K>, dim3(ntx * nchunks), dim3(GT_THREADS), GT_LDS_BYTES,
-                       stream, Xn, Yn, d, ntx, nty, nchunks, tpc, (int)ny, (int)nx_pad, ps, pi);
-  }
+  const int ntx = (int)(nx_pad / G2_BM), nty = (int)(ny_pad / G2_BN);
+  const int nchunks = xsim_chunks(nty);
+  const int tpc = (nty + nchunks - 1) / nchunks;
   int* pi = (int*)((char*)ws + (size_t)nchunks * nx_pad * K * 4);
-  e = hipGetLastError();
+  // tile-major copies of both operands behind the partial lists (one pass over each: ~1.5 ms of the 1.8 s at 1 M x 1 M)
+  f16* xtm = (f16*)((char*)ws + xsim_lists_bytes(nx_pad, ny_pad, K));
+  f16* ytm = xtm + (size_t)nx_pad * d;
+  const f16* src[2] = {Xn, Yn};
+  f16* dst[2] = {xtm, ytm};
+  const int64_t rows[2] = {nx_pad, ny_pad};
+  for (int o = 0; o < 2; ++o)
+    for (int64_t r0 = 0; r0 < rows[o]; r0 += 65535LL * TM_ROWS) {  // grid.y limit of the pack kernel
+      const int64_t nr = std::min<int64_t>(rows[o] - r0, 65535LL * TM_ROWS);
+      hipError_t e = launch_pack_tile_major(src[o] + r0 * d, dst[o] + r0 * d, (int)nr, d, 0, stream);
+      if (e != hipSuccess) return e;
+    }
+  hipLaunchKernelGGL(xsim_tile256_kernel<K>, dim3(ntx * nchunks), dim3(G2_THREADS), lds, stream, xtm, ytm, d, ntx, nty,
+                     nchunks, tpc, (int)ny, (int)nx_pad, ps, pi);
+  hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(xsim_merge_kernel<K>, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, stream,
                      ps, pi, nchunks, nx, (int)nx_pad, k, y_off, idx, score);

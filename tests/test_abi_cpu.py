@@ -124,3 +124,17 @@ def test_tuning_registry_and_no_environment_reads(monkeypatch):
     monkeypatch.setenv("SMI_LONE_KS", "four")
     with pytest.raises(RuntimeError, match="integers"):
         _lib._forward_env_switches(lib)
+
+
+def test_every_tuning_switch_has_a_live_site(lib):
+    """A registry entry without a `tune(TUNE_<NAME>, ...)` site is a switch that does nothing (the weight-prefetch switch had
+    become one in one of its two files); a retired switch is refused like any unknown name."""
+    from sonar_amd import _lib
+
+    names = _lib.tuning_names()
+    assert len(names) == 21, names
+    csrc = pathlib.Path(ROOT) / "sonar_amd" / "csrc"
+    code = "\n".join(p.read_text() for p in sorted(csrc.iterdir()) if p.suffix in (".hip", ".hpp", ".cpp"))
+    for name in names:
+        assert re.search(rf"\btune\(TUNE_{name}\b", code), name
+    assert lib.smi_tuning_set(b"XSIM_TM", 0) != 0 and b"XSIM_TM" in lib.smi_last_error()

@@ -1,4 +1,4 @@
-"""xsim mining time for one (nx, ny) under the SMI_XSIM_* development knobs (read once per process)."""
+"""xsim mining time for one (nx, ny, k)."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,5 +20,5 @@ for _ in range(3):
     torch.cuda.synchronize()
     ts.append(time.perf_counter() - t0)
 t = min(ts)
-print(f"xsim nx={nx} ny={ny} k={k} LL={os.environ.get('SMI_XSIM_LL','1')} TM={os.environ.get('SMI_XSIM_TM','1')}: "
+print(f"xsim nx={nx} ny={ny} k={k}: "
       f"{t*1e3:.1f} ms  {nx*ny/t:.3e} pairs/s  {nx*ny*2048/t/1e12:.0f} TFLOP/s  checksum {int(i.sum())} score-sum {float(s.double().sum()):.6f}", flush=True)
