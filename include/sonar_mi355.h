@@ -291,7 +291,30 @@ int smi_text_decoder_generate(smi_text_decoder* dec, const void* emb, int32_t em
                               const int64_t* prompt, int32_t prompt_len, const smi_beam_search_params* params,
                               int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream);
 
-/* Decision margins of the LAST smi_text_decoder_generate call on this handle: out_margins device fp32
+/* smi_text_decoder_generate with one prompt PER SENTENCE: different target languages in one call, or forced prefixes that
+ * differ from sentence to sentence (fairseq2's `prompt_seqs` [n, P] with a padding mask).  prompts: HOST int64
+ * [n, prompt_stride], left-aligned; prompt_lens: HOST int32 [n], 1 <= prompt_lens[s] <= prompt_stride; entries past a
+ * sentence's length are not read.  Sentence s returns exactly what smi_text_decoder_generate returns for it when called
+ * with the same n embeddings and the one prompt prompts[s]: its result does not depend on the other sentences' prompts.
+ * Every sentence sits at the same position each step; sentence s is forced to prompts[s][step] while step <
+ * prompt_lens[s] (those log-probabilities count towards its score) and free afterwards.
+ * How the length fields are read here -- they cannot carry per-sentence values:
+ *   params->max_seq_len  the model-side cap of prompt + generated tokens, in [2, the decoder's max_seq_len];
+ *   params->min_seq_len  not read;
+ *   gen_cap (>= 1)       most generated tokens per sentence:  max_len_s = min(prompt_lens[s] + gen_cap, params->max_seq_len);
+ *   min_gen_len (>= 0)   fewest:                              min_len_s = min(prompt_lens[s] + min_gen_len, max_len_s).
+ * EOS is blocked while step < min_len_s and forced at step == max_len_s - 1; unk_penalty, the step processors and the
+ * decision margins act on a sentence's own free steps.  A sentence with max_len_s <= prompt_lens[s], or a prompt token
+ * outside the vocabulary, fails the call with SMI_ERR_INVALID_ARG naming the row.
+ * Outputs as smi_text_decoder_generate, the row length of out_tokens being W = max over s of max_len_s:
+ * out_tokens int32 [n, beam, W], sentence s's tokens after ITS prompt, -1 padded.  A call whose prompts are all equal runs
+ * as the one-prompt call, launch for launch. */
+int smi_text_decoder_generate_prompts(smi_text_decoder* dec, const void* emb, int32_t emb_dtype, int32_t n,
+                                      const int64_t* prompts, int32_t prompt_stride, const int32_t* prompt_lens,
+                                      int32_t gen_cap, int32_t min_gen_len, const smi_beam_search_params* params,
+                                      int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream);
+
+/* Decision margins of the LAST smi_text_decoder_generate / smi_text_decoder_generate_prompts call on this handle: out_margins device fp32
  * [n, 2].  [s][0] = the smallest gap, over all free decoding steps of sentence s, between neighbouring
  * entries of the sorted beam x vocab candidate list among the candidates the beam rules consumed plus
  * the first one they did not (log-prob units; for beam_size 1 this is the greedy top-1 / top-2 margin);
@@ -402,6 +425,15 @@ typedef struct smi_sampling_params {
 int smi_text_decoder_sample(smi_text_decoder* dec, const void* emb, int32_t emb_dtype, int32_t n,
                             const int64_t* prompt, int32_t prompt_len, const smi_sampling_params* params,
                             int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream);
+
+/* smi_text_decoder_sample with one prompt per sentence: the prompt triple, gen_cap / min_gen_len and the reading of
+ * params->max_seq_len (the model-side cap) / params->min_seq_len (not read) are those of smi_text_decoder_generate_prompts;
+ * out_tokens int32 [n, W].  The draw of a sentence depends on (seed, sentence, step) only, so sentence s returns what
+ * smi_text_decoder_sample returns for it with the one prompt prompts[s]. */
+int smi_text_decoder_sample_prompts(smi_text_decoder* dec, const void* emb, int32_t emb_dtype, int32_t n,
+                                    const int64_t* prompts, int32_t prompt_stride, const int32_t* prompt_lens,
+                                    int32_t gen_cap, int32_t min_gen_len, const smi_sampling_params* params,
+                                    int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream);
 
 /* The filter + draw of one sampling step on given logits (device fp32 [rows, ld], ld % 4 == 0,
  * ld >= vocab rounded up to 4, vocab <= 2^18), exposed for the parity tests: z device uint64 [rows]

@@ -304,6 +304,8 @@ SYMBOLS = {
     "smi_text_decoder_score": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _i32, C.POINTER(_i32), _vp, _vp]),
     "smi_text_decoder_generate": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), _i32,
                                             C.POINTER(smi_beam_search_params), _vp, _vp, _vp, _vp]),
+    "smi_text_decoder_generate_prompts": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i32,
+                                                    C.POINTER(smi_beam_search_params), _vp, _vp, _vp, _vp]),
     "smi_text_decoder_last_margins": (C.c_int, [_vp, _vp, _i32, _vp]),
     "smi_text_decoder_set_chains": (C.c_int, [_vp, _i32]),
     "smi_text_decoder_set_beam_logits_dtype": (C.c_int, [_vp, _i32]),
@@ -315,6 +317,8 @@ SYMBOLS = {
                                          _vp, _i32, C.POINTER(smi_step_processors), _vp, _vp, _vp, _vp, _vp, _vp]),
     "smi_text_decoder_sample": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), _i32,
                                           C.POINTER(smi_sampling_params), _vp, _vp, _vp, _vp]),
+    "smi_text_decoder_sample_prompts": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), _i32, C.POINTER(_i32), _i32, _i32,
+                                                  C.POINTER(smi_sampling_params), _vp, _vp, _vp, _vp]),
     "smi_sample_rows": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _f32, _f32, _i32, _i32, _i32, _i32, _f32, _vp,
                                   _vp, _vp, _vp, _vp, _vp]),
     "smi_speech_encoder_create": (C.c_int, [C.POINTER(smi_speech_encoder_config),

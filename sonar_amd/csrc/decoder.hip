@@ -545,13 +545,18 @@ __device__ __forceinline__ void vsel_normaliser(const float* __restrict__ tile_m
   }
 }
 
+// TABLE (per-sentence prompts, PromptTableDev): the row's block_eos / unk_penalty follow its own sentence's mode at step_nr,
+// and a row whose sentence is forced there (prompt token, forced EOS, past its cap) leaves after its normaliser, as a k2 = 0
+// launch does for every row.  A free row's candidates are formed exactly as without the table.
+template <bool TABLE>
 __global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restrict__ logits, int ldl, int f16_tm, int vocab,
                                                            const float* __restrict__ tile_max,
                                                            const float* __restrict__ tile_sum, int ntiles,
                                                            int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx, int unk_idx,
                                                            float unk_penalty, int block_eos,
                                                            float* __restrict__ pmax, float* __restrict__ psum,
-                                                           float* __restrict__ pval, int* __restrict__ pidx) {
+                                                           float* __restrict__ pval, int* __restrict__ pidx,
+                                                           PromptTableDev table, int group, int step_nr) {
   __shared__ float s_f[4];
   __shared__ int s_sel[VSEL_SLOTS];
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -559,6 +564,11 @@ __global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restri
   float m[TPT];
   vsel_normaliser(tile_max, tile_sum, ntiles, stat_rows, pmax, psum, m, s_f);
   if (k2 == 0) return;
+  if constexpr (TABLE) {
+    const PromptRowMode md = prompt_row_mode(table, row / group, step_nr);
+    if (!md.free_step) return;
+    block_eos = md.block_eos;
+  }
   // The two selections below are k2 rounds of "workgroup-wide maximum of a sortable key, then retire the winner".  The kernel is
   // VALU-bound (1280 rows x 4 waves on 1024 SIMDs: a round used to rebuild and compare the keys of all of a thread's slots,
   // ~230 VALU instructions, 20 rounds), so every thread now keeps its keys and its current best: a round is one wave reduction
@@ -654,11 +664,13 @@ __global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restri
 // the workgroup-wide arg-max; banned columns are skipped through a per-group 256-bit mask per tile.
 constexpr int VSB_MAX_BANS = kStepProcMaxLen + kStepProcMaxBanned;
 
+template <bool TABLE>
 __global__ __launch_bounds__(256) void vocab_select_banned_kernel(
     const float* __restrict__ logits, int ldl, int f16_tm, int vocab, const float* __restrict__ tile_max,
     const float* __restrict__ tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx,
     int unk_idx, float unk_penalty, int block_eos, const int32_t* __restrict__ hist, int hist_stride, int hist_len,
-    StepProcDev proc, float* __restrict__ pmax, float* __restrict__ psum, float* __restrict__ pval, int* __restrict__ pidx) {
+    StepProcDev proc, float* __restrict__ pmax, float* __restrict__ psum, float* __restrict__ pval, int* __restrict__ pidx,
+    PromptTableDev table, int group, int step_nr) {
   __shared__ float s_f[4];
   __shared__ int32_t s_seq[kStepProcMaxLen];
   __shared__ int32_t s_ban[VSB_MAX_BANS];
@@ -674,6 +686,11 @@ __global__ __launch_bounds__(256) void vocab_select_banned_kernel(
   float m[TPT];
   vsel_normaliser(tile_max, tile_sum, ntiles, stat_rows, pmax, psum, m, s_f);
   if (k2 == 0) return;
+  if constexpr (TABLE) {  // as vocab_select_kernel<true>
+    const PromptRowMode md = prompt_row_mode(table, row / group, step_nr);
+    if (!md.free_step) return;
+    block_eos = md.block_eos;
+  }
   // ---- B0. the row's sequence into LDS, empty ban list / dirty bitmap / slot map
   const int32_t* h = hist + (size_t)row * hist_stride;
   for (int i = tid; i < hist_len; i += 256) s_seq[i] = h[i];
@@ -813,26 +830,40 @@ hipError_t launch_vocab_select_banned(const float* logits, int ldl, int f16_tm, 
                                       const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx,
                                       int eos_idx, int unk_idx, float unk_penalty, int block_eos, const int32_t* hist,
                                       int hist_stride, int hist_len, const StepProcDev& proc, float* pmax, float* psum,
-                                      float* pval, int* pidx, hipStream_t stream) {
+                                      float* pval, int* pidx, hipStream_t stream, const PromptTableDev* table, int group,
+                                      int step_nr) {
   if (rows <= 0 || stat_rows < rows || ntiles <= 0 || ntiles > 2048 || k2 < 0 || k2 > VS_K2MAX || (int64_t)ntiles * 256 < vocab)
     return hipErrorInvalidValue;
+  if (table && (!table->tok || !table->len || group < 1)) return hipErrorInvalidValue;
   if (!hist || hist_len < 1 || hist_len > kStepProcMaxLen || hist_stride < hist_len || proc.num_banned < 0 ||
       proc.num_banned > kStepProcMaxBanned || (proc.num_banned > 0 && (!proc.tokens || !proc.offsets)))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vocab_select_banned_kernel, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
-                     tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, hist,
-                     hist_stride, hist_len, proc, pmax, psum, pval, pidx);
+  if (table)
+    hipLaunchKernelGGL(vocab_select_banned_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
+                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, hist,
+                       hist_stride, hist_len, proc, pmax, psum, pval, pidx, *table, group, step_nr);
+  else
+    hipLaunchKernelGGL(vocab_select_banned_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
+                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, hist,
+                       hist_stride, hist_len, proc, pmax, psum, pval, pidx, PromptTableDev{}, 1, 0);
   return hipGetLastError();
 }
 
 hipError_t launch_vocab_select(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
                                const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx,
                                int unk_idx, float unk_penalty, int block_eos, float* pmax, float* psum, float* pval,
-                               int* pidx, hipStream_t stream) {
+                               int* pidx, hipStream_t stream, const PromptTableDev* table, int group, int step_nr) {
   if (rows <= 0 || stat_rows < rows || ntiles <= 0 || ntiles > 2048 || k2 < 0 || k2 > VS_K2MAX || (int64_t)ntiles * 256 < vocab)
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(vocab_select_kernel, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max, tile_sum,
-                     ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, pmax, psum, pval, pidx);
+  if (table && (!table->tok || !table->len || group < 1)) return hipErrorInvalidValue;
+  if (table)
+    hipLaunchKernelGGL(vocab_select_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
+                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, pmax, psum,
+                       pval, pidx, *table, group, step_nr);
+  else
+    hipLaunchKernelGGL(vocab_select_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
+                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, pmax, psum,
+                       pval, pidx, PromptTableDev{}, 1, 0);
   return hipGetLastError();
 }
 
@@ -856,6 +887,8 @@ struct BeamState {
   float* margins;      // [n][2] smallest decision gap so far: {step candidates (log-prob), final ranking}
 };
 
+// TABLE (per-sentence prompts): prompt_len, forced_tok and max_len are those of the workgroup's own sentence.
+template <bool TABLE>
 __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const float* __restrict__ logits,
                                                         int ldl, int f16_tm, const float* __restrict__ pmax,
                                                         const float* __restrict__ psum,
@@ -864,7 +897,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
                                                         int beam, int k2, int pos, int prompt_len,
                                                         int forced_tok, int max_len, float inv_temp,
                                                         float len_penalty, int normalize, int eos_idx,
-                                                        int hist_stride) {
+                                                        int hist_stride, PromptTableDev table) {
   __shared__ float s_lse[8];
   __shared__ float c_val[8 * VS_K2MAX];
   __shared__ int c_tok[8 * VS_K2MAX];
@@ -875,6 +908,12 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
   const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int base = s * beam;
   const int step_nr = pos + 1;  // index of the token chosen now
+  if constexpr (TABLE) {
+    const PromptRowMode md = prompt_row_mode(table, s, step_nr);
+    prompt_len = md.plen;
+    forced_tok = md.forced_tok;
+    max_len = md.max_len;
+  }
   if (st.done[s]) {  // keep the rows inert
     if (tid < beam) {
       st.parent[base + tid] = base + tid;
@@ -1131,9 +1170,14 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
 hipError_t launch_beam_step(const BeamStepArgs& a, hipStream_t stream) {
   BeamState st{a.tok, a.cum, a.nactive, a.done, a.ndone, a.parent, a.new_tok, a.new_cum,
                a.hist, a.fin_tok, a.fin_len, a.fin_score, a.fin_count, a.margins};
-  hipLaunchKernelGGL(beam_step_kernel, dim3(a.n), dim3(256), 0, stream, st, a.logits, a.ldl, a.logits_f16_tm, a.pmax,
-                     a.psum, a.pval, a.pidx, a.nchunks, a.beam, a.k2, a.pos, a.prompt_len, a.forced_tok,
-                     a.max_len, a.inv_temp, a.len_penalty, a.normalize, a.eos_idx, a.hist_stride);
+  if (a.table.tok)
+    hipLaunchKernelGGL(beam_step_kernel<true>, dim3(a.n), dim3(256), 0, stream, st, a.logits, a.ldl, a.logits_f16_tm, a.pmax,
+                       a.psum, a.pval, a.pidx, a.nchunks, a.beam, a.k2, a.pos, a.prompt_len, a.forced_tok,
+                       a.max_len, a.inv_temp, a.len_penalty, a.normalize, a.eos_idx, a.hist_stride, a.table);
+  else
+    hipLaunchKernelGGL(beam_step_kernel<false>, dim3(a.n), dim3(256), 0, stream, st, a.logits, a.ldl, a.logits_f16_tm, a.pmax,
+                       a.psum, a.pval, a.pidx, a.nchunks, a.beam, a.k2, a.pos, a.prompt_len, a.forced_tok,
+                       a.max_len, a.inv_temp, a.len_penalty, a.normalize, a.eos_idx, a.hist_stride, a.table);
   return hipGetLastError();
 }
 
@@ -1176,9 +1220,11 @@ hipError_t launch_beam_reorder(const int32_t* parent, const int32_t* new_tok, co
 // ------------------------------------------------------------------------- small helpers
 __global__ void beam_init_kernel(int32_t* tok, float* cum, int32_t* nactive, int32_t* done,
                                  int32_t* ndone, int32_t* fin_count, int32_t* hist, int32_t* anc,
-                                 float* margins, int rows, int n, int stride, int first_tok) {
+                                 float* margins, int rows, int n, int stride, int first_tok,
+                                 const int32_t* __restrict__ first_toks, int first_stride, int beam) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < rows) {
+    if (first_toks) first_tok = first_toks[(size_t)(i / beam) * first_stride];
     tok[i] = first_tok;
     cum[i] = 0.f;
     hist[(size_t)i * stride] = first_tok;
@@ -1195,10 +1241,12 @@ __global__ void beam_init_kernel(int32_t* tok, float* cum, int32_t* nactive, int
 
 hipError_t launch_beam_init(int32_t* tok, float* cum, int32_t* nactive, int32_t* done, int32_t* ndone,
                             int32_t* fin_count, int32_t* hist, int32_t* anc, float* margins, int rows, int n,
-                            int stride, int first_tok, hipStream_t stream) {
+                            int stride, int first_tok, hipStream_t stream, const int32_t* first_toks, int first_stride,
+                            int beam) {
   const int total = rows > n ? rows : n;
   hipLaunchKernelGGL(beam_init_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, tok, cum, nactive,
-                     done, ndone, fin_count, hist, anc, margins, rows, n, stride, first_tok);
+                     done, ndone, fin_count, hist, anc, margins, rows, n, stride, first_tok, first_toks, first_stride,
+                     beam < 1 ? 1 : beam);
   return hipGetLastError();
 }
 

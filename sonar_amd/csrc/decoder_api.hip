@@ -51,7 +51,10 @@ struct DecWork {
   DevBuf anc[2], hist[2];
   DevBuf pmax, psum, pval, pidx;
   DevBuf tile_max, tile_sum;  // logits-GEMM tile statistics [rows_pad][vocab_pad / 256]
-  DevBuf prompt_dev;          // sampling under step processors: the prompt, int32
+  // the call's prompt(s), int32.  One prompt: [prompt_len], read by sampling under step processors.  Per-sentence prompts
+  // (smi_text_decoder_*_prompts): ws[0] holds the whole call's table, tokens [n][stride] then lengths [n]; a chain reads its
+  // sentence group's slice of it
+  DevBuf prompt_dev;
   DevBuf sc_lens, sc_tgt, sc_bad, sc_cu;  // teacher-forced scoring: lengths, row targets, bad-id flag, [0, seq, 2 seq, ...]
   int kv_positions = 0;       // positions per layer in the current kv allocation
   bool chained = false;       // this call runs next to other chains: per-launch tile choices differ (decoder_step)
@@ -366,14 +369,104 @@ int record_table_use(DecWork& S, hipStream_t stream) {
   return SMI_OK;
 }
 
+// Per-sentence prompts of a call or of one sentence group of it: the host copy the launch schedule is
+// planned from, and the device table the kernels read.
+struct PromptSpec {
+  const int64_t* tok;   // host [n][stride], left-aligned
+  const int32_t* len;   // host [n]
+  int stride;
+  int gen_cap, min_gen, model_max;
+  int width;            // max over the CALL's sentences of max_len_s: the output row length
+  PromptTableDev dev;   // the same n sentences on the device
+  int max_len(int s) const { return std::min(len[s] + gen_cap, model_max); }
+  int min_len(int s) const { return std::min(len[s] + min_gen, max_len(s)); }
+  PromptSpec slice(int s0) const {
+    PromptSpec q = *this;
+    q.tok += (size_t)s0 * stride;
+    q.len += s0;
+    q.dev.tok += (size_t)s0 * stride;
+    q.dev.len += s0;
+    return q;
+  }
+};
+
+// What the n sentences of a group have in common at each step: where every sentence is in the same mode the step keeps
+// the one-prompt launches (scalar mode), and only the steps in between read the table.
+struct PromptPlan {
+  int pmin = 0, pmax = 0, minlen_lo = 0, minlen_hi = 0, maxlen_lo = 0, maxlen_hi = 0;
+  PromptPlan() = default;  // a one-prompt call: not consulted
+  PromptPlan(const PromptSpec& ps, int n) {
+    pmin = minlen_lo = maxlen_lo = INT32_MAX;
+    pmax = minlen_hi = maxlen_hi = 0;
+    for (int s = 0; s < n; ++s) {
+      pmin = std::min(pmin, (int)ps.len[s]); pmax = std::max(pmax, (int)ps.len[s]);
+      minlen_lo = std::min(minlen_lo, ps.min_len(s)); minlen_hi = std::max(minlen_hi, ps.min_len(s));
+      maxlen_lo = std::min(maxlen_lo, ps.max_len(s)); maxlen_hi = std::max(maxlen_hi, ps.max_len(s));
+    }
+  }
+  bool all_forced(int step_nr) const { return step_nr < pmin; }
+  bool all_force_eos(int step_nr) const { return step_nr >= pmax && maxlen_lo == maxlen_hi && step_nr == maxlen_lo - 1; }
+  // every sentence on a free step, and all of them on the same side of their min_len
+  bool all_free(int step_nr, bool* block_eos) const {
+    if (step_nr < pmax || step_nr >= maxlen_lo - 1) return false;
+    if (step_nr < minlen_lo) { *block_eos = true; return true; }
+    if (step_nr >= minlen_hi) { *block_eos = false; return true; }
+    return false;
+  }
+  bool uniform_prompt_len() const { return pmin == pmax; }
+};
+
+// checks the prompts of a *_prompts call, fills `tab` (int32 tokens [n][stride], then lengths [n]) and *width
+int check_prompts(const smi_text_decoder_config& c, int n, const int64_t* prompts, int stride, const int32_t* lens, int gen_cap,
+                  int min_gen, int model_max, std::vector<int32_t>* tab, int* width) {
+  if (stride < 1) return fail(SMI_ERR_INVALID_ARG, "prompt_stride %d must be positive", stride);
+  if (gen_cap < 1 || min_gen < 0) return fail(SMI_ERR_INVALID_ARG, "gen_cap %d must be >= 1 and min_gen_len %d >= 0", gen_cap, min_gen);
+  if (model_max > c.max_seq_len || model_max < 2)
+    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in [2, model max %d]", model_max, c.max_seq_len);
+  tab->assign((size_t)n * stride + n, 0);
+  *width = 0;
+  for (int s = 0; s < n; ++s) {
+    const int pl = lens[s];
+    if (pl < 1 || pl > stride) return fail(SMI_ERR_INVALID_ARG, "prompt_lens[%d] = %d outside [1, prompt_stride %d]", s, pl, stride);
+    if (std::min(pl + gen_cap, model_max) <= pl)
+      return fail(SMI_ERR_INVALID_ARG, "row %d: max_seq_len %d leaves no room for generation after its prompt of %d tokens", s,
+                  model_max, pl);
+    for (int i = 0; i < pl; ++i) {
+      const int64_t t = prompts[(size_t)s * stride + i];
+      if (t < 0 || t >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "row %d: prompt token %lld out of range", s, (long long)t);
+      (*tab)[(size_t)s * stride + i] = (int32_t)t;
+    }
+    (*tab)[(size_t)n * stride + s] = pl;
+    *width = std::max(*width, std::min(pl + gen_cap, model_max));
+  }
+  return SMI_OK;
+}
+
+// the call's table -> D->ws[0].prompt_dev (stream-ordered upload, finished on return: `tab` is the caller's)
+int upload_prompt_table(smi_text_decoder* D, const std::vector<int32_t>& tab, int n, int stride, hipStream_t stream,
+                        PromptTableDev* dev) {
+  DevBuf& b = D->ws[0].prompt_dev;
+  HIP_TRY(b.reserve(tab.size() * 4));
+  HIP_TRY(hipMemcpyAsync(b.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  dev->tok = b.as<int32_t>();
+  dev->len = b.as<int32_t>() + (size_t)n * stride;
+  dev->stride = stride;
+  return SMI_OK;
+}
+
 // One decode chain: beam search for the n sentences of `emb` on workspace S and stream `stream` (the whole call, or
-// one sentence group of a split call).  margins: device [n][2].
+// one sentence group of a split call).  margins: device [n][2].  ps: the group's per-sentence prompts, or null: every
+// sentence starts with `prompt` (bp->max_seq_len / min_seq_len then hold for all of them).
 int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dtype, int n, const int64_t* prompt,
-                   int prompt_len, const smi_beam_search_params* bp, int32_t* out_tokens, int32_t* out_lens,
-                   float* out_scores, float* margins, hipStream_t stream) {
+                   int prompt_len, const PromptSpec* ps, const smi_beam_search_params* bp, int32_t* out_tokens,
+                   int32_t* out_lens, float* out_scores, float* margins, hipStream_t stream) {
   const smi_text_decoder_config& c = D->cfg;
   const int beam = bp->beam_size;
-  const int max_len = bp->max_seq_len, min_len = bp->min_seq_len;
+  const PromptPlan plan = ps ? PromptPlan(*ps, n) : PromptPlan();
+  // per-sentence prompts: the loop runs to the group's longest cap, the output rows are as wide as the call's
+  const int max_len = ps ? plan.maxlen_hi : bp->max_seq_len, min_len = bp->min_seq_len;
+  const int out_stride = ps ? ps->width : max_len;
 
   const int rows = n * beam;
   const int rows_pad = (int)round_up(rows, 256), n_pad = (int)round_up(n, 256);
@@ -408,7 +501,7 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
   HIP_TRY(launch_beam_init(S.tok.as<int32_t>(), S.cum.as<float>(), S.nactive.as<int32_t>(),
                            S.done.as<int32_t>(), S.ndone.as<int32_t>(), S.fin_count.as<int32_t>(),
                            S.hist[0].as<int32_t>(), S.anc[0].as<int32_t>(), margins, rows, n, stride,
-                           (int)prompt[0], stream));
+                           ps ? 0 : (int)prompt[0], stream, ps ? ps->dev.tok : nullptr, ps ? ps->dev.stride : 0, beam));
   const float inv_temp = 1.0f / bp->temperature;
   // fp16 logits: the handle's setting (SMI_DEC_LOGITS_F16 = 0 / 1 overrides it: A/B runs), MFMA path with the tile-major table
   const int lf_env = tune(TUNE_DEC_LOGITS_F16, -1);
@@ -423,23 +516,35 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     if (int rc = decoder_step(D, S, rows, rows_pad, beam, n_pad, pos, S.anc[cur].as<int32_t>(), stride, s, inv_temp,
                               logits_f16, slab_f16))
       return rc;
-    const bool forced_prompt = step_nr < prompt_len;
-    const bool force_eos = !forced_prompt && step_nr == max_len - 1;
+    // The step's mode.  One prompt: the same for every sentence.  Per-sentence prompts: where the plan finds every sentence
+    // in one mode the step is launched as a one-prompt step (scalar); the steps in between are `mixed` and the kernels take
+    // each sentence's mode from the table.
+    bool forced_prompt = step_nr < prompt_len;
+    bool force_eos = !forced_prompt && step_nr == max_len - 1;
+    bool block_eos = !forced_prompt && !force_eos && step_nr < min_len;
+    bool mixed = false;
+    if (ps) {
+      forced_prompt = plan.all_forced(step_nr);
+      force_eos = plan.all_force_eos(step_nr);
+      block_eos = false;
+      mixed = !forced_prompt && !force_eos && !plan.all_free(step_nr, &block_eos);
+    }
     // forced steps need only the softmax normaliser (the candidate is a given token): k2 = 0
     const bool free_step = !forced_prompt && !force_eos;
+    const PromptTableDev* sel_table = mixed ? &ps->dev : nullptr;
     // step processors act on the free steps only, on the row's sequence so far hist[cur][r][0 .. pos]
     if (free_step && proc.active())
       HIP_TRY(launch_vocab_select_banned(S.logits.as<float>(), (int)D->vocab_pad, logits_f16, rows, (int)c.vocab_size,
                                          S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, rows_pad, k2, inv_temp,
-                                         c.pad_idx, c.eos_idx, c.unk_idx, bp->unk_penalty, step_nr < min_len ? 1 : 0,
+                                         c.pad_idx, c.eos_idx, c.unk_idx, bp->unk_penalty, block_eos ? 1 : 0,
                                          S.hist[cur].as<int32_t>(), stride, pos + 1, proc, S.pmax.as<float>(),
-                                         S.psum.as<float>(), S.pval.as<float>(), S.pidx.as<int>(), s));
+                                         S.psum.as<float>(), S.pval.as<float>(), S.pidx.as<int>(), s, sel_table, beam, step_nr));
     else
       HIP_TRY(launch_vocab_select(S.logits.as<float>(), (int)D->vocab_pad, logits_f16, rows, (int)c.vocab_size,
                                   S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, rows_pad, free_step ? k2 : 0, inv_temp,
                                   c.pad_idx, c.eos_idx, c.unk_idx, free_step ? bp->unk_penalty : 0.f,
-                                  free_step && step_nr < min_len ? 1 : 0, S.pmax.as<float>(), S.psum.as<float>(),
-                                  S.pval.as<float>(), S.pidx.as<int>(), s));
+                                  block_eos ? 1 : 0, S.pmax.as<float>(), S.psum.as<float>(),
+                                  S.pval.as<float>(), S.pidx.as<int>(), s, sel_table, beam, step_nr));
     BeamStepArgs a{};
     a.tok = S.tok.as<int32_t>(); a.cum = S.cum.as<float>(); a.nactive = S.nactive.as<int32_t>();
     a.done = S.done.as<int32_t>(); a.ndone = S.ndone.as<int32_t>();
@@ -450,7 +555,12 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     a.logits = S.logits.as<float>(); a.ldl = (int)D->vocab_pad; a.logits_f16_tm = logits_f16;
     a.pmax = S.pmax.as<float>(); a.psum = S.psum.as<float>(); a.pval = S.pval.as<float>(); a.pidx = S.pidx.as<int>();
     a.nchunks = 1; a.n = n; a.beam = beam; a.k2 = k2; a.pos = pos; a.prompt_len = prompt_len;
-    a.forced_tok = forced_prompt ? (int)prompt[step_nr] : -1; a.max_len = max_len;
+    a.forced_tok = forced_prompt && !ps ? (int)prompt[step_nr] : -1; a.max_len = max_len;
+    if (ps) {
+      // prompts of one length: past them the sentences differ in nothing the beam step reads -- the one-prompt launch
+      if (plan.uniform_prompt_len() && step_nr >= plan.pmax) a.prompt_len = plan.pmax;
+      else a.table = ps->dev;
+    }
     a.inv_temp = inv_temp; a.len_penalty = bp->len_penalty; a.normalize = bp->normalize_scores;
     a.eos_idx = c.eos_idx; a.hist_stride = stride;
     HIP_TRY(launch_beam_step(a, s));
@@ -471,7 +581,7 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
       if (int rc = grow_kv(D, S, rows_pad, std::min(max_len, 2 * S.kv_positions), stream)) return rc;
     if (int rc = enqueue_step(pos, stream)) return rc;
     // every 8 steps: has every sentence collected its `beam` hypotheses?
-    const bool force_eos = step_nr >= prompt_len && step_nr == max_len - 1;
+    const bool force_eos = (ps || step_nr >= prompt_len) && step_nr == max_len - 1;
     if ((step_nr & 7) == 0 || force_eos) {
       int32_t nd = 0;
       HIP_TRY(hipMemcpyAsync(&nd, S.ndone.p, 4, hipMemcpyDeviceToHost, stream));
@@ -480,7 +590,7 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     }
   }
   HIP_TRY(launch_beam_output(S.fin_tok.as<int32_t>(), S.fin_len.as<int32_t>(), S.fin_score.as<float>(),
-                             S.fin_count.as<int32_t>(), n, beam, stride, max_len, out_tokens, out_lens, out_scores,
+                             S.fin_count.as<int32_t>(), n, beam, stride, out_stride, out_tokens, out_lens, out_scores,
                              margins, stream));
   if (proc.active())
     if (int rc = record_table_use(S, stream)) return rc;
@@ -767,25 +877,29 @@ int smi_text_decoder_score(smi_text_decoder* D, const void* emb, int32_t emb_dty
   return SMI_OK;
 }
 
-int smi_text_decoder_generate(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
-                              const int64_t* prompt, int32_t prompt_len, const smi_beam_search_params* bp,
-                              int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
-  if (!D || !emb || !prompt || !bp || !out_tokens || !out_lens || !out_scores)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (n <= 0 || prompt_len <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+}  // extern "C"
+
+namespace {
+
+int check_generate_args(const smi_text_decoder* D, const void* emb, int emb_dtype, int n, const smi_beam_search_params* bp,
+                        const void* out_tokens, const void* out_lens, const void* out_scores) {
+  if (!D || !emb || !bp || !out_tokens || !out_lens || !out_scores) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (n <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
   if (emb_dtype != SMI_F32 && emb_dtype != SMI_F16) return fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
-  const smi_text_decoder_config& c = D->cfg;
   const int beam = bp->beam_size;
   if (beam < 1 || beam > 8) return fail(SMI_ERR_UNSUPPORTED, "beam_size %d outside [1,8]", beam);
-  if (2 * beam >= c.vocab_size) return fail(SMI_ERR_UNSUPPORTED, "vocabulary too small for beam %d", beam);
-  const int max_len = bp->max_seq_len;
-  if (max_len > c.max_seq_len || max_len <= prompt_len)
-    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in (prompt_len %d, model max %d]", max_len, prompt_len,
-                c.max_seq_len);
+  if (2 * beam >= D->cfg.vocab_size) return fail(SMI_ERR_UNSUPPORTED, "vocabulary too small for beam %d", beam);
   if (!(bp->temperature > 0.f)) return fail(SMI_ERR_INVALID_ARG, "temperature must be positive");
-  for (int i = 0; i < prompt_len; ++i)
-    if (prompt[i] < 0 || prompt[i] >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "prompt token out of range");
-  hipStream_t stream = (hipStream_t)stream_v;
+  return SMI_OK;
+}
+
+// the checked call: one prompt (ps null; bp carries the lengths) or per-sentence prompts
+int generate_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, const int64_t* prompt, int prompt_len,
+                 const PromptSpec* ps, const smi_beam_search_params* bp, int32_t* out_tokens, int32_t* out_lens,
+                 float* out_scores, hipStream_t stream) {
+  const smi_text_decoder_config& c = D->cfg;
+  const int beam = bp->beam_size;
+  const int max_len = ps ? ps->width : bp->max_seq_len;  // the output row length
   HIP_TRY(D->margins.reserve((size_t)n * 2 * 4));
   D->margins_n = n;
   float* margins = D->margins.as<float>();
@@ -800,7 +914,7 @@ int smi_text_decoder_generate(smi_text_decoder* D, const void* emb, int32_t emb_
   const int chains = decode_chains(D, n, beam);
   if (chains <= 1) {
     D->ws[0].chained = false;
-    return generate_chain(D, D->ws[0], emb, emb_dtype, n, prompt, prompt_len, bp, out_tokens, out_lens, out_scores,
+    return generate_chain(D, D->ws[0], emb, emb_dtype, n, prompt, prompt_len, ps, bp, out_tokens, out_lens, out_scores,
                           margins, stream);
   }
   int dev = 0;
@@ -828,10 +942,12 @@ int smi_text_decoder_generate(smi_text_decoder* D, const void* emb, int32_t emb_
       hipError_t he = hipSetDevice(dev);
       if (he == hipSuccess) he = hipStreamWaitEvent(S.stream, D->fork_ev, 0);
       if (he != hipSuccess) rc = fail(SMI_ERR_HIP, "chain %d set-up: %s", g, hipGetErrorString(he));
-      if (rc == SMI_OK)
-        rc = generate_chain(D, S, (const char*)emb + (size_t)s0 * emb_row, emb_dtype, ng, prompt, prompt_len, bp,
-                            out_tokens + (size_t)s0 * beam * max_len, out_lens + (size_t)s0 * beam,
-                            out_scores + (size_t)s0 * beam, margins + 2 * (size_t)s0, S.stream);
+      if (rc == SMI_OK) {
+        const PromptSpec group = ps ? ps->slice(s0) : PromptSpec{};  // the table is sliced per sentence group
+        rc = generate_chain(D, S, (const char*)emb + (size_t)s0 * emb_row, emb_dtype, ng, prompt, prompt_len,
+                            ps ? &group : nullptr, bp, out_tokens + (size_t)s0 * beam * max_len,
+                            out_lens + (size_t)s0 * beam, out_scores + (size_t)s0 * beam, margins + 2 * (size_t)s0, S.stream);
+      }
       if (rc == SMI_OK && (he = hipEventRecord(S.done_ev, S.stream)) != hipSuccess)
         rc = fail(SMI_ERR_HIP, "chain %d: %s", g, hipGetErrorString(he));
       rcs[g] = rc;
@@ -851,6 +967,61 @@ int smi_text_decoder_generate(smi_text_decoder* D, const void* emb, int32_t emb_
     if (g * per < n)
       HIP_TRY(hipStreamWaitEvent(stream, D->ws[g].done_ev, 0));
   return SMI_OK;
+}
+
+// every sentence has the prompt of sentence 0: the call IS a one-prompt call
+bool prompts_all_equal(int n, const int64_t* prompts, int stride, const int32_t* lens) {
+  for (int s = 1; s < n; ++s) {
+    if (lens[s] != lens[0]) return false;
+    for (int i = 0; i < lens[0]; ++i)
+      if (prompts[(size_t)s * stride + i] != prompts[i]) return false;
+  }
+  return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smi_text_decoder_generate(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
+                              const int64_t* prompt, int32_t prompt_len, const smi_beam_search_params* bp,
+                              int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
+  if (!prompt) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (int rc = check_generate_args(D, emb, emb_dtype, n, bp, out_tokens, out_lens, out_scores)) return rc;
+  if (prompt_len <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  const smi_text_decoder_config& c = D->cfg;
+  const int max_len = bp->max_seq_len;
+  if (max_len > c.max_seq_len || max_len <= prompt_len)
+    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in (prompt_len %d, model max %d]", max_len, prompt_len,
+                c.max_seq_len);
+  for (int i = 0; i < prompt_len; ++i)
+    if (prompt[i] < 0 || prompt[i] >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "prompt token out of range");
+  return generate_run(D, emb, emb_dtype, n, prompt, prompt_len, nullptr, bp, out_tokens, out_lens, out_scores,
+                      (hipStream_t)stream_v);
+}
+
+int smi_text_decoder_generate_prompts(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
+                                      const int64_t* prompts, int32_t prompt_stride, const int32_t* prompt_lens,
+                                      int32_t gen_cap, int32_t min_gen_len, const smi_beam_search_params* bp,
+                                      int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
+  if (!prompts || !prompt_lens) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (int rc = check_generate_args(D, emb, emb_dtype, n, bp, out_tokens, out_lens, out_scores)) return rc;
+  std::vector<int32_t> tab;
+  PromptSpec ps{prompts, prompt_lens, prompt_stride, gen_cap, min_gen_len, bp->max_seq_len, 0, {}};
+  if (int rc = check_prompts(D->cfg, n, prompts, prompt_stride, prompt_lens, gen_cap, min_gen_len, bp->max_seq_len, &tab,
+                             &ps.width))
+    return rc;
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (prompts_all_equal(n, prompts, prompt_stride, prompt_lens)) {
+    // one prompt after all: the one-prompt call, launch for launch (every max_len_s is the width)
+    smi_beam_search_params one = *bp;
+    one.max_seq_len = ps.width;
+    one.min_seq_len = ps.min_len(0);
+    return generate_run(D, emb, emb_dtype, n, prompts, prompt_lens[0], nullptr, &one, out_tokens, out_lens, out_scores, stream);
+  }
+  ps.dev = PromptTableDev{nullptr, nullptr, prompt_stride, gen_cap, min_gen_len, bp->max_seq_len};
+  if (int rc = upload_prompt_table(D, tab, n, prompt_stride, stream, &ps.dev)) return rc;
+  return generate_run(D, emb, emb_dtype, n, nullptr, 0, &ps, bp, out_tokens, out_lens, out_scores, stream);
 }
 
 int smi_text_decoder_set_chains(smi_text_decoder* D, int32_t chains) {
@@ -882,12 +1053,14 @@ int smi_text_decoder_last_margins(smi_text_decoder* D, float* out_margins, int32
   return SMI_OK;
 }
 
-int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
-                            const int64_t* prompt, int32_t prompt_len, const smi_sampling_params* sp,
-                            int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
-  if (!D || !emb || !prompt || !sp || !out_tokens || !out_lens || !out_scores)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (n <= 0 || prompt_len <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+}  // extern "C"
+
+namespace {
+
+int check_sample_args(const smi_text_decoder* D, const void* emb, int emb_dtype, int n, const smi_sampling_params* sp,
+                      const void* out_tokens, const void* out_lens, const void* out_scores) {
+  if (!D || !emb || !sp || !out_tokens || !out_lens || !out_scores) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (n <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
   if (emb_dtype != SMI_F32 && emb_dtype != SMI_F16) return fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
   const smi_text_decoder_config& c = D->cfg;
   if (sp->sampler == SMI_SAMPLER_TOP_K) {
@@ -899,15 +1072,17 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
   }
   if (c.vocab_size > (1 << 18))
     return fail(SMI_ERR_UNSUPPORTED, "vocab %d: sampling covers up to 2^18 tokens", (int)c.vocab_size);
-  const int max_len = sp->max_seq_len, min_len = sp->min_seq_len;
-  if (max_len > c.max_seq_len || max_len <= prompt_len)
-    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in (prompt_len %d, model max %d]", max_len, prompt_len,
-                c.max_seq_len);
   if (!(sp->temperature > 0.f)) return fail(SMI_ERR_INVALID_ARG, "temperature must be positive");
-  for (int i = 0; i < prompt_len; ++i)
-    if (prompt[i] < 0 || prompt[i] >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "prompt token out of range");
-  hipStream_t stream = (hipStream_t)stream_v;
+  return SMI_OK;
+}
 
+// the checked call: one prompt (ps null; sp carries the lengths) or per-sentence prompts (ps->dev uploaded)
+int sample_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, const int64_t* prompt, int prompt_len,
+               const PromptSpec* ps, const smi_sampling_params* sp, int32_t* out_tokens, int32_t* out_lens, float* out_scores,
+               hipStream_t stream) {
+  const smi_text_decoder_config& c = D->cfg;
+  const int max_len = ps ? ps->width : sp->max_seq_len, min_len = sp->min_seq_len;  // max_len: loop bound and output row length
+  const PromptPlan plan = ps ? PromptPlan(*ps, n) : PromptPlan();
   // one hypothesis per sentence (fairseq2 num_gens = 1): rows = sentences, identity ancestry
   DecWork& S = D->ws[0];
   S.chained = false;
@@ -922,15 +1097,17 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
   HIP_TRY(S.new_cum.reserve((size_t)n * 4));
   HIP_TRY(S.anc[0].reserve((size_t)rows_pad * stride * 4));
   {
-    std::vector<int32_t> ident((size_t)n * stride), first((size_t)n, (int32_t)prompt[0]);
-    for (int r = 0; r < n; ++r)
+    std::vector<int32_t> ident((size_t)n * stride), first((size_t)n, ps ? 0 : (int32_t)prompt[0]);
+    for (int r = 0; r < n; ++r) {
       for (int j = 0; j < stride; ++j) ident[(size_t)r * stride + j] = r;
+      if (ps) first[r] = (int32_t)ps->tok[(size_t)r * ps->stride];
+    }
     HIP_TRY(hipMemcpyAsync(S.anc[0].p, ident.data(), ident.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemcpyAsync(S.tok.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
   }
   const StepProcDev proc = D->step_proc();
-  if (proc.active()) {  // the bans read the prompt on the device
+  if (proc.active() && !ps) {  // the bans read the prompt on the device (per-sentence prompts: from the table)
     std::vector<int32_t> p32(prompt, prompt + prompt_len);
     HIP_TRY(S.prompt_dev.reserve((size_t)prompt_len * 4));
     HIP_TRY(hipMemcpyAsync(S.prompt_dev.p, p32.data(), p32.size() * 4, hipMemcpyHostToDevice, stream));
@@ -949,12 +1126,21 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
     if (pos >= S.kv_positions)
       if (int rc = grow_kv(D, S, rows_pad, std::min(max_len, 2 * S.kv_positions), stream)) return rc;
     if (int rc = decoder_step(D, S, n, rows_pad, 1, n_pad, pos, S.anc[0].as<int32_t>(), stride, stream)) return rc;
-    const bool forced_prompt = step_nr < prompt_len;
-    const bool force_eos = !forced_prompt && step_nr == max_len - 1;
+    // the step's mode, as in generate_chain: the same for every sentence, or `mixed` (the kernel reads the table)
+    bool forced_prompt = step_nr < prompt_len;
+    bool force_eos = !forced_prompt && step_nr == max_len - 1;
+    bool block_eos = !forced_prompt && !force_eos && step_nr < min_len;
+    bool mixed = false;
+    if (ps) {
+      forced_prompt = false;  // the sentences' prompt tokens differ: a forced step reads the table too
+      force_eos = plan.all_force_eos(step_nr);
+      block_eos = false;
+      mixed = !force_eos && !plan.all_free(step_nr, &block_eos);
+    }
     SampleRowsArgs a{};
     a.logits = S.logits.as<float>(); a.ld = D->vocab_pad; a.rows = n; a.vocab = (int)c.vocab_size;
     a.inv_temp = 1.0f / sp->temperature; a.pad_idx = c.pad_idx; a.eos_idx = c.eos_idx;
-    a.block_eos = !forced_prompt && !force_eos && step_nr < min_len;
+    a.block_eos = block_eos;
     a.unk_idx = c.unk_idx; a.unk_penalty = sp->unk_penalty;
     a.forced_tok = forced_prompt ? (int)prompt[step_nr] : (force_eos ? c.eos_idx : -1);
     a.mode = sp->sampler; a.top_k = sp->top_k; a.top_p = sp->top_p; a.z = nullptr; a.seed = sp->seed; a.step = step_nr;
@@ -962,13 +1148,15 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
     if (a.forced_tok < 0 && proc.active()) {
       a.proc = proc; a.prompt = S.prompt_dev.as<int32_t>(); a.prompt_len = prompt_len; a.gen = out_tokens; a.gen_stride = max_len;
     }
+    // (a free step of every sentence under step processors: the bans still read each row's own prompt)
+    if (mixed || (ps && a.forced_tok < 0 && proc.active())) a.table = ps->dev;
     HIP_TRY(launch_sample_rows(a, stream));
     SampleUpdateArgs u{};
     u.samp_tok = S.new_tok.as<int32_t>(); u.samp_logp = S.new_cum.as<float>(); u.tok = S.tok.as<int32_t>();
     u.cum = S.cum.as<float>(); u.done = S.done.as<int32_t>(); u.ndone = S.ndone.as<int32_t>();
     u.out_tokens = out_tokens; u.out_lens = out_lens; u.out_scores = out_scores; u.n = n; u.out_stride = max_len;
     u.pos = pos; u.prompt_len = prompt_len; u.eos_idx = c.eos_idx; u.normalize = sp->normalize_scores;
-    u.len_penalty = sp->len_penalty;
+    u.len_penalty = sp->len_penalty; u.prompt_lens = ps ? ps->dev.len : nullptr;
     HIP_TRY(launch_sample_update(u, stream));
     if ((step_nr & 7) == 0 && !force_eos) {
       int32_t nd = 0;
@@ -980,6 +1168,50 @@ int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dt
   if (proc.active())
     if (int rc = record_table_use(S, stream)) return rc;
   return SMI_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
+                            const int64_t* prompt, int32_t prompt_len, const smi_sampling_params* sp,
+                            int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
+  if (!prompt) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (int rc = check_sample_args(D, emb, emb_dtype, n, sp, out_tokens, out_lens, out_scores)) return rc;
+  if (prompt_len <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  const smi_text_decoder_config& c = D->cfg;
+  const int max_len = sp->max_seq_len;
+  if (max_len > c.max_seq_len || max_len <= prompt_len)
+    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in (prompt_len %d, model max %d]", max_len, prompt_len,
+                c.max_seq_len);
+  for (int i = 0; i < prompt_len; ++i)
+    if (prompt[i] < 0 || prompt[i] >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "prompt token out of range");
+  return sample_run(D, emb, emb_dtype, n, prompt, prompt_len, nullptr, sp, out_tokens, out_lens, out_scores,
+                    (hipStream_t)stream_v);
+}
+
+int smi_text_decoder_sample_prompts(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
+                                    const int64_t* prompts, int32_t prompt_stride, const int32_t* prompt_lens,
+                                    int32_t gen_cap, int32_t min_gen_len, const smi_sampling_params* sp,
+                                    int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
+  if (!prompts || !prompt_lens) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (int rc = check_sample_args(D, emb, emb_dtype, n, sp, out_tokens, out_lens, out_scores)) return rc;
+  std::vector<int32_t> tab;
+  PromptSpec ps{prompts, prompt_lens, prompt_stride, gen_cap, min_gen_len, sp->max_seq_len, 0, {}};
+  if (int rc = check_prompts(D->cfg, n, prompts, prompt_stride, prompt_lens, gen_cap, min_gen_len, sp->max_seq_len, &tab,
+                             &ps.width))
+    return rc;
+  hipStream_t stream = (hipStream_t)stream_v;
+  if (prompts_all_equal(n, prompts, prompt_stride, prompt_lens)) {  // one prompt after all: the one-prompt call
+    smi_sampling_params one = *sp;
+    one.max_seq_len = ps.width;
+    one.min_seq_len = ps.min_len(0);
+    return sample_run(D, emb, emb_dtype, n, prompts, prompt_lens[0], nullptr, &one, out_tokens, out_lens, out_scores, stream);
+  }
+  ps.dev = PromptTableDev{nullptr, nullptr, prompt_stride, gen_cap, min_gen_len, sp->max_seq_len};
+  if (int rc = upload_prompt_table(D, tab, n, prompt_stride, stream, &ps.dev)) return rc;
+  return sample_run(D, emb, emb_dtype, n, nullptr, 0, &ps, sp, out_tokens, out_lens, out_scores, stream);
 }
 
 }  // extern "C"

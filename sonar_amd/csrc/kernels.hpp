@@ -170,6 +170,34 @@ hipError_t launch_sum_layernorm(void* x, const void* parts, int nparts, size_t p
 hipError_t launch_dec_attention(const f16* kv, const int32_t* anc, int anc_stride, f16* ctx, int rows,
                                 int rows_pad, int d, int heads, int pos, hipStream_t stream);
 constexpr int kVocabScanK2Max = 16;
+// Per-sentence prompts of one generate / sample call (smi_text_decoder_generate_prompts): a device table the
+// selection, beam and sampling kernels read their sentence's mode from.  tok == nullptr: the call has ONE prompt and the
+// kernels take the step's mode from their scalar arguments, as before.
+struct PromptTableDev {
+  const int32_t* tok;  // [n][stride], left-aligned
+  const int32_t* len;  // [n], >= 1
+  int stride;
+  int gen_cap, min_gen, model_max;  // max_len_s = min(len_s + gen_cap, model_max), min_len_s = min(len_s + min_gen, max_len_s)
+};
+// what sentence s does at the step that chooses token `step_nr`
+struct PromptRowMode {
+  int plen, max_len;
+  int forced_tok;  // >= 0: a prompt token
+  bool force_eos;  // the sentence's own length cap
+  bool free_step;  // neither; also false past the cap (the sentence is done there)
+  bool block_eos;
+};
+__host__ __device__ inline PromptRowMode prompt_row_mode(const PromptTableDev& t, int s, int step_nr) {
+  PromptRowMode m;
+  m.plen = t.len[s];
+  m.max_len = m.plen + t.gen_cap < t.model_max ? m.plen + t.gen_cap : t.model_max;
+  const int min_len = m.plen + t.min_gen < m.max_len ? m.plen + t.min_gen : m.max_len;
+  m.forced_tok = step_nr < m.plen ? t.tok[(size_t)s * t.stride + step_nr] : -1;
+  m.force_eos = m.forced_tok < 0 && step_nr == m.max_len - 1;
+  m.free_step = m.forced_tok < 0 && step_nr < m.max_len - 1;
+  m.block_eos = m.free_step && step_nr < min_len;
+  return m;
+}
 // Per row: softmax normaliser (pmax, psum) from the GEMM's tile statistics and the top-k2 candidates
 // among the k2 best tiles + tile 0 (pval / pidx [rows][kVocabScanK2Max]), without re-reading the whole
 // logits row.
@@ -177,7 +205,10 @@ constexpr int kVocabScanK2Max = 16;
 hipError_t launch_vocab_select(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
                                const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx,
                                int unk_idx, float unk_penalty, int block_eos, float* pmax, float* psum, float* pval,
-                               int* pidx, hipStream_t stream);
+                               int* pidx, hipStream_t stream, const PromptTableDev* table = nullptr, int group = 1,
+                               int step_nr = 0);
+// (table: row r belongs to sentence r / group and takes block_eos / whether unk_penalty applies from its own mode at step_nr; a
+// row whose sentence is forced there gets its normaliser only.  Both selections.)
 // Step processors (smi_step_processors, device copy): n-gram repeat blocking and banned sequences, CSR on the device
 struct StepProcDev {
   int ngram;              // 0 = off
@@ -195,7 +226,8 @@ hipError_t launch_vocab_select_banned(const float* logits, int ldl, int f16_tm, 
                                       const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx,
                                       int eos_idx, int unk_idx, float unk_penalty, int block_eos, const int32_t* hist,
                                       int hist_stride, int hist_len, const StepProcDev& proc, float* pmax, float* psum,
-                                      float* pval, int* pidx, hipStream_t stream);
+                                      float* pval, int* pidx, hipStream_t stream, const PromptTableDev* table = nullptr,
+                                      int group = 1, int step_nr = 0);
 struct BeamStepArgs {
   int32_t* tok; float* cum; int32_t* nactive; int32_t* done; int32_t* ndone;
   int32_t* parent; int32_t* new_tok; float* new_cum;
@@ -206,6 +238,7 @@ struct BeamStepArgs {
   const float* pmax; const float* psum; const float* pval; const int* pidx; int nchunks;
   int n, beam, k2, pos, prompt_len, forced_tok, max_len;
   float inv_temp, len_penalty; int normalize, eos_idx, hist_stride;
+  PromptTableDev table;  // table.tok != nullptr: prompt_len / forced_tok / max_len are the sentence's own
 };
 hipError_t launch_beam_step(const BeamStepArgs& a, hipStream_t stream);
 hipError_t launch_beam_reorder(const int32_t* parent, const int32_t* new_tok, const float* new_cum,
@@ -214,7 +247,8 @@ hipError_t launch_beam_reorder(const int32_t* parent, const int32_t* new_tok, co
                                hipStream_t stream);
 hipError_t launch_beam_init(int32_t* tok, float* cum, int32_t* nactive, int32_t* done, int32_t* ndone,
                             int32_t* fin_count, int32_t* hist, int32_t* anc, float* margins, int rows, int n,
-                            int stride, int first_tok, hipStream_t stream);
+                            int stride, int first_tok, hipStream_t stream, const int32_t* first_toks = nullptr,
+                            int first_stride = 0, int beam = 1);  // first_toks: sentence s starts with first_toks[s * first_stride]
 hipError_t launch_beam_output(const int32_t* fin_tok, const int32_t* fin_len, const float* fin_score,
                               const int32_t* fin_count, int n, int beam, int stride, int out_stride,
                               int32_t* out_tok, int32_t* out_len, float* out_score, float* margins,
@@ -296,6 +330,8 @@ struct SampleRowsArgs {
   int prompt_len;
   const int32_t* gen;     // [rows][gen_stride]
   int gen_stride;
+  // table.tok != nullptr: forced_tok / block_eos / prompt / prompt_len are the row's own at step `step` (force_eos included)
+  PromptTableDev table;
 };
 
 struct SampleUpdateArgs {
@@ -310,6 +346,7 @@ struct SampleUpdateArgs {
   float* out_scores;
   int n, out_stride, pos, prompt_len, eos_idx, normalize;
   float len_penalty;
+  const int32_t* prompt_lens;  // [n] or null: prompt_len holds for every row
 };
 hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t stream);
 hipError_t launch_sample_update(const SampleUpdateArgs& a, hipStream_t stream);

@@ -99,9 +99,16 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs
   __shared__ u64 s_bc[4];  // broadcast slots
   const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (a.done && a.done[row]) return;
+  if (a.table.tok) {  // per-sentence prompts: the row's own mode at this step (uniform over the workgroup)
+    const PromptRowMode md = prompt_row_mode(a.table, row, a.step);
+    a.forced_tok = md.forced_tok >= 0 ? md.forced_tok : (md.free_step ? -1 : a.eos_idx);
+    a.block_eos = md.block_eos;
+    a.prompt = a.table.tok + (size_t)row * a.table.stride;
+    a.prompt_len = md.plen;
+  }
   const float* lg = a.logits + (size_t)row * a.ld;
   const int V = a.vocab;
-  if constexpr (BAN) {  // the row's sequence so far: prompt + generated tokens; step = its length
+  if constexpr (BAN) if (a.forced_tok < 0) {  // the row's sequence so far: prompt + generated tokens; step = its length
     for (int w = tid; w < (V + 31) / 32; w += SMP_THREADS) s_banbits[w] = 0u;
     const int L = a.step;
     for (int i = tid; i < L; i += SMP_THREADS)
@@ -410,12 +417,13 @@ __global__ void sample_update_kernel(SampleUpdateArgs a) {
   const float cum = a.cum[r] + a.samp_logp[r];
   a.cum[r] = cum;
   a.tok[r] = t;
-  if (step_nr < a.prompt_len) return;
-  a.out_tokens[(size_t)r * a.out_stride + (step_nr - a.prompt_len)] = t;
+  const int plen = a.prompt_lens ? a.prompt_lens[r] : a.prompt_len;
+  if (step_nr < plen) return;
+  a.out_tokens[(size_t)r * a.out_stride + (step_nr - plen)] = t;
   if (t == a.eos_idx) {
     a.done[r] = 1;
     atomicAdd(a.ndone, 1);
-    a.out_lens[r] = step_nr - a.prompt_len + 1;
+    a.out_lens[r] = step_nr - plen + 1;
     a.out_scores[r] = a.normalize ? cum / powf((float)step_nr, a.len_penalty) : cum;
   }
 }
@@ -429,14 +437,17 @@ hipError_t launch_sample_rows(const SampleRowsArgs& a, hipStream_t stream) {
   if (a.rows <= 0 || a.vocab <= 0 || !(a.inv_temp > 0.f) || a.ld % 4 || a.ld < (a.vocab + 3) / 4 * 4)
     return hipErrorInvalidValue;
   if (a.vocab > (1 << 18)) return hipErrorInvalidValue;  // the tie-break descent covers 18-bit token ids
+  if (a.table.tok && (!a.table.len || a.step < 1)) return hipErrorInvalidValue;
   if (a.forced_tok < 0) {
     if (a.mode == 0 && a.top_k < 1) return hipErrorInvalidValue;
     if (a.mode == 1 && !(a.top_p > 0.f && a.top_p <= 1.f)) return hipErrorInvalidValue;
     if (a.mode != 0 && a.mode != 1) return hipErrorInvalidValue;
   }
   if (a.proc.active() && a.forced_tok < 0) {
-    if (!a.prompt || a.prompt_len < 1 || a.step < a.prompt_len || a.step > kStepProcMaxLen || !a.gen ||
-        a.gen_stride < a.step - a.prompt_len || a.proc.num_banned > kStepProcMaxBanned)
+    // (per-sentence prompts: the kernel takes prompt / prompt_len from the table; every prompt is at least one token long)
+    const int plen_min = a.table.tok ? 1 : a.prompt_len;
+    if ((!a.table.tok && (!a.prompt || a.prompt_len < 1 || a.step < a.prompt_len)) || a.step > kStepProcMaxLen || !a.gen ||
+        a.gen_stride < a.step - plen_min || a.proc.num_banned > kStepProcMaxBanned)
       return hipErrorInvalidValue;
     hipLaunchKernelGGL(sample_rows_kernel<true>, dim3(a.rows), dim3(SMP_THREADS), 0, stream, a);
   } else {

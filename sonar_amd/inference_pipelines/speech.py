@@ -284,12 +284,19 @@ class SpeechToTextModelPipeline(SpeechModelPipelineInterface):
         self.device = self.s2vec.device
 
     @torch.inference_mode()
-    def predict(self, input: Sequence[Union[str, Path, torch.Tensor]], target_lang: str, batch_size: int = 3,
-                n_parallel: int = 1, pad_idx: int = 0, n_prefetched_batches: int = 2, progress_bar: bool = False,
+    def predict(self, input: Sequence[Union[str, Path, torch.Tensor]], target_lang: Union[str, Sequence[str]],
+                batch_size: int = 3, n_parallel: int = 1, pad_idx: int = 0, n_prefetched_batches: int = 2,
+                progress_bar: bool = False, prefixes: Optional[Sequence[Optional[str]]] = None,
                 **generator_kwargs) -> List[str]:
+        """`target_lang` (one, or one per input) and `prefixes` as in EmbeddingToTextModelPipeline.predict."""
         if batch_size <= 0:
             raise ValueError("`batch_size` should be strictly positive")
         items = list(input)
+        per_row = not isinstance(target_lang, str)
+        target_lang = list(target_lang) if per_row else target_lang
+        prefixes = None if prefixes is None else list(prefixes)
+        if (per_row and len(target_lang) != len(items)) or (prefixes is not None and len(prefixes) != len(items)):
+            raise ValueError(f"one target language / prefix per input expected ({len(items)} inputs)")
         batches: Iterable = self._prefetched(items, batch_size, n_parallel, n_prefetched_batches)
         if progress_bar:
             batches = add_progress_bar(batches, inputs=items, batch_size=batch_size)
@@ -298,8 +305,10 @@ class SpeechToTextModelPipeline(SpeechModelPipelineInterface):
             batch, lens = self.s2vec._fbank_batch(hb, pad_idx)
             emb = self.s2vec.model(batch).sentence_embeddings
             src_len = max(lens) if batch.padding_mask is not None else batch.seqs.shape[1]
-            out.extend(self.vec2t.predict(emb, target_lang=target_lang, batch_size=emb.shape[0],
-                                          source_len=src_len, **generator_kwargs))
+            rows = slice(len(out), len(out) + emb.shape[0])
+            out.extend(self.vec2t.predict(emb, target_lang=target_lang[rows] if per_row else target_lang,
+                                          batch_size=emb.shape[0], source_len=src_len,
+                                          prefixes=None if prefixes is None else prefixes[rows], **generator_kwargs))
         return out
 
 

@@ -246,7 +246,12 @@ class EmbeddingToTextModelPipeline(torch.nn.Module):
     unk_penalty, temperature, step_processors), or -- with `sampler=TopKSampler(k) / TopPSampler(p)` (sonar_amd.generation)
     -- by fairseq2's SamplingSeq2SeqGenerator (same kwargs minus beam_size).  `step_processors=[...]` takes
     NGramRepeatBlockProcessor / BannedSequenceProcessor (sonar_amd.generation, or fairseq2's objects of those names); they
-    run on the device inside the token selection of both generators."""
+    run on the device inside the token selection of both generators.
+
+    `predict` takes one `target_lang` for the call, or one per input; `prefixes` (one `str | None` per input) is text the
+    output must begin with -- its pieces are appended to the row's prompt and forced, and the returned text includes it.
+    Either makes the prompts differ from row to row; a batch then runs as ONE engine call with per-sentence prompts, and a
+    row's text is what the single-language call gives for it."""
 
     def __init__(self, decoder, tokenizer: Union[str, Path, NllbTokenizer], device: torch.device = CPU,
                  dtype: Optional[torch.dtype] = None) -> None:
@@ -267,13 +272,16 @@ class EmbeddingToTextModelPipeline(torch.nn.Module):
         self.device = getattr(decoder, "device", device)
 
     @torch.inference_mode()
-    def predict(self, inputs: torch.Tensor, target_lang: str, batch_size: int = 5, progress_bar: bool = False,
-                sampler=None, **generator_kwargs) -> List[str]:
+    def predict(self, inputs: torch.Tensor, target_lang: Union[str, Sequence[str]], batch_size: int = 5,
+                progress_bar: bool = False, sampler=None, prefixes: Optional[Sequence[Optional[str]]] = None,
+                **generator_kwargs) -> List[str]:
         if batch_size <= 0:
             raise ValueError("`batch_size` should be strictly positive")
+        rows = list(inputs)
+        if not isinstance(target_lang, str) or prefixes is not None:
+            return self._predict_rows(rows, target_lang, prefixes, batch_size, progress_bar, sampler, generator_kwargs)
         prompt = self.tokenizer.create_encoder(task="translation", lang=target_lang, mode="target").prefix
         decode = self.tokenizer.create_decoder()
-        rows = list(inputs)
         batches: Iterable = [rows[i:i + batch_size] for i in range(0, len(rows), batch_size)]
         if progress_bar:
             batches = add_progress_bar(batches, inputs=rows, batch_size=batch_size)
@@ -291,14 +299,36 @@ class EmbeddingToTextModelPipeline(torch.nn.Module):
                 texts.append(decode(toks[i, : int(lens[i])]))
         return texts
 
+    def _predict_rows(self, rows, target_lang, prefixes, batch_size, progress_bar, sampler, generator_kwargs) -> List[str]:
+        """predict() with per-row prompts: the same batches in input order, each one engine call."""
+        prompts, forced = target_prompts(self.tokenizer, len(rows), target_lang, prefixes)
+        decode = self.tokenizer.create_decoder()
+        batches: Iterable = [range(i, min(i + batch_size, len(rows))) for i in range(0, len(rows), batch_size)]
+        if progress_bar:
+            batches = add_progress_bar(batches, inputs=rows, batch_size=batch_size)
+        texts: List[str] = []
+        for idx in batches:
+            emb = torch.stack([rows[i] for i in idx]).to(self.device)
+            chunk = [prompts[i] for i in idx]
+            if sampler is None:
+                toks, lens, _ = self.model.engine.generate(emb, chunk, **generator_kwargs)
+                toks, lens = toks[:, 0].cpu(), lens[:, 0].cpu()
+            else:
+                toks, lens, _ = self.model.engine.sample(emb, chunk, sampler, sentence_offset=len(texts), **generator_kwargs)
+                toks, lens = toks.cpu(), lens.cpu()
+            for k, i in enumerate(idx):   # the text includes the forced prefix
+                texts.append(decode(forced[i] + toks[k, : int(lens[k])].tolist()))
+        return texts
+
 
     @torch.inference_mode()
-    def score(self, inputs: torch.Tensor, texts: Sequence[str], target_lang: str, batch_size: int = 5,
+    def score(self, inputs: torch.Tensor, texts: Sequence[str], target_lang: Union[str, Sequence[str]], batch_size: int = 5,
               progress_bar: bool = False) -> torch.Tensor:
         """log p(text | sentence embedding) per input, fp32 [n] on the CPU: the sum of the log-probabilities of the text's
         pieces and its final </s>, given the prompt [</s>, __lang__] (teacher forcing, TextDecoderEngine.score).  The
         scored sequence is prompt + pieces + [</s>] (`score_sequences`), the shape generate() produces.  Sentences are
-        sorted by length and scored in buckets of `batch_size`; the result is in input order."""
+        sorted by length and scored in buckets of `batch_size`; the result is in input order.  `target_lang`: one language,
+        or one per input."""
         if batch_size <= 0:
             raise ValueError("`batch_size` should be strictly positive")
         rows, texts = list(inputs), list(texts)
@@ -318,14 +348,46 @@ class EmbeddingToTextModelPipeline(torch.nn.Module):
         return out
 
 
-def score_sequences(tokenizer: NllbTokenizer, texts: Sequence[str], target_lang: str):
+def score_sequences(tokenizer: NllbTokenizer, texts: Sequence[str], target_lang: Union[str, Sequence[str]]):
     """(sequences, prompt length) that EmbeddingToTextModelPipeline.score scores: [</s>, __lang__] + pieces + [</s>] per
     text -- fairseq2's target-mode encoding of a complete sentence, and what generate() returns after its prompt.
-    (NllbEncoder's own target mode keeps its empty suffix: it builds decoder prompts.)"""
-    enc = tokenizer.create_encoder(task="translation", lang=target_lang, mode="target")
+    (NllbEncoder's own target mode keeps its empty suffix: it builds decoder prompts.)  `target_lang`: one language, or one
+    per text (the prompt is two tokens long in every language)."""
     eos = tokenizer.vocab_info.eos_idx
-    ids = enc.encode_batch(list(texts)) if hasattr(enc, "encode_batch") else [enc.ids(t) for t in texts]
+    texts = list(texts)
+    if not isinstance(target_lang, str):
+        langs = list(target_lang)
+        if len(langs) != len(texts):
+            raise ValueError(f"{len(langs)} target languages for {len(texts)} texts")
+        encs = {L: tokenizer.create_encoder(task="translation", lang=L, mode="target") for L in dict.fromkeys(langs)}
+        plens = {len(e.prefix) for e in encs.values()}
+        plen = plens.pop() if plens else 2
+        assert not plens, "target-mode prefixes of one length expected"
+        return [list(encs[L].ids(t)) + [eos] for L, t in zip(langs, texts)], plen
+    enc = tokenizer.create_encoder(task="translation", lang=target_lang, mode="target")
+    ids = enc.encode_batch(texts) if hasattr(enc, "encode_batch") else [enc.ids(t) for t in texts]
     return [list(s) + [eos] for s in ids], len(enc.prefix)
+
+
+def target_prompts(tokenizer: NllbTokenizer, n: int, target_lang: Union[str, Sequence[str]],
+                   prefixes: Optional[Sequence[Optional[str]]] = None):
+    """Per-row decoder prompts of EmbeddingToTextModelPipeline.predict: (prompts, forced), prompts[i] = [</s>, __lang_i__] +
+    the pieces of prefixes[i] (the target-mode encoding of the prefix: no EOS), forced[i] = those pieces.  `target_lang`: one
+    language or one per row; `prefixes`: None, or one `str | None` per row.  ValueError when a count is not n."""
+    langs = [target_lang] * n if isinstance(target_lang, str) else list(target_lang)
+    if len(langs) != n:
+        raise ValueError(f"{len(langs)} target languages for {n} inputs")
+    prefixes = [None] * n if prefixes is None else list(prefixes)
+    if len(prefixes) != n:
+        raise ValueError(f"{len(prefixes)} prefixes for {n} inputs")
+    encs = {L: tokenizer.create_encoder(task="translation", lang=L, mode="target") for L in dict.fromkeys(langs)}
+    prompts, forced = [], []
+    for L, pre in zip(langs, prefixes):
+        enc = encs[L]
+        ids = [int(t) for t in (enc.ids(pre) if pre else enc.prefix)]
+        prompts.append(ids)
+        forced.append(ids[len(enc.prefix):])
+    return prompts, forced
 
 
 class TextToTextModelPipeline(torch.nn.Module):
@@ -343,14 +405,24 @@ class TextToTextModelPipeline(torch.nn.Module):
         self.device = self.t2vec.device
 
     @torch.inference_mode()
-    def predict(self, input: Union[Path, Sequence[str]], source_lang: str, target_lang: str, batch_size: int = 5,
-                progress_bar: bool = False, **generator_kwargs) -> List[str]:
+    def predict(self, input: Union[Path, Sequence[str]], source_lang: str, target_lang: Union[str, Sequence[str]],
+                batch_size: int = 5, progress_bar: bool = False, prefixes: Optional[Sequence[Optional[str]]] = None,
+                **generator_kwargs) -> List[str]:
+        """`target_lang` (one, or one per input) and `prefixes` (one `str | None` per input) as in
+        EmbeddingToTextModelPipeline.predict; `source_lang` is one language per call."""
         model_max = self.vec2t.model.max_target_seq_len
         generator_kwargs["max_seq_len"] = min(model_max, generator_kwargs.get("max_seq_len", model_max))
         if isinstance(input, (str, Path)):
             with open(Path(input), "r", encoding="utf-8") as fh:
                 input = [line.rstrip("\n") for line in fh]
         texts = list(input)
+        per_row = not isinstance(target_lang, str)
+        target_lang = list(target_lang) if per_row else target_lang
+        prefixes = None if prefixes is None else list(prefixes)
+        if per_row and len(target_lang) != len(texts):
+            raise ValueError(f"{len(target_lang)} target languages for {len(texts)} inputs")
+        if prefixes is not None and len(prefixes) != len(texts):
+            raise ValueError(f"{len(prefixes)} prefixes for {len(texts)} inputs")
         out: List[str] = []
         batches: Iterable = [texts[i:i + batch_size] for i in range(0, len(texts), batch_size)]
         if progress_bar:
@@ -365,13 +437,15 @@ class TextToTextModelPipeline(torch.nn.Module):
             else:
                 src_len = max(len(enc(t)) for t in chunk)
             src_len = min(src_len, self.t2vec.model.encoder_frontend.pos_encoder.max_seq_len)
-            out.extend(self.vec2t.predict(emb, target_lang=target_lang, batch_size=len(chunk),
-                                          source_len=src_len, **generator_kwargs))
+            rows = slice(len(out), len(out) + len(chunk))
+            out.extend(self.vec2t.predict(emb, target_lang=list(target_lang[rows]) if per_row else target_lang,
+                                          batch_size=len(chunk), source_len=src_len,
+                                          prefixes=None if prefixes is None else list(prefixes[rows]), **generator_kwargs))
         return out
 
     @torch.inference_mode()
-    def score(self, input: Union[Path, Sequence[str]], targets: Sequence[str], source_lang: str, target_lang: str,
-              batch_size: int = 5, progress_bar: bool = False) -> torch.Tensor:
+    def score(self, input: Union[Path, Sequence[str]], targets: Sequence[str], source_lang: str,
+              target_lang: Union[str, Sequence[str]], batch_size: int = 5, progress_bar: bool = False) -> torch.Tensor:
         """log p(target | encode(source)) per pair, fp32 [n] on the CPU: the sources go through `t2vec`, the targets are
         scored by EmbeddingToTextModelPipeline.score (pieces + final </s> given [</s>, __lang__])."""
         if isinstance(input, (str, Path)):

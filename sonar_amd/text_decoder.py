@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import numbers
 import re
 from dataclasses import dataclass, field
 from typing import Dict, List, Mapping, Optional, Sequence, Tuple, Union
@@ -136,6 +137,75 @@ def convert_sonar_text_decoder_checkpoint(checkpoint: Mapping) -> Dict[str, torc
 
 
 # --------------------------------------------------------------------- engine
+def split_prompts(prompt):
+    """`prompt` of generate() / sample(): (False, [ids]) for one prompt -- a sequence of ints --, or (True, [[ids], ...]) for a
+    sequence of per-sentence prompts (sequences of ints, possibly of different lengths)."""
+    if isinstance(prompt, torch.Tensor):
+        prompt = prompt.tolist()
+    items = [int(t) if isinstance(t, torch.Tensor) and t.dim() == 0 else t for t in prompt]
+    nested = [not isinstance(t, numbers.Integral) for t in items]
+    if not any(nested):
+        return False, [int(t) for t in items]
+    if not all(nested):
+        raise ValueError("`prompt` must be a sequence of ints or a sequence of int sequences, not a mixture")
+    return True, [[int(t) for t in (row.tolist() if isinstance(row, torch.Tensor) else row)] for row in items]
+
+
+def length_limits(decoder_max_seq_len: int, cond_dim: int, plen: int, min_gen_len: int, max_gen_len: Tuple[int, int],
+                  max_seq_len: Optional[int], source_len: Optional[int], row: Optional[int] = None):
+    """(max_len, min_len, gen_cap, model_max) of one prompt of `plen` tokens: see TextDecoderEngine._length_limits.
+    `row`: the sentence the prompt belongs to, named in the error of a prompt that leaves no room."""
+    model_max = max_seq_len if max_seq_len is not None else decoder_max_seq_len
+    if model_max > decoder_max_seq_len:
+        raise ValueError(f"max_seq_len cannot be larger than the decoder's {decoder_max_seq_len}")
+    if source_len is None:
+        source_len = cond_dim   # width of the stacked sentence vectors
+    gen_cap = int(max_gen_len[0] * int(source_len) + max_gen_len[1])
+    if gen_cap < 1:
+        raise ValueError("`max_gen_len` must be greater than or equal to 1 for the given source length")
+    if min_gen_len > gen_cap:
+        raise ValueError(f"`min_gen_len` must be less than or equal to `max_gen_len` ({gen_cap}), "
+                         f"but is {min_gen_len} instead")
+    max_len = min(plen + gen_cap, model_max)
+    if max_len <= plen:
+        where = "" if row is None else f" of row {row} ({plen} tokens)"
+        raise ValueError(f"`max_seq_len` leaves no room for generation after the prompt{where}")
+    return max_len, min(plen + min_gen_len, max_len), gen_cap, model_max
+
+
+@dataclass
+class PromptRows:
+    """Per-sentence prompts of one call, as smi_text_decoder_generate_prompts takes them."""
+    rows: List[List[int]]
+    lens: List[int]
+    stride: int                       # longest prompt
+    limits: List[Tuple[int, int]]     # (max_len, min_len) per row
+    gen_cap: int
+    model_max: int
+    width: int                        # max over the rows of max_len: the output row length
+
+    def flat(self) -> List[int]:
+        return [t for r in self.rows for t in r + [0] * (self.stride - len(r))]
+
+
+def plan_prompt_rows(decoder_max_seq_len: int, cond_dim: int, prompts: Sequence[Sequence[int]], n: int, min_gen_len: int,
+                     max_gen_len: Tuple[int, int], max_seq_len: Optional[int], source_len: Optional[int]) -> PromptRows:
+    """Host side of a per-sentence-prompt call: one prompt per embedding, the length rule applied per row.  ValueError for a
+    count that does not match the embeddings, an empty prompt, or a row with no room to generate."""
+    rows = [list(r) for r in prompts]
+    if len(rows) != n:
+        raise ValueError(f"{len(rows)} prompts for {n} embeddings: one prompt per sentence expected")
+    limits, gen_cap, model_max = [], 0, 0
+    for i, r in enumerate(rows):
+        if not r:
+            raise ValueError(f"the prompt of row {i} is empty")
+        max_len, min_len, gen_cap, model_max = length_limits(decoder_max_seq_len, cond_dim, len(r), min_gen_len, max_gen_len,
+                                                             max_seq_len, source_len, row=i)
+        limits.append((max_len, min_len))
+    lens = [len(r) for r in rows]
+    return PromptRows(rows, lens, max(lens, default=0), limits, gen_cap, model_max, max((m for m, _ in limits), default=0))
+
+
 class TextDecoderEngine:
     """Owns one `smi_text_decoder` handle (packed fp16 weights in HBM + generation workspace)."""
 
@@ -289,21 +359,26 @@ class TextDecoderEngine:
         EmbeddingToTextModelPipeline hands the generator `torch.stack(embeddings)` [n, model_dim] as
         `source_seqs` (text.py:329-333), so there the "source length" is model_dim and the cap is in
         practice the decoder's max_seq_len; TextToText / SpeechToText pass their token / frame count."""
-        model_max = max_seq_len if max_seq_len is not None else self.cfg.max_seq_len
-        if model_max > self.cfg.max_seq_len:
-            raise ValueError(f"max_seq_len cannot be larger than the decoder's {self.cfg.max_seq_len}")
-        if source_len is None:
-            source_len = self.cfg.input_dim or self.cfg.model_dim   # width of the stacked sentence vectors
-        gen_cap = int(max_gen_len[0] * int(source_len) + max_gen_len[1])
-        if gen_cap < 1:
-            raise ValueError("`max_gen_len` must be greater than or equal to 1 for the given source length")
-        if min_gen_len > gen_cap:
-            raise ValueError(f"`min_gen_len` must be less than or equal to `max_gen_len` ({gen_cap}), "
-                             f"but is {min_gen_len} instead")
-        max_len = min(plen + gen_cap, model_max)
-        if max_len <= plen:
-            raise ValueError("`max_seq_len` leaves no room for generation after the prompt")
-        return max_len, min(plen + min_gen_len, max_len)
+        return length_limits(self.cfg.max_seq_len, self.cfg.input_dim or self.cfg.model_dim, plen, min_gen_len, max_gen_len,
+                             max_seq_len, source_len)[:2]
+
+    def _prompt_rows(self, prompts, n, min_gen_len, max_gen_len, max_seq_len, source_len) -> PromptRows:
+        return plan_prompt_rows(self.cfg.max_seq_len, self.cfg.input_dim or self.cfg.model_dim, prompts, n, min_gen_len,
+                                max_gen_len, max_seq_len, source_len)
+
+    def _call_prompts(self, fn, e, pr: PromptRows, min_gen_len, params, toks, lens, scores):
+        n = e.shape[0]
+        prompts = (C.c_int64 * (n * pr.stride))(*pr.flat())
+        plens = (C.c_int32 * n)(*pr.lens)
+        with torch.cuda.device(self.device):
+            try:
+                _lib.check(fn(self._handle, e.data_ptr(), _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16, n,
+                              prompts, pr.stride, plens, pr.gen_cap, int(min_gen_len), C.byref(params), toks.data_ptr(),
+                              lens.data_ptr(), scores.data_ptr(), _lib.current_stream_ptr()))
+            except _lib.SmiError as err:
+                if err.status == _lib.SMI_ERR_INVALID_ARG:
+                    raise ValueError(str(err)) from None
+                raise
 
     def set_beam_logits_dtype(self, dtype: torch.dtype) -> None:
         """Type of the logits the beam search of generate() compares (smi_text_decoder_set_beam_logits_dtype): float16 is what
@@ -364,6 +439,10 @@ class TextDecoderEngine:
         """Beam search with fairseq2's BeamSearchSeq2SeqGenerator defaults.
         Returns (tokens int32 [n, beam, L] (-1 padded), lens int32 [n, beam], scores fp32 [n, beam]),
         hypotheses best first; tokens are the generated part (after the prompt) incl. the final EOS.
+        `prompt`: a sequence of ints, the one prompt of every sentence, or a sequence of n int sequences, one prompt per
+        sentence (different target languages, or forced prefixes of different lengths, in one call).  The length rule is
+        then applied per row, L is the largest max_len among them, and row i returns what the call with the one prompt
+        prompt[i] returns for it (smi_text_decoder_generate_prompts).
         `source_len`: see `_length_limits` (None = the sentence-vector case).  `step_processors`: see
         `set_step_processors`; a banned token's log-probability is -inf after log_softmax, on the free steps."""
         return self._with_step_processors(step_processors, lambda: self._generate(
@@ -374,6 +453,18 @@ class TextDecoderEngine:
                   len_penalty, unk_penalty, temperature, source_len):
         e = self._emb(embeddings)
         n = e.shape[0]
+        nested, prompt = split_prompts(prompt)
+        if nested:
+            pr = self._prompt_rows(prompt, n, min_gen_len, max_gen_len, max_seq_len, source_len)
+            bp = _lib.smi_beam_search_params(beam_size=beam_size, max_seq_len=pr.model_max, min_seq_len=0,
+                                             normalize_scores=1 if normalize_scores else 0, len_penalty=len_penalty,
+                                             unk_penalty=unk_penalty, temperature=temperature, reserved=0)
+            toks = torch.empty((n, beam_size, pr.width), dtype=torch.int32, device=self.device)
+            lens = torch.empty((n, beam_size), dtype=torch.int32, device=self.device)
+            scores = torch.empty((n, beam_size), dtype=torch.float32, device=self.device)
+            if n:
+                self._call_prompts(self.lib.smi_text_decoder_generate_prompts, e, pr, min_gen_len, bp, toks, lens, scores)
+            return toks, lens, scores
         plen = len(prompt)
         max_len, min_len = self._length_limits(plen, min_gen_len, max_gen_len, max_seq_len, source_len)
         bp = _lib.smi_beam_search_params(beam_size=beam_size, max_seq_len=max_len, min_seq_len=min_len,
@@ -400,7 +491,8 @@ class TextDecoderEngine:
         scores fp32 [n]).  `unk_penalty` is subtracted from the UNK token's probability before the filter, as the
         reference's generator does.  `seed` None draws one from torch's global CPU generator, so
         `torch.manual_seed` makes a run repeatable as it does for the reference; the random stream of a
-        sentence depends on (seed, sentence_offset + its index, step) only, not on the batch.  `step_processors`: see
+        sentence depends on (seed, sentence_offset + its index, step) only, not on the batch.  `prompt`: one prompt or one
+        per sentence, as in generate() (smi_text_decoder_sample_prompts).  `step_processors`: see
         `set_step_processors`; a banned token's probability is 0 before the filter."""
         from .generation import resolve_sampler
 
@@ -415,9 +507,21 @@ class TextDecoderEngine:
                 len_penalty, unk_penalty, temperature, seed, sentence_offset, source_len):
         e = self._emb(embeddings)
         n = e.shape[0]
+        seed = (int(seed) + 0x9E3779B97F4A7C15 * 65536 * int(sentence_offset)) & 0xFFFFFFFFFFFFFFFF
+        nested, prompt = split_prompts(prompt)
+        if nested:
+            pr = self._prompt_rows(prompt, n, min_gen_len, max_gen_len, max_seq_len, source_len)
+            sp = _lib.smi_sampling_params(sampler=kind, top_k=k, top_p=p, temperature=temperature, max_seq_len=pr.model_max,
+                                          min_seq_len=0, normalize_scores=1 if normalize_scores else 0,
+                                          len_penalty=len_penalty, seed=seed, unk_penalty=unk_penalty)
+            toks = torch.empty((n, pr.width), dtype=torch.int32, device=self.device)
+            lens = torch.empty((n,), dtype=torch.int32, device=self.device)
+            scores = torch.empty((n,), dtype=torch.float32, device=self.device)
+            if n:
+                self._call_prompts(self.lib.smi_text_decoder_sample_prompts, e, pr, min_gen_len, sp, toks, lens, scores)
+            return toks, lens, scores
         plen = len(prompt)
         max_len, min_len = self._length_limits(plen, min_gen_len, max_gen_len, max_seq_len, source_len)
-        seed = (int(seed) + 0x9E3779B97F4A7C15 * 65536 * int(sentence_offset)) & 0xFFFFFFFFFFFFFFFF
         sp = _lib.smi_sampling_params(sampler=kind, top_k=k, top_p=p, temperature=temperature, max_seq_len=max_len,
                                       min_seq_len=min_len, normalize_scores=1 if normalize_scores else 0,
                                       len_penalty=len_penalty, seed=seed, unk_penalty=unk_penalty)
