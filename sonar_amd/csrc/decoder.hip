@@ -826,44 +826,30 @@ __global__ __launch_bounds__(256) void vocab_select_banned_kernel(
   }
 }
 
-hipError_t launch_vocab_select_banned(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
-                                      const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx,
-                                      int eos_idx, int unk_idx, float unk_penalty, int block_eos, const int32_t* hist,
-                                      int hist_stride, int hist_len, const StepProcDev& proc, float* pmax, float* psum,
-                                      float* pval, int* pidx, hipStream_t stream, const PromptTableDev* table, int group,
-                                      int step_nr) {
-  if (rows <= 0 || stat_rows < rows || ntiles <= 0 || ntiles > 2048 || k2 < 0 || k2 > VS_K2MAX || (int64_t)ntiles * 256 < vocab)
+hipError_t launch_vocab_select(const VocabSelectArgs& a, hipStream_t stream) {
+  if (a.rows <= 0 || a.stat_rows < a.rows || a.ntiles <= 0 || a.ntiles > 2048 || a.k2 < 0 || a.k2 > VS_K2MAX ||
+      (int64_t)a.ntiles * 256 < a.vocab)
     return hipErrorInvalidValue;
-  if (table && (!table->tok || !table->len || group < 1)) return hipErrorInvalidValue;
-  if (!hist || hist_len < 1 || hist_len > kStepProcMaxLen || hist_stride < hist_len || proc.num_banned < 0 ||
-      proc.num_banned > kStepProcMaxBanned || (proc.num_banned > 0 && (!proc.tokens || !proc.offsets)))
-    return hipErrorInvalidValue;
-  if (table)
-    hipLaunchKernelGGL(vocab_select_banned_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
-                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, hist,
-                       hist_stride, hist_len, proc, pmax, psum, pval, pidx, *table, group, step_nr);
-  else
-    hipLaunchKernelGGL(vocab_select_banned_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
-                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, hist,
-                       hist_stride, hist_len, proc, pmax, psum, pval, pidx, PromptTableDev{}, 1, 0);
-  return hipGetLastError();
-}
-
-hipError_t launch_vocab_select(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
-                               const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx,
-                               int unk_idx, float unk_penalty, int block_eos, float* pmax, float* psum, float* pval,
-                               int* pidx, hipStream_t stream, const PromptTableDev* table, int group, int step_nr) {
-  if (rows <= 0 || stat_rows < rows || ntiles <= 0 || ntiles > 2048 || k2 < 0 || k2 > VS_K2MAX || (int64_t)ntiles * 256 < vocab)
-    return hipErrorInvalidValue;
-  if (table && (!table->tok || !table->len || group < 1)) return hipErrorInvalidValue;
-  if (table)
-    hipLaunchKernelGGL(vocab_select_kernel<true>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
-                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, pmax, psum,
-                       pval, pidx, *table, group, step_nr);
-  else
-    hipLaunchKernelGGL(vocab_select_kernel<false>, dim3(rows), dim3(256), 0, stream, logits, ldl, f16_tm, vocab, tile_max,
-                       tile_sum, ntiles, stat_rows, k2, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos, pmax, psum,
-                       pval, pidx, PromptTableDev{}, 1, 0);
+  const bool table = a.table.tok != nullptr;
+  if (table && (!a.table.len || a.group < 1)) return hipErrorInvalidValue;
+  // without a table the kernels read no table argument: they get the empty one
+  const PromptTableDev tab = table ? a.table : PromptTableDev{};
+  const int group = table ? a.group : 1, step_nr = table ? a.step_nr : 0;
+  if (a.hist && a.proc.active()) {
+    const StepProcDev& proc = a.proc;
+    if (a.hist_len < 1 || a.hist_len > kStepProcMaxLen || a.hist_stride < a.hist_len || proc.num_banned < 0 ||
+        proc.num_banned > kStepProcMaxBanned || (proc.num_banned > 0 && (!proc.tokens || !proc.offsets)))
+      return hipErrorInvalidValue;
+    hipLaunchKernelGGL(table ? vocab_select_banned_kernel<true> : vocab_select_banned_kernel<false>, dim3(a.rows), dim3(256), 0,
+                       stream, a.logits, a.ldl, a.f16_tm, a.vocab, a.tile_max, a.tile_sum, a.ntiles, a.stat_rows, a.k2, a.inv_temp,
+                       a.pad_idx, a.eos_idx, a.unk_idx, a.unk_penalty, a.block_eos, a.hist, a.hist_stride, a.hist_len, proc,
+                       a.pmax, a.psum, a.pval, a.pidx, tab, group, step_nr);
+  } else {
+    hipLaunchKernelGGL(table ? vocab_select_kernel<true> : vocab_select_kernel<false>, dim3(a.rows), dim3(256), 0, stream,
+                       a.logits, a.ldl, a.f16_tm, a.vocab, a.tile_max, a.tile_sum, a.ntiles, a.stat_rows, a.k2, a.inv_temp,
+                       a.pad_idx, a.eos_idx, a.unk_idx, a.unk_penalty, a.block_eos, a.pmax, a.psum, a.pval, a.pidx, tab, group,
+                       step_nr);
+  }
   return hipGetLastError();
 }
 

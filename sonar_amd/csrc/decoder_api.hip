@@ -25,15 +25,21 @@ inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
 
 constexpr int kMaxParts = 16;  // split-K slabs the `parts` buffer holds
 
+// step processors on the device: the banned sequences as a CSR in buffers of its own, and what the kernels get of it
+struct StepProcTable {
+  DevBuf tok, off;
+  StepProcDev dev{};
+};
+
 }  // namespace
 
 // Per-call workspace of ONE decode chain (grow-only).  smi_text_decoder_generate may split a batch into several
 // chains of whole sentences: they share nothing but the weights, so each owns its activations, KV cache, beam state
 // and stream, and their launch sequences overlap on the GPU.
-// A/B switches of the decode step, read from the environment when a generate / sample / logits call starts:
-// SMI_DEC_KS_OUT, SMI_DEC_KS_FFN (split-K parts of the attention-output / FFN-output projections; 0 = automatic,
-// KS_OUT 1 = no split), SMI_DEC_FFN1_ENGINE (-1 automatic, 0 the GEMM's own choice, 1 = 128x128, 2 = 256x256),
-// SMI_DEC_LOGITS_GRID (persistent workgroups of a chained call's logits GEMM; 0 = all CUs)
+// A/B switches of the decode step, read from the tuning registry (tuning.hpp, smi_tuning_set; never from the environment)
+// when a generate / sample / logits call starts: TUNE_DEC_KS_OUT, TUNE_DEC_KS_FFN (split-K parts of the attention-output /
+// FFN-output projections; 0 = automatic, KS_OUT 1 = no split), TUNE_DEC_FFN1_ENGINE (-1 automatic, 0 the GEMM's own choice,
+// 1 = 128x128, 2 = 256x256), TUNE_DEC_LOGITS_GRID (persistent workgroups of a chained call's logits GEMM; 0 = all CUs)
 struct DecTuning {
   int ks_out = 0, ks_ffn = 0, ffn1_engine = -1, logits_grid = 0;
   void read() {
@@ -75,15 +81,10 @@ struct smi_text_decoder {
   hipEvent_t fork_ev = nullptr;
   DevBuf margins;       // [n][2] decision margins of the last generate() call
   int margins_n = 0;
-  int chains = 0;       // smi_text_decoder_set_chains: 0 = SMI_DEC_CHAINS / the default
+  int chains = 0;       // smi_text_decoder_set_chains: 0 = TUNE_DEC_CHAINS / the default
   int beam_logits_f16 = 0;  // smi_text_decoder_set_beam_logits_dtype: the beam search's logits are stored in fp16
   int beam_slab_f16 = 0;    // smi_text_decoder_set_slab_dtype: the beam search's split-K partial sums are stored in fp16
-  // smi_text_decoder_set_step_processors: n-gram size (0 = off) and the banned sequences (device CSR, read by every chain)
-  int sp_ngram = 0, sp_num_banned = 0;
-  DevBuf sp_tokens, sp_offsets;
-  StepProcDev step_proc() const {
-    return StepProcDev{sp_ngram, sp_num_banned, sp_tokens.as<int32_t>(), sp_offsets.as<int32_t>()};
-  }
+  StepProcTable sp;  // smi_text_decoder_set_step_processors (dev.ngram 0 = off); read by every chain
   int64_t weight_bytes = 0;
   int ffn_tile_major = 0;  // FFN weights stored tile-major (d, f multiples of 256)
   // Generic-dimension mode (flex.hip): head_dim != 64 or dimensions the MFMA engines do not tile for (the reference's
@@ -118,6 +119,12 @@ int check_dec_cfg(const smi_text_decoder_config& c, bool* flex) {
   *flex = !fast;
   return SMI_OK;
 }
+
+// the sentence vectors of every entry point: fp32 or fp16 rows of input_dim elements
+int check_emb_dtype(int emb_dtype) {
+  return emb_dtype == SMI_F32 || emb_dtype == SMI_F16 ? SMI_OK : fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
+}
+size_t emb_row_bytes(const smi_text_decoder_config& c, int emb_dtype) { return (size_t)c.input_dim * (emb_dtype == SMI_F32 ? 4 : 2); }
 
 // per-sentence cross-attention constants cc[l][s] = W_o (W_v e_s + b_v) + b_o  (fp32 [L][n_pad][d])
 int compute_cross_constants(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dtype, int n, int n_pad,
@@ -221,7 +228,7 @@ int decoder_step(smi_text_decoder* D, DecWork& S, int rows, int rows_pad, int gr
   // shrinks 20.0 -> 15.3 us but its 256 KiB slab store grows 4.3 -> 6.4 us (the slab writes run at the chip's
   // ~9.8 TB/s write path either way) and the fold reads 4 more slabs (profiles/r03_experiments.txt).
   // Attention output (K = d): as many parts as keep every 128x128 unit on a CU of its own (2 at 1280 rows: 160 units
-  // on the lone-tile ring engine); SMI_DEC_KS_OUT overrides for A/B runs, 1 = no split, residual epilogue.
+  // on the lone-tile ring engine); TUNE_DEC_KS_OUT overrides for A/B runs, 1 = no split, residual epilogue.
   const DecTuning& tu = S.tuning;
   // (an override the slab buffer or the K split cannot take falls back to the automatic choice)
   const bool ks_out_ok = tu.ks_out >= 1 && tu.ks_out <= kMaxParts && d % (64 * tu.ks_out) == 0;
@@ -340,7 +347,7 @@ int grow_kv(smi_text_decoder* D, DecWork& S, int rows_pad, int positions, hipStr
 
 constexpr int kKvInitialPositions = 160;
 
-// Number of independent chains for a beam-search call (smi_text_decoder_set_chains / SMI_DEC_CHAINS override).
+// Number of independent chains for a beam-search call (smi_text_decoder_set_chains, or the tuning switch TUNE_DEC_CHAINS).
 // Measured on the `basic` decoder, beam 5, ms per step (profiles/r04_experiments.txt, experiment 1):
 //   sentences (rows)   1 chain   2 chains   3 chains   4 chains
 //   256  (1280)          3.88      4.16-4.25    4.97
@@ -369,104 +376,158 @@ int record_table_use(DecWork& S, hipStream_t stream) {
   return SMI_OK;
 }
 
-// Per-sentence prompts of a call or of one sentence group of it: the host copy the launch schedule is
-// planned from, and the device table the kernels read.
-struct PromptSpec {
-  const int64_t* tok;   // host [n][stride], left-aligned
-  const int32_t* len;   // host [n]
-  int stride;
-  int gen_cap, min_gen, model_max;
-  int width;            // max over the CALL's sentences of max_len_s: the output row length
-  PromptTableDev dev;   // the same n sentences on the device
-  int max_len(int s) const { return std::min(len[s] + gen_cap, model_max); }
-  int min_len(int s) const { return std::min(len[s] + min_gen, max_len(s)); }
-  PromptSpec slice(int s0) const {
-    PromptSpec q = *this;
-    q.tok += (size_t)s0 * stride;
-    q.len += s0;
-    q.dev.tok += (size_t)s0 * stride;
-    q.dev.len += s0;
-    return q;
-  }
-};
-
-// What the n sentences of a group have in common at each step: where every sentence is in the same mode the step keeps
-// the one-prompt launches (scalar mode), and only the steps in between read the table.
+// The prompts and length limits of a generate / sample call, or of one sentence group of it: what the
+// launch schedule is planned from.  Per-sentence prompts (the *_prompts entries): sentence s has the prompt
+// tok[s * stride .. + len[s]) and its own max_len_s / min_len_s, and `dev` is the same n sentences on the device.  A call
+// with ONE prompt is the degenerate plan: stride 0 (every sentence reads tok[0 ..]), no `len`, no device table
+// (dev.tok == nullptr), every range below a single value.
 struct PromptPlan {
+  int n = 0;
+  const int64_t* tok = nullptr;  // host, left-aligned rows
+  const int32_t* len = nullptr;  // host [n]
+  int stride = 0;
+  int width = 0;                 // max over the CALL's sentences of max_len_s: the output row length
+  PromptTableDev dev{};
+  // over the n sentences: prompt lengths, min_len_s, max_len_s
   int pmin = 0, pmax = 0, minlen_lo = 0, minlen_hi = 0, maxlen_lo = 0, maxlen_hi = 0;
-  PromptPlan() = default;  // a one-prompt call: not consulted
-  PromptPlan(const PromptSpec& ps, int n) {
-    pmin = minlen_lo = maxlen_lo = INT32_MAX;
-    pmax = minlen_hi = maxlen_hi = 0;
-    for (int s = 0; s < n; ++s) {
-      pmin = std::min(pmin, (int)ps.len[s]); pmax = std::max(pmax, (int)ps.len[s]);
-      minlen_lo = std::min(minlen_lo, ps.min_len(s)); minlen_hi = std::max(minlen_hi, ps.min_len(s));
-      maxlen_lo = std::min(maxlen_lo, ps.max_len(s)); maxlen_hi = std::max(maxlen_hi, ps.max_len(s));
+
+  bool one_prompt() const { return dev.tok == nullptr; }
+  // the prompt length the kernels get as a scalar (per-sentence prompts: they take it from the table)
+  int scalar_prompt_len() const { return one_prompt() ? pmax : 0; }
+
+  static PromptPlan one(int n, const int64_t* prompt, int prompt_len, int max_len, int min_len) {
+    PromptPlan p;
+    p.n = n; p.tok = prompt; p.width = max_len;
+    p.pmin = p.pmax = prompt_len;
+    p.minlen_lo = p.minlen_hi = min_len;
+    p.maxlen_lo = p.maxlen_hi = max_len;
+    return p;
+  }
+  // the sentences [s0, s0 + ng) of a per-sentence plan (dev holds gen_cap / min_gen / model_max)
+  PromptPlan group(int s0, int ng) const {
+    PromptPlan p = *this;
+    p.n = ng;
+    if (one_prompt()) return p;
+    p.tok += (size_t)s0 * stride; p.len += s0;
+    p.dev.tok += (size_t)s0 * stride; p.dev.len += s0;
+    p.pmin = p.minlen_lo = p.maxlen_lo = INT32_MAX;
+    p.pmax = p.minlen_hi = p.maxlen_hi = 0;
+    for (int s = 0; s < ng; ++s) {
+      const int pl = p.len[s], mx = std::min(pl + dev.gen_cap, dev.model_max), mn = std::min(pl + dev.min_gen, mx);
+      p.pmin = std::min(p.pmin, pl); p.pmax = std::max(p.pmax, pl);
+      p.minlen_lo = std::min(p.minlen_lo, mn); p.minlen_hi = std::max(p.minlen_hi, mn);
+      p.maxlen_lo = std::min(p.maxlen_lo, mx); p.maxlen_hi = std::max(p.maxlen_hi, mx);
     }
+    return p;
   }
-  bool all_forced(int step_nr) const { return step_nr < pmin; }
-  bool all_force_eos(int step_nr) const { return step_nr >= pmax && maxlen_lo == maxlen_hi && step_nr == maxlen_lo - 1; }
-  // every sentence on a free step, and all of them on the same side of their min_len
-  bool all_free(int step_nr, bool* block_eos) const {
-    if (step_nr < pmax || step_nr >= maxlen_lo - 1) return false;
-    if (step_nr < minlen_lo) { *block_eos = true; return true; }
-    if (step_nr >= minlen_hi) { *block_eos = false; return true; }
-    return false;
-  }
-  bool uniform_prompt_len() const { return pmin == pmax; }
 };
 
-// checks the prompts of a *_prompts call, fills `tab` (int32 tokens [n][stride], then lengths [n]) and *width
-int check_prompts(const smi_text_decoder_config& c, int n, const int64_t* prompts, int stride, const int32_t* lens, int gen_cap,
-                  int min_gen, int model_max, std::vector<int32_t>* tab, int* width) {
+// What the plan's sentences have in common at the step that chooses token `step_nr`.  Where every sentence is in one mode
+// the step keeps the one-prompt launches (scalar arguments); only a kMixed step -- and a forced step whose tokens differ
+// (forced_tok < 0) -- makes the kernels take each sentence's mode from the table.  A one-prompt plan is never mixed.
+struct StepMode {
+  enum Kind { kForced, kForceEos, kFree, kMixed } kind;
+  int forced_tok;  // kForced: the prompt token every sentence takes, or -1 (per-sentence prompts)
+  bool block_eos;  // kFree: every sentence is below its min_len
+  bool free_step() const { return kind == kFree || kind == kMixed; }
+};
+StepMode step_mode(const PromptPlan& p, int step_nr) {
+  if (step_nr < p.pmin) return {StepMode::kForced, p.one_prompt() ? (int)p.tok[step_nr] : -1, false};
+  if (step_nr >= p.pmax && p.maxlen_lo == p.maxlen_hi && step_nr == p.maxlen_lo - 1) return {StepMode::kForceEos, -1, false};
+  // every sentence on a free step, and all of them on the same side of their min_len
+  if (step_nr >= p.pmax && step_nr < p.maxlen_lo - 1) {
+    if (step_nr < p.minlen_lo) return {StepMode::kFree, -1, true};
+    if (step_nr >= p.minlen_hi) return {StepMode::kFree, -1, false};
+  }
+  return {StepMode::kMixed, -1, false};
+}
+
+// The plan of a one-prompt call: bp / sp carry absolute lengths that hold for every sentence.
+int plan_one_prompt(const smi_text_decoder_config& c, int n, const int64_t* prompt, int prompt_len, int max_len, int min_len,
+                    PromptPlan* plan) {
+  if (prompt_len <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (max_len > c.max_seq_len || max_len <= prompt_len)
+    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in (prompt_len %d, model max %d]", max_len, prompt_len,
+                c.max_seq_len);
+  for (int i = 0; i < prompt_len; ++i)
+    if (prompt[i] < 0 || prompt[i] >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "prompt token out of range");
+  *plan = PromptPlan::one(n, prompt, prompt_len, max_len, min_len);
+  return SMI_OK;
+}
+
+// The plan of a *_prompts call: max_len_s = min(len_s + gen_cap, model_max), min_len_s = min(len_s + min_gen, max_len_s).
+// Checks the prompts; if they are all equal the call IS a one-prompt call and gets that plan (launch for launch), else the
+// table (int32 tokens [n][stride], then lengths [n]) goes to D->ws[0].prompt_dev, uploaded on return.
+int plan_prompts(smi_text_decoder* D, int n, const int64_t* prompts, int stride, const int32_t* lens, int gen_cap, int min_gen,
+                 int model_max, hipStream_t stream, PromptPlan* plan) {
+  const smi_text_decoder_config& c = D->cfg;
   if (stride < 1) return fail(SMI_ERR_INVALID_ARG, "prompt_stride %d must be positive", stride);
   if (gen_cap < 1 || min_gen < 0) return fail(SMI_ERR_INVALID_ARG, "gen_cap %d must be >= 1 and min_gen_len %d >= 0", gen_cap, min_gen);
   if (model_max > c.max_seq_len || model_max < 2)
     return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in [2, model max %d]", model_max, c.max_seq_len);
-  tab->assign((size_t)n * stride + n, 0);
-  *width = 0;
+  std::vector<int32_t> tab((size_t)n * stride + n, 0);
+  int width = 0;
+  bool all_equal = true;
   for (int s = 0; s < n; ++s) {
     const int pl = lens[s];
     if (pl < 1 || pl > stride) return fail(SMI_ERR_INVALID_ARG, "prompt_lens[%d] = %d outside [1, prompt_stride %d]", s, pl, stride);
     if (std::min(pl + gen_cap, model_max) <= pl)
       return fail(SMI_ERR_INVALID_ARG, "row %d: max_seq_len %d leaves no room for generation after its prompt of %d tokens", s,
                   model_max, pl);
+    all_equal = all_equal && pl == lens[0];
     for (int i = 0; i < pl; ++i) {
       const int64_t t = prompts[(size_t)s * stride + i];
       if (t < 0 || t >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "row %d: prompt token %lld out of range", s, (long long)t);
-      (*tab)[(size_t)s * stride + i] = (int32_t)t;
+      tab[(size_t)s * stride + i] = (int32_t)t;
+      all_equal = all_equal && (i >= lens[0] || t == prompts[i]);
     }
-    (*tab)[(size_t)n * stride + s] = pl;
-    *width = std::max(*width, std::min(pl + gen_cap, model_max));
+    tab[(size_t)n * stride + s] = pl;
+    width = std::max(width, std::min(pl + gen_cap, model_max));
   }
-  return SMI_OK;
-}
-
-// the call's table -> D->ws[0].prompt_dev (stream-ordered upload, finished on return: `tab` is the caller's)
-int upload_prompt_table(smi_text_decoder* D, const std::vector<int32_t>& tab, int n, int stride, hipStream_t stream,
-                        PromptTableDev* dev) {
+  if (all_equal) {  // every max_len_s is the width
+    *plan = PromptPlan::one(n, prompts, lens[0], width, std::min(lens[0] + min_gen, width));
+    return SMI_OK;
+  }
   DevBuf& b = D->ws[0].prompt_dev;
   HIP_TRY(b.reserve(tab.size() * 4));
   HIP_TRY(hipMemcpyAsync(b.p, tab.data(), tab.size() * 4, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipStreamSynchronize(stream));
-  dev->tok = b.as<int32_t>();
-  dev->len = b.as<int32_t>() + (size_t)n * stride;
-  dev->stride = stride;
+  PromptPlan whole;
+  whole.tok = prompts; whole.len = lens; whole.stride = stride; whole.width = width;
+  whole.dev = PromptTableDev{b.as<int32_t>(), b.as<int32_t>() + (size_t)n * stride, stride, gen_cap, min_gen, model_max};
+  *plan = whole.group(0, n);
+  return SMI_OK;
+}
+
+// has every one of the n sentences finished?  (waits for the work queued on `stream`)
+int all_sentences_done(DecWork& S, int n, hipStream_t stream, bool* done) {
+  int32_t nd = 0;
+  HIP_TRY(hipMemcpyAsync(&nd, S.ndone.p, 4, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  *done = nd >= n;
+  return SMI_OK;
+}
+
+// one hypothesis per sentence: anc[0][r][j] = r for the n rows (finished on return)
+int upload_identity_ancestry(DecWork& S, int n, int stride, hipStream_t stream) {
+  std::vector<int32_t> ident((size_t)n * stride);
+  for (int r = 0; r < n; ++r)
+    for (int j = 0; j < stride; ++j) ident[(size_t)r * stride + j] = r;
+  HIP_TRY(hipMemcpyAsync(S.anc[0].p, ident.data(), ident.size() * 4, hipMemcpyHostToDevice, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
   return SMI_OK;
 }
 
 // One decode chain: beam search for the n sentences of `emb` on workspace S and stream `stream` (the whole call, or
-// one sentence group of a split call).  margins: device [n][2].  ps: the group's per-sentence prompts, or null: every
-// sentence starts with `prompt` (bp->max_seq_len / min_seq_len then hold for all of them).
-int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dtype, int n, const int64_t* prompt,
-                   int prompt_len, const PromptSpec* ps, const smi_beam_search_params* bp, int32_t* out_tokens,
-                   int32_t* out_lens, float* out_scores, float* margins, hipStream_t stream) {
+// one sentence group of a split call).  margins: device [n][2].  The plan carries the prompts and the length limits
+// (bp->max_seq_len / min_seq_len are not read here).
+int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dtype, const PromptPlan& plan,
+                   const smi_beam_search_params* bp, int32_t* out_tokens, int32_t* out_lens, float* out_scores,
+                   float* margins, hipStream_t stream) {
   const smi_text_decoder_config& c = D->cfg;
-  const int beam = bp->beam_size;
-  const PromptPlan plan = ps ? PromptPlan(*ps, n) : PromptPlan();
-  // per-sentence prompts: the loop runs to the group's longest cap, the output rows are as wide as the call's
-  const int max_len = ps ? plan.maxlen_hi : bp->max_seq_len, min_len = bp->min_seq_len;
-  const int out_stride = ps ? ps->width : max_len;
+  const int n = plan.n, beam = bp->beam_size;
+  // the loop runs to the group's longest cap, the output rows are as wide as the call's
+  const int max_len = plan.maxlen_hi, out_stride = plan.width;
 
   const int rows = n * beam;
   const int rows_pad = (int)round_up(rows, 256), n_pad = (int)round_up(n, 256);
@@ -501,14 +562,14 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
   HIP_TRY(launch_beam_init(S.tok.as<int32_t>(), S.cum.as<float>(), S.nactive.as<int32_t>(),
                            S.done.as<int32_t>(), S.ndone.as<int32_t>(), S.fin_count.as<int32_t>(),
                            S.hist[0].as<int32_t>(), S.anc[0].as<int32_t>(), margins, rows, n, stride,
-                           ps ? 0 : (int)prompt[0], stream, ps ? ps->dev.tok : nullptr, ps ? ps->dev.stride : 0, beam));
+                           plan.one_prompt() ? (int)plan.tok[0] : 0, stream, plan.dev.tok, plan.dev.stride, beam));
   const float inv_temp = 1.0f / bp->temperature;
-  // fp16 logits: the handle's setting (SMI_DEC_LOGITS_F16 = 0 / 1 overrides it: A/B runs), MFMA path with the tile-major table
+  // fp16 logits: the handle's setting (the tuning switch TUNE_DEC_LOGITS_F16 = 0 / 1 overrides it: A/B runs), MFMA path with the tile-major table
   const int lf_env = tune(TUNE_DEC_LOGITS_F16, -1);
   const int logits_f16 = !D->flex && D->embed_tm.p != nullptr && (lf_env >= 0 ? lf_env != 0 : D->beam_logits_f16 != 0);
   const int sf_env = tune(TUNE_DEC_SLAB_F16, -1);
   const int slab_f16 = !D->flex && (sf_env >= 0 ? sf_env != 0 : D->beam_slab_f16 != 0);
-  const StepProcDev proc = D->step_proc();
+  const StepProcDev proc = D->sp.dev;
 
   // everything one decode step enqueues (position pos; ancestry/history buffer pos & 1)
   auto enqueue_step = [&](int pos, hipStream_t s) -> int {
@@ -516,35 +577,22 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     if (int rc = decoder_step(D, S, rows, rows_pad, beam, n_pad, pos, S.anc[cur].as<int32_t>(), stride, s, inv_temp,
                               logits_f16, slab_f16))
       return rc;
-    // The step's mode.  One prompt: the same for every sentence.  Per-sentence prompts: where the plan finds every sentence
-    // in one mode the step is launched as a one-prompt step (scalar); the steps in between are `mixed` and the kernels take
-    // each sentence's mode from the table.
-    bool forced_prompt = step_nr < prompt_len;
-    bool force_eos = !forced_prompt && step_nr == max_len - 1;
-    bool block_eos = !forced_prompt && !force_eos && step_nr < min_len;
-    bool mixed = false;
-    if (ps) {
-      forced_prompt = plan.all_forced(step_nr);
-      force_eos = plan.all_force_eos(step_nr);
-      block_eos = false;
-      mixed = !forced_prompt && !force_eos && !plan.all_free(step_nr, &block_eos);
-    }
+    const StepMode mode = step_mode(plan, step_nr);
     // forced steps need only the softmax normaliser (the candidate is a given token): k2 = 0
-    const bool free_step = !forced_prompt && !force_eos;
-    const PromptTableDev* sel_table = mixed ? &ps->dev : nullptr;
+    const bool free_step = mode.free_step();
+    VocabSelectArgs v{};
+    v.logits = S.logits.as<float>(); v.ldl = (int)D->vocab_pad; v.f16_tm = logits_f16; v.rows = rows; v.vocab = (int)c.vocab_size;
+    v.tile_max = S.tile_max.as<float>(); v.tile_sum = S.tile_sum.as<float>(); v.ntiles = ntiles; v.stat_rows = rows_pad;
+    v.k2 = free_step ? k2 : 0; v.inv_temp = inv_temp; v.pad_idx = c.pad_idx; v.eos_idx = c.eos_idx; v.unk_idx = c.unk_idx;
+    v.unk_penalty = free_step ? bp->unk_penalty : 0.f; v.block_eos = mode.block_eos ? 1 : 0;
+    v.pmax = S.pmax.as<float>(); v.psum = S.psum.as<float>(); v.pval = S.pval.as<float>(); v.pidx = S.pidx.as<int>();
     // step processors act on the free steps only, on the row's sequence so far hist[cur][r][0 .. pos]
-    if (free_step && proc.active())
-      HIP_TRY(launch_vocab_select_banned(S.logits.as<float>(), (int)D->vocab_pad, logits_f16, rows, (int)c.vocab_size,
-                                         S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, rows_pad, k2, inv_temp,
-                                         c.pad_idx, c.eos_idx, c.unk_idx, bp->unk_penalty, block_eos ? 1 : 0,
-                                         S.hist[cur].as<int32_t>(), stride, pos + 1, proc, S.pmax.as<float>(),
-                                         S.psum.as<float>(), S.pval.as<float>(), S.pidx.as<int>(), s, sel_table, beam, step_nr));
-    else
-      HIP_TRY(launch_vocab_select(S.logits.as<float>(), (int)D->vocab_pad, logits_f16, rows, (int)c.vocab_size,
-                                  S.tile_max.as<float>(), S.tile_sum.as<float>(), ntiles, rows_pad, free_step ? k2 : 0, inv_temp,
-                                  c.pad_idx, c.eos_idx, c.unk_idx, free_step ? bp->unk_penalty : 0.f,
-                                  block_eos ? 1 : 0, S.pmax.as<float>(), S.psum.as<float>(),
-                                  S.pval.as<float>(), S.pidx.as<int>(), s, sel_table, beam, step_nr));
+    if (free_step && proc.active()) {
+      v.hist = S.hist[cur].as<int32_t>(); v.hist_stride = stride; v.hist_len = pos + 1; v.proc = proc;
+    }
+    if (mode.kind == StepMode::kMixed) v.table = plan.dev;
+    v.group = beam; v.step_nr = step_nr;
+    HIP_TRY(launch_vocab_select(v, s));
     BeamStepArgs a{};
     a.tok = S.tok.as<int32_t>(); a.cum = S.cum.as<float>(); a.nactive = S.nactive.as<int32_t>();
     a.done = S.done.as<int32_t>(); a.ndone = S.ndone.as<int32_t>();
@@ -554,12 +602,12 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     a.margins = margins;
     a.logits = S.logits.as<float>(); a.ldl = (int)D->vocab_pad; a.logits_f16_tm = logits_f16;
     a.pmax = S.pmax.as<float>(); a.psum = S.psum.as<float>(); a.pval = S.pval.as<float>(); a.pidx = S.pidx.as<int>();
-    a.nchunks = 1; a.n = n; a.beam = beam; a.k2 = k2; a.pos = pos; a.prompt_len = prompt_len;
-    a.forced_tok = forced_prompt && !ps ? (int)prompt[step_nr] : -1; a.max_len = max_len;
-    if (ps) {
+    a.nchunks = 1; a.n = n; a.beam = beam; a.k2 = k2; a.pos = pos; a.prompt_len = plan.scalar_prompt_len();
+    a.forced_tok = mode.forced_tok; a.max_len = max_len;
+    if (!plan.one_prompt()) {
       // prompts of one length: past them the sentences differ in nothing the beam step reads -- the one-prompt launch
-      if (plan.uniform_prompt_len() && step_nr >= plan.pmax) a.prompt_len = plan.pmax;
-      else a.table = ps->dev;
+      if (plan.pmin == plan.pmax && step_nr >= plan.pmax) a.prompt_len = plan.pmax;
+      else a.table = plan.dev;
     }
     a.inv_temp = inv_temp; a.len_penalty = bp->len_penalty; a.normalize = bp->normalize_scores;
     a.eos_idx = c.eos_idx; a.hist_stride = stride;
@@ -580,13 +628,11 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     if (pos >= S.kv_positions)
       if (int rc = grow_kv(D, S, rows_pad, std::min(max_len, 2 * S.kv_positions), stream)) return rc;
     if (int rc = enqueue_step(pos, stream)) return rc;
-    // every 8 steps: has every sentence collected its `beam` hypotheses?
-    const bool force_eos = (ps || step_nr >= prompt_len) && step_nr == max_len - 1;
-    if ((step_nr & 7) == 0 || force_eos) {
-      int32_t nd = 0;
-      HIP_TRY(hipMemcpyAsync(&nd, S.ndone.p, 4, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (nd >= n) break;
+    // every 8 steps, and after the last one: has every sentence collected its `beam` hypotheses?
+    if ((step_nr & 7) == 0 || step_nr == max_len - 1) {
+      bool done = false;
+      if (int rc = all_sentences_done(S, n, stream, &done)) return rc;
+      if (done) break;
     }
   }
   HIP_TRY(launch_beam_output(S.fin_tok.as<int32_t>(), S.fin_len.as<int32_t>(), S.fin_score.as<float>(),
@@ -805,7 +851,7 @@ int smi_text_decoder_logits(smi_text_decoder* D, const void* emb, int32_t emb_dt
   if (!D || !emb || !prev_tokens || !out_logits) return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (n <= 0 || t <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
   if (t > D->cfg.max_seq_len) return fail(SMI_ERR_INVALID_ARG, "t=%d exceeds max_seq_len %d", t, D->cfg.max_seq_len);
-  if (emb_dtype != SMI_F32 && emb_dtype != SMI_F16) return fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
+  if (int rc = check_emb_dtype(emb_dtype)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
   DecWork& S = D->ws[0];
   S.chained = false;
@@ -816,13 +862,7 @@ int smi_text_decoder_logits(smi_text_decoder* D, const void* emb, int32_t emb_dt
   // for j < pos only through anc[r][j] = r
   const int stride = D->cfg.max_seq_len + 1;
   HIP_TRY(S.anc[0].reserve((size_t)rows_pad * stride * 4));
-  {
-    std::vector<int32_t> ident((size_t)n * stride);
-    for (int r = 0; r < n; ++r)
-      for (int j = 0; j < stride; ++j) ident[(size_t)r * stride + j] = r;
-    HIP_TRY(hipMemcpyAsync(S.anc[0].p, ident.data(), ident.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-  }
+  if (int rc = upload_identity_ancestry(S, n, stride, stream)) return rc;
   if (int rc = compute_cross_constants(D, S, emb, emb_dtype, n, n_pad, stream)) return rc;
   for (int pos = 0; pos < t; ++pos) {
     HIP_TRY(launch_gather_tokens(prev_tokens, t, pos, S.tok.as<int32_t>(), n, stream));
@@ -838,7 +878,7 @@ int smi_text_decoder_score(smi_text_decoder* D, const void* emb, int32_t emb_dty
                            int32_t t, const int32_t* lens, float* out_logprobs, void* stream_v) {
   if (!D || !emb || !tokens || !lens || !out_logprobs) return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (n <= 0 || t <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  if (emb_dtype != SMI_F32 && emb_dtype != SMI_F16) return fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
+  if (int rc = check_emb_dtype(emb_dtype)) return rc;
   const smi_text_decoder_config& c = D->cfg;
   if (t > c.max_seq_len + 1) return fail(SMI_ERR_INVALID_ARG, "t=%d exceeds max_seq_len + 1 = %d", t, c.max_seq_len + 1);
   int lmax = 1;
@@ -863,7 +903,7 @@ int smi_text_decoder_score(smi_text_decoder* D, const void* emb, int32_t emb_dty
   HIP_TRY(hipMemcpyAsync(S.sc_lens.p, lens, (size_t)n * 4, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemcpyAsync(S.sc_cu.p, cu.data(), cu.size() * 4, hipMemcpyHostToDevice, stream));
   HIP_TRY(hipMemsetAsync(S.sc_bad.p, 0, 4, stream));
-  const size_t emb_row = (size_t)c.input_dim * (emb_dtype == SMI_F32 ? 4 : 2);
+  const size_t emb_row = emb_row_bytes(c, emb_dtype);
   for (int s0 = 0; s0 < n; s0 += per) {
     const int ns = std::min(per, n - s0);
     if (int rc = score_group(D, S, (const char*)emb + s0 * emb_row, emb_dtype, ns, tokens + (size_t)s0 * t, t,
@@ -881,11 +921,16 @@ int smi_text_decoder_score(smi_text_decoder* D, const void* emb, int32_t emb_dty
 
 namespace {
 
-int check_generate_args(const smi_text_decoder* D, const void* emb, int emb_dtype, int n, const smi_beam_search_params* bp,
-                        const void* out_tokens, const void* out_lens, const void* out_scores) {
-  if (!D || !emb || !bp || !out_tokens || !out_lens || !out_scores) return fail(SMI_ERR_INVALID_ARG, "null argument");
+// what the four generate / sample entries check alike (params: the beam-search / sampling parameter struct)
+int check_decode_args(const smi_text_decoder* D, const void* emb, int emb_dtype, int n, bool have_prompts, const void* params,
+                      const void* out_tokens, const void* out_lens, const void* out_scores) {
+  if (!have_prompts || !D || !emb || !params || !out_tokens || !out_lens || !out_scores)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (n <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  if (emb_dtype != SMI_F32 && emb_dtype != SMI_F16) return fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
+  return check_emb_dtype(emb_dtype);
+}
+
+int check_beam_params(const smi_text_decoder* D, const smi_beam_search_params* bp) {
   const int beam = bp->beam_size;
   if (beam < 1 || beam > 8) return fail(SMI_ERR_UNSUPPORTED, "beam_size %d outside [1,8]", beam);
   if (2 * beam >= D->cfg.vocab_size) return fail(SMI_ERR_UNSUPPORTED, "vocabulary too small for beam %d", beam);
@@ -893,13 +938,11 @@ int check_generate_args(const smi_text_decoder* D, const void* emb, int emb_dtyp
   return SMI_OK;
 }
 
-// the checked call: one prompt (ps null; bp carries the lengths) or per-sentence prompts
-int generate_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, const int64_t* prompt, int prompt_len,
-                 const PromptSpec* ps, const smi_beam_search_params* bp, int32_t* out_tokens, int32_t* out_lens,
-                 float* out_scores, hipStream_t stream) {
-  const smi_text_decoder_config& c = D->cfg;
-  const int beam = bp->beam_size;
-  const int max_len = ps ? ps->width : bp->max_seq_len;  // the output row length
+// the checked call
+int generate_run(smi_text_decoder* D, const void* emb, int emb_dtype, const PromptPlan& plan, const smi_beam_search_params* bp,
+                 int32_t* out_tokens, int32_t* out_lens, float* out_scores, hipStream_t stream) {
+  const int n = plan.n, beam = bp->beam_size;
+  const int max_len = plan.width;  // the output row length
   HIP_TRY(D->margins.reserve((size_t)n * 2 * 4));
   D->margins_n = n;
   float* margins = D->margins.as<float>();
@@ -914,8 +957,7 @@ int generate_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, con
   const int chains = decode_chains(D, n, beam);
   if (chains <= 1) {
     D->ws[0].chained = false;
-    return generate_chain(D, D->ws[0], emb, emb_dtype, n, prompt, prompt_len, ps, bp, out_tokens, out_lens, out_scores,
-                          margins, stream);
+    return generate_chain(D, D->ws[0], emb, emb_dtype, plan, bp, out_tokens, out_lens, out_scores, margins, stream);
   }
   int dev = 0;
   HIP_TRY(hipGetDevice(&dev));
@@ -927,7 +969,7 @@ int generate_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, con
   }
   // fork: every chain starts behind the work already queued on the caller's stream (the embeddings' producer)
   HIP_TRY(hipEventRecord(D->fork_ev, stream));
-  const size_t emb_row = (size_t)c.input_dim * (emb_dtype == SMI_F32 ? 4 : 2);
+  const size_t emb_row = emb_row_bytes(D->cfg, emb_dtype);
   const int per = (n + chains - 1) / chains;
   int rcs[kMaxChains] = {};
   std::string errs[kMaxChains];
@@ -943,10 +985,10 @@ int generate_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, con
       if (he == hipSuccess) he = hipStreamWaitEvent(S.stream, D->fork_ev, 0);
       if (he != hipSuccess) rc = fail(SMI_ERR_HIP, "chain %d set-up: %s", g, hipGetErrorString(he));
       if (rc == SMI_OK) {
-        const PromptSpec group = ps ? ps->slice(s0) : PromptSpec{};  // the table is sliced per sentence group
-        rc = generate_chain(D, S, (const char*)emb + (size_t)s0 * emb_row, emb_dtype, ng, prompt, prompt_len,
-                            ps ? &group : nullptr, bp, out_tokens + (size_t)s0 * beam * max_len,
-                            out_lens + (size_t)s0 * beam, out_scores + (size_t)s0 * beam, margins + 2 * (size_t)s0, S.stream);
+        // (per-sentence prompts: the table is sliced per sentence group)
+        rc = generate_chain(D, S, (const char*)emb + (size_t)s0 * emb_row, emb_dtype, plan.group(s0, ng), bp,
+                            out_tokens + (size_t)s0 * beam * max_len, out_lens + (size_t)s0 * beam,
+                            out_scores + (size_t)s0 * beam, margins + 2 * (size_t)s0, S.stream);
       }
       if (rc == SMI_OK && (he = hipEventRecord(S.done_ev, S.stream)) != hipSuccess)
         rc = fail(SMI_ERR_HIP, "chain %d: %s", g, hipGetErrorString(he));
@@ -969,16 +1011,6 @@ int generate_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, con
   return SMI_OK;
 }
 
-// every sentence has the prompt of sentence 0: the call IS a one-prompt call
-bool prompts_all_equal(int n, const int64_t* prompts, int stride, const int32_t* lens) {
-  for (int s = 1; s < n; ++s) {
-    if (lens[s] != lens[0]) return false;
-    for (int i = 0; i < lens[0]; ++i)
-      if (prompts[(size_t)s * stride + i] != prompts[i]) return false;
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -986,42 +1018,24 @@ extern "C" {
 int smi_text_decoder_generate(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
                               const int64_t* prompt, int32_t prompt_len, const smi_beam_search_params* bp,
                               int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
-  if (!prompt) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (int rc = check_generate_args(D, emb, emb_dtype, n, bp, out_tokens, out_lens, out_scores)) return rc;
-  if (prompt_len <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  const smi_text_decoder_config& c = D->cfg;
-  const int max_len = bp->max_seq_len;
-  if (max_len > c.max_seq_len || max_len <= prompt_len)
-    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in (prompt_len %d, model max %d]", max_len, prompt_len,
-                c.max_seq_len);
-  for (int i = 0; i < prompt_len; ++i)
-    if (prompt[i] < 0 || prompt[i] >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "prompt token out of range");
-  return generate_run(D, emb, emb_dtype, n, prompt, prompt_len, nullptr, bp, out_tokens, out_lens, out_scores,
-                      (hipStream_t)stream_v);
+  if (int rc = check_decode_args(D, emb, emb_dtype, n, prompt != nullptr, bp, out_tokens, out_lens, out_scores)) return rc;
+  if (int rc = check_beam_params(D, bp)) return rc;
+  PromptPlan plan;
+  if (int rc = plan_one_prompt(D->cfg, n, prompt, prompt_len, bp->max_seq_len, bp->min_seq_len, &plan)) return rc;
+  return generate_run(D, emb, emb_dtype, plan, bp, out_tokens, out_lens, out_scores, (hipStream_t)stream_v);
 }
 
 int smi_text_decoder_generate_prompts(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
                                       const int64_t* prompts, int32_t prompt_stride, const int32_t* prompt_lens,
                                       int32_t gen_cap, int32_t min_gen_len, const smi_beam_search_params* bp,
                                       int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
-  if (!prompts || !prompt_lens) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (int rc = check_generate_args(D, emb, emb_dtype, n, bp, out_tokens, out_lens, out_scores)) return rc;
-  std::vector<int32_t> tab;
-  PromptSpec ps{prompts, prompt_lens, prompt_stride, gen_cap, min_gen_len, bp->max_seq_len, 0, {}};
-  if (int rc = check_prompts(D->cfg, n, prompts, prompt_stride, prompt_lens, gen_cap, min_gen_len, bp->max_seq_len, &tab,
-                             &ps.width))
-    return rc;
+  if (int rc = check_decode_args(D, emb, emb_dtype, n, prompts && prompt_lens, bp, out_tokens, out_lens, out_scores)) return rc;
+  if (int rc = check_beam_params(D, bp)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
-  if (prompts_all_equal(n, prompts, prompt_stride, prompt_lens)) {
-    // one prompt after all: the one-prompt call, launch for launch (every max_len_s is the width)
-    smi_beam_search_params one = *bp;
-    one.max_seq_len = ps.width;
-    one.min_seq_len = ps.min_len(0);
-    return generate_run(D, emb, emb_dtype, n, prompts, prompt_lens[0], nullptr, &one, out_tokens, out_lens, out_scores, stream);
-  }
-  ps.dev = PromptTableDev{nullptr, nullptr, prompt_stride, gen_cap, min_gen_len, bp->max_seq_len};
-  if (int rc = upload_prompt_table(D, tab, n, prompt_stride, stream, &ps.dev)) return rc;
-  return generate_run(D, emb, emb_dtype, n, nullptr, 0, &ps, bp, out_tokens, out_lens, out_scores, stream);
+  PromptPlan plan;
+  if (int rc = plan_prompts(D, n, prompts, prompt_stride, prompt_lens, gen_cap, min_gen_len, bp->max_seq_len, stream, &plan))
+    return rc;
+  return generate_run(D, emb, emb_dtype, plan, bp, out_tokens, out_lens, out_scores, stream);
 }
 
 int smi_text_decoder_set_chains(smi_text_decoder* D, int32_t chains) {
@@ -1057,32 +1071,31 @@ int smi_text_decoder_last_margins(smi_text_decoder* D, float* out_margins, int32
 
 namespace {
 
-int check_sample_args(const smi_text_decoder* D, const void* emb, int emb_dtype, int n, const smi_sampling_params* sp,
-                      const void* out_tokens, const void* out_lens, const void* out_scores) {
-  if (!D || !emb || !sp || !out_tokens || !out_lens || !out_scores) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (n <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  if (emb_dtype != SMI_F32 && emb_dtype != SMI_F16) return fail(SMI_ERR_INVALID_ARG, "bad emb dtype");
-  const smi_text_decoder_config& c = D->cfg;
-  if (sp->sampler == SMI_SAMPLER_TOP_K) {
-    if (sp->top_k < 1) return fail(SMI_ERR_INVALID_ARG, "top_k must be >= 1");
-  } else if (sp->sampler == SMI_SAMPLER_TOP_P) {
-    if (!(sp->top_p > 0.f && sp->top_p <= 1.f)) return fail(SMI_ERR_INVALID_ARG, "top_p must be in (0, 1]");
+int check_sampler(int sampler, int top_k, float top_p) {
+  if (sampler == SMI_SAMPLER_TOP_K) {
+    if (top_k < 1) return fail(SMI_ERR_INVALID_ARG, "top_k must be >= 1");
+  } else if (sampler == SMI_SAMPLER_TOP_P) {
+    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SMI_ERR_INVALID_ARG, "top_p must be in (0, 1]");
   } else {
-    return fail(SMI_ERR_INVALID_ARG, "unknown sampler %d", sp->sampler);
+    return fail(SMI_ERR_INVALID_ARG, "unknown sampler %d", sampler);
   }
-  if (c.vocab_size > (1 << 18))
-    return fail(SMI_ERR_UNSUPPORTED, "vocab %d: sampling covers up to 2^18 tokens", (int)c.vocab_size);
+  return SMI_OK;
+}
+
+int check_sampling_params(const smi_text_decoder* D, const smi_sampling_params* sp) {
+  if (int rc = check_sampler(sp->sampler, sp->top_k, sp->top_p)) return rc;
+  if (D->cfg.vocab_size > (1 << 18))
+    return fail(SMI_ERR_UNSUPPORTED, "vocab %d: sampling covers up to 2^18 tokens", (int)D->cfg.vocab_size);
   if (!(sp->temperature > 0.f)) return fail(SMI_ERR_INVALID_ARG, "temperature must be positive");
   return SMI_OK;
 }
 
-// the checked call: one prompt (ps null; sp carries the lengths) or per-sentence prompts (ps->dev uploaded)
-int sample_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, const int64_t* prompt, int prompt_len,
-               const PromptSpec* ps, const smi_sampling_params* sp, int32_t* out_tokens, int32_t* out_lens, float* out_scores,
-               hipStream_t stream) {
+// the checked call (sp->max_seq_len / min_seq_len are not read here: the plan carries the length limits)
+int sample_run(smi_text_decoder* D, const void* emb, int emb_dtype, const PromptPlan& plan, const smi_sampling_params* sp,
+               int32_t* out_tokens, int32_t* out_lens, float* out_scores, hipStream_t stream) {
   const smi_text_decoder_config& c = D->cfg;
-  const int max_len = ps ? ps->width : sp->max_seq_len, min_len = sp->min_seq_len;  // max_len: loop bound and output row length
-  const PromptPlan plan = ps ? PromptPlan(*ps, n) : PromptPlan();
+  const int n = plan.n;
+  const int max_len = plan.width;  // loop bound and output row length (one sentence group: the longest cap)
   // one hypothesis per sentence (fairseq2 num_gens = 1): rows = sentences, identity ancestry
   DecWork& S = D->ws[0];
   S.chained = false;
@@ -1097,18 +1110,15 @@ int sample_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, const
   HIP_TRY(S.new_cum.reserve((size_t)n * 4));
   HIP_TRY(S.anc[0].reserve((size_t)rows_pad * stride * 4));
   {
-    std::vector<int32_t> ident((size_t)n * stride), first((size_t)n, ps ? 0 : (int32_t)prompt[0]);
-    for (int r = 0; r < n; ++r) {
-      for (int j = 0; j < stride; ++j) ident[(size_t)r * stride + j] = r;
-      if (ps) first[r] = (int32_t)ps->tok[(size_t)r * ps->stride];
-    }
-    HIP_TRY(hipMemcpyAsync(S.anc[0].p, ident.data(), ident.size() * 4, hipMemcpyHostToDevice, stream));
+    std::vector<int32_t> first((size_t)n);
+    for (int r = 0; r < n; ++r) first[r] = (int32_t)plan.tok[(size_t)r * plan.stride];
     HIP_TRY(hipMemcpyAsync(S.tok.p, first.data(), first.size() * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
+    if (int rc = upload_identity_ancestry(S, n, stride, stream)) return rc;  // finishes both copies
   }
-  const StepProcDev proc = D->step_proc();
-  if (proc.active() && !ps) {  // the bans read the prompt on the device (per-sentence prompts: from the table)
-    std::vector<int32_t> p32(prompt, prompt + prompt_len);
+  const StepProcDev proc = D->sp.dev;
+  const int prompt_len = plan.scalar_prompt_len();
+  if (proc.active() && plan.one_prompt()) {  // the bans read the prompt on the device (per-sentence prompts: from the table)
+    std::vector<int32_t> p32(plan.tok, plan.tok + prompt_len);
     HIP_TRY(S.prompt_dev.reserve((size_t)prompt_len * 4));
     HIP_TRY(hipMemcpyAsync(S.prompt_dev.p, p32.data(), p32.size() * 4, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
@@ -1126,43 +1136,34 @@ int sample_run(smi_text_decoder* D, const void* emb, int emb_dtype, int n, const
     if (pos >= S.kv_positions)
       if (int rc = grow_kv(D, S, rows_pad, std::min(max_len, 2 * S.kv_positions), stream)) return rc;
     if (int rc = decoder_step(D, S, n, rows_pad, 1, n_pad, pos, S.anc[0].as<int32_t>(), stride, stream)) return rc;
-    // the step's mode, as in generate_chain: the same for every sentence, or `mixed` (the kernel reads the table)
-    bool forced_prompt = step_nr < prompt_len;
-    bool force_eos = !forced_prompt && step_nr == max_len - 1;
-    bool block_eos = !forced_prompt && !force_eos && step_nr < min_len;
-    bool mixed = false;
-    if (ps) {
-      forced_prompt = false;  // the sentences' prompt tokens differ: a forced step reads the table too
-      force_eos = plan.all_force_eos(step_nr);
-      block_eos = false;
-      mixed = !force_eos && !plan.all_free(step_nr, &block_eos);
-    }
+    // the sentences' prompt tokens differ: a forced step reads the table too
+    const StepMode mode = step_mode(plan, step_nr);
+    const bool mixed = mode.kind == StepMode::kMixed || (mode.kind == StepMode::kForced && mode.forced_tok < 0);
     SampleRowsArgs a{};
     a.logits = S.logits.as<float>(); a.ld = D->vocab_pad; a.rows = n; a.vocab = (int)c.vocab_size;
     a.inv_temp = 1.0f / sp->temperature; a.pad_idx = c.pad_idx; a.eos_idx = c.eos_idx;
-    a.block_eos = block_eos;
+    a.block_eos = mode.block_eos;
     a.unk_idx = c.unk_idx; a.unk_penalty = sp->unk_penalty;
-    a.forced_tok = forced_prompt ? (int)prompt[step_nr] : (force_eos ? c.eos_idx : -1);
+    a.forced_tok = mode.kind == StepMode::kForceEos ? c.eos_idx : mode.forced_tok;
     a.mode = sp->sampler; a.top_k = sp->top_k; a.top_p = sp->top_p; a.z = nullptr; a.seed = sp->seed; a.step = step_nr;
     a.done = S.done.as<int32_t>(); a.out_tok = S.new_tok.as<int32_t>(); a.out_logp = S.new_cum.as<float>();
     if (a.forced_tok < 0 && proc.active()) {
       a.proc = proc; a.prompt = S.prompt_dev.as<int32_t>(); a.prompt_len = prompt_len; a.gen = out_tokens; a.gen_stride = max_len;
     }
     // (a free step of every sentence under step processors: the bans still read each row's own prompt)
-    if (mixed || (ps && a.forced_tok < 0 && proc.active())) a.table = ps->dev;
+    if (mixed || (!plan.one_prompt() && a.forced_tok < 0 && proc.active())) a.table = plan.dev;
     HIP_TRY(launch_sample_rows(a, stream));
     SampleUpdateArgs u{};
     u.samp_tok = S.new_tok.as<int32_t>(); u.samp_logp = S.new_cum.as<float>(); u.tok = S.tok.as<int32_t>();
     u.cum = S.cum.as<float>(); u.done = S.done.as<int32_t>(); u.ndone = S.ndone.as<int32_t>();
     u.out_tokens = out_tokens; u.out_lens = out_lens; u.out_scores = out_scores; u.n = n; u.out_stride = max_len;
     u.pos = pos; u.prompt_len = prompt_len; u.eos_idx = c.eos_idx; u.normalize = sp->normalize_scores;
-    u.len_penalty = sp->len_penalty; u.prompt_lens = ps ? ps->dev.len : nullptr;
+    u.len_penalty = sp->len_penalty; u.prompt_lens = plan.dev.len;
     HIP_TRY(launch_sample_update(u, stream));
-    if ((step_nr & 7) == 0 && !force_eos) {
-      int32_t nd = 0;
-      HIP_TRY(hipMemcpyAsync(&nd, S.ndone.p, 4, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));
-      if (nd >= n) break;
+    if ((step_nr & 7) == 0 && mode.kind != StepMode::kForceEos) {  // (after a forced EOS everything is done anyway)
+      bool done = false;
+      if (int rc = all_sentences_done(S, n, stream, &done)) return rc;
+      if (done) break;
     }
   }
   if (proc.active())
@@ -1177,41 +1178,24 @@ extern "C" {
 int smi_text_decoder_sample(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
                             const int64_t* prompt, int32_t prompt_len, const smi_sampling_params* sp,
                             int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
-  if (!prompt) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (int rc = check_sample_args(D, emb, emb_dtype, n, sp, out_tokens, out_lens, out_scores)) return rc;
-  if (prompt_len <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  const smi_text_decoder_config& c = D->cfg;
-  const int max_len = sp->max_seq_len;
-  if (max_len > c.max_seq_len || max_len <= prompt_len)
-    return fail(SMI_ERR_INVALID_ARG, "max_seq_len %d must be in (prompt_len %d, model max %d]", max_len, prompt_len,
-                c.max_seq_len);
-  for (int i = 0; i < prompt_len; ++i)
-    if (prompt[i] < 0 || prompt[i] >= c.vocab_size) return fail(SMI_ERR_INVALID_ARG, "prompt token out of range");
-  return sample_run(D, emb, emb_dtype, n, prompt, prompt_len, nullptr, sp, out_tokens, out_lens, out_scores,
-                    (hipStream_t)stream_v);
+  if (int rc = check_decode_args(D, emb, emb_dtype, n, prompt != nullptr, sp, out_tokens, out_lens, out_scores)) return rc;
+  if (int rc = check_sampling_params(D, sp)) return rc;
+  PromptPlan plan;
+  if (int rc = plan_one_prompt(D->cfg, n, prompt, prompt_len, sp->max_seq_len, sp->min_seq_len, &plan)) return rc;
+  return sample_run(D, emb, emb_dtype, plan, sp, out_tokens, out_lens, out_scores, (hipStream_t)stream_v);
 }
 
 int smi_text_decoder_sample_prompts(smi_text_decoder* D, const void* emb, int32_t emb_dtype, int32_t n,
                                     const int64_t* prompts, int32_t prompt_stride, const int32_t* prompt_lens,
                                     int32_t gen_cap, int32_t min_gen_len, const smi_sampling_params* sp,
                                     int32_t* out_tokens, int32_t* out_lens, float* out_scores, void* stream_v) {
-  if (!prompts || !prompt_lens) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (int rc = check_sample_args(D, emb, emb_dtype, n, sp, out_tokens, out_lens, out_scores)) return rc;
-  std::vector<int32_t> tab;
-  PromptSpec ps{prompts, prompt_lens, prompt_stride, gen_cap, min_gen_len, sp->max_seq_len, 0, {}};
-  if (int rc = check_prompts(D->cfg, n, prompts, prompt_stride, prompt_lens, gen_cap, min_gen_len, sp->max_seq_len, &tab,
-                             &ps.width))
-    return rc;
+  if (int rc = check_decode_args(D, emb, emb_dtype, n, prompts && prompt_lens, sp, out_tokens, out_lens, out_scores)) return rc;
+  if (int rc = check_sampling_params(D, sp)) return rc;
   hipStream_t stream = (hipStream_t)stream_v;
-  if (prompts_all_equal(n, prompts, prompt_stride, prompt_lens)) {  // one prompt after all: the one-prompt call
-    smi_sampling_params one = *sp;
-    one.max_seq_len = ps.width;
-    one.min_seq_len = ps.min_len(0);
-    return sample_run(D, emb, emb_dtype, n, prompts, prompt_lens[0], nullptr, &one, out_tokens, out_lens, out_scores, stream);
-  }
-  ps.dev = PromptTableDev{nullptr, nullptr, prompt_stride, gen_cap, min_gen_len, sp->max_seq_len};
-  if (int rc = upload_prompt_table(D, tab, n, prompt_stride, stream, &ps.dev)) return rc;
-  return sample_run(D, emb, emb_dtype, n, nullptr, 0, &ps, sp, out_tokens, out_lens, out_scores, stream);
+  PromptPlan plan;
+  if (int rc = plan_prompts(D, n, prompts, prompt_stride, prompt_lens, gen_cap, min_gen_len, sp->max_seq_len, stream, &plan))
+    return rc;
+  return sample_run(D, emb, emb_dtype, plan, sp, out_tokens, out_lens, out_scores, stream);
 }
 
 }  // extern "C"
@@ -1242,6 +1226,16 @@ int upload_i32(DevBuf& dst, const int32_t* src, size_t count) {
   HIP_TRY(hipMemcpy(dst.p, src, count * 4, hipMemcpyHostToDevice));
   return SMI_OK;
 }
+
+// checked processors -> the device table (uploaded on return)
+int upload_step_processors(const smi_step_processors* p, StepProcTable* st) {
+  if (p->num_banned > 0) {
+    if (int rc = upload_i32(st->off, p->banned_offsets, (size_t)p->num_banned + 1)) return rc;
+    if (int rc = upload_i32(st->tok, p->banned_tokens, (size_t)p->banned_offsets[p->num_banned])) return rc;
+  }
+  st->dev = StepProcDev{p->ngram_size, p->num_banned, st->tok.as<int32_t>(), st->off.as<int32_t>()};
+  return SMI_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1249,25 +1243,19 @@ extern "C" {
 int smi_text_decoder_set_step_processors(smi_text_decoder* D, const smi_step_processors* procs) {
   if (!D) return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (!procs || (procs->ngram_size == 0 && procs->num_banned == 0)) {
-    D->sp_ngram = D->sp_num_banned = 0;
+    D->sp.dev.ngram = D->sp.dev.num_banned = 0;
     return SMI_OK;
   }
   if (D->cfg.max_seq_len >= kStepProcMaxLen)
     return fail(SMI_ERR_UNSUPPORTED, "step processors cover max_seq_len up to %d", kStepProcMaxLen - 1);
   if (int rc = check_step_processors(procs, D->cfg.vocab_size, D->cfg.max_seq_len)) return rc;
   // stage the new table in buffers of its own: a failed upload leaves the handle's setting as it was
-  DevBuf tok, off;
-  if (procs->num_banned > 0) {
-    if (int rc = upload_i32(off, procs->banned_offsets, (size_t)procs->num_banned + 1)) return rc;
-    if (int rc = upload_i32(tok, procs->banned_tokens, (size_t)procs->banned_offsets[procs->num_banned])) return rc;
-  }
+  StepProcTable st;
+  if (int rc = upload_step_processors(procs, &st)) return rc;
   // the handle's earlier calls may still read the old table: wait for them (not for the rest of the device)
   for (auto& w : D->ws)
     if (w.sp_ev) HIP_TRY(hipEventSynchronize(w.sp_ev));
-  D->sp_offsets = std::move(off);
-  D->sp_tokens = std::move(tok);
-  D->sp_ngram = procs->ngram_size;
-  D->sp_num_banned = procs->num_banned;
+  D->sp = std::move(st);
   return SMI_OK;
 }
 
@@ -1286,18 +1274,16 @@ int smi_vocab_select_banned(const void* logits, int32_t ldl, int32_t logits_f16_
   if (logits_f16_tm && rows % 256) return fail(SMI_ERR_INVALID_ARG, "tile-major logits need rows padded to 256");
   if (int rc = check_step_processors(procs, vocab, kStepProcMaxLen - 1)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  DevBuf tok, off;
-  if (procs->num_banned > 0) {
-    if (int rc = upload_i32(off, procs->banned_offsets, (size_t)procs->num_banned + 1)) return rc;
-    if (int rc = upload_i32(tok, procs->banned_tokens, (size_t)procs->banned_offsets[procs->num_banned])) return rc;
-  }
-  const StepProcDev proc{procs->ngram_size, procs->num_banned, tok.as<int32_t>(), off.as<int32_t>()};
-  if (!proc.active())  // no processor: the engine's default selection, as generate() runs it
-    HIP_TRY(launch_vocab_select((const float*)logits, ldl, logits_f16_tm, rows, vocab, tile_max, tile_sum, ldl / 256, rows, k2,
-                                1.0f, pad_idx, -1, -1, 0.f, 0, pmax, psum, pval, pidx, (hipStream_t)stream));
-  else HIP_TRY(launch_vocab_select_banned((const float*)logits, ldl, logits_f16_tm, rows, vocab, tile_max, tile_sum, ldl / 256,
-                                     rows, k2, 1.0f, pad_idx, -1, -1, 0.f, 0, hist, hist_stride, hist_len, proc, pmax, psum,
-                                     pval, pidx, (hipStream_t)stream));
+  StepProcTable st;
+  if (int rc = upload_step_processors(procs, &st)) return rc;
+  // (no processor in `procs`: the launcher runs the engine's default selection, as generate() does)
+  VocabSelectArgs v{};
+  v.logits = (const float*)logits; v.ldl = ldl; v.f16_tm = logits_f16_tm; v.rows = rows; v.vocab = vocab;
+  v.tile_max = tile_max; v.tile_sum = tile_sum; v.ntiles = ldl / 256; v.stat_rows = rows;
+  v.k2 = k2; v.inv_temp = 1.0f; v.pad_idx = pad_idx; v.eos_idx = -1; v.unk_idx = -1;
+  v.pmax = pmax; v.psum = psum; v.pval = pval; v.pidx = pidx;
+  v.hist = hist; v.hist_stride = hist_stride; v.hist_len = hist_len; v.proc = st.dev;
+  HIP_TRY(launch_vocab_select(v, (hipStream_t)stream));
   // the CSR copies are freed on return: finish with them first
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
   return SMI_OK;
@@ -1313,21 +1299,12 @@ int smi_sample_rows_banned(const float* logits, int64_t ld, int32_t rows, int32_
   if (vocab > (1 << 18)) return fail(SMI_ERR_UNSUPPORTED, "vocab %d: sampling covers up to 2^18 tokens", vocab);
   if (ld % 4 || ld < (vocab + 3) / 4 * 4) return fail(SMI_ERR_INVALID_ARG, "ld %lld must be a multiple of 4 >= vocab", (long long)ld);
   if (!(temperature > 0.f)) return fail(SMI_ERR_INVALID_ARG, "temperature must be positive");
-  if (sampler == SMI_SAMPLER_TOP_K) {
-    if (top_k < 1) return fail(SMI_ERR_INVALID_ARG, "top_k must be >= 1");
-  } else if (sampler == SMI_SAMPLER_TOP_P) {
-    if (!(top_p > 0.f && top_p <= 1.f)) return fail(SMI_ERR_INVALID_ARG, "top_p must be in (0, 1]");
-  } else {
-    return fail(SMI_ERR_INVALID_ARG, "unknown sampler %d", sampler);
-  }
+  if (int rc = check_sampler(sampler, top_k, top_p)) return rc;
   if (hist_len < 1 || hist_len > kStepProcMaxLen - 1) return fail(SMI_ERR_INVALID_ARG, "hist_len %d outside [1, %d]", hist_len, kStepProcMaxLen - 1);
   if (int rc = check_step_processors(procs, vocab, kStepProcMaxLen - 1)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  DevBuf tok, off;
-  if (procs->num_banned > 0) {
-    if (int rc = upload_i32(off, procs->banned_offsets, (size_t)procs->num_banned + 1)) return rc;
-    if (int rc = upload_i32(tok, procs->banned_tokens, (size_t)procs->banned_offsets[procs->num_banned])) return rc;
-  }
+  StepProcTable st;
+  if (int rc = upload_step_processors(procs, &st)) return rc;
   SampleRowsArgs a{};
   a.logits = logits; a.ld = ld; a.rows = rows; a.vocab = vocab; a.inv_temp = 1.0f / temperature;
   a.pad_idx = pad_idx; a.eos_idx = eos_idx; a.block_eos = block_eos; a.forced_tok = -1;
@@ -1336,7 +1313,7 @@ int smi_sample_rows_banned(const float* logits, int64_t ld, int32_t rows, int32_
   a.out_tok = out_token; a.out_logp = out_logprob; a.out_kept_mass = (unsigned long long*)out_kept_mass;
   a.out_kept_count = out_kept_count;
   // every row's sequence so far is hist[0 .. hist_len): a prompt with nothing generated yet
-  a.proc = StepProcDev{procs->ngram_size, procs->num_banned, tok.as<int32_t>(), off.as<int32_t>()};
+  a.proc = st.dev;
   a.prompt = hist; a.prompt_len = hist_len; a.gen = hist; a.gen_stride = 0; a.step = hist_len;
   HIP_TRY(launch_sample_rows(a, (hipStream_t)stream));
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));  // the CSR copies are freed on return

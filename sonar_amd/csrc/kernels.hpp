@@ -198,17 +198,6 @@ __host__ __device__ inline PromptRowMode prompt_row_mode(const PromptTableDev& t
   m.block_eos = m.free_step && step_nr < min_len;
   return m;
 }
-// Per row: softmax normaliser (pmax, psum) from the GEMM's tile statistics and the top-k2 candidates
-// among the k2 best tiles + tile 0 (pval / pidx [rows][kVocabScanK2Max]), without re-reading the whole
-// logits row.
-// f16_tm: the logits are fp16 in the tile-major layout (K = ldl) instead of fp32 [rows][ldl]
-hipError_t launch_vocab_select(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
-                               const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx, int eos_idx,
-                               int unk_idx, float unk_penalty, int block_eos, float* pmax, float* psum, float* pval,
-                               int* pidx, hipStream_t stream, const PromptTableDev* table = nullptr, int group = 1,
-                               int step_nr = 0);
-// (table: row r belongs to sentence r / group and takes block_eos / whether unk_penalty applies from its own mode at step_nr; a
-// row whose sentence is forced there gets its normaliser only.  Both selections.)
 // Step processors (smi_step_processors, device copy): n-gram repeat blocking and banned sequences, CSR on the device
 struct StepProcDev {
   int ngram;              // 0 = off
@@ -219,15 +208,26 @@ struct StepProcDev {
 };
 constexpr int kStepProcMaxLen = 1024;     // longest sequence a processor reads (LDS copy of it)
 constexpr int kStepProcMaxBanned = 1024;  // banned sequences per handle
-// launch_vocab_select with the bans of `proc` applied to the candidates (not to pmax / psum): row r's sequence so far is
-// hist[r][0 .. hist_len) (stride hist_stride).  The candidates are tile 0, the k2 best tiles without a banned id and every
-// tile with one whose maximum reaches the k2-th of those; the result is the top-k2 of the masked row.
-hipError_t launch_vocab_select_banned(const float* logits, int ldl, int f16_tm, int rows, int vocab, const float* tile_max,
-                                      const float* tile_sum, int ntiles, int stat_rows, int k2, float inv_temp, int pad_idx,
-                                      int eos_idx, int unk_idx, float unk_penalty, int block_eos, const int32_t* hist,
-                                      int hist_stride, int hist_len, const StepProcDev& proc, float* pmax, float* psum,
-                                      float* pval, int* pidx, hipStream_t stream, const PromptTableDev* table = nullptr,
-                                      int group = 1, int step_nr = 0);
+// Per row: softmax normaliser (pmax, psum) from the GEMM's tile statistics and the top-k2 candidates
+// among the k2 best tiles + tile 0 (pval / pidx [rows][kVocabScanK2Max]), without re-reading the whole
+// logits row.  k2 = 0: the normaliser only (a forced step).
+struct VocabSelectArgs {
+  const float* logits; int ldl;
+  int f16_tm;  // the logits are fp16 in the tile-major layout (K = ldl) instead of fp32 [rows][ldl]
+  int rows, vocab;
+  const float* tile_max; const float* tile_sum; int ntiles, stat_rows;
+  int k2; float inv_temp; int pad_idx, eos_idx, unk_idx; float unk_penalty; int block_eos;
+  float* pmax; float* psum; float* pval; int* pidx;
+  // Step processors, taken when hist is given and proc.active(): the bans of `proc` are applied to the candidates (not to
+  // pmax / psum); row r's sequence so far is hist[r][0 .. hist_len) (stride hist_stride).  The candidates are then tile 0,
+  // the k2 best tiles without a banned id and every tile with one whose maximum reaches the k2-th of those; the result is
+  // the top-k2 of the masked row.
+  const int32_t* hist; int hist_stride, hist_len; StepProcDev proc;
+  // table.tok != nullptr: row r belongs to sentence r / group and takes block_eos / whether unk_penalty applies from its
+  // own mode at step_nr; a row whose sentence is forced there gets its normaliser only
+  PromptTableDev table; int group, step_nr;
+};
+hipError_t launch_vocab_select(const VocabSelectArgs& a, hipStream_t stream);
 struct BeamStepArgs {
   int32_t* tok; float* cum; int32_t* nactive; int32_t* done; int32_t* ndone;
   int32_t* parent; int32_t* new_tok; float* new_cum;

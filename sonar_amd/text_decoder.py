@@ -12,6 +12,7 @@ Reference interfaces mirrored (paths relative to facebookresearch/SONAR):
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import numbers
@@ -206,6 +207,22 @@ def plan_prompt_rows(decoder_max_seq_len: int, cond_dim: int, prompts: Sequence[
     return PromptRows(rows, lens, max(lens, default=0), limits, gen_cap, model_max, max((m for m, _ in limits), default=0))
 
 
+def _emb_dtype(e: torch.Tensor) -> int:
+    """The C-ABI dtype constant of a sentence-vector tensor (`_emb` leaves fp32 or fp16)."""
+    return _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16
+
+
+@contextlib.contextmanager
+def _invalid_arg_is_value_error():
+    """What the library refuses as an invalid argument is a ValueError, as what the host refuses is."""
+    try:
+        yield
+    except _lib.SmiError as err:
+        if err.status == _lib.SMI_ERR_INVALID_ARG:
+            raise ValueError(str(err)) from None
+        raise
+
+
 class TextDecoderEngine:
     """Owns one `smi_text_decoder` handle (packed fp16 weights in HBM + generation workspace)."""
 
@@ -302,7 +319,7 @@ class TextDecoderEngine:
         out = torch.empty((n, t, self.cfg.vocab_info.size), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.smi_text_decoder_logits(
-                self._handle, e.data_ptr(), _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16, n,
+                self._handle, e.data_ptr(), _emb_dtype(e), n,
                 prev.data_ptr(), t, out.data_ptr(), _lib.current_stream_ptr()))
         return out
 
@@ -341,15 +358,9 @@ class TextDecoderEngine:
         if n == 0 or t <= 1:
             return out.zero_()
         lens_arr = (C.c_int32 * n)(*lens_l)
-        with torch.cuda.device(self.device):
-            try:
-                _lib.check(self.lib.smi_text_decoder_score(
-                    self._handle, e.data_ptr(), _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16, n,
-                    toks.data_ptr(), t, lens_arr, out.data_ptr(), _lib.current_stream_ptr()))
-            except _lib.SmiError as err:
-                if err.status == _lib.SMI_ERR_INVALID_ARG:
-                    raise ValueError(str(err)) from None
-                raise
+        with torch.cuda.device(self.device), _invalid_arg_is_value_error():
+            _lib.check(self.lib.smi_text_decoder_score(self._handle, e.data_ptr(), _emb_dtype(e), n, toks.data_ptr(), t, lens_arr,
+                                                       out.data_ptr(), _lib.current_stream_ptr()))
         return out
 
     def _length_limits(self, plen: int, min_gen_len: int, max_gen_len: Tuple[int, int],
@@ -366,19 +377,34 @@ class TextDecoderEngine:
         return plan_prompt_rows(self.cfg.max_seq_len, self.cfg.input_dim or self.cfg.model_dim, prompts, n, min_gen_len,
                                 max_gen_len, max_seq_len, source_len)
 
-    def _call_prompts(self, fn, e, pr: PromptRows, min_gen_len, params, toks, lens, scores):
+    def _decode(self, entry: str, e, prompt, out_shape, make_params, min_gen_len, max_gen_len, max_seq_len, source_len):
+        """The call generate() and sample() share: C entry `entry` for one prompt (absolute lengths in the parameter struct,
+        `make_params(max_seq_len, min_seq_len)`), `entry`_prompts for one prompt per sentence (the length rule per row).
+        Returns (tokens int32 [*out_shape, L] , lens int32 out_shape, scores fp32 out_shape)."""
         n = e.shape[0]
-        prompts = (C.c_int64 * (n * pr.stride))(*pr.flat())
-        plens = (C.c_int32 * n)(*pr.lens)
-        with torch.cuda.device(self.device):
-            try:
-                _lib.check(fn(self._handle, e.data_ptr(), _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16, n,
-                              prompts, pr.stride, plens, pr.gen_cap, int(min_gen_len), C.byref(params), toks.data_ptr(),
-                              lens.data_ptr(), scores.data_ptr(), _lib.current_stream_ptr()))
-            except _lib.SmiError as err:
-                if err.status == _lib.SMI_ERR_INVALID_ARG:
-                    raise ValueError(str(err)) from None
-                raise
+        nested, prompt = split_prompts(prompt)
+        if nested:
+            pr = self._prompt_rows(prompt, n, min_gen_len, max_gen_len, max_seq_len, source_len)
+            params, width = make_params(pr.model_max, 0), pr.width
+        else:
+            plen = len(prompt)
+            width, min_len = self._length_limits(plen, min_gen_len, max_gen_len, max_seq_len, source_len)
+            params = make_params(width, min_len)
+        toks = torch.empty((*out_shape, width), dtype=torch.int32, device=self.device)
+        lens = torch.empty(out_shape, dtype=torch.int32, device=self.device)
+        scores = torch.empty(out_shape, dtype=torch.float32, device=self.device)
+        tail = (C.byref(params), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(), _lib.current_stream_ptr())
+        if not nested:
+            prompt_arr = (C.c_int64 * plen)(*[int(t) for t in prompt])
+            with torch.cuda.device(self.device):
+                _lib.check(getattr(self.lib, entry)(self._handle, e.data_ptr(), _emb_dtype(e), n, prompt_arr, plen, *tail))
+        elif n:
+            prompts = (C.c_int64 * (n * pr.stride))(*pr.flat())
+            plens = (C.c_int32 * n)(*pr.lens)
+            with torch.cuda.device(self.device), _invalid_arg_is_value_error():
+                _lib.check(getattr(self.lib, entry + "_prompts")(self._handle, e.data_ptr(), _emb_dtype(e), n, prompts, pr.stride,
+                                                                  plens, pr.gen_cap, int(min_gen_len), *tail))
+        return toks, lens, scores
 
     def set_beam_logits_dtype(self, dtype: torch.dtype) -> None:
         """Type of the logits the beam search of generate() compares (smi_text_decoder_set_beam_logits_dtype): float16 is what
@@ -452,34 +478,14 @@ class TextDecoderEngine:
     def _generate(self, embeddings, prompt, beam_size, min_gen_len, max_gen_len, max_seq_len, normalize_scores,
                   len_penalty, unk_penalty, temperature, source_len):
         e = self._emb(embeddings)
-        n = e.shape[0]
-        nested, prompt = split_prompts(prompt)
-        if nested:
-            pr = self._prompt_rows(prompt, n, min_gen_len, max_gen_len, max_seq_len, source_len)
-            bp = _lib.smi_beam_search_params(beam_size=beam_size, max_seq_len=pr.model_max, min_seq_len=0,
-                                             normalize_scores=1 if normalize_scores else 0, len_penalty=len_penalty,
-                                             unk_penalty=unk_penalty, temperature=temperature, reserved=0)
-            toks = torch.empty((n, beam_size, pr.width), dtype=torch.int32, device=self.device)
-            lens = torch.empty((n, beam_size), dtype=torch.int32, device=self.device)
-            scores = torch.empty((n, beam_size), dtype=torch.float32, device=self.device)
-            if n:
-                self._call_prompts(self.lib.smi_text_decoder_generate_prompts, e, pr, min_gen_len, bp, toks, lens, scores)
-            return toks, lens, scores
-        plen = len(prompt)
-        max_len, min_len = self._length_limits(plen, min_gen_len, max_gen_len, max_seq_len, source_len)
-        bp = _lib.smi_beam_search_params(beam_size=beam_size, max_seq_len=max_len, min_seq_len=min_len,
-                                         normalize_scores=1 if normalize_scores else 0, len_penalty=len_penalty,
-                                         unk_penalty=unk_penalty, temperature=temperature, reserved=0)
-        toks = torch.empty((n, beam_size, max_len), dtype=torch.int32, device=self.device)
-        lens = torch.empty((n, beam_size), dtype=torch.int32, device=self.device)
-        scores = torch.empty((n, beam_size), dtype=torch.float32, device=self.device)
-        prompt_arr = (C.c_int64 * plen)(*[int(t) for t in prompt])
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.smi_text_decoder_generate(
-                self._handle, e.data_ptr(), _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16, n,
-                prompt_arr, plen, C.byref(bp), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(),
-                _lib.current_stream_ptr()))
-        return toks, lens, scores
+
+        def params(max_len, min_len):
+            return _lib.smi_beam_search_params(beam_size=beam_size, max_seq_len=max_len, min_seq_len=min_len,
+                                               normalize_scores=1 if normalize_scores else 0, len_penalty=len_penalty,
+                                               unk_penalty=unk_penalty, temperature=temperature, reserved=0)
+
+        return self._decode("smi_text_decoder_generate", e, prompt, (e.shape[0], beam_size), params, min_gen_len, max_gen_len,
+                            max_seq_len, source_len)
 
     def sample(self, embeddings: torch.Tensor, prompt: Sequence[int], sampler, min_gen_len: int = 1,
                max_gen_len: Tuple[int, int] = (1, 128), max_seq_len: Optional[int] = None,
@@ -506,35 +512,15 @@ class TextDecoderEngine:
     def _sample(self, embeddings, prompt, kind, k, p, min_gen_len, max_gen_len, max_seq_len, normalize_scores,
                 len_penalty, unk_penalty, temperature, seed, sentence_offset, source_len):
         e = self._emb(embeddings)
-        n = e.shape[0]
         seed = (int(seed) + 0x9E3779B97F4A7C15 * 65536 * int(sentence_offset)) & 0xFFFFFFFFFFFFFFFF
-        nested, prompt = split_prompts(prompt)
-        if nested:
-            pr = self._prompt_rows(prompt, n, min_gen_len, max_gen_len, max_seq_len, source_len)
-            sp = _lib.smi_sampling_params(sampler=kind, top_k=k, top_p=p, temperature=temperature, max_seq_len=pr.model_max,
-                                          min_seq_len=0, normalize_scores=1 if normalize_scores else 0,
-                                          len_penalty=len_penalty, seed=seed, unk_penalty=unk_penalty)
-            toks = torch.empty((n, pr.width), dtype=torch.int32, device=self.device)
-            lens = torch.empty((n,), dtype=torch.int32, device=self.device)
-            scores = torch.empty((n,), dtype=torch.float32, device=self.device)
-            if n:
-                self._call_prompts(self.lib.smi_text_decoder_sample_prompts, e, pr, min_gen_len, sp, toks, lens, scores)
-            return toks, lens, scores
-        plen = len(prompt)
-        max_len, min_len = self._length_limits(plen, min_gen_len, max_gen_len, max_seq_len, source_len)
-        sp = _lib.smi_sampling_params(sampler=kind, top_k=k, top_p=p, temperature=temperature, max_seq_len=max_len,
-                                      min_seq_len=min_len, normalize_scores=1 if normalize_scores else 0,
-                                      len_penalty=len_penalty, seed=seed, unk_penalty=unk_penalty)
-        toks = torch.empty((n, max_len), dtype=torch.int32, device=self.device)
-        lens = torch.empty((n,), dtype=torch.int32, device=self.device)
-        scores = torch.empty((n,), dtype=torch.float32, device=self.device)
-        prompt_arr = (C.c_int64 * plen)(*[int(t) for t in prompt])
-        with torch.cuda.device(self.device):
-            _lib.check(self.lib.smi_text_decoder_sample(
-                self._handle, e.data_ptr(), _lib.SMI_F32 if e.dtype == torch.float32 else _lib.SMI_F16, n,
-                prompt_arr, plen, C.byref(sp), toks.data_ptr(), lens.data_ptr(), scores.data_ptr(),
-                _lib.current_stream_ptr()))
-        return toks, lens, scores
+
+        def params(max_len, min_len):
+            return _lib.smi_sampling_params(sampler=kind, top_k=k, top_p=p, temperature=temperature, max_seq_len=max_len,
+                                            min_seq_len=min_len, normalize_scores=1 if normalize_scores else 0,
+                                            len_penalty=len_penalty, seed=seed, unk_penalty=unk_penalty)
+
+        return self._decode("smi_text_decoder_sample", e, prompt, (e.shape[0],), params, min_gen_len, max_gen_len, max_seq_len,
+                            source_len)
 
 
 class ConditionalTransformerDecoderModel:
