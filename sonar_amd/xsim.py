@@ -4,7 +4,7 @@ The reference names xsim as SONAR's evaluation (README.md:5) and computes
 similarities as `F.normalize(x) @ F.normalize(y).T`
 (tests/integration_tests/test_text_sonar.py:42-53, examples/sonar_text_demo.ipynb).
 Here the similarity matrix is never materialised: `smi_xsim_topk` streams
-128x128 score tiles out of the MFMA pipeline into a running top-k.
+256x256 score tiles out of the MFMA pipeline into a running top-k.
 
 Multi-GPU (sharded_topk): X rows are sharded over ranks, every rank's Y shard
 is all-gathered once over RCCL/xGMI (2 GB for 1M x 1024 fp16 -- small next to
