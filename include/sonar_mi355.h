@@ -570,6 +570,47 @@ int smi_xsim_margin_select(const float* fwd_scores, const int32_t* fwd_idx, int6
                            const float* bwd_scores, int64_t ny, int32_t margin, int64_t x_index_offset,
                            int32_t* pred_idx, float* pred_margin, int32_t* err_count, void* stream);
 
+/* Bitext mining, LASER's mine_bitexts.py (facebookresearch/LASER source/mine_bitexts.py; un-vendored, the algorithm is
+ * restated in DESIGN.md 3.13 and, loop for loop, in tests/mining_ref.py).
+ *
+ * smi_xsim_pair_scores: the margin score of m GIVEN pairs (LASER's --mode score),
+ *   out[p] = margin(cos(x_s, y_t), (mean(fwd_scores[s]) + mean(bwd_scores[t])) / 2),  s = src_idx[p], t = trg_idx[p],
+ *   with the cosine computed from row s of xn and row t of yn (matrices from smi_xsim_normalize; every d smi_xsim_topk
+ *   accepts) and the means in smi_xsim_margin_select's arithmetic.  src_idx / trg_idx: device int64 [m]; fwd_scores
+ *   [nx, k] / bwd_scores [ny, k] as for smi_xsim_margin_select, NULL allowed only for SMI_MARGIN_COSINE.  A pair with an
+ *   index outside [0, nx) / [0, ny) scores NaN and reads nothing.
+ *
+ * smi_xsim_mine: the retrieval step (LASER's --mode mine) over the best candidates of both directions,
+ *   fwd_best / fwd_score [nx] = smi_xsim_margin_select(fwd lists, bwd scores), bwd_best / bwd_score [ny] = the same call
+ *   with the roles swapped.  Candidate c < nx is (c, fwd_best[c], fwd_score[c]), candidate c >= nx is
+ *   (bwd_best[c - nx], c - nx, bwd_score[c - nx]).  A candidate with a NaN score or with its source / target outside
+ *   [0, nx) / [0, ny) is excluded: never returned, never blocking another, nothing read or written at that index.
+ *     SMI_MINE_FWD        the forward candidates                                  (capacity nx; bwd_* may be NULL)
+ *     SMI_MINE_BWD        the backward candidates                                 (capacity ny; fwd_* may be NULL)
+ *     SMI_MINE_INTERSECT  forward candidates with bwd_best[fwd_best[i]] == i      (capacity nx; bwd_score may be NULL)
+ *     SMI_MINE_MAX        walk all nx + ny candidates by (score descending, -0 = +0, candidate number ascending) and
+ *                         accept one iff neither its source nor its target belongs to an accepted one (capacity min(nx, ny))
+ *   threshold: only pairs with score > threshold (strict) are returned; -INFINITY = no threshold (every non-excluded pair,
+ *   a score of -inf included).  What SMI_MINE_MAX accepts does not depend on it.  out_src / out_trg (int32) / out_score
+ *   receive the pairs in CANDIDATE ORDER (not by score), *out_count (device int32) their number; entries past the count
+ *   are not written.  workspace: smi_xsim_mine_workspace_bytes() bytes of device memory, 8-byte aligned; a smaller buffer
+ *   is refused before any launch.  nx + ny must fit int32.
+ *   SMI_MINE_MAX BLOCKS ON `stream`: it runs as data-dependent rounds (typically a handful, in principle up to min(nx, ny)) and
+ *   the host reads one int32 back after each, so it cannot be captured into a graph.  The other retrievals are
+ *   asynchronous like the rest of this section. */
+#define SMI_MINE_FWD 0
+#define SMI_MINE_BWD 1
+#define SMI_MINE_INTERSECT 2
+#define SMI_MINE_MAX 3
+int smi_xsim_pair_scores(const void* xn_f16, int64_t nx, const void* yn_f16, int64_t ny, int32_t d,
+                         const int64_t* src_idx, const int64_t* trg_idx, int64_t m, const float* fwd_scores,
+                         const float* bwd_scores, int32_t k, int32_t margin, float* out, void* stream);
+int64_t smi_xsim_mine_workspace_bytes(int64_t nx, int64_t ny, int32_t retrieval);
+int smi_xsim_mine(const int32_t* fwd_best, const float* fwd_score, int64_t nx, const int32_t* bwd_best,
+                  const float* bwd_score, int64_t ny, int32_t retrieval, float threshold, int32_t* out_src,
+                  int32_t* out_trg, float* out_score, int32_t* out_count, void* workspace, int64_t workspace_bytes,
+                  void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

@@ -21,6 +21,7 @@ SMI_ERR_INVALID_ARG = -1
 SMI_F32, SMI_F16, SMI_BF16 = 0, 1, 2
 SMI_POOL = {"mean": 0, "max": 1, "last": 2, "attention": 3}
 SMI_MARGIN = {"ratio": 0, "distance": 1, "cosine": 2}
+SMI_MINE = {"fwd": 0, "bwd": 1, "intersect": 2, "max": 3}
 SMI_GEMM_IN_TM, SMI_GEMM_OUT_TM = 1 << 12, 1 << 13
 SMI_ENC_FP16_RESIDUAL = 1
 SMI_ENC_NORMALIZE_BEFORE = 2
@@ -334,6 +335,9 @@ SYMBOLS = {
     "smi_xsim_topk": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),
     "smi_xsim_merge_topk": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "smi_xsim_margin_select": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "smi_xsim_pair_scores": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
+    "smi_xsim_mine_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "smi_xsim_mine": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "smi_gemm_tn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "smi_gemm_tn_tile_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "smi_gemm_tn_splitk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

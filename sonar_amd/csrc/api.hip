@@ -664,6 +664,49 @@ int smi_xsim_margin_select(const float* fwd_scores, const int32_t* fwd_idx, int6
   return SMI_OK;
 }
 
+int smi_xsim_pair_scores(const void* xn, int64_t nx, const void* yn, int64_t ny, int32_t d, const int64_t* src_idx,
+                         const int64_t* trg_idx, int64_t m, const float* fwd_scores, const float* bwd_scores, int32_t k,
+                         int32_t margin, float* out, void* stream) {
+  if (!xn || !yn || !src_idx || !trg_idx || !out) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (k < 1 || k > 8) return fail(SMI_ERR_UNSUPPORTED, "k=%d outside [1,8]", k);
+  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
+  if (margin < SMI_MARGIN_RATIO || margin > SMI_MARGIN_COSINE) return fail(SMI_ERR_INVALID_ARG, "unknown margin %d", margin);
+  if (nx <= 0 || ny <= 0 || m <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (margin != SMI_MARGIN_COSINE && (!fwd_scores || !bwd_scores))
+    return fail(SMI_ERR_INVALID_ARG, "margin scoring needs the neighbour scores of both directions");
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_pair_scores((const f16*)xn, nx, (const f16*)yn, ny, d, src_idx, trg_idx, m, fwd_scores, bwd_scores, k,
+                             margin, out, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int64_t smi_xsim_mine_workspace_bytes(int64_t nx, int64_t ny, int32_t retrieval) {
+  if (nx <= 0 || ny <= 0 || nx + ny > 0x7fffffffLL || retrieval < SMI_MINE_FWD || retrieval > SMI_MINE_MAX) return 0;
+  return (int64_t)mine_workspace_bytes(nx, ny, retrieval);
+}
+
+int smi_xsim_mine(const int32_t* fwd_best, const float* fwd_score, int64_t nx, const int32_t* bwd_best,
+                  const float* bwd_score, int64_t ny, int32_t retrieval, float threshold, int32_t* out_src,
+                  int32_t* out_trg, float* out_score, int32_t* out_count, void* ws, int64_t ws_bytes, void* stream) {
+  if (retrieval < SMI_MINE_FWD || retrieval > SMI_MINE_MAX) return fail(SMI_ERR_INVALID_ARG, "unknown retrieval %d", retrieval);
+  if (!out_src || !out_trg || !out_score || !out_count || !ws) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (retrieval != SMI_MINE_BWD && (!fwd_best || !fwd_score)) return fail(SMI_ERR_INVALID_ARG, "this retrieval needs the forward candidates");
+  if (retrieval != SMI_MINE_FWD && !bwd_best) return fail(SMI_ERR_INVALID_ARG, "this retrieval needs the backward candidates");
+  if ((retrieval == SMI_MINE_BWD || retrieval == SMI_MINE_MAX) && !bwd_score)
+    return fail(SMI_ERR_INVALID_ARG, "this retrieval needs the backward scores");
+  if (nx <= 0 || ny <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (nx + ny > 0x7fffffffLL) return fail(SMI_ERR_UNSUPPORTED, "nx + ny = %lld candidates do not fit int32", (long long)(nx + ny));
+  if (threshold != threshold) return fail(SMI_ERR_INVALID_ARG, "threshold is NaN (no threshold is -INFINITY)");
+  if ((uintptr_t)ws % 8) return fail(SMI_ERR_INVALID_ARG, "workspace must be 8-byte aligned");
+  if (ws_bytes < smi_xsim_mine_workspace_bytes(nx, ny, retrieval))
+    return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, smi_xsim_mine_workspace_bytes(nx, ny, retrieval) = %lld",
+                (long long)ws_bytes, (long long)smi_xsim_mine_workspace_bytes(nx, ny, retrieval));
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_mine(fwd_best, fwd_score, nx, bwd_best, bwd_score, ny, retrieval, threshold, out_src, out_trg, out_score,
+                      out_count, ws, (hipStream_t)stream));
+  return SMI_OK;
+}
+
 // -------------------------------------------------------- building blocks
 int smi_pack_tile_major(const void* src, void* dst, int32_t rows, int32_t k, int32_t inverse,
                         void* stream) {

@@ -156,6 +156,14 @@ hipError_t launch_topk_merge(const float* part_scores, const int32_t* part_idx, 
 hipError_t launch_margin_select(const float* fwd_scores, const int32_t* fwd_idx, int64_t nx, int k,
                                 const float* bwd_scores, int64_t ny, int kind, int64_t x_off, int32_t* pred,
                                 float* pred_margin, int32_t* err_count, hipStream_t stream);
+// bitext mining over the best candidates (mining.hip): retrieval 0 fwd, 1 bwd, 2 intersect, 3 max (blocks on `stream`)
+size_t mine_workspace_bytes(int64_t nx, int64_t ny, int retrieval);
+hipError_t launch_mine(const int32_t* fwd_best, const float* fwd_score, int64_t nx, const int32_t* bwd_best,
+                       const float* bwd_score, int64_t ny, int retrieval, float threshold, int32_t* out_src,
+                       int32_t* out_trg, float* out_score, int32_t* out_count, void* workspace, hipStream_t stream);
+hipError_t launch_pair_scores(const f16* Xn, int64_t nx, const f16* Yn, int64_t ny, int d, const int64_t* src_idx,
+                              const int64_t* trg_idx, int64_t m, const float* fwd_scores, const float* bwd_scores, int k,
+                              int kind, float* out, hipStream_t stream);
 
 // ---- decoder / beam search (decoder.hip) ----
 hipError_t launch_dec_embed(const int32_t* tok, const f16* table, const float* pe_row, float scale,

@@ -1,0 +1,168 @@
+"""LASER-style bitext mining on the MI355X engine: search / score / mine over two unaligned corpora.
+
+The recipe is LASER's `source/mine_bitexts.py` (un-vendored; restated in DESIGN.md 3.13 and, loop for loop, in
+tests/mining_ref.py): k-NN search in both directions (`smi_xsim_topk`), margin re-scoring of the candidates
+(`smi_xsim_margin_select`, both directions), then one of the retrieval rules `fwd` / `bwd` / `intersect` / `max`
+(`smi_xsim_mine`) or the margin score of given pairs (`smi_xsim_pair_scores`).  Everything but the final ordering of the
+`max` pairs -- one stable sort over at most min(nx, ny) scores -- runs in the library's kernels; there is no CPU path.
+
+Where the original leaves the result open, this one is fixed: ties in `max` go to the lower candidate number (the
+forward candidates 0..nx-1 come before the backward candidates), -0 counts as +0, and a candidate with a NaN score or a
+missing neighbour (index -1) is left out.  `threshold` applies to every retrieval (LASER: `max` only).
+"""
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import torch
+
+from . import _lib
+from .xsim import margin_select, normalize_rows, topk_normalized
+
+MODES = ("search", "score", "mine")
+RETRIEVALS = tuple(_lib.SMI_MINE)
+_MARGIN_ALIAS = {"absolute": "cosine"}
+
+
+def _check_args(mode: str, retrieval: str, margin: str, k: int, threshold: Optional[float], pairs) -> Tuple[str, float]:
+    """Everything that can be refused without looking at a tensor -> (margin name, threshold as a float)."""
+    if mode not in MODES:
+        raise ValueError(f"mode {mode!r}: expected one of {MODES}")
+    if retrieval not in _lib.SMI_MINE:
+        raise ValueError(f"retrieval {retrieval!r}: expected one of {RETRIEVALS}")
+    margin = _MARGIN_ALIAS.get(margin, margin)
+    if margin not in _lib.SMI_MARGIN:
+        raise ValueError(f"margin {margin!r}: expected one of {tuple(_lib.SMI_MARGIN) + tuple(_MARGIN_ALIAS)}")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
+        raise ValueError(f"k = {k!r}: the neighbourhood must be an integer in [1, 8]")
+    if mode == "score" and (pairs is None or len(pairs) != 2):
+        raise ValueError("mode 'score' needs pairs=(src_idx, trg_idx)")
+    thr = -math.inf if threshold is None else float(threshold)
+    if math.isnan(thr):
+        raise ValueError("threshold is NaN")
+    return margin, thr
+
+
+def pair_scores(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, src_idx: torch.Tensor, trg_idx: torch.Tensor,
+                fwd_scores: Optional[torch.Tensor], bwd_scores: Optional[torch.Tensor], margin: str = "ratio") -> torch.Tensor:
+    """Margin scores fp32 [m] of the given (src_idx[p], trg_idx[p]) pairs (smi_xsim_pair_scores).  xn / yn from
+    normalize_rows, fwd_scores [nx, k] / bwd_scores [ny, k] from topk_normalized (None allowed for "cosine").  A pair with
+    an index out of range scores NaN."""
+    margin = _MARGIN_ALIAS.get(margin, margin)
+    if margin not in _lib.SMI_MARGIN:
+        raise ValueError(margin)
+    lib = _lib.load()
+    dev = xn.device
+    si = torch.as_tensor(src_idx, device=dev).to(torch.int64).contiguous()
+    ti = torch.as_tensor(trg_idx, device=dev).to(torch.int64).contiguous()
+    if si.dim() != 1 or si.shape != ti.shape:
+        raise ValueError("pairs must be two index vectors of the same length")
+    if xn.shape[1] != yn.shape[1]:
+        raise ValueError("x and y must have the same dimension")
+    fs = fwd_scores.to(torch.float32).contiguous() if fwd_scores is not None else None
+    bs = bwd_scores.to(torch.float32).contiguous() if bwd_scores is not None else None
+    if fs is not None and bs is not None and fs.shape[1] != bs.shape[1]:
+        raise ValueError("forward and backward neighbour lists must have the same k")
+    k = fs.shape[1] if fs is not None else 1
+    m = si.shape[0]
+    out = torch.empty((m,), dtype=torch.float32, device=dev)
+    if m == 0:
+        return out
+    with torch.cuda.device(dev):
+        _lib.check(lib.smi_xsim_pair_scores(xn.data_ptr(), nx, yn.data_ptr(), ny, xn.shape[1], si.data_ptr(), ti.data_ptr(),
+                                            m, fs.data_ptr() if fs is not None else None,
+                                            bs.data_ptr() if bs is not None else None, k, _lib.SMI_MARGIN[margin],
+                                            out.data_ptr(), _lib.current_stream_ptr()))
+    return out
+
+
+def mine_candidates(fwd_best: Optional[torch.Tensor], fwd_score: Optional[torch.Tensor], bwd_best: Optional[torch.Tensor],
+                    bwd_score: Optional[torch.Tensor], nx: int, ny: int, retrieval: str = "max",
+                    threshold: Optional[float] = None, sort: bool = True):
+    """The retrieval step over the best candidates of both directions (smi_xsim_mine): fwd_best int32 [nx] / fwd_score fp32
+    [nx] and bwd_best [ny] / bwd_score [ny] as margin_select returns them (a side the retrieval does not read may be None).
+    Returns (src_idx int64 [m], trg_idx int64 [m], scores fp32 [m]): in candidate order for fwd / bwd / intersect; for `max`
+    by score descending, equal scores in candidate order (sort=False: candidate order, as the library returns them).
+    `max` blocks on the current stream."""
+    _, thr = _check_args("mine", retrieval, "cosine", 1, threshold, None)
+    lib = _lib.load()
+    kind = _lib.SMI_MINE[retrieval]
+    ref = fwd_best if fwd_best is not None else bwd_best
+    dev = ref.device
+    fb = fwd_best.to(torch.int32).contiguous() if fwd_best is not None else None
+    fs = fwd_score.to(torch.float32).contiguous() if fwd_score is not None else None
+    bb = bwd_best.to(torch.int32).contiguous() if bwd_best is not None else None
+    bs = bwd_score.to(torch.float32).contiguous() if bwd_score is not None else None
+    for t, n, name in ((fb, nx, "fwd_best"), (fs, nx, "fwd_score"), (bb, ny, "bwd_best"), (bs, ny, "bwd_score")):
+        if t is not None and t.shape != (n,):
+            raise ValueError(f"{name} must have shape ({n},)")
+    cap = {"fwd": nx, "bwd": ny, "intersect": nx, "max": min(nx, ny)}[retrieval]
+    ws_bytes = int(lib.smi_xsim_mine_workspace_bytes(nx, ny, kind))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    out_src = torch.empty((cap,), dtype=torch.int32, device=dev)
+    out_trg = torch.empty((cap,), dtype=torch.int32, device=dev)
+    out_score = torch.empty((cap,), dtype=torch.float32, device=dev)
+    count = torch.zeros(1, dtype=torch.int32, device=dev)
+    ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+    with torch.cuda.device(dev):
+        _lib.check(lib.smi_xsim_mine(ptr(fb), ptr(fs), nx, ptr(bb), ptr(bs), ny, kind, thr, out_src.data_ptr(),
+                                     out_trg.data_ptr(), out_score.data_ptr(), count.data_ptr(), ws.data_ptr(), ws_bytes,
+                                     _lib.current_stream_ptr()))
+    m = int(count.item())
+    src, trg, score = out_src[:m].long(), out_trg[:m].long(), out_score[:m].clone()
+    if retrieval == "max" and sort:
+        # candidate order in + a stable sort = (score descending, candidate number ascending); "+ 0.0" folds -0 into +0 so
+        # that a sort on the bit pattern cannot tell them apart either
+        order = torch.sort(score + 0.0, descending=True, stable=True).indices
+        src, trg, score = src[order], trg[order], score[order]
+    return src, trg, score
+
+
+def mine_bitexts_normalized(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, *, mode: str = "mine",
+                            retrieval: str = "max", margin: str = "ratio", k: int = 4, threshold: Optional[float] = None,
+                            pairs=None):
+    """mine_bitexts on matrices from normalize_rows (mine one corpus against several without normalising it again)."""
+    margin, thr = _check_args(mode, retrieval, margin, k, threshold, pairs)
+    if xn.shape[1] != yn.shape[1]:
+        raise ValueError("x and y must have the same dimension")
+    if min(k, nx) != min(k, ny):
+        # LASER would average min(k, ny) forward and min(k, nx) backward neighbours; the margin kernels take one k
+        raise ValueError(f"k = {k} exceeds the rows of one side only ({nx} x {ny}): pass k <= {min(nx, ny)}")
+    kk = min(k, nx, ny)
+    fs, fi = topk_normalized(xn, nx, yn, ny, kk)
+    bs, bi = topk_normalized(yn, ny, xn, nx, kk)
+    if mode == "score":
+        return pair_scores(xn, nx, yn, ny, pairs[0], pairs[1], fs, bs, margin)
+    fwd_best = fwd_score = bwd_best = bwd_score = None
+    if mode == "search" or retrieval != "bwd":
+        fwd_best, fwd_score = margin_select(fs, fi, bs, margin)
+    if mode == "search":
+        return fwd_best.long(), fwd_score
+    if retrieval != "fwd":
+        bwd_best, bwd_score = margin_select(bs, bi, fs, margin)
+    return mine_candidates(fwd_best, fwd_score, bwd_best, bwd_score, nx, ny, retrieval, thr)
+
+
+def mine_bitexts(x: torch.Tensor, y: torch.Tensor, *, mode: str = "mine", retrieval: str = "max", margin: str = "ratio",
+                 k: int = 4, threshold: Optional[float] = None, pairs=None):
+    """LASER's bitext mining over the rows of x [nx, d] and y [ny, d] (fp16 / fp32 embeddings on the device).
+
+    score(i, j) = margin(cos(x_i, y_j), (mean of x_i's k best cosines + mean of y_j's k best cosines) / 2), margin =
+    "ratio" a / b, "distance" a - b or "cosine" ("absolute") a; the best candidate of a row is the best-scoring one of its
+    k nearest neighbours.
+
+      mode="search"  -> (trg_idx int64 [nx], scores fp32 [nx]): the best y row for every x row
+      mode="score"   -> scores fp32 [m] of the given pairs=(src_idx, trg_idx)
+      mode="mine"    -> (src_idx int64 [m], trg_idx int64 [m], scores fp32 [m]) by `retrieval`:
+          "fwd"        every x row with its best y row, in order of x
+          "bwd"        every y row with its best x row, in order of y
+          "intersect"  the fwd pairs whose y row has that x row as its best, in order of x
+          "max"        both lists walked by score descending, a pair accepted iff neither of its rows is in an
+                       accepted pair; returned best first
+    `threshold`: only pairs scoring strictly above it are returned (what `max` accepts does not depend on it).
+    """
+    _check_args(mode, retrieval, margin, k, threshold, pairs)
+    xn, yn = normalize_rows(x), normalize_rows(y)
+    return mine_bitexts_normalized(xn, x.shape[0], yn, y.shape[0], mode=mode, retrieval=retrieval, margin=margin, k=k,
+                                   threshold=threshold, pairs=pairs)
