@@ -528,6 +528,29 @@ int smi_fbank(const float* wave, int64_t nsamples, float waveform_scale, int32_t
 int smi_fbank_batch(const float* waves, const int64_t* offsets, int32_t n, float waveform_scale, int32_t standardize,
                     float* out, int64_t tpad, void* stream);
 
+/* Sample-rate conversion in front of the filterbank: the windowed-sinc polyphase resampler that torchaudio's
+ * functional.resample applies by default (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99).  With g = gcd(orig, new),
+ * o = orig / g, n = new / g:
+ *   base = min(o, n) * 0.99, width = ceil(6 o / base), 2 width + o taps per phase
+ *   k[p][i] = sinc(t) cos(pi t / 12)^2 base / o,  t = ((i - width) / o - p / n) base clamped to [-6, 6]   (double, stored fp32)
+ *   y[m n + p] = sum_i k[p][i] x[m o + i - width],  x zero outside the clip;  ceil(n L / o) outputs for L samples
+ * Per phase only `support` = floor(12 o / base) + 1 consecutive taps are non-zero in fp32; the engine keeps that compact
+ * table and the first tap index of every phase, cached per (o, n) for the life of the process.  Rates <= 0 or above 2^20
+ * and pairs whose compact table exceeds 16 MiB return SMI_ERR_UNSUPPORTED.
+ * smi_resample_num_samples: the output length (< 0 on bad rates).  smi_resample_filter: the table itself, host only, needs
+ * no device; taps [phases * support] and first [phases] may be NULL to ask for the sizes alone. */
+int64_t smi_resample_num_samples(int64_t nsamples, int32_t orig_rate, int32_t new_rate);
+int smi_resample_filter(int32_t orig_rate, int32_t new_rate, int32_t* phases, int32_t* support, int32_t* width, float* taps,
+                        int32_t* first);
+/* One launch for a ragged batch: waves device fp32, the clips back to back at their own rates; in_offsets HOST int64
+ * [n + 1], rates HOST int32 [n]; out device fp32, clip i at out_offsets[i] .. out_offsets[i + 1] (HOST int64 [n + 1]), which
+ * must hold exactly smi_resample_num_samples(len_i, rates[i], new_rate) samples; nothing outside out_offsets[0] ..
+ * out_offsets[n] is written.  A clip already at new_rate is copied bit for bit, an empty clip produces nothing.  Every output is accumulated in fp32 over its taps in
+ * ascending order, so its value depends on its clip, the two rates and its index alone -- not on the rest of the batch.
+ * Asynchronous on `stream`. */
+int smi_resample_batch(const float* waves, const int64_t* in_offsets, const int32_t* rates, int32_t n, int32_t new_rate,
+                       float* out, const int64_t* out_offsets, void* stream);
+
 /* xsim mining ---------------------------------------------------------------
  * Stands in for the similarity search the reference performs as
  * F.normalize(x) @ F.normalize(y).T (tests/integration_tests/test_text_sonar.py:42-53)

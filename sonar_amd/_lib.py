@@ -329,6 +329,9 @@ SYMBOLS = {
     "smi_fbank_num_frames": (_i64, [_i64]),
     "smi_fbank": (C.c_int, [_vp, _i64, _f32, _i32, _vp, _vp]),
     "smi_fbank_batch": (C.c_int, [_vp, C.POINTER(_i64), _i32, _f32, _i32, _vp, _i64, _vp]),
+    "smi_resample_num_samples": (_i64, [_i64, _i32, _i32]),
+    "smi_resample_filter": (C.c_int, [_i32, _i32, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), _vp, _vp]),
+    "smi_resample_batch": (C.c_int, [_vp, C.POINTER(_i64), C.POINTER(_i32), _i32, _i32, _vp, C.POINTER(_i64), _vp]),
     "smi_xsim_padded_rows": (_i64, [_i64]),
     "smi_xsim_normalize": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp]),
     "smi_xsim_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),

@@ -15,6 +15,11 @@ Audio decoding: the reference uses fairseq2n's libsndfile AudioDecoder (speech.p
 libsndfile is not in this image, so RIFF/WAVE (PCM 8/16/24/32, float 32/64, extensible) and native FLAC
 streams are decoded by the engine's own host code (`smi_host_audio_decode`: csrc/host_input.cpp,
 csrc/host_audio.cpp); other containers (Ogg, MP3, ...) raise a ValueError.
+
+Sample rates: the SONAR encoders take 16 kHz audio, and by default anything else is refused, as it always was.  With
+`predict(..., resample=True)` files are decoded at their own rate, an input may be a `(waveform, sample_rate)` pair, the host
+half stages the source-rate samples, and the device half converts the batch to 16 kHz in ONE launch (sonar_amd/resample.py)
+in front of the filterbank whenever a clip of the batch needs it.
 """
 from __future__ import annotations
 
@@ -29,6 +34,7 @@ from typing import Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 import torch
 
 from .. import _lib
+from ..resample import resample_batch_flat
 from ..speech_encoder import (SonarSpeechEncoderModel, fbank_batch_flat, load_sonar_speech_encoder,
                               waveform_to_fbank, waveforms_to_fbank_batch)  # noqa: F401
 from ..text_encoder import PaddingMask, SequenceBatch
@@ -64,6 +70,15 @@ def read_wav(path: Union[str, Path]) -> torch.Tensor:
     if rate != 16000:
         raise ValueError(f"{path}: sample rate {rate}, the SONAR speech encoders expect 16 kHz audio")
     return wav.t().contiguous()
+
+
+def read_audio(path: Union[str, Path]) -> Tuple[torch.Tensor, int]:
+    """([channels, samples] float32 in [-1, 1], sample rate) of a WAV or FLAC file at whatever rate it was recorded:
+    the input of `predict(..., resample=True)` and of `sonar_amd.resample.resample`."""
+    with open(str(path), "rb") as fh:
+        data = fh.read()
+    wav, rate = decode_audio_bytes(data, str(path))
+    return wav.t().contiguous(), rate
 
 
 @dataclass
@@ -107,6 +122,7 @@ class _HostBatch:
     offsets: List[int]                 # clip i = cat[offsets[i]:offsets[i+1]]
     ready: Optional["torch.cuda.Event"]  # H2D copy done (recorded on the producer's stream)
     stage: Optional[torch.Tensor]      # pinned staging buffer, kept alive until the copy has run
+    rates: Optional[List[int]] = None  # resample=True: the sample rate of every clip of `cat` (None: all 16 kHz)
 
 
 class SpeechModelPipelineInterface(torch.nn.Module):
@@ -118,6 +134,8 @@ class SpeechModelPipelineInterface(torch.nn.Module):
     def _load_audio(self, inp: Union[str, Path, torch.Tensor]) -> torch.Tensor:
         """-> mono waveform [T] float32 (host tensor for files; tensors stay where they are).
         speech.py:298-308: tensor inputs are [C, T] at 16 kHz."""
+        if isinstance(inp, tuple):
+            raise ValueError("(waveform, sample_rate) inputs need predict(..., resample=True)")
         if isinstance(inp, torch.Tensor):
             wav = inp
             if wav.dim() == 1:
@@ -129,17 +147,36 @@ class SpeechModelPipelineInterface(torch.nn.Module):
         # channel_last fbank of a multi-channel clip uses the first channel (kaldi takes channel 0)
         return wav[0].to(torch.float32)
 
+    def _load_audio_rate(self, inp) -> Tuple[torch.Tensor, int]:
+        """`_load_audio` of `resample=True` -> (mono waveform [T] float32, its sample rate): files keep their own rate,
+        a `(waveform, sample_rate)` pair states it, a bare tensor is 16 kHz as ever."""
+        if isinstance(inp, tuple):
+            if len(inp) != 2 or not isinstance(inp[0], torch.Tensor):
+                raise ValueError("a pair input must be (waveform tensor, sample rate)")
+            return self._load_audio(inp[0]), int(inp[1])
+        if isinstance(inp, torch.Tensor):
+            return self._load_audio(inp), 16000
+        wav, rate = read_audio(inp)
+        return wav[0].to(torch.float32), rate
+
     # kept for callers of the round-1 name
     def _decode_audio(self, inp: Union[str, Path, torch.Tensor]) -> torch.Tensor:
         return self._load_audio(inp).to(self.device)
 
-    def _host_batches(self, items: Sequence, batch_size: int, n_parallel: int) -> Iterator[_HostBatch]:
-        """The host half of the pipeline for every bucket of `batch_size` inputs."""
+    def _host_batches(self, items: Sequence, batch_size: int, n_parallel: int,
+                      resample: bool = False) -> Iterator[_HostBatch]:
+        """The host half of the pipeline for every bucket of `batch_size` inputs; with `resample` the clips are staged and
+        copied at their source rates and the batch carries those rates."""
         dev = torch.device(self.device)
         side = torch.cuda.Stream(dev) if dev.type == "cuda" else None
         with ThreadPoolExecutor(max_workers=max(1, int(n_parallel))) as pool:
             for i in range(0, len(items), batch_size):
-                wavs = list(pool.map(self._load_audio, items[i:i + batch_size]))
+                rates = None
+                if resample:
+                    loaded = list(pool.map(self._load_audio_rate, items[i:i + batch_size]))
+                    wavs, rates = [w for w, _ in loaded], [r for _, r in loaded]
+                else:
+                    wavs = list(pool.map(self._load_audio, items[i:i + batch_size]))
                 offs = [0]
                 for w in wavs:
                     offs.append(offs[-1] + w.numel())
@@ -149,24 +186,25 @@ class SpeechModelPipelineInterface(torch.nn.Module):
                     if dev.type == "cuda":
                         ev = torch.cuda.Event()
                         ev.record(torch.cuda.current_stream(dev))
-                    yield _HostBatch(cat, offs, ev, None)
+                    yield _HostBatch(cat, offs, ev, None, rates)
                     continue
                 stage = torch.empty(max(offs[-1], 1), dtype=torch.float32, pin_memory=dev.type == "cuda")
                 for w, o in zip(wavs, offs):
                     stage[o:o + w.numel()] = w
                 if side is None:
-                    yield _HostBatch(stage[:offs[-1]].clone(), offs, None, None)
+                    yield _HostBatch(stage[:offs[-1]].clone(), offs, None, None, rates)
                     continue
                 with torch.cuda.stream(side):
                     cat = stage[:offs[-1]].to(dev, non_blocking=True)
                     ev = torch.cuda.Event()
                     ev.record(side)
-                yield _HostBatch(cat, offs, ev, stage)
+                yield _HostBatch(cat, offs, ev, stage, rates)
 
-    def _prefetched(self, items: Sequence, batch_size: int, n_parallel: int, depth: int) -> Iterator[_HostBatch]:
+    def _prefetched(self, items: Sequence, batch_size: int, n_parallel: int, depth: int,
+                    resample: bool = False) -> Iterator[_HostBatch]:
         """`.prefetch(n_prefetched_batches)`: the host half runs on a background thread."""
         if depth <= 0:
-            yield from self._host_batches(items, batch_size, n_parallel)
+            yield from self._host_batches(items, batch_size, n_parallel, resample)
             return
         q: "queue.Queue" = queue.Queue(maxsize=depth)
         end = object()
@@ -183,7 +221,7 @@ class SpeechModelPipelineInterface(torch.nn.Module):
 
         def work():
             try:
-                for hb in self._host_batches(items, batch_size, n_parallel):
+                for hb in self._host_batches(items, batch_size, n_parallel, resample):
                     if not offer(hb):
                         return
                 offer(end)
@@ -214,7 +252,10 @@ class SpeechModelPipelineInterface(torch.nn.Module):
             # it, or the block returns to the side-stream pool when `hb` is dropped and a later batch's H2D copy
             # (issued batches ahead of the GPU) may overwrite it before the filterbank kernel has run
             hb.cat.record_stream(cur)
-        fb, lens = fbank_batch_flat(hb.cat, hb.offsets)
+        cat, offsets = hb.cat, hb.offsets
+        if hb.rates is not None and any(r != 16000 for r in hb.rates):  # one launch; 16 kHz clips of the batch are copied
+            cat, offsets = resample_batch_flat(cat, offsets, hb.rates, 16000)
+        fb, lens = fbank_batch_flat(cat, offsets)
         t = fb.shape[1]
         if pad_idx != 0:
             for i, l in enumerate(lens):
@@ -250,11 +291,14 @@ class SpeechToEmbeddingModelPipeline(SpeechModelPipelineInterface):
 
     @torch.inference_mode()
     def predict(self, input: Sequence[Union[str, Path, torch.Tensor]], batch_size: int = 3, n_parallel: int = 1,
-                pad_idx: int = 0, n_prefetched_batches: int = 2, progress_bar: bool = False) -> torch.Tensor:
+                pad_idx: int = 0, n_prefetched_batches: int = 2, progress_bar: bool = False,
+                resample: bool = False) -> torch.Tensor:
+        """`resample=True`: files of any sample rate and `(waveform, sample_rate)` pairs are converted to 16 kHz on the
+        device (module docstring); the default refuses anything but 16 kHz, as the reference's users are told to."""
         if batch_size <= 0:
             raise ValueError("`batch_size` should be strictly positive")
         items = list(input)
-        batches: Iterable = self._prefetched(items, batch_size, n_parallel, n_prefetched_batches)
+        batches: Iterable = self._prefetched(items, batch_size, n_parallel, n_prefetched_batches, resample)
         if progress_bar:
             batches = add_progress_bar(batches, inputs=items, batch_size=batch_size)
         results: List[torch.Tensor] = []
@@ -287,8 +331,9 @@ class SpeechToTextModelPipeline(SpeechModelPipelineInterface):
     def predict(self, input: Sequence[Union[str, Path, torch.Tensor]], target_lang: Union[str, Sequence[str]],
                 batch_size: int = 3, n_parallel: int = 1, pad_idx: int = 0, n_prefetched_batches: int = 2,
                 progress_bar: bool = False, prefixes: Optional[Sequence[Optional[str]]] = None,
-                **generator_kwargs) -> List[str]:
-        """`target_lang` (one, or one per input) and `prefixes` as in EmbeddingToTextModelPipeline.predict."""
+                resample: bool = False, **generator_kwargs) -> List[str]:
+        """`target_lang` (one, or one per input) and `prefixes` as in EmbeddingToTextModelPipeline.predict; `resample` as in
+        SpeechToEmbeddingModelPipeline.predict."""
         if batch_size <= 0:
             raise ValueError("`batch_size` should be strictly positive")
         items = list(input)
@@ -297,7 +342,7 @@ class SpeechToTextModelPipeline(SpeechModelPipelineInterface):
         prefixes = None if prefixes is None else list(prefixes)
         if (per_row and len(target_lang) != len(items)) or (prefixes is not None and len(prefixes) != len(items)):
             raise ValueError(f"one target language / prefix per input expected ({len(items)} inputs)")
-        batches: Iterable = self._prefetched(items, batch_size, n_parallel, n_prefetched_batches)
+        batches: Iterable = self._prefetched(items, batch_size, n_parallel, n_prefetched_batches, resample)
         if progress_bar:
             batches = add_progress_bar(batches, inputs=items, batch_size=batch_size)
         out: List[str] = []
