@@ -634,6 +634,40 @@ int smi_xsim_mine(const int32_t* fwd_best, const float* fwd_score, int64_t nx, c
                   int32_t* out_trg, float* out_score, int32_t* out_count, void* workspace, int64_t workspace_bytes,
                   void* stream);
 
+/* DTW alignment of two sentence-embedding sequences that are known to be translations of each other, in order -- the
+ * application of the reference's examples/bilingual_document.ipynb (fastdtw over cosine distances; un-vendored, the
+ * contract is restated in DESIGN.md 3.15 and, loop for loop, in tests/alignment_ref.py).  A ragged batch of n_pairs
+ * document pairs: pair b is rows x_offsets[b] .. x_offsets[b+1] of X against rows y_offsets[b] .. y_offsets[b+1] of Y,
+ * nx x ny cells.  All arithmetic fp32:
+ *   D[0][0] = c[0][0];  D[i][j] = min(D[i-1][j], D[i][j-1], D[i-1][j-1]) + c[i][j]   (one rounding: the add)
+ * over the predecessors that exist and are admissible; a tie goes to the first of up (i-1, j), left (i, j-1), diagonal
+ * (i-1, j-1).  +inf costs mark forbidden cells; NaN costs are outside the contract.
+ *   radius: 0 = the full matrix; r >= 1 = a Sakoe-Chiba band, cell (i, j) admissible iff
+ *           |i (ny-1) - j (nx-1)| <= r max(nx-1, ny-1, 1)  (in int64); the DP visits only the steps the band reaches.
+ *   path: int32 [sum over the non-empty pairs of (nx + ny - 1), 2]; pair b's entries start at the sum over the pairs before
+ *         it and run from (0, 0) to (nx-1, ny-1) in ascending order, path_len[b] (int32) of them, pair-local indices; the
+ *         rest of its nx + ny - 1 entries is scratch.  distance[b] (fp32) = D[nx-1][ny-1].  A pair with an empty side has
+ *         path_len 0 and distance +inf and leaves the other pairs alone.
+ *   offsets: int64 [n_pairs + 1], given TWICE: *_host (host memory: validated, sizes the launches) and the same values in
+ *         device memory (what the kernels read) -- the entries copy nothing and read nothing back, so they are stream-ordered
+ *         and can be captured into a graph.
+ *   workspace: smi_dtw_workspace_bytes() bytes of device memory (enough for either entry), 8-byte aligned; the costs and the
+ *         direction codes are kept for the full nx x ny matrix even under a band.  D is never stored.
+ * smi_dtw_align_cost: the costs are given, device fp32, the pairs' row-major [nx, ny] blocks one after the other.
+ * smi_dtw_align: c[i][j] = 1 - x_i . y_j from rows of smi_xsim_normalize (fp16; every d smi_xsim_topk accepts), the dot
+ *   product one fp32 chain in ascending k, so a pair has the same bits alone or in any batch.
+ * Refused before any launch: n_pairs < 1, a negative radius, negative or decreasing offsets, a workspace that is too small
+ * or misaligned (SMI_ERR_INVALID_ARG); n_pairs > 65535, a pair with more than 2^31 - 1 cells or a side above 2^30, d not a
+ * multiple of 64 (SMI_ERR_UNSUPPORTED).  One workgroup works on a pair: a single huge pair does not fill the chip. */
+int64_t smi_dtw_workspace_bytes(int32_t n_pairs, const int64_t* x_offsets_host, const int64_t* y_offsets_host);
+int smi_dtw_align_cost(const float* cost, int32_t n_pairs, const int64_t* x_offsets_host, const int64_t* y_offsets_host,
+                       const int64_t* x_offsets, const int64_t* y_offsets, int64_t radius, int32_t* path,
+                       int32_t* path_len, float* distance, void* workspace, int64_t workspace_bytes, void* stream);
+int smi_dtw_align(const void* xn_f16, const void* yn_f16, int32_t d, int32_t n_pairs, const int64_t* x_offsets_host,
+                  const int64_t* y_offsets_host, const int64_t* x_offsets, const int64_t* y_offsets, int64_t radius,
+                  int32_t* path, int32_t* path_len, float* distance, void* workspace, int64_t workspace_bytes,
+                  void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

@@ -341,6 +341,11 @@ SYMBOLS = {
     "smi_xsim_pair_scores": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),
     "smi_xsim_mine_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "smi_xsim_mine": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "smi_dtw_workspace_bytes": (_i64, [_i32, C.POINTER(_i64), C.POINTER(_i64)]),
+    "smi_dtw_align_cost": (C.c_int, [_vp, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64,
+                                     _vp]),
+    "smi_dtw_align": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i64, _vp, _vp, _vp, _vp,
+                                _i64, _vp]),
     "smi_gemm_tn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "smi_gemm_tn_tile_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "smi_gemm_tn_splitk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

@@ -707,6 +707,80 @@ int smi_xsim_mine(const int32_t* fwd_best, const float* fwd_score, int64_t nx, c
   return SMI_OK;
 }
 
+// ------------------------------------------------------------- alignment
+namespace {
+
+// Everything the offsets decide, from the HOST copies: SMI_OK and the sizes, or the refusal.
+int dtw_check_offsets(int32_t n_pairs, const int64_t* xo, const int64_t* yo, DtwSizes& sz) {
+  if (!xo || !yo) return fail(SMI_ERR_INVALID_ARG, "null offsets");
+  if (n_pairs < 1) return fail(SMI_ERR_INVALID_ARG, "n_pairs = %d", n_pairs);
+  if (n_pairs > 65535) return fail(SMI_ERR_UNSUPPORTED, "n_pairs = %d: at most 65535 pairs per call", n_pairs);
+  sz = DtwSizes{};
+  for (int32_t b = 0; b < n_pairs; ++b) {
+    const int64_t nx = xo[b + 1] - xo[b], ny = yo[b + 1] - yo[b];
+    if (xo[b] < 0 || yo[b] < 0 || nx < 0 || ny < 0)
+      return fail(SMI_ERR_INVALID_ARG, "offsets must be non-negative and non-decreasing (pair %d)", b);
+    sz.line += ny;
+    if (nx == 0 || ny == 0) continue;
+    if (nx > (1 << 30) || ny > (1 << 30) || nx * ny > 0x7fffffffLL)
+      return fail(SMI_ERR_UNSUPPORTED, "pair %d: %lld x %lld cells do not fit int32", b, (long long)nx, (long long)ny);
+    const int64_t units = dtw_strips(nx) * dtw_steps(ny);
+    sz.codes += units / 16 * 64;
+    sz.skew += units * 64;
+    sz.cells += nx * ny;
+    sz.path += nx + ny - 1;
+    sz.max_tiles = std::max(sz.max_tiles, ((nx + 63) / 64) * ((ny + 63) / 64));
+    sz.max_units = std::max(sz.max_units, units);
+  }
+  return SMI_OK;
+}
+
+int64_t dtw_bytes(int32_t n_pairs, const DtwSizes& sz, bool with_cost) {
+  return (int64_t)n_pairs * 32 + 4 * (sz.line + sz.codes + sz.skew + (with_cost ? sz.cells : 0));
+}
+
+int dtw_run(const void* xn, const void* yn, int32_t d, const float* cost, int32_t n_pairs, const int64_t* xo,
+            const int64_t* yo, const int64_t* xo_dev, const int64_t* yo_dev, int64_t radius, int32_t* path,
+            int32_t* path_len, float* distance, void* ws, int64_t ws_bytes, void* stream) {
+  if (!xo_dev || !yo_dev || !path || !path_len || !distance || !ws) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (radius < 0) return fail(SMI_ERR_INVALID_ARG, "radius = %lld (0 = the full matrix)", (long long)radius);
+  DtwSizes sz;
+  if (const int rc = dtw_check_offsets(n_pairs, xo, yo, sz)) return rc;
+  if ((uintptr_t)ws % 8) return fail(SMI_ERR_INVALID_ARG, "workspace must be 8-byte aligned");
+  if (ws_bytes < dtw_bytes(n_pairs, sz, !cost))
+    return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, this call needs %lld (smi_dtw_workspace_bytes covers it)",
+                (long long)ws_bytes, (long long)dtw_bytes(n_pairs, sz, !cost));
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_dtw((const f16*)xn, (const f16*)yn, d, cost, n_pairs, sz, xo_dev, yo_dev, radius, path, path_len, distance,
+                     ws, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+}  // namespace
+
+int64_t smi_dtw_workspace_bytes(int32_t n_pairs, const int64_t* x_offsets_host, const int64_t* y_offsets_host) {
+  DtwSizes sz;
+  if (dtw_check_offsets(n_pairs, x_offsets_host, y_offsets_host, sz) != SMI_OK) return 0;
+  return dtw_bytes(n_pairs, sz, true);
+}
+
+int smi_dtw_align_cost(const float* cost, int32_t n_pairs, const int64_t* x_offsets_host, const int64_t* y_offsets_host,
+                       const int64_t* x_offsets, const int64_t* y_offsets, int64_t radius, int32_t* path,
+                       int32_t* path_len, float* distance, void* ws, int64_t ws_bytes, void* stream) {
+  if (!cost) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  return dtw_run(nullptr, nullptr, 0, cost, n_pairs, x_offsets_host, y_offsets_host, x_offsets, y_offsets, radius, path,
+                 path_len, distance, ws, ws_bytes, stream);
+}
+
+int smi_dtw_align(const void* xn, const void* yn, int32_t d, int32_t n_pairs, const int64_t* x_offsets_host,
+                  const int64_t* y_offsets_host, const int64_t* x_offsets, const int64_t* y_offsets, int64_t radius,
+                  int32_t* path, int32_t* path_len, float* distance, void* ws, int64_t ws_bytes, void* stream) {
+  if (!xn || !yn) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
+  return dtw_run(xn, yn, d, nullptr, n_pairs, x_offsets_host, y_offsets_host, x_offsets, y_offsets, radius, path, path_len,
+                 distance, ws, ws_bytes, stream);
+}
+
 // -------------------------------------------------------- building blocks
 int smi_pack_tile_major(const void* src, void* dst, int32_t rows, int32_t k, int32_t inverse,
                         void* stream) {

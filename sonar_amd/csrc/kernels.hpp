@@ -165,6 +165,23 @@ hipError_t launch_pair_scores(const f16* Xn, int64_t nx, const f16* Yn, int64_t 
                               const int64_t* trg_idx, int64_t m, const float* fwd_scores, const float* bwd_scores, int k,
                               int kind, float* out, hipStream_t stream);
 
+// DTW alignment of sentence-embedding sequences (align.hip).  Strips of 64 rows; a strip takes
+// dtw_steps(ny) wavefront steps (ny + 63 rounded up to the 16 steps of a code word).
+__host__ __device__ inline int64_t dtw_strips(int64_t nx) { return (nx + 63) / 64; }
+__host__ __device__ inline int64_t dtw_steps(int64_t ny) { return (ny + 63 + 15) / 16 * 16; }
+struct DtwSizes {   // element counts of the workspace sections and the launch extents, summed / maximised over the pairs
+  int64_t line;     // fp32: one bottom-row line per pair, sum of ny
+  int64_t codes;    // u32: strips * steps / 16 * 64
+  int64_t skew;     // fp32: strips * steps * 64
+  int64_t cells;    // fp32: sum of nx * ny (the row-major cost smi_dtw_align computes)
+  int64_t path;     // (i, j) entries: sum of nx + ny - 1 over the non-empty pairs
+  int64_t max_tiles, max_units;  // per pair: 64 x 64 cost tiles, strips * steps
+};
+// cost == nullptr: compute it from xn / yn (rows from launch_l2_normalize) into the workspace; xoff / yoff: device [n_pairs + 1]
+hipError_t launch_dtw(const f16* xn, const f16* yn, int d, const float* cost, int n_pairs, const DtwSizes& sizes,
+                      const int64_t* xoff, const int64_t* yoff, int64_t radius, int32_t* path, int32_t* path_len,
+                      float* distance, void* workspace, hipStream_t stream);
+
 // ---- decoder / beam search (decoder.hip) ----
 hipError_t launch_dec_embed(const int32_t* tok, const f16* table, const float* pe_row, float scale,
                             float* x, int rows, int d, int64_t vocab, hipStream_t stream);
