@@ -699,6 +699,73 @@ int smi_head_featurize(int32_t form, const void* src, const void* mt, const void
 int smi_mlp_head_forward(smi_mlp_head* head, const void* x_f16, int32_t rows, int32_t out_act, float* out,
                          void* stream);
 
+/* Training of MLP heads over frozen embeddings ----------------------------------
+ * The recipe of examples/finetune_sonar_as_toxicity_classifier.ipynb part 4 (a head on the frozen encoder, AdamW,
+ * gradient clipping) for the MLP that smi_mlp_head runs: dims [input_dim, hidden..., out], the same divisibility rules.
+ * Semantics of torch.nn / torch.optim.AdamW (one parameter group: weights and biases decay alike).  Storage: masters,
+ * moments and gradients fp32; an fp16 shadow (RNE) of the hidden weights feeds the same GEMM calls as
+ * smi_mlp_head_forward; activations fp16; dz bf16; the backward products gW = dz^T A and dA = dz W take bf16 operands
+ * with fp32 accumulation.  No atomics: every reduction has one fixed order, a run is reproducible bit for bit.
+ * Dropout masks are a pure function: with site 0 = the input and l = after hidden layer l, row = the position in the batch
+ * and step counted from 1, key = (step*16 + site) * 2^40 + row*width + col, z = mix(seed + 0x9E3779B97F4A7C15 * (key+1))
+ * (mix = the splitmix64 finaliser of the sampler), u = (z >> 40) * 2^-24, kept iff u >= p; kept values are scaled by
+ * 1/(1-p) in fp32 and rounded to fp16.  The key is taken modulo 2^64: the masks repeat after 2^20 steps. */
+typedef struct smi_head_trainer smi_head_trainer; /* opaque */
+typedef struct smi_head_trainer_config {
+  int32_t input_dim;  /* % 64 == 0 */
+  int32_t n_layers;   /* Linear layers including the output layer, 1..8 */
+  int32_t hidden_act; /* 0 ReLU, 1 tanh */
+  int32_t loss;       /* 0 ce (int32 labels, out >= 2, mean over rows), 1 bce with logits, 2 mse (fp32 targets
+                         [n, out], mean over all elements) */
+  int32_t max_batch;  /* batch capacity in rows */
+  int32_t reserved;
+  float p_in;         /* dropout on the input, [0, 1) */
+  float p_hidden;     /* dropout after every hidden activation, [0, 1) */
+  uint64_t seed;      /* of the dropout masks */
+  float beta1, beta2, eps, weight_decay;
+} smi_head_trainer_config;
+/* layers: the initial weights, as for smi_mlp_head_create (fp32 or fp16, host or device). */
+int smi_head_trainer_create(const smi_head_trainer_config* cfg, const smi_mlp_head_layer* layers,
+                            smi_head_trainer** out);
+void smi_head_trainer_destroy(smi_head_trainer* t);
+/* One optimizer step on batch row r = dataset row (perm ? perm[offset + r] : offset + r), r < rows.
+ *   x: device [n, input_dim] of x_dtype (SMI_F32 / SMI_F16); targets: device int32 [n] (ce) or fp32 [n, out];
+ *   perm: device int64 or NULL.  lr: this step's learning rate (the schedule lives on the host); max_grad_norm <= 0 =
+ *   no clipping, else the gradients are scaled by min(1, c / (||g|| + 1e-6)).
+ *   The step's loss is recorded on the device (smi_head_trainer_losses).  loss_out == NULL: the step is only enqueued,
+ *   nothing is read back and the caller guarantees labels in range -- provided the loss record has room: it holds 4096
+ *   steps at creation, smi_head_trainer_reserve sizes it for a run up front, and a step past its end grows it, which
+ *   waits for the device (and cannot be captured); loss_out != NULL: the batch's labels are read back
+ *   and checked BEFORE anything is launched, and the call returns after the step with its loss.
+ * Refused before any launch: a null handle or pointer, rows < 1, rows > max_batch, a label outside 0..out-1. */
+int smi_head_trainer_step(smi_head_trainer* t, const void* x, int32_t x_dtype, const void* targets,
+                          const int64_t* perm, int64_t offset, int32_t rows, float lr, float max_grad_norm,
+                          float* loss_out, void* stream);
+/* The same forward and backward pass with the masks of the NEXT step, no update: grads_out (host, fp32) receives the flat
+ * gradient vector in the order W0, b0, W1, b1, ... (nn.Linear layouts). */
+int smi_head_trainer_gradients(smi_head_trainer* t, const void* x, int32_t x_dtype, const void* targets,
+                               const int64_t* perm, int64_t offset, int32_t rows, float* loss_out, float* grads_out,
+                               void* stream);
+/* Room in the loss record for `more_steps` further steps (allocates and waits for the device; call before the run). */
+int smi_head_trainer_reserve(smi_head_trainer* t, int64_t more_steps);
+/* losses of steps first .. first+count-1 (0-based) -> out (host); waits for the device. */
+int smi_head_trainer_losses(smi_head_trainer* t, int64_t first, int64_t count, float* out);
+/* fp32 masters of one layer -> host w_out [out, in], b_out [out]; waits for the device. */
+int smi_head_trainer_export(smi_head_trainer* t, int32_t layer, float* w_out, float* b_out);
+/* Inference on the current weights, the calls of smi_mlp_head_forward (no dropout): x device f16
+ * [(rows+127)/128*128, input_dim], out device fp32 [rows, out]; out_act 0 none, 1 tanh, 2 sigmoid; rows <= max_batch. */
+int smi_head_trainer_forward(smi_head_trainer* t, const void* x_f16, int32_t rows, int32_t out_act, float* out,
+                             void* stream);
+/* Test entries.  smi_head_bwd_gemm: the backward MFMA kernel alone, operands fp16 or bf16 (SMI_F16 / SMI_BF16), fp32 out:
+ *   mode 0: out[M, N] = sum_r P[r, M] Q[r, N];  mode 1: out[R, N] = sum_m P[R, m] Q[m, N];  R, M % 128 == 0, N % 64 == 0.
+ * smi_head_adamw: gradient-norm reduction, clip scale and one AdamW step (1-based `step`) on device vectors of n
+ *   elements; norm_scale_out (host, may be NULL) receives {||g||, clip scale}. */
+int smi_head_bwd_gemm(int32_t mode, const void* P, int32_t p_dtype, const void* Q, int32_t q_dtype, int32_t R,
+                      int32_t M, int32_t N, float* out_f32, void* stream);
+int smi_head_adamw(float* p, const float* g, float* m, float* v, void* shadow_f16, int64_t n, int64_t step, float lr,
+                   float beta1, float beta2, float eps, float weight_decay, float max_grad_norm, float* norm_scale_out,
+                   void* stream);
+
 /* LASER2 BiLSTM text encoder -------------------------------------------------
  * Replaces LaserLstmEncoder.forward(seqs, seq_lens)   sonar/nn/laser_lstm_encoder.py:60-116
  * for the configurations of Laser2Config              sonar/models/laser2_text/config.py:12-38

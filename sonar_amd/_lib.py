@@ -259,6 +259,12 @@ class smi_mlp_head_layer(C.Structure):
     _fields_ = [("w", smi_tensor), ("b", smi_tensor), ("out_dim", C.c_int32), ("reserved", C.c_int32)]
 
 
+class smi_head_trainer_config(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("input_dim", "n_layers", "hidden_act", "loss", "max_batch", "reserved")] + [
+        ("p_in", C.c_float), ("p_hidden", C.c_float), ("seed", C.c_uint64),
+        ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float)]
+
+
 class smi_laser2_config(C.Structure):
     _fields_ = [
         ("vocab_size", C.c_int64),
@@ -353,6 +359,17 @@ SYMBOLS = {
     "smi_mlp_head_destroy": (None, [_vp]),
     "smi_head_featurize": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "smi_mlp_head_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "smi_head_trainer_create": (C.c_int, [C.POINTER(smi_head_trainer_config), C.POINTER(smi_mlp_head_layer),
+                                          C.POINTER(_vp)]),
+    "smi_head_trainer_destroy": (None, [_vp]),
+    "smi_head_trainer_step": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, _f32, _f32, C.POINTER(_f32), _vp]),
+    "smi_head_trainer_gradients": (C.c_int, [_vp, _vp, _i32, _vp, _vp, _i64, _i32, C.POINTER(_f32), _vp, _vp]),
+    "smi_head_trainer_reserve": (C.c_int, [_vp, _i64]),
+    "smi_head_trainer_losses": (C.c_int, [_vp, _i64, _i64, _vp]),
+    "smi_head_trainer_export": (C.c_int, [_vp, _i32, _vp, _vp]),
+    "smi_head_trainer_forward": (C.c_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "smi_head_bwd_gemm": (C.c_int, [_i32, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "smi_head_adamw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _f32, _f32, _vp, _vp]),
     "smi_laser2_create": (C.c_int, [C.POINTER(smi_laser2_config), C.POINTER(smi_tensor), C.POINTER(smi_laser2_layer), _i64,
                                     C.POINTER(_vp)]),
     "smi_laser2_destroy": (None, [_vp]),
