@@ -668,6 +668,49 @@ int smi_dtw_align(const void* xn_f16, const void* yn_f16, int32_t d, int32_t n_p
                   int32_t* path, int32_t* path_len, float* distance, void* workspace, int64_t workspace_bytes,
                   void* stream);
 
+/* Spherical k-means over sentence embeddings (restated in tests/kmeans_ref.py).  Similarity is cosine, as
+ * everywhere in this section: a row belongs to the nearest of K unit centroids, and a centroid is the normalised sum of its
+ * members.  xn is a matrix from smi_xsim_normalize (fp16, smi_xsim_padded_rows(n) rows; the update reads the first n).
+ *
+ * smi_kmeans_update: sums[c][j] = sum over the rows i with labels[i] == c of xn[i][j] * 2^24, as an EXACT integer (every
+ *   finite fp16 is a multiple of 2^-24), counts[c] = the number of such rows.  sums (int64 [K, d]) and counts (int32 [K]) are
+ *   overwritten.  A row whose label is outside [0, K) is skipped: nothing is read or written through that label (the
+ *   convention of smi_xsim_mine).  An Inf or NaN element contributes 0.  Integer sums do not depend on the order: the same
+ *   bits for any permutation of the rows, any grid, any run.  The rows are bucketed by label and summed in registers by work
+ *   units of SMI_KMEANS_UNIT_ROWS consecutive members; one cluster holding every row is spread over n / SMI_KMEANS_UNIT_ROWS
+ *   units.
+ * smi_kmeans_finalize: for a cluster with counts[c] > 0 and a sum that is not all zero,
+ *   centroids_f32[c][j] = (float)sums[c][j] * 2^-24 (one round to nearest even, then an exact scale) and row c of
+ *   centroids_f16 = what smi_xsim_normalize makes of that fp32 row (it is called, not restated).  Any other cluster keeps
+ *   both of its rows as they were; *empty_count (device int32, overwritten) = the number of those.  centroids_f16 has
+ *   smi_xsim_padded_rows(K) rows; the rows from K on are zeroed.
+ * smi_kmeans_fit: the round loop on one stream, with no host read-back (it can be captured).
+ *   resume = 0: centroids_f32 holds the K initial centroids; centroids_f16 = smi_xsim_normalize of them; every row is
+ *     assigned (smi_xsim_topk, k = 1, unchanged: ties between equal centroids go to the lower index, so a duplicate centroid
+ *     stays empty); then n_iter rounds of update -> finalise -> assign.  objective / moved get n_iter + 1 entries, empty
+ *     n_iter.
+ *   resume = 1: continues an earlier call on the same buffers (labels, centroids): n_iter rounds of update -> finalise ->
+ *     assign, n_iter entries in each record.  fit(0) followed by T calls of fit(1, resume) equals fit(T) bit for bit.
+ *   labels (int32 [n]) / scores (fp32 [n]) always belong to the returned centroids.  objective (fp64): the sum of the scores
+ *   of an assignment, added in a fixed order; moved (int32): the rows whose label differs from the assignment before (n for
+ *   the first one); empty (int32): smi_kmeans_finalize's count.  sums / counts: those of the last update.
+ * workspace: device memory, 16-byte aligned.  update and finalise: smi_kmeans_workspace_bytes(n, K, d) bytes (finalise does
+ *   not depend on n: any n >= 1).  fit: smi_kmeans_workspace_bytes(n, K, d) + smi_xsim_workspace_bytes(n, K, 1, d) + 4 n, each
+ *   term rounded up to a multiple of 16, + 3072.  A smaller buffer is refused, not overrun.
+ * Refused before any launch: a null pointer, n < 1, K < 1, n_iter < 0, a small or misaligned workspace
+ *   (SMI_ERR_INVALID_ARG); d not a multiple of 64, n or K above 2^31 - 256 (SMI_ERR_UNSUPPORTED); for these shapes
+ *   smi_kmeans_workspace_bytes returns 0. */
+#define SMI_KMEANS_UNIT_ROWS 64
+int64_t smi_kmeans_workspace_bytes(int64_t n, int64_t K, int32_t d);
+int smi_kmeans_update(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, int64_t K, int64_t* sums,
+                      int32_t* counts, void* workspace, int64_t workspace_bytes, void* stream);
+int smi_kmeans_finalize(const int64_t* sums, const int32_t* counts, int64_t K, int32_t d, float* centroids_f32,
+                        void* centroids_f16, int32_t* empty_count, void* workspace, int64_t workspace_bytes, void* stream);
+int smi_kmeans_fit(const void* xn_f16, int64_t n, int32_t d, int64_t K, int32_t n_iter, int32_t resume,
+                   float* centroids_f32, void* centroids_f16, int32_t* labels, float* scores, int64_t* sums,
+                   int32_t* counts, double* objective, int32_t* moved, int32_t* empty, void* workspace,
+                   int64_t workspace_bytes, void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

@@ -352,6 +352,11 @@ SYMBOLS = {
                                      _vp]),
     "smi_dtw_align": (C.c_int, [_vp, _vp, _i32, _i32, C.POINTER(_i64), C.POINTER(_i64), _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                 _i64, _vp]),
+    "smi_kmeans_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "smi_kmeans_update": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "smi_kmeans_finalize": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "smi_kmeans_fit": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
+                                 _vp]),
     "smi_gemm_tn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "smi_gemm_tn_tile_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "smi_gemm_tn_splitk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
