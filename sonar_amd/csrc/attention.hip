@@ -13,7 +13,7 @@
 // as V^T is fetched in the same order, so P never moves between lanes or
 // through LDS.  K is staged row-major with the 16-B XOR swizzle (conflict-free
 // ds_read_b128), V row-major too and read through the LDS transpose read
-// (ds_read_b64_tr_b16); both arrive by double-buffered global->LDS DMA.  S <= 514 in SONAR, so the
+// (ds_read_b64_tr_b16, common.hpp lds_tr_read_b64); both arrive by double-buffered global->LDS DMA.  S <= 514 in SONAR, so the
 // kernel is HBM-bound (~64 flop/B); the score matrix never leaves registers.
 #include <cstdlib>
 
@@ -24,16 +24,6 @@ namespace smi {
 
 constexpr int AT_QB = 128;  // queries per workgroup
 constexpr int AT_KB = 64;   // keys per K/V tile
-
-// ds_read_b64_tr_b16 as inline asm (see speech.hip: for the builtin hipcc's LDS-DMA alias tracking waits
-// for the next tile's DMA in front of the first read); results are waited for with an lgkmcnt(0) that
-// carries them as operands.
-template <int OFF>
-__device__ __forceinline__ half4 at_tr_read(unsigned lds_addr) {
-  half4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(OFF));
-  return v;
-}
 
 // TM: ctx is written in the tile-major GEMM operand layout (common.hpp) -- a wave then stores
 // 2 KiB runs (32 rows x 64 B of one k-block) instead of 8-B pieces one row stride apart.
@@ -199,10 +189,10 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
 #pragma unroll
       for (int db = 0; db < 2; ++db) {
         const unsigned a = vaddr[db] + (t & 1) * 2 * TILE + kb * 4096;
-        va[db][0][0] = at_tr_read<0>(a);
-        va[db][0][1] = at_tr_read<1024>(a);
-        va[db][1][0] = at_tr_read<2048>(a);
-        va[db][1][1] = at_tr_read<3072>(a);
+        va[db][0][0] = lds_tr_read_b64<0>(a);
+        va[db][0][1] = lds_tr_read_b64<1024>(a);
+        va[db][1][0] = lds_tr_read_b64<2048>(a);
+        va[db][1][1] = lds_tr_read_b64<3072>(a);
       }
       // the wait carries the results as operands: the MFMAs below depend on IT, not just on the reads
       asm volatile("s_waitcnt lgkmcnt(0)"

@@ -61,6 +61,14 @@ __device__ __forceinline__ float wave_sum(float v) {              // all 64 lane
   const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return __uint_as_float(b[0]) + __uint_as_float(b[1]);
 }
+__device__ __forceinline__ float half_sum(float v) {              // lanes 0..31 and lanes 32..63 apart: wave_sum without its last step
+  v += dpp_f<0xB1>(v);
+  v += dpp_f<0x4E>(v);
+  v += dpp_f<0x141>(v);
+  v += dpp_f<0x140>(v);
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(a[0]) + __uint_as_float(a[1]);
+}
 __device__ __forceinline__ float wave_max(float v) {
   v = fmaxf(v, dpp_f<0xB1>(v));
   v = fmaxf(v, dpp_f<0x4E>(v));
@@ -90,6 +98,19 @@ __device__ __forceinline__ float max_over_groups_of_8(float v) {
   v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
   const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
   return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+
+// LDS transpose read (ds_read_b64_tr_b16) at lds_addr + OFF: a 16-lane group fetches a [4 rows][16 columns] block of
+// 16-bit elements and every lane receives the 4 rows of ITS column (the V^T fragment of O^T += V^T P^T without a
+// transposed copy).  Inline asm, not the builtin: where the LDS is filled by double-buffered global->LDS DMA, hipcc's
+// LDS-DMA alias tracking puts `s_waitcnt vmcnt(0)` in front of the builtin's first read while the NEXT block's DMA is in
+// flight (it cannot see that the DMA targets the other buffer), which would expose that latency in every iteration.
+// The results are waited for explicitly: an lgkmcnt(0) that carries them as operands, before the MFMAs read them.
+template <int OFF>
+__device__ __forceinline__ half4 lds_tr_read_b64(unsigned lds_addr) {
+  half4 v;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(OFF));
+  return v;
 }
 
 // Weight prefetch by surplus workgroups (round 4).  A small-batch forward is a chain of latency-bound launches that

@@ -23,6 +23,7 @@
 #include <type_traits>
 
 #include "kernels.hpp"
+#include "ln_core.hpp"
 #include "step_proc.hpp"
 
 namespace smi {
@@ -175,18 +176,7 @@ __global__ __launch_bounds__(256) void sum_ln_kernel(XT* __restrict__ x, const P
     }
     s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
   }
-  constexpr float inv_d = 1.0f / D;
-  const float mean = wave_sum(s) * inv_d;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < NV; ++k)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float t = v[k][i] - mean;
-      v[k][i] = t;
-      q += t * t;
-    }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + eps);
+  const float rstd = ln_center<4>(v, s, 1.0f / D, eps, wave_sum);
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     half4 o;
@@ -234,30 +224,17 @@ hipError_t launch_sum_layernorm(void* x, const void* parts, int nparts, size_t p
                                 size_t pf_bytes, int parts_f16) {
   const int blocks = (rows + 3) / 4;
   if (!parts) nparts = 0;
-#define SMI_AL_GO(NV, XT, PT)                                                                                           \
-  launch_sum_ln_np<NV, XT, PT>(blocks, stream, (XT*)x, (const PT*)parts, nparts, part_stride, c, group, w, b, eps, h, rows, \
-                               h_tm, pf, pf_bytes)
-#define SMI_AL_CASE(NV)                       \
-  case NV * 256:                              \
-    if (x_f16) {                              \
-      if (parts_f16) SMI_AL_GO(NV, f16, f16); \
-      else SMI_AL_GO(NV, f16, float);         \
-    } else {                                  \
-      if (parts_f16) SMI_AL_GO(NV, float, f16); \
-      else SMI_AL_GO(NV, float, float);       \
-    }                                         \
-    break;
-  switch (d) {
-    SMI_AL_CASE(1)
-    SMI_AL_CASE(2)
-    SMI_AL_CASE(3)
-    SMI_AL_CASE(4)
-    SMI_AL_CASE(8)
-    default: return hipErrorInvalidValue;
-  }
-#undef SMI_AL_CASE
-#undef SMI_AL_GO
-  return hipGetLastError();
+  const bool known = dispatch_nv(d, [&](auto nv) {
+    dispatch_f16(x_f16, [&](auto xt) {
+      dispatch_f16(parts_f16, [&](auto pt) {
+        using XT = decltype(xt);
+        using PT = decltype(pt);
+        launch_sum_ln_np<decltype(nv)::value, XT, PT>(blocks, stream, (XT*)x, (const PT*)parts, nparts, part_stride, c, group,
+                                                      w, b, eps, h, rows, h_tm, pf, pf_bytes);
+      });
+    });
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // -------------------------------------------------- single-query (decode) attention

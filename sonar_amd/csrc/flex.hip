@@ -70,6 +70,7 @@ hipError_t launch_flex_linear(const float* X, int ldx, const float* W, const flo
 }
 
 // ------------------------------------------------------------------ y = LN(x) * w + b, one wave per row, any d
+// (a run-time width, the row re-read from memory per pass: no register share for ln_center of ln_core.hpp to centre)
 __global__ __launch_bounds__(256) void flex_layernorm_kernel(const float* __restrict__ x, const float* __restrict__ w,
                                                              const float* __restrict__ b, float eps,
                                                              float* __restrict__ y, int rows, int d) {

@@ -13,6 +13,7 @@
 
 #include "common.hpp"
 #include "kernels.hpp"
+#include "ln_core.hpp"
 
 namespace smi {
 
@@ -175,19 +176,7 @@ __device__ __forceinline__ void ln_row(const XT* __restrict__ xr, const float* _
     }
     s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
   }
-  constexpr float inv_d = 1.0f / (NV * 256);
-  const float mean = wave_sum(s) * inv_d;
-  float q = 0.f;
-#pragma unroll
-  for (int k = 0; k < NV; ++k) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float c = v[k][i] - mean;
-      v[k][i] = c;
-      q += c * c;
-    }
-  }
-  const float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + eps);
+  const float rstd = ln_center<4>(v, s, 1.0f / (NV * 256), eps, wave_sum);
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
     const f32x4 wv = *(const f32x4*)(w + k * 256 + lane * 4);
@@ -209,28 +198,12 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const XT* __restrict__ x
     if constexpr (sizeof(XT) == 2 && NV % 2 == 0) {
       // fp16 stream: 8 consecutive columns per lane and 512-column block -> 16-B loads and stores
       constexpr int NH = NV / 2;
+      half8 raw[NH];
+#pragma unroll
+      for (int k = 0; k < NH; ++k) raw[k] = *(const half8*)(x + (size_t)r * D + k * 512 + lane * 8);
       float v[NH][8];
-      float sum = 0.f;
-#pragma unroll
-      for (int k = 0; k < NH; ++k) {
-        const half8 raw = *(const half8*)(x + (size_t)r * D + k * 512 + lane * 8);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          v[k][i] = (float)raw[i];
-          sum += v[k][i];
-        }
-      }
-      constexpr float inv_d = 1.0f / D;
-      const float mean = wave_sum(sum) * inv_d;
-      float sq = 0.f;
-#pragma unroll
-      for (int k = 0; k < NH; ++k)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          v[k][i] -= mean;
-          sq += v[k][i] * v[k][i];
-        }
-      const float rstd = 1.0f / sqrtf(wave_sum(sq) * inv_d + eps);
+      const float sum = ln_widen8(raw, v);
+      const float rstd = ln_center<8>(v, sum, 1.0f / D, eps, wave_sum);
 #pragma unroll
       for (int k = 0; k < NH; ++k) {
         const float* wp = w + k * 512 + lane * 8;
@@ -292,27 +265,9 @@ __global__ __launch_bounds__(256) void layernorm_tm_kernel(const XT* __restrict_
       for (int j = 0; j < 2; ++j) {
         const int lr = 4 * wv + 2 * j + rsel;
         float v[NV][8];
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k)
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            v[k][i] = (float)raw[j][k][i];
-            sum += v[k][i];
-          }
-        constexpr float inv_d = 1.0f / D;
-        const float mean = pair_sum(sum) * inv_d;
-        float sq = 0.f;
-#pragma unroll
-        for (int k = 0; k < NV; ++k)
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            v[k][i] -= mean;
-            sq += v[k][i] * v[k][i];
-          }
-        const float var = pair_sum(sq) * inv_d;
+        const float sum = ln_widen8(raw[j], v);
+        const float rstd = ln_center<8>(v, sum, 1.0f / D, eps, pair_sum);
         const bool live = r0 + lr < rows;  // rows past the end of x: exact zeros, whatever the padding of x holds
-        const float rstd = 1.0f / sqrtf(var + eps);
 #pragma unroll
         for (int k = 0; k < NV; ++k) {
           const int c = pair_col(lane, k);
@@ -344,26 +299,9 @@ __global__ __launch_bounds__(256) void layernorm_tm_kernel(const XT* __restrict_
       for (int q = 0; q < 4; ++q) {
         const int lr = wv + 4 * q;
         float v[NH][8];
-        float sum = 0.f;
-#pragma unroll
-        for (int k = 0; k < NH; ++k)
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            v[k][i] = (float)raw[q][k][i];
-            sum += v[k][i];
-          }
-        constexpr float inv_d = 1.0f / D;
-        const float mean = wave_sum(sum) * inv_d;
-        float sq = 0.f;
-#pragma unroll
-        for (int k = 0; k < NH; ++k)
-#pragma unroll
-          for (int i = 0; i < 8; ++i) {
-            v[k][i] -= mean;
-            sq += v[k][i] * v[k][i];
-          }
+        const float sum = ln_widen8(raw[q], v);
+        const float rstd = ln_center<8>(v, sum, 1.0f / D, eps, wave_sum);
         const bool live = r0 + lr < rows;  // rows past the end of x: exact zeros
-        const float rstd = 1.0f / sqrtf(wave_sum(sq) * inv_d + eps);
 #pragma unroll
         for (int k = 0; k < NH; ++k) {
           const float* wp = w + k * 512 + lane * 8;
@@ -420,35 +358,22 @@ hipError_t launch_layernorm(const void* x, const float* w, const float* b, float
   if (rows <= 0) return hipErrorInvalidValue;
   if (x_tm && !(out_tm && x_f16 && d % 512 == 0)) return hipErrorInvalidValue;  // tile-major x: fp16 stream, tile-major h
   const int blocks = out_tm ? min((rows + 15) / 16, 256 * 16) : min((rows + 3) / 4, 256 * 32);
-#define SMI_LN_LAUNCH(NV, XT)                                                                                      \
-  if (out_tm && x_tm)                                                                                              \
-    hipLaunchKernelGGL((layernorm_tm_kernel<NV, f16, true>), dim3(blocks), dim3(256), 0, stream, (const f16*)x, w, \
-                       b, eps, h, rows);                                                                           \
-  else if (out_tm)                                                                                                 \
-    hipLaunchKernelGGL((layernorm_tm_kernel<NV, XT, false>), dim3(blocks), dim3(256), 0, stream, (const XT*)x, w,  \
-                       b, eps, h, rows);                                                                           \
-  else                                                                                                             \
-    hipLaunchKernelGGL((layernorm_kernel<NV, XT>), dim3(blocks), dim3(256), 0, stream, (const XT*)x, w, b, eps, h, \
-                       rows);
-#define SMI_LN_CASE(NV)             \
-  case NV * 256:                    \
-    if (x_f16) {                    \
-      SMI_LN_LAUNCH(NV, f16)        \
-    } else {                        \
-      SMI_LN_LAUNCH(NV, float)      \
-    }                               \
-    break;
-  switch (d) {
-    SMI_LN_CASE(1)
-    SMI_LN_CASE(2)
-    SMI_LN_CASE(3)
-    SMI_LN_CASE(4)
-    SMI_LN_CASE(8)
-    default: return hipErrorInvalidValue;
-  }
-#undef SMI_LN_CASE
-#undef SMI_LN_LAUNCH
-  return hipGetLastError();
+  const bool known = dispatch_nv(d, [&](auto nv) {
+    dispatch_f16(x_f16, [&](auto xt) {
+      constexpr int NV = decltype(nv)::value;
+      using XT = decltype(xt);
+      if (out_tm && x_tm)
+        hipLaunchKernelGGL((layernorm_tm_kernel<NV, f16, true>), dim3(blocks), dim3(256), 0, stream, (const f16*)x, w, b,
+                           eps, h, rows);
+      else if (out_tm)
+        hipLaunchKernelGGL((layernorm_tm_kernel<NV, XT, false>), dim3(blocks), dim3(256), 0, stream, (const XT*)x, w, b,
+                           eps, h, rows);
+      else
+        hipLaunchKernelGGL((layernorm_kernel<NV, XT>), dim3(blocks), dim3(256), 0, stream, (const XT*)x, w, b, eps, h,
+                           rows);
+    });
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------- final LayerNorm + pooling
@@ -582,16 +507,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void ln_pool1024_f16_kernel(const f1
           f[c][e] = (float)v[j][c][e];
           sum += f[c][e];
         }
-      const float mean = M::row_sum(sum) * (1.0f / D);
-      float q = 0.f;
-#pragma unroll
-      for (int c = 0; c < M::NC; ++c)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          f[c][e] -= mean;
-          q += f[c][e] * f[c][e];
-        }
-      const float rstd = 1.0f / sqrtf(M::row_sum(q) * (1.0f / D) + eps);
+      const float rstd = ln_center<8>(f, sum, 1.0f / D, eps, M::row_sum);
       const int g = g0 + M::row(lane, j);
       const bool live = g >= start && g < end;
       const bool last = g == end - 1;
@@ -680,36 +596,17 @@ hipError_t launch_ln_pool(const void* x, const float* w, const float* b, float e
 #undef SMI_LP1024
     return hipGetLastError();
   }
-#define SMI_LP_LAUNCH(NV, OutT, XT)                                                                               \
-  hipLaunchKernelGGL((ln_pool_kernel<NV, OutT, XT>), dim3(N), dim3(256), 0, stream, (const XT*)x, w, b, eps, cu, \
-                     (OutT*)out, (OutT*)encoded, S, pooling);
-#define SMI_LP_CASE(NV)                 \
-  case NV * 256:                        \
-    if (out_is_f32) {                   \
-      if (x_f16) {                      \
-        SMI_LP_LAUNCH(NV, float, f16)   \
-      } else {                          \
-        SMI_LP_LAUNCH(NV, float, float) \
-      }                                 \
-    } else {                            \
-      if (x_f16) {                      \
-        SMI_LP_LAUNCH(NV, f16, f16)     \
-      } else {                          \
-        SMI_LP_LAUNCH(NV, f16, float)   \
-      }                                 \
-    }                                   \
-    break;
-  switch (d) {
-    SMI_LP_CASE(1)
-    SMI_LP_CASE(2)
-    SMI_LP_CASE(3)
-    SMI_LP_CASE(4)
-    SMI_LP_CASE(8)
-    default: return hipErrorInvalidValue;
-  }
-#undef SMI_LP_CASE
-#undef SMI_LP_LAUNCH
-  return hipGetLastError();
+  const bool known = dispatch_nv(d, [&](auto nv) {
+    dispatch_f16(!out_is_f32, [&](auto ot) {
+      dispatch_f16(x_f16, [&](auto xt) {
+        using OutT = decltype(ot);
+        using XT = decltype(xt);
+        hipLaunchKernelGGL((ln_pool_kernel<decltype(nv)::value, OutT, XT>), dim3(N), dim3(256), 0, stream, (const XT*)x, w,
+                           b, eps, cu, (OutT*)out, (OutT*)encoded, S, pooling);
+      });
+    });
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ------------------------------------------------- row-major <-> tile-major

@@ -10,6 +10,7 @@
 // semantics of fairseq2 ~=0.4 as listed in SURVEY a26-a29.
 #include "common.hpp"
 #include "kernels.hpp"
+#include "ln_core.hpp"
 
 namespace smi {
 
@@ -275,6 +276,7 @@ hipError_t launch_fbank(const float* wave, int64_t nsamples, float scale, int st
 // =========================================================== frame stacking + LayerNorm(160)
 // out[row(n, j), 0..159] = f16(LN([fb[n, 2j, :], fb[n, 2j+1, :]])), columns 160..191 zero
 // (K padded to a multiple of 64 for the projection GEMM).  One wave per stacked frame.
+// (A run-time width with masked lanes: ln_center of ln_core.hpp takes neither, so the LayerNorm arithmetic is spelled out here.)
 __global__ __launch_bounds__(256) void stack_ln_kernel(const float* __restrict__ fb, int t, int nb,
                                                        const int32_t* __restrict__ cu,
                                                        const float* __restrict__ w,
@@ -342,34 +344,12 @@ __global__ __launch_bounds__(256) void ln2_kernel(XT* __restrict__ x, const floa
     const int r2 = live ? rr : rows - 1;
     XT* xr2 = x + (size_t)r2 * D;
     auto xp = [&](int k) { return x_tm ? x + tm_offset(r2, (l + 32 * k) * 8, D) : xr2 + (l + 32 * k) * 8; };
-    auto half_sum = [](float v) {  // over the 32 lanes of a row: wave_sum without its last step
-      v += dpp_f<0xB1>(v);
-      v += dpp_f<0x4E>(v);
-      v += dpp_f<0x141>(v);
-      v += dpp_f<0x140>(v);
-      const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-      return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    };
+    half8 raw[NV];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) raw[k] = *(const half8*)xp(k);
     float u[NV][8];
-    float s8 = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-      const half8 raw = *(const half8*)xp(k);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        u[k][i] = (float)raw[i];
-        s8 += u[k][i];
-      }
-    }
-    float mean8 = half_sum(s8) * inv_d, q8 = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        u[k][i] -= mean8;
-        q8 += u[k][i] * u[k][i];
-      }
-    float rstd8 = 1.0f / sqrtf(half_sum(q8) * inv_d + eps);
+    float s8 = ln_widen8(raw, u);
+    float rstd8 = ln_center<8>(u, s8, inv_d, eps, half_sum);  // half_sum: the 32 lanes of the row
     s8 = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -388,16 +368,7 @@ __global__ __launch_bounds__(256) void ln2_kernel(XT* __restrict__ x, const floa
     }
     if (!h) return;
     if (w2) {
-      mean8 = half_sum(s8) * inv_d;
-      q8 = 0.f;
-#pragma unroll
-      for (int k = 0; k < NV; ++k)
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          u[k][i] -= mean8;
-          q8 += u[k][i] * u[k][i];
-        }
-      rstd8 = 1.0f / sqrtf(half_sum(q8) * inv_d + eps);
+      rstd8 = ln_center<8>(u, s8, inv_d, eps, half_sum);
 #pragma unroll
       for (int k = 0; k < NV; ++k) {
         const float* wp = w2 + (l + 32 * k) * 8;
@@ -436,15 +407,7 @@ __global__ __launch_bounds__(256) void ln2_kernel(XT* __restrict__ x, const floa
     }
     s += (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
   }
-  float mean = wave_sum(s) * inv_d, q = 0.f;
-#pragma unroll
-  for (int k = 0; k < NV; ++k)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      v[k][i] -= mean;
-      q += v[k][i] * v[k][i];
-    }
-  float rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + eps);
+  float rstd = ln_center<4>(v, s, inv_d, eps, wave_sum);
   s = 0.f;
 #pragma unroll
   for (int k = 0; k < NV; ++k) {
@@ -467,16 +430,7 @@ __global__ __launch_bounds__(256) void ln2_kernel(XT* __restrict__ x, const floa
   }
   if (!h) return;
   if (w2) {
-    mean = wave_sum(s) * inv_d;
-    q = 0.f;
-#pragma unroll
-    for (int k = 0; k < NV; ++k)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        v[k][i] -= mean;
-        q += v[k][i] * v[k][i];
-      }
-    rstd = 1.0f / sqrtf(wave_sum(q) * inv_d + eps);
+    rstd = ln_center<4>(v, s, inv_d, eps, wave_sum);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
       const f32x4 wv = *(const f32x4*)(w2 + k * 256 + lane * 4);
@@ -502,36 +456,18 @@ hipError_t launch_ln2(void* x, const float* w1, const float* b1, const float* w2
   if (rows <= 0) return hipErrorInvalidValue;
   if (x_tm && (!x_f16 || d % 512)) return hipErrorInvalidValue;  // the tile-major stream is fp16, 16-B chunks per lane
   // 4 rows per workgroup (one wave per row); the fp16 stream with an even NV: 8 (a row pair per wave)
-#define SMI_LN2_LAUNCH(NV, TMF, XT)                                                                                      \
-  hipLaunchKernelGGL((ln2_kernel<NV, TMF, XT>), dim3(sizeof(XT) == 2 && NV % 2 == 0 ? (rows + 7) / 8 : (rows + 3) / 4), dim3(256), 0, \
-                     stream, (XT*)x, w1, b1, w2, b2, eps, h, rows, x_tm);
-#define SMI_LN2_CASE(NV)                 \
-  case NV * 256:                         \
-    if (out_tm) {                        \
-      if (x_f16) {                       \
-        SMI_LN2_LAUNCH(NV, true, f16)    \
-      } else {                           \
-        SMI_LN2_LAUNCH(NV, true, float)  \
-      }                                  \
-    } else {                             \
-      if (x_f16) {                       \
-        SMI_LN2_LAUNCH(NV, false, f16)   \
-      } else {                           \
-        SMI_LN2_LAUNCH(NV, false, float) \
-      }                                  \
-    }                                    \
-    break;
-  switch (d) {
-    SMI_LN2_CASE(1)
-    SMI_LN2_CASE(2)
-    SMI_LN2_CASE(3)
-    SMI_LN2_CASE(4)
-    SMI_LN2_CASE(8)
-    default: return hipErrorInvalidValue;
-  }
-#undef SMI_LN2_CASE
-#undef SMI_LN2_LAUNCH
-  return hipGetLastError();
+  const bool known = dispatch_nv(d, [&](auto nv) {
+    dispatch_f16(x_f16, [&](auto xt) {
+      constexpr int NV = decltype(nv)::value;
+      using XT = decltype(xt);
+      const dim3 grid(sizeof(XT) == 2 && NV % 2 == 0 ? (rows + 7) / 8 : (rows + 3) / 4);
+      if (out_tm)
+        hipLaunchKernelGGL((ln2_kernel<NV, true, XT>), grid, dim3(256), 0, stream, (XT*)x, w1, b1, w2, b2, eps, h, rows, x_tm);
+      else
+        hipLaunchKernelGGL((ln2_kernel<NV, false, XT>), grid, dim3(256), 0, stream, (XT*)x, w1, b1, w2, b2, eps, h, rows, x_tm);
+    });
+  });
+  return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 // ========================================================= relative-position self-attention
@@ -551,16 +487,7 @@ constexpr int RA_QB = 128, RA_KB = 32;
 //    keys r, r+2 of a group in different halves of the 128-B row: 4 rows x 64 B = all 64 banks).
 //  * a DMA instruction writes wave-base + lane*16: thread -> (key = tid>>3, slot = tid&7) fetches the
 //    chunk that belongs in that slot.
-// The transpose reads are inline asm: for the builtin, hipcc's LDS-DMA alias tracking puts
-// `s_waitcnt vmcnt(0)` in front of the first read while the NEXT block's DMA is in flight (it cannot see
-// that the DMA targets the other buffer), which would expose that latency in every iteration.  The asm
-// results are waited for explicitly (lgkmcnt(0)) before the MFMAs read them.
-template <int OFF>
-__device__ __forceinline__ half4 ra_tr_read(unsigned lds_addr) {
-  half4 v;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(lds_addr), "n"(OFF));
-  return v;
-}
+// The transpose reads are lds_tr_read_b64 (common.hpp: inline asm, and why).
 
 // 3 waves per SIMD (<= 168 registers; 3 workgroups x 48 KiB of LDS per CU): the kernel is a chain of LDS round trips, DMA
 // waits and one barrier per 32-key block, so a third resident workgroup is what hides them (round 4; it took 204 registers =
@@ -756,10 +683,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int db = 0; db < 2; ++db) {
       const unsigned a = vaddr[db] + (kb & 1) * 2 * BLK;
-      va[db][0][0] = ra_tr_read<0>(a);
-      va[db][0][1] = ra_tr_read<1024>(a);
-      va[db][1][0] = ra_tr_read<2048>(a);
-      va[db][1][1] = ra_tr_read<3072>(a);
+      va[db][0][0] = lds_tr_read_b64<0>(a);
+      va[db][0][1] = lds_tr_read_b64<1024>(a);
+      va[db][1][0] = lds_tr_read_b64<2048>(a);
+      va[db][1][1] = lds_tr_read_b64<3072>(a);
     }
     // the wait carries the 8 results as operands: the MFMAs below depend on IT, not just on the reads
     asm volatile("s_waitcnt lgkmcnt(0)"
@@ -1035,10 +962,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int db = 0; db < 2; ++db) {
       const unsigned a = vaddr[db] + (kb & 1) * 2 * BLK;
-      va[db][0][0] = ra_tr_read<0>(a);
-      va[db][0][1] = ra_tr_read<1024>(a);
-      va[db][1][0] = ra_tr_read<2048>(a);
-      va[db][1][1] = ra_tr_read<3072>(a);
+      va[db][0][0] = lds_tr_read_b64<0>(a);
+      va[db][0][1] = lds_tr_read_b64<1024>(a);
+      va[db][1][0] = lds_tr_read_b64<2048>(a);
+      va[db][1][1] = lds_tr_read_b64<3072>(a);
     }
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(va[0][0][0]), "+v"(va[0][0][1]), "+v"(va[0][1][0]), "+v"(va[0][1][1]), "+v"(va[1][0][0]),
