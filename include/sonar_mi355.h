@@ -906,6 +906,43 @@ int smi_gemm_tn(int32_t epi, const void* x_f16, const void* w_f16, const float* 
  * projections).  fp16 slabs saturate at +-65504.  in_tm: x and w tile-major. */
 int smi_gemm_tn_splitk(const void* x_f16, const void* w_f16, const float* bias, void* parts, int32_t m, int32_t n, int32_t k,
                        int32_t ksplit, int32_t in_tm, int32_t slab_dtype, void* stream);
+/* Which GEMM engine smi_gemm_tn (ksplit == 0) or smi_gemm_tn_splitk (ksplit >= 1; of epi_sel only SMI_GEMM_IN_TM is read, ldo is
+ * ignored) would run for a request, without launching anything: the library's single routing function, steered by the same
+ * tuning switches as a launch.  fold_kind: 0 none, 1 LayerNorm-fold producer, 2 producer that leaves the rows' partial sums,
+ * 3 consumer with the exact mean term, 4 consumer with centred weights (fold_nparts partial sums per row); stats_kind: 0 none,
+ * 1 tile statistics with scale > 0, 2 tile statistics otherwise.  num_cus 0: the current device's (256 without a device); any other
+ * value needs no device.  engine SMI_GEMM_ENGINE_NONE: the launch is refused (SMI_ERR_UNSUPPORTED).  Like a launch, the query sees the
+ * calling thread's grid cap (a chained decoder call caps its logits GEMM): grid_x is what a launch from THIS thread would get. */
+enum {
+  SMI_GEMM_ENGINE_NONE = 0,
+  SMI_GEMM_ENGINE_RING = 1,         /* 128x128 tiles, ring = 0 (two stages, two workgroups per CU) or 4 stages */
+  SMI_GEMM_ENGINE_LONE64 = 2,       /* 64x64 lone units */
+  SMI_GEMM_ENGINE_LONE16 = 3,       /* k-sliced 64x64 units, unit = 128-column K blocks per unit */
+  SMI_GEMM_ENGINE_PP256 = 4,        /* 8-wave 256x256 ping-pong engine */
+  SMI_GEMM_ENGINE_V2 = 5,           /* 4-wave 256x256 engine, flag = LayerNorm-fold consumer */
+  SMI_GEMM_ENGINE_V2_RESID = 6,     /* ... its tile-major residual stream, flag = leaves partial sums */
+  SMI_GEMM_ENGINE_V2_STATS = 7,     /* ... its logits projection with tile statistics */
+  SMI_GEMM_ENGINE_V2_LONE128 = 8,   /* ... its lone units of unit = 128 / 160 / 192 rows, flag = split-K slabs */
+  SMI_GEMM_ENGINE_V2_LONE160 = 9,
+  SMI_GEMM_ENGINE_V2_LONE192 = 10,
+  SMI_GEMM_ENGINE_COUNT = 11
+};
+#define SMI_GEMM_ENGINE_NAMES \
+  { "none", "ring", "lone64", "lone16", "pp256", "v2", "v2_resid", "v2_stats", "v2_lone128", "v2_lone160", "v2_lone192" }
+typedef struct smi_gemm_route_info {
+  int32_t engine;         /* SMI_GEMM_ENGINE_* */
+  int32_t epi, layout;    /* the kernel's epilogue and LAYOUT (0 row-major, 1 tile-major in, 2 and out, 3 tile-major residual stream) */
+  int32_t ring, unit, flag;
+  int32_t grid_x, grid_y, lds_bytes, ksplit, raster;
+  int32_t reserved;
+  int64_t part_stride;    /* bytes between split-K slabs */
+} smi_gemm_route_info;
+int smi_gemm_route(int32_t epi_sel, int32_t m, int32_t n, int32_t k, int32_t ldo, int32_t has_bias, int32_t fold_kind,
+                   int32_t fold_nparts, int32_t stats_kind, int32_t ksplit, int32_t slab_dtype, int32_t num_cus,
+                   smi_gemm_route_info* out);
+/* The number of K parts (<= max_parts) the decode-time projections give smi_gemm_tn_splitk for an [m, k] x [n, k] product;
+ * num_cus as above.  Negative: an smi_status. */
+int smi_gemm_splitk_parts(int32_t m, int32_t n, int32_t k, int32_t max_parts, int32_t num_cus);
 /* The decoder's logits projection with its fused softmax statistics (exported for tests; TiedProjection + the beam search's
  * log_softmax, sonar/models/sonar_text/factory.py:300-315, sonar/inference_pipelines/text.py:305-346): x, w and the f16 output
  * tile-major, no bias (m, n % 256 == 0, k % 64 == 0), scale > 0; per (256-column tile t, row r), over the columns c < valid_n of

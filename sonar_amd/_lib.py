@@ -281,6 +281,15 @@ class smi_laser2_layer(C.Structure):
     _fields_ = [(n, smi_tensor) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")]
 
 
+class GemmRouteInfo(C.Structure):
+    """smi_gemm_route_info (include/sonar_mi355.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("engine", "epi", "layout", "ring", "unit", "flag", "grid_x", "grid_y", "lds_bytes",
+                                         "ksplit", "raster", "reserved")] + [("part_stride", C.c_int64)]
+
+
+GEMM_ENGINE_NAMES = ("none", "ring", "lone64", "lone16", "pp256", "v2", "v2_resid", "v2_stats", "v2_lone128", "v2_lone160",
+                     "v2_lone192")
+
 ABI_VERSION = 7  # SMI_ABI_VERSION of include/sonar_mi355.h
 
 # every symbol include/sonar_mi355.h declares: name -> (restype, argtypes)
@@ -360,6 +369,8 @@ SYMBOLS = {
     "smi_gemm_tn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "smi_gemm_tn_tile_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "smi_gemm_tn_splitk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "smi_gemm_route": (C.c_int, [_i32] * 12 + [C.POINTER(GemmRouteInfo)]),
+    "smi_gemm_splitk_parts": (C.c_int, [_i32] * 5),
     "smi_mlp_head_create": (C.c_int, [C.POINTER(smi_mlp_head_config), C.POINTER(smi_mlp_head_layer), C.POINTER(_vp)]),
     "smi_mlp_head_destroy": (None, [_vp]),
     "smi_head_featurize": (C.c_int, [_i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp]),

@@ -465,7 +465,7 @@ int smi_text_encoder_forward(smi_text_encoder* e, const int64_t* ids, const int3
   // lone-tile ring engine), and the slabs of both projections are folded into the residual stream by the fused
   // sum + LayerNorm kernel that produces the next GEMM's input -- no separate fold, no separate LayerNorm.
   const bool sb = ffn2_ks > 1 && c.num_layers > 0;
-  const int out_ks = sb ? gemm_splitk_parts((int)rows, d, d, 8) : 1;
+  const int out_ks = sb ? gemm_splitk_parts((int)rows, d, d, 8, gemm_env()) : 1;
   const int max_ks = std::max(ffn2_ks, out_ks);
   if (ffn2_ks > 1 && e->parts.bytes < (size_t)max_ks * rows * d * 4) {
     HIP_TRY(hipStreamSynchronize(stream));
@@ -808,8 +808,8 @@ int smi_gemm_tn(int32_t epi, const void* x, const void* w, const float* bias, vo
   {
     const hipError_t he = launch_gemm_tn(epi, (const f16*)x, (const f16*)w, bias, out, m, n, k, ldo, (hipStream_t)stream);
     // combinations only one engine implements (the GLU epilogue with a tile-major output: the 4-wave engine, from its tile
-    // threshold up, with a bias) are refused, not mis-computed
-    if (he == hipErrorInvalidValue)
+    // threshold up, with a bias) are refused by the router, not mis-computed; a failure of the runtime goes to HIP_TRY
+    if (he == hipErrorNotSupported)
       return fail(SMI_ERR_UNSUPPORTED, "gemm m=%d n=%d k=%d epi=%d: no engine takes this combination", m, n, k, epi);
     HIP_TRY(he);
   }
@@ -826,9 +826,39 @@ int smi_gemm_tn_splitk(const void* x, const void* w, const float* bias, void* pa
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   const hipError_t e = launch_gemm_tn_splitk((const f16*)x, (const f16*)w, bias, parts, m, n, k, ksplit, (hipStream_t)stream,
                                              in_tm ? 1 : 0, slab_dtype == SMI_F16);
-  if (e == hipErrorInvalidValue) return fail(SMI_ERR_UNSUPPORTED, "split-K gemm: k=%d does not split into %d parts", k, ksplit);
+  if (e == hipErrorNotSupported) return fail(SMI_ERR_UNSUPPORTED, "split-K gemm: k=%d does not split into %d parts", k, ksplit);
   HIP_TRY(e);
   return SMI_OK;
+}
+
+static_assert(GEMM_NONE == SMI_GEMM_ENGINE_NONE && GEMM_RING == SMI_GEMM_ENGINE_RING && GEMM_LONE64 == SMI_GEMM_ENGINE_LONE64 &&
+                  GEMM_LONE16 == SMI_GEMM_ENGINE_LONE16 && GEMM_PP256 == SMI_GEMM_ENGINE_PP256 && GEMM_V2 == SMI_GEMM_ENGINE_V2 &&
+                  GEMM_V2_RESID == SMI_GEMM_ENGINE_V2_RESID && GEMM_V2_STATS == SMI_GEMM_ENGINE_V2_STATS &&
+                  GEMM_V2_LONE128 == SMI_GEMM_ENGINE_V2_LONE128 && GEMM_V2_LONE160 == SMI_GEMM_ENGINE_V2_LONE160 &&
+                  GEMM_V2_LONE192 == SMI_GEMM_ENGINE_V2_LONE192 && (int)GEMM_ENGINE_COUNT == (int)SMI_GEMM_ENGINE_COUNT,
+              "sonar_mi355.h: SMI_GEMM_ENGINE_* mirror GemmEngine");
+// The router's answer for a launch, without launching (no device needed unless num_cus == 0 asks for the current device's)
+int smi_gemm_route(int32_t epi_sel, int32_t m, int32_t n, int32_t k, int32_t ldo, int32_t has_bias, int32_t fold_kind,
+                   int32_t fold_nparts, int32_t stats_kind, int32_t ksplit, int32_t slab_dtype, int32_t num_cus,
+                   smi_gemm_route_info* out) {
+  if (!out) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (fold_kind < FOLD_NONE || fold_kind > FOLD_CONSUMER_CENTRED || stats_kind < STATS_NONE || stats_kind > STATS_OTHER ||
+      ksplit < 0 || num_cus < 0 || (slab_dtype != SMI_F16 && slab_dtype != SMI_F32))
+    return fail(SMI_ERR_INVALID_ARG, "gemm route query: fold_kind=%d stats_kind=%d ksplit=%d slab_dtype=%d num_cus=%d", fold_kind,
+                stats_kind, ksplit, slab_dtype, num_cus);
+  GemmRequest q = gemm_request(epi_sel, m, n, k, ldo, has_bias != 0, nullptr, nullptr);
+  q.fold = fold_kind, q.fold_nparts = fold_nparts, q.fold_has_c1 = fold_kind >= FOLD_CONSUMER_EXACT;
+  q.stats = stats_kind;
+  if (ksplit) q.ksplit = ksplit, q.slab_f16 = slab_dtype == SMI_F16, q.splitk = true;
+  const GemmRoute r = gemm_route(q, gemm_env(num_cus));
+  *out = smi_gemm_route_info{r.engine, r.epi, r.layout, r.ring, r.unit, r.flag, r.grid_x, r.grid_y, r.lds_bytes, r.ksplit, r.raster,
+                             0, r.part_stride};
+  return SMI_OK;
+}
+
+int smi_gemm_splitk_parts(int32_t m, int32_t n, int32_t k, int32_t max_parts, int32_t num_cus) {
+  if (m <= 0 || n <= 0 || k <= 0 || max_parts < 1 || num_cus < 0) return fail(SMI_ERR_INVALID_ARG, "bad argument");
+  return gemm_splitk_parts(m, n, k, max_parts, gemm_env(num_cus));
 }
 
 int smi_gemm_tn_tile_stats(const void* x, const void* w, void* out, int32_t m, int32_t n, int32_t k, float scale, int32_t valid_n,

@@ -232,7 +232,7 @@ int decoder_step(smi_text_decoder* D, DecWork& S, int rows, int rows_pad, int gr
   const DecTuning& tu = S.tuning;
   // (an override the slab buffer or the K split cannot take falls back to the automatic choice)
   const bool ks_out_ok = tu.ks_out >= 1 && tu.ks_out <= kMaxParts && d % (64 * tu.ks_out) == 0;
-  const int ks_out = ks_out_ok ? tu.ks_out : gemm_splitk_parts(rows_pad, d, d, kMaxParts);
+  const int ks_out = ks_out_ok ? tu.ks_out : gemm_splitk_parts(rows_pad, d, d, kMaxParts, gemm_env());
   const int ks_ffn = tu.ks_ffn > 0 && tu.ks_ffn <= kMaxParts && f % (256 * tu.ks_ffn) == 0
                          ? tu.ks_ffn : (f % 512 == 0 ? 8 : (f % 256 == 0 ? 4 : 1));
   // A chain of a split call (S.chained) has too few FFN-inner tiles for the automatic engine choice (3 x 32 at 768

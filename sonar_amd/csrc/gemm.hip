@@ -4,9 +4,6 @@
 // ConformerBlock built by sonar/models/sonar_speech/factory.py:64-71), fp16 in, fp32
 // accumulate on MFMA (v_mfma_f32_16x16x32_f16 in the 256x256 engine, 32x32x16 in the 128x128 one),
 // with the epilogues fused.
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "gemm_epi.hpp"
@@ -1073,229 +1070,78 @@ int num_cus() {
   return n;
 }
 
+// one relaxed atomic load per switch and launch (decode-time paths switch them per call)
+GemmEnv gemm_env(int cus) {
+  GemmEnv e{cus > 0 ? cus : num_cus(), g2_grid_cap};
+  e.lone = tune(TUNE_LONE, 1), e.lone16 = tune(TUNE_LONE16, 1), e.lone_ks = tune(TUNE_LONE_KS, 0);
+  e.g2_auto_min = tune(TUNE_G2_AUTO_MIN, 128), e.g2_splitk_min = tune(TUNE_G2_SPLITK_MIN, 96);
+  e.g2v2 = tune(TUNE_G2V2, 1), e.g2v2_min = tune(TUNE_G2V2_MIN, 128);
+  e.dec_m160 = tune(TUNE_DEC_M160, 1), e.g2_raster = tune(TUNE_G2_RASTER, 2);
+  return e;
+}
+
+static_assert(ROUTE_LDS_RING_STAGE == GT_STAGE_BYTES && ROUTE_LDS_LONE64 == LoneShape<64, 64>::LDS_BYTES &&
+                  ROUTE_LDS_LONE16 == L16_LDS_BYTES && ROUTE_LDS_PP256 == G2_KERNEL_LDS_BYTES,
+              "gemm_route.hpp: LDS sizes of the engines of this file");
+static_assert(ROUTE_T256 == G2_BM && ROUTE_T256 == G2_BN && ROUTE_T256 == TM_ROWS && ROUTE_BK256 == G2_BK && ROUTE_T128 == GT_BM &&
+                  ROUTE_T128 == GT_BN && ROUTE_BK128 == GT_BK && ROUTE_T64 == L16_BM && ROUTE_T64 == L16_BN,
+              "gemm_route.hpp: tile sizes of the engines of this file");
+
+// The (EPI, LAYOUT) pairs the 128x128 family and the 8-wave engine are instantiated for (gemm_route.hpp: layout_of)
+#define SMI_EPI_LAYOUTS(X)                                                                                              \
+  X(EPI_BIAS_F16, 0) X(EPI_RELU_F16, 0) X(EPI_RESID_F32, 0) X(EPI_STORE_F32, 0) X(EPI_RESID_HALF_F32, 0) X(EPI_SILU_F16, 0) \
+  X(EPI_GLU_F16, 0) X(EPI_TANH_F16, 0) X(EPI_RESID_F16, 0) X(EPI_RESID_HALF_F16, 0)                                     \
+  X(EPI_BIAS_F16, 1) X(EPI_RESID_F32, 1) X(EPI_STORE_F32, 1) X(EPI_RESID_HALF_F32, 1) X(EPI_RESID_F16, 1)               \
+  X(EPI_RESID_HALF_F16, 1) X(EPI_GLU_F16, 1)                                                                            \
+  X(EPI_BIAS_F16, 2) X(EPI_RELU_F16, 2) X(EPI_SILU_F16, 2) X(EPI_RESID_F16, 3) X(EPI_RESID_HALF_F16, 3)
+
+// The engines of this file (GEMM_RING, GEMM_LONE64, GEMM_LONE16, GEMM_PP256): the route's coordinates -> the instantiation
 template <int EPI, int LAYOUT>
-static hipError_t launch_one256(const f16* X, const f16* W, const float* bias, void* out, int M,
-                                int N, int K, int ldo, hipStream_t stream, const GemmTileStats* stats = nullptr,
-                                int ksplit = 1, size_t part_stride = 0, const GemmLnFold* fold = nullptr) {
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn256_kernel<EPI, LAYOUT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, G2_KERNEL_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_done.set();
-  }
-  int grid = std::min((M / G2_BM) * (N / G2_BN) * ksplit, num_cus());
-  if (g2_grid_cap > 0) grid = std::min(grid, g2_grid_cap);
-  const int want_raster = tune(TUNE_G2_RASTER, 2);  // G2_RASTER=0 restores the id-order raster everywhere (A/B measurements)
-  const int ntm = M / G2_BM, ntn = N / G2_BN;
-  // XCD-owned m-groups (see the kernel): whole chip, >= 4 n-quads, and a number of m-groups (8 row tiles each) that
-  // deals evenly to the 8 XCDs -- otherwise the id-order raster balances better
-  const int raster = (want_raster && ksplit == 1 && grid == 256 && ntn % 4 == 0 && ntn >= 16 && ((ntm + 7) / 8) % 8 == 0)
-                         ? want_raster : 0;
-  hipLaunchKernelGGL((gemm_tn256_kernel<EPI, LAYOUT>), dim3(grid), dim3(G2_THREADS), G2_KERNEL_LDS_BYTES,
-                     stream, X, W, bias, out, M, N, K, ldo, stats ? *stats : GemmTileStats{nullptr, nullptr, 1.f, 0}, ksplit,
-                     part_stride, raster, fold ? *fold : GemmLnFold{nullptr, nullptr, nullptr, 0, 0.f, 0.f, 0});
-  return hipGetLastError();
-}
-
-// SMI_LONE: 0 = round 3's ring for every lone-tile launch (A/B runs; read per launch: decode-time paths switch it per
-// call), otherwise 64x64 units of the lone-tile engine (gemm_lone.hpp) when a launch is small enough for them.
-static bool lone_enabled() {
-  return tune(TUNE_LONE, 1) != 0;
-}
-// 64x64 units, two workgroups per CU (64 KiB of LDS each): used while all units are resident at once.  Measured
-// (profiles/r04_experiments.txt, experiment 11): at M = 256 / 512 every projection of the encoder is 25-35 % faster than on
-// 128x128 tiles (more CUs stream operands, a unit has a quarter of the MFMAs and half the LDS traffic); past ~2 units
-// per CU (M = 1280 x N = 3072: 960 units) the 128x128 ring wins again -- a 64x64 unit moves twice the operand bytes per
-// flop through L2.
-static bool lone_fits(int M, int N, int ksplit) {
-  return (int64_t)(M / 64) * (N / 64) * ksplit <= 2 * (int64_t)num_cus();
-}
-static bool ring_fits(int M, int N, int ksplit) {
-  return (int64_t)(M / GT_BM) * (N / GT_BN) * ksplit <= num_cus();
-}
-
-template <int EPI, int LAYOUT, int RING>
-static hipError_t launch_one_ring(const f16* X, const f16* W, const float* bias, void* out, int M, int N,
-                                  int K, int ldo, hipStream_t stream, int ksplit, size_t part_stride) {
-  constexpr int lds = (RING ? RING : 2) * GT_STAGE_BYTES;
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<EPI, LAYOUT, RING>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done.set();
-  }
-  const int grid = (M / GT_BM) * (N / GT_BN);
-  hipLaunchKernelGGL((gemm_tn_kernel<EPI, LAYOUT, RING>), dim3(grid, ksplit), dim3(GT_THREADS), lds,
-                     stream, X, W, bias, out, M, N, K, ldo, ksplit, part_stride);
-  return hipGetLastError();
-}
-
-template <int EPI, int LAYOUT, int BM, int BN>
-static hipError_t launch_lone(const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K, int ldo,
-                              hipStream_t stream, int ksplit, size_t part_stride) {
-  constexpr int lds = LoneShape<BM, BN>::LDS_BYTES;
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_lone_kernel<EPI, LAYOUT, BM, BN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return e;
-    attr_done.set();
-  }
-  const int grid = (M / BM) * (N / BN);
-  hipLaunchKernelGGL((gemm_lone_kernel<EPI, LAYOUT, BM, BN>), dim3(grid, ksplit), dim3(GT_THREADS), lds, stream, X, W,
-                     bias, out, M, N, K, ldo, ksplit, part_stride);
-  return hipGetLastError();
-}
-
-// the k-sliced unit (gemm_lone16.hpp): tile-major operands, K per unit 256 / 512 / 1024.  SMI_LONE16=0: the LDS-ring unit
-// for every lone launch (A/B runs; its results are bit-identical to the other 128x128-family engines, these are not)
-static bool lone16_enabled() {
-  return tune(TUNE_LONE16, 1) != 0;
-}
-template <int EPI, bool OUT_TM>
-static hipError_t launch_lone16(const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K, int ldo,
-                                hipStream_t stream, int ksplit, size_t part_stride) {
-  const int grid = (M / L16_BM) * (N / L16_BN);
-  const int nkb = K / ksplit / 128;
-#define SMI_L16(NKB)                                                                                                      \
-  {                                                                                                                       \
-    static DeviceOnce attr_done;                                                                                          \
-    if (!attr_done.done()) {                                                                                              \
-      hipError_t e = hipFuncSetAttribute((const void*)gemm_lone16_kernel<EPI, OUT_TM, NKB>,                               \
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, L16_LDS_BYTES);                      \
-      if (e != hipSuccess) return e;                                                                                      \
-      attr_done.set();                                                                                                    \
-    }                                                                                                                     \
-    hipLaunchKernelGGL((gemm_lone16_kernel<EPI, OUT_TM, NKB>), dim3(grid, ksplit), dim3(L16_THREADS), L16_LDS_BYTES,     \
-                       stream, X, W, bias, out, M, N, K, ldo, part_stride);                                               \
-  }
-  if (nkb == 8) SMI_L16(8) else if (nkb == 4) SMI_L16(4) else SMI_L16(2)
-#undef SMI_L16
-  return hipGetLastError();
-}
-
-template <int EPI, int LAYOUT = 0>
-static hipError_t launch_one(const f16* X, const f16* W, const float* bias, void* out, int M, int N,
-                             int K, int ldo, hipStream_t stream, int ksplit = 1, size_t part_stride = 0) {
+static hipError_t launch_tile(const GemmRoute& r, const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K,
+                              int ldo, hipStream_t stream, const GemmTileStats* stats, const GemmLnFold* fold) {
+  const dim3 grid(r.grid_x, r.grid_y);
+  const size_t ps = (size_t)r.part_stride;
+  if (r.engine == GEMM_PP256)
+    return launch_with_lds<gemm_tn256_kernel<EPI, LAYOUT>>(grid, G2_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, ldo,
+                                                           stats ? *stats : GemmTileStats{nullptr, nullptr, 1.f, 0}, r.ksplit, ps,
+                                                           r.raster, fold ? *fold : GemmLnFold{nullptr, nullptr, nullptr, 0, 0.f, 0.f, 0});
   if constexpr ((EPI == EPI_BIAS_F16 || EPI == EPI_RELU_F16 || EPI == EPI_STORE_F32) && (LAYOUT == 1 || LAYOUT == 2)) {
-    const int klen = K / ksplit;
-    if (lone_enabled() && lone16_enabled() && lone_fits(M, N, ksplit) && K % ksplit == 0 &&
-        (klen == 256 || klen == 512 || klen == 1024) && (EPI != EPI_STORE_F32 || LAYOUT == 1))
-      return launch_lone16<EPI, LAYOUT == 2>(X, W, bias, out, M, N, K, ldo, stream, ksplit, part_stride);
+    if (r.engine == GEMM_LONE16) {
+#define SMI_L16(NKB)                                                                                                       \
+  launch_with_lds<gemm_lone16_kernel<EPI, LAYOUT == 2, NKB>>(grid, L16_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, ldo, ps)
+      return r.unit == 8 ? SMI_L16(8) : r.unit == 4 ? SMI_L16(4) : SMI_L16(2);
+#undef SMI_L16
+    }
   }
-  if constexpr (EPI != EPI_GLU_F16)  // GLU pairs two 32-column blocks of a wave: 128-column tiles only
-    if (lone_enabled() && lone_fits(M, N, ksplit))
-      return launch_lone<EPI, LAYOUT, 64, 64>(X, W, bias, out, M, N, K, ldo, stream, ksplit, part_stride);
-  // every workgroup gets a CU of its own: hide the DMA latency with a deeper ring instead of a second workgroup
-  if (ring_fits(M, N, ksplit))
-    return launch_one_ring<EPI, LAYOUT, 4>(X, W, bias, out, M, N, K, ldo, stream, ksplit, part_stride);
-  return launch_one_ring<EPI, LAYOUT, 0>(X, W, bias, out, M, N, K, ldo, stream, ksplit, part_stride);
+  if constexpr (EPI != EPI_GLU_F16) {  // GLU pairs two 32-column blocks of a wave: 128-column tiles only
+    if (r.engine == GEMM_LONE64)
+      return launch_with_lds<gemm_lone_kernel<EPI, LAYOUT, 64, 64>>(grid, GT_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K,
+                                                                    ldo, r.ksplit, ps);
+  }
+  if (r.engine != GEMM_RING) return hipErrorInvalidValue;
+  return r.ring ? launch_with_lds<gemm_tn_kernel<EPI, LAYOUT, 4>>(grid, GT_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, ldo,
+                                                                  r.ksplit, ps)
+                : launch_with_lds<gemm_tn_kernel<EPI, LAYOUT, 0>>(grid, GT_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, ldo,
+                                                                  r.ksplit, ps);
+}
+
+static hipError_t launch_route(const GemmRoute& r, const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K,
+                               int ldo, hipStream_t stream, const GemmTileStats* stats, const GemmLnFold* fold) {
+  if (r.engine == GEMM_NONE) return hipErrorNotSupported;
+  if (r.engine >= GEMM_V2_LONE128) return launch_gemm_v2_lone(r, X, W, bias, out, M, N, K, stream);
+  if (r.engine >= GEMM_V2) return launch_gemm_v2(r, X, W, bias, (f16*)out, M, N, K, stream, stats, fold);
+#define SMI_TILE_CASE(E, L) \
+  if (r.epi == E && r.layout == L) return launch_tile<E, L>(r, X, W, bias, out, M, N, K, ldo, stream, stats, fold);
+  SMI_EPI_LAYOUTS(SMI_TILE_CASE)
+#undef SMI_TILE_CASE
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_gemm_tn(int epi_sel, const f16* X, const f16* W, const float* bias, void* out,
                           int M, int N, int K, int ldo, hipStream_t stream, const GemmTileStats* stats,
                           const GemmLnFold* fold) {
-  // epi_sel = epilogue | (engine << 8) | layout flags: engine 0 auto, 1 force 128x128, 2 force
-  // 256x256; GEMM_IN_TM = X and W tile-major, GEMM_OUT_TM = fp16 output tile-major (needs IN_TM)
-  const int epi = epi_sel & 0xff, sel = (epi_sel >> 8) & 0xf;
-  const bool in_tm = epi_sel & GEMM_IN_TM, out_tm = epi_sel & GEMM_OUT_TM;
-  if (M % GT_BM || N % GT_BN || K % GT_BK || M <= 0) return hipErrorInvalidValue;
-  if (in_tm && (M % TM_ROWS || N % TM_ROWS)) return hipErrorInvalidValue;
-  if (out_tm && (!in_tm || ldo != (epi == EPI_GLU_F16 ? N / 2 : N))) return hipErrorInvalidValue;
-  const bool can256 = M % G2_BM == 0 && N % G2_BN == 0;
-  if (sel == 2 && !can256) return hipErrorInvalidValue;
-  // the 256x256 ping-pong engine is ~1.5x more efficient per CU than the 128x128 one but has a 21 us
-  // floor for a K = 1024 tile and one workgroup per CU; measured crossover (tools/probe_engines.py):
-  // 128 tiles tie, 160 tiles win; round 4 (tools/probe_engines_mid.py, M = 1024 x N = 8192 = 128 tiles, tile-major operands): 25.8 vs
-  // 28.6 us hot, 31.8 vs 33.8 us on cold weights -> use it from 128 tiles (half the CUs) up
-  // (SMI_G2_AUTO_MIN overrides the threshold, read per launch: tests that compare runs of different row counts bit for bit
-  // pin the engine family with it)
-  const int64_t auto_min = tune(TUNE_G2_AUTO_MIN, 128);
-  const bool use256 = sel == 2 || (sel == 0 && can256 && (int64_t)(M / G2_BM) * (N / G2_BN) >= auto_min);
-  if (fold) {  // LayerNorm fold: 256x256 engine, tile-major stream
-    if (!can256 || sel == 1 || !in_tm || stats) return hipErrorInvalidValue;
-    if (fold->part_in) {  // consumer: tile-major outputs (bias / relu / silu) or row-major ones (bias / GLU; centred weights)
-      if (!fold->c1 || fold->nparts < 1 || fold->nparts > 4) return hipErrorInvalidValue;
-      if (out_tm) {
-        // the 4-wave engine (gemm_v2.hip) where it applies: >= 24 K slices, several persistent rounds
-        if (gemm_v2_fits(epi, M, N, K, bias, fold)) return launch_gemm_v2(epi, X, W, bias, (f16*)out, M, N, K, stream, fold);
-        if (epi == EPI_BIAS_F16) return launch_one256<EPI_BIAS_F16, 2>(X, W, bias, out, M, N, K, ldo, stream, nullptr, 1, 0, fold);
-        if (epi == EPI_RELU_F16) return launch_one256<EPI_RELU_F16, 2>(X, W, bias, out, M, N, K, ldo, stream, nullptr, 1, 0, fold);
-        if (epi == EPI_SILU_F16 && fold->centered)
-          return launch_one256<EPI_SILU_F16, 2>(X, W, bias, out, M, N, K, ldo, stream, nullptr, 1, 0, fold);
-        return hipErrorInvalidValue;
-      }
-      if (!fold->centered) return hipErrorInvalidValue;
-      if (epi == EPI_BIAS_F16) return launch_one256<EPI_BIAS_F16, 1>(X, W, bias, out, M, N, K, ldo, stream, nullptr, 1, 0, fold);
-      if (epi == EPI_GLU_F16) return launch_one256<EPI_GLU_F16, 1>(X, W, bias, out, M, N, K, ldo, stream, nullptr, 1, 0, fold);
-      return hipErrorInvalidValue;
-    }
-    // producer: the tile-major residual epilogue (part_out may be null: plain read-modify-write of the stream)
-    if (!out_tm) return hipErrorInvalidValue;
-    if ((epi == EPI_RESID_F16 || epi == EPI_RESID_HALF_F16) && gemm_v2_fits(epi, M, N, K, bias, fold))
-      return launch_gemm_v2(epi, X, W, bias, (f16*)out, M, N, K, stream, fold);
-    if (epi == EPI_RESID_F16) return launch_one256<EPI_RESID_F16, 3>(X, W, bias, out, M, N, K, ldo, stream, nullptr, 1, 0, fold);
-    if (epi == EPI_RESID_HALF_F16)
-      return launch_one256<EPI_RESID_HALF_F16, 3>(X, W, bias, out, M, N, K, ldo, stream, nullptr, 1, 0, fold);
-    return hipErrorInvalidValue;
-  }
-  if (stats) {  // tile statistics: the 256x256 engine's fp32-store epilogue or its tile-major fp16 store, without a bias
-    if (epi == EPI_BIAS_F16 && out_tm && in_tm && can256 && sel != 1 && !bias) {
-      if (gemm_v2_stats_fits(M, N, K, stats)) return launch_gemm_v2_stats(X, W, (f16*)out, M, N, K, stream, stats, g2_grid_cap);
-      return launch_one256<EPI_BIAS_F16, 2>(X, W, bias, out, M, N, K, ldo, stream, stats);
-    }
-    if (epi != EPI_STORE_F32 || out_tm || !can256 || sel == 1 || bias) return hipErrorInvalidValue;
-    return in_tm ? launch_one256<EPI_STORE_F32, 1>(X, W, bias, out, M, N, K, ldo, stream, stats)
-                 : launch_one256<EPI_STORE_F32, 0>(X, W, bias, out, M, N, K, ldo, stream, stats);
-  }
-#define SMI_EPI_CASE(E, L)                                                     \
-  case E:                                                                      \
-    return use256 ? launch_one256<E, L>(X, W, bias, out, M, N, K, ldo, stream) \
-                  : launch_one<E, L>(X, W, bias, out, M, N, K, ldo, stream);
-  if (out_tm) {  // fp16 outputs that feed the next GEMM; EPI_RESID_F16: the tile-major residual stream
-    // a decode step's FFN-inner projection (M = 1280 rows): 256 lone units of 160 x 256 instead of 160 of 256 x 256
-    // (and the small-batch encoder's fused QKV projection: bias, tile-major out)
-    if ((epi == EPI_RELU_F16 || epi == EPI_BIAS_F16) && sel != 1 && gemm_v2_lone_fits(M, N, K, 1))
-      return launch_gemm_v2_lone(epi == EPI_RELU_F16 ? 1 : 2, X, W, bias, out, M, N, K, 1, stream);
-    if (use256 && gemm_v2_fits(epi, M, N, K, bias, nullptr))
-      return launch_gemm_v2(epi, X, W, bias, (f16*)out, M, N, K, stream, nullptr);
-    switch (epi) {
-      SMI_EPI_CASE(EPI_BIAS_F16, 2)
-      SMI_EPI_CASE(EPI_RELU_F16, 2)
-      SMI_EPI_CASE(EPI_SILU_F16, 2)
-      SMI_EPI_CASE(EPI_RESID_F16, 3)
-      SMI_EPI_CASE(EPI_RESID_HALF_F16, 3)
-    }
-    return hipErrorInvalidValue;
-  }
-  if (in_tm) {
-    switch (epi) {
-      SMI_EPI_CASE(EPI_BIAS_F16, 1)
-      SMI_EPI_CASE(EPI_RESID_F32, 1)
-      SMI_EPI_CASE(EPI_STORE_F32, 1)
-      SMI_EPI_CASE(EPI_RESID_HALF_F32, 1)
-      SMI_EPI_CASE(EPI_RESID_F16, 1)
-      SMI_EPI_CASE(EPI_RESID_HALF_F16, 1)
-      SMI_EPI_CASE(EPI_GLU_F16, 1)
-    }
-    return hipErrorInvalidValue;
-  }
-  switch (epi) {
-    SMI_EPI_CASE(EPI_BIAS_F16, 0)
-    SMI_EPI_CASE(EPI_RELU_F16, 0)
-    SMI_EPI_CASE(EPI_RESID_F32, 0)
-    SMI_EPI_CASE(EPI_STORE_F32, 0)
-    SMI_EPI_CASE(EPI_RESID_HALF_F32, 0)
-    SMI_EPI_CASE(EPI_SILU_F16, 0)
-    SMI_EPI_CASE(EPI_GLU_F16, 0)
-    SMI_EPI_CASE(EPI_TANH_F16, 0)
-    SMI_EPI_CASE(EPI_RESID_F16, 0)
-    SMI_EPI_CASE(EPI_RESID_HALF_F16, 0)
-  }
-#undef SMI_EPI_CASE
-  return hipErrorInvalidValue;
+  const GemmRequest q = gemm_request(epi_sel, M, N, K, ldo, bias != nullptr, stats, fold);
+  return launch_route(gemm_route(q, gemm_env()), X, W, bias, out, M, N, K, ldo, stream, stats, fold);
 }
 
 // Split-K GEMM into `ksplit` slabs: parts[z][m][n] = X[:, Kz] . W[:, Kz]^T (+ bias for z = 0); the consumer
@@ -1304,74 +1150,10 @@ hipError_t launch_gemm_tn(int epi_sel, const f16* X, const f16* W, const float* 
 // fp32: half the slab traffic between the two kernels), else fp32.
 hipError_t launch_gemm_tn_splitk(const f16* X, const f16* W, const float* bias, void* parts, int M,
                                  int N, int K, int ksplit, hipStream_t stream, int in_tm, int slab_f16) {
-  if (M % GT_BM || N % GT_BN || ksplit < 1 || K % GT_BK || M <= 0) return hipErrorInvalidValue;
-  if (in_tm && (M % TM_ROWS || N % TM_ROWS)) return hipErrorInvalidValue;
-  // the 256x256 ping-pong engine is far more efficient per CU than the 128x128 one (decoder FFN inner:
-  // 160 tiles on 256 CUs still beat 640 small tiles); use it when the units roughly fill the chip once
-  // and every unit has a real K loop (its K parts may be unequal)
-  const int units256 = (M / G2_BM) * (N / G2_BN) * ksplit;
-  const int min_units = tune(TUNE_G2_SPLITK_MIN, 96);  // A/B switch (an atomic load per launch)
-  const size_t ps = (size_t)M * N * (slab_f16 ? 2 : 4);
-  const bool big = M % G2_BM == 0 && N % G2_BN == 0 && (K / G2_BK) / ksplit >= 16 && units256 >= min_units && units256 <= num_cus();
-  if (!big && K % (GT_BK * ksplit)) return hipErrorInvalidValue;  // the 128x128 engine splits K evenly
-  if (slab_f16) {
-    // ... and its FFN-output projection: 8 x 4 tiles x 8 K parts = 256 lone units (gemm_v2_lone.hip)
-    if (in_tm && gemm_v2_lone_fits(M, N, K, ksplit)) return launch_gemm_v2_lone(0, X, W, bias, parts, M, N, K, ksplit, stream);
-    if (big)
-      return in_tm ? launch_one256<EPI_BIAS_F16, 1>(X, W, bias, parts, M, N, K, N, stream, nullptr, ksplit, ps)
-                   : launch_one256<EPI_BIAS_F16, 0>(X, W, bias, parts, M, N, K, N, stream, nullptr, ksplit, ps);
-    return in_tm ? launch_one<EPI_BIAS_F16, 1>(X, W, bias, parts, M, N, K, N, stream, ksplit, ps)
-                 : launch_one<EPI_BIAS_F16, 0>(X, W, bias, parts, M, N, K, N, stream, ksplit, ps);
-  }
-  if (big)
-    return in_tm ? launch_one256<EPI_STORE_F32, 1>(X, W, bias, parts, M, N, K, N, stream, nullptr, ksplit, ps)
-                 : launch_one256<EPI_STORE_F32, 0>(X, W, bias, parts, M, N, K, N, stream, nullptr, ksplit, ps);
-  return in_tm ? launch_one<EPI_STORE_F32, 1>(X, W, bias, parts, M, N, K, N, stream, ksplit, ps)
-               : launch_one<EPI_STORE_F32, 0>(X, W, bias, parts, M, N, K, N, stream, ksplit, ps);
-}
-
-// How many K parts launch_gemm_tn_splitk should be given for a decode-time projection (M = beam x batch rows,
-// N = model_dim): as many as keep EVERY unit on a CU of its own -- one round of lone tiles is the fastest a
-// latency-bound launch gets -- without starving a unit of K loop.  <= max_parts (the slab buffer).
-int gemm_splitk_parts(int M, int N, int K, int max_parts) {
-  if (M % G2_BM == 0 && N % G2_BN == 0) {
-    const int tiles = (M / G2_BM) * (N / G2_BN);
-    const int ks = std::min(std::min(max_parts, num_cus() / std::max(tiles, 1)), (K / G2_BK) / 16);
-    if (ks >= 1 && tiles * ks >= 96) return ks;
-  }
-  if (lone_enabled()) {
-    // Lone-tile units: the part count with the cheapest launch by a two-term model -- K tiles per unit x the time of one
-    // K tile (measured: 0.15 us for a 64x64 unit with a CU of its own, 0.25 us with two per CU, 0.41 us for a 128x128
-    // ring unit), plus what every part adds around the launch (its slab is written here and read by the consumer:
-    // 8 bytes per output element at ~20 TB/s, it is L2 / Infinity-Cache traffic); a unit keeps at least 4 K tiles.
-    // SMI_LONE_KS overrides (A/B runs).
-    if (const int v = tune(TUNE_LONE_KS, 0)) {
-      if (v >= 1 && v <= max_parts && K % (GT_BK * v) == 0 && (lone_fits(M, N, v) || ring_fits(M, N, v))) return v;
-    }
-    int best = 1;
-    double best_cost = 1e30;
-    for (int ks = 1; ks <= max_parts; ks *= 2) {
-      if (K % (GT_BK * ks) || (ks > 1 && K / ks < 4 * GT_BK)) break;
-      double t_tile;
-      if (lone_fits(M, N, ks))
-        t_tile = (int64_t)(M / 64) * (N / 64) * ks <= num_cus() ? 0.15 : 0.25;
-      else if (ring_fits(M, N, ks))
-        t_tile = 0.41;
-      else
-        break;
-      const double cost = (K / ks / GT_BK) * t_tile + ks * ((double)M * N * 8.0 / 20e6);
-      if (cost < best_cost) {
-        best_cost = cost;
-        best = ks;
-      }
-    }
-    return best;
-  }
-  const int tiles = (M / GT_BM) * (N / GT_BN);
-  int ks = 1;
-  while (ks * 2 <= max_parts && tiles * ks * 2 <= num_cus() && K % (GT_BK * ks * 2) == 0 && K / (ks * 2) >= 2 * GT_BK)
-    ks *= 2;
-  return ks;
+  GemmRequest q{};
+  q.in_tm = in_tm != 0, q.M = M, q.N = N, q.K = K, q.ldo = N, q.has_bias = bias != nullptr;
+  q.ksplit = ksplit, q.slab_f16 = slab_f16 != 0, q.splitk = true;
+  return launch_route(gemm_route(q, gemm_env()), X, W, bias, parts, M, N, K, N, stream, nullptr, nullptr);
 }
 
 }  // namespace smi

@@ -1,7 +1,8 @@
 // Tile-major fp16 GEMMs on the second-generation 256x256 engine (gemm_v2.hpp): C = act(rstd * (X . W^T) [- rstd * mean * c1] + c2),
 // X [M, K] and W [N, K] tile-major fp16, C [M, N] tile-major fp16 (the X operand of the next GEMM).  These are the text
 // encoder's fused QKV and FFN-inner projections (reference wiring: sonar/models/sonar_text/factory.py:130-153), the
-// conformer's FFN-inner projections and every other <bias | relu | silu, tile-major in/out> launch with >= 24 K slices.
+// conformer's FFN-inner projections and pointwise_conv1 + GLU, and every other <bias | relu | silu | GLU, tile-major in/out> launch
+// with >= 8 K slices and enough tiles (gemm_route.hpp: v2_fits); below: the tile-major residual stream and the logits projection.
 //
 // Persistent: one workgroup of 4 waves per CU walks tiles in the raster of the 8-wave engine (gemm.hip).  A tile's life:
 //   step 0          its per-tile constants (c2 / bias, c1, the rows' LayerNorm partial sums) are fetched by LDS-DMA into
@@ -13,7 +14,6 @@
 //                   in 128 VGPRs and issuing 2 stores per K step of the next tile does NOT hide them -- the K loop pulls
 //                   32 KiB per 0.7 us through the CU's memory path, 89 % of the 52 GB/s per CU the L2s deliver, and every
 //                   store byte under the loop slows the loop by its own transfer time: -2.6 us of stores, +2.6 us of loop.)
-#include <algorithm>
 #include <type_traits>
 
 #include "gemm_epi.hpp"
@@ -805,94 +805,30 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_stats_kernel(const f16* __
   emit_stats();
 }
 
-template <int EPI, bool FOLD>
-static hipError_t launch_v2(const f16* X, const f16* W, const float* c2, f16* out, int M, int N, int K, hipStream_t stream,
-                            const GemmLnFold* fold) {
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_v2_kernel<EPI, FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       V2_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_done.set();
+static_assert(ROUTE_LDS_V2 == V2_LDS_BYTES && ROUTE_V2_MIN_SLICES == V2_MIN_SLICES, "gemm_route.hpp: the 4-wave engine's limits");
+
+// GEMM_V2 (flag = FOLD), GEMM_V2_RESID (flag = EMIT) and GEMM_V2_STATS: the route's coordinates -> the instantiation
+hipError_t launch_gemm_v2(const GemmRoute& r, const f16* X, const f16* W, const float* bias, f16* out, int M, int N, int K,
+                          hipStream_t stream, const GemmTileStats* stats, const GemmLnFold* fold) {
+  if (r.flag && !fold) return hipErrorInvalidValue;  // FOLD / EMIT routes come from a request with a fold
+  const dim3 grid(r.grid_x);
+  if (r.engine == GEMM_V2_STATS)
+    return stats ? launch_with_lds<gemm_v2_stats_kernel>(grid, V2_THREADS, r.lds_bytes, stream, X, W, out, M, N, K, *stats)
+                 : hipErrorInvalidValue;
+  if (r.engine == GEMM_V2_RESID) {
+    float2* po = r.flag ? fold->part_out : nullptr;
+#define SMI_V2_RESID(E, EMIT) \
+  launch_with_lds<gemm_v2_resid_kernel<E, EMIT>>(grid, V2_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, r.raster, po)
+    if (r.epi == EPI_RESID_F16) return r.flag ? SMI_V2_RESID(EPI_RESID_F16, true) : SMI_V2_RESID(EPI_RESID_F16, false);
+    return r.flag ? SMI_V2_RESID(EPI_RESID_HALF_F16, true) : SMI_V2_RESID(EPI_RESID_HALF_F16, false);
+#undef SMI_V2_RESID
   }
-  const int ntm = M / 256, ntn = N / 256;
-  const int grid = std::min(ntm * ntn, num_cus());
-  const int want_raster = tune(TUNE_G2_RASTER, 2);
-  const int raster = (want_raster && grid == 256 && ntn % 4 == 0 && ntn >= 16 && ((ntm + 7) / 8) % 8 == 0) ? want_raster : 0;
-  hipLaunchKernelGGL((gemm_v2_kernel<EPI, FOLD>), dim3(grid), dim3(V2_THREADS), V2_LDS_BYTES, stream, X, W, c2, out, M, N, K,
-                     raster, fold ? *fold : GemmLnFold{nullptr, nullptr, nullptr, 0, 0.f, 0.f, 0});
-  return hipGetLastError();
-}
-
-bool gemm_v2_stats_fits(int M, int N, int K, const GemmTileStats* stats) {
-  if (tune(TUNE_G2V2, 1) != 1 || !stats || !stats->tile_max || !stats->tile_sum || !(stats->scale > 0.f)) return false;
-  if (M % 256 || N % 256 || K % 128 || K / 32 < V2_MIN_SLICES) return false;
-  return (int64_t)(M / 256) * (N / 256) >= tune(TUNE_G2V2_MIN, 128);
-}
-
-hipError_t launch_gemm_v2_stats(const f16* X, const f16* W, f16* out, int M, int N, int K, hipStream_t stream,
-                                const GemmTileStats* stats, int grid_cap) {
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_v2_stats_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_done.set();
-  }
-  int grid = std::min((M / 256) * (N / 256), num_cus());
-  if (grid_cap > 0) grid = std::min(grid, grid_cap);
-  hipLaunchKernelGGL(gemm_v2_stats_kernel, dim3(grid), dim3(V2_THREADS), V2_LDS_BYTES, stream, X, W, out, M, N, K, *stats);
-  return hipGetLastError();
-}
-
-bool gemm_v2_fits(int epi, int M, int N, int K, const float* bias, const GemmLnFold* fold) {
-  if (tune(TUNE_G2V2, 1) == 0) return false;
-  if (M % 256 || N % 256 || K % 128 || K / 32 < V2_MIN_SLICES) return false;
-  // from half a chip of tiles up (the automatic 256x256 threshold): measured same box with the threshold at 128 instead of
-  // 512, decoder C5 3.62 -> 3.58 ms per step, C1 2.66 -> 2.63 ms (profiles/r06_experiments.txt, experiment 6)
-  if ((int64_t)(M / 256) * (N / 256) < tune(TUNE_G2V2_MIN, 128)) return false;
-  if (epi == EPI_RESID_F16 || epi == EPI_RESID_HALF_F16)  // tile-major residual stream; fold: producer side only
-    return !fold || !fold->part_in;
-  if (epi != EPI_BIAS_F16 && epi != EPI_RELU_F16 && epi != EPI_SILU_F16 && epi != EPI_GLU_F16) return false;
-  if (!bias) return false;
-  if (fold && (!fold->part_in || !fold->c1 || fold->nparts < 1 || fold->nparts > 4)) return false;
-  if (fold && (epi == EPI_SILU_F16 || epi == EPI_GLU_F16) && !fold->centered) return false;
-  return true;
-}
-
-template <int EPI, bool EMIT>
-static hipError_t launch_v2_resid(const f16* X, const f16* W, const float* bias, f16* out, int M, int N, int K,
-                                  hipStream_t stream, float2* part_out) {
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_v2_resid_kernel<EPI, EMIT>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, V2_LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_done.set();
-  }
-  const int ntm = M / 256, ntn = N / 256;
-  const int grid = std::min(ntm * ntn, num_cus());
-  const int want_raster = tune(TUNE_G2_RASTER, 2);
-  const int raster = (want_raster && grid == 256 && ntn % 4 == 0 && ntn >= 16 && ((ntm + 7) / 8) % 8 == 0) ? want_raster : 0;
-  hipLaunchKernelGGL((gemm_v2_resid_kernel<EPI, EMIT>), dim3(grid), dim3(V2_THREADS), V2_LDS_BYTES, stream, X, W, bias, out, M,
-                     N, K, raster, part_out);
-  return hipGetLastError();
-}
-
-hipError_t launch_gemm_v2(int epi, const f16* X, const f16* W, const float* bias, f16* out, int M, int N, int K,
-                          hipStream_t stream, const GemmLnFold* fold) {
-  if (epi == EPI_RESID_F16 || epi == EPI_RESID_HALF_F16) {
-    float2* po = fold ? fold->part_out : nullptr;
-    if (epi == EPI_RESID_F16)
-      return po ? launch_v2_resid<EPI_RESID_F16, true>(X, W, bias, out, M, N, K, stream, po)
-                : launch_v2_resid<EPI_RESID_F16, false>(X, W, bias, out, M, N, K, stream, nullptr);
-    return po ? launch_v2_resid<EPI_RESID_HALF_F16, true>(X, W, bias, out, M, N, K, stream, po)
-              : launch_v2_resid<EPI_RESID_HALF_F16, false>(X, W, bias, out, M, N, K, stream, nullptr);
-  }
-#define SMI_V2_CASE(E)                                                                           \
-  case E:                                                                                        \
-    return fold ? launch_v2<E, true>(X, W, bias, out, M, N, K, stream, fold)                     \
-                : launch_v2<E, false>(X, W, bias, out, M, N, K, stream, nullptr);
-  switch (epi) {
+  const GemmLnFold f = r.flag ? *fold : GemmLnFold{nullptr, nullptr, nullptr, 0, 0.f, 0.f, 0};
+#define SMI_V2_CASE(E)                                                                                                       \
+  case E:                                                                                                                    \
+    return r.flag ? launch_with_lds<gemm_v2_kernel<E, true>>(grid, V2_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, r.raster, f) \
+                  : launch_with_lds<gemm_v2_kernel<E, false>>(grid, V2_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, r.raster, f);
+  switch (r.epi) {
     SMI_V2_CASE(EPI_BIAS_F16)
     SMI_V2_CASE(EPI_RELU_F16)
     SMI_V2_CASE(EPI_SILU_F16)

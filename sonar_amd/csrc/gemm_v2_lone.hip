@@ -21,8 +21,6 @@
 //   (MI 6) three whole ones (its ring has 5 slots of 28 KiB).
 // Outputs: EPI_RELU_F16 -> the tile-major fp16 hidden activation (FFN inner); EPI_BIAS_F16 -> row-major fp16 split-K slabs
 // [kz][M][N], the bias in part 0, saturating fp16 (FFN out; consumed by sum_ln_kernel exactly as the 8-wave engine's slabs).
-#include <algorithm>
-
 #include "gemm_epi.hpp"
 #include "gemm_v2.hpp"
 #include "gemm_v2_lone_asm.inc"
@@ -331,64 +329,27 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_lone_kernel(const f16* __r
 #undef SMI_VM_CHUNK
 }
 
-// Rows per unit (128 / 160 / 192) for a launch, or 0: the tallest of the three heights that divides M, keeps every unit on a CU of
-// its own and puts MORE units on the chip than 256-row tiles would (M a multiple of 256: the tile-major image has 256-row blocks).
-static int lone_rows(int M, int N, int K, int ksplit) {
-  const int mode = tune(TUNE_DEC_M160, 1);
-  if (mode == 0) return 0;
-  if (M % 256 || N % 256 || K % 32 || ksplit < 1 || (K / 32) % ksplit) return 0;
-  const int nt = K / 32 / ksplit;
-  // units with a K loop of >= 32 slices (K >= 1024 per unit): the attention-output projection's 16-slice units measured 18-19 %
-  // SLOWER than the k-sliced 64x64 units they would replace (tools/probe_lone.py, profiles/r06r_probe_lone.log); DEC_M160=2 (tests)
-  // takes every K loop the ring can run
-  if (nt < (mode == 2 ? 8 : 32) || nt % 2) return 0;
-  const int64_t units256 = (int64_t)(M / 256) * (N / 256) * ksplit;
-  int best = 0;
-  int64_t best_units = units256;
-  for (int rows : {192, 160, 128}) {
-    if (M % rows) continue;
-    const int64_t units = (int64_t)(M / rows) * (N / 256) * ksplit;
-    // at least half the chip: below that the k-sliced 64x64 units (gemm_lone16.hpp: M = 256, a batch of 5) are faster
-    if (units <= num_cus() && units >= (mode == 2 ? 1 : num_cus() / 2) && units > best_units) {
-      best = rows;
-      best_units = units;
-    }
-  }
-  return best;
-}
+static_assert(route_lds_v2_lone(128) == VmShape<4>::LDS_BYTES && route_lds_v2_lone(160) == VmShape<5>::LDS_BYTES &&
+                  route_lds_v2_lone(192) == VmShape<6>::LDS_BYTES,
+              "gemm_route.hpp: LDS sizes of the lone units");
 
-bool gemm_v2_lone_fits(int M, int N, int K, int ksplit) { return lone_rows(M, N, K, ksplit) != 0; }
-
-template <int EPI, int MI, bool SLAB>
-static hipError_t launch_lone_unit(const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K, int ksplit,
-                                   size_t part_stride, hipStream_t stream) {
-  static DeviceOnce attr_done;
-  if (!attr_done.done()) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_v2_lone_kernel<EPI, MI, SLAB>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       VmShape<MI>::LDS_BYTES);
-    if (e != hipSuccess) return e;
-    attr_done.set();
-  }
-  const int grid = (M / VmShape<MI>::ROWS) * (N / 256) * ksplit;
-  hipLaunchKernelGGL((gemm_v2_lone_kernel<EPI, MI, SLAB>), dim3(grid), dim3(V2_THREADS), VmShape<MI>::LDS_BYTES, stream, X, W, bias, out,
-                     M, N, K, ksplit, part_stride);
-  return hipGetLastError();
-}
-
-// mode 0: row-major fp16 slabs [ksplit][M][N]; 1: tile-major fp16 relu output [M][N]; 2: tile-major fp16 bias output (ksplit 1)
-hipError_t launch_gemm_v2_lone(int mode, const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K, int ksplit,
+// GEMM_V2_LONE128 / 160 / 192 (unit = rows; gemm_route.hpp: v2_lone_rows chose them).  flag = SLAB: row-major fp16 slabs
+// [ksplit][M][N]; else the tile-major fp16 relu / bias output [M][N] (ksplit 1)
+hipError_t launch_gemm_v2_lone(const GemmRoute& r, const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K,
                                hipStream_t stream) {
-  const int rows = lone_rows(M, N, K, ksplit);
-  if (!rows || (mode && ksplit != 1)) return hipErrorInvalidValue;
-  const size_t ps = (size_t)M * N * 2;
-#define SMI_VM_LAUNCH(MIV)                                                                                                \
-  return mode == 1   ? launch_lone_unit<EPI_RELU_F16, MIV, false>(X, W, bias, out, M, N, K, 1, 0, stream)                 \
-         : mode == 2 ? launch_lone_unit<EPI_BIAS_F16, MIV, false>(X, W, bias, out, M, N, K, 1, 0, stream)                 \
-                     : launch_lone_unit<EPI_BIAS_F16, MIV, true>(X, W, bias, out, M, N, K, ksplit, ps, stream)
-  if (rows == 128) SMI_VM_LAUNCH(4);
-  if (rows == 160) SMI_VM_LAUNCH(5);
+  const dim3 grid(r.grid_x);
+  const size_t ps = (size_t)r.part_stride;
+#define SMI_VM_UNIT(E, MIV, SLAB) \
+  launch_with_lds<gemm_v2_lone_kernel<E, MIV, SLAB>>(grid, V2_THREADS, r.lds_bytes, stream, X, W, bias, out, M, N, K, r.ksplit, ps)
+#define SMI_VM_LAUNCH(MIV)                                                \
+  return r.flag                  ? SMI_VM_UNIT(EPI_BIAS_F16, MIV, true)   \
+         : r.epi == EPI_RELU_F16 ? SMI_VM_UNIT(EPI_RELU_F16, MIV, false)  \
+                                 : SMI_VM_UNIT(EPI_BIAS_F16, MIV, false)
+  if (r.unit == 128) SMI_VM_LAUNCH(4);
+  if (r.unit == 160) SMI_VM_LAUNCH(5);
   SMI_VM_LAUNCH(6);
 #undef SMI_VM_LAUNCH
+#undef SMI_VM_UNIT
 }
 
 }  // namespace smi

@@ -6,6 +6,7 @@
 
 #include <atomic>
 
+#include "gemm_route.hpp"
 #include "tuning.hpp"
 
 namespace smi {
@@ -26,15 +27,19 @@ struct DeviceOnce {
 
 typedef _Float16 f16;
 
-enum GemmEpilogue {
-  EPI_BIAS_F16 = 0, EPI_RELU_F16 = 1, EPI_RESID_F32 = 2, EPI_STORE_F32 = 3,
-  EPI_RESID_HALF_F32 = 4, EPI_SILU_F16 = 5, EPI_GLU_F16 = 6, EPI_TANH_F16 = 7, EPI_RESID_F16 = 8,
-  EPI_RESID_HALF_F16 = 9
-};
-
-// layout flags OR-ed into epi_sel (tile-major layout: common.hpp tm_offset)
-constexpr int GEMM_IN_TM = 1 << 12;   // X and W are tile-major (M, N % 256 == 0)
-constexpr int GEMM_OUT_TM = 1 << 13;  // fp16 output is tile-major with K = N (needs GEMM_IN_TM, ldo == N)
+// Launch `Kernel` with `lds` bytes of dynamic LDS: the MaxDynamicSharedMemorySize attribute is set once per device and kernel
+// instantiation (one DeviceOnce per instantiation of this template), then the launch; returns hipGetLastError().
+template <auto Kernel, typename... Args>
+hipError_t launch_with_lds(dim3 grid, int threads, int lds, hipStream_t stream, Args... args) {
+  static DeviceOnce attr_done;
+  if (!attr_done.done()) {
+    hipError_t e = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    if (e != hipSuccess) return e;
+    attr_done.set();
+  }
+  hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds, stream, args...);
+  return hipGetLastError();
+}
 
 // Optional per-(row, 256-column tile) softmax statistics of an EPI_STORE_F32 GEMM on the 256x256
 // engine (the decoder's logits GEMM): tile_max[N/256][M] = max_n v, tile_sum[N/256][M] =
@@ -69,37 +74,47 @@ struct GemmLnFold {
   int centered;
 };
 
-// C = X[M,K] * W[N,K]^T (+bias, epilogue).  M%128==0, N%128==0, K%64==0.
+// C = X[M,K] * W[N,K]^T (+bias, epilogue).  M%128==0, N%128==0, K%64==0.  epi_sel = epilogue | (engine << 8) | layout flags:
+// engine 0 auto, 1 force the 128x128 family, 2 force 256x256.  Which engine runs is decided by gemm_route (gemm_route.hpp);
+// hipErrorNotSupported, before any HIP call: no engine takes the request.
 hipError_t launch_gemm_tn(int epi_sel, const f16* X, const f16* W, const float* bias, void* out, int M,
                           int N, int K, int ldo, hipStream_t stream, const GemmTileStats* stats = nullptr,
                           const GemmLnFold* fold = nullptr);
-
-// The 4-wave 256x256 engine (gemm_v2.hip): tile-major fp16 in / out, epi in {bias, relu, silu}, optional LayerNorm-fold
-// consumer.  gemm_v2_fits: the launch qualifies (shape, switches); launch_gemm_tn routes to it by itself.
-bool gemm_v2_fits(int epi, int M, int N, int K, const float* bias, const GemmLnFold* fold);
-hipError_t launch_gemm_v2(int epi, const f16* X, const f16* W, const float* bias, f16* out, int M, int N, int K,
-                          hipStream_t stream, const GemmLnFold* fold);
-
-// ... and the decoder's logits projection with the fused softmax statistics (fp16 tile-major logits, no bias, stats->scale > 0)
-bool gemm_v2_stats_fits(int M, int N, int K, const GemmTileStats* stats);
-hipError_t launch_gemm_v2_stats(const f16* X, const f16* W, f16* out, int M, int N, int K, hipStream_t stream,
-                                const GemmTileStats* stats, int grid_cap);
-
-// 160x256 lone units of the 4-wave engine (gemm_v2_lone.hip): M % 1280 == 0 rows, tile-major operands, every unit on its own CU.
-// mode 1 / 2: out = tile-major fp16 relu(X W^T + bias) / X W^T + bias (ksplit 1); mode 0: out = row-major fp16 split-K slabs
-// [ksplit][M][N].  (The 160x256 name is historic: units are 128 / 160 / 192 rows.)
-bool gemm_v2_lone_fits(int M, int N, int K, int ksplit);
-hipError_t launch_gemm_v2_lone(int mode, const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K, int ksplit,
-                               hipStream_t stream);
-
 // in_tm: X and W tile-major (common.hpp; M, N % 256 == 0)
 // slab_f16: fp16 slabs [ksplit][M][N] instead of fp32 ones (the consumers take the same flag)
 hipError_t launch_gemm_tn_splitk(const f16* X, const f16* W, const float* bias, void* parts, int M,
                                  int N, int K, int ksplit, hipStream_t stream, int in_tm = 0, int slab_f16 = 0);
-// cap the persistent grid of the calling thread's next 256x256-engine launches (0 = no cap)
+
+// the request of a launch_gemm_tn call, for gemm_route
+inline GemmRequest gemm_request(int epi_sel, int M, int N, int K, int ldo, bool has_bias, const GemmTileStats* stats,
+                                const GemmLnFold* fold) {
+  GemmRequest q{};
+  q.epi = epi_sel & 0xff, q.sel = (epi_sel >> 8) & 0xf;
+  q.in_tm = epi_sel & GEMM_IN_TM, q.out_tm = epi_sel & GEMM_OUT_TM;
+  q.M = M, q.N = N, q.K = K, q.ldo = ldo, q.has_bias = has_bias;
+  if (fold) {
+    q.fold = fold->part_in ? (fold->centered ? FOLD_CONSUMER_CENTRED : FOLD_CONSUMER_EXACT)
+                           : (fold->part_out ? FOLD_PRODUCER_SUMS : FOLD_PRODUCER);
+    q.fold_nparts = fold->nparts, q.fold_has_c1 = fold->c1 != nullptr;
+  }
+  if (stats) q.stats = stats->tile_max && stats->tile_sum && stats->scale > 0.f ? STATS_POSITIVE : STATS_OTHER;
+  q.ksplit = 1;
+  return q;
+}
+// what gemm_route reads from the outside: the routing switches, the CU count (num_cus <= 0: the current device's) and the calling
+// thread's grid cap (gemm.hip; the only reader of these for routing)
+GemmEnv gemm_env(int num_cus = 0);
+// cap the persistent grid of the calling thread's next 8-wave-engine and logits launches (0 = no cap)
 void set_gemm_grid_cap(int workgroups);
-// number of K parts for a decode-time split-K projection (gemm.hip): every unit on its own CU, <= max_parts
-int gemm_splitk_parts(int M, int N, int K, int max_parts);
+
+// One launcher per engine file: the route's template coordinates -> the kernel instantiation, launched with the route's grid and LDS
+// size.  launch_gemm_tn / launch_gemm_tn_splitk dispatch to them; nothing else calls them.
+// gemm_v2.hip: the 4-wave 256x256 engine (GEMM_V2, GEMM_V2_RESID, GEMM_V2_STATS)
+hipError_t launch_gemm_v2(const GemmRoute& r, const f16* X, const f16* W, const float* bias, f16* out, int M, int N, int K,
+                          hipStream_t stream, const GemmTileStats* stats, const GemmLnFold* fold);
+// gemm_v2_lone.hip: its 128 / 160 / 192-row lone units (GEMM_V2_LONE*)
+hipError_t launch_gemm_v2_lone(const GemmRoute& r, const f16* X, const f16* W, const float* bias, void* out, int M, int N, int K,
+                               hipStream_t stream);
 
 // x[row(n,p), :] = E[ids[n*S+p], :] * scale + PE[p + pos_offset, :]   (packed rows)
 // x_f16: the residual stream x is fp16 (SMI_ENC_FP16_RESIDUAL) instead of fp32

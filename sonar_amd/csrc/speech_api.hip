@@ -536,9 +536,11 @@ int smi_speech_encoder_forward(smi_speech_encoder* E, const float* fbank, const 
                              &produce));
       const GemmLnFold cg = consume(L.c1_pw1);
       // tile-major GLU output where the 4-wave engine takes the launch (its GLU read-out; otherwise row-major, 8-wave engine)
-      glu_tm = gemm_v2_fits(EPI_GLU_F16, R, 2 * d, d, L.c2_pw1.as<float>(), &cg);
-      HIP_TRY(launch_gemm_tn(EPI_GLU_F16 | (2 << 8) | GEMM_IN_TM | (glu_tm ? GEMM_OUT_TM : 0), (const f16*)x, L.wf_pw1.as<f16>(),
-                             L.c2_pw1.as<float>(), E->glu.p, R, 2 * d, d, d, stream, nullptr, &cg));
+      const int glu_sel = EPI_GLU_F16 | (2 << 8) | GEMM_IN_TM;
+      glu_tm = gemm_route(gemm_request(glu_sel | GEMM_OUT_TM, R, 2 * d, d, d, L.c2_pw1.p != nullptr, nullptr, &cg), gemm_env()).engine ==
+               GEMM_V2;
+      HIP_TRY(launch_gemm_tn(glu_sel | (glu_tm ? GEMM_OUT_TM : 0), (const f16*)x, L.wf_pw1.as<f16>(), L.c2_pw1.as<float>(), E->glu.p,
+                             R, 2 * d, d, d, stream, nullptr, &cg));
     } else {
       HIP_TRY(launch_gemm_tn(epi_res | mid_in, ctx, L.w_o.as<f16>(), L.b_o.as<float>(), x, R, d, d, d, stream));
       HIP_TRY(launch_layernorm(x, L.conv_ln_w.as<float>(), L.conv_ln_b.as<float>(), c.ln_eps, h, R, d, stream, tmf, x16));

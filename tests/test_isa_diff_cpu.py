@@ -44,6 +44,16 @@ def test_labels_and_cuid_do_not_count(tmp_path):
     assert out[0].startswith("base 2 kernels, tree 2; identical 2, commuted 0, differing 0, removed 0, added 0")
 
 
+def test_label_width_does_not_move_a_diff(tmp_path):
+    # hipcc pads a label line's comment to a fixed column: a function that becomes number 10 instead of 9 (another instantiation
+    # order) has one space less in front of it
+    base = unit([kernel("k_a", BODY_A, 9)], "0")
+    tree = unit([kernel("k_a", BODY_A, 10).replace(".LBB10_1:                                ;", ".LBB10_1:                               ;")], "0")
+    assert base.replace("BB9_", "BB10_") != tree
+    rc, out = run(tmp_path, base, tree)
+    assert rc == 0 and "IDENTICAL k_a" in out
+
+
 def test_changed_instruction_under_commented_label_is_a_diff(tmp_path):
     # the regression: label lines carry `; @name`, ONE instruction of ONE body differs, the descriptors are equal
     base = unit([kernel("k_a", BODY_A, 0), kernel("k_b", BODY_B, 1)], "0123abcd")

@@ -5,8 +5,8 @@
     python tools/isa_diff.py base/X.s tree/X.s [OLD_NAME=NEW_NAME ...]
 
 Compares function bodies (from the `name:` label line, with or without its `; @name` comment, to the next `.Lfunc_endN:`)
-and .amdhsa_kernel descriptors; the per-file __hip_cuid_<hash> symbol is masked and local labels are renumbered per
-function.  OLD=NEW pairs a kernel of the base with its new mangled name (a template parameter that went).
+and .amdhsa_kernel descriptors; the per-file __hip_cuid_<hash> symbol is masked, local labels are renumbered per
+function and the padding in front of a label line's comment is ignored.  OLD=NEW pairs a kernel of the base with its new mangled name (a template parameter that went).
 Every kernel of the base is IDENTICAL, COMMUTED (equal once the two source operands of every v_add/mul/max/min_f32_e32
 line are sorted -- IEEE add, mul, max and min commute; nothing else is normalised), DIFF or REMOVED; kernels only in the
 tree are ADDED.  Exit status 1 if a kernel is DIFF or ADDED.
@@ -38,7 +38,8 @@ def kernels(path, rename=()):
 def norm(s):  # local labels are numbered per file: renumber per function (comments name blocks without the .L: "Header=BB3_5")
     seen = {}
     s = re.sub(r"(?<![.\w])BB\d+_\d+", lambda m: ".L" + m.group(0), s)
-    return re.sub(r"\.L\w+", lambda m: seen.setdefault(m.group(0), f".L{len(seen)}"), s)
+    s = re.sub(r"\.L\w+", lambda m: seen.setdefault(m.group(0), f".L{len(seen)}"), s)
+    return re.sub(r"^(\.L\d+:)[ \t]+;", r"\1 ;", s, flags=re.M)  # the comment column moves with the label's width (.LBB9_1 / .LBB10_1)
 
 
 def commute(s):
