@@ -956,6 +956,31 @@ int smi_cast(const void* src, int32_t src_dtype, void* dst, int32_t dst_dtype, i
 /* out = f16(LN(x) * w + b); tile_major != 0: out in the tile-major layout ((rows+255)/256*256 rows allocated) */
 int smi_layernorm(const float* x, const float* w, const float* b, float eps, void* out_f16,
                   int32_t rows, int32_t d, int32_t tile_major, void* stream);
+/* The LayerNorm fold (exported for tests): an fp16 model's encoders launch no LayerNorm in front of a projection.  With
+ * h = LN(x) = (x - mean) * rstd * g + b,   h . W^T + bias = rstd * (x . Wf^T - mean * c1) + c2,   Wf = W (.) g,
+ * c1[n] = sum_k Wf[n][k], c2[n] = sum_k b[k] W[n][k] + bias[n]: the projection multiplies the tile-major fp16 residual stream x
+ * ITSELF by the pre-scaled weights and applies the rows' statistics in its epilogue; the residual GEMM that wrote x leaves
+ * them as per-row partial sums.
+ * smi_ln_fold_prep: w f16 [n][k], g / b fp32 [k], bias fp32 [n] or NULL, all row-major -> wf f16 [n][k], c1 / c2 fp32 [n].
+ * centered == 0: wf = f16(f32(w * g)), the fp32 product rounded to fp16, c1 = the row sums of the ROUNDED wf.  centered != 0: wf = f16(w * g - rowmean(w * g)), which
+ * moves the mean term into the product (the epilogue is rstd * acc + c2); c1 = the row sums of wf, the rounding residue. */
+int smi_ln_fold_prep(const void* w_f16, const float* g, const float* b, const float* bias_or_null, void* wf_f16, float* c1,
+                     float* c2, int32_t n, int32_t k, int32_t centered, void* stream);
+/* part[0][r] = (sum, sum of squares) of row r < m of the tile-major f16 stream x [rows % 256 == 0][d] (d % 32 == 0),
+ * part[1 .. nparts-1][r] = (0, 0); part: [nparts][m] pairs of floats.  The statistics of a stream no GEMM has produced. */
+int smi_row_stats_tm(const void* x_f16_tm, float* part, int32_t m, int32_t d, int32_t nparts, void* stream);
+/* smi_gemm_tn with a LayerNorm fold (epi, operands, shapes and ldo as there; m, n % 256 == 0, x and w tile-major).
+ * PRODUCER (part_out given): epilogues 8 / 9 on a tile-major stream; part_out[n/256][m] pairs <- (sum, sum of squares) of the
+ * ROUNDED new values of each row over the 256 columns of each tile.  CONSUMER (part_in given): x = the stream, w = wf,
+ * bias = c2, part_in[nparts][m] pairs whose sum over the parts is the row's (sum, sum of squares), 1 <= nparts <= 4, c1 given;
+ * out = act(rstd * (x . wf^T - mean * c1) + c2), or act(rstd * x . wf^T + c2) with centered != 0, mean = sum / k,
+ * rstd = 1 / sqrt(sumsq / k - mean^2 + eps).  Tile-major outputs: epilogues 0, 1 (both variants), 5 and -- on the 4-wave engine --
+ * 6 (centred only); row-major outputs: 0 and 6, centred only.  part_out and part_in both NULL: the plain launch of the
+ * residual epilogue; both given: SMI_ERR_INVALID_ARG.  What no kernel computes is refused with SMI_ERR_UNSUPPORTED before
+ * anything is launched (smi_gemm_route answers the same question). */
+int smi_gemm_tn_ln_fold(int32_t epi, const void* x_f16_tm, const void* w_f16_tm, const float* bias, void* out, int32_t m,
+                        int32_t n, int32_t k, int32_t ldo, float* part_out, const float* part_in, const float* c1,
+                        int32_t nparts, float eps, int32_t centered, void* stream);
 /* qkv: f16 [t, 3*d] packed rows; cu_seqlens: device int32 [n+1]; ctx: f16 [t, d];
  * tile_major bit 0: ctx written tile-major, bit 1: qkv read tile-major (k = 3*d)
  * ((t+255)/256*256 rows allocated for a tile-major buffer) */

@@ -369,6 +369,9 @@ SYMBOLS = {
     "smi_gemm_tn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "smi_gemm_tn_tile_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "smi_gemm_tn_splitk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "smi_gemm_tn_ln_fold": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _i32, _vp]),
+    "smi_ln_fold_prep": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "smi_row_stats_tm": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
     "smi_gemm_route": (C.c_int, [_i32] * 12 + [C.POINTER(GemmRouteInfo)]),
     "smi_gemm_splitk_parts": (C.c_int, [_i32] * 5),
     "smi_mlp_head_create": (C.c_int, [C.POINTER(smi_mlp_head_config), C.POINTER(smi_mlp_head_layer), C.POINTER(_vp)]),

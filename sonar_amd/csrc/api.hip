@@ -792,8 +792,9 @@ int smi_pack_tile_major(const void* src, void* dst, int32_t rows, int32_t k, int
   return SMI_OK;
 }
 
-int smi_gemm_tn(int32_t epi, const void* x, const void* w, const float* bias, void* out, int32_t m,
-                int32_t n, int32_t k, int32_t ldo, void* stream) {
+// the argument checks smi_gemm_tn and smi_gemm_tn_ln_fold share (SMI_OK: the request may go to the router)
+static int gemm_tn_check_args(int32_t epi, const void* x, const void* w, const void* out, int32_t m, int32_t n, int32_t k,
+                              int32_t ldo) {
   if (!x || !w || !out) return fail(SMI_ERR_INVALID_ARG, "null argument");
   const int e = epi & 0xff, sel = (epi >> 8) & 0xf;
   const bool in_tm = epi & GEMM_IN_TM, out_tm = epi & GEMM_OUT_TM;
@@ -805,6 +806,12 @@ int smi_gemm_tn(int32_t epi, const void* x, const void* w, const float* bias, vo
   if (out_tm && (!in_tm || ldo != (e == 6 ? n / 2 : n)))
     return fail(SMI_ERR_UNSUPPORTED, "tile-major output needs tile-major inputs and ldo == n (n / 2 for the GLU epilogue)");
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  return SMI_OK;
+}
+
+int smi_gemm_tn(int32_t epi, const void* x, const void* w, const float* bias, void* out, int32_t m,
+                int32_t n, int32_t k, int32_t ldo, void* stream) {
+  if (const int rc = gemm_tn_check_args(epi, x, w, out, m, n, k, ldo)) return rc;
   {
     const hipError_t he = launch_gemm_tn(epi, (const f16*)x, (const f16*)w, bias, out, m, n, k, ldo, (hipStream_t)stream);
     // combinations only one engine implements (the GLU epilogue with a tile-major output: the 4-wave engine, from its tile
@@ -813,6 +820,40 @@ int smi_gemm_tn(int32_t epi, const void* x, const void* w, const float* bias, vo
       return fail(SMI_ERR_UNSUPPORTED, "gemm m=%d n=%d k=%d epi=%d: no engine takes this combination", m, n, k, epi);
     HIP_TRY(he);
   }
+  return SMI_OK;
+}
+
+// LayerNorm fold (kernels.hpp: GemmLnFold) as building blocks: the weight preparation, the first statistics of a stream, and a
+// GEMM launch that carries a fold -- what the encoders' forward passes do, one call at a time
+int smi_ln_fold_prep(const void* w, const float* g, const float* b, const float* bias, void* wf, float* c1, float* c2, int32_t n,
+                     int32_t k, int32_t centered, void* stream) {
+  if (!w || !g || !b || !wf || !c1 || !c2 || w == wf || n <= 0 || k <= 0) return fail(SMI_ERR_INVALID_ARG, "bad argument");
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_ln_fold_prep((const f16*)w, g, b, bias, (f16*)wf, c1, c2, n, k, centered != 0, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_row_stats_tm(const void* x, float* part, int32_t m, int32_t d, int32_t nparts, void* stream) {
+  if (!x || !part || m <= 0) return fail(SMI_ERR_INVALID_ARG, "bad argument");
+  if (d <= 0 || d % 32 || nparts < 1 || nparts > 64)
+    return fail(SMI_ERR_UNSUPPORTED, "row statistics need d %% 32 == 0 and 1 <= nparts <= 64 (d=%d nparts=%d)", d, nparts);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_row_stats_tm((const f16*)x, (float2*)part, m, d, nparts, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_gemm_tn_ln_fold(int32_t epi, const void* x, const void* w, const float* bias, void* out, int32_t m, int32_t n, int32_t k,
+                        int32_t ldo, float* part_out, const float* part_in, const float* c1, int32_t nparts, float eps,
+                        int32_t centered, void* stream) {
+  if (part_out && part_in) return fail(SMI_ERR_INVALID_ARG, "a fold is a producer (part_out) or a consumer (part_in), not both");
+  if (const int rc = gemm_tn_check_args(epi, x, w, out, m, n, k, ldo)) return rc;
+  const GemmLnFold fold{(float2*)part_out, (const float2*)part_in, c1, nparts, 1.0f / k, eps, centered != 0};
+  const hipError_t he = launch_gemm_tn(epi, (const f16*)x, (const f16*)w, bias, out, m, n, k, ldo, (hipStream_t)stream, nullptr, &fold);
+  // the router refuses what no fold kernel computes (gemm_route.hpp): nothing has been launched
+  if (he == hipErrorNotSupported)
+    return fail(SMI_ERR_UNSUPPORTED, "gemm m=%d n=%d k=%d epi=%d nparts=%d centered=%d: no engine takes this LayerNorm fold", m, n, k,
+                epi, nparts, centered);
+  HIP_TRY(he);
   return SMI_OK;
 }
 

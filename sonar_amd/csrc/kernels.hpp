@@ -148,7 +148,7 @@ hipError_t launch_f32_to_f16(const float* src, f16* dst, size_t n, hipStream_t s
 // element-wise cast, dtypes 0 = fp32, 1 = fp16, 2 = bf16 (smi_dtype)
 hipError_t launch_cast(const void* src, int src_dtype, void* dst, int dst_dtype, size_t n, hipStream_t stream);
 // x[i] += sum_z parts[z * part_elems + i], i < n (n % 8 == 0); x fp16 or fp32 (rowops.hip)
-// LayerNorm-fold helpers (rowops.hip): Wf = f16(W (.) g), c1 = row sums of Wf, c2 = W . b + bias  (W [N][K] row-major)
+// LayerNorm-fold helpers (rowops.hip): Wf = f16(f32(W (.) g)), c1 = row sums of Wf, c2 = W . b + bias  (W [N][K] row-major)
 // centered: Wf = f16(W (.) g - c1 / K) (row-centred), c1 = the rounding residue sum_k Wf[n][k]
 hipError_t launch_ln_fold_prep(const f16* W, const float* g, const float* b, const float* bias, f16* Wf, float* c1,
                                float* c2, int N, int K, int centered, hipStream_t stream);

@@ -704,7 +704,7 @@ hipError_t launch_fold_residual(void* x, int x_f16, const void* parts, int npart
 }
 
 // ------------------------------------------------------------- LayerNorm folded into the GEMMs (kernels.hpp: GemmLnFold)
-// One wave per weight row n: Wf[n][k] = f16(W[n][k] * g[k]); c1[n] = sum_k float(Wf[n][k]) -- the ROUNDED values, because
+// One wave per weight row n: Wf[n][k] = f16(f32(W[n][k] * g[k])); c1[n] = sum_k float(Wf[n][k]) -- the ROUNDED values, because
 // that is what the GEMM multiplies --; c2[n] = sum_k b[k] * W[n][k] + bias[n].
 __global__ __launch_bounds__(256) void ln_fold_prep_kernel(const f16* __restrict__ W, const float* __restrict__ g,
                                                            const float* __restrict__ b, const float* __restrict__ bias,
@@ -719,13 +719,30 @@ __global__ __launch_bounds__(256) void ln_fold_prep_kernel(const f16* __restrict
     shift = wave_sum(t) / K;
   }
   float s1 = 0.f, s2 = 0.f;
-  for (int k = lane; k < K; k += 64) {
-    const float w = (float)W[(size_t)n * K + k];
-    const f16 wf = (f16)(w * g[k] - shift);
-    Wf[(size_t)n * K + k] = wf;
-    s1 += (float)wf;
-    s2 += b[k] * w;
-  }
+  // Uncentred: the fp32 product, rounded to fp32 and then to fp16 -- (W.float() * g).half() bit for bit.  Written as
+  // `w * g[k] - shift` with shift = 0, hipcc contracted it with the conversion into ONE rounding (v_fma_mixlo_f16), which differs
+  // from that statement by an fp16 ulp in ~1e-4 of the entries.  The centred weights keep the fused form; one loop per variant,
+  // because under a select the compiler moves the conversion behind it and un-fuses both.
+  auto rows = [&](auto centred_tag) {
+    for (int k = lane; k < K; k += 64) {
+      const float w = (float)W[(size_t)n * K + k];
+      f16 wf;
+      if constexpr (decltype(centred_tag)::value)
+        wf = (f16)(w * g[k] - shift);
+      else {
+        float p = w * g[k];
+        asm volatile("" : "+v"(p));  // the product exists as an fp32 value: no fused multiply-and-convert
+        wf = (f16)p;
+      }
+      Wf[(size_t)n * K + k] = wf;
+      s1 += (float)wf;
+      s2 += b[k] * w;
+    }
+  };
+  if (centered)
+    rows(std::true_type{});
+  else
+    rows(std::false_type{});
   s1 = wave_sum(s1);
   s2 = wave_sum(s2);
   if (lane == 0) {

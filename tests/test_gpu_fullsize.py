@@ -22,6 +22,7 @@ def _cos_err(a, b):
 @pytest.mark.parametrize("fp16_residual", [False, True])
 def test_encoder_full_width_vs_oracle(fp16_residual):
     from oracle import text_encoder as O
+    from sonar_amd import _lib
     from sonar_amd.text_encoder import (PaddingMask, SequenceBatch, SonarTextEncoderConfig,
                                         SonarTextTransformerEncoderModel, VocabularyInfo)
 
@@ -33,19 +34,31 @@ def test_encoder_full_width_vs_oracle(fp16_residual):
     assert int(lens.sum()) >= 9216   # >= 36 row tiles: all four projections take the 256x256 engine
     torch.set_num_threads(min(32, torch.get_num_threads()))
     _, ref = O.text_encoder_forward(params, ocfg, ids, lens)
-    model = SonarTextTransformerEncoderModel(cfg, params, device="cuda:0", dtype=torch.float32,
-                                             fp16_residual=fp16_residual)
-    emb = model(SequenceBatch(ids.cuda(), PaddingMask(lens, ids.shape[1]))).sentence_embeddings
-    assert torch.isfinite(emb).all()
-    rel = (emb.float().cpu() - ref).abs().max().item() / ref.abs().max().item()
-    print(f"fp16_residual={fp16_residual}: max (1 - cos) vs oracle = {_cos_err(emb, ref):.2e}, max |diff| / max |ref| = {rel:.2e}")
-    assert _cos_err(emb, ref) <= 1e-3          # north_star tolerance
-    # measured (r02): 1 - cos <= 3e-5; hold the stack to ~10x that and to an elementwise bound, so that a
-    # regression inside the north_star tolerance is still caught
-    assert _cos_err(emb, ref) <= 3e-4 and rel <= 3e-2
-    # a small slice of the same sentences goes through the 128x128 engine: same vectors
-    sub = model(SequenceBatch(ids[:3].cuda(), PaddingMask(lens[:3], ids.shape[1]))).sentence_embeddings
-    assert _cos_err(sub, emb[:3]) <= 2e-5
+    # fp16 stream: the LayerNorm fold replaces the LayerNorm launches.  ENC_LNFOLD (read when the engine is created) = 0 keeps
+    # the launches, 1 folds with the exact mean term, 2 (the default) with row-centred weights: all three against ONE oracle run
+    embs = {}
+    for lnfold in ((0, 1, 2) if fp16_residual else (None,)):
+        with _lib.tuning(**({} if lnfold is None else {"ENC_LNFOLD": lnfold})):
+            model = SonarTextTransformerEncoderModel(cfg, params, device="cuda:0", dtype=torch.float32,
+                                                     fp16_residual=fp16_residual)
+            emb = model(SequenceBatch(ids.cuda(), PaddingMask(lens, ids.shape[1]))).sentence_embeddings
+            # a small slice of the same sentences goes through the 128x128 engine: same vectors
+            sub = model(SequenceBatch(ids[:3].cuda(), PaddingMask(lens[:3], ids.shape[1]))).sentence_embeddings
+        assert torch.isfinite(emb).all()
+        rel = (emb.float().cpu() - ref).abs().max().item() / ref.abs().max().item()
+        print(f"fp16_residual={fp16_residual} ENC_LNFOLD={lnfold}: max (1 - cos) vs oracle = {_cos_err(emb, ref):.2e}, "
+              f"max |diff| / max |ref| = {rel:.2e}")
+        assert _cos_err(emb, ref) <= 1e-3          # north_star tolerance
+        # measured (r02): 1 - cos <= 3e-5; hold the stack to ~10x that and to an elementwise bound, so that a
+        # regression inside the north_star tolerance is still caught
+        assert _cos_err(emb, ref) <= 3e-4 and rel <= 3e-2, lnfold
+        assert _cos_err(sub, emb[:3]) <= 2e-5, lnfold
+        embs[lnfold] = emb
+    if fp16_residual:
+        print("1 - cos vs oracle, ENC_LNFOLD = 0 | 1 | 2: " + " | ".join(f"{_cos_err(embs[v], ref):.2e}" for v in (0, 1, 2)))
+        # the switch reached the kernels: were the three bit-identical, the batch would not have taken the fold path and the
+        # loop would have compared one path with itself
+        assert not (torch.equal(embs[0], embs[1]) and torch.equal(embs[1], embs[2]))
 
 
 @pytest.fixture(scope="module")
