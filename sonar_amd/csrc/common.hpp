@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gemm_walk.hpp"
+
 namespace smi {
 
 typedef _Float16 f16;
@@ -140,15 +142,6 @@ __device__ __forceinline__ void prefetch_range(const void* p, size_t bytes, int 
     for (int j = 0; j < PF_DEPTH; ++j) acc ^= v[j][0] ^ v[j][1] ^ v[j][2] ^ v[j][3];
   }
   if (acc == 0x9e3779b9u && sink) *sink = acc;
-}
-
-// XCD-aware block id remap (bijective for any grid size): hardware deals
-// block b to XCD b%8; give every XCD one contiguous range of logical ids so
-// neighbouring tiles share that XCD's private L2.
-__device__ __forceinline__ int xcd_remap(int b, int nb) {
-  const int q = nb >> 3, r = nb & 7;
-  const int xcd = b & 7, idx = b >> 3;
-  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
 }
 
 // TILE-MAJOR operand layout of a K-major fp16 matrix A[R][K] (R % 256 == 0, K % 32 == 0): block

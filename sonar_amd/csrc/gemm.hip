@@ -401,33 +401,13 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
 
   // unit id = kz * (ntm * ntn) + output tile: neighbouring ids share operand panels of one K part
   const int nout = ntm * ntn;
-  // raster 0: grouped 8(m) x ntn super-tiles in id order (gemm_tile256.hpp).
-  // raster 2 (full 256-workgroup grids, N >= 4 n-quads): XCD c OWNS the m-groups c, c + 8, ... (8 X panels each) and
-  // walks the n-quads of a group in consecutive rounds, in an order rotated by c.  With raster 0 and N = 8192 the
-  // 8 XCDs work on the SAME 8 X panels in every round (each on its own 4 W panels): every X panel is pulled across
-  // the fabric by all 8 XCDs at the same moment (PMC: 3.2 GB fetched per launch for 0.29 GB of operands).  With
-  // XCD-owned m-groups an X panel is fetched by one XCD only, and the rotation keeps the XCDs on different W panels.
-  // Measured (profiles/r02_experiments.txt, experiments 6-7): FFN inner 1.82-1.87 -> 1.75-1.76 ms
-  // (1175-1210 -> 1249-1260 TFLOP/s), 44.0 -> 41.9 ms per C2 step; no effect at N = 3072 (X is shared by 3 XCDs
-  // there), so it is used from 16 n tiles up.  (raster 1 = the same without the rotation.)
-  // Virtual ids t = 256 q + 32 c + j (round q, XCD c, slot j); the last m-group may be partial: its surplus slots,
-  // and XCDs that own one group fewer, skip the id.
+  // the walk (gemm_walk.hpp): raster 0 in id order over all K parts, rasters 1 / 2 XCD-owned m-groups (one K part)
   const int nq = ntn / 4;
-  const int nvirt = raster ? ((ntm + 63) / 64) * nq * 256 : ntiles;
-  auto coords = [&](int t, int& tm_, int& tn_) -> bool {
-    if (raster == 0) {
-      g2_tile_coords_of(t % nout, ntm, ntn, tm_, tn_);
-      return true;
-    }
-    const int q = t / 256, c = (t % 256) / 32, j = t % 32;
-    tm_ = (c + 8 * (q / nq)) * 8 + j % 8;
-    tn_ = ((q + (raster == 2 ? c : 0)) % nq) * 4 + j / 8;
-    return tm_ < ntm;
-  };
+  const int nvirt = raster ? walk_nvirt(ntm, nq) : ntiles;
   int tile_m = 0, tile_n = 0;
   // first valid id of this workgroup at or after t (stride = grid size)
   auto seek = [&](int t) {
-    while (t < nvirt && !coords(t, tile_m, tile_n)) t += gridDim.x;
+    while (t < nvirt && !walk_coords_parts(t, raster, ntm, ntn, nq, nout, tile_m, tile_n)) t += gridDim.x;
     return t;
   };
   int tile = seek(xcd_remap(blockIdx.x, gridDim.x));
@@ -512,11 +492,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
     auto fold_affine_st = [&](GemmTile256Acc& a) {
       float row_rs[2];
 #pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const float mean = row_sq[u].x * fold.inv_k;
-        const float var = fmaxf(row_sq[u].y * fold.inv_k - mean * mean, 0.f);
-        row_rs[u] = __builtin_amdgcn_rsqf(var + fold.eps);
-      }
+      for (int u = 0; u < 2; ++u) row_rs[u] = fold_row_affine(row_sq[u].x, row_sq[u].y, fold.inv_k, fold.eps).x;
       float rsall[8];
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi)
@@ -528,19 +504,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
         for (int r = 0; r < 4; ++r)
           c2v[r] = __int_as_float(__builtin_amdgcn_ds_bpermute((ni * 16 + 4 * kg + r) * 4, __float_as_int(col_c2)));
 #pragma unroll
-        for (int mi = 0; mi < 8; ++mi) {
-          const f32x2 rs2 = {rsall[mi], rsall[mi]};
-          f32x4 v = a.v[ni][mi];
-#pragma unroll
-          for (int hp2 = 0; hp2 < 2; ++hp2) {
-            const f32x2 c2p = {c2v[2 * hp2], c2v[2 * hp2 + 1]};
-            f32x2 vp = {v[2 * hp2], v[2 * hp2 + 1]};
-            vp = __builtin_elementwise_fma(rs2, vp, c2p);
-            v[2 * hp2] = vp[0];
-            v[2 * hp2 + 1] = vp[1];
-          }
-          a.v[ni][mi] = v;
-        }
+        for (int mi = 0; mi < 8; ++mi) a.v[ni][mi] = fold_apply<2>(a.v[ni][mi], c2v, c2v, rsall[mi], 0.f);
       }
     };
     (void)fold_affine_st;
@@ -569,7 +533,6 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
         const int sw = tm_swz(l15);
         f16* lane0 = (f16*)out + ((size_t)(m0 >> 8) * (N >> 5) + (n0 >> 5) + wc * 2) * TM_BLOCK +
                      (wr * 128 + l15) * 32 + ((cidx ^ sw) << 3);
-        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 #pragma unroll
         for (int mi = 0; mi < 8; ++mi) {
           uint32_t h[4][2];
@@ -581,9 +544,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
           }
 #pragma unroll
           for (int j = 0; j < 2; ++j) {  // the store of store_tile (MODE 0) below
-            const auto s0 = __builtin_amdgcn_permlane16_swap(h[2 * j][0], h[2 * j + 1][0], false, false);
-            const auto s1 = __builtin_amdgcn_permlane16_swap(h[2 * j][1], h[2 * j + 1][1], false, false);
-            const u32x4 chunk = {s0[0], s1[0], s0[1], s1[1]};
+            const u32x4 chunk = tm_chunk(uint2{h[2 * j][0], h[2 * j][1]}, uint2{h[2 * j + 1][0], h[2 * j + 1][1]});
             store_nt((u32x4*)(lane0 + (size_t)j * TM_BLOCK + mi * (16 * 32)), chunk);
           }
           f32x2 t[8];  // the lane's 16 ROUNDED values of the row
@@ -596,12 +557,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
               t[ni * 2 + q] = f32x2{(float)hv[0], (float)hv[1]};
               mx = fmaxf(mx, fmaxf(t[ni * 2 + q][0], t[ni * 2 + q][1]));
             }
-          {
-            const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-            const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-          }
+          mx = quad_max(mx);
           const float mxs = mx * sc2;                        // the row maximum in the log2 domain, as the general code has it
           const float nb = mxs == -INFINITY ? 0.f : -mxs;
           const f32x2 sc22 = {sc2, sc2}, nb2 = {nb, nb};
@@ -611,13 +567,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
             const f32x2 a = __builtin_elementwise_fma(t[e], sc22, nb2);
             se2 += f32x2{__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};
           }
-          float se = se2[0] + se2[1];
-          {
-            const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(se), __float_as_uint(se), false, false);
-            se = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-            const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(se), __float_as_uint(se), false, false);
-            se = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-          }
+          const float se = quad_sum(se2[0] + se2[1]);
           if (kg == 0) lds_write_b64_asm(&red[(wr * 128 + mi * 16 + l15) * 4 + wc], float2{mxs, se});
         }
         SMI_LGKM0_BARRIER();
@@ -665,25 +615,14 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
               t[ni][r] = v;
               mx = fmaxf(mx, v);
             }
-          // lanes 16 / 32 apart joined by v_permlane16/32_swap (VALU rate; __shfl_xor is an LDS round trip per step)
-          {
-            const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-            const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-            mx = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-          }
+          mx = quad_max(mx);
           const float ms = mx == -INFINITY ? 0.f : mx;
           float se = 0.f;
 #pragma unroll
           for (int ni = 0; ni < 4; ++ni)
 #pragma unroll
             for (int r = 0; r < 4; ++r) se += __builtin_amdgcn_exp2f(t[ni][r] - ms);
-          {
-            const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(se), __float_as_uint(se), false, false);
-            se = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-            const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(se), __float_as_uint(se), false, false);
-            se = __uint_as_float(b[0]) + __uint_as_float(b[1]);
-          }
+          se = quad_sum(se);
           if (kg == 0) lds_write_b64_asm(&red[(wr * 128 + mi * 16 + l15) * 4 + wc], float2{mx, se});
         }
         SMI_LGKM0_BARRIER();
@@ -762,15 +701,7 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
         // 2 KiB store of the tile's 256 partial (sum, sum of squares) pairs
 #pragma unroll
         for (int mi = 0; mi < 8; ++mi) {
-          float v0 = rs_sum[mi], v1 = rs_sq[mi];
-          auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v0), false, false);
-          v0 = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-          auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v0), __float_as_uint(v0), false, false);
-          v0 = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
-          s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v1), __float_as_uint(v1), false, false);
-          v1 = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-          s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v1), __float_as_uint(v1), false, false);
-          v1 = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+          const float v0 = quad_sum(rs_sum[mi]), v1 = quad_sum(rs_sq[mi]);
           if (kg == 0) lds_write_b64_asm(&rowsum_lds[wc * 256 + wr * 128 + mi * 16 + l15], float2{v0, v1});
         }
         SMI_LGKM0_BARRIER();
@@ -921,10 +852,9 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
         if constexpr (MODE != 0) {
 #pragma unroll
           for (int u = 0; u < 2; ++u) {
-            const float mean = row_sq[u].x * fold.inv_k;
-            const float var = fmaxf(row_sq[u].y * fold.inv_k - mean * mean, 0.f);
-            row_rs[u] = __builtin_amdgcn_rsqf(var + fold.eps);  // 1 ulp; the result is rounded to fp16 a few steps later
-            row_nm[u] = -row_rs[u] * mean;
+            const float2 ra = fold_row_affine(row_sq[u].x, row_sq[u].y, fold.inv_k, fold.eps);
+            row_rs[u] = ra.x;
+            row_nm[u] = ra.y;
           }
         }
         if constexpr (MODE == 2) {  // row mi * 16 + l15 of the wave's 128: lane (mi * 16 + l15) & 63, register mi >> 2
@@ -958,32 +888,12 @@ __global__ __launch_bounds__(G2_THREADS) void gemm_tn256_kernel(const f16* __res
 #pragma unroll
             for (int nl = 0; nl < 2; ++nl) {
               f32x4 v = acc.v[2 * j + nl][mi];
-              if constexpr (MODE != 0) {
-                // v_pk_fma_f32: two values per instruction (a wave64 VALU instruction takes 4 cycles)
-                const f32x2 rs2 = {aff.x, aff.x}, nm2 = {aff.y, aff.y};
-#pragma unroll
-                for (int hp2 = 0; hp2 < 2; ++hp2) {
-                  const f32x2 c2p = {c2v[nl][2 * hp2], c2v[nl][2 * hp2 + 1]};
-                  f32x2 vp = {v[2 * hp2], v[2 * hp2 + 1]};
-                  if constexpr (MODE == 1) {
-                    const f32x2 c1p = {c1v[nl][2 * hp2], c1v[nl][2 * hp2 + 1]};
-                    vp = __builtin_elementwise_fma(rs2, vp, __builtin_elementwise_fma(nm2, c1p, c2p));
-                  } else {
-                    vp = __builtin_elementwise_fma(rs2, vp, c2p);
-                  }
-                  v[2 * hp2] = vp[0];
-                  v[2 * hp2 + 1] = vp[1];
-                }
-              }
+              if constexpr (MODE != 0) v = fold_apply<MODE>(v, c1v[nl], c2v[nl], aff.x, aff.y);
               const uint2 hp = __builtin_bit_cast(uint2, epi_act_pack<EPI>(v));
               h[nl][0] = hp.x;
               h[nl][1] = hp.y;
             }
-            // rows 16..31 / 48..63 of h[0] <-> rows 0..15 / 32..47 of h[1]
-            const auto s0 = __builtin_amdgcn_permlane16_swap(h[0][0], h[1][0], false, false);
-            const auto s1 = __builtin_amdgcn_permlane16_swap(h[0][1], h[1][1], false, false);
-            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-            const u32x4 chunk = {s0[0], s1[0], s0[1], s1[1]};
+            const u32x4 chunk = tm_chunk(uint2{h[0][0], h[0][1]}, uint2{h[1][0], h[1][1]});
             store_nt((u32x4*)(lane0 + (size_t)j * TM_BLOCK + mi * (16 * 32)), chunk);
           }
         }

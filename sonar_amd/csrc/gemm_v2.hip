@@ -22,8 +22,6 @@
 
 namespace smi {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 // MODE 0: out = act(acc + c2)  (c2 = the bias);  1: LayerNorm fold with the exact mean term;  2: fold with centred weights
 template <int EPI, bool FOLD>
 __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restrict__ X, const f16* __restrict__ W,
@@ -37,27 +35,13 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
   const V2Ring rg = v2_make_ring(smem, wave, lane);
   const unsigned voff = wave * 4096 + lane * 16;
 
-  // ---- tile walk: the rasters of gemm_tn256_kernel (gemm.hip) ----
+  // ---- tile walk (gemm_walk.hpp) ----
   const int ntm = M / 256, ntn = N / 256, nt = K / 32, nout = ntm * ntn;
   const int nq = ntn / 4;
-  const int nvirt = raster ? ((ntm + 63) / 64) * nq * 256 : nout;
-  auto coords = [&](int t, int& tm_, int& tn_) -> bool {
-    if (raster == 0) {
-      constexpr int GM = 8;  // grouped 8(m) x ntn super-tiles in id order (gemm_tile256.hpp: g2_tile_coords_of)
-      const int per_group = GM * ntn, group = t / per_group, first_m = group * GM;
-      const int gsz = min(GM, ntm - first_m), in_group = t - group * per_group;
-      tm_ = first_m + in_group % gsz;
-      tn_ = in_group / gsz;
-      return true;
-    }
-    const int q = t / 256, c = (t % 256) / 32, j = t % 32;
-    tm_ = (c + 8 * (q / nq)) * 8 + j % 8;
-    tn_ = ((q + (raster == 2 ? c : 0)) % nq) * 4 + j / 8;
-    return tm_ < ntm;
-  };
+  const int nvirt = raster ? walk_nvirt(ntm, nq) : nout;
   int tile_m = 0, tile_n = 0;
   auto seek = [&](int t) {
-    while (t < nvirt && !coords(t, tile_m, tile_n)) t += gridDim.x;
+    while (t < nvirt && !walk_coords(t, raster, ntm, ntn, nq, tile_m, tile_n)) t += gridDim.x;
     return t;
   };
   int tile = seek(xcd_remap(blockIdx.x, gridDim.x));
@@ -72,7 +56,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
   v2_start(f, st, rg);
 
   // ---- per-wave constant area: c2[128] | c1[128] | partial sums p = 0..3: float2[128 rows] ----
-  const unsigned cbase = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem + V2_RING_BYTES + wave * V2_CONST_BYTES);
+  const unsigned cbase = v2_const_base(smem, wave);
   auto fetch_consts = [&](int m0, int n0) {
     const float* c2p = c2 + n0 + wc * 128 + lane;
     if constexpr (FOLD) {
@@ -95,10 +79,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
           : "v"(c2p), "v"(c1p), "v"(rp[0]), "v"(rp[1]), "v"(rp[2]), "v"(rp[3]), "s"(cbase), "s"(cbase + 512), "s"(cbase + 1024)
           : "memory");
     } else {
-      asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off\n\tglobal_load_lds_dword %0, off offset:256"
-                   :
-                   : "v"(c2p), "s"(cbase)
-                   : "memory");
+      v2_fetch_consts(c2p, cbase);
     }
   };
   constexpr int NCONST = FOLD ? 8 : 2;  // vector-memory operations of fetch_consts per wave
@@ -200,10 +181,9 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
         const float2 p0 = pr[u][0], p1 = fold.nparts > 1 ? pr[u][1] : z, p2 = fold.nparts > 2 ? pr[u][2] : z,
                      p3 = fold.nparts > 3 ? pr[u][3] : z;
         const float sx = (p0.x + p2.x) + (p1.x + p3.x), sy = (p0.y + p2.y) + (p1.y + p3.y);
-        const float mean = sx * fold.inv_k;
-        const float var = fmaxf(sy * fold.inv_k - mean * mean, 0.f);
-        row_rs[u] = __builtin_amdgcn_rsqf(var + fold.eps);
-        row_nm[u] = -row_rs[u] * mean;
+        const float2 aff = fold_row_affine(sx, sy, fold.inv_k, fold.eps);
+        row_rs[u] = aff.x;
+        row_nm[u] = aff.y;
       }
     } else {
       asm volatile("ds_read_b32 %0, %2\n\tds_read_b32 %1, %2 offset:256\n\ts_waitcnt lgkmcnt(0)"
@@ -230,26 +210,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
         }
       }
       if constexpr (GLU) {
-        // the fold / bias affine of one accumulator block (the LayerNorm in front of this GEMM), no activation
-        auto affine = [&](f32x4 v, const f32x4& c2q, const f32x4& c1q, float rs, float nm) {
-          const f32x2 rs2 = {rs, rs}, nm2 = {nm, nm};
-#pragma unroll
-          for (int hp2 = 0; hp2 < 2; ++hp2) {
-            const f32x2 c2p = {c2q[2 * hp2], c2q[2 * hp2 + 1]};
-            f32x2 vp = {v[2 * hp2], v[2 * hp2 + 1]};
-            if constexpr (MODE == 1) {
-              const f32x2 c1p = {c1q[2 * hp2], c1q[2 * hp2 + 1]};
-              vp = __builtin_elementwise_fma(rs2, vp, __builtin_elementwise_fma(nm2, c1p, c2p));
-            } else if constexpr (MODE == 2) {
-              vp = __builtin_elementwise_fma(rs2, vp, c2p);
-            } else {
-              vp = vp + c2p;
-            }
-            v[2 * hp2] = vp[0];
-            v[2 * hp2 + 1] = vp[1];
-          }
-          return v;
-        };
+        // the fold / bias affine of one accumulator block (the LayerNorm in front of this GEMM), no activation: fold_apply
 #define SMI_V2_GLU(G, JA, JG, MI)                                                                                       \
   {                                                                                                                    \
     f32x4 a0, a1, g0, g1;                                                                                              \
@@ -257,19 +218,17 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
     SMI_V2_RDOUT_IDX(JA, 1, MI, a1);                                                                                   \
     SMI_V2_RDOUT_IDX(JG, 0, MI, g0);                                                                                   \
     SMI_V2_RDOUT_IDX(JG, 1, MI, g1);                                                                                   \
-    a0 = affine(a0, c2q[0], c1q[0], rsall[MI], nmall[MI]);                                                             \
-    a1 = affine(a1, c2q[1], c1q[1], rsall[MI], nmall[MI]);                                                             \
-    g0 = affine(g0, c2q[2], c1q[2], rsall[MI], nmall[MI]);                                                             \
-    g1 = affine(g1, c2q[3], c1q[3], rsall[MI], nmall[MI]);                                                             \
+    a0 = fold_apply<MODE>(a0, c1q[0], c2q[0], rsall[MI], nmall[MI]);                                                   \
+    a1 = fold_apply<MODE>(a1, c1q[1], c2q[1], rsall[MI], nmall[MI]);                                                   \
+    g0 = fold_apply<MODE>(g0, c1q[2], c2q[2], rsall[MI], nmall[MI]);                                                   \
+    g1 = fold_apply<MODE>(g1, c1q[3], c2q[3], rsall[MI], nmall[MI]);                                                   \
     _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                                    \
       a0[e] *= sigmoid_f(g0[e]);                                                                                       \
       a1[e] *= sigmoid_f(g1[e]);                                                                                       \
     }                                                                                                                  \
     const uint2 h0 = __builtin_bit_cast(uint2, epi_act_pack<EPI_BIAS_F16>(a0));                                        \
     const uint2 h1 = __builtin_bit_cast(uint2, epi_act_pack<EPI_BIAS_F16>(a1));                                        \
-    const auto s0 = __builtin_amdgcn_permlane16_swap(h0.x, h1.x, false, false);                                        \
-    const auto s1 = __builtin_amdgcn_permlane16_swap(h0.y, h1.y, false, false);                                        \
-    put((G) * 8 + (MI), u32x4{s0[0], s1[0], s0[1], s1[1]});                                                            \
+    put((G) * 8 + (MI), tm_chunk(h0, h1));                                                                             \
   }
 #define SMI_V2_GLU_GROUP(G, JA, JG)                                                                                    \
   {                                                                                                                    \
@@ -296,36 +255,11 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_kernel(const f16* __restri
     SMI_V2_RDOUT_IDX(J, 1, MI, vb);                                                                                    \
     put((J) * 8 + (MI), finish(va, vb, c2v, c1v, rsall[MI], nmall[MI]));                                               \
   }
+      // activation + fp16 of the block pair, then one whole 16-B chunk per lane (gemm_epi.hpp: tm_chunk)
       auto finish = [&](f32x4 va, f32x4 vb, const f32x4 (&c2v)[2], const f32x4 (&c1v)[2], float rs, float nm) {
-        uint32_t h[2][2];
-#pragma unroll
-        for (int nl = 0; nl < 2; ++nl) {
-          f32x4 v = nl ? vb : va;
-          const f32x2 rs2 = {rs, rs}, nm2 = {nm, nm};
-#pragma unroll
-          for (int hp2 = 0; hp2 < 2; ++hp2) {
-            const f32x2 c2p = {c2v[nl][2 * hp2], c2v[nl][2 * hp2 + 1]};
-            f32x2 vp = {v[2 * hp2], v[2 * hp2 + 1]};
-            if constexpr (MODE == 1) {
-              const f32x2 c1p = {c1v[nl][2 * hp2], c1v[nl][2 * hp2 + 1]};
-              vp = __builtin_elementwise_fma(rs2, vp, __builtin_elementwise_fma(nm2, c1p, c2p));
-            } else if constexpr (MODE == 2) {
-              vp = __builtin_elementwise_fma(rs2, vp, c2p);
-            } else {
-              vp = vp + c2p;
-            }
-            v[2 * hp2] = vp[0];
-            v[2 * hp2 + 1] = vp[1];
-          }
-          const uint2 hp = __builtin_bit_cast(uint2, epi_act_pack<EPI>(v));
-          h[nl][0] = hp.x;
-          h[nl][1] = hp.y;
-        }
-        // rows 16..31 / 48..63 of h[0] <-> rows 0..15 / 32..47 of h[1]: every lane then holds one whole 16-B chunk
-        // (lane group kg owns chunk (kg&1)*2 + (kg>>1) of the 32-column k-block; gemm.hip, LAYOUT 2)
-        const auto s0 = __builtin_amdgcn_permlane16_swap(h[0][0], h[1][0], false, false);
-        const auto s1 = __builtin_amdgcn_permlane16_swap(h[0][1], h[1][1], false, false);
-        return u32x4{s0[0], s1[0], s0[1], s1[1]};
+        const uint2 h0 = __builtin_bit_cast(uint2, epi_act_pack<EPI>(fold_apply<MODE>(va, c1v[0], c2v[0], rs, nm)));
+        const uint2 h1 = __builtin_bit_cast(uint2, epi_act_pack<EPI>(fold_apply<MODE>(vb, c1v[1], c2v[1], rs, nm)));
+        return tm_chunk(h0, h1);
       };
 #define SMI_V2_KBLOCK(J)                                                                                               \
   {                                                                                                                    \
@@ -383,24 +317,10 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_resid_kernel(const f16* __
 
   const int ntm = M / 256, ntn = N / 256, nt = K / 32, nout = ntm * ntn;
   const int nq = ntn / 4;
-  const int nvirt = raster ? ((ntm + 63) / 64) * nq * 256 : nout;
-  auto coords = [&](int t, int& tm_, int& tn_) -> bool {
-    if (raster == 0) {
-      constexpr int GM = 8;
-      const int per_group = GM * ntn, group = t / per_group, first_m = group * GM;
-      const int gsz = min(GM, ntm - first_m), in_group = t - group * per_group;
-      tm_ = first_m + in_group % gsz;
-      tn_ = in_group / gsz;
-      return true;
-    }
-    const int q = t / 256, c = (t % 256) / 32, j = t % 32;
-    tm_ = (c + 8 * (q / nq)) * 8 + j % 8;
-    tn_ = ((q + (raster == 2 ? c : 0)) % nq) * 4 + j / 8;
-    return tm_ < ntm;
-  };
+  const int nvirt = raster ? walk_nvirt(ntm, nq) : nout;
   int tile_m = 0, tile_n = 0;
   auto seek = [&](int t) {
-    while (t < nvirt && !coords(t, tile_m, tile_n)) t += gridDim.x;
+    while (t < nvirt && !walk_coords(t, raster, ntm, ntn, nq, tile_m, tile_n)) t += gridDim.x;
     return t;
   };
   int tile = seek(xcd_remap(blockIdx.x, gridDim.x));
@@ -415,16 +335,13 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_resid_kernel(const f16* __
   v2_start(f, st, rg);
 
   // per-wave LDS area above the ring: bias[128] at +0; this wave's row sums float2[128] at +6144
-  const unsigned cbase = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem + V2_RING_BYTES + wave * V2_CONST_BYTES);
+  const unsigned cbase = v2_const_base(smem, wave);
   const unsigned lds_const0 = (unsigned)(size_t)smem + V2_RING_BYTES;
   const bool has_bias = bias != nullptr;
   const float* bias_src = has_bias ? bias : (const float*)W;  // no bias: the same two DMA instructions from a valid address
   auto fetch_consts = [&](int n0) {
     const float* bp = bias_src + (has_bias ? n0 + wc * 128 : 0) + lane;
-    asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dword %0, off\n\tglobal_load_lds_dword %0, off offset:256"
-                 :
-                 : "v"(bp), "s"(cbase)
-                 : "memory");
+    v2_fetch_consts(bp, cbase);
   };
   constexpr int NCONST = 2;
   constexpr int NEMIT = EMIT ? 1 : 0;
@@ -585,15 +502,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_resid_kernel(const f16* __
       // join the 4 lane groups of a row (lanes 16 apart); lane group 0 leaves the wave's 128 row sums in LDS
 #pragma unroll
       for (int mi = 0; mi < 8; ++mi) {
-        float v0 = rs_sum[mi], v1 = rs_sq[mi];
-        auto s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v0), false, false);
-        v0 = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-        auto s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v0), __float_as_uint(v0), false, false);
-        v0 = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
-        s16 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v1), __float_as_uint(v1), false, false);
-        v1 = __uint_as_float(s16[0]) + __uint_as_float(s16[1]);
-        s32 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v1), __float_as_uint(v1), false, false);
-        v1 = __uint_as_float(s32[0]) + __uint_as_float(s32[1]);
+        const float v0 = quad_sum(rs_sum[mi]), v1 = quad_sum(rs_sq[mi]);
         if (kg == 0) {
           const float2 pv = {v0, v1};
           asm volatile("ds_write_b64 %0, %1" ::"v"(cbase + 6144 + (mi * 16 + l15) * 8), "v"(pv) : "memory");
@@ -631,13 +540,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_stats_kernel(const f16* __
   // id-order raster (grouped 8(m) x ntn super-tiles): M = beam x batch rows are a handful of row tiles
   const int ntm = M / 256, ntn = N / 256, nt = K / 32, nout = ntm * ntn;
   int tile_m = 0, tile_n = 0;
-  auto coords = [&](int t) {
-    constexpr int GM = 8;
-    const int per_group = GM * ntn, group = t / per_group, first_m = group * GM;
-    const int gsz = min(GM, ntm - first_m), in_group = t - group * per_group;
-    tile_m = first_m + in_group % gsz;
-    tile_n = in_group / gsz;
-  };
+  auto coords = [&](int t) { walk_grouped(t, ntm, ntn, tile_m, tile_n); };  // a lambda: called directly, hipcc renumbers the SGPRs
   int tile = xcd_remap(blockIdx.x, gridDim.x);
   if (tile >= nout) return;
   coords(tile);
@@ -650,7 +553,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_stats_kernel(const f16* __
   V2Frag f;
   v2_start(f, st, rg);
 
-  const unsigned cbase = __builtin_amdgcn_readfirstlane((unsigned)(size_t)smem + V2_RING_BYTES + wave * V2_CONST_BYTES);
+  const unsigned cbase = v2_const_base(smem, wave);
   const unsigned lds_const0 = (unsigned)(size_t)smem + V2_RING_BYTES;
   const float sc2 = stats.scale * 1.4426950408889634f;  // > 0 (the launcher checks): max and scaling commute
   constexpr int NST = 32, NEMIT = 2;
@@ -736,9 +639,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_stats_kernel(const f16* __
     SMI_V2_SBLK(0, 0, MI) SMI_V2_SBLK(0, 1, MI) SMI_V2_SBLK(1, 0, MI) SMI_V2_SBLK(1, 1, MI)                              \
     SMI_V2_SBLK(2, 0, MI) SMI_V2_SBLK(2, 1, MI) SMI_V2_SBLK(3, 0, MI) SMI_V2_SBLK(3, 1, MI)                              \
     _Pragma("unroll") for (int j = 0; j < 4; ++j) {                                                                      \
-      const auto s0 = __builtin_amdgcn_permlane16_swap(h[2 * j][0], h[2 * j + 1][0], false, false);                      \
-      const auto s1 = __builtin_amdgcn_permlane16_swap(h[2 * j][1], h[2 * j + 1][1], false, false);                      \
-      const u32x4 chunk = {s0[0], s1[0], s0[1], s1[1]};                                                                  \
+      const u32x4 chunk = tm_chunk(uint2{h[2 * j][0], h[2 * j][1]}, uint2{h[2 * j + 1][0], h[2 * j + 1][1]});            \
       store_nt((u32x4*)(obase + (size_t)j * (TM_BLOCK * 2) + (MI) * 1024), chunk);                                       \
     }                                                                                                                    \
     f32x2 t[16]; /* the lane's 32 ROUNDED values of the row (FULL: raw; else scaled to the log2 domain and masked) */     \
@@ -754,12 +655,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_stats_kernel(const f16* __
       t[ni * 2 + q] = v;                                                                                                 \
       mx = fmaxf(mx, fmaxf(v[0], v[1]));                                                                                 \
     }                                                                                                                    \
-    {                                                                                                                    \
-      const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);           \
-      mx = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));                                                          \
-      const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);           \
-      mx = fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));                                                          \
-    }                                                                                                                    \
+    mx = quad_max(mx);                                                                                                   \
     /* the row maximum in the log2 domain (scale > 0: max and scaling commute, bit for bit) */                           \
     const float mxs = (FULL) ? mx * sc2 : mx;                                                                            \
     const float nb = mxs == -INFINITY ? 0.f : -mxs;                                                                      \
@@ -769,13 +665,7 @@ __global__ __launch_bounds__(V2_THREADS) void gemm_v2_stats_kernel(const f16* __
       const f32x2 a = (FULL) ? __builtin_elementwise_fma(t[e], mul2, nb2) : t[e] + nb2;                                  \
       se2 += f32x2{__builtin_amdgcn_exp2f(a[0]), __builtin_amdgcn_exp2f(a[1])};                                          \
     }                                                                                                                    \
-    float se = se2[0] + se2[1];                                                                                          \
-    {                                                                                                                    \
-      const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(se), __float_as_uint(se), false, false);           \
-      se = __uint_as_float(a[0]) + __uint_as_float(a[1]);                                                                \
-      const auto b = __builtin_amdgcn_permlane32_swap(__float_as_uint(se), __float_as_uint(se), false, false);           \
-      se = __uint_as_float(b[0]) + __uint_as_float(b[1]);                                                                \
-    }                                                                                                                    \
+    const float se = quad_sum(se2[0] + se2[1]);                                                                          \
     if (kg == 0) {                                                                                                       \
       const float2 pv = {mxs, se};                                                                                       \
       asm volatile("ds_write_b64 %0, %1" ::"v"(cbase + ((MI) * 16 + l15) * 8), "v"(pv) : "memory");                      \

@@ -41,9 +41,13 @@ def test_pack_tile_major(lib, rows, k):
     assert lib.smi_pack_tile_major(a.data_ptr(), tm.data_ptr(), rows + 1, k, 0, _stream()) != 0
 
 
-@pytest.mark.parametrize("m,n,k", [(256, 256, 64), (256, 512, 192), (512, 1024, 1024), (256, 256, 8192),
-                                   (1024, 768, 256)])
-@pytest.mark.parametrize("epi,out_tm", [(0, 0), (0, 1), (1, 1), (2, 0), (3, 0), (4, 0), (5, 1), (6, 0), (8, 0), (8, 1)])
+# every shape with every epilogue, and the persistent walk's skip path once: 57 x 16 tiles under the XCD-owned raster (the last
+# m-group has one row tile, so seven of every eight slots of its owner are skipped), four tiles per workgroup
+@pytest.mark.parametrize("m,n,k,epi,out_tm", [
+    pytest.param(m, n, k, epi, out_tm, id=f"{epi}-{out_tm}-{m}-{n}-{k}")
+    for m, n, k in [(256, 256, 64), (256, 512, 192), (512, 1024, 1024), (256, 256, 8192), (1024, 768, 256)]
+    for epi, out_tm in [(0, 0), (0, 1), (1, 1), (2, 0), (3, 0), (4, 0), (5, 1), (6, 0), (8, 0), (8, 1)]
+] + [pytest.param(14592, 4096, 256, 1, 1, id="1-1-14592-4096-256")])
 def test_gemm_tn_tile_major(lib, m, n, k, epi, out_tm):
     """Tile-major operands (and output) on both tile engines against the same fp32 reference."""
     from sonar_amd import _lib
@@ -180,12 +184,15 @@ def test_gemm_v2_tile_stats(lib, m, n, k, valid_n):
                                       tsum.data_ptr(), _stream()) != 0
 
 
-@pytest.mark.parametrize("m,n,k", [(6144, 4096, 768),      # 384 tiles on 256 workgroups, the shortest K loop the engine takes (24 slices)
-                                   (6144, 4096, 1024),     # the encoder's K; some workgroups walk two tiles, some one
-                                   (16384, 4096, 1280),    # 1024 tiles: XCD-owned raster, four tiles per workgroup, 40 slices
-                                   (2560, 1024, 8192),     # 40 tiles, K = 8192: one tile per workgroup, long loop
-                                   (512, 256, 1024)])      # two tiles: most of the chip idle
-@pytest.mark.parametrize("epi", [0, 1, 5, 8, 9])
+@pytest.mark.parametrize("m,n,k,epi", [
+    pytest.param(m, n, k, epi, id=f"{epi}-{m}-{n}-{k}")
+    for m, n, k in [(6144, 4096, 768),      # 384 tiles on 256 workgroups, the shortest K loop the engine takes (24 slices)
+                    (6144, 4096, 1024),     # the encoder's K; some workgroups walk two tiles, some one
+                    (16384, 4096, 1280),    # 1024 tiles: XCD-owned raster, four tiles per workgroup, 40 slices
+                    (2560, 1024, 8192),     # 40 tiles, K = 8192: one tile per workgroup, long loop
+                    (512, 256, 1024)]       # two tiles: most of the chip idle
+    for epi in [0, 1, 5, 8, 9]
+] + [pytest.param(14592, 4096, 256, 1, id="1-14592-4096-256")])   # 57 x 16 tiles: the XCD-owned raster's partial last m-group (skipped slots)
 def test_gemm_v2_engine(lib, m, n, k, epi):
     """The 4-wave 256x256 engine (gemm_v2.hip: accumulators in AGPRs, inline-asm K steps, a ring that streams across tiles;
     epi 8 / 9: the tile-major fp16 residual stream, read-modify-write, old tile requested by asm loads under the last K

@@ -102,6 +102,71 @@ def test_commuted_destination_is_a_diff(tmp_path):
     assert rc == 1 and "DIFF k_a" in out
 
 
+def test_swapped_scalar_and_integer_operands_are_commuted(tmp_path):
+    body = ("\ts_add_i32 s5, s0, s2\n\ts_mul_i32 s6, s5, s3\n\ts_and_b32 s7, s6, s1\n\ts_max_u32 s8, s7, s4\n"
+            "\tv_add_u32_e32 v1, v2, v3\n\ts_add_u32 s9, s8, s5\n")
+    swapped = ("\ts_add_i32 s5, s2, s0\n\ts_mul_i32 s6, s3, s5\n\ts_and_b32 s7, s1, s6\n\ts_max_u32 s8, s4, s7\n"
+               "\tv_add_u32_e32 v1, v3, v2\n\ts_add_u32 s9, s5, s8\n")
+    rc, out = run(tmp_path, unit([kernel("k_a", body, 0)], "0"), unit([kernel("k_a", swapped, 0)], "0"))
+    assert rc == 0 and "COMMUTED k_a" in out
+    # a subtraction and a shift do not commute
+    for op in ("s_sub_i32", "s_lshl_b32"):
+        rc, out = run(tmp_path, unit([kernel("k_a", body + f"\t{op} s10, s9, s1\n", 0)], "0"),
+                      unit([kernel("k_a", body + f"\t{op} s10, s1, s9\n", 0)], "0"))
+        assert rc == 1 and "DIFF k_a" in out
+
+
+# a K-loop-like body: address arithmetic between memory operations, counted waits, MFMAs
+BODY_C = ("\ts_lshl_b32 s4, s2, 8\n\tv_lshlrev_b32_e32 v9, 4, v0\n\tglobal_load_dwordx4 v[2:5], v1, s[0:1]\n"
+          "\tds_read_b128 v[10:13], v9\n\ts_waitcnt vmcnt(0) lgkmcnt(0)\n\tv_mfma_f32_16x16x32_f16 a[0:3], v[2:5], v[10:13], a[0:3]\n"
+          "\ts_barrier\n\tv_add_u32_e32 v1, s4, v1\n\tglobal_store_dwordx4 v1, v[2:5], s[0:1]\n")
+DESC_C = DESC + "\t\t.amdhsa_next_free_sgpr 16\n\t\t.amdhsa_accum_offset 16\n\t\t.amdhsa_private_segment_fixed_size 0\n"
+
+
+def test_moved_valu_and_salu_lines_are_rescheduled(tmp_path):
+    lines = BODY_C.splitlines(keepends=True)
+    moved = "".join([lines[1], lines[0], lines[2], lines[3], lines[4], lines[5], lines[7], lines[6], lines[8]])
+    assert moved != BODY_C
+    base = unit([kernel("k_a", BODY_C, 0, desc=DESC_C), kernel("k_b", BODY_B, 1)], "0")
+    rc, out = run(tmp_path, base, unit([kernel("k_a", moved, 0, desc=DESC_C), kernel("k_b", BODY_B, 1)], "0"))
+    assert rc == 0
+    assert "RESCHEDULED k_a" in out and "IDENTICAL k_b" in out
+    assert out[0].endswith("identical 1, commuted 0, differing 0, removed 0, added 0, rescheduled 1")
+    # the same move with one more SGPR in the descriptor, or with a register renumbered, is a DIFF
+    rc, out = run(tmp_path, base, unit([kernel("k_a", moved, 0, desc=DESC_C.replace("sgpr 16", "sgpr 18")), kernel("k_b", BODY_B, 1)], "0"))
+    assert rc == 1 and "DIFF k_a" in out
+    rc, out = run(tmp_path, base, unit([kernel("k_a", moved.replace("s4", "s6"), 0, desc=DESC_C), kernel("k_b", BODY_B, 1)], "0"))
+    assert rc == 1 and "DIFF k_a" in out
+
+
+def test_moved_global_load_is_a_diff_not_rescheduled(tmp_path):
+    lines = BODY_C.splitlines(keepends=True)
+    moved = "".join([lines[0], lines[1], lines[3], lines[2]] + lines[4:])  # the load behind the LDS read
+    rc, out = run(tmp_path, unit([kernel("k_a", BODY_C, 0, desc=DESC_C)], "0"), unit([kernel("k_a", moved, 0, desc=DESC_C)], "0"))
+    assert rc == 1 and "DIFF k_a" in out and not [line for line in out if line.startswith("RESCHEDULED")]
+    # a wait with another count, the rest in place
+    rc, out = run(tmp_path, unit([kernel("k_a", BODY_C, 0, desc=DESC_C)], "0"),
+                  unit([kernel("k_a", BODY_C.replace("vmcnt(0) lgkmcnt(0)", "vmcnt(1) lgkmcnt(0)"), 0, desc=DESC_C)], "0"))
+    assert rc == 1 and "DIFF k_a" in out
+
+
+def test_exchanged_counted_waits_are_a_diff(tmp_path):
+    # the same lines, the same mnemonics in the same order: only the counters of the two waits changed places
+    body = ("\tglobal_load_dwordx4 v[2:5], v1, s[0:1]\n\tglobal_load_dwordx4 v[6:9], v1, s[0:1] offset:16\n\ts_waitcnt vmcnt(1)\n"
+            "\tv_mfma_f32_16x16x32_f16 a[0:3], v[2:5], v[2:5], a[0:3]\n\ts_waitcnt vmcnt(0)\n"
+            "\tv_mfma_f32_16x16x32_f16 a[0:3], v[6:9], v[6:9], a[0:3]\n")
+    swapped = body.replace("vmcnt(1)", "vmcnt(X)").replace("vmcnt(0)", "vmcnt(1)").replace("vmcnt(X)", "vmcnt(0)")
+    assert sorted(body.splitlines()) == sorted(swapped.splitlines())
+    rc, out = run(tmp_path, unit([kernel("k_a", body, 0, desc=DESC_C)], "0"), unit([kernel("k_a", swapped, 0, desc=DESC_C)], "0"))
+    assert rc == 1 and "DIFF k_a" in out and not [line for line in out if line.startswith("RESCHEDULED")]
+    # two counters on one line count too
+    body2 = body.replace("vmcnt(1)", "vmcnt(1) lgkmcnt(0)").replace("s_waitcnt vmcnt(0)\n", "s_waitcnt vmcnt(0) lgkmcnt(1)\n")
+    swapped2 = body2.replace("vmcnt(1) lgkmcnt(0)", "W").replace("vmcnt(0) lgkmcnt(1)", "vmcnt(1) lgkmcnt(0)").replace("W", "vmcnt(0) lgkmcnt(1)")
+    assert body2 != swapped2 and sorted(body2.splitlines()) == sorted(swapped2.splitlines())
+    rc, out = run(tmp_path, unit([kernel("k_a", body2, 0, desc=DESC_C)], "0"), unit([kernel("k_a", swapped2, 0, desc=DESC_C)], "0"))
+    assert rc == 1 and "DIFF k_a" in out
+
+
 def test_rename_pairs_up(tmp_path):
     base = unit([kernel("k_oldILi1ELb1EE", BODY_A, 0), kernel("k_b", BODY_B, 1)], "0")
     tree = unit([kernel("k_newILi1EE", BODY_A, 0), kernel("k_b", BODY_B, 1)], "1")

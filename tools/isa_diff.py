@@ -7,14 +7,24 @@
 Compares function bodies (from the `name:` label line, with or without its `; @name` comment, to the next `.Lfunc_endN:`)
 and .amdhsa_kernel descriptors; the per-file __hip_cuid_<hash> symbol is masked, local labels are renumbered per
 function and the padding in front of a label line's comment is ignored.  OLD=NEW pairs a kernel of the base with its new mangled name (a template parameter that went).
-Every kernel of the base is IDENTICAL, COMMUTED (equal once the two source operands of every v_add/mul/max/min_f32_e32
-line are sorted -- IEEE add, mul, max and min commute; nothing else is normalised), DIFF or REMOVED; kernels only in the
-tree are ADDED.  Exit status 1 if a kernel is DIFF or ADDED.
+Every kernel of the base is IDENTICAL, COMMUTED (equal once the two source operands of every v_add/mul/max/min_f32_e32,
+s_add_i32/u32, s_mul_i32, s_and/or/xor_b32, s_min/max_i32/u32 and v_add_u32_e32 line are sorted -- IEEE add, mul, max and
+min and the integer operations commute exactly, SCC and carry included; nothing else is normalised), RESCHEDULED, DIFF or
+REMOVED; kernels only in the tree are ADDED.  RESCHEDULED: the sequence of v_mfma*, ds_*, global_* / buffer_*, s_waitcnt*,
+s_barrier and s_setprio lines, compared by mnemonic (s_waitcnt: with its counters), equals the base's, and so do the
+descriptor's VGPR / AGPR / SGPR counts, scratch size and LDS size, and the two bodies hold the same lines (as a multiset,
+after the COMMUTED sorting) -- only VALU / SALU address or arithmetic lines moved; a line that changed, a register
+renumbered, is DIFF.  (The 256x256 GEMM engines rely on counted vmcnt waits: the order of memory operations and waits is
+what must not move.)
+Exit status 1 if a kernel is DIFF or ADDED.
 """
 import re
 import sys
 
-COMMUTATIVE = re.compile(r"^(\s*v_(?:add|mul|max|min)_f32_e32 [^,]+), ([^,;]+), ([^,;]+?)(\s*(?:;.*)?)$", re.M)
+COMMUTATIVE = re.compile(r"^(\s*(?:v_(?:add|mul|max|min)_f32_e32|s_add_[iu]32|s_mul_i32|s_(?:and|or|xor)_b32|s_(?:min|max)_[iu]32|v_add_u32_e32)"
+                         r" [^,]+), ([^,;]+), ([^,;]+?)(\s*(?:;.*)?)$", re.M)
+ORDERED = re.compile(r"^\s*(v_mfma\w*|ds_\w+|global_\w+|buffer_\w+|s_barrier|s_setprio|s_waitcnt\w*[^;\n]*)", re.M)  # s_waitcnt: the whole operand text
+RESOURCES = re.compile(r"^\s*\.amdhsa_(?:next_free_vgpr|next_free_sgpr|accum_offset|private_segment_fixed_size|group_segment_fixed_size) .*$", re.M)
 
 
 def kernels(path, rename=()):
@@ -46,17 +56,25 @@ def commute(s):
     return COMMUTATIVE.sub(lambda m: "%s, %s, %s%s" % (m.group(1), *sorted(m.group(2, 3)), m.group(4)), s)
 
 
+def skeleton(s):  # what a RESCHEDULED kernel shares with its base: ordered lines in order, resources, all lines as a multiset
+    return ([" ".join(m.split()) for m in ORDERED.findall(s)], [" ".join(m.split()) for m in RESOURCES.findall(s)],
+            sorted(commute(s).splitlines()))
+
+
 pairs = [tuple(p.split("=", 1)) for p in sys.argv[3:]]
 a, b = ({k: norm(v) for k, v in kernels(*args).items()} for args in ((sys.argv[1], pairs), (sys.argv[2],)))
 both = [k for k in a if k in b]
 same = [k for k in both if a[k] == b[k]]
 comm = [k for k in both if a[k] != b[k] and commute(a[k]) == commute(b[k])]
-diff = [k for k in both if commute(a[k]) != commute(b[k])]
+rest = [k for k in both if commute(a[k]) != commute(b[k])]
+resch = [k for k in rest if skeleton(a[k]) == skeleton(b[k])]
+diff = [k for k in rest if k not in resch]
 print(f"base {len(a)} kernels, tree {len(b)}; identical {len(same)}, commuted {len(comm)}, differing {len(diff)}, "
-      f"removed {len(set(a) - set(b))}, added {len(set(b) - set(a))}")
+      f"removed {len(set(a) - set(b))}, added {len(set(b) - set(a))}, rescheduled {len(resch)}")
 for old, new in pairs: print("PAIRED", old, "->", new)
 for k in same: print("IDENTICAL", k)
 for k in comm: print("COMMUTED", k)
+for k in resch: print("RESCHEDULED", k)
 for k in diff: print("DIFF", k)
 for k in sorted(set(a) - set(b)): print("REMOVED", k)
 for k in sorted(set(b) - set(a)): print("ADDED", k)

@@ -2,14 +2,20 @@
 //   c++ -std=c++17 -g -fsanitize=address,undefined -I sonar_amd/csrc tools/micro/gemm_route_walk.cpp -o route_walk
 //   ./route_walk tests/golden/gemm_routes.json
 // Fills GemmRequest / GemmEnv directly (no library, no HIP), calls gemm_route / gemm_splitk_parts for every case line and compares
-// with the recorded answer.  Exit status 1 on a mismatch.
+// with the recorded answer.  Second pass: for every distinct route on a persistent 256x256 engine (GEMM_PP256, GEMM_V2,
+// GEMM_V2_RESID, GEMM_V2_STATS) it replays the tile walk of all grid_x workgroups with gemm_walk.hpp, as the kernels spell it,
+// and checks that every (tile_m, tile_n, K part) is visited exactly once and nothing out of range is produced; the same for a
+// few synthetic grids with a partial last m-group under rasters 1 and 2.  Exit status 1 on a mismatch or a missed walk.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <set>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "gemm_route.hpp"
+#include "gemm_walk.hpp"
 
 using namespace smi;
 
@@ -25,9 +31,56 @@ static std::vector<long long> ints_after(const char* s, const char* key) {  // t
   return v;
 }
 
+// The walk of all `grid` workgroups over ntm x ntn tiles x ksplit K parts.  parts: gemm_tn256_kernel (ids over the K parts,
+// kz = id / tiles under raster 0); else the 4-wave kernels; stats_walk: gemm_v2_stats_kernel (raster 0 without a seek).
+static bool walk_ok(int ntm, int ntn, int ksplit, int raster, int grid, bool parts, bool stats_walk) {
+  const int nout = ntm * ntn, nq = ntn / 4;
+  const int nvirt = raster ? walk_nvirt(ntm, nq) : nout * ksplit;
+  std::vector<int> seen((size_t)nout * ksplit, 0);
+  bool ok = true;
+  for (int b = 0; b < grid && ok; ++b) {
+    int tile_m = 0, tile_n = 0;
+    auto seek = [&](int t) {
+      while (t < nvirt && !(parts ? walk_coords_parts(t, raster, ntm, ntn, nq, nout, tile_m, tile_n)
+                                  : walk_coords(t, raster, ntm, ntn, nq, tile_m, tile_n)))
+        t += grid;
+      return t;
+    };
+    int tile = xcd_remap(b, grid);
+    if (!stats_walk) tile = seek(tile);
+    while (tile < nvirt) {
+      if (stats_walk) walk_grouped(tile, ntm, ntn, tile_m, tile_n);
+      const int kz = raster ? 0 : tile / nout;
+      if (tile_m < 0 || tile_m >= ntm || tile_n < 0 || tile_n >= ntn || kz < 0 || kz >= ksplit) {
+        fprintf(stderr, "walk out of range: tile (%d, %d, part %d) of %d x %d x %d, raster %d, grid %d\n", tile_m, tile_n, kz, ntm, ntn,
+                ksplit, raster, grid);
+        return false;
+      }
+      ++seen[((size_t)kz * ntm + tile_m) * ntn + tile_n];
+      tile = stats_walk ? tile + grid : seek(tile + grid);
+    }
+  }
+  for (int v : seen) ok = ok && v == 1;
+  if (!ok) fprintf(stderr, "walk misses or repeats a tile: %d x %d x %d, raster %d, grid %d\n", ntm, ntn, ksplit, raster, grid);
+  return ok;
+}
+
+static std::set<std::tuple<int, int, int, int, int, int>> walked;  // (kind, ntm, ntn, ksplit, raster, grid) already replayed
+static long nwalks = 0, bad_walks = 0;
+
+static void check_walk(const GemmRoute& r, int M, int N) {
+  if (r.engine != GEMM_PP256 && r.engine != GEMM_V2 && r.engine != GEMM_V2_RESID && r.engine != GEMM_V2_STATS) return;
+  const bool parts = r.engine == GEMM_PP256, stats_walk = r.engine == GEMM_V2_STATS;
+  const int ksplit = r.ksplit > 0 ? r.ksplit : 1, raster = stats_walk ? 0 : r.raster;
+  if (!walked.emplace(parts ? 0 : stats_walk ? 2 : 1, M / ROUTE_T256, N / ROUTE_T256, ksplit, raster, r.grid_x).second) return;
+  ++nwalks;
+  if (!walk_ok(M / ROUTE_T256, N / ROUTE_T256, ksplit, raster, r.grid_x, parts, stats_walk)) ++bad_walks;
+}
+
 static std::vector<long long> route_fields(const GemmRequest& q, const GemmEnv& env) {
   const GemmRoute r = gemm_route(q, env);
   if (r.engine == GEMM_NONE) return {0};
+  check_walk(r, q.M, q.N);
   return {r.engine, r.epi, r.layout, r.ring, r.unit, r.flag, r.grid_x, r.grid_y, r.lds_bytes, r.ksplit, r.raster, r.part_stride};
 }
 
@@ -128,6 +181,13 @@ int main(int argc, char** argv) {
     }
   }
   fclose(f);
-  printf("%ld cases, %ld mismatches\n", ncases, bad);
-  return bad || !ncases ? 1 : 0;
+  // synthetic: 57 row tiles (the last m-group, owned by XCD 7, has one tile: 7 of every 8 of its slots are skipped) x 16 column tiles
+  for (int raster = 1; raster <= 2; ++raster)
+    for (int grid : {256, 240, 64})
+      for (int parts = 0; parts < 2; ++parts) {
+        ++nwalks;
+        if (!walk_ok(57, 16, 1, raster, grid, parts != 0, false)) ++bad_walks;
+      }
+  printf("%ld cases, %ld mismatches; %ld walks, %ld bad\n", ncases, bad, nwalks, bad_walks);
+  return bad || !ncases || bad_walks || !nwalks ? 1 : 0;
 }
