@@ -711,6 +711,49 @@ int smi_kmeans_fit(const void* xn_f16, int64_t n, int32_t d, int64_t K, int32_t 
                    int32_t* counts, double* objective, int32_t* moved, int32_t* empty, void* workspace,
                    int64_t workspace_bytes, void* stream);
 
+/* IVF-Flat index over sentence embeddings (restated in tests/ivf_ref.py).  K inverted lists over the n fp16
+ * rows of a matrix from smi_xsim_normalize: a search scores a query against the rows of the lists it probes only, about
+ * nprobe / K of smi_xsim_topk's work.  The coarse quantiser is not part of these entries: labels and probes are what
+ * smi_xsim_topk against the centroids returns (k = 1 for the labels, k = nprobe for the probes).
+ *
+ * Storage, list-contiguous: list_rows fp16 [capacity_slots, d] (row copies), list_ids int32 [capacity_slots] (the original
+ *   row number of every slot), list_offsets int32 [K + 1] (list c is the slots list_offsets[c] .. list_offsets[c + 1];
+ *   list_offsets[K] = the slots in use), list_sizes int32 [K] (its rows).  Every list begins at a multiple of
+ *   smi_ivf_list_align() = SMI_IVF_LIST_ALIGN slots (one 16-row block of the scan's MFMA) and is padded to that multiple
+ *   with zero rows whose id is -1, so a 16-slot block of the scan never spans two lists.  smi_ivf_slots_bound(n, K) = the
+ *   largest number of slots any labelling of n rows over K lists can need, min(n, K) * A + floor((n - min(n, K)) / A) * A.
+ * smi_ivf_build: row i goes to list labels[i]; a label outside [0, K) leaves the row out of the index and nothing is
+ *   addressed through it (smi_kmeans_update's convention).  The order of the rows inside a list depends on the arrival order
+ *   of atomics; no search result depends on it.  The host has not seen the labels, so capacity_slots must cover every
+ *   labelling: capacity_slots >= smi_ivf_slots_bound(n, K).  Slots from list_offsets[K] on are not written, except
+ *   list_ids, which is -1 there.
+ * smi_ivf_search: qn = normalised queries [smi_xsim_padded_rows(nq), d]; probes = device int32 [nq, nprobe], the lists
+ *   each query scans; an entry outside [0, K) names no list.  idx [nq, k] / score [nq, k]: the k best rows of the probed
+ *   lists in smi_xsim_topk's total order (score descending, ties to the lower ORIGINAL row number, across lists as inside
+ *   them); (-1, -inf) where fewer than k candidates exist.  A score is the fp32 accumulation of the fp16 products in one
+ *   fixed order over d (MFMA K slices ascending): its bits do not depend on the list the row is in, on its slot, on the
+ *   other queries of the call or on their order.  A probe row that names one list twice (smi_xsim_topk never makes one)
+ *   may return that list's rows twice.  Reads nothing back, allocates nothing; list_rows / list_ids / list_offsets must be
+ *   what smi_ivf_build wrote (they are trusted, as device data is everywhere here).
+ * workspace: device memory, 16-byte aligned, smi_ivf_build_workspace_bytes / smi_ivf_search_workspace_bytes bytes.
+ * Refused before any launch: a null pointer, n / nq / K < 1, k or nprobe outside [1, 8], a small or misaligned workspace,
+ *   capacity_slots below the bound (SMI_ERR_INVALID_ARG); d not a multiple of 64, n, K, nq * nprobe or the slots bound above
+ *   2^31 - 256 (SMI_ERR_UNSUPPORTED).  For these shapes the sizing functions return 0.  One work unit of the scan is one
+ *   list and SMI_IVF_UNIT_QUERIES of the queries that probe it (twice that where nq * nprobe >= 256 K; no bit of the result
+ *   depends on it): a long list probed by few queries runs on few CUs. */
+#define SMI_IVF_LIST_ALIGN 16
+#define SMI_IVF_UNIT_QUERIES 64
+int32_t smi_ivf_list_align(void);
+int64_t smi_ivf_slots_bound(int64_t n, int64_t K);
+int64_t smi_ivf_build_workspace_bytes(int64_t n, int64_t K, int32_t d);
+int smi_ivf_build(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_rows,
+                  int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets, int32_t* list_sizes, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+int64_t smi_ivf_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d);
+int smi_ivf_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                   const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
+                   void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

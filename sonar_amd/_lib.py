@@ -366,6 +366,12 @@ SYMBOLS = {
     "smi_kmeans_finalize": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp]),
     "smi_kmeans_fit": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                  _vp]),
+    "smi_ivf_list_align": (_i32, []),
+    "smi_ivf_slots_bound": (_i64, [_i64, _i64]),
+    "smi_ivf_build_workspace_bytes": (_i64, [_i64, _i64, _i32]),
+    "smi_ivf_build": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    "smi_ivf_search_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "smi_ivf_search": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "smi_gemm_tn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "smi_gemm_tn_tile_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "smi_gemm_tn_splitk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

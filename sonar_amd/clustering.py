@@ -6,9 +6,9 @@ centroids (the mining kernel, unchanged); the centroid update is `smi_kmeans_upd
 fp16 rows, so one seed gives one run bit for bit.  `smi_kmeans_fit` enqueues every round on the current stream and reads
 nothing back; the per-round record is copied to the host only when `history` is read.  There is no CPU path.
 
-Used for semantic de-duplication, as the coarse quantiser of an IVF index (`predict(x, k)` is the probe) and for codebooks
-over SONAR space.  Not here: Euclidean k-means, k-means++ initialisation, splitting of large clusters to refill empty ones
-(an empty cluster keeps its centroid), the index itself, multi-GPU.
+Used for semantic de-duplication, as the coarse quantiser of the IVF index (`sonar_amd.index.IVFFlatIndex`, DESIGN.md 3.18;
+`predict(x, k)` is its probe) and for codebooks over SONAR space.  Not here: Euclidean k-means, k-means++ initialisation,
+splitting of large clusters to refill empty ones (an empty cluster keeps its centroid), multi-GPU.
 """
 from __future__ import annotations
 

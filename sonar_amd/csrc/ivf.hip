@@ -1,0 +1,462 @@
+// IVF-Flat index over rows of smi_xsim_normalize: K inverted lists, list-contiguous copies of the rows, and
+// a scan that scores every query against the rows of the lists it probes only.  The coarse quantiser is spherical k-means
+// (kmeans.hip) and the probe is smi_xsim_topk against its centroids; both are callers' business, not this file's.
+//
+// Both halves bucket int32 keys with the three passes of the k-means update (histogram, exclusive scan, cursor scatter, all
+// wave-aggregated: wave_claim.hpp).  The build buckets the row numbers by label, the search buckets the nq * nprobe
+// (query, probe slot) pairs by list -- the inverted probe table -- so that a work unit of the scan is ONE list and up to
+// 64 or 128 of the pairs that probe it: the list's rows are read once per unit, not once per query.
+//
+// The scan unit walks its list in tiles of as many slots as it has pairs; a tile's scores are fp16 MFMA products
+// (v_mfma_f32_16x16x32_f16, fp32 accumulators, K slices ascending: the bits of a score depend on the two rows alone) that
+// are folded into one running top-k per pair, the LDS key lists of xsim.hip.  A pair's list is written to the partial
+// array [nprobe][nq][k]; smi_xsim_merge_topk's kernel merges the nprobe parts.  No atomics on results.
+#include "api_common.hpp"
+#include "common.hpp"
+#include "topk_order.hpp"
+#include "wave_claim.hpp"
+
+using namespace smi;
+using namespace smi_host;
+
+namespace smi {
+
+namespace {
+
+constexpr int IVF_TB = 256;    // threads per block of every kernel here
+constexpr int IVF_ALIGN = SMI_IVF_LIST_ALIGN;  // slots: one 16-row A block of the 16x16x32 MFMA
+constexpr int IVF_BM = SMI_IVF_UNIT_QUERIES;   // (query, probe slot) pairs of a scan unit = slots of its tiles ...
+constexpr int IVF_BIG = 2 * IVF_BM;            // ... or twice that, where the lists are probed by many pairs
+constexpr int IVF_BK = 64;     // fp16 of a K slice: 128 B of a row, two MFMA K steps
+constexpr int64_t IVF_MAX = 0x7fffff00LL;
+
+static_assert(IVF_ALIGN == 16, "a 16-slot A block of the scan's MFMA never spans two lists");
+static_assert(IVF_BM == 64 && IVF_TB == 256, "the slice loader maps 256 threads to 32 rows x 8 chunks, B / 32 times; 2 x 2 waves");
+
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+// ---------------------------------------------------------------- bucketing (the k-means pattern, for any int32 keys)
+__global__ __launch_bounds__(IVF_TB) void ivf_hist_kernel(const int32_t* __restrict__ keys, int n, int K,
+                                                          int32_t* __restrict__ counts) {
+  const int64_t i = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  const int c = i < n ? keys[i] : -1;
+  km_wave_claim(counts, c, km_label_ok(c, K), threadIdx.x & 63);
+}
+
+// off[c] = sum over c' < c of counts[c'] rounded up to `align`, off[K] = the total; cursor = a copy of off[0 .. K) for the
+// scatter to advance; ubase (nullable) [K + 1] = the same prefix sum of ceil(counts / unit).  One block, as km_scan_kernel.
+__global__ __launch_bounds__(IVF_TB) void ivf_scan_kernel(const int32_t* __restrict__ counts, int K, int align, int unit,
+                                                          int32_t* __restrict__ off, int32_t* __restrict__ cursor,
+                                                          int32_t* __restrict__ ubase) {
+  __shared__ int part[IVF_TB], upart[IVF_TB];
+  const int per = (K + IVF_TB - 1) / IVF_TB;
+  const int64_t lo64 = (int64_t)per * threadIdx.x;
+  const int lo = lo64 < K ? (int)lo64 : K, hi = lo64 + per < K ? (int)(lo64 + per) : K;
+  int sum = 0, usum = 0;
+  for (int i = lo; i < hi; ++i) {
+    const int c = counts[i];
+    sum += (c + align - 1) / align * align;
+    usum += (c + unit - 1) / unit;
+  }
+  part[threadIdx.x] = sum;
+  upart[threadIdx.x] = usum;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int run = 0, urun = 0;
+    for (int i = 0; i < IVF_TB; ++i) {
+      const int p = part[i], u = upart[i];
+      part[i] = run;
+      upart[i] = urun;
+      run += p;
+      urun += u;
+    }
+    off[K] = run;
+    if (ubase) ubase[K] = urun;
+  }
+  __syncthreads();
+  int run = part[threadIdx.x], urun = upart[threadIdx.x];
+  for (int i = lo; i < hi; ++i) {
+    const int c = counts[i];
+    off[i] = run;
+    cursor[i] = run;
+    if (ubase) ubase[i] = urun;
+    run += (c + align - 1) / align * align;
+    urun += (c + unit - 1) / unit;
+  }
+}
+
+// out[p] = i for every i with a key in [0, K), the i of one key at consecutive p from that key's offset on.  Which i lands
+// where inside its run depends on the atomics' arrival order.
+__global__ __launch_bounds__(IVF_TB) void ivf_scatter_kernel(const int32_t* __restrict__ keys, int n, int K,
+                                                             int32_t* __restrict__ cursor, int32_t* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  const int c = i < n ? keys[i] : -1;
+  const bool ok = km_label_ok(c, K);
+  const int pos = km_wave_claim(cursor, c, ok, threadIdx.x & 63);
+  if (ok) out[pos] = (int32_t)i;  // pos < off[c + 1]: the histogram counted this key with the same test
+}
+
+// ---------------------------------------------------------------- build: the row copies
+// One wave per slot below off[K]: the row ids[slot] names, or zeros for a pad slot (id -1).  16 bytes per lane per access.
+__global__ __launch_bounds__(IVF_TB) void ivf_gather_kernel(const f16* __restrict__ xn, int d, const int32_t* __restrict__ ids,
+                                                            const int32_t* __restrict__ off, int K, f16* __restrict__ rows) {
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = (int64_t)blockIdx.x * (IVF_TB / 64) + (threadIdx.x >> 6);
+  if (slot >= off[K]) return;  // wave-uniform
+  const int id = ids[slot];
+  u32x4* o = (u32x4*)(rows + (size_t)slot * d);
+  if (id < 0) {
+    for (int c = lane; c < d / 8; c += 64) o[c] = u32x4{0u, 0u, 0u, 0u};
+  } else {
+    const u32x4* s = (const u32x4*)(xn + (size_t)id * d);
+    for (int c = lane; c < d / 8; c += 64) o[c] = s[c];
+  }
+}
+
+// ---------------------------------------------------------------- search
+// every partial list starts as k x (-inf, -1): what a probe slot that names no list contributes
+__global__ __launch_bounds__(IVF_TB) void ivf_fill_kernel(float* __restrict__ ps, int32_t* __restrict__ pi, int64_t m) {
+  const int64_t i = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  if (i < m) {
+    ps[i] = -INFINITY;
+    pi[i] = -1;
+  }
+}
+
+// Workgroup b = unit b - ubase[l] of the list l with ubase[l] <= b < ubase[l + 1]: pairs poff[l] + B * that .. of the
+// bucketed pair order against the slots off[l] .. off[l + 1].  A unit is B pairs and walks the list in tiles of B slots,
+// B = 64 or 128 (chosen by the host from the shapes alone; the bits of a score do not depend on it).
+//   Why the tile is as large as it is: every K slice of a tile is read from L2 (the list rows are shared by the units of the
+//   list, the query rows are re-read for every tile), 2 * B * 128 bytes for B * B * 128 flop -- B / 2 flop per byte: at
+//   B = 64 the scan ran at the L2's ~10 TB/s and 0.13 of the MFMA peak (profiles/ivf_experiments.txt, item 1).
+//   LDS: two K-slice buffers {pairs' query rows [B][128 B], tile's list rows [B][128 B]} (the 16-B chunk c of row r sits at
+//   chunk c ^ (r & 7): the fragment reads of 16 consecutive rows spread over all banks), the key lists [B][KT], the pair
+//   numbers [B].  Thread t loads chunk t & 7 of rows (t >> 3) + 32 j of both operands for slice i + 1 into registers
+//   while the MFMAs of slice i run, and stores them to the other buffer behind them: one barrier per slice.
+//   Wave (wr, wc) owns slots wr * B / 2 .. of the tile (the A operand: rows of D) against pairs wc * B / 2 .. (B: columns
+//   of D), so lane (l15, kg) holds pair wc * B / 2 + bi * 16 + l15 x slots wr * B / 2 + ai * 16 + 4 kg + r.
+template <int B>
+constexpr int ivf_scan_lds(int KT) { return 2 * 2 * B * IVF_BK * 2 + B * KT * 8 + B * 4; }
+
+template <int KT, int B>
+__global__ __launch_bounds__(IVF_TB) void ivf_scan_lists_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
+                                                                const f16* __restrict__ rows, const int32_t* __restrict__ ids,
+                                                                const int32_t* __restrict__ off, int K,
+                                                                const int32_t* __restrict__ poff,
+                                                                const int32_t* __restrict__ ubase,
+                                                                const int32_t* __restrict__ pairs, int k_out,
+                                                                float* __restrict__ ps, int32_t* __restrict__ pi) {
+  constexpr int OPB = B * IVF_BK * 2;  // bytes of one operand's K slice
+  constexpr int NR = B / 32;           // rows of an operand slice a thread loads; 16-row blocks of a wave per operand
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* lists = (unsigned long long*)(smem + 4 * OPB);
+  int* spair = (int*)(smem + 4 * OPB + B * KT * 8);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
+  const int b = blockIdx.x;
+  if (b >= ubase[K]) return;
+  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ubase[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const int l = lo;
+  const int p0 = poff[l] + (b - ubase[l]) * B;
+  const int npair = min(B, poff[l + 1] - p0);
+  const int s_begin = off[l], s_end = off[l + 1];
+
+  if (tid < B) {
+    spair[tid] = tid < npair ? pairs[p0 + tid] : -1;
+#pragma unroll
+    for (int j = 0; j < KT; ++j) lists[tid * KT + j] = XS_EMPTY;
+  }
+  __syncthreads();
+
+  const int nk = d / IVF_BK;
+  const int ntiles = (s_end - s_begin + B - 1) / B;
+  const int T = ntiles * nk;
+
+  // this thread's rows of a slice, and where its chunk lands in LDS
+  const int cc = tid & 7;
+  const f16* qsrc[NR];
+  int lds_off[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int r = (tid >> 3) + 32 * j;
+    const int pr = spair[r];
+    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
+    lds_off[j] = r * (IVF_BK * 2) + ((cc ^ (r & 7)) << 4);
+  }
+  u32x4 qv[NR], lv[NR];
+  auto load = [&](int it) {
+    const int tile = it / nk, ks = it - tile * nk;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
+      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
+      lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  auto store = [&](int buf) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      *(u32x4*)(smem + buf * 2 * OPB + lds_off[j]) = qv[j];
+      *(u32x4*)(smem + buf * 2 * OPB + OPB + lds_off[j]) = lv[j];
+    }
+  };
+
+  f32x4 acc[NR][NR];  // [slot block ai][pair block bi]
+#pragma unroll
+  for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+    for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // 16-pair blocks of this wave that hold a pair at all (wave-uniform)
+  const int nb_live = min(NR, max(0, (npair - wc * (B / 2) + 15) / 16));
+
+  if (T > 0) {
+    load(0);
+    store(0);
+  }
+  __syncthreads();
+  int ks = 0, tile = 0;
+  for (int it = 0; it < T; ++it) {
+    const int buf = it & 1;
+    if (it + 1 < T) load(it + 1);
+    // 16-slot blocks of this wave below the end of the list (the lists are padded to 16 slots): wave-uniform
+    const int slot_w = s_begin + tile * B + wr * (B / 2);
+    const int na_live = min(NR, max(0, (s_end - slot_w) / 16));
+    if (na_live > 0 && nb_live > 0) {
+      const char* qs = smem + buf * 2 * OPB;
+      const char* ls = qs + OPB;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int ch = kk * 4 + kg;
+        half8 fa[NR], fb[NR];
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai) {
+          const int ra = wr * (B / 2) + ai * 16 + l15;
+          fa[ai] = *(const half8*)(ls + ra * (IVF_BK * 2) + ((ch ^ (ra & 7)) << 4));
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) {
+          const int rb = wc * (B / 2) + bi * 16 + l15;
+          fb[bi] = *(const half8*)(qs + rb * (IVF_BK * 2) + ((ch ^ (rb & 7)) << 4));
+        }
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai)
+          if (ai < na_live) {
+#pragma unroll
+            for (int bi = 0; bi < NR; ++bi)
+              if (bi < nb_live) acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[ai], fb[bi], acc[ai][bi], 0, 0, 0);
+          }
+      }
+    }
+    if (it + 1 < T) store(buf ^ 1);
+    if (++ks == nk) {
+      // the tile is finished: fold this wave's scores into the pairs' lists.  A candidate must beat the pair's current
+      // k-th key's score or tie it (the id decides then); a stale threshold is a valid lower bound.
+#pragma unroll
+      for (int ai = 0; ai < NR; ++ai) {
+        if (ai < na_live) {
+          const int slot0 = slot_w + ai * 16 + 4 * kg;  // < s_end, 16-byte aligned: off % 16 == 0
+          const int4 id4 = *(const int4*)(ids + slot0);
+          const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
+#pragma unroll
+          for (int bi = 0; bi < NR; ++bi) {
+            const int pr = wc * (B / 2) + bi * 16 + l15;
+            if (pr < npair) {
+              unsigned long long* lst = lists + pr * KT;
+              const float thr = xs_unord(
+                  (uint32_t)(__hip_atomic_load(lst + KT - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32));
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (idr[r] >= 0 && acc[ai][bi][r] >= thr) xs_insert<KT>(lst, acc[ai][bi][r], idr[r]);
+            }
+          }
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      ks = 0;
+      ++tile;
+    }
+    __syncthreads();
+  }
+
+  // (the last barrier of the loop, or the one before it when the list is empty, made the lists final)
+  if (tid < npair) {
+    const int pr = spair[tid];
+    const int q = pr / nprobe, p = pr - q * nprobe;
+    const size_t o = ((size_t)p * nq + q) * k_out;
+    for (int j = 0; j < k_out; ++j) {
+      const unsigned long long key = lists[tid * KT + j];
+      const bool have = key != XS_EMPTY;
+      ps[o + j] = have ? xs_unord((uint32_t)(key >> 32)) : -INFINITY;
+      pi[o + j] = have ? (int)(0xffffffffu - (uint32_t)key) : -1;
+    }
+  }
+}
+
+size_t up16(size_t b) { return (b + 15) / 16 * 16; }
+
+int64_t slots_bound(int64_t n, int64_t K) {
+  const int64_t m = std::min(n, K);
+  return m * IVF_ALIGN + (n - m) / IVF_ALIGN * IVF_ALIGN;
+}
+bool build_shape_ok(int64_t n, int64_t K, int32_t d) {
+  return n >= 1 && K >= 1 && d > 0 && d % 64 == 0 && n <= IVF_MAX && K <= IVF_MAX && slots_bound(n, K) <= IVF_MAX;
+}
+bool search_shape_ok(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
+  return nq >= 1 && K >= 1 && d > 0 && d % 64 == 0 && nprobe >= 1 && nprobe <= 8 && k >= 1 && k <= 8 && nq <= IVF_MAX &&
+         K <= IVF_MAX && nq * nprobe <= IVF_MAX;
+}
+// pairs of a scan unit = slots of its tiles: 128 where the lists are probed by 256 pairs or more on average, else 64.  (At
+// 128 pairs per list of ~61 rows, 1 M rows over 16 384 lists at nprobe = 8, the 128-slot tile is half empty and the scan took
+// 1.84 ms against 1.34; at 256 pairs per list of ~977 rows it took 1.45 ms against 2.53: profiles/ivf_experiments.txt.)
+int unit_pairs(int64_t pairs, int64_t K) { return pairs >= 2 * (int64_t)IVF_BIG * K ? IVF_BIG : IVF_BM; }
+// the scan's grid: a list with pairs has at most floor(pairs / unit) + 1 units
+int64_t units_bound(int64_t pairs, int64_t K, int unit) { return pairs / unit + std::min(pairs, K); }
+
+// build: cursor int32 [K]
+size_t build_bytes(int64_t K) { return up16((size_t)K * 4); }
+// search: pair counts [K] | pair offsets [K + 1] | unit offsets [K + 1] | cursor [K] | bucketed pairs [nq * nprobe] |
+//         partial scores fp32 [nprobe][nq][k] | partial ids int32 [nprobe][nq][k]
+size_t search_bytes(int64_t nq, int64_t K, int nprobe, int k) {
+  return 2 * up16((size_t)K * 4) + 2 * up16((size_t)(K + 1) * 4) + up16((size_t)nq * nprobe * 4) +
+         2 * up16((size_t)nq * nprobe * k * 4);
+}
+
+int check_shape(int64_t n, const char* n_name, int32_t d, int64_t K) {
+  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
+  if (K < 1) return fail(SMI_ERR_INVALID_ARG, "K=%lld: at least one list", (long long)K);
+  if (n < 1) return fail(SMI_ERR_INVALID_ARG, "%s=%lld: empty input", n_name, (long long)n);
+  if (n > IVF_MAX || K > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "%s=%lld, K=%lld: row and list numbers must fit int32", n_name, (long long)n, (long long)K);
+  return SMI_OK;
+}
+
+int check_ws(const void* ws, int64_t ws_bytes, int64_t need, const char* formula) {
+  if (!ws) return fail(SMI_ERR_INVALID_ARG, "null workspace");
+  if ((uintptr_t)ws % 16) return fail(SMI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  if (ws_bytes < need)
+    return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, %s = %lld", (long long)ws_bytes, formula, (long long)need);
+  return SMI_OK;
+}
+
+dim3 grid_for(int64_t items, int per_block) { return dim3((unsigned)((items + per_block - 1) / per_block)); }
+
+template <int KT>
+hipError_t launch_scan(int unit, int64_t units, hipStream_t st, const f16* qn, int d, int nq, int nprobe, const f16* rows,
+                       const int32_t* ids, const int32_t* off, int K, const int32_t* poff, const int32_t* ubase,
+                       const int32_t* pairs, int k, float* ps, int32_t* pi) {
+  if (unit == IVF_BIG)
+    return launch_with_lds<ivf_scan_lists_kernel<KT, IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BIG>(KT), st, qn,
+                                                               d, nq, nprobe, rows, ids, off, K, poff, ubase, pairs, k, ps, pi);
+  return launch_with_lds<ivf_scan_lists_kernel<KT, IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BM>(KT), st, qn, d,
+                                                            nq, nprobe, rows, ids, off, K, poff, ubase, pairs, k, ps, pi);
+}
+
+}  // namespace
+
+}  // namespace smi
+
+extern "C" {
+
+int32_t smi_ivf_list_align(void) { return IVF_ALIGN; }
+
+int64_t smi_ivf_slots_bound(int64_t n, int64_t K) {
+  if (n < 1 || K < 1 || n > IVF_MAX || K > IVF_MAX || slots_bound(n, K) > IVF_MAX) return 0;
+  return slots_bound(n, K);
+}
+
+int64_t smi_ivf_build_workspace_bytes(int64_t n, int64_t K, int32_t d) {
+  return build_shape_ok(n, K, d) ? (int64_t)build_bytes(K) : 0;
+}
+
+int smi_ivf_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_rows, int32_t* list_ids,
+                  int64_t capacity_slots, int32_t* list_offsets, int32_t* list_sizes, void* ws, int64_t ws_bytes,
+                  void* stream) {
+  if (!xn || !labels || !list_rows || !list_ids || !list_offsets || !list_sizes)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, "n", d, K)) return rc;
+  const int64_t bound = slots_bound(n, K);
+  if (bound > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "n=%lld rows over K=%lld lists can need %lld slots: slot numbers must fit int32",
+                (long long)n, (long long)K, (long long)bound);
+  if (capacity_slots < bound)
+    return fail(SMI_ERR_INVALID_ARG, "capacity of %lld slots, smi_ivf_slots_bound(n, K) = %lld", (long long)capacity_slots,
+                (long long)bound);
+  if (const int rc = check_ws(ws, ws_bytes, (int64_t)build_bytes(K), "smi_ivf_build_workspace_bytes(n, K, d)")) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  int32_t* cursor = (int32_t*)ws;
+  HIP_TRY(hipMemsetAsync(list_sizes, 0, (size_t)K * 4, st));
+  HIP_TRY(hipMemsetAsync(list_ids, 0xff, (size_t)capacity_slots * 4, st));  // -1: pad slots and the unused tail
+  const dim3 block(IVF_TB), rows_grid = grid_for(n, IVF_TB);
+  hipLaunchKernelGGL(ivf_hist_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, list_sizes);
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, list_sizes, (int)K, IVF_ALIGN, 1, list_offsets, cursor,
+                     (int32_t*)nullptr);
+  hipLaunchKernelGGL(ivf_scatter_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, cursor, list_ids);
+  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
+  hipLaunchKernelGGL(ivf_gather_kernel, grid_for(bound, IVF_TB / 64), block, 0, st, (const f16*)xn, d, list_ids, list_offsets,
+                     (int)K, (f16*)list_rows);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int64_t smi_ivf_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
+  return search_shape_ok(nq, K, nprobe, k, d) ? (int64_t)search_bytes(nq, K, nprobe, k) : 0;
+}
+
+int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                   const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
+                   void* ws, int64_t ws_bytes, void* stream) {
+  if (!qn || !probes || !list_rows || !list_ids || !list_offsets || !idx || !score)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(nq, "nq", d, K)) return rc;
+  if (k < 1 || k > 8) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, 8]", k);
+  if (nprobe < 1 || nprobe > 8) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 8]", nprobe);
+  const int64_t P = nq * nprobe;
+  if (P > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)P);
+  if (const int rc = check_ws(ws, ws_bytes, (int64_t)search_bytes(nq, K, nprobe, k),
+                              "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)"))
+    return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  char* p = (char*)ws;
+  int32_t* pcount = (int32_t*)p;
+  p += up16((size_t)K * 4);
+  int32_t* poff = (int32_t*)p;
+  p += up16((size_t)(K + 1) * 4);
+  int32_t* ubase = (int32_t*)p;
+  p += up16((size_t)(K + 1) * 4);
+  int32_t* cursor = (int32_t*)p;
+  p += up16((size_t)K * 4);
+  int32_t* pairs = (int32_t*)p;
+  p += up16((size_t)P * 4);
+  float* ps = (float*)p;
+  p += up16((size_t)P * k * 4);
+  int32_t* pi = (int32_t*)p;
+
+  // invert the probe table: the (query, probe slot) pairs q * nprobe + p bucketed by the list they name
+  HIP_TRY(hipMemsetAsync(pcount, 0, (size_t)K * 4, st));
+  const dim3 block(IVF_TB), pair_grid = grid_for(P, IVF_TB);
+  hipLaunchKernelGGL(ivf_hist_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, pcount);
+  const int unit = unit_pairs(P, K);
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, pcount, (int)K, 1, unit, poff, cursor, ubase);
+  hipLaunchKernelGGL(ivf_scatter_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, cursor, pairs);
+  hipLaunchKernelGGL(ivf_fill_kernel, grid_for(P * k, IVF_TB), block, 0, st, ps, pi, P * k);
+  HIP_TRY(hipGetLastError());
+  // units for every pair count the table can have: those from ubase[K] on find nothing to do
+  const int64_t units = units_bound(P, K, unit);
+  const f16* q16 = (const f16*)qn;
+  const f16* r16 = (const f16*)list_rows;
+  const int KT = k == 1 ? 1 : k == 2 ? 2 : k <= 4 ? 4 : 8;
+  auto scan = KT == 1 ? launch_scan<1> : KT == 2 ? launch_scan<2> : KT == 4 ? launch_scan<4> : launch_scan<8>;
+  HIP_TRY(scan(unit, units, st, q16, d, (int)nq, nprobe, r16, list_ids, list_offsets, (int)K, poff, ubase, pairs, k, ps, pi));
+  HIP_TRY(launch_topk_merge(ps, pi, nprobe, nq, k, score, idx, st));
+  return SMI_OK;
+}
+
+}  // extern "C"

@@ -17,14 +17,9 @@
 #include "gemm_tile.hpp"
 #include "gemm_tile256.hpp"
 #include "kernels.hpp"
+#include "topk_order.hpp"
 
 namespace smi {
-
-// total order: higher score first, ties -> lower index first (deterministic
-// regardless of the order candidates are met).
-__device__ __forceinline__ bool better(float s, int i, float s2, int i2) {
-  return s > s2 || (s == s2 && i < i2);
-}
 
 template <int K>
 struct TopK {
@@ -115,24 +110,6 @@ __device__ unsigned long long xs_trace_buf[256 * 2 * 4];
 //    maximum of four waves' private K-th bests: no shuffles, no publish step, fewer false passes;
 //  * the walk ends with the lists final: no cross-lane / cross-wave merge.
 // Insertions are rare after the first tiles (~K ln(n / K) per row over a chunk of n rows); they take the slow path.
-constexpr unsigned long long XS_EMPTY = (0x007fffffull << 32) | 0x80000000ull;  // (-inf, index 0x7fffffff)
-__device__ __forceinline__ uint32_t xs_ord(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float xs_unord(uint32_t o) {
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
-template <int K>
-__device__ __forceinline__ void xs_insert(unsigned long long* list, float v, int n) {
-  unsigned long long key = ((unsigned long long)xs_ord(v) << 32) | (uint32_t)(0xffffffffu - (uint32_t)n);
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    const unsigned long long old = __hip_atomic_fetch_max(list + j, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    key = old < key ? old : key;
-    if (key == XS_EMPTY) break;
-  }
-}
 // the 8 row thresholds of a lane (rows wr * 128 + mi * 16 + l15): score word of the last key of each list.  Inline asm, issue
 // and wait in ONE statement: as C++ loads every one of them would get `s_waitcnt vmcnt(0)` from hipcc's LDS-DMA alias tracking
 // (the operand slices of the next tile are in flight) -- gemm.hip, round-3 findings.  A stale value is a valid lower bound.

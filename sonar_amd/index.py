@@ -1,0 +1,282 @@
+"""IVF-Flat index over sentence embeddings on the MI355X engine.
+
+Brute-force `xsim.topk` scores every query against every row.  An inverted-file index scores a query against the rows of the
+`nprobe` nearest of K clusters only, about nprobe / K of the work, which is what repeated search of one corpus (LASER-style
+mining, semantic de-duplication) wants.  The coarse quantiser is `clustering.SphericalKMeans`; the probe is `xsim.topk`
+against its centroids (the mining kernel, unchanged); the lists are fp16 copies of the normalised rows, uncompressed
+("flat"), so a returned score is the cosine `xsim.topk` would return, within the rounding of one fp32 accumulation.
+
+`search` returns what `xsim.topk` returns -- (scores fp32 [nq, k], ids int32 [nq, k]), best first, score descending and
+ties to the lower row number, (-inf, -1) where the probed lists hold fewer than k rows -- so `xsim.margin_select` and
+`mining` consume it unchanged.  Its bits do not depend on the company of a query, on the order of the corpus or on the run.
+There is no CPU path.
+
+Not here: product or scalar quantisation of the stored rows, nprobe or k above 8, incremental add and
+removal, 64-bit ids, splitting of long lists, multi-GPU sharding.
+"""
+from __future__ import annotations
+
+from typing import Dict, Optional, Tuple, Union
+
+import torch
+
+from . import _lib
+from .clustering import SphericalKMeans
+from .xsim import normalize_rows, topk_normalized
+
+LIST_ALIGN = 16    # SMI_IVF_LIST_ALIGN: every list starts at a multiple of this many slots and is padded to it
+UNIT_QUERIES = 64  # SMI_IVF_UNIT_QUERIES: queries of one list that one work unit of the scan takes (128 when nq nprobe >= 256 K)
+
+
+def _check_matrix(t, name: str) -> None:
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: the index runs on a HIP device only (no CPU path); move the embeddings to cuda")
+    if t.dim() != 2:
+        raise ValueError(f"{name} must be [rows, dim], got {t.dim()} dimension(s)")
+    if t.shape[0] < 1:
+        raise ValueError(f"{name} is empty")
+    if t.shape[1] % 64:
+        raise ValueError(f"{name}: dim = {t.shape[1]} must be a multiple of 64")
+
+
+def _check_table(t, name: str, rows: int, cols: Optional[int]) -> None:
+    """A device int32 vector [rows] (cols None) or matrix [rows, cols]."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name}: the index runs on a HIP device only (no CPU path)")
+    shape = (rows,) if cols is None else (rows, cols)
+    if t.dtype != torch.int32 or tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be int32 {list(shape)}, got {t.dtype} {list(t.shape)}")
+
+
+def _check_small(v, name: str) -> None:
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 8:
+        raise ValueError(f"{name} = {v!r}: an integer in [1, 8]")
+
+
+def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
+    """smi_ivf_build: the inverted lists of the first len(labels) rows of xn (contiguous fp16 [>= n, d]) under labels (device
+    int32 [n]; a label outside [0, n_lists) leaves the row out).  Returns (rows fp16 [slots, d], ids int32 [slots], offsets
+    int32 [n_lists + 1], sizes int32 [n_lists]) with slots = smi_ivf_slots_bound(n, n_lists): the host has not seen the
+    labels, so the storage is sized for any labelling.  Slots from offsets[n_lists] on are unused (ids -1, rows unwritten)."""
+    _check_matrix(xn, "xn")
+    if xn.dtype != torch.float16 or not xn.is_contiguous():
+        raise ValueError("xn must be a contiguous fp16 matrix")
+    if isinstance(n_lists, bool) or not isinstance(n_lists, int) or n_lists < 1:
+        raise ValueError(f"n_lists = {n_lists!r}: at least one list")
+    if isinstance(labels, torch.Tensor) and labels.dim() == 1 and not 1 <= labels.shape[0] <= xn.shape[0]:
+        raise ValueError(f"{labels.shape[0]} labels for {xn.shape[0]} rows")
+    _check_table(labels, "labels", labels.shape[0] if isinstance(labels, torch.Tensor) and labels.dim() == 1 else -1, None)
+    lib = _lib.load()
+    n, d, dev = labels.shape[0], xn.shape[1], xn.device
+    cap = int(lib.smi_ivf_slots_bound(n, n_lists))
+    if cap < 1:
+        raise ValueError(f"{n} rows over {n_lists} lists: slot numbers must fit int32")
+    rows = torch.empty((cap, d), dtype=torch.float16, device=dev)
+    ids = torch.empty((cap,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((n_lists + 1,), dtype=torch.int32, device=dev)
+    sizes = torch.empty((n_lists,), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.smi_ivf_build_workspace_bytes(n, n_lists, d))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    labels = labels.contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(lib.smi_ivf_build(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, rows.data_ptr(), ids.data_ptr(), cap,
+                                     offsets.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws_bytes,
+                                     _lib.current_stream_ptr()))
+    return rows, ids, offsets, sizes
+
+
+def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
+                 k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_search: the k best rows of the lists probes (device int32 [nq, 1..8]) names, for the first nq rows of qn
+    (contiguous fp16 [>= nq, d]) against the storage `build_lists` returned: (scores fp32 [nq, k], ids int32 [nq, k])."""
+    _check_small(k, "k")
+    _check_matrix(qn, "qn")
+    if qn.dtype != torch.float16 or not qn.is_contiguous():
+        raise ValueError("qn must be a contiguous fp16 matrix")
+    if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= 8
+                                             or not 1 <= probes.shape[0] <= qn.shape[0]):
+        raise ValueError(f"probes must be [nq, 1..8] with nq <= {qn.shape[0]} rows, got {list(probes.shape)}")
+    _check_table(probes, "probes", *(probes.shape if isinstance(probes, torch.Tensor) else (-1, 1)))
+    lib = _lib.load()
+    (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
+    if rows.shape[1] != d:
+        raise ValueError(f"qn has dim {d}, the lists {rows.shape[1]}")
+    ws_bytes = int(lib.smi_ivf_search_workspace_bytes(nq, n_lists, nprobe, k, d))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
+    score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
+    probes = probes.contiguous()
+    with torch.cuda.device(qn.device):
+        _lib.check(lib.smi_ivf_search(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, rows.data_ptr(), ids.data_ptr(),
+                                      offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(),
+                                      ws_bytes, _lib.current_stream_ptr()))
+    return score, idx
+
+
+class IVFFlatIndex:
+    """train / add / search; see the module text.
+
+    quantizer: a fitted `SphericalKMeans`, or an [K, d] tensor of centroids (normalised with `normalize_rows`)."""
+
+    def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor]):
+        if isinstance(quantizer, SphericalKMeans):
+            c16 = quantizer.centroids_normalized  # raises before fit
+            self._c16 = quantizer._c16.clone()  # a later step() of the quantiser must not move the lists' centroids
+            self._k, self._d = quantizer.n_clusters, c16.shape[1]
+        else:
+            _check_matrix(quantizer, "quantizer")
+            self._k, self._d = quantizer.shape
+            self._c16 = normalize_rows(quantizer)
+        self._added = False
+
+    @classmethod
+    def train(cls, x: torch.Tensor, n_lists: int, n_iter: int = 10, seed: int = 0) -> "IVFFlatIndex":
+        """Fit the coarse quantiser: spherical k-means with `n_lists` clusters on x (fp16 / fp32 [n, d] on the device)."""
+        return cls(SphericalKMeans(n_lists, n_iter=n_iter, seed=seed).fit(x))
+
+    # ------------------------------------------------------------------------------------------------ properties
+    @property
+    def n_lists(self) -> int:
+        return self._k
+
+    @property
+    def dim(self) -> int:
+        return self._d
+
+    @property
+    def centroids_normalized(self) -> torch.Tensor:
+        return self._c16[: self._k]
+
+    def _need_add(self, what: str) -> None:
+        if not self._added:
+            raise RuntimeError(f"{what} before add: the index holds no rows yet")
+
+    @property
+    def list_sizes(self) -> torch.Tensor:
+        """int32 [K] on the device: the rows of every list."""
+        self._need_add("list_sizes")
+        return self._sizes
+
+    @property
+    def list_offsets(self) -> torch.Tensor:
+        """int32 [K + 1] on the device: list c is the slots [offsets[c], offsets[c + 1]); offsets[K] = the slots in use."""
+        self._need_add("list_offsets")
+        return self._offsets
+
+    @property
+    def ntotal(self) -> int:
+        """The rows in the index (those whose label named a list).  Reads the list sizes back."""
+        self._need_add("ntotal")
+        return int(self._sizes.sum().item())
+
+    # ------------------------------------------------------------------------------------------------ add
+    def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None) -> "IVFFlatIndex":
+        """Index the rows of x (fp16 / fp32 [n, d] on the device); ids are the row numbers.  Once per index.
+
+        labels: None (the nearest centroid, the quantiser's top-1) or device int32 [n]; a label outside [0, K) leaves the
+        row out.  Enqueued on the current stream with no read-back: instead of one synchronisation to size the storage from
+        the list counts, the storage is sized for any labelling, `smi_ivf_slots_bound(n, K)` slots, at most
+        (LIST_ALIGN - 1) * min(n, K) more than n; `state_dict` cuts it to the slots in use."""
+        if self._added:
+            raise RuntimeError("add was already called: this index is built once (no incremental add)")
+        _check_matrix(x, "x")
+        if x.shape[1] != self._d:
+            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+        n = x.shape[0]
+        if labels is not None:
+            _check_table(labels, "labels", n, None)
+        xn = normalize_rows(x)
+        if labels is None:
+            labels = topk_normalized(xn, n, self._c16, self._k, 1)[1][:, 0]
+        self._rows, self._ids, self._offsets, self._sizes = build_lists(xn, labels, self._k)
+        self._added = True
+        return self
+
+    # ------------------------------------------------------------------------------------------------ search
+    def probe(self, q: torch.Tensor, nprobe: int = 1) -> torch.Tensor:
+        """int32 [nq, nprobe]: the nprobe nearest lists of every query, nearest first."""
+        _check_small(nprobe, "nprobe")
+        _check_matrix(q, "q")
+        if q.shape[1] != self._d:
+            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
+        return self._probe(normalize_rows(q), q.shape[0], nprobe)
+
+    def _probe(self, qn: torch.Tensor, nq: int, nprobe: int) -> torch.Tensor:
+        if nprobe > self._k:
+            raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
+        return topk_normalized(qn, nq, self._c16, self._k, nprobe)[1]
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1,
+               probes: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The k best rows of the probed lists for every row of q (fp16 / fp32 [nq, d] on the device): (scores fp32
+        [nq, k], ids int32 [nq, k]), the layout and order of `xsim.topk`.
+
+        probes: None (the nprobe nearest lists by the quantiser) or device int32 [nq, 1..8]; an entry outside [0, K) names
+        no list.  A row of probes that names a list twice may return that list's rows twice."""
+        _check_small(k, "k")
+        _check_small(nprobe, "nprobe")
+        self._need_add("search")
+        _check_matrix(q, "q")
+        if q.shape[1] != self._d:
+            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
+        nq = q.shape[0]
+        if probes is not None:
+            if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= 8):
+                raise ValueError(f"probes must be [nq, 1..8], got {list(probes.shape)}")
+            _check_table(probes, "probes", nq, probes.shape[1] if isinstance(probes, torch.Tensor) else 1)
+        elif nprobe > self._k:
+            raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
+        qn = normalize_rows(q)
+        if probes is None:
+            probes = self._probe(qn, nq, nprobe)
+        return search_lists(qn, probes, self._rows, self._ids, self._offsets, k)
+
+    # ------------------------------------------------------------------------------------------------ persistence
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """centroids (fp16 [K, d], normalised), offsets, sizes, ids and rows; the storage is cut to the slots in use (one
+        read-back)."""
+        self._need_add("state_dict")
+        used = int(self._offsets[self._k].item())
+        return {"centroids": self._c16[: self._k].clone(), "offsets": self._offsets.clone(), "sizes": self._sizes.clone(),
+                "ids": self._ids[:used].clone(), "rows": self._rows[:used].clone()}
+
+    @classmethod
+    def from_state_dict(cls, state: Dict[str, torch.Tensor]) -> "IVFFlatIndex":
+        index = cls.__new__(cls)
+        index._added = False
+        index.load_state_dict(state, _fresh=True)
+        return index
+
+    def load_state_dict(self, state: Dict[str, torch.Tensor], _fresh: bool = False) -> "IVFFlatIndex":
+        """Take over a `state_dict()` (tensors on the device).  The centroids must have this index's shape."""
+        missing = {"centroids", "offsets", "sizes", "ids", "rows"} - set(state)
+        if missing:
+            raise ValueError(f"state lacks {sorted(missing)}")
+        c = state["centroids"]
+        _check_matrix(c, "centroids")
+        k, d = c.shape
+        if not _fresh and (k, d) != (self._k, self._d):
+            raise ValueError(f"centroids are [{k}, {d}], this index has [{self._k}, {self._d}]")
+        if c.dtype != torch.float16:
+            raise ValueError("centroids must be the fp16 rows state_dict returns")
+        _check_table(state["offsets"], "offsets", k + 1, None)
+        _check_table(state["sizes"], "sizes", k, None)
+        rows, ids = state["rows"], state["ids"]
+        _check_table(ids, "ids", rows.shape[0] if isinstance(rows, torch.Tensor) else -1, None)
+        if not rows.is_cuda or rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != d:
+            raise ValueError(f"rows must be fp16 [slots, {d}] on the device")
+        used = int(state["offsets"][k].item())
+        if used != rows.shape[0] or used % LIST_ALIGN:
+            raise ValueError(f"offsets end at slot {used}, rows has {rows.shape[0]} (a multiple of {LIST_ALIGN} is expected)")
+        self._k, self._d = k, d
+        pad = (k + 255) // 256 * 256
+        self._c16 = torch.zeros((pad, d), dtype=torch.float16, device=c.device)
+        self._c16[:k] = c
+        self._offsets, self._sizes = state["offsets"].contiguous().clone(), state["sizes"].contiguous().clone()
+        self._ids, self._rows = ids.contiguous().clone(), rows.contiguous().clone()
+        self._added = True
+        return self
