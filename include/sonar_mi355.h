@@ -754,6 +754,43 @@ int smi_ivf_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* pro
                    const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* IVF index with int8 scalar-quantised rows (restated in tests/ivf_i8_ref.py).  The lists of smi_ivf_build
+ * with one signed byte per element and one fp32 scale per row, half the bytes of the fp16 copies, scanned with an integer
+ * MFMA (v_mfma_i32_16x16x64_i8) whose int32 sums are exact, so a score is specified down to its bits for ANY data.
+ *
+ * Encoding of one fp16 row x of length d (per-row symmetric; non-finite elements are outside the contract):
+ *   amax = max_j |x_j|;  inv = 127.0f / amax and scale = amax / 127.0f, both correctly rounded fp32 divisions;
+ *   code_j = clamp(rint(fl32(x_j * inv)), -127, 127), ties to even.  A zero row has all codes 0 and scale 0.
+ * Score of a query row (cq, scale_q) against a stored row (cx, scale_x):
+ *   acc = sum_j cq_j * cx_j in int32 (exact: |acc| <= 127^2 d);  score = fl32(fl32((float)acc * scale_x) * scale_q), an
+ *   int -> fp32 conversion to nearest even and two fp32 multiplies in that order.  Its bits depend on the two fp16 rows
+ *   alone: not on the list, the slot, the tile shape, the unit size, the other queries of the call or the run.
+ * smi_ivf_i8_encode: codes int8 [n, d] and scales fp32 [n] of the first n rows of xn (fp16 [>= n, d]).  The row quantiser on
+ *   its own; smi_ivf_i8_build and smi_ivf_i8_search (for the queries) call the same device function.
+ * Storage: smi_ivf_build's layout with list_codes int8 [capacity_slots, d] in place of list_rows and a new list_scales fp32
+ *   [capacity_slots]; the same SMI_IVF_LIST_ALIGN and the same smi_ivf_slots_bound.  Pad slots have zero codes, scale 0 and
+ *   id -1.  Slots from list_offsets[K] on are not written, except list_ids, which is -1 there.
+ * smi_ivf_i8_build: smi_ivf_build's bucketing (labels outside [0, K) leave the row out), then one wave per slot encodes the
+ *   row list_ids[slot] names.
+ * smi_ivf_i8_search: encodes the first nq rows of qn into the workspace, then inverts the probe table, scans and merges as
+ *   smi_ivf_search does.  idx / score: smi_ivf_search's layout, total order (score descending, ties to the lower ORIGINAL row
+ *   number, across lists as inside them) and (-1, -inf) fill.  Reads nothing back, allocates nothing.
+ * workspace: device memory, 16-byte aligned, smi_ivf_i8_build_workspace_bytes / smi_ivf_i8_search_workspace_bytes bytes.
+ * Refused before any launch: what smi_ivf_build / smi_ivf_search refuse, with the same codes, and d > SMI_IVF_I8_MAX_DIM
+ *   (SMI_ERR_UNSUPPORTED: the int32 sum could overflow).  For these shapes the sizing functions return 0.  The unit-size rule
+ *   is smi_ivf_search's. */
+#define SMI_IVF_I8_MAX_DIM 131072
+int smi_ivf_i8_encode(const void* xn_f16, int64_t n, int32_t d, void* codes, float* scales, void* stream);
+int64_t smi_ivf_i8_build_workspace_bytes(int64_t n, int64_t K, int32_t d);
+int smi_ivf_i8_build(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_codes,
+                     float* list_scales, int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets,
+                     int32_t* list_sizes, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t smi_ivf_i8_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d);
+int smi_ivf_i8_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                      const void* list_codes, const float* list_scales, const int32_t* list_ids,
+                      const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

@@ -11,6 +11,10 @@
 // (v_mfma_f32_16x16x32_f16, fp32 accumulators, K slices ascending: the bits of a score depend on the two rows alone) that
 // are folded into one running top-k per pair, the LDS key lists of xsim.hip.  A pair's list is written to the partial
 // array [nprobe][nq][k]; smi_xsim_merge_topk's kernel merges the nprobe parts.  No atomics on results.
+//
+// The second half of the file is the same index over int8 scalar-quantised rows: the bucketing, the unit
+// rule, the key lists and the merge above are called; the row quantiser, the gather that encodes and the integer-MFMA scan
+// are new.
 #include "api_common.hpp"
 #include "common.hpp"
 #include "topk_order.hpp"
@@ -357,6 +361,355 @@ hipError_t launch_scan(int unit, int64_t units, hipStream_t st, const f16* qn, i
                                                             nq, nprobe, rows, ids, off, K, poff, ubase, pairs, k, ps, pi);
 }
 
+// ================================================================ int8 scalar-quantised lists
+// The same lists with one signed byte per element and one fp32 scale per row.  The scan is ivf_scan_lists_kernel's
+// decomposition with the byte geometry unchanged: a K slice is still 128 bytes of a row, now 128 elements and two
+// v_mfma_i32_16x16x64_i8 steps, so a tile takes half as many slices and barriers.  The int32 sums are exact; the scales
+// meet the sum in the tile fold only.
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+constexpr int IVF_I8_MAX_DIM = SMI_IVF_I8_MAX_DIM;  // 127^2 * d < 2^31
+static_assert((int64_t)127 * 127 * IVF_I8_MAX_DIM < (1LL << 31), "the int32 sum of a row pair cannot overflow");
+
+__device__ __forceinline__ float i8_absmax8(u32x4 v) {
+  const half8 h = __builtin_bit_cast(half8, v);
+  float m = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) m = fmaxf(m, fabsf((float)h[e]));
+  return m;
+}
+
+// THE row quantiser, one wave per row (lane = threadIdx.x & 63; every lane of the wave calls it): codes[0 .. d) and the
+// value of *scale of the d fp16 at x.  amax is a max of exact fp32 values: the same in any order.  Two passes over the row;
+// the second finds it in the cache.
+__device__ __forceinline__ void i8_encode_row(const f16* __restrict__ x, int d, int lane, int8_t* __restrict__ codes,
+                                              float* __restrict__ scale) {
+  const u32x4* s = (const u32x4*)x;
+  float amax = 0.f;
+  for (int c = lane; c < d / 8; c += 64) amax = fmaxf(amax, i8_absmax8(s[c]));
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  const bool zero = amax == 0.f;
+  const float inv = zero ? 0.f : __fdiv_rn(127.0f, amax);
+  if (lane == 0) *scale = zero ? 0.f : __fdiv_rn(amax, 127.0f);
+  uint2* o = (uint2*)codes;
+  for (int c = lane; c < d / 8; c += 64) {
+    const half8 h = __builtin_bit_cast(half8, s[c]);
+    unsigned w[2] = {0u, 0u};
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float r = fminf(fmaxf(rintf((float)h[e] * inv), -127.f), 127.f);
+      w[e >> 2] |= ((unsigned)(int)r & 0xffu) << ((e & 3) * 8);
+    }
+    o[c] = uint2{w[0], w[1]};
+  }
+}
+
+__global__ __launch_bounds__(IVF_TB) void ivf_i8_encode_kernel(const f16* __restrict__ xn, int64_t n, int d,
+                                                               int8_t* __restrict__ codes, float* __restrict__ scales) {
+  const int64_t row = (int64_t)blockIdx.x * (IVF_TB / 64) + (threadIdx.x >> 6);
+  if (row >= n) return;  // wave-uniform
+  i8_encode_row(xn + (size_t)row * d, d, threadIdx.x & 63, codes + (size_t)row * d, scales + row);
+}
+
+// One wave per slot below off[K]: the encoding of the row ids[slot] names, or zero codes and scale 0 for a pad slot.
+__global__ __launch_bounds__(IVF_TB) void ivf_i8_gather_kernel(const f16* __restrict__ xn, int d,
+                                                               const int32_t* __restrict__ ids,
+                                                               const int32_t* __restrict__ off, int K,
+                                                               int8_t* __restrict__ codes, float* __restrict__ scales) {
+  const int lane = threadIdx.x & 63;
+  const int64_t slot = (int64_t)blockIdx.x * (IVF_TB / 64) + (threadIdx.x >> 6);
+  if (slot >= off[K]) return;  // wave-uniform
+  const int id = ids[slot];
+  if (id < 0) {
+    uint2* o = (uint2*)(codes + (size_t)slot * d);
+    for (int c = lane; c < d / 8; c += 64) o[c] = uint2{0u, 0u};
+    if (lane == 0) scales[slot] = 0.f;
+  } else {
+    i8_encode_row(xn + (size_t)id * d, d, lane, codes + (size_t)slot * d, scales + slot);
+  }
+}
+
+// ivf_scan_lists_kernel on int8 codes: the same units, tiles, loader mapping, swizzle, buffers and key lists (read its
+// comment first).  What differs: a K slice is IVF_I8_BK = 128 ELEMENTS (the same 128 bytes of a row), lane (l15, kg) feeds
+// chunk kk * 4 + kg of its row to MFMA step kk as 16 consecutive K bytes of BOTH operands, so the sum is the exact integer
+// whatever K order the instruction uses; nk = ceil(d / 128) and the chunks of the last slice past d (d % 128 == 64) are
+// zero-filled, which adds 0 exactly.  The fold loads the four slot scales beside the four ids, takes the pair's query scale
+// from LDS and forms fl32(fl32((float)acc * scale_x) * scale_q).
+constexpr int IVF_I8_BK = 128;            // bytes = elements of a K slice (256 was tried: profiles/ivf_i8_experiments.txt)
+constexpr int IVF_I8_CH = IVF_I8_BK / 16;  // 16-byte chunks of a row's slice; the swizzle is over all of them
+constexpr int IVF_I8_RP = IVF_TB / IVF_I8_CH;  // rows of an operand slice the 256 threads load in one pass
+static_assert(IVF_I8_BK % 64 == 0 && (IVF_I8_CH & (IVF_I8_CH - 1)) == 0 && IVF_BM % IVF_I8_RP == 0, "loader mapping");
+
+template <int B>
+constexpr int ivf_i8_scan_lds(int KT) { return 2 * 2 * B * IVF_I8_BK + B * KT * 8 + 2 * B * 4; }
+
+template <int KT, int B>
+__global__ __launch_bounds__(IVF_TB) void ivf_i8_scan_lists_kernel(const int8_t* __restrict__ qc, const float* __restrict__ qscale,
+                                                                   int d, int nq, int nprobe, const int8_t* __restrict__ rows,
+                                                                   const float* __restrict__ scales,
+                                                                   const int32_t* __restrict__ ids,
+                                                                   const int32_t* __restrict__ off, int K,
+                                                                   const int32_t* __restrict__ poff,
+                                                                   const int32_t* __restrict__ ubase,
+                                                                   const int32_t* __restrict__ pairs, int k_out,
+                                                                   float* __restrict__ ps, int32_t* __restrict__ pi) {
+  constexpr int OPB = B * IVF_I8_BK;  // bytes of one operand's K slice
+  constexpr int NR = B / 32;          // 16-row blocks of a wave per operand
+  constexpr int NL = B / IVF_I8_RP;   // rows of an operand slice a thread loads
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* lists = (unsigned long long*)(smem + 4 * OPB);
+  int* spair = (int*)(smem + 4 * OPB + B * KT * 8);
+  float* sqs = (float*)(spair + B);  // the pairs' query scales
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
+  const int b = blockIdx.x;
+  if (b >= ubase[K]) return;
+  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ubase[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const int l = lo;
+  const int p0 = poff[l] + (b - ubase[l]) * B;
+  const int npair = min(B, poff[l + 1] - p0);
+  const int s_begin = off[l], s_end = off[l + 1];
+
+  if (tid < B) {
+    const int pr = tid < npair ? pairs[p0 + tid] : -1;
+    spair[tid] = pr;
+    sqs[tid] = pr >= 0 ? qscale[pr / nprobe] : 0.f;
+#pragma unroll
+    for (int j = 0; j < KT; ++j) lists[tid * KT + j] = XS_EMPTY;
+  }
+  __syncthreads();
+
+  const int nk = (d + IVF_I8_BK - 1) / IVF_I8_BK;
+  const int ntiles = (s_end - s_begin + B - 1) / B;
+  const int T = ntiles * nk;
+
+  // this thread's rows of a slice, and where its chunk lands in LDS
+  const int cc = tid % IVF_I8_CH;
+  const int8_t* qsrc[NL];
+  int lds_off[NL];
+#pragma unroll
+  for (int j = 0; j < NL; ++j) {
+    const int r = tid / IVF_I8_CH + IVF_I8_RP * j;
+    const int pr = spair[r];
+    qsrc[j] = pr >= 0 ? qc + (size_t)(pr / nprobe) * d + cc * 16 : nullptr;
+    lds_off[j] = r * IVF_I8_BK + ((cc ^ (r & (IVF_I8_CH - 1))) << 4);
+  }
+  u32x4 qv[NL], lv[NL];
+  auto load = [&](int it) {
+    const int tile = it / nk, ks = it - tile * nk;
+    const bool in_row = ks * IVF_I8_BK + cc * 16 < d;  // false for chunks 4 .. 7 of the last slice when d % 128 == 64
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int slot = s_begin + tile * B + tid / IVF_I8_CH + IVF_I8_RP * j;
+      qv[j] = qsrc[j] && in_row ? *(const u32x4*)(qsrc[j] + ks * IVF_I8_BK) : u32x4{0u, 0u, 0u, 0u};
+      lv[j] = slot < s_end && in_row ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_I8_BK + cc * 16)
+                                     : u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  auto store = [&](int buf) {
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      *(u32x4*)(smem + buf * 2 * OPB + lds_off[j]) = qv[j];
+      *(u32x4*)(smem + buf * 2 * OPB + OPB + lds_off[j]) = lv[j];
+    }
+  };
+
+  i32x4 acc[NR][NR];  // [slot block ai][pair block bi]
+#pragma unroll
+  for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+    for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = i32x4{0, 0, 0, 0};
+  // 16-pair blocks of this wave that hold a pair at all (wave-uniform)
+  const int nb_live = min(NR, max(0, (npair - wc * (B / 2) + 15) / 16));
+
+  if (T > 0) {
+    load(0);
+    store(0);
+  }
+  __syncthreads();
+  int ks = 0, tile = 0;
+  for (int it = 0; it < T; ++it) {
+    const int buf = it & 1;
+    if (it + 1 < T) load(it + 1);
+    // 16-slot blocks of this wave below the end of the list (the lists are padded to 16 slots): wave-uniform
+    const int slot_w = s_begin + tile * B + wr * (B / 2);
+    const int na_live = min(NR, max(0, (s_end - slot_w) / 16));
+    if (na_live > 0 && nb_live > 0) {
+      const char* qs = smem + buf * 2 * OPB;
+      const char* ls = qs + OPB;
+#pragma unroll
+      for (int kk = 0; kk < IVF_I8_BK / 64; ++kk) {
+        const int ch = kk * 4 + kg;
+        i32x4 fa[NR], fb[NR];
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai) {
+          const int ra = wr * (B / 2) + ai * 16 + l15;
+          fa[ai] = *(const i32x4*)(ls + ra * IVF_I8_BK + ((ch ^ (ra & (IVF_I8_CH - 1))) << 4));
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) {
+          const int rb = wc * (B / 2) + bi * 16 + l15;
+          fb[bi] = *(const i32x4*)(qs + rb * IVF_I8_BK + ((ch ^ (rb & (IVF_I8_CH - 1))) << 4));
+        }
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai)
+          if (ai < na_live) {
+#pragma unroll
+            for (int bi = 0; bi < NR; ++bi)
+              if (bi < nb_live) acc[ai][bi] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ai], fb[bi], acc[ai][bi], 0, 0, 0);
+          }
+      }
+    }
+    if (it + 1 < T) store(buf ^ 1);
+    if (++ks == nk) {
+      // the tile is finished: fold this wave's scores into the pairs' lists, as ivf_scan_lists_kernel does
+#pragma unroll
+      for (int ai = 0; ai < NR; ++ai) {
+        if (ai < na_live) {
+          const int slot0 = slot_w + ai * 16 + 4 * kg;  // < s_end, 16-byte aligned: off % 16 == 0
+          const int4 id4 = *(const int4*)(ids + slot0);
+          const float4 sc4 = *(const float4*)(scales + slot0);
+          const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
+          const float scr[4] = {sc4.x, sc4.y, sc4.z, sc4.w};
+#pragma unroll
+          for (int bi = 0; bi < NR; ++bi) {
+            const int pr = wc * (B / 2) + bi * 16 + l15;
+            if (pr < npair) {
+              unsigned long long* lst = lists + pr * KT;
+              const float sq = sqs[pr];
+              const float thr = xs_unord(
+                  (uint32_t)(__hip_atomic_load(lst + KT - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32));
+#pragma unroll
+              for (int r = 0; r < 4; ++r) {
+                const float v = __fmul_rn(__fmul_rn((float)acc[ai][bi][r], scr[r]), sq);
+                if (idr[r] >= 0 && v >= thr) xs_insert<KT>(lst, v, idr[r]);
+              }
+            }
+          }
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = i32x4{0, 0, 0, 0};
+      }
+      ks = 0;
+      ++tile;
+    }
+    __syncthreads();
+  }
+
+  // (the last barrier of the loop, or the one before it when the list is empty, made the lists final)
+  if (tid < npair) {
+    const int pr = spair[tid];
+    const int q = pr / nprobe, p = pr - q * nprobe;
+    const size_t o = ((size_t)p * nq + q) * k_out;
+    for (int j = 0; j < k_out; ++j) {
+      const unsigned long long key = lists[tid * KT + j];
+      const bool have = key != XS_EMPTY;
+      ps[o + j] = have ? xs_unord((uint32_t)(key >> 32)) : -INFINITY;
+      pi[o + j] = have ? (int)(0xffffffffu - (uint32_t)key) : -1;
+    }
+  }
+}
+
+bool i8_dim_ok(int32_t d) { return d <= IVF_I8_MAX_DIM; }
+int i8_check_dim(int32_t d) {
+  if (d > IVF_I8_MAX_DIM)
+    return fail(SMI_ERR_UNSUPPORTED, "d=%d: above %d the int32 sum of int8 products could overflow", d, IVF_I8_MAX_DIM);
+  return SMI_OK;
+}
+// search: the flat search's workspace | query codes int8 [nq, d] | query scales fp32 [nq]
+size_t i8_search_bytes(int64_t nq, int64_t K, int nprobe, int k, int d) {
+  return search_bytes(nq, K, nprobe, k) + up16((size_t)nq * d) + up16((size_t)nq * 4);
+}
+
+template <int KT>
+hipError_t launch_i8_scan(int unit, int64_t units, hipStream_t st, const int8_t* qc, const float* qscale, int d, int nq,
+                          int nprobe, const int8_t* rows, const float* scales, const int32_t* ids, const int32_t* off, int K,
+                          const int32_t* poff, const int32_t* ubase, const int32_t* pairs, int k, float* ps, int32_t* pi) {
+  if (unit == IVF_BIG)
+    return launch_with_lds<ivf_i8_scan_lists_kernel<KT, IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_i8_scan_lds<IVF_BIG>(KT),
+                                                                  st, qc, qscale, d, nq, nprobe, rows, scales, ids, off, K,
+                                                                  poff, ubase, pairs, k, ps, pi);
+  return launch_with_lds<ivf_i8_scan_lists_kernel<KT, IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_i8_scan_lds<IVF_BM>(KT), st,
+                                                               qc, qscale, d, nq, nprobe, rows, scales, ids, off, K, poff,
+                                                               ubase, pairs, k, ps, pi);
+}
+
+// ---------------------------------------------------------------- host halves shared by the flat and the int8 entries
+int check_build_args(int64_t n, int32_t d, int64_t K, int64_t capacity_slots, const void* ws, int64_t ws_bytes,
+                     const char* sizing) {
+  if (const int rc = check_shape(n, "n", d, K)) return rc;
+  const int64_t bound = slots_bound(n, K);
+  if (bound > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "n=%lld rows over K=%lld lists can need %lld slots: slot numbers must fit int32",
+                (long long)n, (long long)K, (long long)bound);
+  if (capacity_slots < bound)
+    return fail(SMI_ERR_INVALID_ARG, "capacity of %lld slots, smi_ivf_slots_bound(n, K) = %lld", (long long)capacity_slots,
+                (long long)bound);
+  return check_ws(ws, ws_bytes, (int64_t)build_bytes(K), sizing);
+}
+
+// the three bucketing passes of a build: list_sizes, list_offsets and the row number of every slot (-1: pad or unused)
+hipError_t bucket_rows(const int32_t* labels, int64_t n, int64_t K, int32_t* list_ids, int64_t capacity_slots,
+                       int32_t* list_offsets, int32_t* list_sizes, int32_t* cursor, hipStream_t st) {
+  if (hipError_t e = hipMemsetAsync(list_sizes, 0, (size_t)K * 4, st); e != hipSuccess) return e;
+  if (hipError_t e = hipMemsetAsync(list_ids, 0xff, (size_t)capacity_slots * 4, st); e != hipSuccess) return e;  // -1
+  const dim3 block(IVF_TB), rows_grid = grid_for(n, IVF_TB);
+  hipLaunchKernelGGL(ivf_hist_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, list_sizes);
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, list_sizes, (int)K, IVF_ALIGN, 1, list_offsets, cursor,
+                     (int32_t*)nullptr);
+  hipLaunchKernelGGL(ivf_scatter_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, cursor, list_ids);
+  return hipGetLastError();
+}
+
+int check_search_args(int64_t nq, int32_t d, int64_t K, int32_t nprobe, int32_t k) {
+  if (const int rc = check_shape(nq, "nq", d, K)) return rc;
+  if (k < 1 || k > 8) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, 8]", k);
+  if (nprobe < 1 || nprobe > 8) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 8]", nprobe);
+  if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
+  return SMI_OK;
+}
+
+// the flat search's workspace, carved; `end` is where the int8 search's query codes begin
+struct SearchWs {
+  int32_t *pcount, *poff, *ubase, *cursor, *pairs, *pi;
+  float* ps;
+  char* end;
+  SearchWs(void* ws, int64_t P, int64_t K, int k) {
+    char* p = (char*)ws;
+    pcount = (int32_t*)p;
+    p += up16((size_t)K * 4);
+    poff = (int32_t*)p;
+    p += up16((size_t)(K + 1) * 4);
+    ubase = (int32_t*)p;
+    p += up16((size_t)(K + 1) * 4);
+    cursor = (int32_t*)p;
+    p += up16((size_t)K * 4);
+    pairs = (int32_t*)p;
+    p += up16((size_t)P * 4);
+    ps = (float*)p;
+    p += up16((size_t)P * k * 4);
+    pi = (int32_t*)p;
+    end = p + up16((size_t)P * k * 4);
+  }
+};
+
+// invert the probe table: the (query, probe slot) pairs q * nprobe + p bucketed by the list they name, the units' prefix
+// sum for `unit` pairs per unit, and the partial lists pre-filled
+hipError_t invert_probes(const int32_t* probes, int64_t P, int64_t K, int k, int unit, const SearchWs& w, hipStream_t st) {
+  if (hipError_t e = hipMemsetAsync(w.pcount, 0, (size_t)K * 4, st); e != hipSuccess) return e;
+  const dim3 block(IVF_TB), pair_grid = grid_for(P, IVF_TB);
+  hipLaunchKernelGGL(ivf_hist_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, w.pcount);
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, w.pcount, (int)K, 1, unit, w.poff, w.cursor, w.ubase);
+  hipLaunchKernelGGL(ivf_scatter_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, w.cursor, w.pairs);
+  hipLaunchKernelGGL(ivf_fill_kernel, grid_for(P * k, IVF_TB), block, 0, st, w.ps, w.pi, P * k);
+  return hipGetLastError();
+}
+
 }  // namespace
 
 }  // namespace smi
@@ -379,28 +732,13 @@ int smi_ivf_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, i
                   void* stream) {
   if (!xn || !labels || !list_rows || !list_ids || !list_offsets || !list_sizes)
     return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, K)) return rc;
-  const int64_t bound = slots_bound(n, K);
-  if (bound > IVF_MAX)
-    return fail(SMI_ERR_UNSUPPORTED, "n=%lld rows over K=%lld lists can need %lld slots: slot numbers must fit int32",
-                (long long)n, (long long)K, (long long)bound);
-  if (capacity_slots < bound)
-    return fail(SMI_ERR_INVALID_ARG, "capacity of %lld slots, smi_ivf_slots_bound(n, K) = %lld", (long long)capacity_slots,
-                (long long)bound);
-  if (const int rc = check_ws(ws, ws_bytes, (int64_t)build_bytes(K), "smi_ivf_build_workspace_bytes(n, K, d)")) return rc;
+  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_build_workspace_bytes(n, K, d)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  int32_t* cursor = (int32_t*)ws;
-  HIP_TRY(hipMemsetAsync(list_sizes, 0, (size_t)K * 4, st));
-  HIP_TRY(hipMemsetAsync(list_ids, 0xff, (size_t)capacity_slots * 4, st));  // -1: pad slots and the unused tail
-  const dim3 block(IVF_TB), rows_grid = grid_for(n, IVF_TB);
-  hipLaunchKernelGGL(ivf_hist_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, list_sizes);
-  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, list_sizes, (int)K, IVF_ALIGN, 1, list_offsets, cursor,
-                     (int32_t*)nullptr);
-  hipLaunchKernelGGL(ivf_scatter_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, cursor, list_ids);
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, (int32_t*)ws, st));
   // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
-  hipLaunchKernelGGL(ivf_gather_kernel, grid_for(bound, IVF_TB / 64), block, 0, st, (const f16*)xn, d, list_ids, list_offsets,
-                     (int)K, (f16*)list_rows);
+  hipLaunchKernelGGL(ivf_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d, list_ids,
+                     list_offsets, (int)K, (f16*)list_rows);
   HIP_TRY(hipGetLastError());
   return SMI_OK;
 }
@@ -414,48 +752,90 @@ int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes,
                    void* ws, int64_t ws_bytes, void* stream) {
   if (!qn || !probes || !list_rows || !list_ids || !list_offsets || !idx || !score)
     return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(nq, "nq", d, K)) return rc;
-  if (k < 1 || k > 8) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, 8]", k);
-  if (nprobe < 1 || nprobe > 8) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 8]", nprobe);
+  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
   const int64_t P = nq * nprobe;
-  if (P > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)P);
   if (const int rc = check_ws(ws, ws_bytes, (int64_t)search_bytes(nq, K, nprobe, k),
                               "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)"))
     return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)ws;
-  int32_t* pcount = (int32_t*)p;
-  p += up16((size_t)K * 4);
-  int32_t* poff = (int32_t*)p;
-  p += up16((size_t)(K + 1) * 4);
-  int32_t* ubase = (int32_t*)p;
-  p += up16((size_t)(K + 1) * 4);
-  int32_t* cursor = (int32_t*)p;
-  p += up16((size_t)K * 4);
-  int32_t* pairs = (int32_t*)p;
-  p += up16((size_t)P * 4);
-  float* ps = (float*)p;
-  p += up16((size_t)P * k * 4);
-  int32_t* pi = (int32_t*)p;
-
-  // invert the probe table: the (query, probe slot) pairs q * nprobe + p bucketed by the list they name
-  HIP_TRY(hipMemsetAsync(pcount, 0, (size_t)K * 4, st));
-  const dim3 block(IVF_TB), pair_grid = grid_for(P, IVF_TB);
-  hipLaunchKernelGGL(ivf_hist_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, pcount);
+  const SearchWs w(ws, P, K, k);
   const int unit = unit_pairs(P, K);
-  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, pcount, (int)K, 1, unit, poff, cursor, ubase);
-  hipLaunchKernelGGL(ivf_scatter_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, cursor, pairs);
-  hipLaunchKernelGGL(ivf_fill_kernel, grid_for(P * k, IVF_TB), block, 0, st, ps, pi, P * k);
-  HIP_TRY(hipGetLastError());
+  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
   // units for every pair count the table can have: those from ubase[K] on find nothing to do
   const int64_t units = units_bound(P, K, unit);
-  const f16* q16 = (const f16*)qn;
-  const f16* r16 = (const f16*)list_rows;
   const int KT = k == 1 ? 1 : k == 2 ? 2 : k <= 4 ? 4 : 8;
   auto scan = KT == 1 ? launch_scan<1> : KT == 2 ? launch_scan<2> : KT == 4 ? launch_scan<4> : launch_scan<8>;
-  HIP_TRY(scan(unit, units, st, q16, d, (int)nq, nprobe, r16, list_ids, list_offsets, (int)K, poff, ubase, pairs, k, ps, pi));
-  HIP_TRY(launch_topk_merge(ps, pi, nprobe, nq, k, score, idx, st));
+  HIP_TRY(scan(unit, units, st, (const f16*)qn, d, (int)nq, nprobe, (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff,
+               w.ubase, w.pairs, k, w.ps, w.pi));
+  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  return SMI_OK;
+}
+
+// ---------------------------------------------------------------- int8 lists
+int smi_ivf_i8_encode(const void* xn, int64_t n, int32_t d, void* codes, float* scales, void* stream) {
+  if (!xn || !codes || !scales) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = i8_check_dim(d)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d,
+                     (int8_t*)codes, scales);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int64_t smi_ivf_i8_build_workspace_bytes(int64_t n, int64_t K, int32_t d) {
+  return build_shape_ok(n, K, d) && i8_dim_ok(d) ? (int64_t)build_bytes(K) : 0;
+}
+
+int smi_ivf_i8_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_codes,
+                     float* list_scales, int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets,
+                     int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
+  if (!xn || !labels || !list_codes || !list_scales || !list_ids || !list_offsets || !list_sizes)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_i8_build_workspace_bytes(n, K, d)"))
+    return rc;
+  if (const int rc = i8_check_dim(d)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, (int32_t*)ws, st));
+  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
+  hipLaunchKernelGGL(ivf_i8_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d,
+                     list_ids, list_offsets, (int)K, (int8_t*)list_codes, list_scales);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int64_t smi_ivf_i8_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
+  return search_shape_ok(nq, K, nprobe, k, d) && i8_dim_ok(d) ? (int64_t)i8_search_bytes(nq, K, nprobe, k, d) : 0;
+}
+
+int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
+                      const float* list_scales, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
+                      int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
+  if (!qn || !probes || !list_codes || !list_scales || !list_ids || !list_offsets || !idx || !score)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
+  if (const int rc = i8_check_dim(d)) return rc;
+  const int64_t P = nq * nprobe;
+  if (const int rc = check_ws(ws, ws_bytes, (int64_t)i8_search_bytes(nq, K, nprobe, k, d),
+                              "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)"))
+    return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const SearchWs w(ws, P, K, k);
+  int8_t* qc = (int8_t*)w.end;
+  float* qscale = (float*)(w.end + up16((size_t)nq * d));
+  hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, qc, qscale);
+  // the flat search's unit rule holds here too: 128 won from 256 pairs per list on, 64 below (profiles/ivf_i8_experiments.txt)
+  const int unit = unit_pairs(P, K);
+  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
+  const int64_t units = units_bound(P, K, unit);
+  const int KT = k == 1 ? 1 : k == 2 ? 2 : k <= 4 ? 4 : 8;
+  auto scan = KT == 1 ? launch_i8_scan<1> : KT == 2 ? launch_i8_scan<2> : KT == 4 ? launch_i8_scan<4> : launch_i8_scan<8>;
+  HIP_TRY(scan(unit, units, st, qc, qscale, d, (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets,
+               (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi));
+  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
   return SMI_OK;
 }
 

@@ -1,4 +1,5 @@
-"""IVF-Flat index over sentence embeddings on the MI355X engine.
+"""IVF indexes over sentence embeddings on the MI355X engine: flat fp16 lists and int8 scalar-quantised
+lists.
 
 Brute-force `xsim.topk` scores every query against every row.  An inverted-file index scores a query against the rows of the
 `nprobe` nearest of K clusters only, about nprobe / K of the work, which is what repeated search of one corpus (LASER-style
@@ -11,7 +12,14 @@ ties to the lower row number, (-inf, -1) where the probed lists hold fewer than 
 `mining` consume it unchanged.  Its bits do not depend on the company of a query, on the order of the corpus or on the run.
 There is no CPU path.
 
-Not here: product or scalar quantisation of the stored rows, nprobe or k above 8, incremental add and
+`IVFInt8Index` is the same index with one signed byte per element and one fp32 scale per row (per-row symmetric, amax / 127):
+half the bytes, scanned with an integer MFMA whose sums are exact, so a score is specified down to its bits for any data
+(tests/ivf_i8_ref.py).  Its raw scores are the quantised rows' dot products, within a derived bound of the cosine but not
+the cosine; `search(..., refine=xn)` re-scores the k candidates against the fp16 corpus with `mining.pair_scores` and
+re-orders them, which is what margin mining wants.  The quality was measured on synthetic planted data only; real SONAR
+embeddings may have heavier-tailed rows, where a per-row scale loses more.
+
+Not here: product quantisation and fewer than 8 bits, nprobe or k above 8, incremental add and
 removal, 64-bit ids, splitting of long lists, multi-GPU sharding.
 """
 from __future__ import annotations
@@ -22,10 +30,12 @@ import torch
 
 from . import _lib
 from .clustering import SphericalKMeans
+from .mining import pair_scores
 from .xsim import normalize_rows, topk_normalized
 
 LIST_ALIGN = 16    # SMI_IVF_LIST_ALIGN: every list starts at a multiple of this many slots and is padded to it
 UNIT_QUERIES = 64  # SMI_IVF_UNIT_QUERIES: queries of one list that one work unit of the scan takes (128 when nq nprobe >= 256 K)
+INT8_MAX_DIM = 131072  # SMI_IVF_I8_MAX_DIM: above it the int32 sum of int8 products could overflow
 
 
 def _check_matrix(t, name: str) -> None:
@@ -57,11 +67,7 @@ def _check_small(v, name: str) -> None:
         raise ValueError(f"{name} = {v!r}: an integer in [1, 8]")
 
 
-def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
-    """smi_ivf_build: the inverted lists of the first len(labels) rows of xn (contiguous fp16 [>= n, d]) under labels (device
-    int32 [n]; a label outside [0, n_lists) leaves the row out).  Returns (rows fp16 [slots, d], ids int32 [slots], offsets
-    int32 [n_lists + 1], sizes int32 [n_lists]) with slots = smi_ivf_slots_bound(n, n_lists): the host has not seen the
-    labels, so the storage is sized for any labelling.  Slots from offsets[n_lists] on are unused (ids -1, rows unwritten)."""
+def _check_build_args(xn, labels, n_lists) -> None:
     _check_matrix(xn, "xn")
     if xn.dtype != torch.float16 or not xn.is_contiguous():
         raise ValueError("xn must be a contiguous fp16 matrix")
@@ -70,29 +76,42 @@ def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
     if isinstance(labels, torch.Tensor) and labels.dim() == 1 and not 1 <= labels.shape[0] <= xn.shape[0]:
         raise ValueError(f"{labels.shape[0]} labels for {xn.shape[0]} rows")
     _check_table(labels, "labels", labels.shape[0] if isinstance(labels, torch.Tensor) and labels.dim() == 1 else -1, None)
+
+
+def _check_int8_dim(d: int) -> None:
+    if d > INT8_MAX_DIM:
+        raise ValueError(f"dim = {d} exceeds {INT8_MAX_DIM}: the int32 sum of int8 products could overflow")
+
+
+def _build(xn, labels, n_lists: int, int8: bool):
+    """smi_ivf_build / smi_ivf_i8_build: (row storage ..., ids, offsets, sizes)."""
+    _check_build_args(xn, labels, n_lists)
+    if int8:
+        _check_int8_dim(xn.shape[1])
     lib = _lib.load()
     n, d, dev = labels.shape[0], xn.shape[1], xn.device
     cap = int(lib.smi_ivf_slots_bound(n, n_lists))
     if cap < 1:
         raise ValueError(f"{n} rows over {n_lists} lists: slot numbers must fit int32")
-    rows = torch.empty((cap, d), dtype=torch.float16, device=dev)
+    rows = torch.empty((cap, d), dtype=torch.int8 if int8 else torch.float16, device=dev)
+    scales = (torch.empty((cap,), dtype=torch.float32, device=dev),) if int8 else ()
     ids = torch.empty((cap,), dtype=torch.int32, device=dev)
     offsets = torch.empty((n_lists + 1,), dtype=torch.int32, device=dev)
     sizes = torch.empty((n_lists,), dtype=torch.int32, device=dev)
-    ws_bytes = int(lib.smi_ivf_build_workspace_bytes(n, n_lists, d))
+    sizing, entry = ((lib.smi_ivf_i8_build_workspace_bytes, lib.smi_ivf_i8_build) if int8 else
+                     (lib.smi_ivf_build_workspace_bytes, lib.smi_ivf_build))
+    ws_bytes = int(sizing(n, n_lists, d))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     labels = labels.contiguous()
     with torch.cuda.device(dev):
-        _lib.check(lib.smi_ivf_build(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, rows.data_ptr(), ids.data_ptr(), cap,
-                                     offsets.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws_bytes,
-                                     _lib.current_stream_ptr()))
-    return rows, ids, offsets, sizes
+        _lib.check(entry(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, rows.data_ptr(), *(t.data_ptr() for t in scales),
+                         ids.data_ptr(), cap, offsets.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws_bytes,
+                         _lib.current_stream_ptr()))
+    return (rows, *scales, ids, offsets, sizes)
 
 
-def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
-                 k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
-    """smi_ivf_search: the k best rows of the lists probes (device int32 [nq, 1..8]) names, for the first nq rows of qn
-    (contiguous fp16 [>= nq, d]) against the storage `build_lists` returned: (scores fp32 [nq, k], ids int32 [nq, k])."""
+def _search(qn, probes, rows, scales, ids, offsets, k: int):
+    """smi_ivf_search (scales None) / smi_ivf_i8_search."""
     _check_small(k, "k")
     _check_matrix(qn, "qn")
     if qn.dtype != torch.float16 or not qn.is_contiguous():
@@ -101,26 +120,83 @@ def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids
                                              or not 1 <= probes.shape[0] <= qn.shape[0]):
         raise ValueError(f"probes must be [nq, 1..8] with nq <= {qn.shape[0]} rows, got {list(probes.shape)}")
     _check_table(probes, "probes", *(probes.shape if isinstance(probes, torch.Tensor) else (-1, 1)))
+    int8 = scales is not None
+    if int8:
+        _check_int8_dim(qn.shape[1])
     lib = _lib.load()
     (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
     if rows.shape[1] != d:
         raise ValueError(f"qn has dim {d}, the lists {rows.shape[1]}")
-    ws_bytes = int(lib.smi_ivf_search_workspace_bytes(nq, n_lists, nprobe, k, d))
+    sizing, entry = ((lib.smi_ivf_i8_search_workspace_bytes, lib.smi_ivf_i8_search) if int8 else
+                     (lib.smi_ivf_search_workspace_bytes, lib.smi_ivf_search))
+    ws_bytes = int(sizing(nq, n_lists, nprobe, k, d))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
     idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
     score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
     probes = probes.contiguous()
     with torch.cuda.device(qn.device):
-        _lib.check(lib.smi_ivf_search(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, rows.data_ptr(), ids.data_ptr(),
-                                      offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(),
-                                      ws_bytes, _lib.current_stream_ptr()))
+        _lib.check(entry(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, rows.data_ptr(),
+                         *((scales.data_ptr(),) if int8 else ()), ids.data_ptr(), offsets.data_ptr(), n_lists, k,
+                         idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
     return score, idx
 
 
-class IVFFlatIndex:
-    """train / add / search; see the module text.
+def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
+    """smi_ivf_build: the inverted lists of the first len(labels) rows of xn (contiguous fp16 [>= n, d]) under labels (device
+    int32 [n]; a label outside [0, n_lists) leaves the row out).  Returns (rows fp16 [slots, d], ids int32 [slots], offsets
+    int32 [n_lists + 1], sizes int32 [n_lists]) with slots = smi_ivf_slots_bound(n, n_lists): the host has not seen the
+    labels, so the storage is sized for any labelling.  Slots from offsets[n_lists] on are unused (ids -1, rows unwritten)."""
+    return _build(xn, labels, n_lists, int8=False)
 
-    quantizer: a fitted `SphericalKMeans`, or an [K, d] tensor of centroids (normalised with `normalize_rows`)."""
+
+def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
+                 k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_search: the k best rows of the lists probes (device int32 [nq, 1..8]) names, for the first nq rows of qn
+    (contiguous fp16 [>= nq, d]) against the storage `build_lists` returned: (scores fp32 [nq, k], ids int32 [nq, k])."""
+    return _search(qn, probes, rows, None, ids, offsets, k)
+
+
+def encode_rows_int8(xn: torch.Tensor, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_i8_encode: (codes int8 [n, d], scales fp32 [n]) of the first n rows (default: all) of xn (contiguous fp16
+    [>= n, d]): scale = amax / 127, code = rint(x * (127 / amax)), a zero row all zeros (tests/ivf_i8_ref.py)."""
+    _check_matrix(xn, "xn")
+    if xn.dtype != torch.float16 or not xn.is_contiguous():
+        raise ValueError("xn must be a contiguous fp16 matrix")
+    n = xn.shape[0] if n is None else n
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= xn.shape[0]:
+        raise ValueError(f"n = {n!r}: between 1 and the {xn.shape[0]} rows of xn")
+    _check_int8_dim(xn.shape[1])
+    lib = _lib.load()
+    codes = torch.empty((n, xn.shape[1]), dtype=torch.int8, device=xn.device)
+    scales = torch.empty((n,), dtype=torch.float32, device=xn.device)
+    with torch.cuda.device(xn.device):
+        _lib.check(lib.smi_ivf_i8_encode(xn.data_ptr(), n, xn.shape[1], codes.data_ptr(), scales.data_ptr(),
+                                         _lib.current_stream_ptr()))
+    return codes, scales
+
+
+def build_lists_int8(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
+    """smi_ivf_i8_build: `build_lists` with encoded rows.  Returns (codes int8 [slots, d], scales fp32 [slots], ids, offsets,
+    sizes); a pad slot has zero codes, scale 0 and id -1."""
+    return _build(xn, labels, n_lists, int8=True)
+
+
+def search_lists_int8(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, ids: torch.Tensor,
+                      offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_i8_search: `search_lists` against the storage `build_lists_int8` returned; the queries are encoded like the
+    rows.  score = fl32(fl32((float)(integer dot product) * scale_row) * scale_query)."""
+    if not isinstance(scales, torch.Tensor):
+        raise TypeError("scales must be a torch.Tensor")
+    return _search(qn, probes, codes, scales, ids, offsets, k)
+
+
+class _IVFIndex:
+    """What `IVFFlatIndex` and `IVFInt8Index` share: the quantiser, the probe, the argument checks and the persistence.  A
+    subclass names its storage (`_ROWS_DTYPE`, `_STORAGE`: the attributes `add` fills, in the order of its build entry) and
+    gives `_build_lists` and `_search_lists`."""
+
+    _ROWS_DTYPE = torch.float16
+    _STORAGE = ("_rows", "_ids", "_offsets", "_sizes")
 
     def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor]):
         if isinstance(quantizer, SphericalKMeans):
@@ -134,7 +210,7 @@ class IVFFlatIndex:
         self._added = False
 
     @classmethod
-    def train(cls, x: torch.Tensor, n_lists: int, n_iter: int = 10, seed: int = 0) -> "IVFFlatIndex":
+    def train(cls, x: torch.Tensor, n_lists: int, n_iter: int = 10, seed: int = 0):
         """Fit the coarse quantiser: spherical k-means with `n_lists` clusters on x (fp16 / fp32 [n, d] on the device)."""
         return cls(SphericalKMeans(n_lists, n_iter=n_iter, seed=seed).fit(x))
 
@@ -174,7 +250,7 @@ class IVFFlatIndex:
         return int(self._sizes.sum().item())
 
     # ------------------------------------------------------------------------------------------------ add
-    def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None) -> "IVFFlatIndex":
+    def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None):
         """Index the rows of x (fp16 / fp32 [n, d] on the device); ids are the row numbers.  Once per index.
 
         labels: None (the nearest centroid, the quantiser's top-1) or device int32 [n]; a label outside [0, K) leaves the
@@ -192,7 +268,8 @@ class IVFFlatIndex:
         xn = normalize_rows(x)
         if labels is None:
             labels = topk_normalized(xn, n, self._c16, self._k, 1)[1][:, 0]
-        self._rows, self._ids, self._offsets, self._sizes = build_lists(xn, labels, self._k)
+        for name, t in zip(self._STORAGE, self._build_lists(xn, labels)):
+            setattr(self, name, t)
         self._added = True
         return self
 
@@ -210,13 +287,8 @@ class IVFFlatIndex:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
         return topk_normalized(qn, nq, self._c16, self._k, nprobe)[1]
 
-    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1,
-               probes: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The k best rows of the probed lists for every row of q (fp16 / fp32 [nq, d] on the device): (scores fp32
-        [nq, k], ids int32 [nq, k]), the layout and order of `xsim.topk`.
-
-        probes: None (the nprobe nearest lists by the quantiser) or device int32 [nq, 1..8]; an entry outside [0, K) names
-        no list.  A row of probes that names a list twice may return that list's rows twice."""
+    def _checked_search(self, q, k, nprobe, probes):
+        """The argument checks of `search`; returns (scores, ids, qn) of the subclass's scan."""
         _check_small(k, "k")
         _check_small(nprobe, "nprobe")
         self._need_add("search")
@@ -233,27 +305,29 @@ class IVFFlatIndex:
         qn = normalize_rows(q)
         if probes is None:
             probes = self._probe(qn, nq, nprobe)
-        return search_lists(qn, probes, self._rows, self._ids, self._offsets, k)
+        return (*self._search_lists(qn, probes, k), qn)
 
     # ------------------------------------------------------------------------------------------------ persistence
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        """centroids (fp16 [K, d], normalised), offsets, sizes, ids and rows; the storage is cut to the slots in use (one
-        read-back)."""
+        """centroids (fp16 [K, d], normalised), offsets, sizes, ids and rows (and scales, where the rows are int8 codes); the
+        storage is cut to the slots in use (one read-back)."""
         self._need_add("state_dict")
         used = int(self._offsets[self._k].item())
-        return {"centroids": self._c16[: self._k].clone(), "offsets": self._offsets.clone(), "sizes": self._sizes.clone(),
-                "ids": self._ids[:used].clone(), "rows": self._rows[:used].clone()}
+        state = {"centroids": self._c16[: self._k].clone(), "offsets": self._offsets.clone(), "sizes": self._sizes.clone()}
+        for name in self._STORAGE[:-2]:
+            state[name[1:]] = getattr(self, name)[:used].clone()
+        return state
 
     @classmethod
-    def from_state_dict(cls, state: Dict[str, torch.Tensor]) -> "IVFFlatIndex":
+    def from_state_dict(cls, state: Dict[str, torch.Tensor]):
         index = cls.__new__(cls)
         index._added = False
         index.load_state_dict(state, _fresh=True)
         return index
 
-    def load_state_dict(self, state: Dict[str, torch.Tensor], _fresh: bool = False) -> "IVFFlatIndex":
+    def load_state_dict(self, state: Dict[str, torch.Tensor], _fresh: bool = False):
         """Take over a `state_dict()` (tensors on the device).  The centroids must have this index's shape."""
-        missing = {"centroids", "offsets", "sizes", "ids", "rows"} - set(state)
+        missing = {"centroids", "offsets", "sizes", *(name[1:] for name in self._STORAGE[:-2])} - set(state)
         if missing:
             raise ValueError(f"state lacks {sorted(missing)}")
         c = state["centroids"]
@@ -267,8 +341,12 @@ class IVFFlatIndex:
         _check_table(state["sizes"], "sizes", k, None)
         rows, ids = state["rows"], state["ids"]
         _check_table(ids, "ids", rows.shape[0] if isinstance(rows, torch.Tensor) else -1, None)
-        if not rows.is_cuda or rows.dtype != torch.float16 or rows.dim() != 2 or rows.shape[1] != d:
-            raise ValueError(f"rows must be fp16 [slots, {d}] on the device")
+        if not rows.is_cuda or rows.dtype != self._ROWS_DTYPE or rows.dim() != 2 or rows.shape[1] != d:
+            raise ValueError(f"rows must be {'fp16' if self._ROWS_DTYPE == torch.float16 else 'int8'} [slots, {d}] on the device")
+        scales = state["scales"] if "_scales" in self._STORAGE else None
+        if scales is not None and (not isinstance(scales, torch.Tensor) or not scales.is_cuda
+                                   or scales.dtype != torch.float32 or tuple(scales.shape) != (rows.shape[0],)):
+            raise ValueError(f"scales must be fp32 [{rows.shape[0]}] on the device")
         used = int(state["offsets"][k].item())
         if used != rows.shape[0] or used % LIST_ALIGN:
             raise ValueError(f"offsets end at slot {used}, rows has {rows.shape[0]} (a multiple of {LIST_ALIGN} is expected)")
@@ -278,5 +356,79 @@ class IVFFlatIndex:
         self._c16[:k] = c
         self._offsets, self._sizes = state["offsets"].contiguous().clone(), state["sizes"].contiguous().clone()
         self._ids, self._rows = ids.contiguous().clone(), rows.contiguous().clone()
+        if scales is not None:
+            self._scales = scales.contiguous().clone()
         self._added = True
         return self
+
+
+class IVFFlatIndex(_IVFIndex):
+    """train / add / search over fp16 copies of the rows; see the module text.
+
+    quantizer: a fitted `SphericalKMeans`, or an [K, d] tensor of centroids (normalised with `normalize_rows`)."""
+
+    def _build_lists(self, xn, labels):
+        return build_lists(xn, labels, self._k)
+
+    def _search_lists(self, qn, probes, k):
+        return search_lists(qn, probes, self._rows, self._ids, self._offsets, k)
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1,
+               probes: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The k best rows of the probed lists for every row of q (fp16 / fp32 [nq, d] on the device): (scores fp32
+        [nq, k], ids int32 [nq, k]), the layout and order of `xsim.topk`.
+
+        probes: None (the nprobe nearest lists by the quantiser) or device int32 [nq, 1..8]; an entry outside [0, K) names
+        no list.  A row of probes that names a list twice may return that list's rows twice."""
+        return self._checked_search(q, k, nprobe, probes)[:2]
+
+
+class IVFInt8Index(_IVFIndex):
+    """`IVFFlatIndex` over int8 codes and one fp32 scale per row: half the storage, exact integer scan.
+    `state_dict` adds `scales`, and its `rows` are the int8 codes."""
+
+    _ROWS_DTYPE = torch.int8
+    _STORAGE = ("_rows", "_scales", "_ids", "_offsets", "_sizes")
+
+    def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor]):
+        super().__init__(quantizer)
+        _check_int8_dim(self._d)
+
+    def _build_lists(self, xn, labels):
+        return build_lists_int8(xn, labels, self._k)
+
+    def _search_lists(self, qn, probes, k):
+        return search_lists_int8(qn, probes, self._rows, self._scales, self._ids, self._offsets, k)
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
+               refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`IVFFlatIndex.search` on the quantised rows: the scores are the quantised dot products of tests/ivf_i8_ref.py.
+
+        refine: None, or the normalised fp16 corpus the index was built from (`normalize_rows(x)`, row number = id).  The k
+        candidates of every query are then re-scored with their fp16 cosines (`mining.pair_scores`, cosine mode) and each
+        row is re-ordered into the same total order; (-inf, -1) entries stay what they are.  No host synchronisation."""
+        if refine is not None:
+            _check_matrix(refine, "refine")
+            if refine.dtype != torch.float16 or not refine.is_contiguous() or refine.shape[1] != self._d:
+                raise ValueError(f"refine must be the contiguous fp16 [rows, {self._d}] matrix normalize_rows returned")
+        score, idx, qn = self._checked_search(q, k, nprobe, probes)
+        if refine is None:
+            return score, idx
+        return refine_candidates(qn, q.shape[0], refine, idx)
+
+
+def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The candidates idx (int32 [nq, k], -1 = none) of the first nq rows of qn re-scored with their fp16 cosines against the
+    rows of xn (both from `normalize_rows`) and every row re-ordered into the total order: (scores fp32 [nq, k], ids int32
+    [nq, k]).  `mining.pair_scores` in cosine mode and two stable sorts; an empty entry never reaches the kernel's NaN path
+    (it scores row 0 and is overwritten with -inf)."""
+    k = idx.shape[1]
+    have = idx >= 0
+    src = torch.arange(nq, device=idx.device).repeat_interleave(k)
+    trg = torch.where(have, idx, torch.zeros_like(idx)).reshape(-1)
+    cos = pair_scores(qn, nq, xn, xn.shape[0], src, trg, None, None, "cosine").reshape(nq, k)
+    cos = torch.where(have, cos, torch.full_like(cos, float("-inf")))
+    by_id = torch.sort(idx, dim=1, stable=True)[1]  # then a stable sort by score: ties go to the lower id
+    cos, idx = torch.gather(cos, 1, by_id), torch.gather(idx, 1, by_id)
+    order = torch.sort(cos, dim=1, descending=True, stable=True)[1]
+    return torch.gather(cos, 1, order), torch.gather(idx, 1, order)
