@@ -754,6 +754,33 @@ int smi_ivf_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* pro
                    const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Semantic de-duplication over the IVF-Flat lists (restated in tests/dedup_ref.py): the per-list self-join of
+ * SemDeDup (Abbas et al. 2023).  For every row, the best score against the rows of its own list that PRECEDE it in a keep
+ * order; a caller thresholds it (keep = !(max_sim > threshold), strict) and may sweep the threshold over one stored result.
+ *
+ * Input: the storage smi_ivf_build wrote, unchanged: list_rows fp16 [slots, d], list_ids int32 [slots] (-1 = pad or unused
+ *   slot), list_offsets int32 [K + 1].  n = the number of original rows; ids lie in [0, n).  priority = device fp32 [n]
+ *   indexed by ORIGINAL row number, or NULL: every priority compares equal.  NaN priorities are outside the contract.
+ * Precedence: row j precedes row i iff both are in the same list and (priority[j] > priority[i] or (priority[j] ==
+ *   priority[i] and j < i)).  A row never precedes itself; with no priority this reads "keep the first occurrence".
+ * Output, indexed by original row number and pre-filled on the device: max_sim fp32 [n] = the best score of row i against
+ *   the rows that precede it, -inf if none does (also for a row that is in no list); nearest int32 [n] = the id of that row,
+ *   or -1.  "Best" is smi_xsim_topk's total order: score descending, ties to the lower original id.
+ * Score: what smi_ivf_search returns for the same two rows (fp32 accumulation of the fp16 products, MFMA K slices
+ *   ascending).  Its bits depend on the two rows alone -- not on the list, the slot, the tile shape, the unit size, the order
+ *   of the corpus or the run -- and the score of (i, j) has the bits of the score of (j, i).
+ * A row is compared with its own list only.  One work unit is one list and 64 consecutive slots of it (128 where n >= 256 K;
+ *   no bit depends on it) and walks the whole list: a very long list costs its size squared, on size / unit CUs.
+ * Reads nothing back, allocates nothing, is capturable.  workspace: device memory, 16-byte aligned,
+ *   smi_ivf_dedup_workspace_bytes bytes.
+ * Refused before any launch: a null pointer except priority, n / K / slots < 1, slots not a multiple of SMI_IVF_LIST_ALIGN, a
+ *   small or misaligned workspace (SMI_ERR_INVALID_ARG); d not a multiple of 64, n, K or slots above 2^31 - 256
+ *   (SMI_ERR_UNSUPPORTED).  For these shapes the sizing function returns 0. */
+int64_t smi_ivf_dedup_workspace_bytes(int64_t slots, int64_t n, int64_t K, int32_t d);
+int smi_ivf_dedup(const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int64_t slots,
+                  int32_t d, const float* priority_or_null, int64_t n, float* max_sim, int32_t* nearest, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+
 /* IVF index with int8 scalar-quantised rows (restated in tests/ivf_i8_ref.py).  The lists of smi_ivf_build
  * with one signed byte per element and one fp32 scale per row, half the bytes of the fp16 copies, scanned with an integer
  * MFMA (v_mfma_i32_16x16x64_i8) whose int32 sums are exact, so a score is specified down to its bits for ANY data.

@@ -710,6 +710,222 @@ hipError_t invert_probes(const int32_t* probes, int64_t P, int64_t K, int k, int
   return hipGetLastError();
 }
 
+// ================================================================ semantic de-duplication
+// The per-list self-join of SemDeDup over the flat lists: for every row, the best score against the rows of its own list
+// that PRECEDE it in a keep order (higher priority first, ties to the lower original id).  The queries are the list rows
+// themselves, so nothing is gathered by index and no probe table is inverted: a unit is one list and B consecutive slots of
+// it (its own rows, the MFMA B operand) and walks the whole list in tiles of B slots (the A operand) with
+// ivf_scan_lists_kernel's slice loop (read its comment first): the same loader mapping, swizzle, buffers, fragment reads,
+// MFMA and K order, so a score has the bits smi_ivf_search returns for the same two rows.  What differs is the fold: one
+// 64-bit key per own row and lane, in registers, which a candidate enters iff it is a row (id >= 0) and precedes the own row.
+
+// span[l] = off[l + 1] - off[l]: the padded size of every list, what the unit prefix scan counts
+__global__ __launch_bounds__(IVF_TB) void ivf_span_kernel(const int32_t* __restrict__ off, int K, int32_t* __restrict__ span) {
+  const int64_t l = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  if (l < K) span[l] = off[l + 1] - off[l];
+}
+
+// sprio[slot] = priority[ids[slot]] for the slots in use: the priorities in slot order, once per call.  0 for a pad slot
+// (never compared) and for every slot when there is no priority (all equal: the id decides).
+__global__ __launch_bounds__(IVF_TB) void ivf_slot_priority_kernel(const int32_t* __restrict__ ids,
+                                                                   const int32_t* __restrict__ off, int K,
+                                                                   const float* __restrict__ priority, int n,
+                                                                   float* __restrict__ sprio) {
+  const int64_t slot = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  if (slot >= off[K]) return;
+  const int id = ids[slot];
+  sprio[slot] = priority && id >= 0 && id < n ? priority[id] : 0.f;  // an id outside [0, n) breaks the contract: not read
+}
+
+template <int B>
+constexpr int ivf_selfjoin_lds() { return 2 * 2 * B * IVF_BK * 2 + B * 8; }
+
+// Workgroup b = unit b - ubase[l] of the list l with ubase[l] <= b < ubase[l + 1]: own slots off[l] + B * that .. against
+// the slots off[l] .. off[l + 1].  Lane (l15, kg) of wave (wr, wc) holds own row wc * B / 2 + bi * 16 + l15 x candidate
+// slots wr * B / 2 + ai * 16 + 4 kg + r of the tile: the best key of an own row is spread over 4 lanes of 2 waves until the
+// end of the walk, where two shuffles and one LDS max per wave join it.
+template <int B>
+__global__ __launch_bounds__(IVF_TB) void ivf_selfjoin_kernel(const f16* __restrict__ rows, int d,
+                                                              const int32_t* __restrict__ ids,
+                                                              const float* __restrict__ sprio,
+                                                              const int32_t* __restrict__ off, int K,
+                                                              const int32_t* __restrict__ ubase, int n,
+                                                              float* __restrict__ max_sim, int32_t* __restrict__ nearest) {
+  constexpr int OPB = B * IVF_BK * 2;  // bytes of one operand's K slice
+  constexpr int NR = B / 32;           // rows of an operand slice a thread loads; 16-row blocks of a wave per operand
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* sbest = (unsigned long long*)(smem + 4 * OPB);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
+  const int b = blockIdx.x;
+  if (b >= ubase[K]) return;
+  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ubase[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const int l = lo;
+  const int s_begin = off[l], s_end = off[l + 1];
+  const int u0 = s_begin + (b - ubase[l]) * B;  // < s_end: the list has ceil((s_end - s_begin) / B) units
+  const int nown = min(B, s_end - u0);          // a multiple of 16
+
+  if (tid < B) sbest[tid] = XS_EMPTY;
+
+  const int nk = d / IVF_BK;
+  const int ntiles = (s_end - s_begin + B - 1) / B;
+  const int T = ntiles * nk;
+
+  // this thread's rows of a slice, and where its chunk lands in LDS
+  const int cc = tid & 7;
+  const f16* qsrc[NR];
+  int lds_off[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int r = (tid >> 3) + 32 * j;
+    qsrc[j] = r < nown ? rows + (size_t)(u0 + r) * d + cc * 8 : nullptr;
+    lds_off[j] = r * (IVF_BK * 2) + ((cc ^ (r & 7)) << 4);
+  }
+  u32x4 qv[NR], lv[NR];
+  auto load = [&](int it) {
+    const int tile = it / nk, ks = it - tile * nk;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
+      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
+      lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  auto store = [&](int buf) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      *(u32x4*)(smem + buf * 2 * OPB + lds_off[j]) = qv[j];
+      *(u32x4*)(smem + buf * 2 * OPB + OPB + lds_off[j]) = lv[j];
+    }
+  };
+
+  f32x4 acc[NR][NR];  // [candidate block ai][own block bi]
+#pragma unroll
+  for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+    for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // 16-row blocks of this wave that hold an own slot at all (wave-uniform)
+  const int nb_live = min(NR, max(0, (nown - wc * (B / 2)) / 16));
+  // this lane's own rows: id (-1: a pad slot, or no slot), priority, best key so far
+  int own_id[NR];
+  float own_p[NR];
+  unsigned long long best[NR];
+#pragma unroll
+  for (int bi = 0; bi < NR; ++bi) {
+    const int pr = wc * (B / 2) + bi * 16 + l15;
+    own_id[bi] = pr < nown ? ids[u0 + pr] : -1;
+    own_p[bi] = pr < nown ? sprio[u0 + pr] : 0.f;
+    best[bi] = XS_EMPTY;
+  }
+
+  load(0);  // T > 0: a list with a unit has a slot
+  store(0);
+  __syncthreads();
+  int ks = 0, tile = 0;
+  for (int it = 0; it < T; ++it) {
+    const int buf = it & 1;
+    if (it + 1 < T) load(it + 1);
+    // 16-slot blocks of this wave below the end of the list (the lists are padded to 16 slots): wave-uniform
+    const int slot_w = s_begin + tile * B + wr * (B / 2);
+    const int na_live = min(NR, max(0, (s_end - slot_w) / 16));
+    if (na_live > 0 && nb_live > 0) {
+      const char* qs = smem + buf * 2 * OPB;
+      const char* ls = qs + OPB;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int ch = kk * 4 + kg;
+        half8 fa[NR], fb[NR];
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai) {
+          const int ra = wr * (B / 2) + ai * 16 + l15;
+          fa[ai] = *(const half8*)(ls + ra * (IVF_BK * 2) + ((ch ^ (ra & 7)) << 4));
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) {
+          const int rb = wc * (B / 2) + bi * 16 + l15;
+          fb[bi] = *(const half8*)(qs + rb * (IVF_BK * 2) + ((ch ^ (rb & 7)) << 4));
+        }
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai)
+          if (ai < na_live) {
+#pragma unroll
+            for (int bi = 0; bi < NR; ++bi)
+              if (bi < nb_live) acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[ai], fb[bi], acc[ai][bi], 0, 0, 0);
+          }
+      }
+    }
+    if (it + 1 < T) store(buf ^ 1);
+    if (++ks == nk) {
+      // the tile is finished: a candidate enters the own row's key iff it is a row and precedes the own row
+#pragma unroll
+      for (int ai = 0; ai < NR; ++ai) {
+        if (ai < na_live && nb_live > 0) {
+          const int slot0 = slot_w + ai * 16 + 4 * kg;  // < s_end, 16-byte aligned: off % 16 == 0
+          const int4 id4 = *(const int4*)(ids + slot0);
+          const float4 p4 = *(const float4*)(sprio + slot0);
+          const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
+          const float prr[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+          for (int bi = 0; bi < NR; ++bi) {
+            const int oid = own_id[bi];
+            const float op = own_p[bi];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const bool precedes = idr[r] >= 0 && oid >= 0 && (prr[r] > op || (prr[r] == op && idr[r] < oid));
+              const unsigned long long key =
+                  ((unsigned long long)xs_ord(acc[ai][bi][r]) << 32) | (uint32_t)(0xffffffffu - (uint32_t)idr[r]);
+              if (precedes && key > best[bi]) best[bi] = key;
+            }
+          }
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      ks = 0;
+      ++tile;
+    }
+    __syncthreads();
+  }
+
+  // join the 4 kg lanes of an own row, then the two wr waves (sbest was initialised before the loop's barriers)
+#pragma unroll
+  for (int bi = 0; bi < NR; ++bi) {
+    unsigned long long k = best[bi];
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) {
+      const unsigned long long other = __shfl_xor(k, o, 64);
+      k = other > k ? other : k;
+    }
+    if (kg == 0 && k != XS_EMPTY)
+      __hip_atomic_fetch_max(sbest + wc * (B / 2) + bi * 16 + l15, k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  // the unit owns its rows: no atomics on results.  A row nothing precedes keeps the pre-filled (-inf, -1).
+  if (tid < nown) {
+    const int id = ids[u0 + tid];
+    const unsigned long long key = sbest[tid];
+    if (id >= 0 && id < n && key != XS_EMPTY) {  // (an id outside [0, n) breaks the contract: nothing is written through it)
+      max_sim[id] = xs_unord((uint32_t)(key >> 32));
+      nearest[id] = (int)(0xffffffffu - (uint32_t)key);
+    }
+  }
+}
+
+bool dedup_shape_ok(int64_t slots, int64_t n, int64_t K, int32_t d) {
+  return slots >= 1 && slots % IVF_ALIGN == 0 && n >= 1 && K >= 1 && d > 0 && d % 64 == 0 && slots <= IVF_MAX && n <= IVF_MAX &&
+         K <= IVF_MAX && slots / IVF_BM + K <= IVF_MAX;
+}
+// dedup: padded list sizes [K] | their prefix sum [K + 1] | unit offsets [K + 1] | cursor [K] | priorities in slot order
+//        fp32 [slots]
+size_t dedup_bytes(int64_t slots, int64_t K) {
+  return 2 * up16((size_t)K * 4) + 2 * up16((size_t)(K + 1) * 4) + up16((size_t)slots * 4);
+}
+
 }  // namespace
 
 }  // namespace smi
@@ -769,6 +985,62 @@ int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes,
   HIP_TRY(scan(unit, units, st, (const f16*)qn, d, (int)nq, nprobe, (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff,
                w.ubase, w.pairs, k, w.ps, w.pi));
   HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  return SMI_OK;
+}
+
+// ---------------------------------------------------------------- semantic de-duplication
+int64_t smi_ivf_dedup_workspace_bytes(int64_t slots, int64_t n, int64_t K, int32_t d) {
+  return dedup_shape_ok(slots, n, K, d) ? (int64_t)dedup_bytes(slots, K) : 0;
+}
+
+int smi_ivf_dedup(const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int64_t slots,
+                  int32_t d, const float* priority, int64_t n, float* max_sim, int32_t* nearest, void* ws, int64_t ws_bytes,
+                  void* stream) {
+  if (!list_rows || !list_ids || !list_offsets || !max_sim || !nearest) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, "n", d, K)) return rc;
+  if (slots < 1) return fail(SMI_ERR_INVALID_ARG, "slots=%lld: empty storage", (long long)slots);
+  if (slots > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "slots=%lld: slot numbers must fit int32", (long long)slots);
+  if (slots % IVF_ALIGN)
+    return fail(SMI_ERR_INVALID_ARG, "slots=%lld must be a multiple of %d, as smi_ivf_build's storage is", (long long)slots,
+                IVF_ALIGN);
+  if (slots / IVF_BM + K > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "slots=%lld, K=%lld: the unit count must fit int32", (long long)slots, (long long)K);
+  if (const int rc = check_ws(ws, ws_bytes, (int64_t)dedup_bytes(slots, K), "smi_ivf_dedup_workspace_bytes(slots, n, K, d)"))
+    return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  char* p = (char*)ws;
+  int32_t* span = (int32_t*)p;
+  p += up16((size_t)K * 4);
+  int32_t* span_off = (int32_t*)p;  // the scan's first output: list_offsets again
+  p += up16((size_t)(K + 1) * 4);
+  int32_t* ubase = (int32_t*)p;
+  p += up16((size_t)(K + 1) * 4);
+  int32_t* cursor = (int32_t*)p;
+  p += up16((size_t)K * 4);
+  float* sprio = (float*)p;
+  // own rows of a unit = slots of its tiles: 128 where the lists average 256 rows or more, else 64 (unit_pairs' rule with
+  // one "pair" per row)
+  const int unit = unit_pairs(n, K);
+  const dim3 block(IVF_TB);
+  hipLaunchKernelGGL(ivf_fill_kernel, grid_for(n, IVF_TB), block, 0, st, max_sim, nearest, n);
+  hipLaunchKernelGGL(ivf_span_kernel, grid_for(K, IVF_TB), block, 0, st, list_offsets, (int)K, span);
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, span, (int)K, 1, unit, span_off, cursor, ubase);
+  hipLaunchKernelGGL(ivf_slot_priority_kernel, grid_for(slots, IVF_TB), block, 0, st, list_ids, list_offsets, (int)K, priority,
+                     (int)n, sprio);
+  HIP_TRY(hipGetLastError());
+  // units for every list layout the storage can hold: a list has ceil(padded size / unit) of them, at most slots / unit + K
+  // in all; those from ubase[K] on find nothing to do
+  const int64_t units = slots / unit + K;
+  if (unit == IVF_BIG) {
+    HIP_TRY(launch_with_lds<ivf_selfjoin_kernel<IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_selfjoin_lds<IVF_BIG>(), st,
+                                                          (const f16*)list_rows, d, list_ids, sprio, list_offsets, (int)K, ubase,
+                                                          (int)n, max_sim, nearest));
+  } else {
+    HIP_TRY(launch_with_lds<ivf_selfjoin_kernel<IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_selfjoin_lds<IVF_BM>(), st,
+                                                         (const f16*)list_rows, d, list_ids, sprio, list_offsets, (int)K, ubase,
+                                                         (int)n, max_sim, nearest));
+  }
   return SMI_OK;
 }
 

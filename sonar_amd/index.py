@@ -19,6 +19,8 @@ the cosine; `search(..., refine=xn)` re-scores the k candidates against the fp16
 re-orders them, which is what margin mining wants.  The quality was measured on synthetic planted data only; real SONAR
 embeddings may have heavier-tailed rows, where a per-row scale loses more.
 
+`IVFFlatIndex.self_join` and `sonar_amd.dedup` are the de-duplication over the flat lists.
+
 Not here: product quantisation and fewer than 8 bits, nprobe or k above 8, incremental add and
 removal, 64-bit ids, splitting of long lists, multi-GPU sharding.
 """
@@ -382,6 +384,19 @@ class IVFFlatIndex(_IVFIndex):
         no list.  A row of probes that names a list twice may return that list's rows twice."""
         return self._checked_search(q, k, nprobe, probes)[:2]
 
+    def self_join(self, priority: Optional[torch.Tensor] = None, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`dedup.self_join` over this index's own lists: (max_sim fp32 [n], nearest int32 [n]), for every
+        row its best score against the rows of its list that precede it (priority higher, or equal and id lower), and that
+        row's id.  n: the number of rows `add` was given (ids lie in [0, n)); None takes the length of `priority`."""
+        from . import dedup
+
+        self._need_add("self_join")
+        if n is None:
+            if not isinstance(priority, torch.Tensor):
+                raise ValueError("give n, the number of rows the index was filled from, or a priority tensor of that length")
+            n = priority.shape[0] if priority.dim() == 1 else -1
+        return dedup.self_join(self._rows, self._ids, self._offsets, n, priority)
+
 
 class IVFInt8Index(_IVFIndex):
     """`IVFFlatIndex` over int8 codes and one fp32 scale per row: half the storage, exact integer scan.
@@ -415,6 +430,9 @@ class IVFInt8Index(_IVFIndex):
         if refine is None:
             return score, idx
         return refine_candidates(qn, q.shape[0], refine, idx)
+
+    def self_join(self, *args, **kwargs):
+        raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFInt8Index holds int8 codes")
 
 
 def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
