@@ -818,6 +818,55 @@ int smi_ivf_i8_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* 
                       const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* Product quantiser and IVF index with product-quantised rows (restated in tests/ivf_pq_ref.py).
+ * d = M * dsub: M sub-quantisers over dsub in {8, 16, 32, 64} dimensions each, always 256 codewords, so a code is one byte
+ * and a row M bytes (128 / 64 / 32 / 16 at d = 1024).  codebooks: fp16 [M][256][dsub], 16-byte aligned; codes: uint8 [n][M].
+ *
+ * Encoding of subvector x (the fp16 x[m dsub .. (m + 1) dsub) of a row) against codeword c (fp16 [dsub]), all in fp32:
+ *   n2 = ((0 + c_0 c_0) + c_1 c_1) + ... ascending;  bias = -0.5f * n2 (exact);
+ *   key = fmaf(x_{dsub-1}, c_{dsub-1}, ... fmaf(x_0, c_0, bias)), one chain ascending in j;
+ *   code_m = the c with the largest key, ties to the lower code: the Euclidean nearest codeword.  A product of two fp16 is
+ *   exact in fp32, so every step is one rounding of an exact sum.  Non-finite input is outside the contract.
+ * smi_pq_encode: codes of the first n rows of xn (fp16 [>= n, d]).  smi_pq_train (every round) and smi_ivf_pq_build call
+ *   the same device function: a row has the same codes wherever it is encoded.
+ * smi_pq_decode: rows fp16 [n, d] (16-byte aligned), row r = the concatenation of the M codewords codes[r] names.
+ * smi_pq_train: Lloyd rounds on the first n rows of xn.  init = device int32 [256], row numbers in [0, n) (trusted):
+ *   codeword c of every sub-quantiser starts as that subvector of row init[c].  A round encodes all rows, forms
+ *   S[m][c][j] = sum over the members of x_j * 2^24 as int64 (exact in any order; needs n * max|x| * 2^24 < 2^63, always
+ *   true for rows of smi_xsim_normalize) and count[m][c], then c_j = fp16_rn(fdiv_rn((float)S, (float)count) * 2^-24), the
+ *   int64 -> fp32 conversion, the division and the fp16 conversion to nearest even; a codeword with no member keeps its
+ *   value.  n_iter >= 0 rounds (0: the start), all enqueued on the stream, no read-back, integer atomics only: one init
+ *   gives one result bit for bit.
+ * Storage of the index: smi_ivf_build's layout with list_codes uint8 [capacity_slots, M] in place of list_rows; the same
+ *   SMI_IVF_LIST_ALIGN and smi_ivf_slots_bound.  A pad slot has id -1 and all codes 0.  Slots from list_offsets[K] on are
+ *   not written, except list_ids, which is -1 there.
+ * smi_ivf_pq_build: smi_ivf_build's bucketing, then one wave per slot encodes the row list_ids[slot] names.
+ * smi_ivf_pq_search: inverts the probe table, scans and merges as smi_ivf_search does; the scan decodes every tile's codes
+ *   into the flat scan's fp16 LDS image once per tile and K slice.  Score: the fp32 accumulation, in MFMA K steps of 32
+ *   ascending, of the fp16 query row against the fp16 decoded row -- the bits smi_ivf_search returns for that query against
+ *   smi_pq_decode of the row, whatever the list, slot, unit size, company or run.  idx / score: smi_ivf_search's layout,
+ *   total order and (-1, -inf) fill.  Reads nothing back, allocates nothing.
+ * workspace: device memory, 16-byte aligned, of the size the matching *_workspace_bytes function returns.
+ * Refused before any launch: what smi_ivf_build / smi_ivf_search refuse, with the same codes; dsub outside {8, 16, 32, 64}
+ *   or not dividing d (SMI_ERR_UNSUPPORTED); null or misaligned codebooks, n_iter < 0 (SMI_ERR_INVALID_ARG).  For these
+ *   shapes the sizing functions return 0. */
+int smi_pq_encode(const void* xn_f16, int64_t n, int32_t d, int32_t dsub, const void* codebooks_f16, void* codes,
+                  void* stream);
+int smi_pq_decode(const void* codes, int64_t n, int32_t d, int32_t dsub, const void* codebooks_f16, void* rows_f16,
+                  void* stream);
+int64_t smi_pq_train_workspace_bytes(int64_t n, int32_t d, int32_t dsub);
+int smi_pq_train(const void* xn_f16, int64_t n, int32_t d, int32_t dsub, const int32_t* init_rows, int32_t n_iter,
+                 void* codebooks_f16, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t smi_ivf_pq_build_workspace_bytes(int64_t n, int64_t K, int32_t d, int32_t dsub);
+int smi_ivf_pq_build(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, int64_t K, int32_t dsub,
+                     const void* codebooks_f16, void* list_codes, int32_t* list_ids, int64_t capacity_slots,
+                     int32_t* list_offsets, int32_t* list_sizes, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t smi_ivf_pq_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d, int32_t dsub);
+int smi_ivf_pq_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                      const void* list_codes, int32_t dsub, const void* codebooks_f16, const int32_t* list_ids,
+                      const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

@@ -926,6 +926,423 @@ size_t dedup_bytes(int64_t slots, int64_t K) {
   return 2 * up16((size_t)K * 4) + 2 * up16((size_t)(K + 1) * 4) + up16((size_t)slots * 4);
 }
 
+// ================================================================ product-quantised lists
+// The same lists with one byte per sub-quantiser and row: d = M * dsub, M sub-quantisers of PQ_CW = 256 codewords each,
+// codebooks fp16 [M][256][dsub], a code row uint8 [M].  The bucketing, the unit rule, the key lists and the merge above are
+// called.  New: the product quantiser (encode, train, decode), the gather that encodes, and a scan that decodes a tile's
+// codes into ivf_scan_lists_kernel's LDS image once per tile and K slice and then runs that kernel's slice loop unchanged,
+// so a score has the bits smi_ivf_search returns against the decoded row.
+constexpr int PQ_CW = 256;     // codewords of every sub-quantiser: a code is one byte
+constexpr int PQ_ROWS = 2048;  // rows one block of the training update takes of one sub-quantiser
+
+bool pq_dsub_ok(int32_t d, int32_t dsub) {
+  return (dsub == 8 || dsub == 16 || dsub == 32 || dsub == 64) && d > 0 && d % dsub == 0;
+}
+int pq_check_dsub(int32_t d, int32_t dsub) {
+  if (dsub != 8 && dsub != 16 && dsub != 32 && dsub != 64)
+    return fail(SMI_ERR_UNSUPPORTED, "dsub=%d must be 8, 16, 32 or 64", dsub);
+  if (d % dsub) return fail(SMI_ERR_UNSUPPORTED, "dsub=%d does not divide d=%d", dsub, d);
+  return SMI_OK;
+}
+int pq_check_codebooks(const void* cb) {
+  if (!cb) return fail(SMI_ERR_INVALID_ARG, "null codebooks");
+  if ((uintptr_t)cb % 16) return fail(SMI_ERR_INVALID_ARG, "codebooks must be 16-byte aligned");
+  return SMI_OK;
+}
+int pq_shift(int dsub) { return dsub == 8 ? 3 : dsub == 16 ? 4 : dsub == 32 ? 5 : 6; }
+
+// The key of subvector x against the codeword at cw, the contract's chain: n2 = c_0 c_0 + c_1 c_1 + ... ascending (the
+// product of two fp16 is exact in fp32, so fmaf(c, c, n2) is the rounded add of the header), bias = -0.5 n2 (exact),
+// key = fmaf(x_j, c_j, key) ascending from the bias.  The largest key is the Euclidean nearest codeword.
+template <int DSUB>
+__device__ __forceinline__ float pq_key(const half8 (&x)[DSUB / 8], const f16* __restrict__ cw) {
+  half8 c[DSUB / 8];
+#pragma unroll
+  for (int ch = 0; ch < DSUB / 8; ++ch) c[ch] = *(const half8*)(cw + ch * 8);
+  float n2 = 0.f;
+#pragma unroll
+  for (int ch = 0; ch < DSUB / 8; ++ch)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const float cf = (float)c[ch][e];
+      n2 = __fmaf_rn(cf, cf, n2);
+    }
+  float key = -0.5f * n2;
+#pragma unroll
+  for (int ch = 0; ch < DSUB / 8; ++ch)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) key = __fmaf_rn((float)x[ch][e], (float)c[ch][e], key);
+  return key;
+}
+
+// THE row encoder, one wave per row (every lane of the wave calls it): codes[0 .. d / DSUB) of the d fp16 at x.  Lane l
+// scores the codewords l, l + 64, l + 128, l + 192 of a sub-quantiser (ascending, a later one must beat the earlier), a
+// butterfly takes the largest key of the wave, ties to the lower code, and leaves it in every lane; lane m % 64 keeps
+// the code of sub-quantiser m and the wave stores 64 consecutive code bytes at a time.
+template <int DSUB>
+__device__ __forceinline__ void pq_encode_row_t(const f16* __restrict__ x, int d, const f16* __restrict__ cb, int lane,
+                                                uint8_t* __restrict__ codes) {
+  const int M = d / DSUB;
+  int mine = 0;
+  for (int m = 0; m < M; ++m) {
+    half8 xs[DSUB / 8];
+#pragma unroll
+    for (int ch = 0; ch < DSUB / 8; ++ch) xs[ch] = *(const half8*)(x + m * DSUB + ch * 8);
+    const f16* cm = cb + (size_t)m * PQ_CW * DSUB;
+    float best = pq_key<DSUB>(xs, cm + (size_t)lane * DSUB);
+    int bc = lane;
+#pragma unroll
+    for (int i = 1; i < PQ_CW / 64; ++i) {
+      const int c = i * 64 + lane;
+      const float key = pq_key<DSUB>(xs, cm + (size_t)c * DSUB);
+      if (key > best) {
+        best = key;
+        bc = c;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float ok = __shfl_xor(best, o, 64);
+      const int oc = __shfl_xor(bc, o, 64);
+      if (ok > best || (ok == best && oc < bc)) {
+        best = ok;
+        bc = oc;
+      }
+    }
+    if (lane == (m & 63)) mine = bc;
+    if ((m & 63) == 63 || m == M - 1) {
+      if (lane <= (m & 63)) codes[(m & ~63) + lane] = (uint8_t)mine;
+    }
+  }
+}
+
+__device__ __forceinline__ void pq_encode_row(const f16* __restrict__ x, int d, int dsub, const f16* __restrict__ cb, int lane,
+                                              uint8_t* __restrict__ codes) {
+  switch (dsub) {  // wave-uniform
+    case 8: pq_encode_row_t<8>(x, d, cb, lane, codes); break;
+    case 16: pq_encode_row_t<16>(x, d, cb, lane, codes); break;
+    case 32: pq_encode_row_t<32>(x, d, cb, lane, codes); break;
+    default: pq_encode_row_t<64>(x, d, cb, lane, codes); break;
+  }
+}
+
+__global__ __launch_bounds__(IVF_TB) void pq_encode_kernel(const f16* __restrict__ xn, int64_t n, int d, int dsub,
+                                                           const f16* __restrict__ cb, uint8_t* __restrict__ codes) {
+  const int64_t row = (int64_t)blockIdx.x * (IVF_TB / 64) + (threadIdx.x >> 6);
+  if (row >= n) return;  // wave-uniform
+  pq_encode_row(xn + (size_t)row * d, d, dsub, cb, threadIdx.x & 63, codes + (size_t)row * (d / dsub));
+}
+
+// rows[r] = the concatenation of the codewords codes[r] names: one thread per 16 bytes of output
+__global__ __launch_bounds__(IVF_TB) void pq_decode_kernel(const uint8_t* __restrict__ codes, int64_t n, int d, int dsub,
+                                                           const f16* __restrict__ cb, f16* __restrict__ rows) {
+  const int64_t t = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  const int cpr = d / 8;
+  if (t >= n * cpr) return;
+  const int64_t r = t / cpr;
+  const int k0 = (int)(t - r * cpr) * 8, m = k0 / dsub;
+  const int code = codes[(size_t)r * (d / dsub) + m];
+  *(u32x4*)(rows + (size_t)t * 8) = *(const u32x4*)(cb + ((size_t)m * PQ_CW + code) * dsub + k0 % dsub);
+}
+
+// training, the start: codeword c of every sub-quantiser = that subvector of row init[c].  One thread per 16 bytes.
+__global__ __launch_bounds__(IVF_TB) void pq_init_kernel(const f16* __restrict__ xn, int d, int dsub,
+                                                         const int32_t* __restrict__ init, f16* __restrict__ cb) {
+  const int t = blockIdx.x * IVF_TB + threadIdx.x;  // < 256 * d / 8
+  if (t >= PQ_CW * (d / 8)) return;
+  const int cpc = dsub / 8, cw = t / cpc, ch = t - cw * cpc;
+  const int m = cw / PQ_CW, c = cw - m * PQ_CW;
+  *(u32x4*)(cb + (size_t)t * 8) = *(const u32x4*)(xn + (size_t)init[c] * d + m * dsub + ch * 8);
+}
+
+// training, the update: block (row block rb, sub-quantiser m) = blockIdx.x adds the subvectors m of its PQ_ROWS rows, as
+// int64 in units of 2^-24 (exact in any order: kmeans.hip), into LDS sums [256][DSUB] and counts [256] with LDS integer
+// atomics, and flushes what is not zero with global integer atomics.  LDS: 2 KB * DSUB + 1 KB, 129 KB at DSUB = 64.
+template <int DSUB>
+constexpr int pq_accumulate_lds() { return PQ_CW * DSUB * 8 + PQ_CW * 4; }
+
+template <int DSUB>
+__global__ __launch_bounds__(IVF_TB) void pq_accumulate_kernel(const f16* __restrict__ xn, int64_t n, int d,
+                                                               const uint8_t* __restrict__ codes,
+                                                               unsigned long long* __restrict__ sums,
+                                                               int32_t* __restrict__ counts) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* ls = (unsigned long long*)smem;
+  int* lc = (int*)(smem + PQ_CW * DSUB * 8);
+  const int M = d / DSUB, tid = threadIdx.x;
+  const int m = blockIdx.x % M;
+  const int64_t r0 = (int64_t)(blockIdx.x / M) * PQ_ROWS;
+  const int64_t r1 = r0 + PQ_ROWS < n ? r0 + PQ_ROWS : n;
+  for (int i = tid; i < PQ_CW * DSUB; i += IVF_TB) ls[i] = 0ull;
+  lc[tid] = 0;  // IVF_TB == PQ_CW
+  __syncthreads();
+  for (int64_t r = r0 + tid; r < r1; r += IVF_TB) {
+    const int code = codes[(size_t)r * M + m];
+    atomicAdd(lc + code, 1);
+    const f16* x = xn + (size_t)r * d + m * DSUB;
+#pragma unroll
+    for (int ch = 0; ch < DSUB / 8; ++ch) {
+      const half8 h = *(const half8*)(x + ch * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const long long v = (long long)((float)h[e] * 0x1p24f);  // exact: an fp16 is a multiple of 2^-24 below 2^40
+        if (v != 0) atomicAdd(ls + code * DSUB + ch * 8 + e, (unsigned long long)v);
+      }
+    }
+  }
+  __syncthreads();
+  unsigned long long* gs = sums + (size_t)m * PQ_CW * DSUB;
+  for (int i = tid; i < PQ_CW * DSUB; i += IVF_TB) {
+    const unsigned long long v = ls[i];
+    if (v != 0ull) atomicAdd(gs + i, v);
+  }
+  if (lc[tid] != 0) atomicAdd(counts + m * PQ_CW + tid, lc[tid]);
+}
+static_assert(IVF_TB == PQ_CW, "one thread per codeword count");
+
+// training, the finalise: c_j = fp16_rn(fdiv_rn((float)S, (float)count) * 2^-24), the conversions and the division to
+// nearest even, the scaling exact; a codeword with no member keeps its value.  One thread per element.
+__global__ __launch_bounds__(IVF_TB) void pq_finalize_kernel(const long long* __restrict__ sums,
+                                                             const int32_t* __restrict__ counts, int d, int dsub,
+                                                             f16* __restrict__ cb) {
+  const int t = blockIdx.x * IVF_TB + threadIdx.x;
+  if (t >= PQ_CW * d) return;
+  const int count = counts[t / dsub];
+  if (count > 0) cb[t] = (f16)(__fdiv_rn(__ll2float_rn(sums[t]), (float)count) * 0x1p-24f);
+}
+
+// One wave per slot below off[K]: the codes of the row ids[slot] names, or zero codes for a pad slot.
+__global__ __launch_bounds__(IVF_TB) void ivf_pq_gather_kernel(const f16* __restrict__ xn, int d, int dsub,
+                                                               const f16* __restrict__ cb, const int32_t* __restrict__ ids,
+                                                               const int32_t* __restrict__ off, int K,
+                                                               uint8_t* __restrict__ codes) {
+  const int lane = threadIdx.x & 63, M = d / dsub;
+  const int64_t slot = (int64_t)blockIdx.x * (IVF_TB / 64) + (threadIdx.x >> 6);
+  if (slot >= off[K]) return;  // wave-uniform
+  const int id = ids[slot];
+  if (id < 0) {
+    for (int m = lane; m < M; m += 64) codes[(size_t)slot * M + m] = 0;
+  } else {
+    pq_encode_row(xn + (size_t)id * d, d, dsub, cb, lane, codes + (size_t)slot * M);
+  }
+}
+
+// ivf_scan_lists_kernel on product-quantised lists: the same units, tiles, loader mapping, swizzle, buffers, barriers, MFMA
+// order, fold and read-out (read its comment first).  What differs is where the list operand's slice comes from: thread
+// (row r, chunk cc) of slice ks owns the dimensions ks * 64 + cc * 8 .. + 8, reads the code byte of sub-quantiser
+// m = (ks * 64 + cc * 8) / dsub of its slot and gathers 16 bytes of that codeword from the codebooks (256 * d * 2 bytes,
+// which stay in L2).  Code -> codeword is two dependent round trips and one slice of prefetch covers one, so the code
+// bytes are fetched a slice further ahead than the codewords: `load(it)` gathers with the codes an earlier call left in
+// cd and fetches those of slice it + 1.  Slots at or past the end of the list are zero-filled without touching the codes;
+// a pad slot (codes 0) decodes codeword 0 of every sub-quantiser and is skipped by the fold (id -1).
+template <int KT, int B>
+__global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
+                                                                   const uint8_t* __restrict__ codes, int dshift,
+                                                                   const f16* __restrict__ cb, const int32_t* __restrict__ ids,
+                                                                   const int32_t* __restrict__ off, int K,
+                                                                   const int32_t* __restrict__ poff,
+                                                                   const int32_t* __restrict__ ubase,
+                                                                   const int32_t* __restrict__ pairs, int k_out,
+                                                                   float* __restrict__ ps, int32_t* __restrict__ pi) {
+  constexpr int OPB = B * IVF_BK * 2;  // bytes of one operand's K slice
+  constexpr int NR = B / 32;           // rows of an operand slice a thread loads; 16-row blocks of a wave per operand
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* lists = (unsigned long long*)(smem + 4 * OPB);
+  int* spair = (int*)(smem + 4 * OPB + B * KT * 8);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
+  const int b = blockIdx.x;
+  if (b >= ubase[K]) return;
+  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (ubase[mid] <= b) lo = mid;
+    else hi = mid;
+  }
+  const int l = lo;
+  const int p0 = poff[l] + (b - ubase[l]) * B;
+  const int npair = min(B, poff[l + 1] - p0);
+  const int s_begin = off[l], s_end = off[l + 1];
+
+  if (tid < B) {
+    spair[tid] = tid < npair ? pairs[p0 + tid] : -1;
+#pragma unroll
+    for (int j = 0; j < KT; ++j) lists[tid * KT + j] = XS_EMPTY;
+  }
+  __syncthreads();
+
+  const int nk = d / IVF_BK;
+  const int ntiles = (s_end - s_begin + B - 1) / B;
+  const int T = ntiles * nk;
+  const int M = d >> dshift, dsub = 1 << dshift;
+
+  // this thread's rows of a slice, and where its chunk lands in LDS
+  const int cc = tid & 7;
+  const f16* qsrc[NR];
+  int lds_off[NR];
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int r = (tid >> 3) + 32 * j;
+    const int pr = spair[r];
+    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
+    lds_off[j] = r * (IVF_BK * 2) + ((cc ^ (r & 7)) << 4);
+  }
+  u32x4 qv[NR], lv[NR];
+  unsigned cd[NR];  // the code bytes of this thread's chunk of the slice the next `load` gathers
+  auto fetch_codes = [&](int it) {
+    const int tile = it / nk, ks = it - tile * nk;
+    const int m = (ks * IVF_BK + cc * 8) >> dshift;  // < M
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
+      cd[j] = slot < s_end ? codes[(size_t)slot * M + m] : 0u;
+    }
+  };
+  auto load = [&](int it) {
+    const int tile = it / nk, ks = it - tile * nk;
+    const int k0 = ks * IVF_BK + cc * 8;
+    const f16* cw = cb + ((size_t)(k0 >> dshift) * PQ_CW << dshift) + (k0 & (dsub - 1));  // codeword 0 of the sub-quantiser
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
+      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
+      lv[j] = slot < s_end ? *(const u32x4*)(cw + ((size_t)cd[j] << dshift)) : u32x4{0u, 0u, 0u, 0u};
+    }
+    if (it + 1 < T) fetch_codes(it + 1);
+  };
+  auto store = [&](int buf) {
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      *(u32x4*)(smem + buf * 2 * OPB + lds_off[j]) = qv[j];
+      *(u32x4*)(smem + buf * 2 * OPB + OPB + lds_off[j]) = lv[j];
+    }
+  };
+
+  f32x4 acc[NR][NR];  // [slot block ai][pair block bi]
+#pragma unroll
+  for (int ai = 0; ai < NR; ++ai)
+#pragma unroll
+    for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
+  // 16-pair blocks of this wave that hold a pair at all (wave-uniform)
+  const int nb_live = min(NR, max(0, (npair - wc * (B / 2) + 15) / 16));
+
+  if (T > 0) {
+    fetch_codes(0);
+    load(0);
+    store(0);
+  }
+  __syncthreads();
+  int ks = 0, tile = 0;
+  for (int it = 0; it < T; ++it) {
+    const int buf = it & 1;
+    if (it + 1 < T) load(it + 1);
+    // 16-slot blocks of this wave below the end of the list (the lists are padded to 16 slots): wave-uniform
+    const int slot_w = s_begin + tile * B + wr * (B / 2);
+    const int na_live = min(NR, max(0, (s_end - slot_w) / 16));
+    if (na_live > 0 && nb_live > 0) {
+      const char* qs = smem + buf * 2 * OPB;
+      const char* ls = qs + OPB;
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const int ch = kk * 4 + kg;
+        half8 fa[NR], fb[NR];
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai) {
+          const int ra = wr * (B / 2) + ai * 16 + l15;
+          fa[ai] = *(const half8*)(ls + ra * (IVF_BK * 2) + ((ch ^ (ra & 7)) << 4));
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) {
+          const int rb = wc * (B / 2) + bi * 16 + l15;
+          fb[bi] = *(const half8*)(qs + rb * (IVF_BK * 2) + ((ch ^ (rb & 7)) << 4));
+        }
+#pragma unroll
+        for (int ai = 0; ai < NR; ++ai)
+          if (ai < na_live) {
+#pragma unroll
+            for (int bi = 0; bi < NR; ++bi)
+              if (bi < nb_live) acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[ai], fb[bi], acc[ai][bi], 0, 0, 0);
+          }
+      }
+    }
+    if (it + 1 < T) store(buf ^ 1);
+    if (++ks == nk) {
+      // the tile is finished: fold this wave's scores into the pairs' lists, as ivf_scan_lists_kernel does
+#pragma unroll
+      for (int ai = 0; ai < NR; ++ai) {
+        if (ai < na_live) {
+          const int slot0 = slot_w + ai * 16 + 4 * kg;  // < s_end, 16-byte aligned: off % 16 == 0
+          const int4 id4 = *(const int4*)(ids + slot0);
+          const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
+#pragma unroll
+          for (int bi = 0; bi < NR; ++bi) {
+            const int pr = wc * (B / 2) + bi * 16 + l15;
+            if (pr < npair) {
+              unsigned long long* lst = lists + pr * KT;
+              const float thr = xs_unord(
+                  (uint32_t)(__hip_atomic_load(lst + KT - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32));
+#pragma unroll
+              for (int r = 0; r < 4; ++r)
+                if (idr[r] >= 0 && acc[ai][bi][r] >= thr) xs_insert<KT>(lst, acc[ai][bi][r], idr[r]);
+            }
+          }
+        }
+#pragma unroll
+        for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      ks = 0;
+      ++tile;
+    }
+    __syncthreads();
+  }
+
+  // (the last barrier of the loop, or the one before it when the list is empty, made the lists final)
+  if (tid < npair) {
+    const int pr = spair[tid];
+    const int q = pr / nprobe, p = pr - q * nprobe;
+    const size_t o = ((size_t)p * nq + q) * k_out;
+    for (int j = 0; j < k_out; ++j) {
+      const unsigned long long key = lists[tid * KT + j];
+      const bool have = key != XS_EMPTY;
+      ps[o + j] = have ? xs_unord((uint32_t)(key >> 32)) : -INFINITY;
+      pi[o + j] = have ? (int)(0xffffffffu - (uint32_t)key) : -1;
+    }
+  }
+}
+
+template <int KT>
+hipError_t launch_pq_scan(int unit, int64_t units, hipStream_t st, const f16* qn, int d, int nq, int nprobe,
+                          const uint8_t* codes, int dshift, const f16* cb, const int32_t* ids, const int32_t* off, int K,
+                          const int32_t* poff, const int32_t* ubase, const int32_t* pairs, int k, float* ps, int32_t* pi) {
+  if (unit == IVF_BIG)
+    return launch_with_lds<ivf_pq_scan_lists_kernel<KT, IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BIG>(KT), st,
+                                                                  qn, d, nq, nprobe, codes, dshift, cb, ids, off, K, poff,
+                                                                  ubase, pairs, k, ps, pi);
+  return launch_with_lds<ivf_pq_scan_lists_kernel<KT, IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BM>(KT), st, qn,
+                                                               d, nq, nprobe, codes, dshift, cb, ids, off, K, poff, ubase,
+                                                               pairs, k, ps, pi);
+}
+
+// training: codes uint8 [n, M] | sums int64 [M][256][dsub] | counts int32 [M][256]
+size_t pq_train_bytes(int64_t n, int d, int dsub) {
+  return up16((size_t)n * (d / dsub)) + (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * (d / dsub) * 4;
+}
+// blocks of the training update: (row blocks) x M
+int64_t pq_update_blocks(int64_t n, int d, int dsub) { return (n + PQ_ROWS - 1) / PQ_ROWS * (d / dsub); }
+bool pq_rows_ok(int64_t n, int32_t d, int32_t dsub) {
+  return n >= 1 && n <= IVF_MAX && d > 0 && d % 64 == 0 && pq_dsub_ok(d, dsub);
+}
+bool pq_train_shape_ok(int64_t n, int32_t d, int32_t dsub) {
+  return pq_rows_ok(n, d, dsub) && (int64_t)PQ_CW * d <= IVF_MAX && pq_update_blocks(n, d, dsub) <= IVF_MAX;
+}
+
+template <int DSUB>
+hipError_t launch_pq_accumulate(int64_t blocks, hipStream_t st, const f16* xn, int64_t n, int d, const uint8_t* codes,
+                                unsigned long long* sums, int32_t* counts) {
+  return launch_with_lds<pq_accumulate_kernel<DSUB>>(dim3((unsigned)blocks), IVF_TB, pq_accumulate_lds<DSUB>(), st, xn, n, d,
+                                                     codes, sums, counts);
+}
+
 }  // namespace
 
 }  // namespace smi
@@ -1107,6 +1524,125 @@ int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
   auto scan = KT == 1 ? launch_i8_scan<1> : KT == 2 ? launch_i8_scan<2> : KT == 4 ? launch_i8_scan<4> : launch_i8_scan<8>;
   HIP_TRY(scan(unit, units, st, qc, qscale, d, (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets,
                (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi));
+  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  return SMI_OK;
+}
+
+// ---------------------------------------------------------------- product quantiser and product-quantised lists
+int smi_pq_encode(const void* xn, int64_t n, int32_t d, int32_t dsub, const void* codebooks, void* codes, void* stream) {
+  if (!xn || !codes) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipLaunchKernelGGL(pq_encode_kernel, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d, dsub,
+                     (const f16*)codebooks, (uint8_t*)codes);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int smi_pq_decode(const void* codes, int64_t n, int32_t d, int32_t dsub, const void* codebooks, void* rows, void* stream) {
+  if (!codes || !rows) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if ((uintptr_t)rows % 16) return fail(SMI_ERR_INVALID_ARG, "rows must be 16-byte aligned");
+  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipLaunchKernelGGL(pq_decode_kernel, grid_for(n * (d / 8), IVF_TB), dim3(IVF_TB), 0, (hipStream_t)stream, (const uint8_t*)codes,
+                     n, d, dsub, (const f16*)codebooks, (f16*)rows);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int64_t smi_pq_train_workspace_bytes(int64_t n, int32_t d, int32_t dsub) {
+  return pq_train_shape_ok(n, d, dsub) ? (int64_t)pq_train_bytes(n, d, dsub) : 0;
+}
+
+int smi_pq_train(const void* xn, int64_t n, int32_t d, int32_t dsub, const int32_t* init, int32_t n_iter, void* codebooks,
+                 void* ws, int64_t ws_bytes, void* stream) {
+  if (!xn || !init) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d must not be negative", n_iter);
+  if ((int64_t)PQ_CW * d > IVF_MAX || pq_update_blocks(n, d, dsub) > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "n=%lld, d=%d: the codebook elements and the update's blocks must fit int32", (long long)n, d);
+  if (const int rc = check_ws(ws, ws_bytes, (int64_t)pq_train_bytes(n, d, dsub), "smi_pq_train_workspace_bytes(n, d, dsub)"))
+    return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const int M = d / dsub;
+  uint8_t* codes = (uint8_t*)ws;
+  unsigned long long* sums = (unsigned long long*)((char*)ws + up16((size_t)n * M));
+  int32_t* counts = (int32_t*)(sums + (size_t)PQ_CW * d);
+  const dim3 block(IVF_TB);
+  hipLaunchKernelGGL(pq_init_kernel, grid_for((int64_t)PQ_CW * (d / 8), IVF_TB), block, 0, st, (const f16*)xn, d, dsub, init,
+                     (f16*)codebooks);
+  HIP_TRY(hipGetLastError());
+  const int64_t blocks = pq_update_blocks(n, d, dsub);
+  auto accumulate = dsub == 8 ? launch_pq_accumulate<8> : dsub == 16 ? launch_pq_accumulate<16>
+                  : dsub == 32 ? launch_pq_accumulate<32> : launch_pq_accumulate<64>;
+  for (int it = 0; it < n_iter; ++it) {
+    hipLaunchKernelGGL(pq_encode_kernel, grid_for(n, IVF_TB / 64), block, 0, st, (const f16*)xn, n, d, dsub,
+                       (const f16*)codebooks, codes);
+    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * M * 4, st));  // the sums and the counts behind them
+    HIP_TRY(accumulate(blocks, st, (const f16*)xn, n, d, codes, sums, counts));
+    hipLaunchKernelGGL(pq_finalize_kernel, grid_for((int64_t)PQ_CW * d, IVF_TB), block, 0, st, (const long long*)sums, counts, d,
+                       dsub, (f16*)codebooks);
+    HIP_TRY(hipGetLastError());
+  }
+  return SMI_OK;
+}
+
+int64_t smi_ivf_pq_build_workspace_bytes(int64_t n, int64_t K, int32_t d, int32_t dsub) {
+  return build_shape_ok(n, K, d) && pq_dsub_ok(d, dsub) ? (int64_t)build_bytes(K) : 0;
+}
+
+int smi_ivf_pq_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, int32_t dsub,
+                     const void* codebooks, void* list_codes, int32_t* list_ids, int64_t capacity_slots,
+                     int32_t* list_offsets, int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
+  if (!xn || !labels || !list_codes || !list_ids || !list_offsets || !list_sizes)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_pq_build_workspace_bytes(n, K, d, dsub)"))
+    return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, (int32_t*)ws, st));
+  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
+  hipLaunchKernelGGL(ivf_pq_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d, dsub,
+                     (const f16*)codebooks, list_ids, list_offsets, (int)K, (uint8_t*)list_codes);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int64_t smi_ivf_pq_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d, int32_t dsub) {
+  return search_shape_ok(nq, K, nprobe, k, d) && pq_dsub_ok(d, dsub) ? (int64_t)search_bytes(nq, K, nprobe, k) : 0;
+}
+
+int smi_ivf_pq_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
+                      int32_t dsub, const void* codebooks, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
+                      int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
+  if (!qn || !probes || !list_codes || !list_ids || !list_offsets || !idx || !score)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  const int64_t P = nq * nprobe;
+  if (const int rc = check_ws(ws, ws_bytes, (int64_t)search_bytes(nq, K, nprobe, k),
+                              "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)"))
+    return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const SearchWs w(ws, P, K, k);
+  const int unit = unit_pairs(P, K);  // the flat search's rule: the image and the MFMA work of a unit are the same
+  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
+  const int64_t units = units_bound(P, K, unit);
+  const int KT = k == 1 ? 1 : k == 2 ? 2 : k <= 4 ? 4 : 8;
+  auto scan = KT == 1 ? launch_pq_scan<1> : KT == 2 ? launch_pq_scan<2> : KT == 4 ? launch_pq_scan<4> : launch_pq_scan<8>;
+  HIP_TRY(scan(unit, units, st, (const f16*)qn, d, (int)nq, nprobe, (const uint8_t*)list_codes, pq_shift(dsub),
+               (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi));
   HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
   return SMI_OK;
 }

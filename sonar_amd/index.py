@@ -21,8 +21,15 @@ embeddings may have heavier-tailed rows, where a per-row scale loses more.
 
 `IVFFlatIndex.self_join` and `sonar_amd.dedup` are the de-duplication over the flat lists.
 
-Not here: product quantisation and fewer than 8 bits, nprobe or k above 8, incremental add and
-removal, 64-bit ids, splitting of long lists, multi-GPU sharding.
+`ProductQuantizer` and `IVFPQIndex` are the same index over product-quantised rows: d / dsub bytes per row,
+one byte per sub-quantiser of 256 codewords, 1/16 (dsub = 8) to 1/128 (dsub = 64) of the fp16 rows.  The scan decodes a
+tile's codes into the flat scan's fp16 image once per tile, so a raw score is bit for bit the flat index's score against the
+reconstructed row (tests/ivf_pq_ref.py); `search(..., refine=xn)` re-scores the candidates like the int8 index.  The quality
+was measured on synthetic planted data only, whose noise is isotropic and does not compress; real SONAR rows are unmeasured.
+
+Not here: residual encoding against the list centroid, an OPQ rotation, a look-up-table scan for a handful of
+queries, codes of fewer than 8 bits, nprobe or k above 8, de-duplication over quantised lists, incremental add and removal,
+64-bit ids, splitting of long lists, multi-GPU sharding.
 """
 from __future__ import annotations
 
@@ -31,13 +38,15 @@ from typing import Dict, Optional, Tuple, Union
 import torch
 
 from . import _lib
-from .clustering import SphericalKMeans
+from .clustering import SphericalKMeans, init_rows
 from .mining import pair_scores
 from .xsim import normalize_rows, topk_normalized
 
 LIST_ALIGN = 16    # SMI_IVF_LIST_ALIGN: every list starts at a multiple of this many slots and is padded to it
 UNIT_QUERIES = 64  # SMI_IVF_UNIT_QUERIES: queries of one list that one work unit of the scan takes (128 when nq nprobe >= 256 K)
 INT8_MAX_DIM = 131072  # SMI_IVF_I8_MAX_DIM: above it the int32 sum of int8 products could overflow
+PQ_CODEWORDS = 256  # codewords of every sub-quantiser: a code is one byte
+PQ_DSUBS = (8, 16, 32, 64)  # dimensions per sub-quantiser
 
 
 def _check_matrix(t, name: str) -> None:
@@ -112,8 +121,7 @@ def _build(xn, labels, n_lists: int, int8: bool):
     return (rows, *scales, ids, offsets, sizes)
 
 
-def _search(qn, probes, rows, scales, ids, offsets, k: int):
-    """smi_ivf_search (scales None) / smi_ivf_i8_search."""
+def _check_search_args(qn, probes, k) -> None:
     _check_small(k, "k")
     _check_matrix(qn, "qn")
     if qn.dtype != torch.float16 or not qn.is_contiguous():
@@ -122,6 +130,11 @@ def _search(qn, probes, rows, scales, ids, offsets, k: int):
                                              or not 1 <= probes.shape[0] <= qn.shape[0]):
         raise ValueError(f"probes must be [nq, 1..8] with nq <= {qn.shape[0]} rows, got {list(probes.shape)}")
     _check_table(probes, "probes", *(probes.shape if isinstance(probes, torch.Tensor) else (-1, 1)))
+
+
+def _search(qn, probes, rows, scales, ids, offsets, k: int):
+    """smi_ivf_search (scales None) / smi_ivf_i8_search."""
+    _check_search_args(qn, probes, k)
     int8 = scales is not None
     if int8:
         _check_int8_dim(qn.shape[1])
@@ -192,13 +205,223 @@ def search_lists_int8(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tenso
     return _search(qn, probes, codes, scales, ids, offsets, k)
 
 
+def _check_codebooks(codebooks, d: Optional[int] = None) -> Tuple[int, int]:
+    """(M, dsub) of fp16 codebooks [M, 256, dsub] on the device; d: the row width they must add up to."""
+    if not isinstance(codebooks, torch.Tensor):
+        raise TypeError("codebooks must be a torch.Tensor")
+    if not codebooks.is_cuda:
+        raise RuntimeError("codebooks: the index runs on a HIP device only (no CPU path)")
+    if (codebooks.dtype != torch.float16 or codebooks.dim() != 3 or codebooks.shape[1] != PQ_CODEWORDS
+            or codebooks.shape[2] not in PQ_DSUBS or codebooks.shape[0] < 1 or not codebooks.is_contiguous()):
+        raise ValueError(f"codebooks must be contiguous fp16 [M, {PQ_CODEWORDS}, dsub] with dsub in {PQ_DSUBS}, got "
+                         f"{codebooks.dtype} {list(codebooks.shape)}")
+    m, dsub = codebooks.shape[0], codebooks.shape[2]
+    if (m * dsub) % 64:
+        raise ValueError(f"codebooks: dim = {m} * {dsub} must be a multiple of 64")
+    if d is not None and m * dsub != d:
+        raise ValueError(f"codebooks cover dim {m} * {dsub} = {m * dsub}, the rows have {d}")
+    return m, dsub
+
+
+def _check_dsub(dsub, d: int) -> None:
+    if isinstance(dsub, bool) or not isinstance(dsub, int) or dsub not in PQ_DSUBS:
+        raise ValueError(f"dsub = {dsub!r}: one of {PQ_DSUBS}")
+    if d % dsub:
+        raise ValueError(f"dsub = {dsub} does not divide dim = {d}")
+
+
+def _check_codes(codes, name: str, m: int) -> None:
+    if not isinstance(codes, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not codes.is_cuda:
+        raise RuntimeError(f"{name}: the index runs on a HIP device only (no CPU path)")
+    if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[0] < 1 or codes.shape[1] != m or not codes.is_contiguous():
+        raise ValueError(f"{name} must be contiguous uint8 [rows, {m}], got {codes.dtype} {list(codes.shape)}")
+
+
+def _check_rows16(xn, name: str, n) -> int:
+    _check_matrix(xn, name)
+    if xn.dtype != torch.float16 or not xn.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous fp16 matrix")
+    n = xn.shape[0] if n is None else n
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= xn.shape[0]:
+        raise ValueError(f"n = {n!r}: between 1 and the {xn.shape[0]} rows of {name}")
+    return n
+
+
+def pq_train(xn: torch.Tensor, dsub: int, init: torch.Tensor, n_iter: int = 10, n: Optional[int] = None) -> torch.Tensor:
+    """smi_pq_train: codebooks fp16 [d / dsub, 256, dsub] after n_iter Lloyd rounds on the first n rows (default: all) of xn
+    (contiguous fp16 [>= n, d], rows of `normalize_rows`), started from the subvectors of the rows init names (device int32
+    [256], values in [0, n): not checked here).  No read-back; one init gives one result bit for bit."""
+    n = _check_rows16(xn, "xn", n)
+    d = xn.shape[1]
+    _check_dsub(dsub, d)
+    if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+        raise ValueError(f"n_iter = {n_iter!r}: a non-negative integer")
+    _check_table(init, "init", PQ_CODEWORDS, None)
+    lib = _lib.load()
+    ws_bytes = int(lib.smi_pq_train_workspace_bytes(n, d, dsub))
+    if ws_bytes < 1:
+        raise ValueError(f"{n} rows of dim {d}: too large for one training call")
+    codebooks = torch.empty((d // dsub, PQ_CODEWORDS, dsub), dtype=torch.float16, device=xn.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xn.device)
+    init = init.contiguous()
+    with torch.cuda.device(xn.device):
+        _lib.check(lib.smi_pq_train(xn.data_ptr(), n, d, dsub, init.data_ptr(), n_iter, codebooks.data_ptr(), ws.data_ptr(),
+                                    ws_bytes, _lib.current_stream_ptr()))
+    return codebooks
+
+
+def pq_encode(xn: torch.Tensor, codebooks: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
+    """smi_pq_encode: codes uint8 [n, M] of the first n rows (default: all) of xn (contiguous fp16 [>= n, d]) against
+    codebooks (fp16 [M, 256, dsub]): per sub-quantiser the Euclidean nearest codeword by the fp32 chain of
+    tests/ivf_pq_ref.py, ties to the lower code."""
+    n = _check_rows16(xn, "xn", n)
+    m, dsub = _check_codebooks(codebooks, xn.shape[1])
+    lib = _lib.load()
+    codes = torch.empty((n, m), dtype=torch.uint8, device=xn.device)
+    with torch.cuda.device(xn.device):
+        _lib.check(lib.smi_pq_encode(xn.data_ptr(), n, xn.shape[1], dsub, codebooks.data_ptr(), codes.data_ptr(),
+                                     _lib.current_stream_ptr()))
+    return codes
+
+
+def pq_decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """smi_pq_decode: rows fp16 [n, d], row r the concatenation of the codewords codes[r] (uint8 [n, M]) names."""
+    m, dsub = _check_codebooks(codebooks)
+    _check_codes(codes, "codes", m)
+    lib = _lib.load()
+    rows = torch.empty((codes.shape[0], m * dsub), dtype=torch.float16, device=codes.device)
+    with torch.cuda.device(codes.device):
+        _lib.check(lib.smi_pq_decode(codes.data_ptr(), codes.shape[0], m * dsub, dsub, codebooks.data_ptr(), rows.data_ptr(),
+                                     _lib.current_stream_ptr()))
+    return rows
+
+
+def build_lists_pq(xn: torch.Tensor, labels: torch.Tensor, n_lists: int, codebooks: torch.Tensor):
+    """smi_ivf_pq_build: `build_lists` with every row encoded against codebooks (fp16 [M, 256, dsub]).  Returns (codes uint8
+    [slots, M], ids, offsets, sizes); a pad slot has zero codes and id -1."""
+    _check_build_args(xn, labels, n_lists)
+    m, dsub = _check_codebooks(codebooks, xn.shape[1])
+    lib = _lib.load()
+    n, d, dev = labels.shape[0], xn.shape[1], xn.device
+    cap = int(lib.smi_ivf_slots_bound(n, n_lists))
+    if cap < 1:
+        raise ValueError(f"{n} rows over {n_lists} lists: slot numbers must fit int32")
+    codes = torch.empty((cap, m), dtype=torch.uint8, device=dev)
+    ids = torch.empty((cap,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((n_lists + 1,), dtype=torch.int32, device=dev)
+    sizes = torch.empty((n_lists,), dtype=torch.int32, device=dev)
+    ws_bytes = int(lib.smi_ivf_pq_build_workspace_bytes(n, n_lists, d, dsub))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    labels = labels.contiguous()
+    with torch.cuda.device(dev):
+        _lib.check(lib.smi_ivf_pq_build(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, dsub, codebooks.data_ptr(),
+                                        codes.data_ptr(), ids.data_ptr(), cap, offsets.data_ptr(), sizes.data_ptr(),
+                                        ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+    return codes, ids, offsets, sizes
+
+
+def search_lists_pq(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, codebooks: torch.Tensor, ids: torch.Tensor,
+                    offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_pq_search: `search_lists` against the storage `build_lists_pq` returned.  A score has the bits `search_lists`
+    returns for the query against `pq_decode` of the row."""
+    _check_search_args(qn, probes, k)
+    m, dsub = _check_codebooks(codebooks, qn.shape[1])
+    _check_codes(codes, "codes", m)
+    lib = _lib.load()
+    (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
+    ws_bytes = int(lib.smi_ivf_pq_search_workspace_bytes(nq, n_lists, nprobe, k, d, dsub))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
+    score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
+    probes = probes.contiguous()
+    with torch.cuda.device(qn.device):
+        _lib.check(lib.smi_ivf_pq_search(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, codes.data_ptr(), dsub,
+                                         codebooks.data_ptr(), ids.data_ptr(), offsets.data_ptr(), n_lists, k, idx.data_ptr(),
+                                         score.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+    return score, idx
+
+
+class ProductQuantizer:
+    """M = d / dsub sub-quantisers of 256 codewords each over rows of `normalize_rows`.
+
+    codebooks: fp16 [M, 256, dsub] on the device, dsub in {8, 16, 32, 64}, M * dsub a multiple of 64 (copied)."""
+
+    def __init__(self, codebooks: torch.Tensor):
+        self._m, self._dsub = _check_codebooks(codebooks)
+        self._codebooks = codebooks.clone()
+
+    @classmethod
+    def train(cls, x: torch.Tensor, dsub: int = 16, n_iter: int = 10, seed: int = 0, init: Optional[torch.Tensor] = None):
+        """Lloyd rounds on `normalize_rows(x)` (x fp16 / fp32 [n, d] on the device).  init: None (256 distinct rows from
+        `clustering.init_rows(n, 256, seed)`, so n >= 256) or 256 row numbers (a host or device integer tensor); a row named
+        twice gives twin codewords, of which the higher code never gets a member and keeps its value."""
+        _check_matrix(x, "x")
+        n, d = x.shape
+        _check_dsub(dsub, d)
+        if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
+            raise ValueError(f"n_iter = {n_iter!r}: a non-negative integer")
+        if init is None:
+            init = init_rows(n, PQ_CODEWORDS, seed)
+        else:
+            if not isinstance(init, torch.Tensor) or init.dtype not in (torch.int32, torch.int64) or tuple(init.shape) != (PQ_CODEWORDS,):
+                raise ValueError(f"init must be an integer tensor of {PQ_CODEWORDS} row numbers")
+            if init.device.type != "meta" and not bool(((init >= 0) & (init < n)).all()):
+                raise ValueError(f"init names rows outside [0, {n})")
+        xn = normalize_rows(x)
+        return cls(pq_train(xn, dsub, init.to(device=x.device, dtype=torch.int32), n_iter, n))
+
+    @property
+    def codebooks(self) -> torch.Tensor:
+        return self._codebooks
+
+    @property
+    def dim(self) -> int:
+        return self._m * self._dsub
+
+    @property
+    def dsub(self) -> int:
+        return self._dsub
+
+    @property
+    def n_subquantizers(self) -> int:
+        return self._m
+
+    def encode(self, x: torch.Tensor) -> torch.Tensor:
+        """codes uint8 [n, M] of `normalize_rows(x)` (x fp16 / fp32 [n, d] on the device)."""
+        _check_matrix(x, "x")
+        if x.shape[1] != self.dim:
+            raise ValueError(f"x has dim {x.shape[1]}, the codebooks {self.dim}")
+        return pq_encode(normalize_rows(x), self._codebooks, x.shape[0])
+
+    def decode(self, codes: torch.Tensor) -> torch.Tensor:
+        """fp16 [n, d]: the reconstructed rows of codes (uint8 [n, M])."""
+        return pq_decode(codes, self._codebooks)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        return {"codebooks": self._codebooks.clone()}
+
+    @classmethod
+    def from_state_dict(cls, state: Dict[str, torch.Tensor]):
+        if "codebooks" not in state:
+            raise ValueError("state lacks ['codebooks']")
+        return cls(state["codebooks"])
+
+
 class _IVFIndex:
-    """What `IVFFlatIndex` and `IVFInt8Index` share: the quantiser, the probe, the argument checks and the persistence.  A
-    subclass names its storage (`_ROWS_DTYPE`, `_STORAGE`: the attributes `add` fills, in the order of its build entry) and
-    gives `_build_lists` and `_search_lists`."""
+    """What the IVF indexes share: the quantiser, the probe, the argument checks and the persistence.  A subclass names its
+    storage (`_ROWS_DTYPE`, `_ROWS_NAME`, `_STORAGE`: the attributes `add` fills, in the order of its build entry; `_EXTRA`:
+    further tensors of its state; `_row_width`: the columns of `rows`) and gives `_build_lists` and `_search_lists`."""
 
     _ROWS_DTYPE = torch.float16
+    _ROWS_NAME = "fp16"
     _STORAGE = ("_rows", "_ids", "_offsets", "_sizes")
+    _EXTRA = ()
+
+    def _check_extra(self, state, d: int, fresh: bool):
+        """load_state_dict: (the columns `rows` must have, the attributes to take over from the `_EXTRA` entries)."""
+        return d, {}
 
     def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor]):
         if isinstance(quantizer, SphericalKMeans):
@@ -311,13 +534,15 @@ class _IVFIndex:
 
     # ------------------------------------------------------------------------------------------------ persistence
     def state_dict(self) -> Dict[str, torch.Tensor]:
-        """centroids (fp16 [K, d], normalised), offsets, sizes, ids and rows (and scales, where the rows are int8 codes); the
-        storage is cut to the slots in use (one read-back)."""
+        """centroids (fp16 [K, d], normalised), offsets, sizes, ids and rows (and scales, where the rows are int8 codes, or
+        codebooks, where they are product-quantiser codes); the storage is cut to the slots in use (one read-back)."""
         self._need_add("state_dict")
         used = int(self._offsets[self._k].item())
         state = {"centroids": self._c16[: self._k].clone(), "offsets": self._offsets.clone(), "sizes": self._sizes.clone()}
         for name in self._STORAGE[:-2]:
             state[name[1:]] = getattr(self, name)[:used].clone()
+        for name in self._EXTRA:
+            state[name[1:]] = getattr(self, name).clone()
         return state
 
     @classmethod
@@ -329,7 +554,7 @@ class _IVFIndex:
 
     def load_state_dict(self, state: Dict[str, torch.Tensor], _fresh: bool = False):
         """Take over a `state_dict()` (tensors on the device).  The centroids must have this index's shape."""
-        missing = {"centroids", "offsets", "sizes", *(name[1:] for name in self._STORAGE[:-2])} - set(state)
+        missing = {"centroids", "offsets", "sizes", *(name[1:] for name in self._STORAGE[:-2] + self._EXTRA)} - set(state)
         if missing:
             raise ValueError(f"state lacks {sorted(missing)}")
         c = state["centroids"]
@@ -343,8 +568,9 @@ class _IVFIndex:
         _check_table(state["sizes"], "sizes", k, None)
         rows, ids = state["rows"], state["ids"]
         _check_table(ids, "ids", rows.shape[0] if isinstance(rows, torch.Tensor) else -1, None)
-        if not rows.is_cuda or rows.dtype != self._ROWS_DTYPE or rows.dim() != 2 or rows.shape[1] != d:
-            raise ValueError(f"rows must be {'fp16' if self._ROWS_DTYPE == torch.float16 else 'int8'} [slots, {d}] on the device")
+        width, extra = self._check_extra(state, d, _fresh)
+        if not rows.is_cuda or rows.dtype != self._ROWS_DTYPE or rows.dim() != 2 or rows.shape[1] != width:
+            raise ValueError(f"rows must be {self._ROWS_NAME} [slots, {width}] on the device")
         scales = state["scales"] if "_scales" in self._STORAGE else None
         if scales is not None and (not isinstance(scales, torch.Tensor) or not scales.is_cuda
                                    or scales.dtype != torch.float32 or tuple(scales.shape) != (rows.shape[0],)):
@@ -360,6 +586,8 @@ class _IVFIndex:
         self._ids, self._rows = ids.contiguous().clone(), rows.contiguous().clone()
         if scales is not None:
             self._scales = scales.contiguous().clone()
+        for name, t in extra.items():
+            setattr(self, name, t)
         self._added = True
         return self
 
@@ -403,6 +631,7 @@ class IVFInt8Index(_IVFIndex):
     `state_dict` adds `scales`, and its `rows` are the int8 codes."""
 
     _ROWS_DTYPE = torch.int8
+    _ROWS_NAME = "int8"
     _STORAGE = ("_rows", "_scales", "_ids", "_offsets", "_sizes")
 
     def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor]):
@@ -433,6 +662,69 @@ class IVFInt8Index(_IVFIndex):
 
     def self_join(self, *args, **kwargs):
         raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFInt8Index holds int8 codes")
+
+
+class IVFPQIndex(_IVFIndex):
+    """`IVFFlatIndex` over product-quantised rows: d / dsub bytes per row.  A raw score is the flat index's
+    score against the reconstructed row, bit for bit.  `state_dict` adds `codebooks`, and its `rows` are the uint8 codes.
+
+    quantizer: as for `IVFFlatIndex`; pq: a `ProductQuantizer` of the same dim, or its fp16 [M, 256, dsub] codebooks."""
+
+    _ROWS_DTYPE = torch.uint8
+    _ROWS_NAME = "uint8"
+    _EXTRA = ("_codebooks",)
+
+    def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor], pq: Union[ProductQuantizer, torch.Tensor]):
+        super().__init__(quantizer)
+        if not isinstance(pq, ProductQuantizer):
+            pq = ProductQuantizer(pq)
+        if pq.dim != self._d:
+            raise ValueError(f"the product quantiser has dim {pq.dim}, the centroids {self._d}")
+        self._codebooks = pq.codebooks.clone()
+
+    @classmethod
+    def train(cls, x: torch.Tensor, n_lists: int, dsub: int = 16, n_iter: int = 10, pq_iter: int = 8, seed: int = 0):
+        """Fit the coarse quantiser (spherical k-means, `n_lists` clusters, n_iter rounds) and the product quantiser (dsub
+        dimensions per sub-quantiser, pq_iter Lloyd rounds) on x (fp16 / fp32 [n, d] on the device, n >= 256)."""
+        _check_matrix(x, "x")
+        _check_dsub(dsub, x.shape[1])
+        return cls(SphericalKMeans(n_lists, n_iter=n_iter, seed=seed).fit(x),
+                   ProductQuantizer.train(x, dsub=dsub, n_iter=pq_iter, seed=seed))
+
+    @property
+    def codebooks(self) -> torch.Tensor:
+        return self._codebooks
+
+    @property
+    def dsub(self) -> int:
+        return self._codebooks.shape[2]
+
+    def _build_lists(self, xn, labels):
+        return build_lists_pq(xn, labels, self._k, self._codebooks)
+
+    def _search_lists(self, qn, probes, k):
+        return search_lists_pq(qn, probes, self._rows, self._codebooks, self._ids, self._offsets, k)
+
+    def _check_extra(self, state, d: int, fresh: bool):
+        codebooks = state["codebooks"]
+        m, _ = _check_codebooks(codebooks, d)
+        return m, {"_codebooks": codebooks.clone()}
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
+               refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`IVFFlatIndex.search` on the reconstructed rows.  refine: as for `IVFInt8Index.search`, the normalised fp16 corpus
+        the index was built from; the k candidates are re-scored with their fp16 cosines and re-ordered."""
+        if refine is not None:
+            _check_matrix(refine, "refine")
+            if refine.dtype != torch.float16 or not refine.is_contiguous() or refine.shape[1] != self._d:
+                raise ValueError(f"refine must be the contiguous fp16 [rows, {self._d}] matrix normalize_rows returned")
+        score, idx, qn = self._checked_search(q, k, nprobe, probes)
+        if refine is None:
+            return score, idx
+        return refine_candidates(qn, q.shape[0], refine, idx)
+
+    def self_join(self, *args, **kwargs):
+        raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFPQIndex holds product-quantiser codes")
 
 
 def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
