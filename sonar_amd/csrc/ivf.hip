@@ -7,18 +7,25 @@
 // (query, probe slot) pairs by list -- the inverted probe table -- so that a work unit of the scan is ONE list and up to
 // 64 or 128 of the pairs that probe it: the list's rows are read once per unit, not once per query.
 //
-// The scan unit walks its list in tiles of as many slots as it has pairs; a tile's scores are fp16 MFMA products
-// (v_mfma_f32_16x16x32_f16, fp32 accumulators, K slices ascending: the bits of a score depend on the two rows alone) that
-// are folded into one running top-k per pair, the LDS key lists of xsim.hip.  A pair's list is written to the partial
-// array [nprobe][nq][k]; smi_xsim_merge_topk's kernel merges the nprobe parts.  No atomics on results.
-//
-// The second half of the file is the same index over int8 scalar-quantised rows: the bucketing, the unit
-// rule, the key lists and the merge above are called; the row quantiser, the gather that encodes and the integer-MFMA scan
-// are new.
+// The scan unit walks its list in tiles of as many slots as it has pairs; a tile's scores are MFMA products, K slices
+// ascending (the bits of a score depend on the two rows alone), that are folded into one running top-k per pair, the LDS key
+// lists of xsim.hip.  A pair's list is written to the partial array [nprobe][nq][k]; smi_xsim_merge_topk's kernel merges
+// the nprobe parts.  No atomics on results.  The unit itself -- lookup, pair table, slice loop, fold, read-out -- is
+// ivf_scan.hpp (read its comment first).  Four kernels here walk lists that way:
+//   ivf_scan_lists_kernel      fp16 rows (3.18): ivf_scan.hpp's functions; fetches both operands from memory;
+//   ivf_pq_scan_lists_kernel   product-quantised rows (3.21): the same functions, so a score has the flat scan's bits BY
+//                              CONSTRUCTION; the list operand is decoded from the codebooks in the fetch;
+//   ivf_i8_scan_lists_kernel   int8 codes and one fp32 scale per row (3.19): the integer MFMA, the scales enter in the fold;
+//   ivf_selfjoin_kernel        SemDeDup's per-list self-join (3.20): the unit's rows are list rows, its own fold and ending.
+// The last two spell the same loop out in their own text (keep it equal to ivf_slice_walk's): as instances of the
+// function the 128-row self-join waited for the prefetched slice in front of its MFMAs, and the int8 scan measured
+// 0.2-0.4 % slower in two cells of one round of two (profiles/isa_identity_ivf.txt).  The bucketing, the unit rule, the merge and the host halves are shared by calls; the quantisers (int8 rows; PQ encode,
+// train, decode) and the gathers that encode follow their scans.
 #include "api_common.hpp"
-#include "common.hpp"
-#include "topk_order.hpp"
+#include "ivf_scan.hpp"
 #include "wave_claim.hpp"
+
+#include <type_traits>
 
 using namespace smi;
 using namespace smi_host;
@@ -27,17 +34,14 @@ namespace smi {
 
 namespace {
 
-constexpr int IVF_TB = 256;    // threads per block of every kernel here
 constexpr int IVF_ALIGN = SMI_IVF_LIST_ALIGN;  // slots: one 16-row A block of the 16x16x32 MFMA
 constexpr int IVF_BM = SMI_IVF_UNIT_QUERIES;   // (query, probe slot) pairs of a scan unit = slots of its tiles ...
 constexpr int IVF_BIG = 2 * IVF_BM;            // ... or twice that, where the lists are probed by many pairs
-constexpr int IVF_BK = 64;     // fp16 of a K slice: 128 B of a row, two MFMA K steps
+constexpr int IVF_BK = IVF_SLICE / 2;  // fp16 of a K slice
 constexpr int64_t IVF_MAX = 0x7fffff00LL;
 
 static_assert(IVF_ALIGN == 16, "a 16-slot A block of the scan's MFMA never spans two lists");
-static_assert(IVF_BM == 64 && IVF_TB == 256, "the slice loader maps 256 threads to 32 rows x 8 chunks, B / 32 times; 2 x 2 waves");
-
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+static_assert(IVF_BM == 64, "the slice loader takes B / 32 passes");
 
 // ---------------------------------------------------------------- bucketing (the k-means pattern, for any int32 keys)
 __global__ __launch_bounds__(IVF_TB) void ivf_hist_kernel(const int32_t* __restrict__ keys, int n, int K,
@@ -127,20 +131,10 @@ __global__ __launch_bounds__(IVF_TB) void ivf_fill_kernel(float* __restrict__ ps
   }
 }
 
-// Workgroup b = unit b - ubase[l] of the list l with ubase[l] <= b < ubase[l + 1]: pairs poff[l] + B * that .. of the
-// bucketed pair order against the slots off[l] .. off[l + 1].  A unit is B pairs and walks the list in tiles of B slots,
-// B = 64 or 128 (chosen by the host from the shapes alone; the bits of a score do not depend on it).
-//   Why the tile is as large as it is: every K slice of a tile is read from L2 (the list rows are shared by the units of the
-//   list, the query rows are re-read for every tile), 2 * B * 128 bytes for B * B * 128 flop -- B / 2 flop per byte: at
-//   B = 64 the scan ran at the L2's ~10 TB/s and 0.13 of the MFMA peak (profiles/ivf_experiments.txt, item 1).
-//   LDS: two K-slice buffers {pairs' query rows [B][128 B], tile's list rows [B][128 B]} (the 16-B chunk c of row r sits at
-//   chunk c ^ (r & 7): the fragment reads of 16 consecutive rows spread over all banks), the key lists [B][KT], the pair
-//   numbers [B].  Thread t loads chunk t & 7 of rows (t >> 3) + 32 j of both operands for slice i + 1 into registers
-//   while the MFMAs of slice i run, and stores them to the other buffer behind them: one barrier per slice.
-//   Wave (wr, wc) owns slots wr * B / 2 .. of the tile (the A operand: rows of D) against pairs wc * B / 2 .. (B: columns
-//   of D), so lane (l15, kg) holds pair wc * B / 2 + bi * 16 + l15 x slots wr * B / 2 + ai * 16 + 4 kg + r.
+// The unit of ivf_scan.hpp with pairs poff[l] + B * (b - ubase[l]) .. of the bucketed pair order as its rows: the query rows
+// the pairs name.  LDS behind the slice buffers: the key lists [B][KT], the pair numbers [B].
 template <int B>
-constexpr int ivf_scan_lds(int KT) { return 2 * 2 * B * IVF_BK * 2 + B * KT * 8 + B * 4; }
+constexpr int ivf_scan_lds(int KT) { return 2 * 2 * B * IVF_SLICE + B * KT * 8 + B * 4; }
 
 template <int KT, int B>
 __global__ __launch_bounds__(IVF_TB) void ivf_scan_lists_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
@@ -150,50 +144,26 @@ __global__ __launch_bounds__(IVF_TB) void ivf_scan_lists_kernel(const f16* __res
                                                                 const int32_t* __restrict__ ubase,
                                                                 const int32_t* __restrict__ pairs, int k_out,
                                                                 float* __restrict__ ps, int32_t* __restrict__ pi) {
-  constexpr int OPB = B * IVF_BK * 2;  // bytes of one operand's K slice
-  constexpr int NR = B / 32;           // rows of an operand slice a thread loads; 16-row blocks of a wave per operand
+  constexpr int NR = B / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* lists = (unsigned long long*)(smem + 4 * OPB);
-  int* spair = (int*)(smem + 4 * OPB + B * KT * 8);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
-  const int b = blockIdx.x;
+  unsigned long long* lists = (unsigned long long*)(smem + 4 * B * IVF_SLICE);
+  int* spair = (int*)(lists + B * KT);
+  const int tid = threadIdx.x, b = blockIdx.x;
   if (b >= ubase[K]) return;
-  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ubase[mid] <= b) lo = mid;
-    else hi = mid;
-  }
-  const int l = lo;
+  const int l = ivf_unit_list(ubase, K, b);
   const int p0 = poff[l] + (b - ubase[l]) * B;
   const int npair = min(B, poff[l + 1] - p0);
   const int s_begin = off[l], s_end = off[l + 1];
+  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [](int) {});
 
-  if (tid < B) {
-    spair[tid] = tid < npair ? pairs[p0 + tid] : -1;
-#pragma unroll
-    for (int j = 0; j < KT; ++j) lists[tid * KT + j] = XS_EMPTY;
-  }
-  __syncthreads();
-
-  const int nk = d / IVF_BK;
-  const int ntiles = (s_end - s_begin + B - 1) / B;
-  const int T = ntiles * nk;
-
-  // this thread's rows of a slice, and where its chunk lands in LDS
-  const int cc = tid & 7;
-  const f16* qsrc[NR];
-  int lds_off[NR];
+  const int nk = d / IVF_BK, cc = tid & 7;
+  const f16* qsrc[NR];  // this thread's query rows of a slice
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
-    const int r = (tid >> 3) + 32 * j;
-    const int pr = spair[r];
+    const int pr = spair[(tid >> 3) + 32 * j];
     qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
-    lds_off[j] = r * (IVF_BK * 2) + ((cc ^ (r & 7)) << 4);
   }
-  u32x4 qv[NR], lv[NR];
-  auto load = [&](int it) {
+  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {
     const int tile = it / nk, ks = it - tile * nk;
 #pragma unroll
     for (int j = 0; j < NR; ++j) {
@@ -202,106 +172,12 @@ __global__ __launch_bounds__(IVF_TB) void ivf_scan_lists_kernel(const f16* __res
       lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
     }
   };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      *(u32x4*)(smem + buf * 2 * OPB + lds_off[j]) = qv[j];
-      *(u32x4*)(smem + buf * 2 * OPB + OPB + lds_off[j]) = lv[j];
-    }
+  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
+    ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, IvfSumIsScore{});
   };
-
-  f32x4 acc[NR][NR];  // [slot block ai][pair block bi]
-#pragma unroll
-  for (int ai = 0; ai < NR; ++ai)
-#pragma unroll
-    for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // 16-pair blocks of this wave that hold a pair at all (wave-uniform)
-  const int nb_live = min(NR, max(0, (npair - wc * (B / 2) + 15) / 16));
-
-  if (T > 0) {
-    load(0);
-    store(0);
-  }
-  __syncthreads();
-  int ks = 0, tile = 0;
-  for (int it = 0; it < T; ++it) {
-    const int buf = it & 1;
-    if (it + 1 < T) load(it + 1);
-    // 16-slot blocks of this wave below the end of the list (the lists are padded to 16 slots): wave-uniform
-    const int slot_w = s_begin + tile * B + wr * (B / 2);
-    const int na_live = min(NR, max(0, (s_end - slot_w) / 16));
-    if (na_live > 0 && nb_live > 0) {
-      const char* qs = smem + buf * 2 * OPB;
-      const char* ls = qs + OPB;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ch = kk * 4 + kg;
-        half8 fa[NR], fb[NR];
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai) {
-          const int ra = wr * (B / 2) + ai * 16 + l15;
-          fa[ai] = *(const half8*)(ls + ra * (IVF_BK * 2) + ((ch ^ (ra & 7)) << 4));
-        }
-#pragma unroll
-        for (int bi = 0; bi < NR; ++bi) {
-          const int rb = wc * (B / 2) + bi * 16 + l15;
-          fb[bi] = *(const half8*)(qs + rb * (IVF_BK * 2) + ((ch ^ (rb & 7)) << 4));
-        }
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai)
-          if (ai < na_live) {
-#pragma unroll
-            for (int bi = 0; bi < NR; ++bi)
-              if (bi < nb_live) acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[ai], fb[bi], acc[ai][bi], 0, 0, 0);
-          }
-      }
-    }
-    if (it + 1 < T) store(buf ^ 1);
-    if (++ks == nk) {
-      // the tile is finished: fold this wave's scores into the pairs' lists.  A candidate must beat the pair's current
-      // k-th key's score or tie it (the id decides then); a stale threshold is a valid lower bound.
-#pragma unroll
-      for (int ai = 0; ai < NR; ++ai) {
-        if (ai < na_live) {
-          const int slot0 = slot_w + ai * 16 + 4 * kg;  // < s_end, 16-byte aligned: off % 16 == 0
-          const int4 id4 = *(const int4*)(ids + slot0);
-          const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
-#pragma unroll
-          for (int bi = 0; bi < NR; ++bi) {
-            const int pr = wc * (B / 2) + bi * 16 + l15;
-            if (pr < npair) {
-              unsigned long long* lst = lists + pr * KT;
-              const float thr = xs_unord(
-                  (uint32_t)(__hip_atomic_load(lst + KT - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32));
-#pragma unroll
-              for (int r = 0; r < 4; ++r)
-                if (idr[r] >= 0 && acc[ai][bi][r] >= thr) xs_insert<KT>(lst, acc[ai][bi][r], idr[r]);
-            }
-          }
-        }
-#pragma unroll
-        for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      ks = 0;
-      ++tile;
-    }
-    __syncthreads();
-  }
-
-  // (the last barrier of the loop, or the one before it when the list is empty, made the lists final)
-  if (tid < npair) {
-    const int pr = spair[tid];
-    const int q = pr / nprobe, p = pr - q * nprobe;
-    const size_t o = ((size_t)p * nq + q) * k_out;
-    for (int j = 0; j < k_out; ++j) {
-      const unsigned long long key = lists[tid * KT + j];
-      const bool have = key != XS_EMPTY;
-      ps[o + j] = have ? xs_unord((uint32_t)(key >> 32)) : -INFINITY;
-      pi[o + j] = have ? (int)(0xffffffffu - (uint32_t)key) : -1;
-    }
-  }
+  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
+  ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
 }
-
 size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 
 int64_t slots_bound(int64_t n, int64_t K) {
@@ -350,20 +226,24 @@ int check_ws(const void* ws, int64_t ws_bytes, int64_t need, const char* formula
 
 dim3 grid_for(int64_t items, int per_block) { return dim3((unsigned)((items + per_block - 1) / per_block)); }
 
-template <int KT>
-hipError_t launch_scan(int unit, int64_t units, hipStream_t st, const f16* qn, int d, int nq, int nprobe, const f16* rows,
-                       const int32_t* ids, const int32_t* off, int K, const int32_t* poff, const int32_t* ubase,
-                       const int32_t* pairs, int k, float* ps, int32_t* pi) {
-  if (unit == IVF_BIG)
-    return launch_with_lds<ivf_scan_lists_kernel<KT, IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BIG>(KT), st, qn,
-                                                               d, nq, nprobe, rows, ids, off, K, poff, ubase, pairs, k, ps, pi);
-  return launch_with_lds<ivf_scan_lists_kernel<KT, IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BM>(KT), st, qn, d,
-                                                            nq, nprobe, rows, ids, off, K, poff, ubase, pairs, k, ps, pi);
+// the launch of a list-walking kernel: its instantiation for units of IVF_BM or of IVF_BIG rows, as `unit` says
+template <auto Small, auto Big, typename... Args>
+hipError_t launch_units(int unit, int64_t units, int lds_small, int lds_big, hipStream_t st, Args... args) {
+  if (unit == IVF_BIG) return launch_with_lds<Big>(dim3((unsigned)units), IVF_TB, lds_big, st, args...);
+  return launch_with_lds<Small>(dim3((unsigned)units), IVF_TB, lds_small, st, args...);
+}
+// launch(KT as a std::integral_constant), KT = the key-list length of a search for k results: 1, 2, 4 or 8
+template <class Launch>
+hipError_t with_key_list(int k, Launch launch) {
+  if (k == 1) return launch(std::integral_constant<int, 1>{});
+  if (k == 2) return launch(std::integral_constant<int, 2>{});
+  if (k <= 4) return launch(std::integral_constant<int, 4>{});
+  return launch(std::integral_constant<int, 8>{});
 }
 
 // ================================================================ int8 scalar-quantised lists
-// The same lists with one signed byte per element and one fp32 scale per row.  The scan is ivf_scan_lists_kernel's
-// decomposition with the byte geometry unchanged: a K slice is still 128 bytes of a row, now 128 elements and two
+// The same lists with one signed byte per element and one fp32 scale per row.  The scan is ivf_scan.hpp's decomposition
+// with the byte geometry unchanged: a K slice is still 128 bytes of a row, now 128 elements and two
 // v_mfma_i32_16x16x64_i8 steps, so a tile takes half as many slices and barriers.  The int32 sums are exact; the scales
 // meet the sum in the tile fold only.
 typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -429,8 +309,8 @@ __global__ __launch_bounds__(IVF_TB) void ivf_i8_gather_kernel(const f16* __rest
   }
 }
 
-// ivf_scan_lists_kernel on int8 codes: the same units, tiles, loader mapping, swizzle, buffers and key lists (read its
-// comment first).  What differs: a K slice is IVF_I8_BK = 128 ELEMENTS (the same 128 bytes of a row), lane (l15, kg) feeds
+// ivf_scan_lists_kernel on int8 codes: the same units, tiles, loader mapping, swizzle, buffers and key lists (read
+// ivf_scan.hpp's comment first), spelled out here (see the head of the file).  What differs: a K slice is IVF_I8_BK = 128 ELEMENTS (the same 128 bytes of a row), lane (l15, kg) feeds
 // chunk kk * 4 + kg of its row to MFMA step kk as 16 consecutive K bytes of BOTH operands, so the sum is the exact integer
 // whatever K order the instruction uses; nk = ceil(d / 128) and the chunks of the last slice past d (d % 128 == 64) are
 // zero-filled, which adds 0 exactly.  The fold loads the four slot scales beside the four ids, takes the pair's query scale
@@ -626,20 +506,7 @@ size_t i8_search_bytes(int64_t nq, int64_t K, int nprobe, int k, int d) {
   return search_bytes(nq, K, nprobe, k) + up16((size_t)nq * d) + up16((size_t)nq * 4);
 }
 
-template <int KT>
-hipError_t launch_i8_scan(int unit, int64_t units, hipStream_t st, const int8_t* qc, const float* qscale, int d, int nq,
-                          int nprobe, const int8_t* rows, const float* scales, const int32_t* ids, const int32_t* off, int K,
-                          const int32_t* poff, const int32_t* ubase, const int32_t* pairs, int k, float* ps, int32_t* pi) {
-  if (unit == IVF_BIG)
-    return launch_with_lds<ivf_i8_scan_lists_kernel<KT, IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_i8_scan_lds<IVF_BIG>(KT),
-                                                                  st, qc, qscale, d, nq, nprobe, rows, scales, ids, off, K,
-                                                                  poff, ubase, pairs, k, ps, pi);
-  return launch_with_lds<ivf_i8_scan_lists_kernel<KT, IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_i8_scan_lds<IVF_BM>(KT), st,
-                                                               qc, qscale, d, nq, nprobe, rows, scales, ids, off, K, poff,
-                                                               ubase, pairs, k, ps, pi);
-}
-
-// ---------------------------------------------------------------- host halves shared by the flat and the int8 entries
+// ---------------------------------------------------------------- host halves shared by the flat, int8 and PQ entries
 int check_build_args(int64_t n, int32_t d, int64_t K, int64_t capacity_slots, const void* ws, int64_t ws_bytes,
                      const char* sizing) {
   if (const int rc = check_shape(n, "n", d, K)) return rc;
@@ -714,10 +581,13 @@ hipError_t invert_probes(const int32_t* probes, int64_t P, int64_t K, int k, int
 // The per-list self-join of SemDeDup over the flat lists: for every row, the best score against the rows of its own list
 // that PRECEDE it in a keep order (higher priority first, ties to the lower original id).  The queries are the list rows
 // themselves, so nothing is gathered by index and no probe table is inverted: a unit is one list and B consecutive slots of
-// it (its own rows, the MFMA B operand) and walks the whole list in tiles of B slots (the A operand) with
-// ivf_scan_lists_kernel's slice loop (read its comment first): the same loader mapping, swizzle, buffers, fragment reads,
-// MFMA and K order, so a score has the bits smi_ivf_search returns for the same two rows.  What differs is the fold: one
-// 64-bit key per own row and lane, in registers, which a candidate enters iff it is a row (id >= 0) and precedes the own row.
+// it (its own rows, the MFMA B operand) and walks the whole list in tiles of B slots (the A operand) with the slice loop of
+// ivf_scan.hpp, so a score has the bits smi_ivf_search returns for the same two rows.  What it adds is
+// the fold: one 64-bit key per own row and lane, in registers, which a candidate enters iff it is a row (id >= 0) and
+// precedes the own row; and the join of those keys at the end of the walk.
+// A COPY: the kernel spells ivf_slice_walk's loop out (lds_off to the barrier at the loop's end; keep the two texts the same).
+// As an instance of the function hipcc waits for the prefetched slice before the MFMAs of the current one in the
+// 128-row kernel, whichever way the fold was written (profiles/isa_identity_ivf.txt), so the loop keeps its text here.
 
 // span[l] = off[l + 1] - off[l]: the padded size of every list, what the unit prefix scan counts
 __global__ __launch_bounds__(IVF_TB) void ivf_span_kernel(const int32_t* __restrict__ off, int K, int32_t* __restrict__ span) {
@@ -738,7 +608,7 @@ __global__ __launch_bounds__(IVF_TB) void ivf_slot_priority_kernel(const int32_t
 }
 
 template <int B>
-constexpr int ivf_selfjoin_lds() { return 2 * 2 * B * IVF_BK * 2 + B * 8; }
+constexpr int ivf_selfjoin_lds() { return 2 * 2 * B * IVF_SLICE + B * 8; }
 
 // Workgroup b = unit b - ubase[l] of the list l with ubase[l] <= b < ubase[l + 1]: own slots off[l] + B * that .. against
 // the slots off[l] .. off[l + 1].  Lane (l15, kg) of wave (wr, wc) holds own row wc * B / 2 + bi * 16 + l15 x candidate
@@ -759,13 +629,7 @@ __global__ __launch_bounds__(IVF_TB) void ivf_selfjoin_kernel(const f16* __restr
   const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
   const int b = blockIdx.x;
   if (b >= ubase[K]) return;
-  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ubase[mid] <= b) lo = mid;
-    else hi = mid;
-  }
-  const int l = lo;
+  const int l = ivf_unit_list(ubase, K, b);
   const int s_begin = off[l], s_end = off[l + 1];
   const int u0 = s_begin + (b - ubase[l]) * B;  // < s_end: the list has ceil((s_end - s_begin) / B) units
   const int nown = min(B, s_end - u0);          // a multiple of 16
@@ -929,9 +793,9 @@ size_t dedup_bytes(int64_t slots, int64_t K) {
 // ================================================================ product-quantised lists
 // The same lists with one byte per sub-quantiser and row: d = M * dsub, M sub-quantisers of PQ_CW = 256 codewords each,
 // codebooks fp16 [M][256][dsub], a code row uint8 [M].  The bucketing, the unit rule, the key lists and the merge above are
-// called.  New: the product quantiser (encode, train, decode), the gather that encodes, and a scan that decodes a tile's
-// codes into ivf_scan_lists_kernel's LDS image once per tile and K slice and then runs that kernel's slice loop unchanged,
-// so a score has the bits smi_ivf_search returns against the decoded row.
+// called.  New: the product quantiser (encode, train, decode), the gather that encodes, and a scan whose fetch decodes a
+// tile's codes into the slice loop's LDS image once per tile and K slice: the loop is ivf_scan_lists_kernel's, so a score
+// has the bits smi_ivf_search returns against the decoded row.
 constexpr int PQ_CW = 256;     // codewords of every sub-quantiser: a code is one byte
 constexpr int PQ_ROWS = 2048;  // rows one block of the training update takes of one sub-quantiser
 
@@ -1127,12 +991,11 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_gather_kernel(const f16* __rest
   }
 }
 
-// ivf_scan_lists_kernel on product-quantised lists: the same units, tiles, loader mapping, swizzle, buffers, barriers, MFMA
-// order, fold and read-out (read its comment first).  What differs is where the list operand's slice comes from: thread
+// ivf_scan_lists_kernel's unit on product-quantised lists.  What it adds is where the list operand's slice comes from: thread
 // (row r, chunk cc) of slice ks owns the dimensions ks * 64 + cc * 8 .. + 8, reads the code byte of sub-quantiser
 // m = (ks * 64 + cc * 8) / dsub of its slot and gathers 16 bytes of that codeword from the codebooks (256 * d * 2 bytes,
 // which stay in L2).  Code -> codeword is two dependent round trips and one slice of prefetch covers one, so the code
-// bytes are fetched a slice further ahead than the codewords: `load(it)` gathers with the codes an earlier call left in
+// bytes are fetched a slice further ahead than the codewords: `fetch(it)` gathers with the codes an earlier call left in
 // cd and fetches those of slice it + 1.  Slots at or past the end of the list are zero-filled without touching the codes;
 // a pad slot (codes 0) decodes codeword 0 of every sub-quantiser and is skipped by the fold (id -1).
 template <int KT, int B>
@@ -1144,51 +1007,28 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __
                                                                    const int32_t* __restrict__ ubase,
                                                                    const int32_t* __restrict__ pairs, int k_out,
                                                                    float* __restrict__ ps, int32_t* __restrict__ pi) {
-  constexpr int OPB = B * IVF_BK * 2;  // bytes of one operand's K slice
-  constexpr int NR = B / 32;           // rows of an operand slice a thread loads; 16-row blocks of a wave per operand
+  constexpr int NR = B / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* lists = (unsigned long long*)(smem + 4 * OPB);
-  int* spair = (int*)(smem + 4 * OPB + B * KT * 8);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
-  const int b = blockIdx.x;
+  unsigned long long* lists = (unsigned long long*)(smem + 4 * B * IVF_SLICE);
+  int* spair = (int*)(lists + B * KT);
+  const int tid = threadIdx.x, b = blockIdx.x;
   if (b >= ubase[K]) return;
-  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ubase[mid] <= b) lo = mid;
-    else hi = mid;
-  }
-  const int l = lo;
+  const int l = ivf_unit_list(ubase, K, b);
   const int p0 = poff[l] + (b - ubase[l]) * B;
   const int npair = min(B, poff[l + 1] - p0);
   const int s_begin = off[l], s_end = off[l + 1];
+  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [](int) {});
 
-  if (tid < B) {
-    spair[tid] = tid < npair ? pairs[p0 + tid] : -1;
-#pragma unroll
-    for (int j = 0; j < KT; ++j) lists[tid * KT + j] = XS_EMPTY;
-  }
-  __syncthreads();
-
-  const int nk = d / IVF_BK;
-  const int ntiles = (s_end - s_begin + B - 1) / B;
-  const int T = ntiles * nk;
+  const int nk = d / IVF_BK, cc = tid & 7;
+  const int T = (s_end - s_begin + B - 1) / B * nk;  // the slices of the walk
   const int M = d >> dshift, dsub = 1 << dshift;
-
-  // this thread's rows of a slice, and where its chunk lands in LDS
-  const int cc = tid & 7;
-  const f16* qsrc[NR];
-  int lds_off[NR];
+  const f16* qsrc[NR];  // this thread's query rows of a slice
 #pragma unroll
   for (int j = 0; j < NR; ++j) {
-    const int r = (tid >> 3) + 32 * j;
-    const int pr = spair[r];
+    const int pr = spair[(tid >> 3) + 32 * j];
     qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
-    lds_off[j] = r * (IVF_BK * 2) + ((cc ^ (r & 7)) << 4);
   }
-  u32x4 qv[NR], lv[NR];
-  unsigned cd[NR];  // the code bytes of this thread's chunk of the slice the next `load` gathers
+  unsigned cd[NR];  // the code bytes of this thread's chunk of the slice the next `fetch` gathers
   auto fetch_codes = [&](int it) {
     const int tile = it / nk, ks = it - tile * nk;
     const int m = (ks * IVF_BK + cc * 8) >> dshift;  // < M
@@ -1198,7 +1038,8 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __
       cd[j] = slot < s_end ? codes[(size_t)slot * M + m] : 0u;
     }
   };
-  auto load = [&](int it) {
+  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {
+    if (it == 0) fetch_codes(0);
     const int tile = it / nk, ks = it - tile * nk;
     const int k0 = ks * IVF_BK + cc * 8;
     const f16* cw = cb + ((size_t)(k0 >> dshift) * PQ_CW << dshift) + (k0 & (dsub - 1));  // codeword 0 of the sub-quantiser
@@ -1210,119 +1051,12 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __
     }
     if (it + 1 < T) fetch_codes(it + 1);
   };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      *(u32x4*)(smem + buf * 2 * OPB + lds_off[j]) = qv[j];
-      *(u32x4*)(smem + buf * 2 * OPB + OPB + lds_off[j]) = lv[j];
-    }
+  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
+    ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, IvfSumIsScore{});
   };
-
-  f32x4 acc[NR][NR];  // [slot block ai][pair block bi]
-#pragma unroll
-  for (int ai = 0; ai < NR; ++ai)
-#pragma unroll
-    for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
-  // 16-pair blocks of this wave that hold a pair at all (wave-uniform)
-  const int nb_live = min(NR, max(0, (npair - wc * (B / 2) + 15) / 16));
-
-  if (T > 0) {
-    fetch_codes(0);
-    load(0);
-    store(0);
-  }
-  __syncthreads();
-  int ks = 0, tile = 0;
-  for (int it = 0; it < T; ++it) {
-    const int buf = it & 1;
-    if (it + 1 < T) load(it + 1);
-    // 16-slot blocks of this wave below the end of the list (the lists are padded to 16 slots): wave-uniform
-    const int slot_w = s_begin + tile * B + wr * (B / 2);
-    const int na_live = min(NR, max(0, (s_end - slot_w) / 16));
-    if (na_live > 0 && nb_live > 0) {
-      const char* qs = smem + buf * 2 * OPB;
-      const char* ls = qs + OPB;
-#pragma unroll
-      for (int kk = 0; kk < 2; ++kk) {
-        const int ch = kk * 4 + kg;
-        half8 fa[NR], fb[NR];
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai) {
-          const int ra = wr * (B / 2) + ai * 16 + l15;
-          fa[ai] = *(const half8*)(ls + ra * (IVF_BK * 2) + ((ch ^ (ra & 7)) << 4));
-        }
-#pragma unroll
-        for (int bi = 0; bi < NR; ++bi) {
-          const int rb = wc * (B / 2) + bi * 16 + l15;
-          fb[bi] = *(const half8*)(qs + rb * (IVF_BK * 2) + ((ch ^ (rb & 7)) << 4));
-        }
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai)
-          if (ai < na_live) {
-#pragma unroll
-            for (int bi = 0; bi < NR; ++bi)
-              if (bi < nb_live) acc[ai][bi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[ai], fb[bi], acc[ai][bi], 0, 0, 0);
-          }
-      }
-    }
-    if (it + 1 < T) store(buf ^ 1);
-    if (++ks == nk) {
-      // the tile is finished: fold this wave's scores into the pairs' lists, as ivf_scan_lists_kernel does
-#pragma unroll
-      for (int ai = 0; ai < NR; ++ai) {
-        if (ai < na_live) {
-          const int slot0 = slot_w + ai * 16 + 4 * kg;  // < s_end, 16-byte aligned: off % 16 == 0
-          const int4 id4 = *(const int4*)(ids + slot0);
-          const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
-#pragma unroll
-          for (int bi = 0; bi < NR; ++bi) {
-            const int pr = wc * (B / 2) + bi * 16 + l15;
-            if (pr < npair) {
-              unsigned long long* lst = lists + pr * KT;
-              const float thr = xs_unord(
-                  (uint32_t)(__hip_atomic_load(lst + KT - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32));
-#pragma unroll
-              for (int r = 0; r < 4; ++r)
-                if (idr[r] >= 0 && acc[ai][bi][r] >= thr) xs_insert<KT>(lst, acc[ai][bi][r], idr[r]);
-            }
-          }
-        }
-#pragma unroll
-        for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      ks = 0;
-      ++tile;
-    }
-    __syncthreads();
-  }
-
-  // (the last barrier of the loop, or the one before it when the list is empty, made the lists final)
-  if (tid < npair) {
-    const int pr = spair[tid];
-    const int q = pr / nprobe, p = pr - q * nprobe;
-    const size_t o = ((size_t)p * nq + q) * k_out;
-    for (int j = 0; j < k_out; ++j) {
-      const unsigned long long key = lists[tid * KT + j];
-      const bool have = key != XS_EMPTY;
-      ps[o + j] = have ? xs_unord((uint32_t)(key >> 32)) : -INFINITY;
-      pi[o + j] = have ? (int)(0xffffffffu - (uint32_t)key) : -1;
-    }
-  }
+  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
+  ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
 }
-
-template <int KT>
-hipError_t launch_pq_scan(int unit, int64_t units, hipStream_t st, const f16* qn, int d, int nq, int nprobe,
-                          const uint8_t* codes, int dshift, const f16* cb, const int32_t* ids, const int32_t* off, int K,
-                          const int32_t* poff, const int32_t* ubase, const int32_t* pairs, int k, float* ps, int32_t* pi) {
-  if (unit == IVF_BIG)
-    return launch_with_lds<ivf_pq_scan_lists_kernel<KT, IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BIG>(KT), st,
-                                                                  qn, d, nq, nprobe, codes, dshift, cb, ids, off, K, poff,
-                                                                  ubase, pairs, k, ps, pi);
-  return launch_with_lds<ivf_pq_scan_lists_kernel<KT, IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_scan_lds<IVF_BM>(KT), st, qn,
-                                                               d, nq, nprobe, codes, dshift, cb, ids, off, K, poff, ubase,
-                                                               pairs, k, ps, pi);
-}
-
 // training: codes uint8 [n, M] | sums int64 [M][256][dsub] | counts int32 [M][256]
 size_t pq_train_bytes(int64_t n, int d, int dsub) {
   return up16((size_t)n * (d / dsub)) + (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * (d / dsub) * 4;
@@ -1397,10 +1131,12 @@ int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes,
   HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
   // units for every pair count the table can have: those from ubase[K] on find nothing to do
   const int64_t units = units_bound(P, K, unit);
-  const int KT = k == 1 ? 1 : k == 2 ? 2 : k <= 4 ? 4 : 8;
-  auto scan = KT == 1 ? launch_scan<1> : KT == 2 ? launch_scan<2> : KT == 4 ? launch_scan<4> : launch_scan<8>;
-  HIP_TRY(scan(unit, units, st, (const f16*)qn, d, (int)nq, nprobe, (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff,
-               w.ubase, w.pairs, k, w.ps, w.pi));
+  HIP_TRY(with_key_list(k, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    return launch_units<ivf_scan_lists_kernel<KT, IVF_BM>, ivf_scan_lists_kernel<KT, IVF_BIG>>(
+        unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
+        (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi);
+  }));
   HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
   return SMI_OK;
 }
@@ -1449,15 +1185,9 @@ int smi_ivf_dedup(const void* list_rows, const int32_t* list_ids, const int32_t*
   // units for every list layout the storage can hold: a list has ceil(padded size / unit) of them, at most slots / unit + K
   // in all; those from ubase[K] on find nothing to do
   const int64_t units = slots / unit + K;
-  if (unit == IVF_BIG) {
-    HIP_TRY(launch_with_lds<ivf_selfjoin_kernel<IVF_BIG>>(dim3((unsigned)units), IVF_TB, ivf_selfjoin_lds<IVF_BIG>(), st,
-                                                          (const f16*)list_rows, d, list_ids, sprio, list_offsets, (int)K, ubase,
-                                                          (int)n, max_sim, nearest));
-  } else {
-    HIP_TRY(launch_with_lds<ivf_selfjoin_kernel<IVF_BM>>(dim3((unsigned)units), IVF_TB, ivf_selfjoin_lds<IVF_BM>(), st,
-                                                         (const f16*)list_rows, d, list_ids, sprio, list_offsets, (int)K, ubase,
-                                                         (int)n, max_sim, nearest));
-  }
+  HIP_TRY((launch_units<ivf_selfjoin_kernel<IVF_BM>, ivf_selfjoin_kernel<IVF_BIG>>(
+      unit, units, ivf_selfjoin_lds<IVF_BM>(), ivf_selfjoin_lds<IVF_BIG>(), st, (const f16*)list_rows, d, list_ids, sprio,
+      list_offsets, (int)K, ubase, (int)n, max_sim, nearest)));
   return SMI_OK;
 }
 
@@ -1520,10 +1250,13 @@ int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
   const int unit = unit_pairs(P, K);
   HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
   const int64_t units = units_bound(P, K, unit);
-  const int KT = k == 1 ? 1 : k == 2 ? 2 : k <= 4 ? 4 : 8;
-  auto scan = KT == 1 ? launch_i8_scan<1> : KT == 2 ? launch_i8_scan<2> : KT == 4 ? launch_i8_scan<4> : launch_i8_scan<8>;
-  HIP_TRY(scan(unit, units, st, qc, qscale, d, (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets,
-               (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi));
+  HIP_TRY(with_key_list(k, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    return launch_units<ivf_i8_scan_lists_kernel<KT, IVF_BM>, ivf_i8_scan_lists_kernel<KT, IVF_BIG>>(
+        unit, units, ivf_i8_scan_lds<IVF_BM>(KT), ivf_i8_scan_lds<IVF_BIG>(KT), st, (const int8_t*)qc, (const float*)qscale, d,
+        (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k,
+        w.ps, w.pi);
+  }));
   HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
   return SMI_OK;
 }
@@ -1639,10 +1372,13 @@ int smi_ivf_pq_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
   const int unit = unit_pairs(P, K);  // the flat search's rule: the image and the MFMA work of a unit are the same
   HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
   const int64_t units = units_bound(P, K, unit);
-  const int KT = k == 1 ? 1 : k == 2 ? 2 : k <= 4 ? 4 : 8;
-  auto scan = KT == 1 ? launch_pq_scan<1> : KT == 2 ? launch_pq_scan<2> : KT == 4 ? launch_pq_scan<4> : launch_pq_scan<8>;
-  HIP_TRY(scan(unit, units, st, (const f16*)qn, d, (int)nq, nprobe, (const uint8_t*)list_codes, pq_shift(dsub),
-               (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi));
+  HIP_TRY(with_key_list(k, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    return launch_units<ivf_pq_scan_lists_kernel<KT, IVF_BM>, ivf_pq_scan_lists_kernel<KT, IVF_BIG>>(
+        unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
+        (const uint8_t*)list_codes, pq_shift(dsub), (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase,
+        w.pairs, k, w.ps, w.pi);
+  }));
   HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
   return SMI_OK;
 }

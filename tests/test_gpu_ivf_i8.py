@@ -202,6 +202,16 @@ def test_search_at_the_threshold_between_the_two_unit_sizes(nq):
     _check_search(x, labels, 1, q, np.zeros((nq, 1), dtype=np.int64), (1, 8))
 
 
+@pytest.mark.parametrize("nq", [70, 256])  # units of 64 pairs (two of them), units of 128
+def test_search_every_key_list_length_at_both_unit_sizes(nq):
+    """Every instantiation <KT, B> of the scan: k = 1, 2, 3, 8 are the key lists of 1, 2, 4 and 8 entries.  One list of
+    130 rows is two tiles at B = 128 and three at B = 64, the last one partial; d = 192 is a full K slice and a zero-filled
+    half of one."""
+    rng = np.random.default_rng(1200 + nq)
+    x, q = _unit_rows(rng, 130, 192), _unit_rows(rng, nq, 192)
+    _check_search(x, np.zeros(130, dtype=np.int64), 1, q, np.zeros((nq, 1), dtype=np.int64), (1, 2, 3, 8))
+
+
 def test_search_units_of_128_pairs_d1024():
     rng = np.random.default_rng(11)
     x, q = _unit_rows(rng, 600, 1024), _unit_rows(rng, 300, 1024)

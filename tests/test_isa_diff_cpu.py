@@ -139,6 +139,27 @@ def test_moved_valu_and_salu_lines_are_rescheduled(tmp_path):
     assert rc == 1 and "DIFF k_a" in out
 
 
+def test_a_diff_says_what_a_refactor_is_judged_by(tmp_path):
+    # registers renumbered on two lines and two fewer SGPRs: DIFF, with the memory operations, waits and MFMAs in the base's order
+    base = unit([kernel("k_a", BODY_C, 0, desc=DESC_C), kernel("k_b", BODY_B, 1)], "0")
+    renumbered = BODY_C.replace("s4", "s6")
+    rc, out = run(tmp_path, base, unit([kernel("k_a", renumbered, 0, desc=DESC_C.replace("sgpr 16", "sgpr 14")), kernel("k_b", BODY_B, 1)], "0"))
+    assert rc == 1 and "identical 1, commuted 0, differing 1" in out[0]
+    detail = out[out.index("DIFF k_a") + 1]
+    assert detail.startswith("  ordered sequence same (6 -> 6 lines); resources next_free_sgpr 16 -> 14; changed lines 3 of ")
+    # a wait with another counter and a larger LDS segment: the sequence differs, both resources are listed, one line changed
+    waits = BODY_C.replace("vmcnt(0) lgkmcnt(0)", "vmcnt(1) lgkmcnt(0)")
+    desc = DESC_C.replace("group_segment_fixed_size 0", "group_segment_fixed_size 512").replace("vgpr 8", "vgpr 12")
+    rc, out = run(tmp_path, base, unit([kernel("k_a", waits, 0, desc=desc), kernel("k_b", BODY_B, 1)], "0"))
+    detail = out[out.index("DIFF k_a") + 1]
+    assert rc == 1 and detail.startswith("  ordered sequence DIFFERS (6 -> 6 lines); resources group_segment_fixed_size 0 -> 512, "
+                                         "next_free_vgpr 8 -> 12; changed lines 3 of ")
+    # equal resources are said to be equal; no other class grows a second line
+    rc, out = run(tmp_path, base, unit([kernel("k_a", renumbered, 0, desc=DESC_C), kernel("k_b", BODY_B, 1)], "0"))
+    assert out[out.index("DIFF k_a") + 1].startswith("  ordered sequence same (6 -> 6 lines); resources same; changed lines 2 of ")
+    assert out[out.index("IDENTICAL k_b") + 1] == "DIFF k_a" and len(out) == 4
+
+
 def test_moved_global_load_is_a_diff_not_rescheduled(tmp_path):
     lines = BODY_C.splitlines(keepends=True)
     moved = "".join([lines[0], lines[1], lines[3], lines[2]] + lines[4:])  # the load behind the LDS read

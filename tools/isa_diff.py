@@ -10,7 +10,9 @@ function and the padding in front of a label line's comment is ignored.  OLD=NEW
 Every kernel of the base is IDENTICAL, COMMUTED (equal once the two source operands of every v_add/mul/max/min_f32_e32,
 s_add_i32/u32, s_mul_i32, s_and/or/xor_b32, s_min/max_i32/u32 and v_add_u32_e32 line are sorted -- IEEE add, mul, max and
 min and the integer operations commute exactly, SCC and carry included; nothing else is normalised), RESCHEDULED, DIFF or
-REMOVED; kernels only in the tree are ADDED.  RESCHEDULED: the sequence of v_mfma*, ds_*, global_* / buffer_*, s_waitcnt*,
+REMOVED; kernels only in the tree are ADDED.  Under a DIFF line: whether the ordered sequence (next sentence) is the base's all the
+same, every descriptor resource that differs as `field base -> tree`, and the count of changed lines (the larger side of a
+line diff, descriptor included) -- what a refactor that renumbers registers is judged by.  RESCHEDULED: the sequence of v_mfma*, ds_*, global_* / buffer_*, s_waitcnt*,
 s_barrier and s_setprio lines, compared by mnemonic (s_waitcnt: with its counters), equals the base's, and so do the
 descriptor's VGPR / AGPR / SGPR counts, scratch size and LDS size, and the two bodies hold the same lines (as a multiset,
 after the COMMUTED sorting) -- only VALU / SALU address or arithmetic lines moved; a line that changed, a register
@@ -18,6 +20,7 @@ renumbered, is DIFF.  (The 256x256 GEMM engines rely on counted vmcnt waits: the
 what must not move.)
 Exit status 1 if a kernel is DIFF or ADDED.
 """
+import difflib
 import re
 import sys
 
@@ -41,7 +44,8 @@ def kernels(path, rename=()):
         elif name:
             body.append(line)
     for m in re.finditer(r"^\t\.amdhsa_kernel (\w+)\n(.*?)^\t\.end_amdhsa_kernel", txt, flags=re.M | re.S):
-        out[m.group(1)] = out.get(m.group(1), "") + m.group(2)
+        if m.group(2) not in out.get(m.group(1), ""):  # (hipcc prints the descriptor behind .Lfunc_end: once, not twice)
+            out[m.group(1)] = out.get(m.group(1), "") + m.group(2)
     return out
 
 
@@ -75,7 +79,14 @@ for old, new in pairs: print("PAIRED", old, "->", new)
 for k in same: print("IDENTICAL", k)
 for k in comm: print("COMMUTED", k)
 for k in resch: print("RESCHEDULED", k)
-for k in diff: print("DIFF", k)
+for k in diff:
+    print("DIFF", k)
+    (oa, ra, _), (ob, rb, _) = skeleton(a[k]), skeleton(b[k])
+    fa, fb = ({r.split()[0].replace(".amdhsa_", ""): r.split()[1] for r in rs} for rs in (ra, rb))
+    moved = [f"{f} {fa.get(f, '-')} -> {fb.get(f, '-')}" for f in dict.fromkeys([*fa, *fb]) if fa.get(f) != fb.get(f)]
+    marks = [d[0] for d in difflib.unified_diff(a[k].splitlines(), b[k].splitlines(), n=0, lineterm="")][2:]
+    print(f"  ordered sequence {'same' if oa == ob else 'DIFFERS'} ({len(oa)} -> {len(ob)} lines); resources "
+          f"{', '.join(moved) if moved else 'same'}; changed lines {max(marks.count('-'), marks.count('+'))} of {len(a[k].splitlines())}")
 for k in sorted(set(a) - set(b)): print("REMOVED", k)
 for k in sorted(set(b) - set(a)): print("ADDED", k)
 sys.exit(1 if diff or set(b) - set(a) else 0)
