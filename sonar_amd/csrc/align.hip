@@ -24,8 +24,8 @@
 // used in place: a strip reads column j before it overwrites it, and its successor reads it only after that.
 #include <algorithm>
 
+#include "api_common.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
 
 namespace smi {
 
@@ -353,30 +353,43 @@ __global__ __launch_bounds__(64) void dtw_backtrack_kernel(const int64_t* __rest
   if (lane == 0) path_len[b] = (int32_t)n;
 }
 
+// workspace: plan int64 [4 B] | line fp32 [sum ny] | codes u32 | skewed cost fp32 | row-major cost fp32 (smi_dtw_align only)
+struct DtwWs : smi_host::WsLayout {
+  int64_t* plan;
+  float *line, *skew, *cost;
+  uint32_t* codes;
+  DtwWs(void* ws, int n_pairs, const DtwSizes& sz, bool with_cost) : smi_host::WsLayout(ws) {
+    plan = take<int64_t>(4 * (size_t)n_pairs);
+    line = take<float>(sz.line);
+    codes = take<uint32_t>(sz.codes);
+    skew = take<float>(sz.skew);
+    cost = take<float>(with_cost ? sz.cells : 0);
+  }
+};
+
 }  // namespace
 
-// workspace: plan int64 [4 B] | line fp32 [sum ny] | codes u32 | skewed cost fp32 | row-major cost fp32 (smi_dtw_align only)
+size_t dtw_workspace_bytes(int n_pairs, const DtwSizes& sz, bool with_cost) {
+  return DtwWs(nullptr, n_pairs, sz, with_cost).bytes();
+}
+
 hipError_t launch_dtw(const f16* xn, const f16* yn, int d, const float* cost, int n_pairs, const DtwSizes& sz,
                       const int64_t* xoff, const int64_t* yoff, int64_t radius, int32_t* path, int32_t* path_len,
                       float* distance, void* ws, hipStream_t stream) {
-  int64_t* plan = (int64_t*)ws;
-  float* line = (float*)(plan + 4 * (int64_t)n_pairs);
-  uint32_t* codes = (uint32_t*)(line + sz.line);
-  float* skew = (float*)(codes + sz.codes);
-  hipLaunchKernelGGL(dtw_plan_kernel, dim3(1), dim3(256), 0, stream, xoff, yoff, n_pairs, plan);
+  const DtwWs w(ws, n_pairs, sz, !cost);
+  hipLaunchKernelGGL(dtw_plan_kernel, dim3(1), dim3(256), 0, stream, xoff, yoff, n_pairs, w.plan);
   if (sz.cells > 0) {
     if (!cost) {
-      float* c = skew + sz.skew;
       hipLaunchKernelGGL(dtw_cost_kernel, dim3((unsigned)sz.max_tiles, (unsigned)n_pairs), dim3(256), 0, stream, xn, yn, d,
-                         xoff, yoff, plan, c);
-      cost = c;
+                         xoff, yoff, w.plan, w.cost);
+      cost = w.cost;
     }
     hipLaunchKernelGGL(dtw_skew_kernel, dim3((unsigned)((sz.max_units + 3) / 4), (unsigned)n_pairs), dim3(256), 0, stream,
-                       cost, xoff, yoff, plan, skew);
-    hipLaunchKernelGGL(dtw_dp_kernel, dim3((unsigned)n_pairs), dim3(DT), 0, stream, xoff, yoff, plan, radius, skew, codes,
-                       line, distance);
+                       cost, xoff, yoff, w.plan, w.skew);
+    hipLaunchKernelGGL(dtw_dp_kernel, dim3((unsigned)n_pairs), dim3(DT), 0, stream, xoff, yoff, w.plan, radius, w.skew, w.codes,
+                       w.line, distance);
   }
-  hipLaunchKernelGGL(dtw_backtrack_kernel, dim3((unsigned)n_pairs), dim3(64), 0, stream, xoff, yoff, plan, codes,
+  hipLaunchKernelGGL(dtw_backtrack_kernel, dim3((unsigned)n_pairs), dim3(64), 0, stream, xoff, yoff, w.plan, w.codes,
                      (int2*)path, path_len, distance);
   return hipGetLastError();
 }

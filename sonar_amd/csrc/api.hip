@@ -735,10 +735,6 @@ int dtw_check_offsets(int32_t n_pairs, const int64_t* xo, const int64_t* yo, Dtw
   return SMI_OK;
 }
 
-int64_t dtw_bytes(int32_t n_pairs, const DtwSizes& sz, bool with_cost) {
-  return (int64_t)n_pairs * 32 + 4 * (sz.line + sz.codes + sz.skew + (with_cost ? sz.cells : 0));
-}
-
 int dtw_run(const void* xn, const void* yn, int32_t d, const float* cost, int32_t n_pairs, const int64_t* xo,
             const int64_t* yo, const int64_t* xo_dev, const int64_t* yo_dev, int64_t radius, int32_t* path,
             int32_t* path_len, float* distance, void* ws, int64_t ws_bytes, void* stream) {
@@ -747,9 +743,9 @@ int dtw_run(const void* xn, const void* yn, int32_t d, const float* cost, int32_
   DtwSizes sz;
   if (const int rc = dtw_check_offsets(n_pairs, xo, yo, sz)) return rc;
   if ((uintptr_t)ws % 8) return fail(SMI_ERR_INVALID_ARG, "workspace must be 8-byte aligned");
-  if (ws_bytes < dtw_bytes(n_pairs, sz, !cost))
+  if (ws_bytes < (int64_t)dtw_workspace_bytes(n_pairs, sz, !cost))
     return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, this call needs %lld (smi_dtw_workspace_bytes covers it)",
-                (long long)ws_bytes, (long long)dtw_bytes(n_pairs, sz, !cost));
+                (long long)ws_bytes, (long long)dtw_workspace_bytes(n_pairs, sz, !cost));
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   HIP_TRY(launch_dtw((const f16*)xn, (const f16*)yn, d, cost, n_pairs, sz, xo_dev, yo_dev, radius, path, path_len, distance,
                      ws, (hipStream_t)stream));
@@ -761,7 +757,7 @@ int dtw_run(const void* xn, const void* yn, int32_t d, const float* cost, int32_
 int64_t smi_dtw_workspace_bytes(int32_t n_pairs, const int64_t* x_offsets_host, const int64_t* y_offsets_host) {
   DtwSizes sz;
   if (dtw_check_offsets(n_pairs, x_offsets_host, y_offsets_host, sz) != SMI_OK) return 0;
-  return dtw_bytes(n_pairs, sz, true);
+  return (int64_t)dtw_workspace_bytes(n_pairs, sz, true);
 }
 
 int smi_dtw_align_cost(const float* cost, int32_t n_pairs, const int64_t* x_offsets_host, const int64_t* y_offsets_host,

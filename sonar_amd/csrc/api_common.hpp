@@ -1,4 +1,5 @@
-// Shared host-side helpers of the C-ABI translation units (api.hip, decoder_api.hip).
+// Shared host-side helpers of the C-ABI translation units (api.hip, decoder_api.hip, ...) and of the files that carve a
+// caller's workspace (xsim.hip, mining.hip, align.hip, kmeans.hip, ivf.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -80,6 +81,50 @@ struct DevBuf {
     return (T*)p;
   }
 };
+
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+inline dim3 grid_for(int64_t items, int per_block) { return dim3((unsigned)((items + per_block - 1) / per_block)); }
+
+// A caller-provided workspace, stated once: a layout is a struct over this that take()s its regions in order.  Over a null
+// base it only measures (every pointer is null, bytes() is what a *_workspace_bytes function returns); over the caller's
+// pointer it carves as well, so the size and the pointers cannot disagree.  A region is `count` T, its size rounded up to
+// `align` bytes (so, over a base aligned to `align`, the next region is aligned too); none by default.
+class WsLayout {
+  char* base_;
+  size_t off_ = 0;
+ public:
+  explicit WsLayout(void* base) : base_((char*)base) {}
+  template <typename T>
+  T* take(size_t count, size_t align = 1) {
+    T* p = base_ ? (T*)(base_ + off_) : nullptr;
+    off_ += (size_t)round_up((int64_t)(count * sizeof(T)), (int64_t)align);
+    return p;
+  }
+  size_t bytes() const { return off_; }
+};
+
+// The workspace checks of every entry point that takes one; `sizing` is the call that returns `need`.
+inline int check_ws(const void* ws, int64_t ws_bytes, size_t need, const char* sizing) {
+  if (!ws) return fail(SMI_ERR_INVALID_ARG, "null workspace");
+  if ((uintptr_t)ws % 16) return fail(SMI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
+  if (ws_bytes < (int64_t)need)
+    return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, %s = %lld", (long long)ws_bytes, sizing, (long long)need);
+  return SMI_OK;
+}
+
+// The shape checks of the entries over n rows of d fp16 and K buckets of them (`bucket`: "cluster", "list"); row and bucket
+// numbers are int32 on the device.  n_name: what the caller calls n, or null where the refusal names nothing (k-means).
+inline int check_shape(int64_t n, const char* n_name, int32_t d, int64_t K, const char* bucket) {
+  constexpr int64_t kMax = 0x7fffff00LL;
+  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
+  if (K < 1) return fail(SMI_ERR_INVALID_ARG, "K=%lld: at least one %s", (long long)K, bucket);
+  if (n < 1) return n_name ? fail(SMI_ERR_INVALID_ARG, "%s=%lld: empty input", n_name, (long long)n)
+                           : fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (n > kMax || K > kMax)
+    return fail(SMI_ERR_UNSUPPORTED, "%s=%lld, K=%lld: row and %s numbers must fit int32", n_name ? n_name : "n", (long long)n,
+                (long long)K, bucket);
+  return SMI_OK;
+}
 
 // Copy a caller tensor into a freshly allocated device buffer as fp16 or fp32;
 // `pad_numel` (>= numel) zero-pads the destination.

@@ -21,8 +21,6 @@ struct DecLayer {
   DevBuf ln3_w, ln3_b, w_1, b_1, w_2, b_2;
 };
 
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
 constexpr int kMaxParts = 16;  // split-K slabs the `parts` buffer holds
 
 // step processors on the device: the banned sequences as a CSR in buffers of its own, and what the kernels get of it

@@ -3,7 +3,7 @@
 // (kmeans.hip) and the probe is smi_xsim_topk against its centroids; both are callers' business, not this file's.
 //
 // Both halves bucket int32 keys with the three passes of the k-means update (histogram, exclusive scan, cursor scatter, all
-// wave-aggregated: wave_claim.hpp).  The build buckets the row numbers by label, the search buckets the nq * nprobe
+// wave-aggregated: bucket.hpp).  The build buckets the row numbers by label, the search buckets the nq * nprobe
 // (query, probe slot) pairs by list -- the inverted probe table -- so that a work unit of the scan is ONE list and up to
 // 64 or 128 of the pairs that probe it: the list's rows are read once per unit, not once per query.
 //
@@ -23,7 +23,7 @@
 // train, decode) and the gathers that encode follow their scans.
 #include "api_common.hpp"
 #include "ivf_scan.hpp"
-#include "wave_claim.hpp"
+#include "bucket.hpp"
 
 #include <type_traits>
 
@@ -43,65 +43,27 @@ constexpr int64_t IVF_MAX = 0x7fffff00LL;
 static_assert(IVF_ALIGN == 16, "a 16-slot A block of the scan's MFMA never spans two lists");
 static_assert(IVF_BM == 64, "the slice loader takes B / 32 passes");
 
-// ---------------------------------------------------------------- bucketing (the k-means pattern, for any int32 keys)
-__global__ __launch_bounds__(IVF_TB) void ivf_hist_kernel(const int32_t* __restrict__ keys, int n, int K,
-                                                          int32_t* __restrict__ counts) {
-  const int64_t i = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
-  const int c = i < n ? keys[i] : -1;
-  km_wave_claim(counts, c, km_label_ok(c, K), threadIdx.x & 63);
-}
-
+// ---------------------------------------------------------------- bucketing (bucket.hpp, for any int32 keys)
 // off[c] = sum over c' < c of counts[c'] rounded up to `align`, off[K] = the total; cursor = a copy of off[0 .. K) for the
-// scatter to advance; ubase (nullable) [K + 1] = the same prefix sum of ceil(counts / unit).  One block, as km_scan_kernel.
+// scatter to advance; ubase (nullable) [K + 1] = the same prefix sum of ceil(counts / unit).
 __global__ __launch_bounds__(IVF_TB) void ivf_scan_kernel(const int32_t* __restrict__ counts, int K, int align, int unit,
                                                           int32_t* __restrict__ off, int32_t* __restrict__ cursor,
                                                           int32_t* __restrict__ ubase) {
-  __shared__ int part[IVF_TB], upart[IVF_TB];
-  const int per = (K + IVF_TB - 1) / IVF_TB;
-  const int64_t lo64 = (int64_t)per * threadIdx.x;
-  const int lo = lo64 < K ? (int)lo64 : K, hi = lo64 + per < K ? (int)(lo64 + per) : K;
-  int sum = 0, usum = 0;
-  for (int i = lo; i < hi; ++i) {
-    const int c = counts[i];
-    sum += (c + align - 1) / align * align;
-    usum += (c + unit - 1) / unit;
-  }
-  part[threadIdx.x] = sum;
-  upart[threadIdx.x] = usum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0, urun = 0;
-    for (int i = 0; i < IVF_TB; ++i) {
-      const int p = part[i], u = upart[i];
-      part[i] = run;
-      upart[i] = urun;
-      run += p;
-      urun += u;
-    }
-    off[K] = run;
-    if (ubase) ubase[K] = urun;
-  }
-  __syncthreads();
-  int run = part[threadIdx.x], urun = upart[threadIdx.x];
-  for (int i = lo; i < hi; ++i) {
-    const int c = counts[i];
-    off[i] = run;
-    cursor[i] = run;
-    if (ubase) ubase[i] = urun;
-    run += (c + align - 1) / align * align;
-    urun += (c + unit - 1) / unit;
-  }
-}
-
-// out[p] = i for every i with a key in [0, K), the i of one key at consecutive p from that key's offset on.  Which i lands
-// where inside its run depends on the atomics' arrival order.
-__global__ __launch_bounds__(IVF_TB) void ivf_scatter_kernel(const int32_t* __restrict__ keys, int n, int K,
-                                                             int32_t* __restrict__ cursor, int32_t* __restrict__ out) {
-  const int64_t i = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
-  const int c = i < n ? keys[i] : -1;
-  const bool ok = km_label_ok(c, K);
-  const int pos = km_wave_claim(cursor, c, ok, threadIdx.x & 63);
-  if (ok) out[pos] = (int32_t)i;  // pos < off[c + 1]: the histogram counted this key with the same test
+  bucket_scan<IVF_TB, 2>(
+      K,
+      [&](int i, int(&v)[2]) {
+        const int c = counts[i];
+        v[0] = (c + align - 1) / align * align;
+        v[1] = (c + unit - 1) / unit;
+      },
+      [&](int i, const int(&run)[2]) {
+        off[i] = cursor[i] = run[0];
+        if (ubase) ubase[i] = run[1];
+      },
+      [&](const int(&run)[2]) {
+        off[K] = run[0];
+        if (ubase) ubase[K] = run[1];
+      });
 }
 
 // ---------------------------------------------------------------- build: the row copies
@@ -178,7 +140,6 @@ __global__ __launch_bounds__(IVF_TB) void ivf_scan_lists_kernel(const f16* __res
   ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
   ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
 }
-size_t up16(size_t b) { return (b + 15) / 16 * 16; }
 
 int64_t slots_bound(int64_t n, int64_t K) {
   const int64_t m = std::min(n, K);
@@ -199,32 +160,30 @@ int unit_pairs(int64_t pairs, int64_t K) { return pairs >= 2 * (int64_t)IVF_BIG 
 int64_t units_bound(int64_t pairs, int64_t K, int unit) { return pairs / unit + std::min(pairs, K); }
 
 // build: cursor int32 [K]
-size_t build_bytes(int64_t K) { return up16((size_t)K * 4); }
+struct BuildWs : WsLayout {
+  int32_t* cursor;
+  BuildWs(void* ws, int64_t K) : WsLayout(ws) { cursor = take<int32_t>(K, 16); }
+};
 // search: pair counts [K] | pair offsets [K + 1] | unit offsets [K + 1] | cursor [K] | bucketed pairs [nq * nprobe] |
 //         partial scores fp32 [nprobe][nq][k] | partial ids int32 [nprobe][nq][k]
-size_t search_bytes(int64_t nq, int64_t K, int nprobe, int k) {
-  return 2 * up16((size_t)K * 4) + 2 * up16((size_t)(K + 1) * 4) + up16((size_t)nq * nprobe * 4) +
-         2 * up16((size_t)nq * nprobe * k * 4);
-}
-
-int check_shape(int64_t n, const char* n_name, int32_t d, int64_t K) {
-  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
-  if (K < 1) return fail(SMI_ERR_INVALID_ARG, "K=%lld: at least one list", (long long)K);
-  if (n < 1) return fail(SMI_ERR_INVALID_ARG, "%s=%lld: empty input", n_name, (long long)n);
-  if (n > IVF_MAX || K > IVF_MAX)
-    return fail(SMI_ERR_UNSUPPORTED, "%s=%lld, K=%lld: row and list numbers must fit int32", n_name, (long long)n, (long long)K);
-  return SMI_OK;
-}
-
-int check_ws(const void* ws, int64_t ws_bytes, int64_t need, const char* formula) {
-  if (!ws) return fail(SMI_ERR_INVALID_ARG, "null workspace");
-  if ((uintptr_t)ws % 16) return fail(SMI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-  if (ws_bytes < need)
-    return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, %s = %lld", (long long)ws_bytes, formula, (long long)need);
-  return SMI_OK;
-}
-
-dim3 grid_for(int64_t items, int per_block) { return dim3((unsigned)((items + per_block - 1) / per_block)); }
+//         and behind them, in the int8 search (i8_dim = its d, else 0): query codes int8 [nq, d] | query scales fp32 [nq]
+struct SearchWs : WsLayout {
+  int32_t *pcount, *poff, *ubase, *cursor, *pairs, *pi;
+  float *ps, *qscale;
+  int8_t* qc;
+  SearchWs(void* ws, int64_t nq, int64_t K, int nprobe, int k, int i8_dim = 0) : WsLayout(ws) {
+    const size_t P = (size_t)nq * nprobe;
+    pcount = take<int32_t>(K, 16);
+    poff = take<int32_t>(K + 1, 16);
+    ubase = take<int32_t>(K + 1, 16);
+    cursor = take<int32_t>(K, 16);
+    pairs = take<int32_t>(P, 16);
+    ps = take<float>(P * k, 16);
+    pi = take<int32_t>(P * k, 16);
+    qc = take<int8_t>(i8_dim ? (size_t)nq * i8_dim : 0, 16);
+    qscale = take<float>(i8_dim ? nq : 0, 16);
+  }
+};
 
 // the launch of a list-walking kernel: its instantiation for units of IVF_BM or of IVF_BIG rows, as `unit` says
 template <auto Small, auto Big, typename... Args>
@@ -501,15 +460,11 @@ int i8_check_dim(int32_t d) {
     return fail(SMI_ERR_UNSUPPORTED, "d=%d: above %d the int32 sum of int8 products could overflow", d, IVF_I8_MAX_DIM);
   return SMI_OK;
 }
-// search: the flat search's workspace | query codes int8 [nq, d] | query scales fp32 [nq]
-size_t i8_search_bytes(int64_t nq, int64_t K, int nprobe, int k, int d) {
-  return search_bytes(nq, K, nprobe, k) + up16((size_t)nq * d) + up16((size_t)nq * 4);
-}
 
 // ---------------------------------------------------------------- host halves shared by the flat, int8 and PQ entries
 int check_build_args(int64_t n, int32_t d, int64_t K, int64_t capacity_slots, const void* ws, int64_t ws_bytes,
                      const char* sizing) {
-  if (const int rc = check_shape(n, "n", d, K)) return rc;
+  if (const int rc = check_shape(n, "n", d, K, "list")) return rc;
   const int64_t bound = slots_bound(n, K);
   if (bound > IVF_MAX)
     return fail(SMI_ERR_UNSUPPORTED, "n=%lld rows over K=%lld lists can need %lld slots: slot numbers must fit int32",
@@ -517,7 +472,7 @@ int check_build_args(int64_t n, int32_t d, int64_t K, int64_t capacity_slots, co
   if (capacity_slots < bound)
     return fail(SMI_ERR_INVALID_ARG, "capacity of %lld slots, smi_ivf_slots_bound(n, K) = %lld", (long long)capacity_slots,
                 (long long)bound);
-  return check_ws(ws, ws_bytes, (int64_t)build_bytes(K), sizing);
+  return check_ws(ws, ws_bytes, BuildWs(nullptr, K).bytes(), sizing);
 }
 
 // the three bucketing passes of a build: list_sizes, list_offsets and the row number of every slot (-1: pad or unused)
@@ -526,53 +481,31 @@ hipError_t bucket_rows(const int32_t* labels, int64_t n, int64_t K, int32_t* lis
   if (hipError_t e = hipMemsetAsync(list_sizes, 0, (size_t)K * 4, st); e != hipSuccess) return e;
   if (hipError_t e = hipMemsetAsync(list_ids, 0xff, (size_t)capacity_slots * 4, st); e != hipSuccess) return e;  // -1
   const dim3 block(IVF_TB), rows_grid = grid_for(n, IVF_TB);
-  hipLaunchKernelGGL(ivf_hist_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, list_sizes);
+  hipLaunchKernelGGL(bucket_hist_kernel<IVF_TB>, rows_grid, block, 0, st, labels, (int)n, (int)K, list_sizes);
   hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, list_sizes, (int)K, IVF_ALIGN, 1, list_offsets, cursor,
                      (int32_t*)nullptr);
-  hipLaunchKernelGGL(ivf_scatter_kernel, rows_grid, block, 0, st, labels, (int)n, (int)K, cursor, list_ids);
+  hipLaunchKernelGGL(bucket_scatter_kernel<IVF_TB>, rows_grid, block, 0, st, labels, (int)n, (int)K, cursor, list_ids,
+                     (int32_t*)nullptr);
   return hipGetLastError();
 }
 
 int check_search_args(int64_t nq, int32_t d, int64_t K, int32_t nprobe, int32_t k) {
-  if (const int rc = check_shape(nq, "nq", d, K)) return rc;
+  if (const int rc = check_shape(nq, "nq", d, K, "list")) return rc;
   if (k < 1 || k > 8) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, 8]", k);
   if (nprobe < 1 || nprobe > 8) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 8]", nprobe);
   if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
   return SMI_OK;
 }
 
-// the flat search's workspace, carved; `end` is where the int8 search's query codes begin
-struct SearchWs {
-  int32_t *pcount, *poff, *ubase, *cursor, *pairs, *pi;
-  float* ps;
-  char* end;
-  SearchWs(void* ws, int64_t P, int64_t K, int k) {
-    char* p = (char*)ws;
-    pcount = (int32_t*)p;
-    p += up16((size_t)K * 4);
-    poff = (int32_t*)p;
-    p += up16((size_t)(K + 1) * 4);
-    ubase = (int32_t*)p;
-    p += up16((size_t)(K + 1) * 4);
-    cursor = (int32_t*)p;
-    p += up16((size_t)K * 4);
-    pairs = (int32_t*)p;
-    p += up16((size_t)P * 4);
-    ps = (float*)p;
-    p += up16((size_t)P * k * 4);
-    pi = (int32_t*)p;
-    end = p + up16((size_t)P * k * 4);
-  }
-};
-
 // invert the probe table: the (query, probe slot) pairs q * nprobe + p bucketed by the list they name, the units' prefix
 // sum for `unit` pairs per unit, and the partial lists pre-filled
 hipError_t invert_probes(const int32_t* probes, int64_t P, int64_t K, int k, int unit, const SearchWs& w, hipStream_t st) {
   if (hipError_t e = hipMemsetAsync(w.pcount, 0, (size_t)K * 4, st); e != hipSuccess) return e;
   const dim3 block(IVF_TB), pair_grid = grid_for(P, IVF_TB);
-  hipLaunchKernelGGL(ivf_hist_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, w.pcount);
+  hipLaunchKernelGGL(bucket_hist_kernel<IVF_TB>, pair_grid, block, 0, st, probes, (int)P, (int)K, w.pcount);
   hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, w.pcount, (int)K, 1, unit, w.poff, w.cursor, w.ubase);
-  hipLaunchKernelGGL(ivf_scatter_kernel, pair_grid, block, 0, st, probes, (int)P, (int)K, w.cursor, w.pairs);
+  hipLaunchKernelGGL(bucket_scatter_kernel<IVF_TB>, pair_grid, block, 0, st, probes, (int)P, (int)K, w.cursor, w.pairs,
+                     (int32_t*)nullptr);
   hipLaunchKernelGGL(ivf_fill_kernel, grid_for(P * k, IVF_TB), block, 0, st, w.ps, w.pi, P * k);
   return hipGetLastError();
 }
@@ -784,11 +717,19 @@ bool dedup_shape_ok(int64_t slots, int64_t n, int64_t K, int32_t d) {
   return slots >= 1 && slots % IVF_ALIGN == 0 && n >= 1 && K >= 1 && d > 0 && d % 64 == 0 && slots <= IVF_MAX && n <= IVF_MAX &&
          K <= IVF_MAX && slots / IVF_BM + K <= IVF_MAX;
 }
-// dedup: padded list sizes [K] | their prefix sum [K + 1] | unit offsets [K + 1] | cursor [K] | priorities in slot order
-//        fp32 [slots]
-size_t dedup_bytes(int64_t slots, int64_t K) {
-  return 2 * up16((size_t)K * 4) + 2 * up16((size_t)(K + 1) * 4) + up16((size_t)slots * 4);
-}
+// dedup: padded list sizes [K] | their prefix sum [K + 1] (the scan's first output: list_offsets again) | unit offsets
+//        [K + 1] | cursor [K] | priorities in slot order fp32 [slots]
+struct DedupWs : WsLayout {
+  int32_t *span, *span_off, *ubase, *cursor;
+  float* sprio;
+  DedupWs(void* ws, int64_t slots, int64_t K) : WsLayout(ws) {
+    span = take<int32_t>(K, 16);
+    span_off = take<int32_t>(K + 1, 16);
+    ubase = take<int32_t>(K + 1, 16);
+    cursor = take<int32_t>(K, 16);
+    sprio = take<float>(slots, 16);
+  }
+};
 
 // ================================================================ product-quantised lists
 // The same lists with one byte per sub-quantiser and row: d = M * dsub, M sub-quantisers of PQ_CW = 256 codewords each,
@@ -1057,10 +998,17 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __
   ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
   ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
 }
-// training: codes uint8 [n, M] | sums int64 [M][256][dsub] | counts int32 [M][256]
-size_t pq_train_bytes(int64_t n, int d, int dsub) {
-  return up16((size_t)n * (d / dsub)) + (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * (d / dsub) * 4;
-}
+// training: codes uint8 [n, M] | sums int64 [M][256][dsub] | counts int32 [M][256] (one memset clears the sums and the counts)
+struct PqTrainWs : WsLayout {
+  uint8_t* codes;
+  unsigned long long* sums;
+  int32_t* counts;
+  PqTrainWs(void* ws, int64_t n, int d, int dsub) : WsLayout(ws) {
+    codes = take<uint8_t>((size_t)n * (d / dsub), 16);
+    sums = take<unsigned long long>((size_t)PQ_CW * d);
+    counts = take<int32_t>((size_t)PQ_CW * (d / dsub));
+  }
+};
 // blocks of the training update: (row blocks) x M
 int64_t pq_update_blocks(int64_t n, int d, int dsub) { return (n + PQ_ROWS - 1) / PQ_ROWS * (d / dsub); }
 bool pq_rows_ok(int64_t n, int32_t d, int32_t dsub) {
@@ -1091,7 +1039,7 @@ int64_t smi_ivf_slots_bound(int64_t n, int64_t K) {
 }
 
 int64_t smi_ivf_build_workspace_bytes(int64_t n, int64_t K, int32_t d) {
-  return build_shape_ok(n, K, d) ? (int64_t)build_bytes(K) : 0;
+  return build_shape_ok(n, K, d) ? (int64_t)BuildWs(nullptr, K).bytes() : 0;
 }
 
 int smi_ivf_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_rows, int32_t* list_ids,
@@ -1102,7 +1050,7 @@ int smi_ivf_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, i
   if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_build_workspace_bytes(n, K, d)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, (int32_t*)ws, st));
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
   // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
   hipLaunchKernelGGL(ivf_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d, list_ids,
                      list_offsets, (int)K, (f16*)list_rows);
@@ -1111,7 +1059,7 @@ int smi_ivf_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, i
 }
 
 int64_t smi_ivf_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
-  return search_shape_ok(nq, K, nprobe, k, d) ? (int64_t)search_bytes(nq, K, nprobe, k) : 0;
+  return search_shape_ok(nq, K, nprobe, k, d) ? (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes() : 0;
 }
 
 int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
@@ -1121,12 +1069,10 @@ int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes,
     return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
   const int64_t P = nq * nprobe;
-  if (const int rc = check_ws(ws, ws_bytes, (int64_t)search_bytes(nq, K, nprobe, k),
-                              "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)"))
-    return rc;
+  const SearchWs w(ws, nq, K, nprobe, k);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  const SearchWs w(ws, P, K, k);
   const int unit = unit_pairs(P, K);
   HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
   // units for every pair count the table can have: those from ubase[K] on find nothing to do
@@ -1143,14 +1089,14 @@ int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes,
 
 // ---------------------------------------------------------------- semantic de-duplication
 int64_t smi_ivf_dedup_workspace_bytes(int64_t slots, int64_t n, int64_t K, int32_t d) {
-  return dedup_shape_ok(slots, n, K, d) ? (int64_t)dedup_bytes(slots, K) : 0;
+  return dedup_shape_ok(slots, n, K, d) ? (int64_t)DedupWs(nullptr, slots, K).bytes() : 0;
 }
 
 int smi_ivf_dedup(const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int64_t slots,
                   int32_t d, const float* priority, int64_t n, float* max_sim, int32_t* nearest, void* ws, int64_t ws_bytes,
                   void* stream) {
   if (!list_rows || !list_ids || !list_offsets || !max_sim || !nearest) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, K)) return rc;
+  if (const int rc = check_shape(n, "n", d, K, "list")) return rc;
   if (slots < 1) return fail(SMI_ERR_INVALID_ARG, "slots=%lld: empty storage", (long long)slots);
   if (slots > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "slots=%lld: slot numbers must fit int32", (long long)slots);
   if (slots % IVF_ALIGN)
@@ -1158,43 +1104,33 @@ int smi_ivf_dedup(const void* list_rows, const int32_t* list_ids, const int32_t*
                 IVF_ALIGN);
   if (slots / IVF_BM + K > IVF_MAX)
     return fail(SMI_ERR_UNSUPPORTED, "slots=%lld, K=%lld: the unit count must fit int32", (long long)slots, (long long)K);
-  if (const int rc = check_ws(ws, ws_bytes, (int64_t)dedup_bytes(slots, K), "smi_ivf_dedup_workspace_bytes(slots, n, K, d)"))
-    return rc;
+  const DedupWs w(ws, slots, K);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_dedup_workspace_bytes(slots, n, K, d)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)ws;
-  int32_t* span = (int32_t*)p;
-  p += up16((size_t)K * 4);
-  int32_t* span_off = (int32_t*)p;  // the scan's first output: list_offsets again
-  p += up16((size_t)(K + 1) * 4);
-  int32_t* ubase = (int32_t*)p;
-  p += up16((size_t)(K + 1) * 4);
-  int32_t* cursor = (int32_t*)p;
-  p += up16((size_t)K * 4);
-  float* sprio = (float*)p;
   // own rows of a unit = slots of its tiles: 128 where the lists average 256 rows or more, else 64 (unit_pairs' rule with
   // one "pair" per row)
   const int unit = unit_pairs(n, K);
   const dim3 block(IVF_TB);
   hipLaunchKernelGGL(ivf_fill_kernel, grid_for(n, IVF_TB), block, 0, st, max_sim, nearest, n);
-  hipLaunchKernelGGL(ivf_span_kernel, grid_for(K, IVF_TB), block, 0, st, list_offsets, (int)K, span);
-  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, span, (int)K, 1, unit, span_off, cursor, ubase);
+  hipLaunchKernelGGL(ivf_span_kernel, grid_for(K, IVF_TB), block, 0, st, list_offsets, (int)K, w.span);
+  hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, w.span, (int)K, 1, unit, w.span_off, w.cursor, w.ubase);
   hipLaunchKernelGGL(ivf_slot_priority_kernel, grid_for(slots, IVF_TB), block, 0, st, list_ids, list_offsets, (int)K, priority,
-                     (int)n, sprio);
+                     (int)n, w.sprio);
   HIP_TRY(hipGetLastError());
   // units for every list layout the storage can hold: a list has ceil(padded size / unit) of them, at most slots / unit + K
   // in all; those from ubase[K] on find nothing to do
   const int64_t units = slots / unit + K;
   HIP_TRY((launch_units<ivf_selfjoin_kernel<IVF_BM>, ivf_selfjoin_kernel<IVF_BIG>>(
-      unit, units, ivf_selfjoin_lds<IVF_BM>(), ivf_selfjoin_lds<IVF_BIG>(), st, (const f16*)list_rows, d, list_ids, sprio,
-      list_offsets, (int)K, ubase, (int)n, max_sim, nearest)));
+      unit, units, ivf_selfjoin_lds<IVF_BM>(), ivf_selfjoin_lds<IVF_BIG>(), st, (const f16*)list_rows, d, list_ids, w.sprio,
+      list_offsets, (int)K, w.ubase, (int)n, max_sim, nearest)));
   return SMI_OK;
 }
 
 // ---------------------------------------------------------------- int8 lists
 int smi_ivf_i8_encode(const void* xn, int64_t n, int32_t d, void* codes, float* scales, void* stream) {
   if (!xn || !codes || !scales) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
   if (const int rc = i8_check_dim(d)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d,
@@ -1204,7 +1140,7 @@ int smi_ivf_i8_encode(const void* xn, int64_t n, int32_t d, void* codes, float* 
 }
 
 int64_t smi_ivf_i8_build_workspace_bytes(int64_t n, int64_t K, int32_t d) {
-  return build_shape_ok(n, K, d) && i8_dim_ok(d) ? (int64_t)build_bytes(K) : 0;
+  return build_shape_ok(n, K, d) && i8_dim_ok(d) ? (int64_t)BuildWs(nullptr, K).bytes() : 0;
 }
 
 int smi_ivf_i8_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_codes,
@@ -1217,7 +1153,7 @@ int smi_ivf_i8_build(const void* xn, const int32_t* labels, int64_t n, int32_t d
   if (const int rc = i8_check_dim(d)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, (int32_t*)ws, st));
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
   // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
   hipLaunchKernelGGL(ivf_i8_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d,
                      list_ids, list_offsets, (int)K, (int8_t*)list_codes, list_scales);
@@ -1226,7 +1162,7 @@ int smi_ivf_i8_build(const void* xn, const int32_t* labels, int64_t n, int32_t d
 }
 
 int64_t smi_ivf_i8_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
-  return search_shape_ok(nq, K, nprobe, k, d) && i8_dim_ok(d) ? (int64_t)i8_search_bytes(nq, K, nprobe, k, d) : 0;
+  return search_shape_ok(nq, K, nprobe, k, d) && i8_dim_ok(d) ? (int64_t)SearchWs(nullptr, nq, K, nprobe, k, d).bytes() : 0;
 }
 
 int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
@@ -1237,15 +1173,11 @@ int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
   if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
   if (const int rc = i8_check_dim(d)) return rc;
   const int64_t P = nq * nprobe;
-  if (const int rc = check_ws(ws, ws_bytes, (int64_t)i8_search_bytes(nq, K, nprobe, k, d),
-                              "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)"))
-    return rc;
+  const SearchWs w(ws, nq, K, nprobe, k, d);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  const SearchWs w(ws, P, K, k);
-  int8_t* qc = (int8_t*)w.end;
-  float* qscale = (float*)(w.end + up16((size_t)nq * d));
-  hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, qc, qscale);
+  hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, w.qc, w.qscale);
   // the flat search's unit rule holds here too: 128 won from 256 pairs per list on, 64 below (profiles/ivf_i8_experiments.txt)
   const int unit = unit_pairs(P, K);
   HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
@@ -1253,7 +1185,7 @@ int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
   HIP_TRY(with_key_list(k, [&](auto kt) {
     constexpr int KT = decltype(kt)::value;
     return launch_units<ivf_i8_scan_lists_kernel<KT, IVF_BM>, ivf_i8_scan_lists_kernel<KT, IVF_BIG>>(
-        unit, units, ivf_i8_scan_lds<IVF_BM>(KT), ivf_i8_scan_lds<IVF_BIG>(KT), st, (const int8_t*)qc, (const float*)qscale, d,
+        unit, units, ivf_i8_scan_lds<IVF_BM>(KT), ivf_i8_scan_lds<IVF_BIG>(KT), st, (const int8_t*)w.qc, (const float*)w.qscale, d,
         (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k,
         w.ps, w.pi);
   }));
@@ -1264,7 +1196,7 @@ int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
 // ---------------------------------------------------------------- product quantiser and product-quantised lists
 int smi_pq_encode(const void* xn, int64_t n, int32_t d, int32_t dsub, const void* codebooks, void* codes, void* stream) {
   if (!xn || !codes) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
   if (const int rc = pq_check_dsub(d, dsub)) return rc;
   if (const int rc = pq_check_codebooks(codebooks)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
@@ -1277,7 +1209,7 @@ int smi_pq_encode(const void* xn, int64_t n, int32_t d, int32_t dsub, const void
 int smi_pq_decode(const void* codes, int64_t n, int32_t d, int32_t dsub, const void* codebooks, void* rows, void* stream) {
   if (!codes || !rows) return fail(SMI_ERR_INVALID_ARG, "null argument");
   if ((uintptr_t)rows % 16) return fail(SMI_ERR_INVALID_ARG, "rows must be 16-byte aligned");
-  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
   if (const int rc = pq_check_dsub(d, dsub)) return rc;
   if (const int rc = pq_check_codebooks(codebooks)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
@@ -1288,26 +1220,23 @@ int smi_pq_decode(const void* codes, int64_t n, int32_t d, int32_t dsub, const v
 }
 
 int64_t smi_pq_train_workspace_bytes(int64_t n, int32_t d, int32_t dsub) {
-  return pq_train_shape_ok(n, d, dsub) ? (int64_t)pq_train_bytes(n, d, dsub) : 0;
+  return pq_train_shape_ok(n, d, dsub) ? (int64_t)PqTrainWs(nullptr, n, d, dsub).bytes() : 0;
 }
 
 int smi_pq_train(const void* xn, int64_t n, int32_t d, int32_t dsub, const int32_t* init, int32_t n_iter, void* codebooks,
                  void* ws, int64_t ws_bytes, void* stream) {
   if (!xn || !init) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, 1)) return rc;
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
   if (const int rc = pq_check_dsub(d, dsub)) return rc;
   if (const int rc = pq_check_codebooks(codebooks)) return rc;
   if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d must not be negative", n_iter);
   if ((int64_t)PQ_CW * d > IVF_MAX || pq_update_blocks(n, d, dsub) > IVF_MAX)
     return fail(SMI_ERR_UNSUPPORTED, "n=%lld, d=%d: the codebook elements and the update's blocks must fit int32", (long long)n, d);
-  if (const int rc = check_ws(ws, ws_bytes, (int64_t)pq_train_bytes(n, d, dsub), "smi_pq_train_workspace_bytes(n, d, dsub)"))
-    return rc;
+  const PqTrainWs w(ws, n, d, dsub);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_pq_train_workspace_bytes(n, d, dsub)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
   const int M = d / dsub;
-  uint8_t* codes = (uint8_t*)ws;
-  unsigned long long* sums = (unsigned long long*)((char*)ws + up16((size_t)n * M));
-  int32_t* counts = (int32_t*)(sums + (size_t)PQ_CW * d);
   const dim3 block(IVF_TB);
   hipLaunchKernelGGL(pq_init_kernel, grid_for((int64_t)PQ_CW * (d / 8), IVF_TB), block, 0, st, (const f16*)xn, d, dsub, init,
                      (f16*)codebooks);
@@ -1317,18 +1246,18 @@ int smi_pq_train(const void* xn, int64_t n, int32_t d, int32_t dsub, const int32
                   : dsub == 32 ? launch_pq_accumulate<32> : launch_pq_accumulate<64>;
   for (int it = 0; it < n_iter; ++it) {
     hipLaunchKernelGGL(pq_encode_kernel, grid_for(n, IVF_TB / 64), block, 0, st, (const f16*)xn, n, d, dsub,
-                       (const f16*)codebooks, codes);
-    HIP_TRY(hipMemsetAsync(sums, 0, (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * M * 4, st));  // the sums and the counts behind them
-    HIP_TRY(accumulate(blocks, st, (const f16*)xn, n, d, codes, sums, counts));
-    hipLaunchKernelGGL(pq_finalize_kernel, grid_for((int64_t)PQ_CW * d, IVF_TB), block, 0, st, (const long long*)sums, counts, d,
-                       dsub, (f16*)codebooks);
+                       (const f16*)codebooks, w.codes);
+    HIP_TRY(hipMemsetAsync(w.sums, 0, (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * M * 4, st));  // the sums and the counts behind
+    HIP_TRY(accumulate(blocks, st, (const f16*)xn, n, d, w.codes, w.sums, w.counts));
+    hipLaunchKernelGGL(pq_finalize_kernel, grid_for((int64_t)PQ_CW * d, IVF_TB), block, 0, st, (const long long*)w.sums,
+                       w.counts, d, dsub, (f16*)codebooks);
     HIP_TRY(hipGetLastError());
   }
   return SMI_OK;
 }
 
 int64_t smi_ivf_pq_build_workspace_bytes(int64_t n, int64_t K, int32_t d, int32_t dsub) {
-  return build_shape_ok(n, K, d) && pq_dsub_ok(d, dsub) ? (int64_t)build_bytes(K) : 0;
+  return build_shape_ok(n, K, d) && pq_dsub_ok(d, dsub) ? (int64_t)BuildWs(nullptr, K).bytes() : 0;
 }
 
 int smi_ivf_pq_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, int32_t dsub,
@@ -1342,7 +1271,7 @@ int smi_ivf_pq_build(const void* xn, const int32_t* labels, int64_t n, int32_t d
   if (const int rc = pq_check_codebooks(codebooks)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, (int32_t*)ws, st));
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
   // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
   hipLaunchKernelGGL(ivf_pq_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d, dsub,
                      (const f16*)codebooks, list_ids, list_offsets, (int)K, (uint8_t*)list_codes);
@@ -1351,7 +1280,7 @@ int smi_ivf_pq_build(const void* xn, const int32_t* labels, int64_t n, int32_t d
 }
 
 int64_t smi_ivf_pq_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d, int32_t dsub) {
-  return search_shape_ok(nq, K, nprobe, k, d) && pq_dsub_ok(d, dsub) ? (int64_t)search_bytes(nq, K, nprobe, k) : 0;
+  return search_shape_ok(nq, K, nprobe, k, d) && pq_dsub_ok(d, dsub) ? (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes() : 0;
 }
 
 int smi_ivf_pq_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
@@ -1363,12 +1292,10 @@ int smi_ivf_pq_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
   if (const int rc = pq_check_dsub(d, dsub)) return rc;
   if (const int rc = pq_check_codebooks(codebooks)) return rc;
   const int64_t P = nq * nprobe;
-  if (const int rc = check_ws(ws, ws_bytes, (int64_t)search_bytes(nq, K, nprobe, k),
-                              "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)"))
-    return rc;
+  const SearchWs w(ws, nq, K, nprobe, k);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  const SearchWs w(ws, P, K, k);
   const int unit = unit_pairs(P, K);  // the flat search's rule: the image and the MFMA work of a unit are the same
   HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
   const int64_t units = units_bound(P, K, unit);

@@ -192,6 +192,8 @@ struct DtwSizes {   // element counts of the workspace sections and the launch e
   int64_t path;     // (i, j) entries: sum of nx + ny - 1 over the non-empty pairs
   int64_t max_tiles, max_units;  // per pair: 64 x 64 cost tiles, strips * steps
 };
+// the workspace of launch_dtw; with_cost: the call computes the cost itself (cost == nullptr)
+size_t dtw_workspace_bytes(int n_pairs, const DtwSizes& sizes, bool with_cost);
 // cost == nullptr: compute it from xn / yn (rows from launch_l2_normalize) into the workspace; xoff / yoff: device [n_pairs + 1]
 hipError_t launch_dtw(const f16* xn, const f16* yn, int d, const float* cost, int n_pairs, const DtwSizes& sizes,
                       const int64_t* xoff, const int64_t* yoff, int64_t radius, int32_t* path, int32_t* path_len,

@@ -7,7 +7,7 @@
 // grid or chunking.  Integer atomics are therefore as reproducible here as a fixed-order sum.
 //
 // Mechanism (sized in DESIGN.md 3.17): adding every element with a global atomic would be n * d atomics (1e9 per million
-// rows).  Instead the row numbers are bucketed by label -- histogram, exclusive scan, cursor scatter, all with
+// rows).  Instead the row numbers are bucketed by label -- histogram, exclusive scan, cursor scatter (bucket.hpp), all with
 // wave-aggregated int32 atomics (one atomic per distinct label of a wave, so one huge cluster costs n / 64 of them) -- and
 // every work unit, ONE WAVE, takes KM_UNIT consecutive positions of the bucketed order, gathers their rows with 16-byte
 // loads and accumulates in registers (exactly, see the kernel).  A unit adds its registers to `sums` when the label changes
@@ -19,7 +19,7 @@
 
 #include "api_common.hpp"
 #include "common.hpp"
-#include "wave_claim.hpp"
+#include "bucket.hpp"
 
 using namespace smi;
 using namespace smi_host;
@@ -58,55 +58,12 @@ __device__ __forceinline__ u32x4 km_zero_nonfinite(u32x4 w) {
   return w;
 }
 
-__global__ __launch_bounds__(KM_TB) void km_hist_kernel(const int32_t* __restrict__ labels, int n, int K,
-                                                        int32_t* __restrict__ counts) {
-  const int64_t i = (int64_t)blockIdx.x * KM_TB + threadIdx.x;
-  const int c = i < n ? labels[i] : -1;
-  km_wave_claim(counts, c, km_label_ok(c, K), threadIdx.x & 63);
-}
-
-// cursor[c] = number of valid rows with a label below c; *total = number of valid rows.  One block: thread t owns a
-// contiguous run of the clusters (mining.hip's scan).
+// cursor[c] = number of valid rows with a label below c; *total = number of valid rows (bucket.hpp's one-block scan)
 __global__ __launch_bounds__(KM_TB) void km_scan_kernel(const int32_t* __restrict__ counts, int K,
                                                         int32_t* __restrict__ cursor, int32_t* __restrict__ total) {
-  __shared__ int part[KM_TB];
-  const int per = (K + KM_TB - 1) / KM_TB;
-  const int64_t lo64 = (int64_t)per * threadIdx.x;
-  const int lo = lo64 < K ? (int)lo64 : K, hi = lo64 + per < K ? (int)(lo64 + per) : K;
-  int sum = 0;
-  for (int i = lo; i < hi; ++i) sum += counts[i];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int i = 0; i < KM_TB; ++i) {
-      const int p = part[i];
-      part[i] = run;
-      run += p;
-    }
-    *total = run;
-  }
-  __syncthreads();
-  int run = part[threadIdx.x];
-  for (int i = lo; i < hi; ++i) {
-    cursor[i] = run;
-    run += counts[i];
-  }
-}
-
-// order[p] = a row number, olab[p] = its label, the rows of a cluster at consecutive p.  Which member lands where inside
-// its cluster's run depends on the atomics' arrival order; the sums do not.
-__global__ __launch_bounds__(KM_TB) void km_scatter_kernel(const int32_t* __restrict__ labels, int n, int K,
-                                                           int32_t* __restrict__ cursor, int32_t* __restrict__ order,
-                                                           int32_t* __restrict__ olab) {
-  const int64_t i = (int64_t)blockIdx.x * KM_TB + threadIdx.x;
-  const int c = i < n ? labels[i] : -1;
-  const bool ok = km_label_ok(c, K);
-  const int pos = km_wave_claim(cursor, c, ok, threadIdx.x & 63);
-  if (ok) {  // pos < *total <= n: the histogram counted this row with the same test
-    order[pos] = (int32_t)i;
-    olab[pos] = c;
-  }
+  bucket_scan<KM_TB, 1>(
+      K, [&](int i, int(&v)[1]) { v[0] = counts[i]; }, [&](int i, const int(&run)[1]) { cursor[i] = run[0]; },
+      [&](const int(&run)[1]) { *total = run[0]; });
 }
 
 // One wave = one work unit: positions [u * KM_UNIT, (u + 1) * KM_UNIT) of the bucketed order.  Lane l of a column pass owns
@@ -294,71 +251,76 @@ __global__ __launch_bounds__(KM_PARTS) void km_round_sum_kernel(const double* __
   }
 }
 
-size_t up16(size_t b) { return (b + 15) / 16 * 16; }
-
-// update:   cursor int32 [K] | total int32 [4] | order int32 [n] | labels in bucket order int32 [n]
+// update: cursor int32 [K] | total int32 [4] | order int32 [n] | labels in bucket order int32 [n]
+struct KmUpdateWs : WsLayout {
+  int32_t *cursor, *total, *order, *olab;
+  KmUpdateWs(void* ws, int64_t n, int64_t K) : WsLayout(ws) {
+    cursor = take<int32_t>(K, 16);
+    total = take<int32_t>(4, 16);
+    order = take<int32_t>(n, 16);
+    olab = take<int32_t>(n, 16);
+  }
+};
 // finalise: live flags int32 [K] | fp16 rows from smi_xsim_normalize [padded K][d]
-size_t km_update_bytes(int64_t n, int64_t K) { return up16((size_t)K * 4) + 16 + 2 * up16((size_t)n * 4); }
-size_t km_finalize_bytes(int64_t K, int d) { return up16((size_t)K * 4) + (size_t)smi_xsim_padded_rows(K) * d * 2; }
-size_t km_workspace_bytes(int64_t n, int64_t K, int d) { return std::max(km_update_bytes(n, K), km_finalize_bytes(K, d)); }
-// fit, behind the above: new labels int32 [n] | partial objectives fp64 [KM_PARTS] | partial moved counts int32 [KM_PARTS]
-size_t km_fit_own_bytes(int64_t n) { return up16((size_t)n * 4) + KM_PARTS * 12; }
+struct KmFinalizeWs : WsLayout {
+  int32_t* live_flag;
+  f16* tmp;
+  KmFinalizeWs(void* ws, int64_t K, int d) : WsLayout(ws) {
+    live_flag = take<int32_t>(K, 16);
+    tmp = take<f16>((size_t)smi_xsim_padded_rows(K) * d, 16);
+  }
+};
+// the two are never live at once: smi_kmeans_workspace_bytes
+size_t km_workspace_bytes(int64_t n, int64_t K, int d) {
+  return std::max(KmUpdateWs(nullptr, n, K).bytes(), KmFinalizeWs(nullptr, K, d).bytes());
+}
+// fit: the workspace above | smi_xsim_topk's at k = 1 | new labels int32 [n] | partial objectives fp64 [KM_PARTS] | partial
+//      moved counts int32 [KM_PARTS]
+struct KmFitWs : WsLayout {
+  void *km_ws, *xs_ws;
+  int32_t *new_labels, *part_moved;
+  double* part_obj;
+  KmFitWs(void* ws, int64_t n, int64_t K, int d) : WsLayout(ws) {
+    km_ws = take<char>(km_workspace_bytes(n, K, d), 16);
+    xs_ws = take<char>((size_t)smi_xsim_workspace_bytes(n, K, 1, d), 16);
+    new_labels = take<int32_t>(n, 16);
+    part_obj = take<double>(KM_PARTS);
+    part_moved = take<int32_t>(KM_PARTS);
+  }
+};
 
 hipError_t km_update(const f16* xn, const int32_t* labels, int n, int d, int K, long long* sums, int32_t* counts, void* ws,
                      hipStream_t stream) {
-  char* p = (char*)ws;
-  int32_t* cursor = (int32_t*)p;
-  p += up16((size_t)K * 4);
-  int32_t* total = (int32_t*)p;
-  p += 16;
-  int32_t* order = (int32_t*)p;
-  p += up16((size_t)n * 4);
-  int32_t* olab = (int32_t*)p;
+  const KmUpdateWs w(ws, n, K);
   hipError_t e;
   if ((e = hipMemsetAsync(counts, 0, (size_t)K * 4, stream)) != hipSuccess) return e;
   if ((e = hipMemsetAsync(sums, 0, (size_t)K * d * 8, stream)) != hipSuccess) return e;
-  const dim3 rows_grid((unsigned)(((int64_t)n + KM_TB - 1) / KM_TB)), block(KM_TB);
-  hipLaunchKernelGGL(km_hist_kernel, rows_grid, block, 0, stream, labels, n, K, counts);
-  hipLaunchKernelGGL(km_scan_kernel, dim3(1), block, 0, stream, counts, K, cursor, total);
-  hipLaunchKernelGGL(km_scatter_kernel, rows_grid, block, 0, stream, labels, n, K, cursor, order, olab);
+  const dim3 rows_grid = grid_for(n, KM_TB), block(KM_TB);
+  // order[p] = a row number, olab[p] = its label, the rows of a cluster at consecutive p.  Which member lands where inside
+  // its cluster's run depends on the atomics' arrival order; the sums do not.
+  hipLaunchKernelGGL(bucket_hist_kernel<KM_TB>, rows_grid, block, 0, stream, labels, n, K, counts);
+  hipLaunchKernelGGL(km_scan_kernel, dim3(1), block, 0, stream, counts, K, w.cursor, w.total);
+  hipLaunchKernelGGL(bucket_scatter_kernel<KM_TB>, rows_grid, block, 0, stream, labels, n, K, w.cursor, w.order, w.olab);
   // units for all n rows: those past the number of valid rows find nothing to do
   const int64_t units = ((int64_t)n + KM_UNIT - 1) / KM_UNIT;
-  hipLaunchKernelGGL(km_accumulate_kernel, dim3((unsigned)((units + KM_TB / 64 - 1) / (KM_TB / 64))), block, 0, stream, xn,
-                     d, order, olab, total, (unsigned long long*)sums);
+  hipLaunchKernelGGL(km_accumulate_kernel, grid_for(units, KM_TB / 64), block, 0, stream, xn, d, w.order, w.olab, w.total,
+                     (unsigned long long*)sums);
   return hipGetLastError();
 }
 
 hipError_t km_finalize(const long long* sums, const int32_t* counts, int K, int d, float* cf32, f16* cf16,
                        int32_t* empty_count, void* ws, hipStream_t stream) {
-  int32_t* live_flag = (int32_t*)ws;
-  f16* tmp = (f16*)((char*)ws + up16((size_t)K * 4));
+  const KmFinalizeWs w(ws, K, d);
   const int64_t rows_pad = smi_xsim_padded_rows(K);
   hipError_t e;
   if ((e = hipMemsetAsync(empty_count, 0, 4, stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(km_finalize_kernel, dim3((unsigned)(((int64_t)K + 3) / 4)), dim3(KM_TB), 0, stream, sums, counts, K, d,
-                     cf32, live_flag, empty_count);
+  hipLaunchKernelGGL(km_finalize_kernel, grid_for(K, KM_TB / 64), dim3(KM_TB), 0, stream, sums, counts, K, d, cf32, w.live_flag,
+                     empty_count);
   // the fp16 rows are smi_xsim_normalize's, of every fp32 row; only the live ones are taken over
-  if ((e = launch_l2_normalize(cf32, 1, tmp, K, d, stream)) != hipSuccess) return e;
-  hipLaunchKernelGGL(km_select_kernel, dim3((unsigned)((rows_pad + 3) / 4)), dim3(KM_TB), 0, stream, tmp, live_flag, K,
-                     rows_pad, d, cf16);
+  if ((e = launch_l2_normalize(cf32, 1, w.tmp, K, d, stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(km_select_kernel, grid_for(rows_pad, KM_TB / 64), dim3(KM_TB), 0, stream, w.tmp, w.live_flag, K, rows_pad, d,
+                     cf16);
   return hipGetLastError();
-}
-
-int km_check_shape(int64_t n, int32_t d, int64_t K) {
-  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
-  if (K < 1) return fail(SMI_ERR_INVALID_ARG, "K=%lld: at least one cluster", (long long)K);
-  if (n < 1) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  if (n > 0x7fffff00LL || K > 0x7fffff00LL)
-    return fail(SMI_ERR_UNSUPPORTED, "n=%lld, K=%lld: row and cluster numbers must fit int32", (long long)n, (long long)K);
-  return SMI_OK;
-}
-
-int km_check_ws(const void* ws, int64_t ws_bytes, int64_t need, const char* formula) {
-  if (!ws) return fail(SMI_ERR_INVALID_ARG, "null workspace");
-  if ((uintptr_t)ws % 16) return fail(SMI_ERR_INVALID_ARG, "workspace must be 16-byte aligned");
-  if (ws_bytes < need)
-    return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, %s = %lld", (long long)ws_bytes, formula, (long long)need);
-  return SMI_OK;
 }
 
 }  // namespace
@@ -375,8 +337,8 @@ int64_t smi_kmeans_workspace_bytes(int64_t n, int64_t K, int32_t d) {
 int smi_kmeans_update(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, int64_t* sums,
                       int32_t* counts, void* ws, int64_t ws_bytes, void* stream) {
   if (!xn || !labels || !sums || !counts) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = km_check_shape(n, d, K)) return rc;
-  if (const int rc = km_check_ws(ws, ws_bytes, smi_kmeans_workspace_bytes(n, K, d), "smi_kmeans_workspace_bytes(n, K, d)"))
+  if (const int rc = check_shape(n, nullptr, d, K, "cluster")) return rc;
+  if (const int rc = check_ws(ws, ws_bytes, smi_kmeans_workspace_bytes(n, K, d), "smi_kmeans_workspace_bytes(n, K, d)"))
     return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   HIP_TRY(km_update((const f16*)xn, labels, (int)n, d, (int)K, (long long*)sums, counts, ws, (hipStream_t)stream));
@@ -386,8 +348,8 @@ int smi_kmeans_update(const void* xn, const int32_t* labels, int64_t n, int32_t 
 int smi_kmeans_finalize(const int64_t* sums, const int32_t* counts, int64_t K, int32_t d, float* centroids_f32,
                         void* centroids_f16, int32_t* empty_count, void* ws, int64_t ws_bytes, void* stream) {
   if (!sums || !counts || !centroids_f32 || !centroids_f16 || !empty_count) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = km_check_shape(1, d, K)) return rc;
-  if (const int rc = km_check_ws(ws, ws_bytes, smi_kmeans_workspace_bytes(1, K, d), "smi_kmeans_workspace_bytes(1, K, d)"))
+  if (const int rc = check_shape(1, nullptr, d, K, "cluster")) return rc;
+  if (const int rc = check_ws(ws, ws_bytes, smi_kmeans_workspace_bytes(1, K, d), "smi_kmeans_workspace_bytes(1, K, d)"))
     return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   HIP_TRY(km_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, empty_count, ws,
@@ -400,36 +362,26 @@ int smi_kmeans_fit(const void* xn, int64_t n, int32_t d, int64_t K, int32_t n_it
                    int32_t* moved, int32_t* empty, void* ws, int64_t ws_bytes, void* stream) {
   if (!xn || !centroids_f32 || !centroids_f16 || !labels || !scores || !sums || !counts || !objective || !moved || !empty)
     return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = km_check_shape(n, d, K)) return rc;
+  if (const int rc = check_shape(n, nullptr, d, K, "cluster")) return rc;
   if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d", n_iter);
   if (resume != 0 && resume != 1) return fail(SMI_ERR_INVALID_ARG, "resume=%d (0 or 1)", resume);
-  const int64_t km_bytes = smi_kmeans_workspace_bytes(n, K, d), xs_bytes = smi_xsim_workspace_bytes(n, K, 1, d);
-  const int64_t need = km_bytes + (int64_t)up16((size_t)xs_bytes) + (int64_t)km_fit_own_bytes(n);
-  if (const int rc = km_check_ws(ws, ws_bytes, need,
-                                 "smi_kmeans_workspace_bytes(n, K, d) + smi_xsim_workspace_bytes(n, K, 1, d) + 4 n (each "
-                                 "rounded up to 16) + 3072"))
+  const KmFitWs w(ws, n, K, d);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(),
+                              "smi_kmeans_workspace_bytes(n, K, d) + smi_xsim_workspace_bytes(n, K, 1, d) + 4 n (each "
+                              "rounded up to 16) + 3072"))
     return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  char* p = (char*)ws;
-  void* km_ws = p;
-  p += km_bytes;
-  void* xs_ws = p;
-  p += up16((size_t)xs_bytes);
-  int32_t* new_labels = (int32_t*)p;
-  p += up16((size_t)n * 4);
-  double* part_obj = (double*)p;
-  int32_t* part_moved = (int32_t*)(p + KM_PARTS * 8);
   const int per = (int)((n + KM_PARTS - 1) / KM_PARTS);
   const int64_t n_pad = smi_xsim_padded_rows(n), k_pad = smi_xsim_padded_rows(K);
 
   // assign every row to its nearest centroid (ties to the lower index: smi_xsim_topk's order), then this round's record
   auto assign = [&](int slot) -> int {
-    HIP_TRY(launch_xsim_topk((const f16*)xn, n, n_pad, (const f16*)centroids_f16, K, k_pad, d, 1, 0, new_labels, scores,
-                             xs_ws, st));
-    hipLaunchKernelGGL(km_round_part_kernel, dim3(KM_PARTS), dim3(KM_TB), 0, st, scores, new_labels, labels, (int)n, per,
-                       part_obj, part_moved);
-    hipLaunchKernelGGL(km_round_sum_kernel, dim3(1), dim3(KM_PARTS), 0, st, part_obj, part_moved, objective + slot,
+    HIP_TRY(launch_xsim_topk((const f16*)xn, n, n_pad, (const f16*)centroids_f16, K, k_pad, d, 1, 0, w.new_labels, scores,
+                             w.xs_ws, st));
+    hipLaunchKernelGGL(km_round_part_kernel, dim3(KM_PARTS), dim3(KM_TB), 0, st, scores, w.new_labels, labels, (int)n, per,
+                       w.part_obj, w.part_moved);
+    hipLaunchKernelGGL(km_round_sum_kernel, dim3(1), dim3(KM_PARTS), 0, st, w.part_obj, w.part_moved, objective + slot,
                        moved + slot);
     HIP_TRY(hipGetLastError());
     return SMI_OK;
@@ -442,8 +394,8 @@ int smi_kmeans_fit(const void* xn, int64_t n, int32_t d, int64_t K, int32_t n_it
     if (const int rc = assign(slot++)) return rc;
   }
   for (int it = 0; it < n_iter; ++it) {
-    HIP_TRY(km_update((const f16*)xn, labels, (int)n, d, (int)K, (long long*)sums, counts, km_ws, st));
-    HIP_TRY(km_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, empty + it, km_ws, st));
+    HIP_TRY(km_update((const f16*)xn, labels, (int)n, d, (int)K, (long long*)sums, counts, w.km_ws, st));
+    HIP_TRY(km_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, empty + it, w.km_ws, st));
     if (const int rc = assign(slot++)) return rc;
   }
   return SMI_OK;

@@ -174,14 +174,13 @@ __global__ __launch_bounds__(256) void laser2_finalize_kernel(const float* __res
   }
 }
 
-inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
-
 }  // namespace
 }  // namespace smi
 
 using namespace smi;
 using smi_host::DevBuf;
 using smi_host::fail;
+using smi_host::round_up;
 
 struct smi_laser2 {
   smi_laser2_config cfg{};

@@ -19,8 +19,9 @@
 // (one byte each); at the 3-4 rounds real data takes that is a few hundred KB of traffic.
 #include <algorithm>
 
+#include "api_common.hpp"
+#include "bucket.hpp"
 #include "common.hpp"
-#include "kernels.hpp"
 
 namespace smi {
 
@@ -164,33 +165,13 @@ __global__ __launch_bounds__(MB) void mine_count_kernel(MineArgs a, const unsign
   }
 }
 
-// block_count[0 .. nb) -> its exclusive prefix sums in place, the total to *out_count.  One block: thread t owns a contiguous
-// run of the counts (nb is ncand / 256: 2048 at 262 144 x 262 144).
-__global__ __launch_bounds__(MB) void mine_scan_kernel(int32_t* __restrict__ block_count, int64_t nb,
+// block_count[0 .. nb) -> its exclusive prefix sums in place (one pointer reads and writes the counts: its __restrict__ says
+// nothing about them), the total to *out_count: bucket.hpp's one-block scan (nb is ncand / 256: 2048 at 262 144 x 262 144).
+__global__ __launch_bounds__(MB) void mine_scan_kernel(int32_t* __restrict__ block_count, int nb,
                                                        int32_t* __restrict__ out_count) {
-  __shared__ int part[MB];
-  const int64_t per = (nb + MB - 1) / MB;
-  const int64_t lo = per * threadIdx.x < nb ? per * threadIdx.x : nb, hi = lo + per < nb ? lo + per : nb;
-  int sum = 0;
-  for (int64_t i = lo; i < hi; ++i) sum += block_count[i];
-  part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int i = 0; i < MB; ++i) {
-      const int p = part[i];
-      part[i] = run;
-      run += p;
-    }
-    *out_count = run;
-  }
-  __syncthreads();
-  int run = part[threadIdx.x];
-  for (int64_t i = lo; i < hi; ++i) {
-    const int n = block_count[i];
-    block_count[i] = run;
-    run += n;
-  }
+  bucket_scan<MB, 1>(
+      nb, [&](int i, int(&v)[1]) { v[0] = block_count[i]; }, [&](int i, const int(&run)[1]) { block_count[i] = run[0]; },
+      [&](const int(&run)[1]) { *out_count = run[0]; });
 }
 
 __global__ __launch_bounds__(MB) void mine_scatter_kernel(MineArgs a, const unsigned char* __restrict__ state,
@@ -259,15 +240,28 @@ int64_t mine_candidates(int64_t nx, int64_t ny, int retrieval) {
   return retrieval == 1 ? ny : (retrieval == 3 ? nx + ny : nx);
 }
 
+// workspace: [max only: source slots u64 [nx] | target slots u64 [ny]] block counts int32 [nb] | live count int32
+//            [max only: candidate states u8 [nx + ny] | source taken u8 [nx] | target taken u8 [ny]]; the max-only regions
+//            are empty for the other retrievals
+struct MineWs : smi_host::WsLayout {
+  unsigned long long *src_slot, *trg_slot;
+  int32_t *block_count, *live_count;
+  unsigned char *state, *src_taken, *trg_taken;
+  MineWs(void* ws, int64_t nx, int64_t ny, int retrieval) : smi_host::WsLayout(ws) {
+    const int64_t mx = retrieval == 3 ? nx : 0, my = retrieval == 3 ? ny : 0;
+    src_slot = take<unsigned long long>(mx);
+    trg_slot = take<unsigned long long>(my);
+    block_count = take<int32_t>((mine_candidates(nx, ny, retrieval) + MB - 1) / MB);
+    live_count = take<int32_t>(1);
+    state = take<unsigned char>(mx + my);
+    src_taken = take<unsigned char>(mx);
+    trg_taken = take<unsigned char>(my);
+  }
+};
+
 }  // namespace
 
-// workspace: [max only: source slots u64 [nx] | target slots u64 [ny]] block counts int32 [nb] | live count int32
-//            [max only: candidate states u8 [nx + ny] | source taken u8 [nx] | target taken u8 [ny]]
-size_t mine_workspace_bytes(int64_t nx, int64_t ny, int retrieval) {
-  const int64_t ncand = mine_candidates(nx, ny, retrieval);
-  const size_t counts = (size_t)((ncand + MB - 1) / MB + 1) * 4;
-  return retrieval == 3 ? counts + (size_t)(nx + ny) * 10 : counts;
-}
+size_t mine_workspace_bytes(int64_t nx, int64_t ny, int retrieval) { return MineWs(nullptr, nx, ny, retrieval).bytes(); }
 
 hipError_t launch_mine(const int32_t* fwd_best, const float* fwd_score, int64_t nx, const int32_t* bwd_best,
                        const float* bwd_score, int64_t ny, int retrieval, float threshold, int32_t* out_src,
@@ -288,38 +282,27 @@ hipError_t launch_mine(const int32_t* fwd_best, const float* fwd_score, int64_t 
   a.thr = threshold;
   const int64_t nb = (a.ncand + MB - 1) / MB;
   const dim3 grid((unsigned)nb), block(MB);
-  char* p = (char*)ws;
-  unsigned long long *src_slot = nullptr, *trg_slot = nullptr;
-  if (retrieval == 3) {
-    src_slot = (unsigned long long*)p;
-    trg_slot = src_slot + nx;
-    p += (size_t)(nx + ny) * 8;
-  }
-  int32_t* block_count = (int32_t*)p;
-  int32_t* live_count = block_count + nb;
-  unsigned char* state = nullptr;
+  const MineWs w(ws, nx, ny, retrieval);
   hipError_t e;
   if (retrieval == 3) {
-    state = (unsigned char*)(live_count + 1);
-    unsigned char* src_taken = state + a.ncand;
-    unsigned char* trg_taken = src_taken + nx;
-    if ((e = hipMemsetAsync(src_slot, 0, (size_t)(nx + ny) * 8, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(src_taken, 0, (size_t)(nx + ny), stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(max_init_kernel, grid, block, 0, stream, a, state);
+    // the slots of both sides, then the taken flags of both sides: each pair is one contiguous run
+    if ((e = hipMemsetAsync(w.src_slot, 0, (size_t)(nx + ny) * 8, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(w.src_taken, 0, (size_t)(nx + ny), stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(max_init_kernel, grid, block, 0, stream, a, w.state);
     int32_t live = 0;
     do {
-      hipLaunchKernelGGL(max_bid_kernel, grid, block, 0, stream, a, state, src_slot, trg_slot, live_count);
-      hipLaunchKernelGGL(max_accept_kernel, grid, block, 0, stream, a, state, src_slot, trg_slot, src_taken, trg_taken);
-      hipLaunchKernelGGL(max_retire_kernel, grid, block, 0, stream, a, state, src_slot, trg_slot, src_taken, trg_taken,
-                         live_count);
+      hipLaunchKernelGGL(max_bid_kernel, grid, block, 0, stream, a, w.state, w.src_slot, w.trg_slot, w.live_count);
+      hipLaunchKernelGGL(max_accept_kernel, grid, block, 0, stream, a, w.state, w.src_slot, w.trg_slot, w.src_taken, w.trg_taken);
+      hipLaunchKernelGGL(max_retire_kernel, grid, block, 0, stream, a, w.state, w.src_slot, w.trg_slot, w.src_taken, w.trg_taken,
+                         w.live_count);
       if ((e = hipGetLastError()) != hipSuccess) return e;
-      if ((e = hipMemcpyAsync(&live, live_count, sizeof(live), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
+      if ((e = hipMemcpyAsync(&live, w.live_count, sizeof(live), hipMemcpyDeviceToHost, stream)) != hipSuccess) return e;
       if ((e = hipStreamSynchronize(stream)) != hipSuccess) return e;
     } while (live > 0);
   }
-  hipLaunchKernelGGL(mine_count_kernel, grid, block, 0, stream, a, state, block_count);
-  hipLaunchKernelGGL(mine_scan_kernel, dim3(1), block, 0, stream, block_count, nb, out_count);
-  hipLaunchKernelGGL(mine_scatter_kernel, grid, block, 0, stream, a, state, block_count, out_src, out_trg, out_score);
+  hipLaunchKernelGGL(mine_count_kernel, grid, block, 0, stream, a, w.state, w.block_count);
+  hipLaunchKernelGGL(mine_scan_kernel, dim3(1), block, 0, stream, w.block_count, (int)nb, out_count);
+  hipLaunchKernelGGL(mine_scatter_kernel, grid, block, 0, stream, a, w.state, w.block_count, out_src, out_trg, out_score);
   return hipGetLastError();
 }
 

@@ -32,8 +32,6 @@ __global__ void glu_interleave_kernel(const f16* __restrict__ src, f16* __restri
 
 namespace {
 
-inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
-
 int fetch_host(const smi_tensor& t, int64_t expect, std::vector<float>& out, const char* name) {
   if (!t.data) return fail(SMI_ERR_INVALID_ARG, "weight %s: null data", name);
   if (t.numel != expect)

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "api_common.hpp"
 #include "gemm_tile.hpp"
 #include "gemm_tile256.hpp"
 #include "kernels.hpp"
@@ -615,16 +616,25 @@ hipError_t launch_margin_select(const float* fs, const int32_t* fi, int64_t nx, 
 static int xsim_chunks(int64_t nty) { return (int)(nty < 8 ? nty : 8); }
 static int round_k(int k) { return k <= 1 ? 1 : (k <= 2 ? 2 : (k <= 4 ? 4 : 8)); }
 
-// per-chunk partial lists: [chunks][nx_pad][K] scores + indices
-static size_t xsim_lists_bytes(int64_t nx_pad, int64_t ny_pad, int K) {
-  return (size_t)xsim_chunks(ny_pad / GT_BN) * nx_pad * K * 8;
-}
-// ... followed by the tile-major copies of Xn and Yn.  The formula depends on the shapes alone: what a caller queried is what
-// xsim_run writes, whatever another host thread does to the tuning switches in between.
+// workspace: partial scores fp32 [chunks][nx_pad][K] | partial indices int32 [chunks][nx_pad][K] | tile-major copy of Xn
+//            f16 [nx_pad][d] | of Yn f16 [ny_pad][d] (one pass over each: ~1.5 ms of the 1.8 s at 1 M x 1 M)
+// `chunks` is one per 128 columns of Yn up to 8 (the size since the 128 x 128 engine); xsim_run fills one per 256, never more.
+// The layout depends on the shapes alone: what a caller queried is what xsim_run writes, whatever another host thread does
+// to the tuning switches in between.
+struct XsimWs : smi_host::WsLayout {
+  float* ps;
+  int* pi;
+  f16 *xtm, *ytm;
+  XsimWs(void* ws, int64_t nx_pad, int64_t ny_pad, int K, int d) : smi_host::WsLayout(ws) {
+    const size_t lists = (size_t)xsim_chunks(ny_pad / GT_BN) * nx_pad * K;
+    ps = take<float>(lists);
+    pi = take<int>(lists);
+    xtm = take<f16>((size_t)nx_pad * d);
+    ytm = take<f16>((size_t)ny_pad * d);
+  }
+};
 size_t xsim_workspace_bytes(int64_t nx_pad, int64_t ny_pad, int k, int d) {
-  const int K = round_k(k);
-  const size_t tm = (size_t)(nx_pad + ny_pad) * d * sizeof(f16);
-  return xsim_lists_bytes(nx_pad, ny_pad, K) + tm;
+  return XsimWs(nullptr, nx_pad, ny_pad, round_k(k), d).bytes();
 }
 
 template <int K>
@@ -639,16 +649,12 @@ static hipError_t xsim_run(const f16* Xn, int64_t nx, int64_t nx_pad, const f16*
     if (e != hipSuccess) return e;
     attr_done.set();
   }
-  float* ps = (float*)ws;
+  const XsimWs w(ws, nx_pad, ny_pad, K, d);
   const int ntx = (int)(nx_pad / G2_BM), nty = (int)(ny_pad / G2_BN);
   const int nchunks = xsim_chunks(nty);
   const int tpc = (nty + nchunks - 1) / nchunks;
-  int* pi = (int*)((char*)ws + (size_t)nchunks * nx_pad * K * 4);
-  // tile-major copies of both operands behind the partial lists (one pass over each: ~1.5 ms of the 1.8 s at 1 M x 1 M)
-  f16* xtm = (f16*)((char*)ws + xsim_lists_bytes(nx_pad, ny_pad, K));
-  f16* ytm = xtm + (size_t)nx_pad * d;
   const f16* src[2] = {Xn, Yn};
-  f16* dst[2] = {xtm, ytm};
+  f16* dst[2] = {w.xtm, w.ytm};
   const int64_t rows[2] = {nx_pad, ny_pad};
   for (int o = 0; o < 2; ++o)
     for (int64_t r0 = 0; r0 < rows[o]; r0 += 65535LL * TM_ROWS) {  // grid.y limit of the pack kernel
@@ -656,12 +662,12 @@ static hipError_t xsim_run(const f16* Xn, int64_t nx, int64_t nx_pad, const f16*
       hipError_t e = launch_pack_tile_major(src[o] + r0 * d, dst[o] + r0 * d, (int)nr, d, 0, stream);
       if (e != hipSuccess) return e;
     }
-  hipLaunchKernelGGL(xsim_tile256_kernel<K>, dim3(ntx * nchunks), dim3(G2_THREADS), lds, stream, xtm, ytm, d, ntx, nty,
-                     nchunks, tpc, (int)ny, (int)nx_pad, ps, pi);
+  hipLaunchKernelGGL(xsim_tile256_kernel<K>, dim3(ntx * nchunks), dim3(G2_THREADS), lds, stream, w.xtm, w.ytm, d, ntx, nty,
+                     nchunks, tpc, (int)ny, (int)nx_pad, w.ps, w.pi);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(xsim_merge_kernel<K>, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, stream,
-                     ps, pi, nchunks, nx, (int)nx_pad, k, y_off, idx, score);
+                     w.ps, w.pi, nchunks, nx, (int)nx_pad, k, y_off, idx, score);
   return hipGetLastError();
 }
 

@@ -77,9 +77,13 @@ def _check_build(x16, labels, k):
     return off, sizes, ids
 
 
+# k = 255 .. 513 (at n = 4099 only): a thread of the one-block scan (csrc/bucket.hpp) owns ceil(k / 256) lists -- one at 256,
+# two at 257 with half the threads owning none, three at 513
+BUILD_CASES = [(n, k) for n in (1, A - 1, A, A + 1, 4099) for k in (1, 3, 300)] + [(4099, k) for k in (255, 256, 257, 513)]
+
+
 @pytest.mark.parametrize("d", [64, 192, 1024])
-@pytest.mark.parametrize("k", [1, 3, 300])
-@pytest.mark.parametrize("n", [1, A - 1, A, A + 1, 4099])
+@pytest.mark.parametrize("n,k", BUILD_CASES)
 def test_build_is_the_exact_list_layout(n, k, d):
     rng = np.random.default_rng(n * 1000003 + k * 1009 + d)
     x = rng.standard_normal((n, d)).astype(np.float16)
@@ -134,18 +138,21 @@ def test_search_one_long_list_many_tiles_several_query_blocks():
     _check_search(x, np.zeros(4099, dtype=np.int64), 1, q, np.zeros((257, 1), dtype=np.int64), (1, 4, 8))
 
 
-def test_search_lists_shorter_than_k_and_empty_lists():
+# the list count also walks the boundaries of the inversion's one-block scan (csrc/bucket.hpp): a thread owns ceil(K / 256)
+# lists -- one at 256, two at 257 with half the threads owning none, three at 513 -- in the pair offsets and the unit offsets
+@pytest.mark.parametrize("k_lists", [300, 255, 256, 257, 513])
+def test_search_lists_shorter_than_k_and_empty_lists(k_lists):
     rng = np.random.default_rng(4)
     x, q = R.integer_rows(rng, 4099, 64), R.integer_rows(rng, 300, 64)
-    labels = rng.integers(0, 300, 4099)
-    labels[labels % 5 == 0] += 1  # every fifth list stays empty
+    labels = rng.integers(0, k_lists, 4099)
+    labels[labels % 5 == 0] += 1  # every fifth list stays empty (at 256 lists the rows of list 255 get no list at all)
     labels[:40] = np.arange(40) % 2 * 2 + 1  # two larger lists; most of the others hold ~17 rows, some fewer than 8
-    probes = _distinct_probes(rng, 300, 300, 8)
+    probes = _distinct_probes(rng, 300, k_lists, 8)
     probes[:5] = np.arange(0, 40, 5).reshape(1, 8)  # rows that probe empty lists only: k x (-inf, -1)
     probes[5, :] = [0, 5, 10, 15, 20, 25, 30, 7]    # one short list among empty ones: a (-inf, -1) tail
-    _check_search(x, labels, 300, q, probes, (8,))
-    few = np.where(np.arange(4099) < 20, np.arange(4099) % 10, -1)  # lists of 2 rows, 290 empty, most rows left out
-    _check_search(x, few, 300, q, rng.integers(0, 12, (300, 8)), (8, 3))  # repeated lists in a row: rows returned twice
+    _check_search(x, labels, k_lists, q, probes, (8,))
+    few = np.where(np.arange(4099) < 20, np.arange(4099) % 10, -1)  # lists of 2 rows, the others empty, most rows left out
+    _check_search(x, few, k_lists, q, rng.integers(0, 12, (300, 8)), (8, 3))  # repeated lists in a row: rows returned twice
 
 
 def test_search_d1024_nprobe4_k5():

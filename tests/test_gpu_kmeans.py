@@ -48,11 +48,13 @@ def _check_update(x16, labels, k):
 
 
 # ------------------------------------------------------------------------------------------------ update
-# a sampled cross of n in {1, 63, 64, 65, 255, 256, 257, 1000, 4099}, K in {1, 2, 7, 255, 256, 257, 300}, d in {64, 192, 1024}
+# a sampled cross of n in {1, 63, 64, 65, 255, 256, 257, 1000, 4099}, K in {1, 2, 7, 255, 256, 257, 300}, d in {64, 192, 1024};
+# and K = 513: a thread of the one-block scan (csrc/bucket.hpp) owns ceil(K / 256) clusters -- one at 256, two at 257 with
+# half the threads owning none, three at 513
 UPDATE_SHAPES = [(1, 1, 64), (1, 300, 1024), (63, 2, 64), (63, 255, 192), (64, 7, 192), (64, 1, 1024), (65, 255, 64),
                  (65, 2, 1024), (255, 256, 192), (255, 7, 1024), (256, 257, 64), (256, 2, 192), (257, 300, 1024),
                  (257, 1, 64), (1000, 7, 1024), (1000, 256, 64), (1000, 257, 192), (4099, 1, 1024), (4099, 300, 192),
-                 (4099, 255, 64), (4099, 7, 1024)]
+                 (4099, 255, 64), (4099, 7, 1024), (4099, 513, 64)]
 PATTERNS = ("random", "sorted", "reversed", "one", "skipped")
 
 

@@ -91,7 +91,10 @@ def _assert_mine_exact(fb, fs, bb, bs, nx, ny, retrieval, threshold=None):
 #   255 x 257      max: 512 candidates = two full blocks; fwd one partial block, bwd one block and one thread
 #   600 x 513      several blocks, the last partial
 #   2305 x 769     ten and four blocks; max: 3074 candidates
-_SHAPES = [(1, 1), (1, 300), (300, 1), (255, 257), (600, 513), (2305, 769)]
+#   65536 x 1, 32768 x 32769   the block-count scan (one block of 256 threads, csrc/bucket.hpp) where a thread's run is one
+#                  count: fwd 65 536 candidates = 256 blocks, every thread owns one; max 65 537 = 257 blocks, a run is two
+#                  counts and half the threads own none -- once with one target for all, once as a matching of several rounds
+_SHAPES = [(1, 1), (1, 300), (300, 1), (255, 257), (600, 513), (2305, 769), (65536, 1), (32768, 32769)]
 _QUARTERS = np.arange(-4, 5, dtype=np.float32) / 4      # multiples of 1/4 in [-1, 1]
 
 

@@ -43,7 +43,7 @@ def kernel_trace(fn):
         out = {}
         for ev in prof.events():
             if ev.device_time > 0:
-                name = next((s for s in ("ivf_scan_lists", "ivf_hist", "ivf_scan_kernel", "ivf_scatter", "ivf_gather",
+                name = next((s for s in ("ivf_scan_lists", "bucket_hist", "ivf_scan_kernel", "bucket_scatter", "ivf_gather",
                                          "ivf_fill", "topk_merge", "Memset", "memset") if s in ev.name), None)
                 if name:
                     out[name] = round(out.get(name, 0.0) + ev.device_time, 2)

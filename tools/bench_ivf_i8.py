@@ -32,8 +32,8 @@ from bench_ivf import PEAK_FP16, queries  # noqa: E402
 from bench_kmeans import planted, windows_ms  # noqa: E402
 
 PEAK_I8 = 2 * PEAK_FP16  # dense int8 MFMA, op/s: twice the fp16 rate
-KERNELS = ("ivf_i8_scan_lists", "ivf_scan_lists", "ivf_i8_encode", "ivf_i8_gather", "ivf_gather", "ivf_hist",
-           "ivf_scan_kernel", "ivf_scatter", "ivf_fill", "topk_merge", "Memset", "memset")
+KERNELS = ("ivf_i8_scan_lists", "ivf_scan_lists", "ivf_i8_encode", "ivf_i8_gather", "ivf_gather", "bucket_hist",
+           "ivf_scan_kernel", "bucket_scatter", "ivf_fill", "topk_merge", "Memset", "memset")
 
 
 def kernel_trace(fn):

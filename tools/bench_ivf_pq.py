@@ -33,7 +33,7 @@ from bench_ivf_i8 import recalls  # noqa: E402
 from bench_kmeans import planted, windows_ms  # noqa: E402
 
 KERNELS = ("ivf_pq_scan_lists", "ivf_scan_lists", "ivf_pq_gather", "ivf_gather", "pq_encode", "pq_accumulate", "pq_finalize",
-           "pq_init", "ivf_hist", "ivf_scan_kernel", "ivf_scatter", "ivf_fill", "topk_merge", "Memset", "memset")
+           "pq_init", "bucket_hist", "ivf_scan_kernel", "bucket_scatter", "ivf_fill", "topk_merge", "Memset", "memset")
 
 
 def kernel_trace(fn):

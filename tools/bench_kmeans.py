@@ -50,8 +50,7 @@ def kernel_trace(fn):
             torch.cuda.synchronize()
         out = {}
         for ev in prof.events():
-            if ev.device_time > 0 and ("km_" in ev.name or "xsim" in ev.name or "l2norm" in ev.name or "pack" in ev.name
-                                       or "Memset" in ev.name or "memset" in ev.name):
+            if ev.device_time > 0 and any(s in ev.name for s in ("km_", "bucket_", "xsim", "l2norm", "pack", "Memset", "memset")):
                 name = ev.name.split("(")[0][-48:]
                 out[name] = round(out.get(name, 0.0) + ev.device_time, 2)
         return out or None
