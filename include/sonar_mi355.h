@@ -867,6 +867,44 @@ int smi_ivf_pq_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* 
                       const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* Residual encoding against the list centroid for the IVF-PQ index (restated in
+ * tests/ivf_pq_residual_ref.py): FAISS's `by_residual`.  A row is product-quantised as its difference from the centroid of
+ * its list, so the codewords describe only what the coarse quantiser has not already said.
+ *
+ * centroids: the fp16 normalised centroid table [K, d], 16-byte aligned.  Residual of row i with label l in [0, K):
+ *   r_i[j] = fp16_rn(fp32_rn((float)x_i[j] - (float)c[l][j])), two roundings to nearest even.  A label outside [0, K) addresses
+ *   nothing: the residual is the row itself.  A residual is fp16, a multiple of 2^-24 with |r| <= 2 for normalised operands,
+ *   so the exact int64 training sums of smi_pq_train and their range condition carry over.
+ * Codes, codebooks, decode: those of the plain quantiser applied to r instead of x -- the same key chain, ties, finalise
+ *   rounding and start (codeword c = that subvector of the RESIDUAL of row init[c]).  A row's codes depend on its label.
+ * smi_pq_residuals: out fp16 [n, d] (16-byte aligned) = the residuals of the first n rows of xn, labels int32 [n].  The other
+ *   entries form the same element inside their kernels and keep no n x d temporary; this one is what they are tested against.
+ * smi_pq_encode_residual / smi_pq_train_residual / smi_ivf_pq_build_residual: smi_pq_encode / smi_pq_train /
+ *   smi_ivf_pq_build on the residuals; labels int32 [n] (of the build: the labels it buckets by).  Storage, byte for byte, and
+ *   workspaces are the plain index's: size them with smi_pq_train_workspace_bytes / smi_ivf_pq_build_workspace_bytes.
+ * smi_ivf_pq_search_residual: smi_ivf_pq_search with coarse = device fp32 [nq, nprobe], the score of query q against the
+ *   centroid of the list probes[q][p] names.  score = fl32(acc + coarse[q][p]), acc = smi_ivf_pq_search's score against the
+ *   decoded residual row: one fp32 add is the whole difference.  Total order, (-1, -inf) fill and merge are unchanged; nothing
+ *   is added to an empty entry; a probe entry outside [0, K) names no list and its coarse entry is not read.  Non-finite
+ *   coarse is outside the contract.  Workspace: smi_ivf_pq_search_workspace_bytes.
+ * Refused before any launch: what the plain entries refuse, with the same codes; null labels / coarse, null or misaligned
+ *   centroids / out, K < 1 (SMI_ERR_INVALID_ARG); K above 2^31 - 256 (SMI_ERR_UNSUPPORTED). */
+int smi_pq_residuals(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, const void* centroids_f16, int64_t K,
+                     void* out_f16, void* stream);
+int smi_pq_encode_residual(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, const void* centroids_f16,
+                           int64_t K, int32_t dsub, const void* codebooks_f16, void* codes, void* stream);
+int smi_pq_train_residual(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, const void* centroids_f16,
+                          int64_t K, int32_t dsub, const int32_t* init_rows, int32_t n_iter, void* codebooks_f16,
+                          void* workspace, int64_t workspace_bytes, void* stream);
+int smi_ivf_pq_build_residual(const void* xn_f16, const int32_t* labels, int64_t n, int32_t d, int64_t K,
+                              const void* centroids_f16, int32_t dsub, const void* codebooks_f16, void* list_codes,
+                              int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets, int32_t* list_sizes,
+                              void* workspace, int64_t workspace_bytes, void* stream);
+int smi_ivf_pq_search_residual(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, const float* coarse,
+                               int32_t nprobe, const void* list_codes, int32_t dsub, const void* codebooks_f16,
+                               const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx,
+                               float* score, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

@@ -14,7 +14,9 @@
 // ivf_scan.hpp (read its comment first).  Four kernels here walk lists that way:
 //   ivf_scan_lists_kernel      fp16 rows (3.18): ivf_scan.hpp's functions; fetches both operands from memory;
 //   ivf_pq_scan_lists_kernel   product-quantised rows (3.21): the same functions, so a score has the flat scan's bits BY
-//                              CONSTRUCTION; the list operand is decoded from the codebooks in the fetch;
+//                              CONSTRUCTION; the list operand is decoded from the codebooks in the fetch; its RES
+//                              instantiation (3.22: rows encoded as residuals against their list's centroid) adds one fp32
+//                              per pair, the query's score against that centroid, where a sum meets the fold;
 //   ivf_i8_scan_lists_kernel   int8 codes and one fp32 scale per row (3.19): the integer MFMA, the scales enter in the fold;
 //   ivf_selfjoin_kernel        SemDeDup's per-list self-join (3.20): the unit's rows are list rows, its own fold and ending.
 // The last two spell the same loop out in their own text (keep it equal to ivf_slice_walk's): as instances of the
@@ -756,6 +758,26 @@ int pq_check_codebooks(const void* cb) {
 }
 int pq_shift(int dsub) { return dsub == 8 ? 3 : dsub == 16 ? 4 : dsub == 32 ? 5 : 6; }
 
+// Residual encoding: a row is quantised as its difference from the centroid of its list.  THE residual
+// element, wherever one is formed: fp16_rn(fp32_rn((float)x - (float)c)), two roundings to nearest even (the bits of numpy's
+// (x.astype(f32) - c.astype(f32)).astype(f16)).
+__device__ __forceinline__ f16 pq_residual(f16 x, f16 c) { return (f16)((float)x - (float)c); }
+__device__ __forceinline__ half8 pq_residual8(half8 x, half8 c) {
+  half8 r;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) r[e] = pq_residual(x[e], c[e]);
+  return r;
+}
+// the centroid row a label names, or null: a label outside [0, K) addresses nothing and the residual is the row itself
+__device__ __forceinline__ const f16* pq_centroid_row(const f16* __restrict__ cent, int K, int d, int label) {
+  return (unsigned)label < (unsigned)K ? cent + (size_t)label * d : nullptr;
+}
+// 8 elements at x + k against the same 8 of the centroid row c (null: none)
+__device__ __forceinline__ half8 pq_residual_chunk(const f16* __restrict__ x, const f16* __restrict__ c, int k) {
+  const half8 h = *(const half8*)(x + k);
+  return c ? pq_residual8(h, *(const half8*)(c + k)) : h;
+}
+
 // The key of subvector x against the codeword at cw, the contract's chain: n2 = c_0 c_0 + c_1 c_1 + ... ascending (the
 // product of two fp16 is exact in fp32, so fmaf(c, c, n2) is the rounded add of the header), bias = -0.5 n2 (exact),
 // key = fmaf(x_j, c_j, key) ascending from the bias.  The largest key is the Euclidean nearest codeword.
@@ -783,16 +805,20 @@ __device__ __forceinline__ float pq_key(const half8 (&x)[DSUB / 8], const f16* _
 // THE row encoder, one wave per row (every lane of the wave calls it): codes[0 .. d / DSUB) of the d fp16 at x.  Lane l
 // scores the codewords l, l + 64, l + 128, l + 192 of a sub-quantiser (ascending, a later one must beat the earlier), a
 // butterfly takes the largest key of the wave, ties to the lower code, and leaves it in every lane; lane m % 64 keeps
-// the code of sub-quantiser m and the wave stores 64 consecutive code bytes at a time.
-template <int DSUB>
+// the code of sub-quantiser m and the wave stores 64 consecutive code bytes at a time.  RES: what is encoded is the residual
+// of x against the centroid row c (null: x itself).
+template <int DSUB, bool RES = false>
 __device__ __forceinline__ void pq_encode_row_t(const f16* __restrict__ x, int d, const f16* __restrict__ cb, int lane,
-                                                uint8_t* __restrict__ codes) {
+                                                uint8_t* __restrict__ codes, const f16* __restrict__ c = nullptr) {
   const int M = d / DSUB;
   int mine = 0;
   for (int m = 0; m < M; ++m) {
     half8 xs[DSUB / 8];
 #pragma unroll
-    for (int ch = 0; ch < DSUB / 8; ++ch) xs[ch] = *(const half8*)(x + m * DSUB + ch * 8);
+    for (int ch = 0; ch < DSUB / 8; ++ch) {
+      if constexpr (RES) xs[ch] = pq_residual_chunk(x, c, m * DSUB + ch * 8);
+      else xs[ch] = *(const half8*)(x + m * DSUB + ch * 8);
+    }
     const f16* cm = cb + (size_t)m * PQ_CW * DSUB;
     float best = pq_key<DSUB>(xs, cm + (size_t)lane * DSUB);
     int bc = lane;
@@ -837,6 +863,31 @@ __global__ __launch_bounds__(IVF_TB) void pq_encode_kernel(const f16* __restrict
   if (row >= n) return;  // wave-uniform
   pq_encode_row(xn + (size_t)row * d, d, dsub, cb, threadIdx.x & 63, codes + (size_t)row * (d / dsub));
 }
+// The same on the residual of row `row` against the centroid labels[row] names.  The residual kernels take dsub as a template
+// argument, chosen by the host: behind the in-kernel switch every dsub pays the registers of dsub = 64, and with the centroid's
+// chunks on top of the row's that was 200 VGPRs and one wave per SIMD less than the plain encoder (tools/kernel_resources.py).
+template <int DSUB>
+__global__ __launch_bounds__(IVF_TB) void pq_encode_residual_kernel(const f16* __restrict__ xn, int64_t n, int d,
+                                                                    const f16* __restrict__ cb, uint8_t* __restrict__ codes,
+                                                                    const int32_t* __restrict__ labels,
+                                                                    const f16* __restrict__ cent, int K) {
+  const int64_t row = (int64_t)blockIdx.x * (IVF_TB / 64) + (threadIdx.x >> 6);
+  if (row >= n) return;  // wave-uniform
+  pq_encode_row_t<DSUB, true>(xn + (size_t)row * d, d, cb, threadIdx.x & 63, codes + (size_t)row * (d / DSUB),
+                              pq_centroid_row(cent, K, d, labels[row]));
+}
+
+// out[r] = the residual of row r: one thread per 16 bytes of output
+__global__ __launch_bounds__(IVF_TB) void pq_residuals_kernel(const f16* __restrict__ xn, int64_t n, int d,
+                                                              const int32_t* __restrict__ labels,
+                                                              const f16* __restrict__ cent, int K, f16* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  const int cpr = d / 8;
+  if (t >= n * cpr) return;
+  const int64_t r = t / cpr;
+  const int k0 = (int)(t - r * cpr) * 8;
+  *(half8*)(out + (size_t)t * 8) = pq_residual_chunk(xn + (size_t)r * d, pq_centroid_row(cent, K, d, labels[r]), k0);
+}
 
 // rows[r] = the concatenation of the codewords codes[r] names: one thread per 16 bytes of output
 __global__ __launch_bounds__(IVF_TB) void pq_decode_kernel(const uint8_t* __restrict__ codes, int64_t n, int d, int dsub,
@@ -850,14 +901,24 @@ __global__ __launch_bounds__(IVF_TB) void pq_decode_kernel(const uint8_t* __rest
   *(u32x4*)(rows + (size_t)t * 8) = *(const u32x4*)(cb + ((size_t)m * PQ_CW + code) * dsub + k0 % dsub);
 }
 
-// training, the start: codeword c of every sub-quantiser = that subvector of row init[c].  One thread per 16 bytes.
+// training, the start: codeword c of every sub-quantiser = that subvector of row init[c] (RES: of its residual against the
+// centroid labels[init[c]] names).  One thread per 16 bytes.
+template <bool RES>
 __global__ __launch_bounds__(IVF_TB) void pq_init_kernel(const f16* __restrict__ xn, int d, int dsub,
-                                                         const int32_t* __restrict__ init, f16* __restrict__ cb) {
+                                                         const int32_t* __restrict__ init, f16* __restrict__ cb,
+                                                         const int32_t* __restrict__ labels, const f16* __restrict__ cent,
+                                                         int K) {
   const int t = blockIdx.x * IVF_TB + threadIdx.x;  // < 256 * d / 8
   if (t >= PQ_CW * (d / 8)) return;
   const int cpc = dsub / 8, cw = t / cpc, ch = t - cw * cpc;
   const int m = cw / PQ_CW, c = cw - m * PQ_CW;
-  *(u32x4*)(cb + (size_t)t * 8) = *(const u32x4*)(xn + (size_t)init[c] * d + m * dsub + ch * 8);
+  const int row = init[c];
+  if constexpr (RES) {
+    *(half8*)(cb + (size_t)t * 8) =
+        pq_residual_chunk(xn + (size_t)row * d, pq_centroid_row(cent, K, d, labels[row]), m * dsub + ch * 8);
+  } else {
+    *(u32x4*)(cb + (size_t)t * 8) = *(const u32x4*)(xn + (size_t)row * d + m * dsub + ch * 8);
+  }
 }
 
 // training, the update: block (row block rb, sub-quantiser m) = blockIdx.x adds the subvectors m of its PQ_ROWS rows, as
@@ -866,11 +927,14 @@ __global__ __launch_bounds__(IVF_TB) void pq_init_kernel(const f16* __restrict__
 template <int DSUB>
 constexpr int pq_accumulate_lds() { return PQ_CW * DSUB * 8 + PQ_CW * 4; }
 
-template <int DSUB>
+// RES: what is added is the residual of the row against the centroid its label names.
+template <int DSUB, bool RES>
 __global__ __launch_bounds__(IVF_TB) void pq_accumulate_kernel(const f16* __restrict__ xn, int64_t n, int d,
                                                                const uint8_t* __restrict__ codes,
                                                                unsigned long long* __restrict__ sums,
-                                                               int32_t* __restrict__ counts) {
+                                                               int32_t* __restrict__ counts,
+                                                               const int32_t* __restrict__ labels,
+                                                               const f16* __restrict__ cent, int K) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* ls = (unsigned long long*)smem;
   int* lc = (int*)(smem + PQ_CW * DSUB * 8);
@@ -885,9 +949,16 @@ __global__ __launch_bounds__(IVF_TB) void pq_accumulate_kernel(const f16* __rest
     const int code = codes[(size_t)r * M + m];
     atomicAdd(lc + code, 1);
     const f16* x = xn + (size_t)r * d + m * DSUB;
+    const f16* c = nullptr;
+    if constexpr (RES) {
+      c = pq_centroid_row(cent, K, d, labels[r]);
+      if (c) c += m * DSUB;
+    }
 #pragma unroll
     for (int ch = 0; ch < DSUB / 8; ++ch) {
-      const half8 h = *(const half8*)(x + ch * 8);
+      half8 h;
+      if constexpr (RES) h = pq_residual_chunk(x, c, ch * 8);
+      else h = *(const half8*)(x + ch * 8);
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const long long v = (long long)((float)h[e] * 0x1p24f);  // exact: an fp16 is a multiple of 2^-24 below 2^40
@@ -916,17 +987,25 @@ __global__ __launch_bounds__(IVF_TB) void pq_finalize_kernel(const long long* __
   if (count > 0) cb[t] = (f16)(__fdiv_rn(__ll2float_rn(sums[t]), (float)count) * 0x1p-24f);
 }
 
-// One wave per slot below off[K]: the codes of the row ids[slot] names, or zero codes for a pad slot.
+// One wave per slot below off[K]: the codes of the row ids[slot] names, or zero codes for a pad slot.  RES_DSUB = 0: the plain
+// gather, dsub at run time; RES_DSUB = dsub: the codes of the row's residual against the centroid its label names, which is
+// the centroid of the slot's list.
+template <int RES_DSUB>
 __global__ __launch_bounds__(IVF_TB) void ivf_pq_gather_kernel(const f16* __restrict__ xn, int d, int dsub,
                                                                const f16* __restrict__ cb, const int32_t* __restrict__ ids,
                                                                const int32_t* __restrict__ off, int K,
-                                                               uint8_t* __restrict__ codes) {
+                                                               uint8_t* __restrict__ codes,
+                                                               const int32_t* __restrict__ labels,
+                                                               const f16* __restrict__ cent) {
   const int lane = threadIdx.x & 63, M = d / dsub;
   const int64_t slot = (int64_t)blockIdx.x * (IVF_TB / 64) + (threadIdx.x >> 6);
   if (slot >= off[K]) return;  // wave-uniform
   const int id = ids[slot];
   if (id < 0) {
     for (int m = lane; m < M; m += 64) codes[(size_t)slot * M + m] = 0;
+  } else if constexpr (RES_DSUB != 0) {
+    pq_encode_row_t<RES_DSUB, true>(xn + (size_t)id * d, d, cb, lane, codes + (size_t)slot * M,
+                                    pq_centroid_row(cent, K, d, labels[id]));
   } else {
     pq_encode_row(xn + (size_t)id * d, d, dsub, cb, lane, codes + (size_t)slot * M);
   }
@@ -939,7 +1018,13 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_gather_kernel(const f16* __rest
 // bytes are fetched a slice further ahead than the codewords: `fetch(it)` gathers with the codes an earlier call left in
 // cd and fetches those of slice it + 1.  Slots at or past the end of the list are zero-filled without touching the codes;
 // a pad slot (codes 0) decodes codeword 0 of every sub-quantiser and is skipped by the fold (id -1).
-template <int KT, int B>
+// RES (3.22): the rows are residuals against their list's centroid and a score is fl32(sum + coarse[pair]), coarse fp32
+// [nq][nprobe] = the query's score against that centroid: a pair's value is kept in a float [B] behind the pair numbers in
+// LDS and added where a sum meets the fold.
+template <int B>
+constexpr int ivf_pq_residual_scan_lds(int KT) { return ivf_scan_lds<B>(KT) + B * 4; }
+
+template <int KT, int B, bool RES>
 __global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
                                                                    const uint8_t* __restrict__ codes, int dshift,
                                                                    const f16* __restrict__ cb, const int32_t* __restrict__ ids,
@@ -947,18 +1032,21 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __
                                                                    const int32_t* __restrict__ poff,
                                                                    const int32_t* __restrict__ ubase,
                                                                    const int32_t* __restrict__ pairs, int k_out,
-                                                                   float* __restrict__ ps, int32_t* __restrict__ pi) {
+                                                                   float* __restrict__ ps, int32_t* __restrict__ pi,
+                                                                   const float* __restrict__ coarse) {
   constexpr int NR = B / 32;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   unsigned long long* lists = (unsigned long long*)(smem + 4 * B * IVF_SLICE);
   int* spair = (int*)(lists + B * KT);
+  [[maybe_unused]] float* scoarse = (float*)(spair + B);  // RES only
   const int tid = threadIdx.x, b = blockIdx.x;
   if (b >= ubase[K]) return;
   const int l = ivf_unit_list(ubase, K, b);
   const int p0 = poff[l] + (b - ubase[l]) * B;
   const int npair = min(B, poff[l + 1] - p0);
   const int s_begin = off[l], s_end = off[l + 1];
-  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [](int) {});
+  if constexpr (RES) ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [&](int pr) { scoarse[tid] = pr >= 0 ? coarse[pr] : 0.f; });
+  else ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [](int) {});
 
   const int nk = d / IVF_BK, cc = tid & 7;
   const int T = (s_end - s_begin + B - 1) / B * nk;  // the slices of the walk
@@ -993,7 +1081,14 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __
     if (it + 1 < T) fetch_codes(it + 1);
   };
   auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
-    ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, IvfSumIsScore{});
+    if constexpr (RES) {
+      ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, [scoarse](int pr) {
+        const float c = scoarse[pr];
+        return [c](float a, int) { return a + c; };
+      });
+    } else {
+      ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, IvfSumIsScore{});
+    }
   };
   ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
   ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
@@ -1018,11 +1113,134 @@ bool pq_train_shape_ok(int64_t n, int32_t d, int32_t dsub) {
   return pq_rows_ok(n, d, dsub) && (int64_t)PQ_CW * d <= IVF_MAX && pq_update_blocks(n, d, dsub) <= IVF_MAX;
 }
 
-template <int DSUB>
+template <int DSUB, bool RES>
 hipError_t launch_pq_accumulate(int64_t blocks, hipStream_t st, const f16* xn, int64_t n, int d, const uint8_t* codes,
-                                unsigned long long* sums, int32_t* counts) {
-  return launch_with_lds<pq_accumulate_kernel<DSUB>>(dim3((unsigned)blocks), IVF_TB, pq_accumulate_lds<DSUB>(), st, xn, n, d,
-                                                     codes, sums, counts);
+                                unsigned long long* sums, int32_t* counts, const int32_t* labels, const f16* cent, int K) {
+  return launch_with_lds<pq_accumulate_kernel<DSUB, RES>>(dim3((unsigned)blocks), IVF_TB, pq_accumulate_lds<DSUB>(), st, xn, n,
+                                                          d, codes, sums, counts, labels, cent, K);
+}
+
+// launch(dsub as a std::integral_constant): the residual kernels that take dsub at compile time
+template <class Launch>
+void with_dsub(int dsub, Launch launch) {
+  if (dsub == 8) launch(std::integral_constant<int, 8>{});
+  else if (dsub == 16) launch(std::integral_constant<int, 16>{});
+  else if (dsub == 32) launch(std::integral_constant<int, 32>{});
+  else launch(std::integral_constant<int, 64>{});
+}
+void launch_pq_encode_residual(const f16* xn, int64_t n, int d, int dsub, const f16* cb, uint8_t* codes, const int32_t* labels,
+                               const f16* cent, int K, hipStream_t st) {
+  with_dsub(dsub, [&](auto ds) {
+    hipLaunchKernelGGL(pq_encode_residual_kernel<decltype(ds)::value>, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, st, xn, n, d, cb,
+                       codes, labels, cent, K);
+  });
+}
+
+int pq_check_centroids(const void* centroids, int64_t K) {
+  if (!centroids) return fail(SMI_ERR_INVALID_ARG, "null centroids");
+  if ((uintptr_t)centroids % 16) return fail(SMI_ERR_INVALID_ARG, "centroids must be 16-byte aligned");
+  if (K < 1) return fail(SMI_ERR_INVALID_ARG, "K=%lld: at least one list", (long long)K);
+  if (K > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "K=%lld: list numbers must fit int32", (long long)K);
+  return SMI_OK;
+}
+
+// The entries of the plain (3.21) and the residual (3.22) product quantiser, stated once: the refusals of the plain entry, in
+// its order, then those of what RES adds (labels, the centroids cent fp16 [K, d], coarse), then the launches.
+template <bool RES>
+int pq_train_entry(const void* xn, const int32_t* labels, int64_t n, int32_t d, const void* cent, int64_t K, int32_t dsub,
+                   const int32_t* init, int32_t n_iter, void* codebooks, void* ws, int64_t ws_bytes, void* stream) {
+  if (!xn || !init || (RES && !labels)) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  if constexpr (RES)
+    if (const int rc = pq_check_centroids(cent, K)) return rc;
+  if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d must not be negative", n_iter);
+  if ((int64_t)PQ_CW * d > IVF_MAX || pq_update_blocks(n, d, dsub) > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "n=%lld, d=%d: the codebook elements and the update's blocks must fit int32", (long long)n, d);
+  const PqTrainWs w(ws, n, d, dsub);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_pq_train_workspace_bytes(n, d, dsub)")) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const int M = d / dsub;
+  const dim3 block(IVF_TB);
+  hipLaunchKernelGGL(pq_init_kernel<RES>, grid_for((int64_t)PQ_CW * (d / 8), IVF_TB), block, 0, st, (const f16*)xn, d, dsub, init,
+                     (f16*)codebooks, labels, (const f16*)cent, (int)K);
+  HIP_TRY(hipGetLastError());
+  const int64_t blocks = pq_update_blocks(n, d, dsub);
+  auto accumulate = dsub == 8 ? launch_pq_accumulate<8, RES> : dsub == 16 ? launch_pq_accumulate<16, RES>
+                  : dsub == 32 ? launch_pq_accumulate<32, RES> : launch_pq_accumulate<64, RES>;
+  for (int it = 0; it < n_iter; ++it) {
+    if constexpr (RES)
+      launch_pq_encode_residual((const f16*)xn, n, d, dsub, (const f16*)codebooks, w.codes, labels, (const f16*)cent, (int)K, st);
+    else
+      hipLaunchKernelGGL(pq_encode_kernel, grid_for(n, IVF_TB / 64), block, 0, st, (const f16*)xn, n, d, dsub,
+                         (const f16*)codebooks, w.codes);
+    HIP_TRY(hipMemsetAsync(w.sums, 0, (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * M * 4, st));  // the sums and the counts behind
+    HIP_TRY(accumulate(blocks, st, (const f16*)xn, n, d, w.codes, w.sums, w.counts, labels, (const f16*)cent, (int)K));
+    hipLaunchKernelGGL(pq_finalize_kernel, grid_for((int64_t)PQ_CW * d, IVF_TB), block, 0, st, (const long long*)w.sums,
+                       w.counts, d, dsub, (f16*)codebooks);
+    HIP_TRY(hipGetLastError());
+  }
+  return SMI_OK;
+}
+
+template <bool RES>
+int pq_build_entry(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, const void* cent, int32_t dsub,
+                   const void* codebooks, void* list_codes, int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets,
+                   int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
+  if (!xn || !labels || !list_codes || !list_ids || !list_offsets || !list_sizes)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_pq_build_workspace_bytes(n, K, d, dsub)"))
+    return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  if constexpr (RES)
+    if (const int rc = pq_check_centroids(cent, K)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
+  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
+  const dim3 grid = grid_for(slots_bound(n, K), IVF_TB / 64);
+  auto gather = [&](auto ds) {
+    hipLaunchKernelGGL(ivf_pq_gather_kernel<decltype(ds)::value>, grid, dim3(IVF_TB), 0, st, (const f16*)xn, d, dsub,
+                       (const f16*)codebooks, (const int32_t*)list_ids, (const int32_t*)list_offsets, (int)K, (uint8_t*)list_codes,
+                       labels, (const f16*)cent);
+  };
+  if constexpr (RES) with_dsub(dsub, gather);
+  else gather(std::integral_constant<int, 0>{});
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+template <bool RES>
+int pq_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes, const float* coarse, int32_t nprobe,
+                    const void* list_codes, int32_t dsub, const void* codebooks, const int32_t* list_ids,
+                    const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
+                    void* stream) {
+  if (!qn || !probes || !list_codes || !list_ids || !list_offsets || !idx || !score || (RES && !coarse))
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
+  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  const int64_t P = nq * nprobe;
+  const SearchWs w(ws, nq, K, nprobe, k);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)")) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const int unit = unit_pairs(P, K);  // the flat search's rule: the image and the MFMA work of a unit are the same
+  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
+  const int64_t units = units_bound(P, K, unit);
+  HIP_TRY(with_key_list(k, [&](auto kt) {
+    constexpr int KT = decltype(kt)::value;
+    constexpr int lds_small = RES ? ivf_pq_residual_scan_lds<IVF_BM>(KT) : ivf_scan_lds<IVF_BM>(KT);
+    constexpr int lds_big = RES ? ivf_pq_residual_scan_lds<IVF_BIG>(KT) : ivf_scan_lds<IVF_BIG>(KT);
+    return launch_units<ivf_pq_scan_lists_kernel<KT, IVF_BM, RES>, ivf_pq_scan_lists_kernel<KT, IVF_BIG, RES>>(
+        unit, units, lds_small, lds_big, st, (const f16*)qn, d, (int)nq, nprobe, (const uint8_t*)list_codes, pq_shift(dsub),
+        (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi, coarse);
+  }));
+  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  return SMI_OK;
 }
 
 }  // namespace
@@ -1225,35 +1443,7 @@ int64_t smi_pq_train_workspace_bytes(int64_t n, int32_t d, int32_t dsub) {
 
 int smi_pq_train(const void* xn, int64_t n, int32_t d, int32_t dsub, const int32_t* init, int32_t n_iter, void* codebooks,
                  void* ws, int64_t ws_bytes, void* stream) {
-  if (!xn || !init) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d must not be negative", n_iter);
-  if ((int64_t)PQ_CW * d > IVF_MAX || pq_update_blocks(n, d, dsub) > IVF_MAX)
-    return fail(SMI_ERR_UNSUPPORTED, "n=%lld, d=%d: the codebook elements and the update's blocks must fit int32", (long long)n, d);
-  const PqTrainWs w(ws, n, d, dsub);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_pq_train_workspace_bytes(n, d, dsub)")) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  const int M = d / dsub;
-  const dim3 block(IVF_TB);
-  hipLaunchKernelGGL(pq_init_kernel, grid_for((int64_t)PQ_CW * (d / 8), IVF_TB), block, 0, st, (const f16*)xn, d, dsub, init,
-                     (f16*)codebooks);
-  HIP_TRY(hipGetLastError());
-  const int64_t blocks = pq_update_blocks(n, d, dsub);
-  auto accumulate = dsub == 8 ? launch_pq_accumulate<8> : dsub == 16 ? launch_pq_accumulate<16>
-                  : dsub == 32 ? launch_pq_accumulate<32> : launch_pq_accumulate<64>;
-  for (int it = 0; it < n_iter; ++it) {
-    hipLaunchKernelGGL(pq_encode_kernel, grid_for(n, IVF_TB / 64), block, 0, st, (const f16*)xn, n, d, dsub,
-                       (const f16*)codebooks, w.codes);
-    HIP_TRY(hipMemsetAsync(w.sums, 0, (size_t)PQ_CW * d * 8 + (size_t)PQ_CW * M * 4, st));  // the sums and the counts behind
-    HIP_TRY(accumulate(blocks, st, (const f16*)xn, n, d, w.codes, w.sums, w.counts));
-    hipLaunchKernelGGL(pq_finalize_kernel, grid_for((int64_t)PQ_CW * d, IVF_TB), block, 0, st, (const long long*)w.sums,
-                       w.counts, d, dsub, (f16*)codebooks);
-    HIP_TRY(hipGetLastError());
-  }
-  return SMI_OK;
+  return pq_train_entry<false>(xn, nullptr, n, d, nullptr, 0, dsub, init, n_iter, codebooks, ws, ws_bytes, stream);
 }
 
 int64_t smi_ivf_pq_build_workspace_bytes(int64_t n, int64_t K, int32_t d, int32_t dsub) {
@@ -1263,20 +1453,8 @@ int64_t smi_ivf_pq_build_workspace_bytes(int64_t n, int64_t K, int32_t d, int32_
 int smi_ivf_pq_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, int32_t dsub,
                      const void* codebooks, void* list_codes, int32_t* list_ids, int64_t capacity_slots,
                      int32_t* list_offsets, int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
-  if (!xn || !labels || !list_codes || !list_ids || !list_offsets || !list_sizes)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_pq_build_workspace_bytes(n, K, d, dsub)"))
-    return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
-  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
-  hipLaunchKernelGGL(ivf_pq_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d, dsub,
-                     (const f16*)codebooks, list_ids, list_offsets, (int)K, (uint8_t*)list_codes);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return pq_build_entry<false>(xn, labels, n, d, K, nullptr, dsub, codebooks, list_codes, list_ids, capacity_slots, list_offsets,
+                               list_sizes, ws, ws_bytes, stream);
 }
 
 int64_t smi_ivf_pq_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d, int32_t dsub) {
@@ -1286,28 +1464,57 @@ int64_t smi_ivf_pq_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe,
 int smi_ivf_pq_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
                       int32_t dsub, const void* codebooks, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
                       int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
-  if (!qn || !probes || !list_codes || !list_ids || !list_offsets || !idx || !score)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
+  return pq_search_entry<false>(qn, nq, d, probes, nullptr, nprobe, list_codes, dsub, codebooks, list_ids, list_offsets, K, k, idx,
+                                score, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- residual encoding against the list centroid (3.22)
+int smi_pq_residuals(const void* xn, const int32_t* labels, int64_t n, int32_t d, const void* centroids, int64_t K, void* out,
+                     void* stream) {
+  if (!xn || !labels || !out) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if ((uintptr_t)out % 16) return fail(SMI_ERR_INVALID_ARG, "out must be 16-byte aligned");
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
+  if (const int rc = pq_check_centroids(centroids, K)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipLaunchKernelGGL(pq_residuals_kernel, grid_for(n * (d / 8), IVF_TB), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d,
+                     labels, (const f16*)centroids, (int)K, (f16*)out);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int smi_pq_encode_residual(const void* xn, const int32_t* labels, int64_t n, int32_t d, const void* centroids, int64_t K,
+                           int32_t dsub, const void* codebooks, void* codes, void* stream) {
+  if (!xn || !labels || !codes) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
   if (const int rc = pq_check_dsub(d, dsub)) return rc;
   if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  const int64_t P = nq * nprobe;
-  const SearchWs w(ws, nq, K, nprobe, k);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)")) return rc;
+  if (const int rc = pq_check_centroids(centroids, K)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  const int unit = unit_pairs(P, K);  // the flat search's rule: the image and the MFMA work of a unit are the same
-  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
-  const int64_t units = units_bound(P, K, unit);
-  HIP_TRY(with_key_list(k, [&](auto kt) {
-    constexpr int KT = decltype(kt)::value;
-    return launch_units<ivf_pq_scan_lists_kernel<KT, IVF_BM>, ivf_pq_scan_lists_kernel<KT, IVF_BIG>>(
-        unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
-        (const uint8_t*)list_codes, pq_shift(dsub), (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase,
-        w.pairs, k, w.ps, w.pi);
-  }));
-  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  launch_pq_encode_residual((const f16*)xn, n, d, dsub, (const f16*)codebooks, (uint8_t*)codes, labels, (const f16*)centroids, (int)K,
+                            (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
   return SMI_OK;
+}
+
+int smi_pq_train_residual(const void* xn, const int32_t* labels, int64_t n, int32_t d, const void* centroids, int64_t K,
+                          int32_t dsub, const int32_t* init, int32_t n_iter, void* codebooks, void* ws, int64_t ws_bytes,
+                          void* stream) {
+  return pq_train_entry<true>(xn, labels, n, d, centroids, K, dsub, init, n_iter, codebooks, ws, ws_bytes, stream);
+}
+
+int smi_ivf_pq_build_residual(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, const void* centroids,
+                              int32_t dsub, const void* codebooks, void* list_codes, int32_t* list_ids, int64_t capacity_slots,
+                              int32_t* list_offsets, int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
+  return pq_build_entry<true>(xn, labels, n, d, K, centroids, dsub, codebooks, list_codes, list_ids, capacity_slots, list_offsets,
+                              list_sizes, ws, ws_bytes, stream);
+}
+
+int smi_ivf_pq_search_residual(const void* qn, int64_t nq, int32_t d, const int32_t* probes, const float* coarse, int32_t nprobe,
+                               const void* list_codes, int32_t dsub, const void* codebooks, const int32_t* list_ids,
+                               const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws,
+                               int64_t ws_bytes, void* stream) {
+  return pq_search_entry<true>(qn, nq, d, probes, coarse, nprobe, list_codes, dsub, codebooks, list_ids, list_offsets, K, k, idx,
+                               score, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,5 @@
-"""IVF indexes over sentence embeddings on the MI355X engine: flat fp16 lists and int8 scalar-quantised
-lists.
+"""IVF indexes over sentence embeddings on the MI355X engine: flat fp16 lists, int8 scalar-quantised
+lists and product-quantised lists, plain or of residuals.
 
 Brute-force `xsim.topk` scores every query against every row.  An inverted-file index scores a query against the rows of the
 `nprobe` nearest of K clusters only, about nprobe / K of the work, which is what repeated search of one corpus (LASER-style
@@ -27,9 +27,13 @@ tile's codes into the flat scan's fp16 image once per tile, so a raw score is bi
 reconstructed row (tests/ivf_pq_ref.py); `search(..., refine=xn)` re-scores the candidates like the int8 index.  The quality
 was measured on synthetic planted data only, whose noise is isotropic and does not compress; real SONAR rows are unmeasured.
 
-Not here: residual encoding against the list centroid, an OPQ rotation, a look-up-table scan for a handful of
-queries, codes of fewer than 8 bits, nprobe or k above 8, de-duplication over quantised lists, incremental add and removal,
-64-bit ids, splitting of long lists, multi-GPU sharding.
+`IVFPQResidualIndex` is `IVFPQIndex` with every row encoded as its residual against the centroid of its list (DESIGN.md 3.22,
+FAISS's `by_residual`): the same bytes, a lower quantisation error, and one fp32 add per score -- the query's score against
+the list's centroid, which the probe has already computed (tests/ivf_pq_residual_ref.py).
+
+Not here: an OPQ rotation, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, nprobe or
+k above 8, de-duplication over quantised lists, incremental add and removal, 64-bit ids, splitting of long lists, multi-GPU
+sharding.
 """
 from __future__ import annotations
 
@@ -249,11 +253,8 @@ def _check_rows16(xn, name: str, n) -> int:
     return n
 
 
-def pq_train(xn: torch.Tensor, dsub: int, init: torch.Tensor, n_iter: int = 10, n: Optional[int] = None) -> torch.Tensor:
-    """smi_pq_train: codebooks fp16 [d / dsub, 256, dsub] after n_iter Lloyd rounds on the first n rows (default: all) of xn
-    (contiguous fp16 [>= n, d], rows of `normalize_rows`), started from the subvectors of the rows init names (device int32
-    [256], values in [0, n): not checked here).  No read-back; one init gives one result bit for bit."""
-    n = _check_rows16(xn, "xn", n)
+def _pq_train(xn, n: int, dsub, init, n_iter, residual=None) -> torch.Tensor:
+    """smi_pq_train on the first n rows of xn, or smi_pq_train_residual with residual = (labels, centroids, K)."""
     d = xn.shape[1]
     _check_dsub(dsub, d)
     if isinstance(n_iter, bool) or not isinstance(n_iter, int) or n_iter < 0:
@@ -266,10 +267,21 @@ def pq_train(xn: torch.Tensor, dsub: int, init: torch.Tensor, n_iter: int = 10, 
     codebooks = torch.empty((d // dsub, PQ_CODEWORDS, dsub), dtype=torch.float16, device=xn.device)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xn.device)
     init = init.contiguous()
+    tail = (dsub, init.data_ptr(), n_iter, codebooks.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr())
     with torch.cuda.device(xn.device):
-        _lib.check(lib.smi_pq_train(xn.data_ptr(), n, d, dsub, init.data_ptr(), n_iter, codebooks.data_ptr(), ws.data_ptr(),
-                                    ws_bytes, _lib.current_stream_ptr()))
+        if residual is None:
+            _lib.check(lib.smi_pq_train(xn.data_ptr(), n, d, *tail))
+        else:
+            labels, centroids, k = residual
+            _lib.check(lib.smi_pq_train_residual(xn.data_ptr(), labels.data_ptr(), n, d, centroids.data_ptr(), k, *tail))
     return codebooks
+
+
+def pq_train(xn: torch.Tensor, dsub: int, init: torch.Tensor, n_iter: int = 10, n: Optional[int] = None) -> torch.Tensor:
+    """smi_pq_train: codebooks fp16 [d / dsub, 256, dsub] after n_iter Lloyd rounds on the first n rows (default: all) of xn
+    (contiguous fp16 [>= n, d], rows of `normalize_rows`), started from the subvectors of the rows init names (device int32
+    [256], values in [0, n): not checked here).  No read-back; one init gives one result bit for bit."""
+    return _pq_train(xn, _check_rows16(xn, "xn", n), dsub, init, n_iter)
 
 
 def pq_encode(xn: torch.Tensor, codebooks: torch.Tensor, n: Optional[int] = None) -> torch.Tensor:
@@ -298,10 +310,8 @@ def pq_decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
     return rows
 
 
-def build_lists_pq(xn: torch.Tensor, labels: torch.Tensor, n_lists: int, codebooks: torch.Tensor):
-    """smi_ivf_pq_build: `build_lists` with every row encoded against codebooks (fp16 [M, 256, dsub]).  Returns (codes uint8
-    [slots, M], ids, offsets, sizes); a pad slot has zero codes and id -1."""
-    _check_build_args(xn, labels, n_lists)
+def _build_pq(xn, labels, n_lists: int, codebooks, centroids=None):
+    """smi_ivf_pq_build, or smi_ivf_pq_build_residual against centroids (fp16 [n_lists, d])."""
     m, dsub = _check_codebooks(codebooks, xn.shape[1])
     lib = _lib.load()
     n, d, dev = labels.shape[0], xn.shape[1], xn.device
@@ -315,18 +325,36 @@ def build_lists_pq(xn: torch.Tensor, labels: torch.Tensor, n_lists: int, codeboo
     ws_bytes = int(lib.smi_ivf_pq_build_workspace_bytes(n, n_lists, d, dsub))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     labels = labels.contiguous()
+    entry, cent = (lib.smi_ivf_pq_build, ()) if centroids is None else (lib.smi_ivf_pq_build_residual, (centroids.data_ptr(),))
     with torch.cuda.device(dev):
-        _lib.check(lib.smi_ivf_pq_build(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, dsub, codebooks.data_ptr(),
-                                        codes.data_ptr(), ids.data_ptr(), cap, offsets.data_ptr(), sizes.data_ptr(),
-                                        ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+        _lib.check(entry(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, *cent, dsub, codebooks.data_ptr(), codes.data_ptr(),
+                         ids.data_ptr(), cap, offsets.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws_bytes,
+                         _lib.current_stream_ptr()))
     return codes, ids, offsets, sizes
 
 
-def search_lists_pq(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, codebooks: torch.Tensor, ids: torch.Tensor,
-                    offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
-    """smi_ivf_pq_search: `search_lists` against the storage `build_lists_pq` returned.  A score has the bits `search_lists`
-    returns for the query against `pq_decode` of the row."""
+def build_lists_pq(xn: torch.Tensor, labels: torch.Tensor, n_lists: int, codebooks: torch.Tensor):
+    """smi_ivf_pq_build: `build_lists` with every row encoded against codebooks (fp16 [M, 256, dsub]).  Returns (codes uint8
+    [slots, M], ids, offsets, sizes); a pad slot has zero codes and id -1."""
+    _check_build_args(xn, labels, n_lists)
+    return _build_pq(xn, labels, n_lists, codebooks)
+
+
+def _check_coarse(coarse, shape) -> None:
+    """The coarse term of a residual search: device fp32 of the probe table's shape."""
+    if not isinstance(coarse, torch.Tensor):
+        raise TypeError("coarse must be a torch.Tensor")
+    if not coarse.is_cuda:
+        raise RuntimeError("coarse: the index runs on a HIP device only (no CPU path)")
+    if coarse.dtype != torch.float32 or tuple(coarse.shape) != tuple(shape):
+        raise ValueError(f"coarse must be fp32 {list(shape)}, got {coarse.dtype} {list(coarse.shape)}")
+
+
+def _search_pq(qn, probes, codes, codebooks, ids, offsets, k: int, coarse=None):
+    """smi_ivf_pq_search, or smi_ivf_pq_search_residual with coarse (fp32, the shape of probes)."""
     _check_search_args(qn, probes, k)
+    if coarse is not None:
+        _check_coarse(coarse, probes.shape)
     m, dsub = _check_codebooks(codebooks, qn.shape[1])
     _check_codes(codes, "codes", m)
     lib = _lib.load()
@@ -336,11 +364,92 @@ def search_lists_pq(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor,
     idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
     score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
     probes = probes.contiguous()
+    entry, extra = lib.smi_ivf_pq_search, ()
+    if coarse is not None:
+        coarse = coarse.contiguous()
+        entry, extra = lib.smi_ivf_pq_search_residual, (coarse.data_ptr(),)
     with torch.cuda.device(qn.device):
-        _lib.check(lib.smi_ivf_pq_search(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, codes.data_ptr(), dsub,
-                                         codebooks.data_ptr(), ids.data_ptr(), offsets.data_ptr(), n_lists, k, idx.data_ptr(),
-                                         score.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+        _lib.check(entry(qn.data_ptr(), nq, d, probes.data_ptr(), *extra, nprobe, codes.data_ptr(), dsub, codebooks.data_ptr(),
+                         ids.data_ptr(), offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(),
+                         ws_bytes, _lib.current_stream_ptr()))
     return score, idx
+
+
+def search_lists_pq(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, codebooks: torch.Tensor, ids: torch.Tensor,
+                    offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_pq_search: `search_lists` against the storage `build_lists_pq` returned.  A score has the bits `search_lists`
+    returns for the query against `pq_decode` of the row."""
+    return _search_pq(qn, probes, codes, codebooks, ids, offsets, k)
+
+
+def _check_centroids(centroids, d: int) -> int:
+    """K of the fp16 centroid table [>= K, d] a residual function is given: K = its rows."""
+    _check_matrix(centroids, "centroids")
+    if centroids.dtype != torch.float16 or not centroids.is_contiguous() or centroids.shape[1] != d:
+        raise ValueError(f"centroids must be a contiguous fp16 [K, {d}] matrix, got {centroids.dtype} {list(centroids.shape)}")
+    return centroids.shape[0]
+
+
+def _check_residual_args(xn, labels, centroids) -> Tuple[int, int]:
+    """(n, K): the rows labels covers and the rows of centroids."""
+    _check_matrix(xn, "xn")
+    k = _check_centroids(centroids, xn.shape[1])
+    _check_build_args(xn, labels, k)
+    return labels.shape[0], k
+
+
+def pq_residuals(xn: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """smi_pq_residuals: fp16 [n, d], row i = fp16(fp32(xn[i]) - fp32(centroids[labels[i]])) for the first n = len(labels) rows of
+    xn (contiguous fp16 [>= n, d]); labels device int32 [n], centroids contiguous fp16 [K, d].  A label outside [0, K) leaves
+    the row as it is.  The other residual functions form these elements inside their kernels."""
+    n, k = _check_residual_args(xn, labels, centroids)
+    lib = _lib.load()
+    out = torch.empty((n, xn.shape[1]), dtype=torch.float16, device=xn.device)
+    labels = labels.contiguous()
+    with torch.cuda.device(xn.device):
+        _lib.check(lib.smi_pq_residuals(xn.data_ptr(), labels.data_ptr(), n, xn.shape[1], centroids.data_ptr(), k,
+                                        out.data_ptr(), _lib.current_stream_ptr()))
+    return out
+
+
+def pq_encode_residual(xn: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
+    """smi_pq_encode_residual: `pq_encode(pq_residuals(xn, labels, centroids), codebooks)` without the residual matrix."""
+    n, k = _check_residual_args(xn, labels, centroids)
+    m, dsub = _check_codebooks(codebooks, xn.shape[1])
+    lib = _lib.load()
+    codes = torch.empty((n, m), dtype=torch.uint8, device=xn.device)
+    labels = labels.contiguous()
+    with torch.cuda.device(xn.device):
+        _lib.check(lib.smi_pq_encode_residual(xn.data_ptr(), labels.data_ptr(), n, xn.shape[1], centroids.data_ptr(), k, dsub,
+                                              codebooks.data_ptr(), codes.data_ptr(), _lib.current_stream_ptr()))
+    return codes
+
+
+def pq_train_residual(xn: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor, dsub: int, init: torch.Tensor,
+                      n_iter: int = 10) -> torch.Tensor:
+    """smi_pq_train_residual: `pq_train(pq_residuals(xn, labels, centroids), dsub, init, n_iter)` without the residual
+    matrix: the codebooks start from the residuals of the rows init names."""
+    n, k = _check_residual_args(xn, labels, centroids)
+    return _pq_train(xn, n, dsub, init, n_iter, (labels.contiguous(), centroids, k))
+
+
+def build_lists_pq_residual(xn: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor, codebooks: torch.Tensor):
+    """smi_ivf_pq_build_residual: `build_lists_pq` over the n_lists = len(centroids) lists with every row encoded as its
+    residual against the centroid of its list.  Returns (codes uint8 [slots, M], ids, offsets, sizes): `build_lists_pq`'s
+    storage, byte for byte."""
+    _, n_lists = _check_residual_args(xn, labels, centroids)
+    return _build_pq(xn, labels, n_lists, codebooks, centroids)
+
+
+def search_lists_pq_residual(qn: torch.Tensor, probes: torch.Tensor, coarse: torch.Tensor, codes: torch.Tensor,
+                             codebooks: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
+                             k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_pq_search_residual: `search_lists_pq` against the storage `build_lists_pq_residual` returned, with
+    coarse (device fp32 [nq, nprobe]: the score of query q against the centroid of the list probes[q, p]) added to every score
+    of that pair in fp32.  The entry of a probe that names no list is not read."""
+    if coarse is None:
+        raise TypeError("coarse must be a torch.Tensor")
+    return _search_pq(qn, probes, codes, codebooks, ids, offsets, k, coarse)
 
 
 class ProductQuantizer:
@@ -407,6 +516,14 @@ class ProductQuantizer:
         if "codebooks" not in state:
             raise ValueError("state lacks ['codebooks']")
         return cls(state["codebooks"])
+
+
+def _check_refine(refine, d: int) -> None:
+    """`refine` of a quantised index's search: None, or the normalised fp16 corpus."""
+    if refine is not None:
+        _check_matrix(refine, "refine")
+        if refine.dtype != torch.float16 or not refine.is_contiguous() or refine.shape[1] != d:
+            raise ValueError(f"refine must be the contiguous fp16 [rows, {d}] matrix normalize_rows returned")
 
 
 class _IVFIndex:
@@ -514,6 +631,14 @@ class _IVFIndex:
 
     def _checked_search(self, q, k, nprobe, probes):
         """The argument checks of `search`; returns (scores, ids, qn) of the subclass's scan."""
+        nq = self._check_search(q, k, nprobe, probes)
+        qn = normalize_rows(q)
+        if probes is None:
+            probes = self._probe(qn, nq, nprobe)
+        return (*self._search_lists(qn, probes, k), qn)
+
+    def _check_search(self, q, k, nprobe, probes) -> int:
+        """The argument checks of `search`; returns nq."""
         _check_small(k, "k")
         _check_small(nprobe, "nprobe")
         self._need_add("search")
@@ -527,10 +652,7 @@ class _IVFIndex:
             _check_table(probes, "probes", nq, probes.shape[1] if isinstance(probes, torch.Tensor) else 1)
         elif nprobe > self._k:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
-        qn = normalize_rows(q)
-        if probes is None:
-            probes = self._probe(qn, nq, nprobe)
-        return (*self._search_lists(qn, probes, k), qn)
+        return nq
 
     # ------------------------------------------------------------------------------------------------ persistence
     def state_dict(self) -> Dict[str, torch.Tensor]:
@@ -651,10 +773,7 @@ class IVFInt8Index(_IVFIndex):
         refine: None, or the normalised fp16 corpus the index was built from (`normalize_rows(x)`, row number = id).  The k
         candidates of every query are then re-scored with their fp16 cosines (`mining.pair_scores`, cosine mode) and each
         row is re-ordered into the same total order; (-inf, -1) entries stay what they are.  No host synchronisation."""
-        if refine is not None:
-            _check_matrix(refine, "refine")
-            if refine.dtype != torch.float16 or not refine.is_contiguous() or refine.shape[1] != self._d:
-                raise ValueError(f"refine must be the contiguous fp16 [rows, {self._d}] matrix normalize_rows returned")
+        _check_refine(refine, self._d)
         score, idx, qn = self._checked_search(q, k, nprobe, probes)
         if refine is None:
             return score, idx
@@ -705,7 +824,13 @@ class IVFPQIndex(_IVFIndex):
     def _search_lists(self, qn, probes, k):
         return search_lists_pq(qn, probes, self._rows, self._codebooks, self._ids, self._offsets, k)
 
+    _BY_RESIDUAL = False  # the codes are of the rows themselves; `IVFPQResidualIndex`: of their residuals
+
     def _check_extra(self, state, d: int, fresh: bool):
+        if ("by_residual" in state) != self._BY_RESIDUAL:
+            raise ValueError("the state is that of an IVFPQResidualIndex: its codes are residuals against the list centroids"
+                             if "by_residual" in state else
+                             "state lacks ['by_residual']: the state is that of a plain IVFPQIndex")
         codebooks = state["codebooks"]
         m, _ = _check_codebooks(codebooks, d)
         return m, {"_codebooks": codebooks.clone()}
@@ -714,10 +839,7 @@ class IVFPQIndex(_IVFIndex):
                refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """`IVFFlatIndex.search` on the reconstructed rows.  refine: as for `IVFInt8Index.search`, the normalised fp16 corpus
         the index was built from; the k candidates are re-scored with their fp16 cosines and re-ordered."""
-        if refine is not None:
-            _check_matrix(refine, "refine")
-            if refine.dtype != torch.float16 or not refine.is_contiguous() or refine.shape[1] != self._d:
-                raise ValueError(f"refine must be the contiguous fp16 [rows, {self._d}] matrix normalize_rows returned")
+        _check_refine(refine, self._d)
         score, idx, qn = self._checked_search(q, k, nprobe, probes)
         if refine is None:
             return score, idx
@@ -725,6 +847,78 @@ class IVFPQIndex(_IVFIndex):
 
     def self_join(self, *args, **kwargs):
         raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFPQIndex holds product-quantiser codes")
+
+
+class IVFPQResidualIndex(IVFPQIndex):
+    """`IVFPQIndex` with every row encoded as its residual against the centroid of its list (FAISS's
+    `by_residual`): the same storage, byte for byte, and the codewords describe only what the coarse quantiser has not
+    already said.  A raw score is fl32(the plain scan's score against the decoded residual + the query's score against the
+    list's centroid), the second term one fp32 per (query, probed list).  `state_dict` adds the marker `by_residual`, so that
+    neither class loads the other's state.
+
+    The codes hang on the bits of the centroids: a tensor given as `quantizer` is normalised (once more, if it already was),
+    so a second index over the same lists is built from the fitted `SphericalKMeans` or from a state dict."""
+
+    _BY_RESIDUAL = True
+
+    @classmethod
+    def train(cls, x: torch.Tensor, n_lists: int, dsub: int = 16, n_iter: int = 10, pq_iter: int = 8, seed: int = 0):
+        """Fit the coarse quantiser (spherical k-means, `n_lists` clusters, n_iter rounds), label the rows with their nearest
+        centroid as `add` will, and fit the product quantiser on the residuals (dsub dimensions per sub-quantiser, pq_iter
+        Lloyd rounds, started from the residuals of `clustering.init_rows(n, 256, seed)`); x fp16 / fp32 [n, d] on the
+        device, n >= 256."""
+        _check_matrix(x, "x")
+        n, d = x.shape
+        _check_dsub(dsub, d)
+        init = init_rows(n, PQ_CODEWORDS, seed)
+        km = SphericalKMeans(n_lists, n_iter=n_iter, seed=seed).fit(x)
+        c16 = km._c16[:n_lists]
+        xn = normalize_rows(x)
+        labels = topk_normalized(xn, n, km._c16, n_lists, 1)[1][:, 0].contiguous()
+        return cls(km, pq_train_residual(xn, labels, c16, dsub, init.to(device=x.device, dtype=torch.int32), pq_iter))
+
+    def _build_lists(self, xn, labels):
+        return build_lists_pq_residual(xn, labels, self._c16[: self._k], self._codebooks)
+
+    def coarse_scores(self, qn: torch.Tensor, nq: int, probes: torch.Tensor) -> torch.Tensor:
+        """fp32 [nq, nprobe]: the cosines of the first nq rows of qn (`normalize_rows`) against the centroids probes names,
+        by `mining.pair_scores` in cosine mode; an entry outside [0, K) is clamped into range first (the scan does not read
+        its value).  The probe's own scores (`xsim.topk_normalized`) are the tiled mining kernel's and may differ from these
+        in the last place."""
+        src = torch.arange(nq, device=probes.device).repeat_interleave(probes.shape[1])
+        trg = probes.clamp(0, self._k - 1).reshape(-1)
+        return pair_scores(qn, nq, self._c16, self._k, src, trg, None, None, "cosine").reshape(nq, probes.shape[1])
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
+               coarse: Optional[torch.Tensor] = None, refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`IVFPQIndex.search`.  With probes None the index probes by itself and the coarse term is the score
+        `xsim.topk_normalized` returns beside every list number: no extra work.  With probes given, coarse is None (computed
+        by `coarse_scores`; its bits may differ from the probe's own in the last place) or device fp32 [nq, nprobe], the
+        query's score against the centroid of every probed list.  refine: re-scores against the original rows, unchanged."""
+        _check_refine(refine, self._d)
+        nq = self._check_search(q, k, nprobe, probes)
+        if coarse is not None:
+            if probes is None:
+                raise ValueError("coarse belongs to probes: give both, or neither")
+            _check_coarse(coarse, probes.shape)
+        qn = normalize_rows(q)
+        if probes is None:
+            coarse, probes = topk_normalized(qn, nq, self._c16, self._k, nprobe)
+        elif coarse is None:
+            coarse = self.coarse_scores(qn, nq, probes)
+        score, idx = search_lists_pq_residual(qn, probes, coarse, self._rows, self._codebooks, self._ids, self._offsets, k)
+        if refine is None:
+            return score, idx
+        return refine_candidates(qn, nq, refine, idx)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        state = super().state_dict()
+        state["by_residual"] = torch.ones(1, dtype=torch.uint8, device=self._rows.device)
+        return state
+
+    def self_join(self, *args, **kwargs):
+        raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFPQResidualIndex holds "
+                        "product-quantiser codes of residuals")
 
 
 def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
