@@ -21,8 +21,10 @@
 //   ivf_selfjoin_kernel        SemDeDup's per-list self-join (3.20): the unit's rows are list rows, its own fold and ending.
 // The last two spell the same loop out in their own text (keep it equal to ivf_slice_walk's): as instances of the
 // function the 128-row self-join waited for the prefetched slice in front of its MFMAs, and the int8 scan measured
-// 0.2-0.4 % slower in two cells of one round of two (profiles/isa_identity_ivf.txt).  The bucketing, the unit rule, the merge and the host halves are shared by calls; the quantisers (int8 rows; PQ encode,
-// train, decode) and the gathers that encode follow their scans.
+// 0.2-0.4 % slower in two cells of one round of two (profiles/isa_identity_ivf.txt).
+// The bucketing, the unit rule, the merge and the host halves are shared by calls: an entry gives the skeletons below
+// (build_entry, search_entry, rows_entry) its own checks and its gather or scan launch.  The quantisers (int8 rows; PQ
+// encode, train, decode) and the gathers that encode follow their scans.
 #include "api_common.hpp"
 #include "ivf_scan.hpp"
 #include "bucket.hpp"
@@ -147,13 +149,12 @@ int64_t slots_bound(int64_t n, int64_t K) {
   const int64_t m = std::min(n, K);
   return m * IVF_ALIGN + (n - m) / IVF_ALIGN * IVF_ALIGN;
 }
-bool build_shape_ok(int64_t n, int64_t K, int32_t d) {
-  return n >= 1 && K >= 1 && d > 0 && d % 64 == 0 && n <= IVF_MAX && K <= IVF_MAX && slots_bound(n, K) <= IVF_MAX;
-}
-bool search_shape_ok(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
-  return nq >= 1 && K >= 1 && d > 0 && d % 64 == 0 && nprobe >= 1 && nprobe <= 8 && k >= 1 && k <= 8 && nq <= IVF_MAX &&
-         K <= IVF_MAX && nq * nprobe <= IVF_MAX;
-}
+// A *_workspace_bytes function runs the shape checks of its entry -- the same functions, so it returns 0 exactly where the
+// entry refuses on shape -- under this guard: a sizing call leaves smi_last_error() as it was.
+struct KeepLastError {
+  const std::string text = last_error();
+  ~KeepLastError() { last_error() = text; }
+};
 // pairs of a scan unit = slots of its tiles: 128 where the lists are probed by 256 pairs or more on average, else 64.  (At
 // 128 pairs per list of ~61 rows, 1 M rows over 16 384 lists at nprobe = 8, the 128-slot tile is half empty and the scan took
 // 1.84 ms against 1.34; at 256 pairs per list of ~977 rows it took 1.45 ms against 2.53: profiles/ivf_experiments.txt.)
@@ -271,8 +272,9 @@ __global__ __launch_bounds__(IVF_TB) void ivf_i8_gather_kernel(const f16* __rest
 }
 
 // ivf_scan_lists_kernel on int8 codes: the same units, tiles, loader mapping, swizzle, buffers and key lists (read
-// ivf_scan.hpp's comment first), spelled out here (see the head of the file).  What differs: a K slice is IVF_I8_BK = 128 ELEMENTS (the same 128 bytes of a row), lane (l15, kg) feeds
-// chunk kk * 4 + kg of its row to MFMA step kk as 16 consecutive K bytes of BOTH operands, so the sum is the exact integer
+// ivf_scan.hpp's comment first), spelled out here (see the head of the file).
+// What differs: a K slice is IVF_I8_BK = 128 ELEMENTS (the same 128 bytes of a row), lane (l15, kg) feeds chunk
+// kk * 4 + kg of its row to MFMA step kk as 16 consecutive K bytes of BOTH operands, so the sum is the exact integer
 // whatever K order the instruction uses; nk = ceil(d / 128) and the chunks of the last slice past d (d % 128 == 64) are
 // zero-filled, which adds 0 exactly.  The fold loads the four slot scales beside the four ids, takes the pair's query scale
 // from LDS and forms fl32(fl32((float)acc * scale_x) * scale_q).
@@ -315,15 +317,7 @@ __global__ __launch_bounds__(IVF_TB) void ivf_i8_scan_lists_kernel(const int8_t*
   const int p0 = poff[l] + (b - ubase[l]) * B;
   const int npair = min(B, poff[l + 1] - p0);
   const int s_begin = off[l], s_end = off[l + 1];
-
-  if (tid < B) {
-    const int pr = tid < npair ? pairs[p0 + tid] : -1;
-    spair[tid] = pr;
-    sqs[tid] = pr >= 0 ? qscale[pr / nprobe] : 0.f;
-#pragma unroll
-    for (int j = 0; j < KT; ++j) lists[tid * KT + j] = XS_EMPTY;
-  }
-  __syncthreads();
+  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [&](int pr) { sqs[tid] = pr >= 0 ? qscale[pr / nprobe] : 0.f; });
 
   const int nk = (d + IVF_I8_BK - 1) / IVF_I8_BK;
   const int ntiles = (s_end - s_begin + B - 1) / B;
@@ -456,7 +450,6 @@ __global__ __launch_bounds__(IVF_TB) void ivf_i8_scan_lists_kernel(const int8_t*
   }
 }
 
-bool i8_dim_ok(int32_t d) { return d <= IVF_I8_MAX_DIM; }
 int i8_check_dim(int32_t d) {
   if (d > IVF_I8_MAX_DIM)
     return fail(SMI_ERR_UNSUPPORTED, "d=%d: above %d the int32 sum of int8 products could overflow", d, IVF_I8_MAX_DIM);
@@ -464,16 +457,20 @@ int i8_check_dim(int32_t d) {
 }
 
 // ---------------------------------------------------------------- host halves shared by the flat, int8 and PQ entries
+// the refusals of a build: on shape (all the sizing functions ask), then on the caller's storage and workspace
+int check_build_shape(int64_t n, int32_t d, int64_t K) {
+  if (const int rc = check_shape(n, "n", d, K, "list")) return rc;
+  if (slots_bound(n, K) > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "n=%lld rows over K=%lld lists can need %lld slots: slot numbers must fit int32",
+                (long long)n, (long long)K, (long long)slots_bound(n, K));
+  return SMI_OK;
+}
 int check_build_args(int64_t n, int32_t d, int64_t K, int64_t capacity_slots, const void* ws, int64_t ws_bytes,
                      const char* sizing) {
-  if (const int rc = check_shape(n, "n", d, K, "list")) return rc;
-  const int64_t bound = slots_bound(n, K);
-  if (bound > IVF_MAX)
-    return fail(SMI_ERR_UNSUPPORTED, "n=%lld rows over K=%lld lists can need %lld slots: slot numbers must fit int32",
-                (long long)n, (long long)K, (long long)bound);
-  if (capacity_slots < bound)
+  if (const int rc = check_build_shape(n, d, K)) return rc;
+  if (capacity_slots < slots_bound(n, K))
     return fail(SMI_ERR_INVALID_ARG, "capacity of %lld slots, smi_ivf_slots_bound(n, K) = %lld", (long long)capacity_slots,
-                (long long)bound);
+                (long long)slots_bound(n, K));
   return check_ws(ws, ws_bytes, BuildWs(nullptr, K).bytes(), sizing);
 }
 
@@ -510,6 +507,69 @@ hipError_t invert_probes(const int32_t* probes, int64_t P, int64_t K, int k, int
                      (int32_t*)nullptr);
   hipLaunchKernelGGL(ivf_fill_kernel, grid_for(P * k, IVF_TB), block, 0, st, w.ps, w.pi, P * k);
   return hipGetLastError();
+}
+
+// A build entry, stated once.  The kind gives: whether a pointer of its own is null, the name of its sizing function, its own
+// refusals (they follow check_build_args) and gather(grid, st), the launch of one wave per slot any labelling can need:
+// the waves from list_offsets[K] on find nothing to do.
+template <class Refusals, class Gather>
+int build_entry(bool null_arg, const int32_t* labels, int64_t n, int32_t d, int64_t K, int32_t* list_ids, int64_t capacity_slots,
+                int32_t* list_offsets, int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream, const char* sizing,
+                Refusals refusals, Gather gather) {
+  if (null_arg || !labels || !list_ids || !list_offsets || !list_sizes) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, sizing)) return rc;
+  if (const int rc = refusals()) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
+  gather(grid_for(slots_bound(n, K), IVF_TB / 64), st);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+// A search entry, stated once.  The kind gives: whether a pointer of its own is null, the name of its sizing function, the
+// i8_dim of its workspace, its own refusals (they follow check_search_args), prepare(w, st), what it enqueues in front of
+// the inversion (the int8 search encodes its queries there), and scan(kt, unit, units, w, st), the launch of its
+// list-walking kernel with key lists of decltype(kt)::value over units for every pair count the table can have: those from
+// ubase[K] on find nothing to do.
+template <class Refusals, class Prepare, class Scan>
+int search_entry(bool null_arg, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const int32_t* list_ids,
+                 const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
+                 void* stream, const char* sizing, int i8_dim, Refusals refusals, Prepare prepare, Scan scan) {
+  if (null_arg || !probes || !list_ids || !list_offsets || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
+  if (const int rc = refusals()) return rc;
+  const int64_t P = nq * nprobe;
+  const SearchWs w(ws, nq, K, nprobe, k, i8_dim);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), sizing)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  prepare(w, st);
+  // one unit rule for every kind: the image and the MFMA work of a PQ unit are the flat unit's, and on int8 lists 128 won
+  // from 256 pairs per list on and 64 below as well (profiles/ivf_i8_experiments.txt)
+  const int unit = unit_pairs(P, K);
+  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
+  const int64_t units = units_bound(P, K, unit);
+  HIP_TRY(with_key_list(k, [&](auto kt) { return scan(kt, unit, units, w, st); }));
+  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  return SMI_OK;
+}
+constexpr auto no_refusals = [] { return (int)SMI_OK; };
+constexpr auto no_prepare = [](const SearchWs&, hipStream_t) {};
+
+// A one-kernel entry over n rows of d fp16 (the encoders, the decoder, the residuals), stated once: null pointers, the
+// alignment of the output `name` (out16; null where the kernel does not need it), check_shape, the kind's own refusals, the
+// device, the launch.
+template <class Refusals, class Launch>
+int rows_entry(bool null_arg, const void* out16, const char* name, int64_t n, int32_t d, Refusals refusals, Launch launch) {
+  if (null_arg) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if ((uintptr_t)out16 % 16) return fail(SMI_ERR_INVALID_ARG, "%s must be 16-byte aligned", name);
+  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
+  if (const int rc = refusals()) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  launch();
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
 }
 
 // ================================================================ semantic de-duplication
@@ -715,9 +775,16 @@ __global__ __launch_bounds__(IVF_TB) void ivf_selfjoin_kernel(const f16* __restr
   }
 }
 
-bool dedup_shape_ok(int64_t slots, int64_t n, int64_t K, int32_t d) {
-  return slots >= 1 && slots % IVF_ALIGN == 0 && n >= 1 && K >= 1 && d > 0 && d % 64 == 0 && slots <= IVF_MAX && n <= IVF_MAX &&
-         K <= IVF_MAX && slots / IVF_BM + K <= IVF_MAX;
+int check_dedup_shape(int64_t slots, int64_t n, int64_t K, int32_t d) {
+  if (const int rc = check_shape(n, "n", d, K, "list")) return rc;
+  if (slots < 1) return fail(SMI_ERR_INVALID_ARG, "slots=%lld: empty storage", (long long)slots);
+  if (slots > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "slots=%lld: slot numbers must fit int32", (long long)slots);
+  if (slots % IVF_ALIGN)
+    return fail(SMI_ERR_INVALID_ARG, "slots=%lld must be a multiple of %d, as smi_ivf_build's storage is", (long long)slots,
+                IVF_ALIGN);
+  if (slots / IVF_BM + K > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "slots=%lld, K=%lld: the unit count must fit int32", (long long)slots, (long long)K);
+  return SMI_OK;
 }
 // dedup: padded list sizes [K] | their prefix sum [K + 1] (the scan's first output: list_offsets again) | unit offsets
 //        [K + 1] | cursor [K] | priorities in slot order fp32 [slots]
@@ -742,16 +809,15 @@ struct DedupWs : WsLayout {
 constexpr int PQ_CW = 256;     // codewords of every sub-quantiser: a code is one byte
 constexpr int PQ_ROWS = 2048;  // rows one block of the training update takes of one sub-quantiser
 
-bool pq_dsub_ok(int32_t d, int32_t dsub) {
-  return (dsub == 8 || dsub == 16 || dsub == 32 || dsub == 64) && d > 0 && d % dsub == 0;
-}
-int pq_check_dsub(int32_t d, int32_t dsub) {
+int pq_check_dsub(int32_t d, int32_t dsub) {  // behind check_shape: d > 0
   if (dsub != 8 && dsub != 16 && dsub != 32 && dsub != 64)
     return fail(SMI_ERR_UNSUPPORTED, "dsub=%d must be 8, 16, 32 or 64", dsub);
   if (d % dsub) return fail(SMI_ERR_UNSUPPORTED, "dsub=%d does not divide d=%d", dsub, d);
   return SMI_OK;
 }
-int pq_check_codebooks(const void* cb) {
+// the refusals every entry that is given codebooks starts its own with: dsub, then the pointer
+int pq_check_codebooks(int32_t d, int32_t dsub, const void* cb) {
+  if (const int rc = pq_check_dsub(d, dsub)) return rc;
   if (!cb) return fail(SMI_ERR_INVALID_ARG, "null codebooks");
   if ((uintptr_t)cb % 16) return fail(SMI_ERR_INVALID_ARG, "codebooks must be 16-byte aligned");
   return SMI_OK;
@@ -1106,11 +1172,10 @@ struct PqTrainWs : WsLayout {
 };
 // blocks of the training update: (row blocks) x M
 int64_t pq_update_blocks(int64_t n, int d, int dsub) { return (n + PQ_ROWS - 1) / PQ_ROWS * (d / dsub); }
-bool pq_rows_ok(int64_t n, int32_t d, int32_t dsub) {
-  return n >= 1 && n <= IVF_MAX && d > 0 && d % 64 == 0 && pq_dsub_ok(d, dsub);
-}
-bool pq_train_shape_ok(int64_t n, int32_t d, int32_t dsub) {
-  return pq_rows_ok(n, d, dsub) && (int64_t)PQ_CW * d <= IVF_MAX && pq_update_blocks(n, d, dsub) <= IVF_MAX;
+int pq_check_train_size(int64_t n, int32_t d, int32_t dsub) {  // behind check_shape and pq_check_dsub
+  if ((int64_t)PQ_CW * d > IVF_MAX || pq_update_blocks(n, d, dsub) > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "n=%lld, d=%d: the codebook elements and the update's blocks must fit int32", (long long)n, d);
+  return SMI_OK;
 }
 
 template <int DSUB, bool RES>
@@ -1151,13 +1216,11 @@ int pq_train_entry(const void* xn, const int32_t* labels, int64_t n, int32_t d, 
                    const int32_t* init, int32_t n_iter, void* codebooks, void* ws, int64_t ws_bytes, void* stream) {
   if (!xn || !init || (RES && !labels)) return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
+  if (const int rc = pq_check_codebooks(d, dsub, codebooks)) return rc;
   if constexpr (RES)
     if (const int rc = pq_check_centroids(cent, K)) return rc;
   if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d must not be negative", n_iter);
-  if ((int64_t)PQ_CW * d > IVF_MAX || pq_update_blocks(n, d, dsub) > IVF_MAX)
-    return fail(SMI_ERR_UNSUPPORTED, "n=%lld, d=%d: the codebook elements and the update's blocks must fit int32", (long long)n, d);
+  if (const int rc = pq_check_train_size(n, d, dsub)) return rc;
   const PqTrainWs w(ws, n, d, dsub);
   if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_pq_train_workspace_bytes(n, d, dsub)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
@@ -1189,28 +1252,22 @@ template <bool RES>
 int pq_build_entry(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, const void* cent, int32_t dsub,
                    const void* codebooks, void* list_codes, int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets,
                    int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
-  if (!xn || !labels || !list_codes || !list_ids || !list_offsets || !list_sizes)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_pq_build_workspace_bytes(n, K, d, dsub)"))
-    return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  if constexpr (RES)
-    if (const int rc = pq_check_centroids(cent, K)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
-  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
-  const dim3 grid = grid_for(slots_bound(n, K), IVF_TB / 64);
-  auto gather = [&](auto ds) {
-    hipLaunchKernelGGL(ivf_pq_gather_kernel<decltype(ds)::value>, grid, dim3(IVF_TB), 0, st, (const f16*)xn, d, dsub,
-                       (const f16*)codebooks, (const int32_t*)list_ids, (const int32_t*)list_offsets, (int)K, (uint8_t*)list_codes,
-                       labels, (const f16*)cent);
-  };
-  if constexpr (RES) with_dsub(dsub, gather);
-  else gather(std::integral_constant<int, 0>{});
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return build_entry(
+      !xn || !list_codes, labels, n, d, K, list_ids, capacity_slots, list_offsets, list_sizes, ws, ws_bytes, stream,
+      "smi_ivf_pq_build_workspace_bytes(n, K, d, dsub)",
+      [&] {
+        const int rc = pq_check_codebooks(d, dsub, codebooks);
+        return rc || !RES ? rc : pq_check_centroids(cent, K);
+      },
+      [&](dim3 grid, hipStream_t st) {
+        auto gather = [&](auto ds) {
+          hipLaunchKernelGGL(ivf_pq_gather_kernel<decltype(ds)::value>, grid, dim3(IVF_TB), 0, st, (const f16*)xn, d, dsub,
+                             (const f16*)codebooks, (const int32_t*)list_ids, (const int32_t*)list_offsets, (int)K,
+                             (uint8_t*)list_codes, labels, (const f16*)cent);
+        };
+        if constexpr (RES) with_dsub(dsub, gather);
+        else gather(std::integral_constant<int, 0>{});
+      });
 }
 
 template <bool RES>
@@ -1218,29 +1275,17 @@ int pq_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes
                     const void* list_codes, int32_t dsub, const void* codebooks, const int32_t* list_ids,
                     const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
                     void* stream) {
-  if (!qn || !probes || !list_codes || !list_ids || !list_offsets || !idx || !score || (RES && !coarse))
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  const int64_t P = nq * nprobe;
-  const SearchWs w(ws, nq, K, nprobe, k);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)")) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  const int unit = unit_pairs(P, K);  // the flat search's rule: the image and the MFMA work of a unit are the same
-  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
-  const int64_t units = units_bound(P, K, unit);
-  HIP_TRY(with_key_list(k, [&](auto kt) {
-    constexpr int KT = decltype(kt)::value;
-    constexpr int lds_small = RES ? ivf_pq_residual_scan_lds<IVF_BM>(KT) : ivf_scan_lds<IVF_BM>(KT);
-    constexpr int lds_big = RES ? ivf_pq_residual_scan_lds<IVF_BIG>(KT) : ivf_scan_lds<IVF_BIG>(KT);
-    return launch_units<ivf_pq_scan_lists_kernel<KT, IVF_BM, RES>, ivf_pq_scan_lists_kernel<KT, IVF_BIG, RES>>(
-        unit, units, lds_small, lds_big, st, (const f16*)qn, d, (int)nq, nprobe, (const uint8_t*)list_codes, pq_shift(dsub),
-        (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi, coarse);
-  }));
-  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
-  return SMI_OK;
+  return search_entry(
+      !qn || !list_codes || (RES && !coarse), nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)", 0, [&] { return pq_check_codebooks(d, dsub, codebooks); },
+      no_prepare, [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
+        constexpr int KT = decltype(kt)::value;
+        constexpr int lds_small = RES ? ivf_pq_residual_scan_lds<IVF_BM>(KT) : ivf_scan_lds<IVF_BM>(KT);
+        constexpr int lds_big = RES ? ivf_pq_residual_scan_lds<IVF_BIG>(KT) : ivf_scan_lds<IVF_BIG>(KT);
+        return launch_units<ivf_pq_scan_lists_kernel<KT, IVF_BM, RES>, ivf_pq_scan_lists_kernel<KT, IVF_BIG, RES>>(
+            unit, units, lds_small, lds_big, st, (const f16*)qn, d, (int)nq, nprobe, (const uint8_t*)list_codes, pq_shift(dsub),
+            (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi, coarse);
+      });
 }
 
 }  // namespace
@@ -1252,76 +1297,56 @@ extern "C" {
 int32_t smi_ivf_list_align(void) { return IVF_ALIGN; }
 
 int64_t smi_ivf_slots_bound(int64_t n, int64_t K) {
-  if (n < 1 || K < 1 || n > IVF_MAX || K > IVF_MAX || slots_bound(n, K) > IVF_MAX) return 0;
-  return slots_bound(n, K);
+  const KeepLastError keep;
+  return check_build_shape(n, 64, K) ? 0 : slots_bound(n, K);  // (any d a build takes: the bound does not depend on it)
 }
 
 int64_t smi_ivf_build_workspace_bytes(int64_t n, int64_t K, int32_t d) {
-  return build_shape_ok(n, K, d) ? (int64_t)BuildWs(nullptr, K).bytes() : 0;
+  const KeepLastError keep;
+  return check_build_shape(n, d, K) ? 0 : (int64_t)BuildWs(nullptr, K).bytes();
 }
 
 int smi_ivf_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_rows, int32_t* list_ids,
                   int64_t capacity_slots, int32_t* list_offsets, int32_t* list_sizes, void* ws, int64_t ws_bytes,
                   void* stream) {
-  if (!xn || !labels || !list_rows || !list_ids || !list_offsets || !list_sizes)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_build_workspace_bytes(n, K, d)")) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
-  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
-  hipLaunchKernelGGL(ivf_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d, list_ids,
-                     list_offsets, (int)K, (f16*)list_rows);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return build_entry(
+      !xn || !list_rows, labels, n, d, K, list_ids, capacity_slots, list_offsets, list_sizes, ws, ws_bytes, stream,
+      "smi_ivf_build_workspace_bytes(n, K, d)", no_refusals, [&](dim3 grid, hipStream_t st) {
+        hipLaunchKernelGGL(ivf_gather_kernel, grid, dim3(IVF_TB), 0, st, (const f16*)xn, d, list_ids, list_offsets, (int)K,
+                           (f16*)list_rows);
+      });
 }
 
 int64_t smi_ivf_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
-  return search_shape_ok(nq, K, nprobe, k, d) ? (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes() : 0;
+  const KeepLastError keep;
+  return check_search_args(nq, d, K, nprobe, k) ? 0 : (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes();
 }
 
 int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
                    const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                    void* ws, int64_t ws_bytes, void* stream) {
-  if (!qn || !probes || !list_rows || !list_ids || !list_offsets || !idx || !score)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
-  const int64_t P = nq * nprobe;
-  const SearchWs w(ws, nq, K, nprobe, k);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)")) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  const int unit = unit_pairs(P, K);
-  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
-  // units for every pair count the table can have: those from ubase[K] on find nothing to do
-  const int64_t units = units_bound(P, K, unit);
-  HIP_TRY(with_key_list(k, [&](auto kt) {
-    constexpr int KT = decltype(kt)::value;
-    return launch_units<ivf_scan_lists_kernel<KT, IVF_BM>, ivf_scan_lists_kernel<KT, IVF_BIG>>(
-        unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
-        (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi);
-  }));
-  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
-  return SMI_OK;
+  return search_entry(
+      !qn || !list_rows, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)", 0, no_refusals, no_prepare,
+      [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
+        constexpr int KT = decltype(kt)::value;
+        return launch_units<ivf_scan_lists_kernel<KT, IVF_BM>, ivf_scan_lists_kernel<KT, IVF_BIG>>(
+            unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
+            (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi);
+      });
 }
 
 // ---------------------------------------------------------------- semantic de-duplication
 int64_t smi_ivf_dedup_workspace_bytes(int64_t slots, int64_t n, int64_t K, int32_t d) {
-  return dedup_shape_ok(slots, n, K, d) ? (int64_t)DedupWs(nullptr, slots, K).bytes() : 0;
+  const KeepLastError keep;
+  return check_dedup_shape(slots, n, K, d) ? 0 : (int64_t)DedupWs(nullptr, slots, K).bytes();
 }
 
 int smi_ivf_dedup(const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int64_t slots,
                   int32_t d, const float* priority, int64_t n, float* max_sim, int32_t* nearest, void* ws, int64_t ws_bytes,
                   void* stream) {
   if (!list_rows || !list_ids || !list_offsets || !max_sim || !nearest) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, K, "list")) return rc;
-  if (slots < 1) return fail(SMI_ERR_INVALID_ARG, "slots=%lld: empty storage", (long long)slots);
-  if (slots > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "slots=%lld: slot numbers must fit int32", (long long)slots);
-  if (slots % IVF_ALIGN)
-    return fail(SMI_ERR_INVALID_ARG, "slots=%lld must be a multiple of %d, as smi_ivf_build's storage is", (long long)slots,
-                IVF_ALIGN);
-  if (slots / IVF_BM + K > IVF_MAX)
-    return fail(SMI_ERR_UNSUPPORTED, "slots=%lld, K=%lld: the unit count must fit int32", (long long)slots, (long long)K);
+  if (const int rc = check_dedup_shape(slots, n, K, d)) return rc;
   const DedupWs w(ws, slots, K);
   if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_dedup_workspace_bytes(slots, n, K, d)")) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
@@ -1347,98 +1372,72 @@ int smi_ivf_dedup(const void* list_rows, const int32_t* list_ids, const int32_t*
 
 // ---------------------------------------------------------------- int8 lists
 int smi_ivf_i8_encode(const void* xn, int64_t n, int32_t d, void* codes, float* scales, void* stream) {
-  if (!xn || !codes || !scales) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
-  if (const int rc = i8_check_dim(d)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d,
-                     (int8_t*)codes, scales);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return rows_entry(!xn || !codes || !scales, nullptr, "", n, d, [&] { return i8_check_dim(d); }, [&] {
+    hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d,
+                       (int8_t*)codes, scales);
+  });
 }
 
 int64_t smi_ivf_i8_build_workspace_bytes(int64_t n, int64_t K, int32_t d) {
-  return build_shape_ok(n, K, d) && i8_dim_ok(d) ? (int64_t)BuildWs(nullptr, K).bytes() : 0;
+  const KeepLastError keep;
+  return check_build_shape(n, d, K) || i8_check_dim(d) ? 0 : (int64_t)BuildWs(nullptr, K).bytes();
 }
 
 int smi_ivf_i8_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, void* list_codes,
                      float* list_scales, int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets,
                      int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
-  if (!xn || !labels || !list_codes || !list_scales || !list_ids || !list_offsets || !list_sizes)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_build_args(n, d, K, capacity_slots, ws, ws_bytes, "smi_ivf_i8_build_workspace_bytes(n, K, d)"))
-    return rc;
-  if (const int rc = i8_check_dim(d)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  HIP_TRY(bucket_rows(labels, n, K, list_ids, capacity_slots, list_offsets, list_sizes, BuildWs(ws, K).cursor, st));
-  // waves for every slot any labelling can need: those from list_offsets[K] on find nothing to do
-  hipLaunchKernelGGL(ivf_i8_gather_kernel, grid_for(slots_bound(n, K), IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)xn, d,
-                     list_ids, list_offsets, (int)K, (int8_t*)list_codes, list_scales);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return build_entry(
+      !xn || !list_codes || !list_scales, labels, n, d, K, list_ids, capacity_slots, list_offsets, list_sizes, ws, ws_bytes, stream,
+      "smi_ivf_i8_build_workspace_bytes(n, K, d)", [&] { return i8_check_dim(d); }, [&](dim3 grid, hipStream_t st) {
+        hipLaunchKernelGGL(ivf_i8_gather_kernel, grid, dim3(IVF_TB), 0, st, (const f16*)xn, d, list_ids, list_offsets, (int)K,
+                           (int8_t*)list_codes, list_scales);
+      });
 }
 
 int64_t smi_ivf_i8_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
-  return search_shape_ok(nq, K, nprobe, k, d) && i8_dim_ok(d) ? (int64_t)SearchWs(nullptr, nq, K, nprobe, k, d).bytes() : 0;
+  const KeepLastError keep;
+  const bool refused = check_search_args(nq, d, K, nprobe, k) || i8_check_dim(d);
+  return refused ? 0 : (int64_t)SearchWs(nullptr, nq, K, nprobe, k, d).bytes();
 }
 
 int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
                       const float* list_scales, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
                       int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
-  if (!qn || !probes || !list_codes || !list_scales || !list_ids || !list_offsets || !idx || !score)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
-  if (const int rc = i8_check_dim(d)) return rc;
-  const int64_t P = nq * nprobe;
-  const SearchWs w(ws, nq, K, nprobe, k, d);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)")) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, w.qc, w.qscale);
-  // the flat search's unit rule holds here too: 128 won from 256 pairs per list on, 64 below (profiles/ivf_i8_experiments.txt)
-  const int unit = unit_pairs(P, K);
-  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
-  const int64_t units = units_bound(P, K, unit);
-  HIP_TRY(with_key_list(k, [&](auto kt) {
-    constexpr int KT = decltype(kt)::value;
-    return launch_units<ivf_i8_scan_lists_kernel<KT, IVF_BM>, ivf_i8_scan_lists_kernel<KT, IVF_BIG>>(
-        unit, units, ivf_i8_scan_lds<IVF_BM>(KT), ivf_i8_scan_lds<IVF_BIG>(KT), st, (const int8_t*)w.qc, (const float*)w.qscale, d,
-        (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k,
-        w.ps, w.pi);
-  }));
-  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
-  return SMI_OK;
+  return search_entry(
+      !qn || !list_codes || !list_scales, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)", d, [&] { return i8_check_dim(d); },
+      [&](const SearchWs& w, hipStream_t st) {  // the queries, encoded like the rows
+        hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, w.qc,
+                           w.qscale);
+      },
+      [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
+        constexpr int KT = decltype(kt)::value;
+        return launch_units<ivf_i8_scan_lists_kernel<KT, IVF_BM>, ivf_i8_scan_lists_kernel<KT, IVF_BIG>>(
+            unit, units, ivf_i8_scan_lds<IVF_BM>(KT), ivf_i8_scan_lds<IVF_BIG>(KT), st, (const int8_t*)w.qc, (const float*)w.qscale,
+            d, (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k,
+            w.ps, w.pi);
+      });
 }
 
 // ---------------------------------------------------------------- product quantiser and product-quantised lists
 int smi_pq_encode(const void* xn, int64_t n, int32_t d, int32_t dsub, const void* codebooks, void* codes, void* stream) {
-  if (!xn || !codes) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipLaunchKernelGGL(pq_encode_kernel, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d, dsub,
-                     (const f16*)codebooks, (uint8_t*)codes);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return rows_entry(!xn || !codes, nullptr, "", n, d, [&] { return pq_check_codebooks(d, dsub, codebooks); }, [&] {
+    hipLaunchKernelGGL(pq_encode_kernel, grid_for(n, IVF_TB / 64), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d, dsub,
+                       (const f16*)codebooks, (uint8_t*)codes);
+  });
 }
 
 int smi_pq_decode(const void* codes, int64_t n, int32_t d, int32_t dsub, const void* codebooks, void* rows, void* stream) {
-  if (!codes || !rows) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if ((uintptr_t)rows % 16) return fail(SMI_ERR_INVALID_ARG, "rows must be 16-byte aligned");
-  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipLaunchKernelGGL(pq_decode_kernel, grid_for(n * (d / 8), IVF_TB), dim3(IVF_TB), 0, (hipStream_t)stream, (const uint8_t*)codes,
-                     n, d, dsub, (const f16*)codebooks, (f16*)rows);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return rows_entry(!codes || !rows, rows, "rows", n, d, [&] { return pq_check_codebooks(d, dsub, codebooks); }, [&] {
+    hipLaunchKernelGGL(pq_decode_kernel, grid_for(n * (d / 8), IVF_TB), dim3(IVF_TB), 0, (hipStream_t)stream, (const uint8_t*)codes,
+                       n, d, dsub, (const f16*)codebooks, (f16*)rows);
+  });
 }
 
 int64_t smi_pq_train_workspace_bytes(int64_t n, int32_t d, int32_t dsub) {
-  return pq_train_shape_ok(n, d, dsub) ? (int64_t)PqTrainWs(nullptr, n, d, dsub).bytes() : 0;
+  const KeepLastError keep;
+  const bool refused = check_shape(n, "n", d, 1, "list") || pq_check_dsub(d, dsub) || pq_check_train_size(n, d, dsub);
+  return refused ? 0 : (int64_t)PqTrainWs(nullptr, n, d, dsub).bytes();
 }
 
 int smi_pq_train(const void* xn, int64_t n, int32_t d, int32_t dsub, const int32_t* init, int32_t n_iter, void* codebooks,
@@ -1447,7 +1446,8 @@ int smi_pq_train(const void* xn, int64_t n, int32_t d, int32_t dsub, const int32
 }
 
 int64_t smi_ivf_pq_build_workspace_bytes(int64_t n, int64_t K, int32_t d, int32_t dsub) {
-  return build_shape_ok(n, K, d) && pq_dsub_ok(d, dsub) ? (int64_t)BuildWs(nullptr, K).bytes() : 0;
+  const KeepLastError keep;
+  return check_build_shape(n, d, K) || pq_check_dsub(d, dsub) ? 0 : (int64_t)BuildWs(nullptr, K).bytes();
 }
 
 int smi_ivf_pq_build(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, int32_t dsub,
@@ -1458,7 +1458,9 @@ int smi_ivf_pq_build(const void* xn, const int32_t* labels, int64_t n, int32_t d
 }
 
 int64_t smi_ivf_pq_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d, int32_t dsub) {
-  return search_shape_ok(nq, K, nprobe, k, d) && pq_dsub_ok(d, dsub) ? (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes() : 0;
+  const KeepLastError keep;
+  const bool refused = check_search_args(nq, d, K, nprobe, k) || pq_check_dsub(d, dsub);
+  return refused ? 0 : (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes();
 }
 
 int smi_ivf_pq_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
@@ -1471,29 +1473,24 @@ int smi_ivf_pq_search(const void* qn, int64_t nq, int32_t d, const int32_t* prob
 // ---------------------------------------------------------------- residual encoding against the list centroid (3.22)
 int smi_pq_residuals(const void* xn, const int32_t* labels, int64_t n, int32_t d, const void* centroids, int64_t K, void* out,
                      void* stream) {
-  if (!xn || !labels || !out) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if ((uintptr_t)out % 16) return fail(SMI_ERR_INVALID_ARG, "out must be 16-byte aligned");
-  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
-  if (const int rc = pq_check_centroids(centroids, K)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipLaunchKernelGGL(pq_residuals_kernel, grid_for(n * (d / 8), IVF_TB), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n, d,
-                     labels, (const f16*)centroids, (int)K, (f16*)out);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return rows_entry(!xn || !labels || !out, out, "out", n, d, [&] { return pq_check_centroids(centroids, K); }, [&] {
+    hipLaunchKernelGGL(pq_residuals_kernel, grid_for(n * (d / 8), IVF_TB), dim3(IVF_TB), 0, (hipStream_t)stream, (const f16*)xn, n,
+                       d, labels, (const f16*)centroids, (int)K, (f16*)out);
+  });
 }
 
 int smi_pq_encode_residual(const void* xn, const int32_t* labels, int64_t n, int32_t d, const void* centroids, int64_t K,
                            int32_t dsub, const void* codebooks, void* codes, void* stream) {
-  if (!xn || !labels || !codes) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, "n", d, 1, "list")) return rc;
-  if (const int rc = pq_check_dsub(d, dsub)) return rc;
-  if (const int rc = pq_check_codebooks(codebooks)) return rc;
-  if (const int rc = pq_check_centroids(centroids, K)) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  launch_pq_encode_residual((const f16*)xn, n, d, dsub, (const f16*)codebooks, (uint8_t*)codes, labels, (const f16*)centroids, (int)K,
-                            (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return SMI_OK;
+  return rows_entry(
+      !xn || !labels || !codes, nullptr, "", n, d,
+      [&] {
+        const int rc = pq_check_codebooks(d, dsub, codebooks);
+        return rc ? rc : pq_check_centroids(centroids, K);
+      },
+      [&] {
+        launch_pq_encode_residual((const f16*)xn, n, d, dsub, (const f16*)codebooks, (uint8_t*)codes, labels, (const f16*)centroids,
+                                  (int)K, (hipStream_t)stream);
+      });
 }
 
 int smi_pq_train_residual(const void* xn, const int32_t* labels, int64_t n, int32_t d, const void* centroids, int64_t K,

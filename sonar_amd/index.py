@@ -53,11 +53,15 @@ PQ_CODEWORDS = 256  # codewords of every sub-quantiser: a code is one byte
 PQ_DSUBS = (8, 16, 32, 64)  # dimensions per sub-quantiser
 
 
-def _check_matrix(t, name: str) -> None:
+def _check_device_tensor(t, name: str, hint: str = "") -> None:
     if not isinstance(t, torch.Tensor):
         raise TypeError(f"{name} must be a torch.Tensor")
     if not t.is_cuda:
-        raise RuntimeError(f"{name}: the index runs on a HIP device only (no CPU path); move the embeddings to cuda")
+        raise RuntimeError(f"{name}: the index runs on a HIP device only (no CPU path){hint}")
+
+
+def _check_matrix(t, name: str) -> None:
+    _check_device_tensor(t, name, "; move the embeddings to cuda")
     if t.dim() != 2:
         raise ValueError(f"{name} must be [rows, dim], got {t.dim()} dimension(s)")
     if t.shape[0] < 1:
@@ -68,10 +72,7 @@ def _check_matrix(t, name: str) -> None:
 
 def _check_table(t, name: str, rows: int, cols: Optional[int]) -> None:
     """A device int32 vector [rows] (cols None) or matrix [rows, cols]."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not t.is_cuda:
-        raise RuntimeError(f"{name}: the index runs on a HIP device only (no CPU path)")
+    _check_device_tensor(t, name)
     shape = (rows,) if cols is None else (rows, cols)
     if t.dtype != torch.int32 or tuple(t.shape) != shape:
         raise ValueError(f"{name} must be int32 {list(shape)}, got {t.dtype} {list(t.shape)}")
@@ -82,10 +83,19 @@ def _check_small(v, name: str) -> None:
         raise ValueError(f"{name} = {v!r}: an integer in [1, 8]")
 
 
-def _check_build_args(xn, labels, n_lists) -> None:
-    _check_matrix(xn, "xn")
+def _check_rows16(xn, name: str, n=None) -> int:
+    """A contiguous fp16 device matrix; returns n, the rows of it a call takes (None: all)."""
+    _check_matrix(xn, name)
     if xn.dtype != torch.float16 or not xn.is_contiguous():
-        raise ValueError("xn must be a contiguous fp16 matrix")
+        raise ValueError(f"{name} must be a contiguous fp16 matrix")
+    n = xn.shape[0] if n is None else n
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= xn.shape[0]:
+        raise ValueError(f"n = {n!r}: between 1 and the {xn.shape[0]} rows of {name}")
+    return n
+
+
+def _check_build_args(xn, labels, n_lists) -> None:
+    _check_rows16(xn, "xn")
     if isinstance(n_lists, bool) or not isinstance(n_lists, int) or n_lists < 1:
         raise ValueError(f"n_lists = {n_lists!r}: at least one list")
     if isinstance(labels, torch.Tensor) and labels.dim() == 1 and not 1 <= labels.shape[0] <= xn.shape[0]:
@@ -98,66 +108,59 @@ def _check_int8_dim(d: int) -> None:
         raise ValueError(f"dim = {d} exceeds {INT8_MAX_DIM}: the int32 sum of int8 products could overflow")
 
 
-def _build(xn, labels, n_lists: int, int8: bool):
-    """smi_ivf_build / smi_ivf_i8_build: (row storage ..., ids, offsets, sizes)."""
-    _check_build_args(xn, labels, n_lists)
-    if int8:
-        _check_int8_dim(xn.shape[1])
+def _build(entry: str, sizing: str, xn, labels, n_lists: int, extras, storage, dsub=()):
+    """A build entry of the C ABI and its sizing call, both by name; the arguments were checked by the caller.  The four
+    signatures are `head + extras + storage + tail`: extras are the kind's own arguments behind the list count, storage names
+    the row tensors it fills as (dtype, trailing shape); dsub: what the sizing call takes behind d.  Returns (row storage ...,
+    ids, offsets, sizes)."""
     lib = _lib.load()
     n, d, dev = labels.shape[0], xn.shape[1], xn.device
     cap = int(lib.smi_ivf_slots_bound(n, n_lists))
     if cap < 1:
         raise ValueError(f"{n} rows over {n_lists} lists: slot numbers must fit int32")
-    rows = torch.empty((cap, d), dtype=torch.int8 if int8 else torch.float16, device=dev)
-    scales = (torch.empty((cap,), dtype=torch.float32, device=dev),) if int8 else ()
+    rows = [torch.empty((cap, *shape), dtype=dtype, device=dev) for dtype, shape in storage]
     ids = torch.empty((cap,), dtype=torch.int32, device=dev)
     offsets = torch.empty((n_lists + 1,), dtype=torch.int32, device=dev)
     sizes = torch.empty((n_lists,), dtype=torch.int32, device=dev)
-    sizing, entry = ((lib.smi_ivf_i8_build_workspace_bytes, lib.smi_ivf_i8_build) if int8 else
-                     (lib.smi_ivf_build_workspace_bytes, lib.smi_ivf_build))
-    ws_bytes = int(sizing(n, n_lists, d))
+    ws_bytes = int(getattr(lib, sizing)(n, n_lists, d, *dsub))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     labels = labels.contiguous()
     with torch.cuda.device(dev):
-        _lib.check(entry(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, rows.data_ptr(), *(t.data_ptr() for t in scales),
-                         ids.data_ptr(), cap, offsets.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws_bytes,
-                         _lib.current_stream_ptr()))
-    return (rows, *scales, ids, offsets, sizes)
+        _lib.check(getattr(lib, entry)(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, *extras, *(t.data_ptr() for t in rows),
+                                       ids.data_ptr(), cap, offsets.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws_bytes,
+                                       _lib.current_stream_ptr()))
+    return (*rows, ids, offsets, sizes)
 
 
 def _check_search_args(qn, probes, k) -> None:
     _check_small(k, "k")
-    _check_matrix(qn, "qn")
-    if qn.dtype != torch.float16 or not qn.is_contiguous():
-        raise ValueError("qn must be a contiguous fp16 matrix")
+    _check_rows16(qn, "qn")
     if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= 8
                                              or not 1 <= probes.shape[0] <= qn.shape[0]):
         raise ValueError(f"probes must be [nq, 1..8] with nq <= {qn.shape[0]} rows, got {list(probes.shape)}")
     _check_table(probes, "probes", *(probes.shape if isinstance(probes, torch.Tensor) else (-1, 1)))
 
 
-def _search(qn, probes, rows, scales, ids, offsets, k: int):
-    """smi_ivf_search (scales None) / smi_ivf_i8_search."""
-    _check_search_args(qn, probes, k)
-    int8 = scales is not None
-    if int8:
-        _check_int8_dim(qn.shape[1])
+def _search(entry: str, sizing: str, qn, probes, k: int, extras, storage, ids, offsets, dsub=()):
+    """A search entry of the C ABI and its sizing call, as in `_build`: `head + extras + nprobe + storage + tail`, storage the
+    arguments that describe the lists (pointers of tensors the caller holds).  Returns (scores, ids)."""
     lib = _lib.load()
     (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
-    if rows.shape[1] != d:
-        raise ValueError(f"qn has dim {d}, the lists {rows.shape[1]}")
-    sizing, entry = ((lib.smi_ivf_i8_search_workspace_bytes, lib.smi_ivf_i8_search) if int8 else
-                     (lib.smi_ivf_search_workspace_bytes, lib.smi_ivf_search))
-    ws_bytes = int(sizing(nq, n_lists, nprobe, k, d))
+    ws_bytes = int(getattr(lib, sizing)(nq, n_lists, nprobe, k, d, *dsub))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
     idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
     score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
     probes = probes.contiguous()
     with torch.cuda.device(qn.device):
-        _lib.check(entry(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, rows.data_ptr(),
-                         *((scales.data_ptr(),) if int8 else ()), ids.data_ptr(), offsets.data_ptr(), n_lists, k,
-                         idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+        _lib.check(getattr(lib, entry)(qn.data_ptr(), nq, d, probes.data_ptr(), *extras, nprobe, *storage, ids.data_ptr(),
+                                       offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes,
+                                       _lib.current_stream_ptr()))
     return score, idx
+
+
+def _check_lists_dim(qn, rows) -> None:
+    if rows.shape[1] != qn.shape[1]:
+        raise ValueError(f"qn has dim {qn.shape[1]}, the lists {rows.shape[1]}")
 
 
 def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
@@ -165,25 +168,23 @@ def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
     int32 [n]; a label outside [0, n_lists) leaves the row out).  Returns (rows fp16 [slots, d], ids int32 [slots], offsets
     int32 [n_lists + 1], sizes int32 [n_lists]) with slots = smi_ivf_slots_bound(n, n_lists): the host has not seen the
     labels, so the storage is sized for any labelling.  Slots from offsets[n_lists] on are unused (ids -1, rows unwritten)."""
-    return _build(xn, labels, n_lists, int8=False)
+    _check_build_args(xn, labels, n_lists)
+    return _build("smi_ivf_build", "smi_ivf_build_workspace_bytes", xn, labels, n_lists, (), [(torch.float16, xn.shape[1:])])
 
 
 def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
                  k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_ivf_search: the k best rows of the lists probes (device int32 [nq, 1..8]) names, for the first nq rows of qn
     (contiguous fp16 [>= nq, d]) against the storage `build_lists` returned: (scores fp32 [nq, k], ids int32 [nq, k])."""
-    return _search(qn, probes, rows, None, ids, offsets, k)
+    _check_search_args(qn, probes, k)
+    _check_lists_dim(qn, rows)
+    return _search("smi_ivf_search", "smi_ivf_search_workspace_bytes", qn, probes, k, (), (rows.data_ptr(),), ids, offsets)
 
 
 def encode_rows_int8(xn: torch.Tensor, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_ivf_i8_encode: (codes int8 [n, d], scales fp32 [n]) of the first n rows (default: all) of xn (contiguous fp16
     [>= n, d]): scale = amax / 127, code = rint(x * (127 / amax)), a zero row all zeros (tests/ivf_i8_ref.py)."""
-    _check_matrix(xn, "xn")
-    if xn.dtype != torch.float16 or not xn.is_contiguous():
-        raise ValueError("xn must be a contiguous fp16 matrix")
-    n = xn.shape[0] if n is None else n
-    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= xn.shape[0]:
-        raise ValueError(f"n = {n!r}: between 1 and the {xn.shape[0]} rows of xn")
+    n = _check_rows16(xn, "xn", n)
     _check_int8_dim(xn.shape[1])
     lib = _lib.load()
     codes = torch.empty((n, xn.shape[1]), dtype=torch.int8, device=xn.device)
@@ -197,24 +198,27 @@ def encode_rows_int8(xn: torch.Tensor, n: Optional[int] = None) -> Tuple[torch.T
 def build_lists_int8(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
     """smi_ivf_i8_build: `build_lists` with encoded rows.  Returns (codes int8 [slots, d], scales fp32 [slots], ids, offsets,
     sizes); a pad slot has zero codes, scale 0 and id -1."""
-    return _build(xn, labels, n_lists, int8=True)
+    _check_build_args(xn, labels, n_lists)
+    _check_int8_dim(xn.shape[1])
+    return _build("smi_ivf_i8_build", "smi_ivf_i8_build_workspace_bytes", xn, labels, n_lists, (),
+                  [(torch.int8, xn.shape[1:]), (torch.float32, ())])
 
 
 def search_lists_int8(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, ids: torch.Tensor,
                       offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_ivf_i8_search: `search_lists` against the storage `build_lists_int8` returned; the queries are encoded like the
     rows.  score = fl32(fl32((float)(integer dot product) * scale_row) * scale_query)."""
-    if not isinstance(scales, torch.Tensor):
-        raise TypeError("scales must be a torch.Tensor")
-    return _search(qn, probes, codes, scales, ids, offsets, k)
+    _check_device_tensor(scales, "scales")
+    _check_search_args(qn, probes, k)
+    _check_int8_dim(qn.shape[1])
+    _check_lists_dim(qn, codes)
+    return _search("smi_ivf_i8_search", "smi_ivf_i8_search_workspace_bytes", qn, probes, k, (),
+                   (codes.data_ptr(), scales.data_ptr()), ids, offsets)
 
 
 def _check_codebooks(codebooks, d: Optional[int] = None) -> Tuple[int, int]:
     """(M, dsub) of fp16 codebooks [M, 256, dsub] on the device; d: the row width they must add up to."""
-    if not isinstance(codebooks, torch.Tensor):
-        raise TypeError("codebooks must be a torch.Tensor")
-    if not codebooks.is_cuda:
-        raise RuntimeError("codebooks: the index runs on a HIP device only (no CPU path)")
+    _check_device_tensor(codebooks, "codebooks")
     if (codebooks.dtype != torch.float16 or codebooks.dim() != 3 or codebooks.shape[1] != PQ_CODEWORDS
             or codebooks.shape[2] not in PQ_DSUBS or codebooks.shape[0] < 1 or not codebooks.is_contiguous()):
         raise ValueError(f"codebooks must be contiguous fp16 [M, {PQ_CODEWORDS}, dsub] with dsub in {PQ_DSUBS}, got "
@@ -235,22 +239,9 @@ def _check_dsub(dsub, d: int) -> None:
 
 
 def _check_codes(codes, name: str, m: int) -> None:
-    if not isinstance(codes, torch.Tensor):
-        raise TypeError(f"{name} must be a torch.Tensor")
-    if not codes.is_cuda:
-        raise RuntimeError(f"{name}: the index runs on a HIP device only (no CPU path)")
+    _check_device_tensor(codes, name)
     if codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[0] < 1 or codes.shape[1] != m or not codes.is_contiguous():
         raise ValueError(f"{name} must be contiguous uint8 [rows, {m}], got {codes.dtype} {list(codes.shape)}")
-
-
-def _check_rows16(xn, name: str, n) -> int:
-    _check_matrix(xn, name)
-    if xn.dtype != torch.float16 or not xn.is_contiguous():
-        raise ValueError(f"{name} must be a contiguous fp16 matrix")
-    n = xn.shape[0] if n is None else n
-    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= xn.shape[0]:
-        raise ValueError(f"n = {n!r}: between 1 and the {xn.shape[0]} rows of {name}")
-    return n
 
 
 def _pq_train(xn, n: int, dsub, init, n_iter, residual=None) -> torch.Tensor:
@@ -313,24 +304,9 @@ def pq_decode(codes: torch.Tensor, codebooks: torch.Tensor) -> torch.Tensor:
 def _build_pq(xn, labels, n_lists: int, codebooks, centroids=None):
     """smi_ivf_pq_build, or smi_ivf_pq_build_residual against centroids (fp16 [n_lists, d])."""
     m, dsub = _check_codebooks(codebooks, xn.shape[1])
-    lib = _lib.load()
-    n, d, dev = labels.shape[0], xn.shape[1], xn.device
-    cap = int(lib.smi_ivf_slots_bound(n, n_lists))
-    if cap < 1:
-        raise ValueError(f"{n} rows over {n_lists} lists: slot numbers must fit int32")
-    codes = torch.empty((cap, m), dtype=torch.uint8, device=dev)
-    ids = torch.empty((cap,), dtype=torch.int32, device=dev)
-    offsets = torch.empty((n_lists + 1,), dtype=torch.int32, device=dev)
-    sizes = torch.empty((n_lists,), dtype=torch.int32, device=dev)
-    ws_bytes = int(lib.smi_ivf_pq_build_workspace_bytes(n, n_lists, d, dsub))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    labels = labels.contiguous()
-    entry, cent = (lib.smi_ivf_pq_build, ()) if centroids is None else (lib.smi_ivf_pq_build_residual, (centroids.data_ptr(),))
-    with torch.cuda.device(dev):
-        _lib.check(entry(xn.data_ptr(), labels.data_ptr(), n, d, n_lists, *cent, dsub, codebooks.data_ptr(), codes.data_ptr(),
-                         ids.data_ptr(), cap, offsets.data_ptr(), sizes.data_ptr(), ws.data_ptr(), ws_bytes,
-                         _lib.current_stream_ptr()))
-    return codes, ids, offsets, sizes
+    entry, cent = ("smi_ivf_pq_build", ()) if centroids is None else ("smi_ivf_pq_build_residual", (centroids.data_ptr(),))
+    return _build(entry, "smi_ivf_pq_build_workspace_bytes", xn, labels, n_lists, (*cent, dsub, codebooks.data_ptr()),
+                  [(torch.uint8, (m,))], (dsub,))
 
 
 def build_lists_pq(xn: torch.Tensor, labels: torch.Tensor, n_lists: int, codebooks: torch.Tensor):
@@ -342,10 +318,7 @@ def build_lists_pq(xn: torch.Tensor, labels: torch.Tensor, n_lists: int, codeboo
 
 def _check_coarse(coarse, shape) -> None:
     """The coarse term of a residual search: device fp32 of the probe table's shape."""
-    if not isinstance(coarse, torch.Tensor):
-        raise TypeError("coarse must be a torch.Tensor")
-    if not coarse.is_cuda:
-        raise RuntimeError("coarse: the index runs on a HIP device only (no CPU path)")
+    _check_device_tensor(coarse, "coarse")
     if coarse.dtype != torch.float32 or tuple(coarse.shape) != tuple(shape):
         raise ValueError(f"coarse must be fp32 {list(shape)}, got {coarse.dtype} {list(coarse.shape)}")
 
@@ -357,22 +330,12 @@ def _search_pq(qn, probes, codes, codebooks, ids, offsets, k: int, coarse=None):
         _check_coarse(coarse, probes.shape)
     m, dsub = _check_codebooks(codebooks, qn.shape[1])
     _check_codes(codes, "codes", m)
-    lib = _lib.load()
-    (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
-    ws_bytes = int(lib.smi_ivf_pq_search_workspace_bytes(nq, n_lists, nprobe, k, d, dsub))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
-    idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
-    score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
-    probes = probes.contiguous()
-    entry, extra = lib.smi_ivf_pq_search, ()
+    entry, extra = "smi_ivf_pq_search", ()
     if coarse is not None:
-        coarse = coarse.contiguous()
-        entry, extra = lib.smi_ivf_pq_search_residual, (coarse.data_ptr(),)
-    with torch.cuda.device(qn.device):
-        _lib.check(entry(qn.data_ptr(), nq, d, probes.data_ptr(), *extra, nprobe, codes.data_ptr(), dsub, codebooks.data_ptr(),
-                         ids.data_ptr(), offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(),
-                         ws_bytes, _lib.current_stream_ptr()))
-    return score, idx
+        coarse = coarse.contiguous()  # (held until the call is enqueued)
+        entry, extra = "smi_ivf_pq_search_residual", (coarse.data_ptr(),)
+    return _search(entry, "smi_ivf_pq_search_workspace_bytes", qn, probes, k, extra, (codes.data_ptr(), dsub, codebooks.data_ptr()),
+                   ids, offsets, (dsub,))
 
 
 def search_lists_pq(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, codebooks: torch.Tensor, ids: torch.Tensor,
@@ -527,14 +490,18 @@ def _check_refine(refine, d: int) -> None:
 
 
 class _IVFIndex:
-    """What the IVF indexes share: the quantiser, the probe, the argument checks and the persistence.  A subclass names its
-    storage (`_ROWS_DTYPE`, `_ROWS_NAME`, `_STORAGE`: the attributes `add` fills, in the order of its build entry; `_EXTRA`:
-    further tensors of its state; `_row_width`: the columns of `rows`) and gives `_build_lists` and `_search_lists`."""
+    """What the IVF indexes share: the quantiser, the probe, `search` with its argument checks, and the persistence.  A
+    subclass names its storage (`_ROWS_DTYPE`, `_ROWS_NAME`; `_STORAGE`: the attributes `add` fills, in the order of its build
+    entry; `_SLOT_VECTORS`: those of them that hold one value per slot beside `rows`, as (attribute, dtype, its name);
+    `_EXTRA`: further tensors of its state, checked by `_check_extra`), says what it `_HOLDS` and gives `_build_lists` and
+    `_search_lists`."""
 
     _ROWS_DTYPE = torch.float16
     _ROWS_NAME = "fp16"
     _STORAGE = ("_rows", "_ids", "_offsets", "_sizes")
+    _SLOT_VECTORS = ()
     _EXTRA = ()
+    _HOLDS = None  # the sentence that ends the refusal of `self_join`
 
     def _check_extra(self, state, d: int, fresh: bool):
         """load_state_dict: (the columns `rows` must have, the attributes to take over from the `_EXTRA` entries)."""
@@ -622,20 +589,29 @@ class _IVFIndex:
         _check_matrix(q, "q")
         if q.shape[1] != self._d:
             raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
-        return self._probe(normalize_rows(q), q.shape[0], nprobe)
-
-    def _probe(self, qn: torch.Tensor, nq: int, nprobe: int) -> torch.Tensor:
+        qn = normalize_rows(q)
         if nprobe > self._k:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
-        return topk_normalized(qn, nq, self._c16, self._k, nprobe)[1]
+        return topk_normalized(qn, q.shape[0], self._c16, self._k, nprobe)[1]
 
-    def _checked_search(self, q, k, nprobe, probes):
-        """The argument checks of `search`; returns (scores, ids, qn) of the subclass's scan."""
+    def _checked_search(self, q, k, nprobe, probes, refine=None, coarse=None):
+        """`search` of every kind: the argument checks, the probe, the subclass's scan and, with refine, the re-scoring.
+        coarse: the scores that belong to probes (`IVFPQResidualIndex` alone passes them on); where the index probes by
+        itself they are the probe's own, so `_search_lists` is handed them either way."""
+        _check_refine(refine, self._d)
         nq = self._check_search(q, k, nprobe, probes)
+        if coarse is not None:
+            if probes is None:
+                raise ValueError("coarse belongs to probes: give both, or neither")
+            _check_coarse(coarse, probes.shape)
         qn = normalize_rows(q)
         if probes is None:
-            probes = self._probe(qn, nq, nprobe)
-        return (*self._search_lists(qn, probes, k), qn)
+            coarse, probes = topk_normalized(qn, nq, self._c16, self._k, nprobe)
+        score, idx = self._search_lists(qn, probes, k, coarse)
+        return (score, idx) if refine is None else refine_candidates(qn, nq, refine, idx)
+
+    def self_join(self, *args, **kwargs):
+        raise TypeError(f"self_join and semdedup need the fp16 lists of an IVFFlatIndex; {self._HOLDS}")
 
     def _check_search(self, q, k, nprobe, probes) -> int:
         """The argument checks of `search`; returns nq."""
@@ -693,10 +669,11 @@ class _IVFIndex:
         width, extra = self._check_extra(state, d, _fresh)
         if not rows.is_cuda or rows.dtype != self._ROWS_DTYPE or rows.dim() != 2 or rows.shape[1] != width:
             raise ValueError(f"rows must be {self._ROWS_NAME} [slots, {width}] on the device")
-        scales = state["scales"] if "_scales" in self._STORAGE else None
-        if scales is not None and (not isinstance(scales, torch.Tensor) or not scales.is_cuda
-                                   or scales.dtype != torch.float32 or tuple(scales.shape) != (rows.shape[0],)):
-            raise ValueError(f"scales must be fp32 [{rows.shape[0]}] on the device")
+        for attr, dtype, name in self._SLOT_VECTORS:
+            t = state[attr[1:]]
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or tuple(t.shape) != (rows.shape[0],):
+                raise ValueError(f"{attr[1:]} must be {name} [{rows.shape[0]}] on the device")
+            extra[attr] = t.contiguous().clone()
         used = int(state["offsets"][k].item())
         if used != rows.shape[0] or used % LIST_ALIGN:
             raise ValueError(f"offsets end at slot {used}, rows has {rows.shape[0]} (a multiple of {LIST_ALIGN} is expected)")
@@ -706,8 +683,6 @@ class _IVFIndex:
         self._c16[:k] = c
         self._offsets, self._sizes = state["offsets"].contiguous().clone(), state["sizes"].contiguous().clone()
         self._ids, self._rows = ids.contiguous().clone(), rows.contiguous().clone()
-        if scales is not None:
-            self._scales = scales.contiguous().clone()
         for name, t in extra.items():
             setattr(self, name, t)
         self._added = True
@@ -722,7 +697,7 @@ class IVFFlatIndex(_IVFIndex):
     def _build_lists(self, xn, labels):
         return build_lists(xn, labels, self._k)
 
-    def _search_lists(self, qn, probes, k):
+    def _search_lists(self, qn, probes, k, coarse):
         return search_lists(qn, probes, self._rows, self._ids, self._offsets, k)
 
     def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1,
@@ -732,7 +707,7 @@ class IVFFlatIndex(_IVFIndex):
 
         probes: None (the nprobe nearest lists by the quantiser) or device int32 [nq, 1..8]; an entry outside [0, K) names
         no list.  A row of probes that names a list twice may return that list's rows twice."""
-        return self._checked_search(q, k, nprobe, probes)[:2]
+        return self._checked_search(q, k, nprobe, probes)
 
     def self_join(self, priority: Optional[torch.Tensor] = None, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """`dedup.self_join` over this index's own lists: (max_sim fp32 [n], nearest int32 [n]), for every
@@ -755,6 +730,8 @@ class IVFInt8Index(_IVFIndex):
     _ROWS_DTYPE = torch.int8
     _ROWS_NAME = "int8"
     _STORAGE = ("_rows", "_scales", "_ids", "_offsets", "_sizes")
+    _SLOT_VECTORS = (("_scales", torch.float32, "fp32"),)
+    _HOLDS = "an IVFInt8Index holds int8 codes"
 
     def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor]):
         super().__init__(quantizer)
@@ -763,7 +740,7 @@ class IVFInt8Index(_IVFIndex):
     def _build_lists(self, xn, labels):
         return build_lists_int8(xn, labels, self._k)
 
-    def _search_lists(self, qn, probes, k):
+    def _search_lists(self, qn, probes, k, coarse):
         return search_lists_int8(qn, probes, self._rows, self._scales, self._ids, self._offsets, k)
 
     def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
@@ -773,14 +750,7 @@ class IVFInt8Index(_IVFIndex):
         refine: None, or the normalised fp16 corpus the index was built from (`normalize_rows(x)`, row number = id).  The k
         candidates of every query are then re-scored with their fp16 cosines (`mining.pair_scores`, cosine mode) and each
         row is re-ordered into the same total order; (-inf, -1) entries stay what they are.  No host synchronisation."""
-        _check_refine(refine, self._d)
-        score, idx, qn = self._checked_search(q, k, nprobe, probes)
-        if refine is None:
-            return score, idx
-        return refine_candidates(qn, q.shape[0], refine, idx)
-
-    def self_join(self, *args, **kwargs):
-        raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFInt8Index holds int8 codes")
+        return self._checked_search(q, k, nprobe, probes, refine)
 
 
 class IVFPQIndex(_IVFIndex):
@@ -792,6 +762,7 @@ class IVFPQIndex(_IVFIndex):
     _ROWS_DTYPE = torch.uint8
     _ROWS_NAME = "uint8"
     _EXTRA = ("_codebooks",)
+    _HOLDS = "an IVFPQIndex holds product-quantiser codes"
 
     def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor], pq: Union[ProductQuantizer, torch.Tensor]):
         super().__init__(quantizer)
@@ -821,7 +792,7 @@ class IVFPQIndex(_IVFIndex):
     def _build_lists(self, xn, labels):
         return build_lists_pq(xn, labels, self._k, self._codebooks)
 
-    def _search_lists(self, qn, probes, k):
+    def _search_lists(self, qn, probes, k, coarse):
         return search_lists_pq(qn, probes, self._rows, self._codebooks, self._ids, self._offsets, k)
 
     _BY_RESIDUAL = False  # the codes are of the rows themselves; `IVFPQResidualIndex`: of their residuals
@@ -839,14 +810,7 @@ class IVFPQIndex(_IVFIndex):
                refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """`IVFFlatIndex.search` on the reconstructed rows.  refine: as for `IVFInt8Index.search`, the normalised fp16 corpus
         the index was built from; the k candidates are re-scored with their fp16 cosines and re-ordered."""
-        _check_refine(refine, self._d)
-        score, idx, qn = self._checked_search(q, k, nprobe, probes)
-        if refine is None:
-            return score, idx
-        return refine_candidates(qn, q.shape[0], refine, idx)
-
-    def self_join(self, *args, **kwargs):
-        raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFPQIndex holds product-quantiser codes")
+        return self._checked_search(q, k, nprobe, probes, refine)
 
 
 class IVFPQResidualIndex(IVFPQIndex):
@@ -860,6 +824,7 @@ class IVFPQResidualIndex(IVFPQIndex):
     so a second index over the same lists is built from the fitted `SphericalKMeans` or from a state dict."""
 
     _BY_RESIDUAL = True
+    _HOLDS = "an IVFPQResidualIndex holds product-quantiser codes of residuals"
 
     @classmethod
     def train(cls, x: torch.Tensor, n_lists: int, dsub: int = 16, n_iter: int = 10, pq_iter: int = 8, seed: int = 0):
@@ -880,6 +845,11 @@ class IVFPQResidualIndex(IVFPQIndex):
     def _build_lists(self, xn, labels):
         return build_lists_pq_residual(xn, labels, self._c16[: self._k], self._codebooks)
 
+    def _search_lists(self, qn, probes, k, coarse):
+        if coarse is None:
+            coarse = self.coarse_scores(qn, probes.shape[0], probes)
+        return search_lists_pq_residual(qn, probes, coarse, self._rows, self._codebooks, self._ids, self._offsets, k)
+
     def coarse_scores(self, qn: torch.Tensor, nq: int, probes: torch.Tensor) -> torch.Tensor:
         """fp32 [nq, nprobe]: the cosines of the first nq rows of qn (`normalize_rows`) against the centroids probes names,
         by `mining.pair_scores` in cosine mode; an entry outside [0, K) is clamped into range first (the scan does not read
@@ -895,30 +865,12 @@ class IVFPQResidualIndex(IVFPQIndex):
         `xsim.topk_normalized` returns beside every list number: no extra work.  With probes given, coarse is None (computed
         by `coarse_scores`; its bits may differ from the probe's own in the last place) or device fp32 [nq, nprobe], the
         query's score against the centroid of every probed list.  refine: re-scores against the original rows, unchanged."""
-        _check_refine(refine, self._d)
-        nq = self._check_search(q, k, nprobe, probes)
-        if coarse is not None:
-            if probes is None:
-                raise ValueError("coarse belongs to probes: give both, or neither")
-            _check_coarse(coarse, probes.shape)
-        qn = normalize_rows(q)
-        if probes is None:
-            coarse, probes = topk_normalized(qn, nq, self._c16, self._k, nprobe)
-        elif coarse is None:
-            coarse = self.coarse_scores(qn, nq, probes)
-        score, idx = search_lists_pq_residual(qn, probes, coarse, self._rows, self._codebooks, self._ids, self._offsets, k)
-        if refine is None:
-            return score, idx
-        return refine_candidates(qn, nq, refine, idx)
+        return self._checked_search(q, k, nprobe, probes, refine, coarse)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         state = super().state_dict()
         state["by_residual"] = torch.ones(1, dtype=torch.uint8, device=self._rows.device)
         return state
-
-    def self_join(self, *args, **kwargs):
-        raise TypeError("self_join and semdedup need the fp16 lists of an IVFFlatIndex; an IVFPQResidualIndex holds "
-                        "product-quantiser codes of residuals")
 
 
 def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
