@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "ln_core.hpp"
 #include "step_proc.hpp"
+#include "topk_order.hpp"
 
 namespace smi {
 
@@ -357,11 +358,68 @@ hipError_t launch_dec_attention(const f16* kv, const int32_t* anc, int anc_strid
   return hipGetLastError();
 }
 
-// candidate ordering shared by the selection and the beam step: value desc, token asc
+// candidate ordering shared by the selection and the beam step: value desc, token asc (topk_order.hpp: better, xs_key)
 constexpr int VS_K2MAX = 16;
 
-__device__ __forceinline__ bool cand_better(float a, int ia, float b, int ib) {
-  return a > b || (a == b && ia < ib);
+// Wave-wide arg-best reduction of the selection kernels on DPP row operations + v_permlane16/32_swap (VALU rate) instead of
+// __shfl_xor (= ds_bpermute, an LDS round trip per step and word: vocab_select ran 20 rounds x 12 of them back to back,
+// the beam step ~420 per sentence).  Step order as wave_max (common.hpp): xor 1, xor 2, half-row mirror, row mirror, then the
+// two lane swaps, whose both results are folded (one is the lane's own value, the other its partner's).  A lane holds N
+// 32-bit words; first(a, b) says that a precedes b.  Every lane ends with the same winner: the orders are total.
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_u(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+}
+template <int N, typename First>
+__device__ __forceinline__ void wave_first(unsigned (&w)[N], First first) {
+  auto fold = [&](const unsigned(&a)[N], const unsigned(&b)[N]) {  // w = first(a, b) ? a : b
+    const bool fa = first(a, b);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const unsigned x = a[i], y = b[i];  // (selected as values: `fa ? a[i] : b[i]` selects an address, and went to scratch)
+      w[i] = fa ? x : y;
+    }
+  };
+  auto dpp = [&](auto ctrl) {
+    unsigned o[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) o[i] = dpp_u<decltype(ctrl)::value>(w[i]);
+    fold(o, w);
+  };
+  auto swap = [&](auto wide) {
+    unsigned a[N], b[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+      const auto r = decltype(wide)::value ? __builtin_amdgcn_permlane32_swap(w[i], w[i], false, false)
+                                           : __builtin_amdgcn_permlane16_swap(w[i], w[i], false, false);
+      a[i] = r[0];
+      b[i] = r[1];
+    }
+    fold(b, a);
+  };
+  dpp(std::integral_constant<int, 0xB1>{});
+  dpp(std::integral_constant<int, 0x4E>{});
+  dpp(std::integral_constant<int, 0x141>{});
+  dpp(std::integral_constant<int, 0x140>{});
+  swap(std::false_type{});
+  swap(std::true_type{});
+}
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
+  auto u64 = [](const unsigned(&w)[2]) { return ((unsigned long long)w[1] << 32) | w[0]; };
+  unsigned w[2] = {(unsigned)k, (unsigned)(k >> 32)};
+  wave_first(w, [&](const unsigned(&a)[2], const unsigned(&b)[2]) { return u64(a) > u64(b); });
+  return u64(w);
+}
+// best (score desc, row asc, token asc) continuation of the wave, in every lane
+__device__ __forceinline__ void wave_best3(float& bv, int& br, int& bt) {
+  unsigned w[3] = {__float_as_uint(bv), (unsigned)br, (unsigned)bt};
+  wave_first(w, [](const unsigned(&a)[3], const unsigned(&b)[3]) {
+    const float va = __uint_as_float(a[0]), vb = __uint_as_float(b[0]);
+    return va > vb || (va == vb && ((int)a[1] < (int)b[1] || (a[1] == b[1] && (int)a[2] < (int)b[2])));
+  });
+  bv = __uint_as_float(w[0]);
+  br = (int)w[1];
+  bt = (int)w[2];
 }
 
 // ------------------------------------------------- vocabulary select (per row, tile statistics)
@@ -374,117 +432,16 @@ __device__ __forceinline__ bool cand_better(float a, int ia, float b, int ib) {
 //     loses every value tie against them (lower token wins).  Tile 0 is always read too: it holds the
 //     tokens the generation masks touch (PAD, UNK penalty, blocked EOS), so its raw maximum says
 //     nothing.  Thread t owns column t of every selected tile; k2 rounds of a workgroup-wide arg-max
-//     over sortable (value desc, token asc) keys produce the exact ordered list.
+//     over sortable (value desc, token asc) keys (xs_key; 0 = no candidate) produce the exact ordered list.
+// The pieces below are shared by vocab_select_kernel and vocab_select_banned_kernel.
 constexpr int VSEL_SLOTS = VS_K2MAX + 1;
-
-__device__ __forceinline__ unsigned long long cand_key(float v, int idx) {
-  unsigned u = __float_as_uint(v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (unsigned)(0xffffffffu - (unsigned)idx);
-}
-// Wave-wide arg-best reductions of the selection kernels on DPP row operations + v_permlane16/32_swap (VALU rate) instead of
-// __shfl_xor (= ds_bpermute, an LDS round trip per step and word: vocab_select ran 20 rounds x 12 of them back to back,
-// the beam step ~420 per sentence).  Step order as wave_max (common.hpp): xor 1, xor 2, half-row mirror, row mirror, then the
-// two lane swaps, whose both results are folded (one is the lane's own value, the other its partner's).  Every lane ends
-// with the same winner: the orders are total.
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u(unsigned v) {
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long k) {
-  auto fold = [&](unsigned lo, unsigned hi) {
-    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
-    k = o > k ? o : k;
-  };
-  fold(dpp_u<0xB1>((unsigned)k), dpp_u<0xB1>((unsigned)(k >> 32)));
-  fold(dpp_u<0x4E>((unsigned)k), dpp_u<0x4E>((unsigned)(k >> 32)));
-  fold(dpp_u<0x141>((unsigned)k), dpp_u<0x141>((unsigned)(k >> 32)));
-  fold(dpp_u<0x140>((unsigned)k), dpp_u<0x140>((unsigned)(k >> 32)));
-  {
-    const auto lo = __builtin_amdgcn_permlane16_swap((unsigned)k, (unsigned)k, false, false);
-    const auto hi = __builtin_amdgcn_permlane16_swap((unsigned)(k >> 32), (unsigned)(k >> 32), false, false);
-    const unsigned long long a = ((unsigned long long)hi[0] << 32) | lo[0], b = ((unsigned long long)hi[1] << 32) | lo[1];
-    k = a > b ? a : b;
-  }
-  {
-    const auto lo = __builtin_amdgcn_permlane32_swap((unsigned)k, (unsigned)k, false, false);
-    const auto hi = __builtin_amdgcn_permlane32_swap((unsigned)(k >> 32), (unsigned)(k >> 32), false, false);
-    const unsigned long long a = ((unsigned long long)hi[0] << 32) | lo[0], b = ((unsigned long long)hi[1] << 32) | lo[1];
-    k = a > b ? a : b;
-  }
-  return k;
-}
-// best (value desc, token asc) candidate of the wave, in every lane
-__device__ __forceinline__ void wave_best2(float& bv, int& bi) {
-  auto fold = [&](unsigned ov_, unsigned oi_) {
-    const float ov = __uint_as_float(ov_);
-    const int oi = (int)oi_;
-    if (cand_better(ov, oi, bv, bi)) {
-      bv = ov;
-      bi = oi;
-    }
-  };
-  fold(dpp_u<0xB1>(__float_as_uint(bv)), dpp_u<0xB1>((unsigned)bi));
-  fold(dpp_u<0x4E>(__float_as_uint(bv)), dpp_u<0x4E>((unsigned)bi));
-  fold(dpp_u<0x141>(__float_as_uint(bv)), dpp_u<0x141>((unsigned)bi));
-  fold(dpp_u<0x140>(__float_as_uint(bv)), dpp_u<0x140>((unsigned)bi));
-  {
-    const auto v = __builtin_amdgcn_permlane16_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-    const auto i = __builtin_amdgcn_permlane16_swap((unsigned)bi, (unsigned)bi, false, false);
-    bv = __uint_as_float(v[0]);
-    bi = (int)i[0];
-    fold(v[1], i[1]);
-  }
-  {
-    const auto v = __builtin_amdgcn_permlane32_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-    const auto i = __builtin_amdgcn_permlane32_swap((unsigned)bi, (unsigned)bi, false, false);
-    bv = __uint_as_float(v[0]);
-    bi = (int)i[0];
-    fold(v[1], i[1]);
-  }
-}
-// best (score desc, row asc, token asc) continuation of the wave, in every lane
-__device__ __forceinline__ void wave_best3(float& bv, int& br, int& bt) {
-  auto fold = [&](unsigned ov_, unsigned or_, unsigned ot_) {
-    const float ov = __uint_as_float(ov_);
-    const int orow = (int)or_, otok = (int)ot_;
-    if (ov > bv || (ov == bv && (orow < br || (orow == br && otok < bt)))) {
-      bv = ov;
-      br = orow;
-      bt = otok;
-    }
-  };
-  fold(dpp_u<0xB1>(__float_as_uint(bv)), dpp_u<0xB1>((unsigned)br), dpp_u<0xB1>((unsigned)bt));
-  fold(dpp_u<0x4E>(__float_as_uint(bv)), dpp_u<0x4E>((unsigned)br), dpp_u<0x4E>((unsigned)bt));
-  fold(dpp_u<0x141>(__float_as_uint(bv)), dpp_u<0x141>((unsigned)br), dpp_u<0x141>((unsigned)bt));
-  fold(dpp_u<0x140>(__float_as_uint(bv)), dpp_u<0x140>((unsigned)br), dpp_u<0x140>((unsigned)bt));
-  {
-    const auto v = __builtin_amdgcn_permlane16_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-    const auto r = __builtin_amdgcn_permlane16_swap((unsigned)br, (unsigned)br, false, false);
-    const auto t = __builtin_amdgcn_permlane16_swap((unsigned)bt, (unsigned)bt, false, false);
-    bv = __uint_as_float(v[0]);
-    br = (int)r[0];
-    bt = (int)t[0];
-    fold(v[1], r[1], t[1]);
-  }
-  {
-    const auto v = __builtin_amdgcn_permlane32_swap(__float_as_uint(bv), __float_as_uint(bv), false, false);
-    const auto r = __builtin_amdgcn_permlane32_swap((unsigned)br, (unsigned)br, false, false);
-    const auto t = __builtin_amdgcn_permlane32_swap((unsigned)bt, (unsigned)bt, false, false);
-    bv = __uint_as_float(v[0]);
-    br = (int)r[0];
-    bt = (int)t[0];
-    fold(v[1], r[1], t[1]);
-  }
-}
+constexpr int VSEL_TPT = 8;  // tiles per thread: up to 2048 tiles = 524288 tokens
 
 // logits of (row, token): fp32 row-major [rows][ldl], or -- f16_tm -- fp16 in the tile-major layout of common.hpp with K = ldl
 // (what the logits GEMM of an fp16 model stores, round 4)
 __device__ __forceinline__ float logit_at(const float* __restrict__ logits, int ldl, int f16_tm, int row, int tok) {
   return f16_tm ? (float)((const f16*)logits)[tm_offset(row, tok, ldl)] : logits[(size_t)row * ldl + tok];
 }
-
-constexpr int VSEL_TPT = 8;  // tiles per thread: up to 2048 tiles = 524288 tokens
 
 // step 1 of the selection: the row's softmax normaliser (pmax, psum) from its tile statistics; m[] = the thread's tile maxima
 __device__ __forceinline__ void vsel_normaliser(const float* __restrict__ tile_max, const float* __restrict__ tile_sum,
@@ -522,9 +479,98 @@ __device__ __forceinline__ void vsel_normaliser(const float* __restrict__ tile_m
   }
 }
 
-// TABLE (per-sentence prompts, PromptTableDev): the row's block_eos / unk_penalty follow its own sentence's mode at step_nr,
-// and a row whose sentence is forced there (prompt token, forced EOS, past its cap) leaves after its normaliser, as a k2 = 0
-// launch does for every row.  A free row's candidates are formed exactly as without the table.
+// Does a row of sentence s select at step_nr?  TABLE (per-sentence prompts, PromptTableDev): the row's block_eos follows its
+// own sentence's mode there, and a row whose sentence is forced (prompt token, forced EOS, past its cap) leaves after its
+// normaliser, as a k2 = 0 launch does for every row.  A free row's candidates are formed exactly as without the table.
+// (The k2 = 0 test stays in the kernels: inside this helper it cost vocab_select_kernel<true> 6 SGPRs and a wait.)
+template <bool TABLE>
+__device__ __forceinline__ bool vsel_row_free(const PromptTableDev& table, int s, int step_nr, int& block_eos) {
+  if constexpr (TABLE) {
+    const PromptRowMode md = prompt_row_mode(table, s, step_nr);
+    if (!md.free_step) return false;
+    block_eos = md.block_eos;
+  }
+  return true;
+}
+
+// The selections are rounds of "workgroup-wide maximum of a sortable key, then retire the winner".  The kernels are VALU-bound
+// (1280 rows x 4 waves on 1024 SIMDs: a round used to rebuild and compare the keys of all of a thread's slots, ~230 VALU
+// instructions, 20 rounds), so every thread keeps its keys and its current best: a round is one wave reduction of the
+// per-thread bests, one LDS exchange behind ONE barrier (the wave results alternate between the two halves of slot, by the
+// running round count `rounds`), and only the winner's thread rescans its slots.
+__device__ __forceinline__ unsigned long long vsel_wg_max(unsigned long long mine, unsigned long long (*slot)[4], int& rounds) {
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const unsigned long long w = wave_max_u64(mine);
+  unsigned long long* s = slot[rounds & 1];
+  if (lane == 0) s[wv] = w;
+  __syncthreads();
+  unsigned long long b = s[0];
+#pragma unroll
+  for (int q = 1; q < 4; ++q) b = s[q] > b ? s[q] : b;
+  ++rounds;
+  return b;
+}
+// The round's winner b leaves the slots of the thread that held it.  Keys are unique (the tile or token index is part of
+// them): exactly one thread.
+template <int N>
+__device__ __forceinline__ void vsel_retire(unsigned long long (&k)[N], unsigned long long& best, unsigned long long b) {
+  if (b == 0ull || b != best) return;
+  best = 0ull;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const unsigned long long kj = k[j] == b ? 0ull : k[j];
+    k[j] = kj;
+    best = kj > best ? kj : best;
+  }
+}
+// The k2 best tiles >= 1 (value desc, tile asc) that `skip` does not exclude, to sel[1..]; sel[0] = tile 0, which is taken
+// unconditionally.  Returns the number of entries of sel; last = the key of the last tile taken.  The rounds end early with
+// fewer than k2 such tiles: the caller's barrier before it reads sel is also what lines the workgroup up again.
+template <typename Skip>
+__device__ __forceinline__ int vsel_best_tiles(const float (&m)[VSEL_TPT], int k2, int* sel, unsigned long long (*slot)[4],
+                                               int& rounds, unsigned long long& last, Skip skip) {
+  const int tid = threadIdx.x;
+  unsigned long long tk[VSEL_TPT];
+  unsigned long long tbest = 0ull;
+#pragma unroll
+  for (int j = 0; j < VSEL_TPT; ++j) {
+    const int t = tid + 256 * j;
+    tk[j] = (m[j] != -INFINITY && t != 0 && !skip(t)) ? xs_key(m[j], t) : 0ull;
+    tbest = tk[j] > tbest ? tk[j] : tbest;
+  }
+  if (tid == 0) sel[0] = 0;
+  int nsel = 1;
+  for (int round = 0; round < k2; ++round) {
+    const unsigned long long b = vsel_wg_max(tbest, slot, rounds);
+    if (b == 0ull) break;
+    if (tid == 0) sel[nsel] = xs_key_index(b);
+    ++nsel;
+    last = b;
+    vsel_retire(tk, tbest, b);
+  }
+  return nsel;
+}
+// A column's key from its logit under the generation masks: 0 for a token that is no candidate.
+struct VselColumns {
+  const float* __restrict__ logits;
+  int ldl, f16_tm, vocab;
+  float inv_temp;
+  int pad_idx, eos_idx, unk_idx;
+  float unk_penalty;
+  int block_eos;
+  __device__ __forceinline__ unsigned long long key(int row, int tok) const {
+    if (tok >= vocab || tok == pad_idx || (block_eos && tok == eos_idx)) return 0ull;
+    float v = logit_at(logits, ldl, f16_tm, row, tok) * inv_temp;
+    if (tok == unk_idx) v -= unk_penalty;
+    return v != -INFINITY ? xs_key(v, tok) : 0ull;
+  }
+};
+// entry o of the ordered list: the candidate of key b, or (-inf, 0x7fffffff) for none
+__device__ __forceinline__ void vsel_write(unsigned long long b, float* __restrict__ pval, int* __restrict__ pidx, size_t o) {
+  pval[o] = b != 0ull ? xs_key_value(b) : -INFINITY;
+  pidx[o] = b != 0ull ? xs_key_index(b) : 0x7fffffff;
+}
+
 template <bool TABLE>
 __global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restrict__ logits, int ldl, int f16_tm, int vocab,
                                                            const float* __restrict__ tile_max,
@@ -536,96 +582,31 @@ __global__ __launch_bounds__(256) void vocab_select_kernel(const float* __restri
                                                            PromptTableDev table, int group, int step_nr) {
   __shared__ float s_f[4];
   __shared__ int s_sel[VSEL_SLOTS];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  constexpr int TPT = VSEL_TPT;
-  float m[TPT];
+  __shared__ unsigned long long s_k2[2][4];
+  const int row = blockIdx.x, tid = threadIdx.x;
+  float m[VSEL_TPT];
   vsel_normaliser(tile_max, tile_sum, ntiles, stat_rows, pmax, psum, m, s_f);
   if (k2 == 0) return;
-  if constexpr (TABLE) {
-    const PromptRowMode md = prompt_row_mode(table, row / group, step_nr);
-    if (!md.free_step) return;
-    block_eos = md.block_eos;
-  }
-  // The two selections below are k2 rounds of "workgroup-wide maximum of a sortable key, then retire the winner".  The kernel is
-  // VALU-bound (1280 rows x 4 waves on 1024 SIMDs: a round used to rebuild and compare the keys of all of a thread's slots,
-  // ~230 VALU instructions, 20 rounds), so every thread now keeps its keys and its current best: a round is one wave reduction
-  // of the per-thread bests, one LDS exchange behind ONE barrier (the slots alternate between two buffers), and only the
-  // winner's thread rescans its slots.
-  __shared__ unsigned long long s_k2[2][4];
-  auto wg_max = [&](unsigned long long mine, int round) {
-    const unsigned long long w = wave_max_u64(mine);
-    if (lane == 0) s_k2[round & 1][wv] = w;
-    __syncthreads();
-    unsigned long long b = s_k2[round & 1][0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) b = s_k2[round & 1][q] > b ? s_k2[round & 1][q] : b;
-    return b;
-  };
-  // ---- 2a. the k2 best tiles among tiles >= 1 (value desc, tile asc), plus tile 0
-  unsigned long long tk[TPT];
-  unsigned long long tbest = 0ull;
-#pragma unroll
-  for (int j = 0; j < TPT; ++j) {
-    const int t = tid + 256 * j;
-    tk[j] = (m[j] != -INFINITY && t != 0) ? cand_key(m[j], t) : 0ull;  // tile 0 is taken unconditionally
-    tbest = tk[j] > tbest ? tk[j] : tbest;
-  }
-  if (tid == 0) s_sel[0] = 0;
-  int nsel = 1;
-  for (int round = 0; round < k2; ++round) {
-    const unsigned long long b = wg_max(tbest, round);
-    if (b == 0ull) break;  // fewer than k2 tiles
-    if (tid == 0) s_sel[nsel] = (int)(0xffffffffu - (unsigned)(b & 0xffffffffu));
-    ++nsel;
-    if (b == tbest) {  // keys are unique (the tile index is part of them): exactly one thread
-      tbest = 0ull;
-#pragma unroll
-      for (int j = 0; j < TPT; ++j) {
-        if (tk[j] == b) tk[j] = 0ull;
-        tbest = tk[j] > tbest ? tk[j] : tbest;
-      }
-    }
-  }
-  __syncthreads();
+  if (!vsel_row_free<TABLE>(table, row / group, step_nr, block_eos)) return;
+  // ---- 2a. the k2 best tiles among tiles >= 1, plus tile 0
+  int rounds = 0;
+  unsigned long long last = 0ull;
+  const int nsel = vsel_best_tiles(m, k2, s_sel, s_k2, rounds, last, [](int) { return false; });
+  __syncthreads();  // s_sel is complete; also what makes an early end of the tile rounds safe
   // ---- 2b. thread t owns column t of every selected tile
+  const VselColumns cols{logits, ldl, f16_tm, vocab, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos};
   unsigned long long ck[VSEL_SLOTS];
   unsigned long long cbest = 0ull;
 #pragma unroll
   for (int j = 0; j < VSEL_SLOTS; ++j) {
-    ck[j] = 0ull;
-    if (j < nsel) {
-      const int tok = s_sel[j] * 256 + tid;
-      if (tok < vocab && tok != pad_idx && !(block_eos && tok == eos_idx)) {
-        float v = logit_at(logits, ldl, f16_tm, row, tok) * inv_temp;
-        if (tok == unk_idx) v -= unk_penalty;
-        if (v != -INFINITY) ck[j] = cand_key(v, tok);
-      }
-    }
+    ck[j] = j < nsel ? cols.key(row, s_sel[j] * 256 + tid) : 0ull;
     cbest = ck[j] > cbest ? ck[j] : cbest;
   }
   // ---- 2c. ordered top-k2 by k2 workgroup-wide arg-max rounds
   for (int round = 0; round < k2; ++round) {
-    const unsigned long long b = wg_max(cbest, round + k2);
-    float val = -INFINITY;
-    int idx = 0x7fffffff;
-    if (b != 0ull) {
-      unsigned u = (unsigned)(b >> 32);
-      u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-      val = __uint_as_float(u);
-      idx = (int)(0xffffffffu - (unsigned)(b & 0xffffffffu));
-    }
-    if (tid == 0) {
-      pval[(size_t)row * VS_K2MAX + round] = val;
-      pidx[(size_t)row * VS_K2MAX + round] = idx;
-    }
-    if (b != 0ull && b == cbest) {
-      cbest = 0ull;
-#pragma unroll
-      for (int j = 0; j < VSEL_SLOTS; ++j) {
-        if (ck[j] == b) ck[j] = 0ull;
-        cbest = ck[j] > cbest ? ck[j] : cbest;
-      }
-    }
+    const unsigned long long b = vsel_wg_max(cbest, s_k2, rounds);
+    if (tid == 0) vsel_write(b, pval, pidx, (size_t)row * VS_K2MAX + round);
+    vsel_retire(ck, cbest, b);
   }
 }
 
@@ -658,16 +639,12 @@ __global__ __launch_bounds__(256) void vocab_select_banned_kernel(
   __shared__ unsigned long long s_top[VS_K2MAX];
   __shared__ unsigned long long s_k2[2][4];
   __shared__ int s_nban, s_ndirty;
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int row = blockIdx.x, tid = threadIdx.x;
   constexpr int TPT = VSEL_TPT;
   float m[TPT];
   vsel_normaliser(tile_max, tile_sum, ntiles, stat_rows, pmax, psum, m, s_f);
   if (k2 == 0) return;
-  if constexpr (TABLE) {  // as vocab_select_kernel<true>
-    const PromptRowMode md = prompt_row_mode(table, row / group, step_nr);
-    if (!md.free_step) return;
-    block_eos = md.block_eos;
-  }
+  if (!vsel_row_free<TABLE>(table, row / group, step_nr, block_eos)) return;
   // ---- B0. the row's sequence into LDS, empty ban list / dirty bitmap / slot map
   const int32_t* h = hist + (size_t)row * hist_stride;
   for (int i = tid; i < hist_len; i += 256) s_seq[i] = h[i];
@@ -689,51 +666,13 @@ __global__ __launch_bounds__(256) void vocab_select_banned_kernel(
   __syncthreads();
   const int nban = min(s_nban, VSB_MAX_BANS);
   auto dirty = [&](int t) { return (s_dirty[t >> 5] >> (t & 31)) & 1u; };
-  int rr = 0;  // running round: the wave results alternate between the two halves of s_k2
-  auto wg_max = [&](unsigned long long mine) {
-    const unsigned long long w = wave_max_u64(mine);
-    if (lane == 0) s_k2[rr & 1][wv] = w;
-    __syncthreads();
-    unsigned long long b = s_k2[rr & 1][0];
-#pragma unroll
-    for (int q = 1; q < 4; ++q) b = s_k2[rr & 1][q] > b ? s_k2[rr & 1][q] : b;
-    ++rr;
-    return b;
-  };
   // ---- B2. the k2 best clean tiles >= 1, and the k2-th one's maximum
-  unsigned long long tk[TPT];
-  unsigned long long tbest = 0ull, last = 0ull;
-#pragma unroll
-  for (int j = 0; j < TPT; ++j) {
-    const int t = tid + 256 * j;
-    tk[j] = (m[j] != -INFINITY && t != 0 && !dirty(t)) ? cand_key(m[j], t) : 0ull;
-    tbest = tk[j] > tbest ? tk[j] : tbest;
-  }
-  if (tid == 0) s_tiles[0] = 0;
-  int nsel = 1;
-  for (int round = 0; round < k2; ++round) {
-    const unsigned long long b = wg_max(tbest);
-    if (b == 0ull) break;  // fewer than k2 clean tiles
-    if (tid == 0) s_tiles[nsel] = (int)(0xffffffffu - (unsigned)(b & 0xffffffffu));
-    ++nsel;
-    last = b;
-    if (b == tbest) {
-      tbest = 0ull;
-#pragma unroll
-      for (int j = 0; j < TPT; ++j) {
-        if (tk[j] == b) tk[j] = 0ull;
-        tbest = tk[j] > tbest ? tk[j] : tbest;
-      }
-    }
-  }
+  int rounds = 0;
+  unsigned long long last = 0ull;
+  const int nsel = vsel_best_tiles(m, k2, s_tiles, s_k2, rounds, last, dirty);
   // ---- B3. the dirty tiles that can hold a candidate
   const bool all_dirty = nsel - 1 < k2;
-  float thr = -INFINITY;
-  if (!all_dirty) {  // invert cand_key's value half
-    unsigned u = (unsigned)(last >> 32);
-    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    thr = __uint_as_float(u);
-  }
+  const float thr = all_dirty ? -INFINITY : xs_key_value(last);
 #pragma unroll
   for (int j = 0; j < TPT; ++j) {
     const int t = tid + 256 * j;
@@ -743,6 +682,7 @@ __global__ __launch_bounds__(256) void vocab_select_banned_kernel(
   __syncthreads();
   const int ncand = nsel + s_ndirty;
   // ---- B4. groups of VSEL_SLOTS tiles, each merged with the running top-k2
+  const VselColumns cols{logits, ldl, f16_tm, vocab, inv_temp, pad_idx, eos_idx, unk_idx, unk_penalty, block_eos};
   for (int g0 = 0; g0 < ncand; g0 += VSEL_SLOTS) {
     const int gn = min(VSEL_SLOTS, ncand - g0);
     if (tid < VSEL_SLOTS * 8) s_mask[tid >> 3][tid & 7] = 0u;
@@ -758,49 +698,22 @@ __global__ __launch_bounds__(256) void vocab_select_banned_kernel(
 #pragma unroll
     for (int j = 0; j < VSEL_SLOTS; ++j) {
       ck[j] = 0ull;
-      if (j < gn) {
-        const int tok = s_tiles[g0 + j] * 256 + tid;
-        const bool banned = (s_mask[j][tid >> 5] >> (tid & 31)) & 1u;
-        if (tok < vocab && !banned && tok != pad_idx && !(block_eos && tok == eos_idx)) {
-          float v = logit_at(logits, ldl, f16_tm, row, tok) * inv_temp;
-          if (tok == unk_idx) v -= unk_penalty;
-          if (v != -INFINITY) ck[j] = cand_key(v, tok);
-        }
-      }
+      if (j < gn && !((s_mask[j][tid >> 5] >> (tid & 31)) & 1u)) ck[j] = cols.key(row, s_tiles[g0 + j] * 256 + tid);
       cbest = ck[j] > cbest ? ck[j] : cbest;
     }
     ck[VSEL_SLOTS] = tid < k2 ? s_top[tid] : 0ull;  // the running list takes part as one more slot
     cbest = ck[VSEL_SLOTS] > cbest ? ck[VSEL_SLOTS] : cbest;
     __syncthreads();  // every s_top read before the rounds rewrite it
     for (int round = 0; round < k2; ++round) {
-      const unsigned long long b = wg_max(cbest);
+      const unsigned long long b = vsel_wg_max(cbest, s_k2, rounds);
       if (tid == 0) s_top[round] = b;
-      if (b != 0ull && b == cbest) {  // keys are unique (the token is part of them): exactly one thread
-        cbest = 0ull;
-#pragma unroll
-        for (int j = 0; j <= VSEL_SLOTS; ++j) {
-          if (ck[j] == b) ck[j] = 0ull;
-          cbest = ck[j] > cbest ? ck[j] : cbest;
-        }
-      }
+      vsel_retire(ck, cbest, b);
     }
     if (tid < gn) s_slot[s_tiles[g0 + tid]] = -1;
     __syncthreads();
   }
   // ---- B5. the ordered list
-  if (tid < k2) {
-    const unsigned long long b = s_top[tid];
-    float val = -INFINITY;
-    int idx = 0x7fffffff;
-    if (b != 0ull) {
-      unsigned u = (unsigned)(b >> 32);
-      u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-      val = __uint_as_float(u);
-      idx = (int)(0xffffffffu - (unsigned)(b & 0xffffffffu));
-    }
-    pval[(size_t)row * VS_K2MAX + tid] = val;
-    pidx[(size_t)row * VS_K2MAX + tid] = idx;
-  }
+  if (tid < k2) vsel_write(s_top[tid], pval, pidx, (size_t)row * VS_K2MAX + tid);
 }
 
 hipError_t launch_vocab_select(const VocabSelectArgs& a, hipStream_t stream) {
@@ -831,8 +744,8 @@ hipError_t launch_vocab_select(const VocabSelectArgs& a, hipStream_t stream) {
 }
 
 // ----------------------------------------------------------------- beam step (per sentence)
-// One workgroup (256 threads) per sentence.  Merges the chunk partials of each live row,
-// forms the 2*beam best (row, token) continuations and applies the fairseq2 EOS rules.
+// One workgroup (256 threads) per sentence.  Takes the ordered top-k2 list and the normaliser vocab_select left for each
+// live row, forms the 2*beam best (row, token) continuations and applies the fairseq2 EOS rules.
 struct BeamState {
   int32_t* tok;        // [R] token fed at the current position
   float* cum;          // [R] cumulative log-prob
@@ -856,7 +769,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
                                                         int ldl, int f16_tm, const float* __restrict__ pmax,
                                                         const float* __restrict__ psum,
                                                         const float* __restrict__ pval,
-                                                        const int* __restrict__ pidx, int nchunks,
+                                                        const int* __restrict__ pidx,
                                                         int beam, int k2, int pos, int prompt_len,
                                                         int forced_tok, int max_len, float inv_temp,
                                                         float len_penalty, int normalize, int eos_idx,
@@ -886,17 +799,10 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
     return;
   }
   const int na = st.nactive[s];
-  // (1) log-sum-exp of every live row
-  for (int r = wv; r < na; r += 4) {
-    const size_t o = (size_t)(base + r) * nchunks;
-    float m = -INFINITY;
-    for (int c = lane; c < nchunks; c += 64) m = fmaxf(m, pmax[o + c]);
-    m = wave_max(m);
-    float sum = 0.f;
-    for (int c = lane; c < nchunks; c += 64) sum += psum[o + c] * __expf(pmax[o + c] - m);
-    sum = wave_sum(sum);
-    if (lane == 0) s_lse[r] = m + __logf(sum);
-  }
+  // (1) log-sum-exp of every live row: pmax + log(psum) of the ONE normaliser entry vocab_select leaves per row.  (The
+  // chunk-partial merge this replaces gave the same bits for one entry: the wave maximum over one lane's pmax and 63
+  // -inf is pmax, the lane's term is psum * __expf(pmax - pmax) = psum * 1, and the wave sum adds 63 zeros to it.)
+  if (tid < na) s_lse[tid] = pmax[base + tid] + __logf(psum[base + tid]);
   __syncthreads();
 
   const bool forced_prompt = step_nr < prompt_len;
@@ -925,7 +831,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
         int order[8];
         for (int r = 0; r < na; ++r) order[r] = r;
         for (int a = 1; a < na; ++a)
-          for (int b = a; b > 0 && cand_better(c_val[order[b]], order[b], c_val[order[b - 1]], order[b - 1]); --b) {
+          for (int b = a; b > 0 && better(c_val[order[b]], order[b], c_val[order[b - 1]], order[b - 1]); --b) {
             const int t = order[b];
             order[b] = order[b - 1];
             order[b - 1] = t;
@@ -951,51 +857,14 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
       }
     }
   } else {
-    // (2) per live row: best k2 tokens over its chunk partials (value desc, token asc).
-    // One wave per row; its <= 1024 partial candidates sit in registers (16 per lane).
+    // (2) per live row: the selection's ordered top-k2 list as cumulative log-probs.  One wave per row.
     for (int r = wv; r < na; r += 4) {
-      const size_t o = (size_t)(base + r) * nchunks * VS_K2MAX;
-      if (nchunks == 1) {  // the tile-statistics selection already leaves ONE ordered list per row: nothing to merge
-        if (lane < k2) {
-          const float v = pval[o + lane];
-          c_val[r * VS_K2MAX + lane] = v == -INFINITY ? -INFINITY : st.cum[base + r] + v - s_lse[r];
-          c_tok[r * VS_K2MAX + lane] = pidx[o + lane];
-          c_row[r * VS_K2MAX + lane] = base + r;
-        }
-        continue;
-      }
-      const int total = nchunks * k2;
-      float cv[16];
-      int ci[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int e = q * 64 + lane;
-        cv[q] = -INFINITY;
-        ci[q] = 0x7fffffff;
-        if (e < total) {
-          const int off = (e / k2) * VS_K2MAX + (e % k2);
-          cv[q] = pval[o + off];
-          ci[q] = pidx[o + off];
-        }
-      }
-      for (int round = 0; round < k2; ++round) {
-        float bv = -INFINITY;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          if (cand_better(cv[q], ci[q], bv, bi)) {
-            bv = cv[q];
-            bi = ci[q];
-          }
-        wave_best2(bv, bi);
-        if (lane == 0) {
-          c_val[r * VS_K2MAX + round] = bv == -INFINITY ? -INFINITY : st.cum[base + r] + bv - s_lse[r];
-          c_tok[r * VS_K2MAX + round] = bi;
-          c_row[r * VS_K2MAX + round] = base + r;
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          if (ci[q] == bi) cv[q] = -INFINITY;
+      const size_t o = (size_t)(base + r) * VS_K2MAX;
+      if (lane < k2) {
+        const float v = pval[o + lane];
+        c_val[r * VS_K2MAX + lane] = v == -INFINITY ? -INFINITY : st.cum[base + r] + v - s_lse[r];
+        c_tok[r * VS_K2MAX + lane] = pidx[o + lane];
+        c_row[r * VS_K2MAX + lane] = base + r;
       }
     }
     __syncthreads();
@@ -1133,14 +1002,9 @@ __global__ __launch_bounds__(256) void beam_step_kernel(BeamState st, const floa
 hipError_t launch_beam_step(const BeamStepArgs& a, hipStream_t stream) {
   BeamState st{a.tok, a.cum, a.nactive, a.done, a.ndone, a.parent, a.new_tok, a.new_cum,
                a.hist, a.fin_tok, a.fin_len, a.fin_score, a.fin_count, a.margins};
-  if (a.table.tok)
-    hipLaunchKernelGGL(beam_step_kernel<true>, dim3(a.n), dim3(256), 0, stream, st, a.logits, a.ldl, a.logits_f16_tm, a.pmax,
-                       a.psum, a.pval, a.pidx, a.nchunks, a.beam, a.k2, a.pos, a.prompt_len, a.forced_tok,
-                       a.max_len, a.inv_temp, a.len_penalty, a.normalize, a.eos_idx, a.hist_stride, a.table);
-  else
-    hipLaunchKernelGGL(beam_step_kernel<false>, dim3(a.n), dim3(256), 0, stream, st, a.logits, a.ldl, a.logits_f16_tm, a.pmax,
-                       a.psum, a.pval, a.pidx, a.nchunks, a.beam, a.k2, a.pos, a.prompt_len, a.forced_tok,
-                       a.max_len, a.inv_temp, a.len_penalty, a.normalize, a.eos_idx, a.hist_stride, a.table);
+  hipLaunchKernelGGL(a.table.tok ? beam_step_kernel<true> : beam_step_kernel<false>, dim3(a.n), dim3(256), 0, stream, st,
+                     a.logits, a.ldl, a.logits_f16_tm, a.pmax, a.psum, a.pval, a.pidx, a.beam, a.k2, a.pos, a.prompt_len,
+                     a.forced_tok, a.max_len, a.inv_temp, a.len_penalty, a.normalize, a.eos_idx, a.hist_stride, a.table);
   return hipGetLastError();
 }
 

@@ -600,7 +600,7 @@ int generate_chain(smi_text_decoder* D, DecWork& S, const void* emb, int emb_dty
     a.margins = margins;
     a.logits = S.logits.as<float>(); a.ldl = (int)D->vocab_pad; a.logits_f16_tm = logits_f16;
     a.pmax = S.pmax.as<float>(); a.psum = S.psum.as<float>(); a.pval = S.pval.as<float>(); a.pidx = S.pidx.as<int>();
-    a.nchunks = 1; a.n = n; a.beam = beam; a.k2 = k2; a.pos = pos; a.prompt_len = plan.scalar_prompt_len();
+    a.n = n; a.beam = beam; a.k2 = k2; a.pos = pos; a.prompt_len = plan.scalar_prompt_len();
     a.forced_tok = mode.forced_tok; a.max_len = max_len;
     if (!plan.one_prompt()) {
       // prompts of one length: past them the sentences differ in nothing the beam step reads -- the one-prompt launch

@@ -444,8 +444,8 @@ __global__ __launch_bounds__(IVF_TB) void ivf_i8_scan_lists_kernel(const int8_t*
     for (int j = 0; j < k_out; ++j) {
       const unsigned long long key = lists[tid * KT + j];
       const bool have = key != XS_EMPTY;
-      ps[o + j] = have ? xs_unord((uint32_t)(key >> 32)) : -INFINITY;
-      pi[o + j] = have ? (int)(0xffffffffu - (uint32_t)key) : -1;
+      ps[o + j] = have ? xs_key_value(key) : -INFINITY;
+      pi[o + j] = have ? xs_key_index(key) : -1;
     }
   }
 }
@@ -736,8 +736,7 @@ __global__ __launch_bounds__(IVF_TB) void ivf_selfjoin_kernel(const f16* __restr
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const bool precedes = idr[r] >= 0 && oid >= 0 && (prr[r] > op || (prr[r] == op && idr[r] < oid));
-              const unsigned long long key =
-                  ((unsigned long long)xs_ord(acc[ai][bi][r]) << 32) | (uint32_t)(0xffffffffu - (uint32_t)idr[r]);
+              const unsigned long long key = xs_key(acc[ai][bi][r], idr[r]);
               if (precedes && key > best[bi]) best[bi] = key;
             }
           }
@@ -769,8 +768,8 @@ __global__ __launch_bounds__(IVF_TB) void ivf_selfjoin_kernel(const f16* __restr
     const int id = ids[u0 + tid];
     const unsigned long long key = sbest[tid];
     if (id >= 0 && id < n && key != XS_EMPTY) {  // (an id outside [0, n) breaks the contract: nothing is written through it)
-      max_sim[id] = xs_unord((uint32_t)(key >> 32));
-      nearest[id] = (int)(0xffffffffu - (uint32_t)key);
+      max_sim[id] = xs_key_value(key);
+      nearest[id] = xs_key_index(key);
     }
   }
 }

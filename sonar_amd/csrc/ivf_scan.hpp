@@ -209,8 +209,8 @@ __device__ __forceinline__ void ivf_lists_readout(const unsigned long long* list
     for (int j = 0; j < k_out; ++j) {
       const unsigned long long key = lists[tid * KT + j];
       const bool have = key != XS_EMPTY;
-      ps[o + j] = have ? xs_unord((uint32_t)(key >> 32)) : -INFINITY;
-      pi[o + j] = have ? (int)(0xffffffffu - (uint32_t)key) : -1;
+      ps[o + j] = have ? xs_key_value(key) : -INFINITY;
+      pi[o + j] = have ? xs_key_index(key) : -1;
     }
   }
 }

@@ -277,7 +277,8 @@ struct BeamStepArgs {
   float* margins;  // [n][2] or null
   const float* logits; int ldl;
   int logits_f16_tm;  // logits are fp16 in the tile-major layout (K = ldl) instead of fp32 [rows][ldl]
-  const float* pmax; const float* psum; const float* pval; const int* pidx; int nchunks;
+  // what launch_vocab_select left: one normaliser entry [rows] and one ordered top-k2 list [rows][kVocabScanK2Max] per row
+  const float* pmax; const float* psum; const float* pval; const int* pidx;
   int n, beam, k2, pos, prompt_len, forced_tok, max_len;
   float inv_temp, len_penalty; int normalize, eos_idx, hist_stride;
   PromptTableDev table;  // table.tok != nullptr: prompt_len / forced_tok / max_len are the sentence's own

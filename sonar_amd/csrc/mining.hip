@@ -22,6 +22,7 @@
 #include "api_common.hpp"
 #include "bucket.hpp"
 #include "common.hpp"
+#include "topk_order.hpp"
 
 namespace smi {
 
@@ -63,9 +64,7 @@ __device__ __forceinline__ bool over_threshold(const MineArgs& a, float v) { ret
 // earlier in the walk.  Never 0, so 0 marks an empty slot.
 __device__ __forceinline__ unsigned long long cand_key(float v, int64_t c) {
   if (v == 0.f) v = 0.f;
-  unsigned u = __float_as_uint(v);
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((unsigned long long)u << 32) | (unsigned)~(unsigned)c;
+  return xs_key(v, (int)c);
 }
 
 enum : unsigned char { DEAD = 0, LIVE = 1, ACCEPTED = 2 };

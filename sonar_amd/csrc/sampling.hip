@@ -18,6 +18,7 @@
 #include "common.hpp"
 #include "kernels.hpp"
 #include "step_proc.hpp"
+#include "topk_order.hpp"
 
 using namespace smi;
 using namespace smi_host;
@@ -31,10 +32,6 @@ constexpr int SMP_WAVES = SMP_THREADS / 64;
 constexpr int SMP_BUCKETS = 2048;
 constexpr int SMP_PER_THREAD = SMP_BUCKETS / SMP_THREADS;  // 2
 
-__device__ __forceinline__ uint32_t smp_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
 // Q40 mass of a scaled logit t = l / T - M (t <= 0)
 __device__ __forceinline__ u64 smp_mass(float t) {
   return (u64)(__builtin_amdgcn_exp2f(t * 1.4426950408889634f) * 1099511627776.0f);
@@ -172,11 +169,11 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs
     unk_dead = w1 <= 0;
     w_unk = unk_dead ? 0 : (u64)w1;
     // rank: the logit whose softmax mass is w_unk (approximate; only its ORDER among the other tokens is used)
-    key_unk = smp_key((__logf((float)w_unk * (1.0f / 1099511627776.0f)) + M) / it);
+    key_unk = xs_ord((__logf((float)w_unk * (1.0f / 1099511627776.0f)) + M) / it);
     __syncthreads();
   }
   auto mass_of = [&](int idx, float v) { return (pen && idx == a.unk_idx) ? w_unk : smp_mass(v * it - M); };
-  auto key_of = [&](int idx, float v) { return (pen && idx == a.unk_idx) ? key_unk : smp_key(v); };
+  auto key_of = [&](int idx, float v) { return (pen && idx == a.unk_idx) ? key_unk : xs_ord(v); };
 
   if (a.forced_tok >= 0) {  // prompt forcing / forced EOS: only the step score is needed
     u64 zloc = 0, zf;
@@ -346,13 +343,13 @@ __global__ __launch_bounds__(SMP_THREADS) void sample_rows_kernel(SampleRowsArgs
     u64 bestk = 0;
     for_each([&](int idx, float v) {
       if (!kept(idx, v)) return;
-      const u64 k = ((u64)key_of(idx, v) << 32) | (u64)(0xffffffffu - (uint32_t)idx);
+      const u64 k = xs_key_ord(key_of(idx, v), idx);
       bestk = k > bestk ? k : bestk;
     });
     if (bestk) atomicMax(&s_bc[3], bestk);
     __syncthreads();
     if (tid == 0) {  // s_bc[3] != 0: the kept set is never empty (its first token always fits)
-      const int t = (int)(0xffffffffu - (uint32_t)(s_bc[3] & 0xffffffffu));
+      const int t = xs_key_index(s_bc[3]);
       a.out_tok[row] = t;
       a.out_logp[row] = (lg[t] * it - M) - logz;
     }

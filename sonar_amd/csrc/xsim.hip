@@ -365,8 +365,8 @@ __global__ __launch_bounds__(G2_THREADS) void xsim_tile256_kernel(const f16* __r
 #pragma unroll
       for (int j = 0; j < K; ++j) {
         const unsigned long long key = lists[tid * K + j];
-        ps[o + j] = xs_unord((uint32_t)(key >> 32));
-        pi[o + j] = (int)(0xffffffffu - (uint32_t)key);
+        ps[o + j] = xs_key_value(key);
+        pi[o + j] = xs_key_index(key);
       }
     }
   } else {

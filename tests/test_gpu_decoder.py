@@ -68,6 +68,25 @@ def _logit_range(OD, params, ocfg, emb, prompt):
     return (lg.max() - lg.min()).item()
 
 
+def _check_best_hypothesis(OD, params, ocfg, e, prompt, beam, toks, lens, scores, margins):
+    """What holds for one sentence's result whatever the oracle's near-ties: returns the best hypothesis and the oracle's
+    normalised score of it."""
+    L = int(lens[0])
+    seq = toks[0, :L].tolist()
+    assert L >= 2 and seq[-1] == 3 and 0 not in seq and all(t >= 0 for t in seq)
+    assert (toks[0, L:] == -1).all()
+    # the engine's best hypothesis is a valid hypothesis with the score the oracle assigns to it
+    total = _rescored(OD, params, ocfg, e, prompt, seq)
+    norm = total / (len(prompt) + L - 1)
+    assert abs(norm - scores[0].item()) <= 5e-3, (norm, scores[0].item())
+    # hypotheses come out best first
+    k = int((lens > 0).sum())
+    assert k == beam
+    assert all(scores[j] >= scores[j + 1] - 1e-6 for j in range(k - 1))
+    assert margins[0] >= 0 and (beam == 1 or margins[1] >= 0)
+    return seq, norm
+
+
 @pytest.mark.parametrize("beam", [1, 3, 5])
 def test_beam_search_vs_oracle(setup, beam):
     from tests.neartie import check_engine_margin, oracle_excuses
@@ -87,19 +106,7 @@ def test_beam_search_vs_oracle(setup, beam):
     eps = EPS_REL * _logit_range(OD, params, ocfg, emb, prompt)
     excused = []
     for i in range(n):
-        L = int(lens[i, 0])
-        seq = toks[i, 0, :L].tolist()
-        assert L >= 2 and seq[-1] == 3 and 0 not in seq and all(t >= 0 for t in seq)
-        assert (toks[i, 0, L:] == -1).all()
-        # the engine's best hypothesis is a valid hypothesis with the score the oracle assigns to it
-        total = _rescored(OD, params, ocfg, emb[i], prompt, seq)
-        norm = total / (len(prompt) + L - 1)
-        assert abs(norm - scores[i, 0].item()) <= 5e-3, (norm, scores[i, 0].item())
-        # hypotheses come out best first
-        k = int((lens[i] > 0).sum())
-        assert k == beam
-        assert all(scores[i, j] >= scores[i, j + 1] - 1e-6 for j in range(k - 1))
-        assert margins[i, 0] >= 0 and (beam == 1 or margins[i, 1] >= 0)
+        seq, norm = _check_best_hypothesis(OD, params, ocfg, emb[i], prompt, beam, toks[i], lens[i], scores[i], margins[i])
         check_engine_margin(margins[i], om[i], eps, f"beam {beam}, sentence {i}")
         if seq != ref[i][0].seq.tolist():
             step_gap, final_gap = om[i][:2]
@@ -113,6 +120,21 @@ def test_beam_search_vs_oracle(setup, beam):
           f"measured near-ties (< {eps:.2e}): {excused}")
     # near-ties are rare events, not a blanket excuse
     assert len(excused) <= max(1, n // 8), excused
+
+
+def test_beam_8_fills_both_candidates_of_every_lane(setup):
+    """Beam 8 is k2 = 16 (the selection's largest list) and 8 x 16 = 128 row candidates: exactly two per lane of the wave
+    that ranks them.  No token comparison with the oracle: at beam 8 the oracle's own margins put nearly every sentence
+    under its epsilon, so only what holds regardless of near-ties is asserted."""
+    OD, ocfg, params, eng = setup
+    beam, n, prompt = 8, 24, [3, 700]
+    emb = torch.randn(n, ocfg.model_dim, generator=torch.Generator().manual_seed(10 + beam)) * 0.3
+    toks, lens, scores = eng.generate(emb.cuda(), prompt, beam_size=beam, max_gen_len=(0, 13))
+    margins = eng.last_margins(n).cpu()
+    torch.cuda.synchronize()
+    toks, lens, scores = toks.cpu(), lens.cpu(), scores.cpu()
+    for i in range(n):
+        _check_best_hypothesis(OD, params, ocfg, emb[i], prompt, beam, toks[i], lens[i], scores[i], margins[i])
 
 
 def test_greedy_margins_are_the_top2_logprob_gaps(setup):

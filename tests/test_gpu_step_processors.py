@@ -123,7 +123,7 @@ def _adversarial(vocab, rows, L, k2, seed):
             lg[r, t1 * 256 + 9] = 51.0
             ids = [t1 * 256 + 9]
         elif kind == 5 and vocab <= L + k2:   # all but < k2 tokens banned
-            keep = set(torch.randperm(vocab, generator=g)[:k2 - 2].tolist())
+            keep = set(torch.randperm(vocab, generator=g)[:max(k2 - 2, 0)].tolist())
             ids = [i for i in range(vocab) if i not in keep]
         else:             # random bans + the argmax
             ids = torch.randint(0, vocab, (40,), generator=g).tolist() + [int(row.argmax())]
@@ -144,13 +144,17 @@ def _expected(lg, vocab, banlists, k2, pad_idx=0):
     return vals, idx
 
 
-@pytest.mark.parametrize("vocab", [1000, 256206])
+# vocab 1000 is 4 tiles, fewer than any k2 > 3: the tile rounds end early, and an odd k2 leaves the arg-max's double buffer on
+# either parity when they do; 16 is the largest k2 (VS_K2MAX); k2 = 1 leaves the "all but < k2" row with no candidate at all.
+@pytest.mark.parametrize("vocab,k2", [pytest.param(1000, 10, id="1000"), pytest.param(256206, 10, id="256206"),
+                                      pytest.param(1000, 1, id="1000-k2_1"), pytest.param(1000, 7, id="1000-k2_7"),
+                                      pytest.param(1000, 16, id="1000-k2_16"), pytest.param(256206, 16, id="256206-k2_16")])
 @pytest.mark.parametrize("f16_tm", [0, 1])
-def test_banned_selection_equals_masked_topk(vocab, f16_tm):
+def test_banned_selection_equals_masked_topk(vocab, k2, f16_tm):
     from sonar_amd import _lib
 
     lib = _lib.load()
-    rows, k2, L = 256, 10, 1000 if vocab == 1000 else 64
+    rows, L = 256, 1000 if vocab == 1000 else 64
     lg, hist, banlists = _adversarial(vocab, rows, L, k2, seed=vocab + f16_tm)
     for r, ids in enumerate(banlists):
         assert set(hist[r].tolist()) == set(ids)
