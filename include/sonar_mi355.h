@@ -754,6 +754,38 @@ int smi_ivf_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* pro
                    const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Range search over the IVF-Flat lists (restated in tests/ivf_range_ref.py): EVERY row of the lists a query
+ * probes whose score is at least the query's threshold, where smi_ivf_search returns the k <= 8 best.  How many rows that
+ * is is known only after the lists were walked, so there are two calls and the caller sizes the output between them.
+ *
+ * Inputs of both calls: qn, nq, d, probes, nprobe in [1, 8], list_rows, list_ids, list_offsets, K are smi_ivf_search's (an
+ *   entry of probes outside [0, K) names no list; a list named twice contributes its rows twice); threshold = device fp32
+ *   [nq].  Pair q * nprobe + p is query q against the list probes[q, p].
+ * Hit: row i of a probed list is a hit of query q iff score(q, i) >= threshold[q], an fp32 compare: a NaN threshold gives
+ *   no hit, -inf every row of the probed lists.  The score has the bits smi_ivf_search returns for the same two rows; pad
+ *   slots are never hits.
+ * smi_range_search_count: inverts the probe table into the workspace and writes pair_counts int32 [nq * nprobe], the hits
+ *   of every pair (0 for a pair that names no list).  No atomics on global memory: the counts do not depend on the run.
+ * smi_range_search_emit: pair_base = device int64 [nq * nprobe + 1], the exclusive prefix sum of pair_counts, its last entry
+ *   = total (also passed by value); score fp32 [total] / idx int32 [total]: the hits of pair j are the entries pair_base[j]
+ *   .. pair_base[j + 1], in no specified order, so those of query q are pair_base[q * nprobe] .. pair_base[(q + 1) * nprobe].
+ *   NEEDS THE WORKSPACE AS smi_range_search_count LEFT IT, and the same inputs: it does not invert the probe table again.
+ *   A pair that has more hits than its segment holds (thresholds lowered between the calls) loses the surplus: nothing is
+ *   written outside [pair_base[j], min(pair_base[j + 1], total)).  With fewer hits the segment's tail is not written.
+ * Neither call reads anything back or allocates; one work unit is smi_ivf_search's (no bit of the result depends on its size).
+ * workspace: device memory, 16-byte aligned, smi_range_search_ws_bytes bytes.
+ * Refused before any launch: a null pointer, nq / K < 1, nprobe outside [1, 8], a small or misaligned workspace, total < 0
+ *   (SMI_ERR_INVALID_ARG); d not a multiple of 64, nq, K or nq * nprobe above 2^31 - 256 (SMI_ERR_UNSUPPORTED).  For these
+ *   shapes the sizing function returns 0. */
+int64_t smi_range_search_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t d);
+int smi_range_search_count(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                           const float* threshold, const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets,
+                           int64_t K, int32_t* pair_counts, void* workspace, int64_t workspace_bytes, void* stream);
+int smi_range_search_emit(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                          const float* threshold, const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets,
+                          int64_t K, const int64_t* pair_base, int64_t total, float* score, int32_t* idx, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* Semantic de-duplication over the IVF-Flat lists (restated in tests/dedup_ref.py): the per-list self-join of
  * SemDeDup (Abbas et al. 2023).  For every row, the best score against the rows of its own list that PRECEDE it in a keep
  * order; a caller thresholds it (keep = !(max_sim > threshold), strict) and may sweep the threshold over one stored result.

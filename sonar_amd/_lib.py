@@ -372,6 +372,10 @@ SYMBOLS = {
     "smi_ivf_build": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "smi_ivf_search_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
     "smi_ivf_search": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "smi_range_search_ws_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "smi_range_search_count": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "smi_range_search_emit": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64,
+                                        _vp]),
     "smi_ivf_dedup_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32]),
     "smi_ivf_dedup": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "smi_ivf_i8_encode": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),

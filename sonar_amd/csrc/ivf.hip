@@ -11,8 +11,10 @@
 // ascending (the bits of a score depend on the two rows alone), that are folded into one running top-k per pair, the LDS key
 // lists of xsim.hip.  A pair's list is written to the partial array [nprobe][nq][k]; smi_xsim_merge_topk's kernel merges
 // the nprobe parts.  No atomics on results.  The unit itself -- lookup, pair table, slice loop, fold, read-out -- is
-// ivf_scan.hpp (read its comment first).  Four kernels here walk lists that way:
+// ivf_scan.hpp (read its comment first).  Five kernels here walk lists that way:
 //   ivf_scan_lists_kernel      fp16 rows (3.18): ivf_scan.hpp's functions; fetches both operands from memory;
+//   ivf_range_lists_kernel     the same rows, unit and loop with a threshold fold (3.23): every row at or above a per-query
+//                              threshold, counted in one walk and written in a second;
 //   ivf_pq_scan_lists_kernel   product-quantised rows (3.21): the same functions, so a score has the flat scan's bits BY
 //                              CONSTRUCTION; the list operand is decoded from the codebooks in the fetch; its RES
 //                              instantiation (3.22: rows encoded as residuals against their list's centroid) adds one fp32
@@ -201,6 +203,100 @@ hipError_t with_key_list(int k, Launch launch) {
   if (k == 2) return launch(std::integral_constant<int, 2>{});
   if (k <= 4) return launch(std::integral_constant<int, 4>{});
   return launch(std::integral_constant<int, 8>{});
+}
+
+// ---------------------------------------------------------------- range search
+// ivf_scan_lists_kernel with another fold and another ending: every row of the probed lists whose score is at least the
+// query's threshold, not the k best.  The unit, the pair table, the fetch and the slice loop are the flat scan's, so a hit's
+// score has the bits smi_ivf_search returns for the same two rows.  How many rows a pair hits is not known before the walk, so
+// the lists are walked twice: !EMIT counts (a lane's unit rows are fixed for the whole walk: it counts in registers and adds
+// to the LDS counter of the row once, at the end; a pair belongs to one unit, which writes pair_counts[pair]: no global
+// atomics), EMIT writes hit number c of a pair (c: a fetch-add on the row's LDS counter, any order) to base[pair] + c --
+// only below base[pair + 1] and below `total`, so thresholds that were lowered between the two calls lose hits and never
+// write outside the pair's segment.  LDS behind the slice buffers: pair numbers [B], thresholds [B], counters [B].
+template <int B>
+constexpr int ivf_range_lds() { return 2 * 2 * B * IVF_SLICE + 3 * B * 4; }
+
+template <int B, bool EMIT>
+__global__ __launch_bounds__(IVF_TB) void ivf_range_lists_kernel(const f16* __restrict__ qn, int d, int nprobe,
+                                                                 const float* __restrict__ threshold,
+                                                                 const f16* __restrict__ rows, const int32_t* __restrict__ ids,
+                                                                 const int32_t* __restrict__ off, int K,
+                                                                 const int32_t* __restrict__ poff,
+                                                                 const int32_t* __restrict__ ubase,
+                                                                 const int32_t* __restrict__ pairs,
+                                                                 int32_t* __restrict__ pair_counts,
+                                                                 const int64_t* __restrict__ base, int64_t total,
+                                                                 float* __restrict__ score, int32_t* __restrict__ idx) {
+  constexpr int NR = B / 32;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int* spair = (int*)(smem + 4 * B * IVF_SLICE);
+  float* sthr = (float*)(spair + B);
+  unsigned* scnt = (unsigned*)(sthr + B);
+  const int tid = threadIdx.x, b = blockIdx.x;
+  if (b >= ubase[K]) return;
+  const int l = ivf_unit_list(ubase, K, b);
+  const int p0 = poff[l] + (b - ubase[l]) * B;
+  const int npair = min(B, poff[l + 1] - p0);
+  const int s_begin = off[l], s_end = off[l + 1];
+  ivf_range_init<B>(spair, sthr, scnt, pairs, p0, npair, nprobe, threshold);
+
+  const int nk = d / IVF_BK, cc = tid & 7;
+  const f16* qsrc[NR];  // this thread's query rows of a slice
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int pr = spair[(tid >> 3) + 32 * j];
+    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
+  }
+  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {  // ivf_scan_lists_kernel's, which keeps its own text
+    const int tile = it / nk, ks = it - tile * nk;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
+      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
+      lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  // what this lane keeps of its unit rows wc * B / 2 + bi * 16 + l15: the threshold, and the hits counted so far or the
+  // pair's segment [lo, hi) of the output
+  const int row0 = (tid >> 6 & 1) * (B / 2) + (tid & 15);
+  float thr[NR];
+  int hits[NR];
+  int64_t lo[NR], hi[NR];
+#pragma unroll
+  for (int bi = 0; bi < NR; ++bi) {
+    const int pr = spair[row0 + bi * 16];
+    thr[bi] = sthr[row0 + bi * 16];
+    hits[bi] = 0;
+    lo[bi] = EMIT && pr >= 0 ? base[pr] : 0;
+    hi[bi] = EMIT && pr >= 0 ? min(base[pr + 1], total) : 0;
+  }
+  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
+    ivf_range_fold<B>(ids, slot0, thr, acc, [&](int bi, unsigned mask, const int(&idr)[4]) {
+      if constexpr (EMIT) {
+        int64_t pos = lo[bi] + atomicAdd(&scnt[row0 + bi * 16], (unsigned)__popc(mask));
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+          if (mask >> r & 1u) {
+            if (pos < hi[bi]) {
+              score[pos] = acc[bi][r];
+              idx[pos] = idr[r];
+            }
+            ++pos;
+          }
+      } else {
+        hits[bi] += __popc(mask);
+      }
+    });
+  };
+  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
+  if constexpr (!EMIT) {
+#pragma unroll
+    for (int bi = 0; bi < NR; ++bi)
+      if (hits[bi]) atomicAdd(&scnt[row0 + bi * 16], (unsigned)hits[bi]);
+    __syncthreads();
+    if (tid < npair) pair_counts[spair[tid]] = (int32_t)scnt[tid];
+  }
 }
 
 // ================================================================ int8 scalar-quantised lists
@@ -497,7 +593,7 @@ int check_search_args(int64_t nq, int32_t d, int64_t K, int32_t nprobe, int32_t 
 }
 
 // invert the probe table: the (query, probe slot) pairs q * nprobe + p bucketed by the list they name, the units' prefix
-// sum for `unit` pairs per unit, and the partial lists pre-filled
+// sum for `unit` pairs per unit, and (k > 0) the partial lists pre-filled
 hipError_t invert_probes(const int32_t* probes, int64_t P, int64_t K, int k, int unit, const SearchWs& w, hipStream_t st) {
   if (hipError_t e = hipMemsetAsync(w.pcount, 0, (size_t)K * 4, st); e != hipSuccess) return e;
   const dim3 block(IVF_TB), pair_grid = grid_for(P, IVF_TB);
@@ -505,7 +601,7 @@ hipError_t invert_probes(const int32_t* probes, int64_t P, int64_t K, int k, int
   hipLaunchKernelGGL(ivf_scan_kernel, dim3(1), block, 0, st, w.pcount, (int)K, 1, unit, w.poff, w.cursor, w.ubase);
   hipLaunchKernelGGL(bucket_scatter_kernel<IVF_TB>, pair_grid, block, 0, st, probes, (int)P, (int)K, w.cursor, w.pairs,
                      (int32_t*)nullptr);
-  hipLaunchKernelGGL(ivf_fill_kernel, grid_for(P * k, IVF_TB), block, 0, st, w.ps, w.pi, P * k);
+  if (k > 0) hipLaunchKernelGGL(ivf_fill_kernel, grid_for(P * k, IVF_TB), block, 0, st, w.ps, w.pi, P * k);
   return hipGetLastError();
 }
 
@@ -556,6 +652,47 @@ int search_entry(bool null_arg, int64_t nq, int32_t d, const int32_t* probes, in
 }
 constexpr auto no_refusals = [] { return (int)SMI_OK; };
 constexpr auto no_prepare = [](const SearchWs&, hipStream_t) {};
+
+// The two passes of the range search, stated once.  Its workspace is the search's with k = 0: the inverted
+// probe table and no partial lists.  `emit` (pair_base non-null) trusts the workspace as `count` left it.
+int check_range_shape(int64_t nq, int32_t d, int64_t K, int32_t nprobe) {
+  if (const int rc = check_shape(nq, "nq", d, K, "list")) return rc;
+  if (nprobe < 1 || nprobe > 8) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 8]", nprobe);
+  if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
+  return SMI_OK;
+}
+int range_entry(bool null_arg, const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                const float* threshold, const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
+                int32_t* pair_counts, const int64_t* pair_base, int64_t total, float* score, int32_t* idx, void* ws,
+                int64_t ws_bytes, void* stream) {
+  if (null_arg || !qn || !probes || !threshold || !list_rows || !list_ids || !list_offsets)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_range_shape(nq, d, K, nprobe)) return rc;
+  const int64_t P = nq * nprobe;
+  const SearchWs w(ws, nq, K, nprobe, 0);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_range_search_ws_bytes(nq, K, nprobe, d)")) return rc;
+  if (pair_base && total < 0) return fail(SMI_ERR_INVALID_ARG, "total=%lld: the last entry of pair_base", (long long)total);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const int unit = unit_pairs(P, K);  // the search's rule, a function of the shapes: both passes walk the same units
+  const int64_t units = units_bound(P, K, unit);
+  const auto walk = [&](auto emit) {
+    constexpr bool EMIT = decltype(emit)::value;
+    return launch_units<ivf_range_lists_kernel<IVF_BM, EMIT>, ivf_range_lists_kernel<IVF_BIG, EMIT>>(
+        unit, units, ivf_range_lds<IVF_BM>(), ivf_range_lds<IVF_BIG>(), st, (const f16*)qn, d, nprobe, threshold,
+        (const f16*)list_rows, list_ids, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
+        (const int32_t*)w.pairs, pair_counts, pair_base, total, score, idx);
+  };
+  if (pair_base) {
+    HIP_TRY(walk(std::true_type{}));
+    return SMI_OK;
+  }
+  // a pair that names no list is in no unit: its count reads 0
+  HIP_TRY(hipMemsetAsync(pair_counts, 0, (size_t)P * 4, st));
+  HIP_TRY(invert_probes(probes, P, K, 0, unit, w, st));
+  HIP_TRY(walk(std::false_type{}));
+  return SMI_OK;
+}
 
 // A one-kernel entry over n rows of d fp16 (the encoders, the decoder, the residuals), stated once: null pointers, the
 // alignment of the output `name` (out16; null where the kernel does not need it), check_shape, the kind's own refusals, the
@@ -1333,6 +1470,27 @@ int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes,
             unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
             (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi);
       });
+}
+
+// ---------------------------------------------------------------- range search
+int64_t smi_range_search_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t d) {
+  const KeepLastError keep;
+  return check_range_shape(nq, d, K, nprobe) ? 0 : (int64_t)SearchWs(nullptr, nq, K, nprobe, 0).bytes();
+}
+
+int smi_range_search_count(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const float* threshold,
+                           const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
+                           int32_t* pair_counts, void* ws, int64_t ws_bytes, void* stream) {
+  return range_entry(!pair_counts, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets, K, pair_counts,
+                     nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+int smi_range_search_emit(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const float* threshold,
+                          const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
+                          const int64_t* pair_base, int64_t total, float* score, int32_t* idx, void* ws, int64_t ws_bytes,
+                          void* stream) {
+  return range_entry(!pair_base || !score || !idx, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets, K,
+                     nullptr, pair_base, total, score, idx, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------- semantic de-duplication

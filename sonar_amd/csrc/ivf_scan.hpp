@@ -215,4 +215,46 @@ __device__ __forceinline__ void ivf_lists_readout(const unsigned long long* list
   }
 }
 
+// ---------------------------------------------------------------- the range scan
+// LDS of a range unit behind the slice buffers, in place of the key lists: per unit row its pair number [B] (-1: no pair),
+// the threshold of the pair's query [B] (fp32) and one 32-bit counter [B] (zero).  A barrier follows.
+template <int B>
+__device__ __forceinline__ void ivf_range_init(int* spair, float* sthr, unsigned* scnt, const int32_t* __restrict__ pairs, int p0,
+                                               int npair, int nprobe, const float* __restrict__ threshold) {
+  const int tid = threadIdx.x;
+  if (tid < B) {
+    const int pr = tid < npair ? pairs[p0 + tid] : -1;
+    spair[tid] = pr;
+    sthr[tid] = pr >= 0 ? threshold[pr / nprobe] : __builtin_nanf("");
+    scnt[tid] = 0u;
+  }
+  __syncthreads();
+}
+
+// The fold of a range scan: sum acc[bi][r] of the slot with id id(r) against unit row wc * B / 2 + bi * 16 + l15 is a hit iff
+// the unit row holds a pair, the slot holds a row (id >= 0: a pad slot is a zero row that scores 0.0 and must not hit at a
+// threshold <= 0) and acc >= the pair's threshold, an fp32 compare (a NaN threshold gives no hit).  thr[bi]: the threshold of
+// this lane's unit row bi, NaN where the row holds no pair -- that is how `pr < npair` is stated here.  Most tiles hold no hit:
+// the ids are loaded and the slots are looked at one by one only where some lane of the wave has a sum at its threshold.
+// hit(bi, mask, idr): the slots r of `mask` (bits 0 .. 3), whose ids are idr[r], are hits of unit row bi.
+template <int B, class Acc, class Hit>
+__device__ __forceinline__ void ivf_range_fold(const int32_t* __restrict__ ids, int slot0, const float (&thr)[B / 32],
+                                               const Acc (&acc)[B / 32], Hit hit) {
+  bool some = false;
+#pragma unroll
+  for (int bi = 0; bi < B / 32; ++bi)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) some |= acc[bi][r] >= thr[bi];
+  if (!__any(some)) return;  // wave-uniform
+  const int4 id4 = *(const int4*)(ids + slot0);
+  const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
+#pragma unroll
+  for (int bi = 0; bi < B / 32; ++bi) {
+    unsigned mask = 0u;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) mask |= (unsigned)(idr[r] >= 0 && acc[bi][r] >= thr[bi]) << r;
+    if (mask) hit(bi, mask, idr);
+  }
+}
+
 }  // namespace smi

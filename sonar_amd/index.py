@@ -20,6 +20,8 @@ re-orders them, which is what margin mining wants.  The quality was measured on 
 embeddings may have heavier-tailed rows, where a per-row scale loses more.
 
 `IVFFlatIndex.self_join` and `sonar_amd.dedup` are the de-duplication over the flat lists.
+`IVFFlatIndex.range_search` returns every row of the probed lists at or above a per-query threshold, not the k <= 8 best
+(FAISS's `range_search`).
 
 `ProductQuantizer` and `IVFPQIndex` are the same index over product-quantised rows: d / dsub bytes per row,
 one byte per sub-quantiser of 256 codewords, 1/16 (dsub = 8) to 1/128 (dsub = 64) of the fp16 rows.  The scan decodes a
@@ -32,12 +34,12 @@ FAISS's `by_residual`): the same bytes, a lower quantisation error, and one fp32
 the list's centroid, which the probe has already computed (tests/ivf_pq_residual_ref.py).
 
 Not here: an OPQ rotation, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, nprobe or
-k above 8, de-duplication over quantised lists, incremental add and removal, 64-bit ids, splitting of long lists, multi-GPU
-sharding.
+k above 8, de-duplication or range search over quantised lists, incremental add and removal, 64-bit ids, splitting of long
+lists, multi-GPU sharding.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Tuple, Union
+from typing import Dict, NamedTuple, Optional, Tuple, Union
 
 import torch
 
@@ -179,6 +181,94 @@ def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids
     _check_search_args(qn, probes, k)
     _check_lists_dim(qn, rows)
     return _search("smi_ivf_search", "smi_ivf_search_workspace_bytes", qn, probes, k, (), (rows.data_ptr(),), ids, offsets)
+
+
+class RangeResult(NamedTuple):
+    """What a range search returns, in FAISS's layout: the hits of query q are the entries lims[q] .. lims[q + 1] of scores
+    and ids.  lims int64 [nq + 1], scores fp32 [total], ids int32 [total], all on the device."""
+
+    lims: torch.Tensor
+    scores: torch.Tensor
+    ids: torch.Tensor
+
+    @property
+    def counts(self) -> torch.Tensor:
+        """int64 [nq]: the hits of every query."""
+        return self.lims[1:] - self.lims[:-1]
+
+
+def _check_thresholds(threshold, nq: int, like: torch.Tensor) -> torch.Tensor:
+    """The thresholds of a range search as a device fp32 [nq] tensor: a Python float (NaN refused) for every query, or such
+    a tensor."""
+    if isinstance(threshold, (int, float)) and not isinstance(threshold, bool):
+        if threshold != threshold:
+            raise ValueError("threshold is NaN: no score compares to it")
+        return torch.full((nq,), float(threshold), dtype=torch.float32, device=like.device)
+    _check_device_tensor(threshold, "threshold")
+    if threshold.dtype != torch.float32 or tuple(threshold.shape) != (nq,):
+        raise ValueError(f"threshold must be a float or fp32 [{nq}], got {threshold.dtype} {list(threshold.shape)}")
+    return threshold.contiguous()
+
+
+def _check_max_total(max_total) -> None:
+    if max_total is not None and (isinstance(max_total, bool) or not isinstance(max_total, int) or max_total < 0):
+        raise ValueError(f"max_total = {max_total!r}: None or a non-negative integer")
+
+
+def range_search_lists(qn: torch.Tensor, probes: torch.Tensor, thresholds: Union[float, torch.Tensor], rows: torch.Tensor,
+                       ids: torch.Tensor, offsets: torch.Tensor, sort: bool = True,
+                       max_total: Optional[int] = None) -> RangeResult:
+    """smi_range_search_count / smi_range_search_emit: every row of the lists probes (device int32 [nq, 1..8]) names whose
+    score against query q is >= thresholds[q] (device fp32 [nq], or one Python float for all; an fp32 compare, so NaN hits
+    nothing and -inf everything probed), for the first nq rows of qn against the storage `build_lists` returned.  A score
+    has the bits `search_lists` returns for the same two rows.
+
+    Two walks of the lists, count and emit, with `torch.cumsum` of the pair counts between them and ONE READ-BACK, of the
+    total, to size the output: the call synchronises with the host and cannot be captured in a graph.  max_total: raise
+    (ValueError, the total named) instead of allocating more than this many hits.
+
+    sort: every query's segment in `xsim.topk`'s total order, score descending and ties to the lower id (three stable
+    `torch.sort`s); the result then has the same bits whatever the batch or the run.  sort=False leaves the order inside a
+    segment unspecified (it differs from run to run)."""
+    _check_search_args(qn, probes, 1)
+    _check_lists_dim(qn, rows)
+    _check_max_total(max_total)
+    (nq, nprobe), d, n_lists, dev = probes.shape, qn.shape[1], offsets.shape[0] - 1, qn.device
+    thresholds = _check_thresholds(thresholds, nq, qn)
+    lib = _lib.load()
+    ws_bytes = int(lib.smi_range_search_ws_bytes(nq, n_lists, nprobe, d))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    pair_counts = torch.empty((nq * nprobe,), dtype=torch.int32, device=dev)
+    probes = probes.contiguous()
+    inputs = (qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, thresholds.data_ptr(), rows.data_ptr(), ids.data_ptr(),
+              offsets.data_ptr(), n_lists)
+    with torch.cuda.device(dev):
+        _lib.check(lib.smi_range_search_count(*inputs, pair_counts.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+        base = torch.zeros((nq * nprobe + 1,), dtype=torch.int64, device=dev)
+        torch.cumsum(pair_counts, 0, dtype=torch.int64, out=base[1:])
+        total = int(base[-1].item())  # the read-back
+        if max_total is not None and total > max_total:
+            raise ValueError(f"the range search has {total} hits, max_total = {max_total}")
+        score = torch.empty((total,), dtype=torch.float32, device=dev)
+        idx = torch.empty((total,), dtype=torch.int32, device=dev)
+        if total:
+            _lib.check(lib.smi_range_search_emit(*inputs, base.data_ptr(), total, score.data_ptr(), idx.data_ptr(), ws.data_ptr(),
+                                                 ws_bytes, _lib.current_stream_ptr()))
+    lims = base[::nprobe].contiguous()
+    if sort and total:
+        score, idx = _sort_segments(lims, score, idx)
+    return RangeResult(lims, score, idx)
+
+
+def _sort_segments(lims: torch.Tensor, score: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Every segment lims[q] .. lims[q + 1] of (score, idx) in the total order: stable sorts by id, by score descending, by
+    query, the last key first (`refine_candidates`' way)."""
+    nq, total = lims.shape[0] - 1, score.shape[0]
+    query = torch.repeat_interleave(torch.arange(nq, device=lims.device), lims[1:] - lims[:-1], output_size=total)
+    order = torch.sort(idx, stable=True)[1]
+    order = order[torch.sort(score[order], descending=True, stable=True)[1]]
+    order = order[torch.sort(query[order], stable=True)[1]]
+    return score[order], idx[order]
 
 
 def encode_rows_int8(xn: torch.Tensor, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -613,11 +703,14 @@ class _IVFIndex:
     def self_join(self, *args, **kwargs):
         raise TypeError(f"self_join and semdedup need the fp16 lists of an IVFFlatIndex; {self._HOLDS}")
 
-    def _check_search(self, q, k, nprobe, probes) -> int:
-        """The argument checks of `search`; returns nq."""
+    def range_search(self, *args, **kwargs):
+        raise TypeError(f"range_search needs the fp16 lists of an IVFFlatIndex; {self._HOLDS}")
+
+    def _check_search(self, q, k, nprobe, probes, what: str = "search") -> int:
+        """The argument checks of `search` (and of `range_search`, with k = 1); returns nq."""
         _check_small(k, "k")
         _check_small(nprobe, "nprobe")
-        self._need_add("search")
+        self._need_add(what)
         _check_matrix(q, "q")
         if q.shape[1] != self._d:
             raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
@@ -708,6 +801,28 @@ class IVFFlatIndex(_IVFIndex):
         probes: None (the nprobe nearest lists by the quantiser) or device int32 [nq, 1..8]; an entry outside [0, K) names
         no list.  A row of probes that names a list twice may return that list's rows twice."""
         return self._checked_search(q, k, nprobe, probes)
+
+    def range_search(self, q: torch.Tensor, threshold: Union[float, torch.Tensor], nprobe: int = 1,
+                     probes: Optional[torch.Tensor] = None, sort: bool = True, max_total: Optional[int] = None) -> RangeResult:
+        """EVERY row of the probed lists whose score is >= threshold, for every row of q (fp16 / fp32 [nq, d] on the device):
+        `RangeResult(lims int64 [nq + 1], scores fp32 [total], ids int32 [total])`, FAISS's layout -- the hits of query i are
+        the entries lims[i] .. lims[i + 1].  A score has the bits `search` returns for the same two rows.
+
+        threshold: a Python float for every query (NaN is refused), or device fp32 [nq], one per query (an fp32 compare:
+        a NaN entry hits nothing, -inf every row of the probed lists).  probes: as for `search`; a list named twice returns
+        its hits twice.  sort: every segment best first, in `search`'s total order (score descending, ties to the lower
+        id); with sort=False the order inside a segment is unspecified.  max_total: raise ValueError, the total named, where
+        more hits than this would be allocated.
+
+        The lists are walked twice, to count and to write, and the total is READ BACK once in between to size the result:
+        the call synchronises with the host and is not capturable."""
+        nq = self._check_search(q, 1, nprobe, probes, "range_search")
+        _check_max_total(max_total)
+        threshold = _check_thresholds(threshold, nq, q)
+        qn = normalize_rows(q)
+        if probes is None:
+            probes = topk_normalized(qn, nq, self._c16, self._k, nprobe)[1]
+        return range_search_lists(qn, probes, threshold, self._rows, self._ids, self._offsets, sort, max_total)
 
     def self_join(self, priority: Optional[torch.Tensor] = None, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """`dedup.self_join` over this index's own lists: (max_sim fp32 [n], nearest int32 [n]), for every
