@@ -786,6 +786,60 @@ int smi_range_search_emit(const void* qn_f16, int64_t nq, int32_t d, const int32
                           int64_t K, const int64_t* pair_base, int64_t total, float* score, int32_t* idx, void* workspace,
                           int64_t workspace_bytes, void* stream);
 
+/* Filtered search over the IVF lists (restated in tests/ivf_filter_ref.py): a candidate (query q, row i)
+ * counts iff the row is VISIBLE (a row mask shared by all queries of a call) and the pair passes the KEY PREDICATE: every row
+ * has a signed int32 key, every query one, and `row key REL query key` holds for the relation of the call.  Everything else is
+ * the contract of the unfiltered entry: a query's filtered result is, bit for bit, the unfiltered result over lists that hold
+ * only the rows this query may see.
+ *
+ * smi_slot_filter: the filter in slot order, once per filter and reusable: slot_ids_out int32 [slots] = list_ids[slot] where
+ *   the row is visible (row_mask null, or row_mask[id] != 0; one byte per row), else -1; slot_keys_out int32 [slots] =
+ *   row_keys[id], 0 where the slot holds no visible row.  row_keys / row_mask = device [n], either may be null, not both;
+ *   row_keys and slot_keys_out go together.  An id outside [0, n) is treated as masked out and never read.  slots = the
+ *   slots of the storage (list_ids' length); slots from list_offsets[K] on get id -1.  Both outputs 16-byte aligned.
+ *   Enqueued; nothing is read back.  THE MASK NEEDS NO OTHER ENTRY: every scan skips a slot whose id is -1, so the unfiltered
+ *   entries run on slot_ids_out in place of list_ids.
+ * smi_*_keyed: the entry of the same name with the key predicate.  The arguments of the twin (list_ids may be slot_ids_out),
+ *   then slot_keys = device int32 [slots], 16-byte aligned (the key of a slot whose id is -1 is never looked at), query_keys =
+ *   device int32 [nq], accept = the relation as a 3-bit mask over the outcome of ONE signed compare of the row's key with the
+ *   query's: bit 0 less, bit 1 equal, bit 2 greater -- == 2, != 5, < 1, <= 3, > 4, >= 6; 0 lets nothing pass, 7 everything
+ *   (the twin's result, bit for bit).  Workspace: the twin's sizing function.  smi_range_search_emit_keyed needs the workspace
+ *   as smi_range_search_count_keyed left it and the same keys.
+ * Refused before any launch: what the twin refuses, in its order and words; behind its null-pointer check a null slot_keys or
+ *   query_keys, slot_keys not 16-byte aligned, accept outside [0, 7] (SMI_ERR_INVALID_ARG). */
+int smi_slot_filter(const int32_t* list_ids, const int32_t* list_offsets, int64_t K, const int32_t* row_keys,
+                    const uint8_t* row_mask, int64_t n, int32_t* slot_ids_out, int32_t* slot_keys_out, int64_t slots,
+                    void* stream);
+int smi_ivf_search_keyed(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                         const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
+                         int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, void* stream,
+                         const int32_t* slot_keys, const int32_t* query_keys, int32_t accept);
+int smi_ivf_i8_search_keyed(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                            const void* list_codes, const float* list_scales, const int32_t* list_ids,
+                            const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* workspace,
+                            int64_t workspace_bytes, void* stream, const int32_t* slot_keys, const int32_t* query_keys,
+                            int32_t accept);
+int smi_ivf_pq_search_keyed(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                            const void* list_codes, int32_t dsub, const void* codebooks_f16, const int32_t* list_ids,
+                            const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* workspace,
+                            int64_t workspace_bytes, void* stream, const int32_t* slot_keys, const int32_t* query_keys,
+                            int32_t accept);
+int smi_ivf_pq_search_residual_keyed(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, const float* coarse,
+                                     int32_t nprobe, const void* list_codes, int32_t dsub, const void* codebooks_f16,
+                                     const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx,
+                                     float* score, void* workspace, int64_t workspace_bytes, void* stream,
+                                     const int32_t* slot_keys, const int32_t* query_keys, int32_t accept);
+int smi_range_search_count_keyed(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                                 const float* threshold, const void* list_rows, const int32_t* list_ids,
+                                 const int32_t* list_offsets, int64_t K, int32_t* pair_counts, void* workspace,
+                                 int64_t workspace_bytes, void* stream, const int32_t* slot_keys, const int32_t* query_keys,
+                                 int32_t accept);
+int smi_range_search_emit_keyed(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                                const float* threshold, const void* list_rows, const int32_t* list_ids,
+                                const int32_t* list_offsets, int64_t K, const int64_t* pair_base, int64_t total, float* score,
+                                int32_t* idx, void* workspace, int64_t workspace_bytes, void* stream, const int32_t* slot_keys,
+                                const int32_t* query_keys, int32_t accept);
+
 /* Semantic de-duplication over the IVF-Flat lists (restated in tests/dedup_ref.py): the per-list self-join of
  * SemDeDup (Abbas et al. 2023).  For every row, the best score against the rows of its own list that PRECEDE it in a keep
  * order; a caller thresholds it (keep = !(max_sim > threshold), strict) and may sweep the threshold over one stored result.

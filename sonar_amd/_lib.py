@@ -376,6 +376,20 @@ SYMBOLS = {
     "smi_range_search_count": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
     "smi_range_search_emit": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64,
                                         _vp]),
+    # filtered search: the slot filter, and every scan entry again with (slot_keys, query_keys, accept) behind
+    "smi_slot_filter": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "smi_ivf_search_keyed": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp,
+                                       _vp, _vp, _i32]),
+    "smi_ivf_i8_search_keyed": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp,
+                                          _vp, _vp, _i32]),
+    "smi_ivf_pq_search_keyed": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64,
+                                          _vp, _vp, _vp, _i32]),
+    "smi_ivf_pq_search_residual_keyed": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp,
+                                                   _vp, _vp, _i64, _vp, _vp, _vp, _i32]),
+    "smi_range_search_count_keyed": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp,
+                                               _vp, _vp, _i32]),
+    "smi_range_search_emit_keyed": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
+                                              _i64, _vp, _vp, _vp, _i32]),
     "smi_ivf_dedup_workspace_bytes": (_i64, [_i64, _i64, _i64, _i32]),
     "smi_ivf_dedup": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "smi_ivf_i8_encode": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),

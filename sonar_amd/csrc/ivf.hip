@@ -24,6 +24,8 @@
 // The last two spell the same loop out in their own text (keep it equal to ivf_slice_walk's): as instances of the
 // function the 128-row self-join waited for the prefetched slice in front of its MFMAs, and the int8 scan measured
 // 0.2-0.4 % slower in two cells of one round of two (profiles/isa_identity_ivf.txt).
+// The first four answer a search and each has a KEYED TWIN for the filtered search (3.24: a per-query key predicate in the
+// fold; a row mask needs no kernel, only ids of -1): their text is csrc/ivf_list_kernels.hpp, included twice below.
 // The bucketing, the unit rule, the merge and the host halves are shared by calls: an entry gives the skeletons below
 // (build_entry, search_entry, rows_entry) its own checks and its gather or scan launch.  The quantisers (int8 rows; PQ
 // encode, train, decode) and the gathers that encode follow their scans.
@@ -104,48 +106,7 @@ __global__ __launch_bounds__(IVF_TB) void ivf_fill_kernel(float* __restrict__ ps
 template <int B>
 constexpr int ivf_scan_lds(int KT) { return 2 * 2 * B * IVF_SLICE + B * KT * 8 + B * 4; }
 
-template <int KT, int B>
-__global__ __launch_bounds__(IVF_TB) void ivf_scan_lists_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
-                                                                const f16* __restrict__ rows, const int32_t* __restrict__ ids,
-                                                                const int32_t* __restrict__ off, int K,
-                                                                const int32_t* __restrict__ poff,
-                                                                const int32_t* __restrict__ ubase,
-                                                                const int32_t* __restrict__ pairs, int k_out,
-                                                                float* __restrict__ ps, int32_t* __restrict__ pi) {
-  constexpr int NR = B / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* lists = (unsigned long long*)(smem + 4 * B * IVF_SLICE);
-  int* spair = (int*)(lists + B * KT);
-  const int tid = threadIdx.x, b = blockIdx.x;
-  if (b >= ubase[K]) return;
-  const int l = ivf_unit_list(ubase, K, b);
-  const int p0 = poff[l] + (b - ubase[l]) * B;
-  const int npair = min(B, poff[l + 1] - p0);
-  const int s_begin = off[l], s_end = off[l + 1];
-  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [](int) {});
-
-  const int nk = d / IVF_BK, cc = tid & 7;
-  const f16* qsrc[NR];  // this thread's query rows of a slice
-#pragma unroll
-  for (int j = 0; j < NR; ++j) {
-    const int pr = spair[(tid >> 3) + 32 * j];
-    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
-  }
-  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {
-    const int tile = it / nk, ks = it - tile * nk;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
-      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
-      lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
-    ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, IvfSumIsScore{});
-  };
-  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
-  ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
-}
+// (the kernel, ivf_scan_lists_kernel<KT, B>, and its keyed twin: ivf_list_kernels.hpp, included below)
 
 int64_t slots_bound(int64_t n, int64_t K) {
   const int64_t m = std::min(n, K);
@@ -196,6 +157,22 @@ hipError_t launch_units(int unit, int64_t units, int lds_small, int lds_big, hip
   if (unit == IVF_BIG) return launch_with_lds<Big>(dim3((unsigned)units), IVF_TB, lds_big, st, args...);
   return launch_with_lds<Small>(dim3((unsigned)units), IVF_TB, lds_small, st, args...);
 }
+// the same for a kernel with a keyed twin: with keys, the twin, the keys behind the kernel's own arguments and
+// the query keys [unit] behind its LDS
+template <auto Small, auto Big, auto KeyedSmall, auto KeyedBig, typename... Args>
+hipError_t launch_units_keyed(const IvfKeys* keys, int unit, int64_t units, int lds_small, int lds_big, hipStream_t st,
+                              Args... args) {
+  if (!keys) return launch_units<Small, Big>(unit, units, lds_small, lds_big, st, args...);
+  return launch_units<KeyedSmall, KeyedBig>(unit, units, lds_small + IVF_BM * 4, lds_big + IVF_BIG * 4, st, args..., *keys);
+}
+// the refusals of a keyed entry's own arguments: they follow the null checks of its twin
+int check_keys(const IvfKeys& keys) {
+  if (!keys.slot_keys || !keys.query_keys) return fail(SMI_ERR_INVALID_ARG, "null slot_keys or query_keys");
+  if ((uintptr_t)keys.slot_keys % 16) return fail(SMI_ERR_INVALID_ARG, "slot_keys must be 16-byte aligned");
+  if (keys.accept < 0 || keys.accept > 7)
+    return fail(SMI_ERR_INVALID_ARG, "accept=%d must be in [0, 7]: bit 0 less, bit 1 equal, bit 2 greater", keys.accept);
+  return SMI_OK;
+}
 // launch(KT as a std::integral_constant), KT = the key-list length of a search for k results: 1, 2, 4 or 8
 template <class Launch>
 hipError_t with_key_list(int k, Launch launch) {
@@ -216,88 +193,7 @@ hipError_t with_key_list(int k, Launch launch) {
 // write outside the pair's segment.  LDS behind the slice buffers: pair numbers [B], thresholds [B], counters [B].
 template <int B>
 constexpr int ivf_range_lds() { return 2 * 2 * B * IVF_SLICE + 3 * B * 4; }
-
-template <int B, bool EMIT>
-__global__ __launch_bounds__(IVF_TB) void ivf_range_lists_kernel(const f16* __restrict__ qn, int d, int nprobe,
-                                                                 const float* __restrict__ threshold,
-                                                                 const f16* __restrict__ rows, const int32_t* __restrict__ ids,
-                                                                 const int32_t* __restrict__ off, int K,
-                                                                 const int32_t* __restrict__ poff,
-                                                                 const int32_t* __restrict__ ubase,
-                                                                 const int32_t* __restrict__ pairs,
-                                                                 int32_t* __restrict__ pair_counts,
-                                                                 const int64_t* __restrict__ base, int64_t total,
-                                                                 float* __restrict__ score, int32_t* __restrict__ idx) {
-  constexpr int NR = B / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int* spair = (int*)(smem + 4 * B * IVF_SLICE);
-  float* sthr = (float*)(spair + B);
-  unsigned* scnt = (unsigned*)(sthr + B);
-  const int tid = threadIdx.x, b = blockIdx.x;
-  if (b >= ubase[K]) return;
-  const int l = ivf_unit_list(ubase, K, b);
-  const int p0 = poff[l] + (b - ubase[l]) * B;
-  const int npair = min(B, poff[l + 1] - p0);
-  const int s_begin = off[l], s_end = off[l + 1];
-  ivf_range_init<B>(spair, sthr, scnt, pairs, p0, npair, nprobe, threshold);
-
-  const int nk = d / IVF_BK, cc = tid & 7;
-  const f16* qsrc[NR];  // this thread's query rows of a slice
-#pragma unroll
-  for (int j = 0; j < NR; ++j) {
-    const int pr = spair[(tid >> 3) + 32 * j];
-    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
-  }
-  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {  // ivf_scan_lists_kernel's, which keeps its own text
-    const int tile = it / nk, ks = it - tile * nk;
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
-      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
-      lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  // what this lane keeps of its unit rows wc * B / 2 + bi * 16 + l15: the threshold, and the hits counted so far or the
-  // pair's segment [lo, hi) of the output
-  const int row0 = (tid >> 6 & 1) * (B / 2) + (tid & 15);
-  float thr[NR];
-  int hits[NR];
-  int64_t lo[NR], hi[NR];
-#pragma unroll
-  for (int bi = 0; bi < NR; ++bi) {
-    const int pr = spair[row0 + bi * 16];
-    thr[bi] = sthr[row0 + bi * 16];
-    hits[bi] = 0;
-    lo[bi] = EMIT && pr >= 0 ? base[pr] : 0;
-    hi[bi] = EMIT && pr >= 0 ? min(base[pr + 1], total) : 0;
-  }
-  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
-    ivf_range_fold<B>(ids, slot0, thr, acc, [&](int bi, unsigned mask, const int(&idr)[4]) {
-      if constexpr (EMIT) {
-        int64_t pos = lo[bi] + atomicAdd(&scnt[row0 + bi * 16], (unsigned)__popc(mask));
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-          if (mask >> r & 1u) {
-            if (pos < hi[bi]) {
-              score[pos] = acc[bi][r];
-              idx[pos] = idr[r];
-            }
-            ++pos;
-          }
-      } else {
-        hits[bi] += __popc(mask);
-      }
-    });
-  };
-  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
-  if constexpr (!EMIT) {
-#pragma unroll
-    for (int bi = 0; bi < NR; ++bi)
-      if (hits[bi]) atomicAdd(&scnt[row0 + bi * 16], (unsigned)hits[bi]);
-    __syncthreads();
-    if (tid < npair) pair_counts[spair[tid]] = (int32_t)scnt[tid];
-  }
-}
+// (the kernel, ivf_range_lists_kernel<B, EMIT>, and its keyed twin: ivf_list_kernels.hpp, included below)
 
 // ================================================================ int8 scalar-quantised lists
 // The same lists with one signed byte per element and one fp32 scale per row.  The scan is ivf_scan.hpp's decomposition
@@ -382,169 +278,34 @@ static_assert(IVF_I8_BK % 64 == 0 && (IVF_I8_CH & (IVF_I8_CH - 1)) == 0 && IVF_B
 template <int B>
 constexpr int ivf_i8_scan_lds(int KT) { return 2 * 2 * B * IVF_I8_BK + B * KT * 8 + 2 * B * 4; }
 
-template <int KT, int B>
-__global__ __launch_bounds__(IVF_TB) void ivf_i8_scan_lists_kernel(const int8_t* __restrict__ qc, const float* __restrict__ qscale,
-                                                                   int d, int nq, int nprobe, const int8_t* __restrict__ rows,
-                                                                   const float* __restrict__ scales,
-                                                                   const int32_t* __restrict__ ids,
-                                                                   const int32_t* __restrict__ off, int K,
-                                                                   const int32_t* __restrict__ poff,
-                                                                   const int32_t* __restrict__ ubase,
-                                                                   const int32_t* __restrict__ pairs, int k_out,
-                                                                   float* __restrict__ ps, int32_t* __restrict__ pi) {
-  constexpr int OPB = B * IVF_I8_BK;  // bytes of one operand's K slice
-  constexpr int NR = B / 32;          // 16-row blocks of a wave per operand
-  constexpr int NL = B / IVF_I8_RP;   // rows of an operand slice a thread loads
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* lists = (unsigned long long*)(smem + 4 * OPB);
-  int* spair = (int*)(smem + 4 * OPB + B * KT * 8);
-  float* sqs = (float*)(spair + B);  // the pairs' query scales
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 1, wc = wave & 1;
-  const int b = blockIdx.x;
-  if (b >= ubase[K]) return;
-  int lo = 0, hi = K;  // the last l in [0, K) with ubase[l] <= b; ubase[l + 1] > b follows from b < ubase[K]
-  while (hi - lo > 1) {
-    const int mid = (lo + hi) >> 1;
-    if (ubase[mid] <= b) lo = mid;
-    else hi = mid;
-  }
-  const int l = lo;
-  const int p0 = poff[l] + (b - ubase[l]) * B;
-  const int npair = min(B, poff[l + 1] - p0);
-  const int s_begin = off[l], s_end = off[l + 1];
-  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [&](int pr) { sqs[tid] = pr >= 0 ? qscale[pr / nprobe] : 0.f; });
+// (the kernel, ivf_i8_scan_lists_kernel<KT, B>, and its keyed twin: ivf_list_kernels.hpp)
 
-  const int nk = (d + IVF_I8_BK - 1) / IVF_I8_BK;
-  const int ntiles = (s_end - s_begin + B - 1) / B;
-  const int T = ntiles * nk;
-
-  // this thread's rows of a slice, and where its chunk lands in LDS
-  const int cc = tid % IVF_I8_CH;
-  const int8_t* qsrc[NL];
-  int lds_off[NL];
-#pragma unroll
-  for (int j = 0; j < NL; ++j) {
-    const int r = tid / IVF_I8_CH + IVF_I8_RP * j;
-    const int pr = spair[r];
-    qsrc[j] = pr >= 0 ? qc + (size_t)(pr / nprobe) * d + cc * 16 : nullptr;
-    lds_off[j] = r * IVF_I8_BK + ((cc ^ (r & (IVF_I8_CH - 1))) << 4);
-  }
-  u32x4 qv[NL], lv[NL];
-  auto load = [&](int it) {
-    const int tile = it / nk, ks = it - tile * nk;
-    const bool in_row = ks * IVF_I8_BK + cc * 16 < d;  // false for chunks 4 .. 7 of the last slice when d % 128 == 64
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      const int slot = s_begin + tile * B + tid / IVF_I8_CH + IVF_I8_RP * j;
-      qv[j] = qsrc[j] && in_row ? *(const u32x4*)(qsrc[j] + ks * IVF_I8_BK) : u32x4{0u, 0u, 0u, 0u};
-      lv[j] = slot < s_end && in_row ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_I8_BK + cc * 16)
-                                     : u32x4{0u, 0u, 0u, 0u};
-    }
-  };
-  auto store = [&](int buf) {
-#pragma unroll
-    for (int j = 0; j < NL; ++j) {
-      *(u32x4*)(smem + buf * 2 * OPB + lds_off[j]) = qv[j];
-      *(u32x4*)(smem + buf * 2 * OPB + OPB + lds_off[j]) = lv[j];
-    }
-  };
-
-  i32x4 acc[NR][NR];  // [slot block ai][pair block bi]
-#pragma unroll
-  for (int ai = 0; ai < NR; ++ai)
-#pragma unroll
-    for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = i32x4{0, 0, 0, 0};
-  // 16-pair blocks of this wave that hold a pair at all (wave-uniform)
-  const int nb_live = min(NR, max(0, (npair - wc * (B / 2) + 15) / 16));
-
-  if (T > 0) {
-    load(0);
-    store(0);
-  }
-  __syncthreads();
-  int ks = 0, tile = 0;
-  for (int it = 0; it < T; ++it) {
-    const int buf = it & 1;
-    if (it + 1 < T) load(it + 1);
-    // 16-slot blocks of this wave below the end of the list (the lists are padded to 16 slots): wave-uniform
-    const int slot_w = s_begin + tile * B + wr * (B / 2);
-    const int na_live = min(NR, max(0, (s_end - slot_w) / 16));
-    if (na_live > 0 && nb_live > 0) {
-      const char* qs = smem + buf * 2 * OPB;
-      const char* ls = qs + OPB;
-#pragma unroll
-      for (int kk = 0; kk < IVF_I8_BK / 64; ++kk) {
-        const int ch = kk * 4 + kg;
-        i32x4 fa[NR], fb[NR];
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai) {
-          const int ra = wr * (B / 2) + ai * 16 + l15;
-          fa[ai] = *(const i32x4*)(ls + ra * IVF_I8_BK + ((ch ^ (ra & (IVF_I8_CH - 1))) << 4));
-        }
-#pragma unroll
-        for (int bi = 0; bi < NR; ++bi) {
-          const int rb = wc * (B / 2) + bi * 16 + l15;
-          fb[bi] = *(const i32x4*)(qs + rb * IVF_I8_BK + ((ch ^ (rb & (IVF_I8_CH - 1))) << 4));
-        }
-#pragma unroll
-        for (int ai = 0; ai < NR; ++ai)
-          if (ai < na_live) {
-#pragma unroll
-            for (int bi = 0; bi < NR; ++bi)
-              if (bi < nb_live) acc[ai][bi] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ai], fb[bi], acc[ai][bi], 0, 0, 0);
-          }
-      }
-    }
-    if (it + 1 < T) store(buf ^ 1);
-    if (++ks == nk) {
-      // the tile is finished: fold this wave's scores into the pairs' lists, as ivf_scan_lists_kernel does
-#pragma unroll
-      for (int ai = 0; ai < NR; ++ai) {
-        if (ai < na_live) {
-          const int slot0 = slot_w + ai * 16 + 4 * kg;  // < s_end, 16-byte aligned: off % 16 == 0
-          const int4 id4 = *(const int4*)(ids + slot0);
-          const float4 sc4 = *(const float4*)(scales + slot0);
-          const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
-          const float scr[4] = {sc4.x, sc4.y, sc4.z, sc4.w};
-#pragma unroll
-          for (int bi = 0; bi < NR; ++bi) {
-            const int pr = wc * (B / 2) + bi * 16 + l15;
-            if (pr < npair) {
-              unsigned long long* lst = lists + pr * KT;
-              const float sq = sqs[pr];
-              const float thr = xs_unord(
-                  (uint32_t)(__hip_atomic_load(lst + KT - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32));
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const float v = __fmul_rn(__fmul_rn((float)acc[ai][bi][r], scr[r]), sq);
-                if (idr[r] >= 0 && v >= thr) xs_insert<KT>(lst, v, idr[r]);
-              }
-            }
-          }
-        }
-#pragma unroll
-        for (int bi = 0; bi < NR; ++bi) acc[ai][bi] = i32x4{0, 0, 0, 0};
-      }
-      ks = 0;
-      ++tile;
-    }
-    __syncthreads();
-  }
-
-  // (the last barrier of the loop, or the one before it when the list is empty, made the lists final)
-  if (tid < npair) {
-    const int pr = spair[tid];
-    const int q = pr / nprobe, p = pr - q * nprobe;
-    const size_t o = ((size_t)p * nq + q) * k_out;
-    for (int j = 0; j < k_out; ++j) {
-      const unsigned long long key = lists[tid * KT + j];
-      const bool have = key != XS_EMPTY;
-      ps[o + j] = have ? xs_key_value(key) : -INFINITY;
-      pi[o + j] = have ? xs_key_index(key) : -1;
-    }
-  }
-}
+// ---------------------------------------------------------------- the list-walking kernels, each with its keyed twin
+// The four kernels that answer a search are stated once, in ivf_list_kernels.hpp, and compiled twice: as
+// they always were (IvfNoKeys: IvfKeyTest keeps nothing and lets every candidate pass, and the kernel is instruction for
+// instruction what it was: profiles/isa_identity_filter.txt), and as <name>_keyed with one more argument, IvfKeys,
+// the query keys [B] behind everything else in LDS and the key predicate in the fold.  Two inclusions, not one function
+// called by two kernels: as the instance of a shared function the unkeyed kernels came out with other registers and another
+// order of their argument loads, whichever way the arguments were passed.
+constexpr int PQ_CW = 256;  // codewords of every sub-quantiser of the product-quantised lists (3.21): a code is one byte
+#define IVF_TWIN(name) name
+#define IVF_TWIN_PARAM
+#define IVF_TWIN_KEYS IvfNoKeys
+#define IVF_TWIN_KEYARGS IvfNoKeys{}
+#include "ivf_list_kernels.hpp"
+#undef IVF_TWIN
+#undef IVF_TWIN_PARAM
+#undef IVF_TWIN_KEYS
+#undef IVF_TWIN_KEYARGS
+#define IVF_TWIN(name) name##_keyed
+#define IVF_TWIN_PARAM , IvfKeys keyargs
+#define IVF_TWIN_KEYS IvfKeys
+#define IVF_TWIN_KEYARGS keyargs
+#include "ivf_list_kernels.hpp"
+#undef IVF_TWIN
+#undef IVF_TWIN_PARAM
+#undef IVF_TWIN_KEYS
+#undef IVF_TWIN_KEYARGS
 
 int i8_check_dim(int32_t d) {
   if (d > IVF_I8_MAX_DIM)
@@ -627,12 +388,15 @@ int build_entry(bool null_arg, const int32_t* labels, int64_t n, int32_t d, int6
 // i8_dim of its workspace, its own refusals (they follow check_search_args), prepare(w, st), what it enqueues in front of
 // the inversion (the int8 search encodes its queries there), and scan(kt, unit, units, w, st), the launch of its
 // list-walking kernel with key lists of decltype(kt)::value over units for every pair count the table can have: those from
-// ubase[K] on find nothing to do.
+// ubase[K] on find nothing to do.  keys: null, or the key predicate of a keyed entry, which the kind's scan
+// hands to launch_units_keyed.
 template <class Refusals, class Prepare, class Scan>
-int search_entry(bool null_arg, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const int32_t* list_ids,
+int search_entry(bool null_arg, const IvfKeys* keys, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const int32_t* list_ids,
                  const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
                  void* stream, const char* sizing, int i8_dim, Refusals refusals, Prepare prepare, Scan scan) {
   if (null_arg || !probes || !list_ids || !list_offsets || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (keys)
+    if (const int rc = check_keys(*keys)) return rc;
   if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
   if (const int rc = refusals()) return rc;
   const int64_t P = nq * nprobe;
@@ -661,12 +425,14 @@ int check_range_shape(int64_t nq, int32_t d, int64_t K, int32_t nprobe) {
   if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
   return SMI_OK;
 }
-int range_entry(bool null_arg, const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+int range_entry(bool null_arg, const IvfKeys* keys, const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
                 const float* threshold, const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
                 int32_t* pair_counts, const int64_t* pair_base, int64_t total, float* score, int32_t* idx, void* ws,
                 int64_t ws_bytes, void* stream) {
   if (null_arg || !qn || !probes || !threshold || !list_rows || !list_ids || !list_offsets)
     return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (keys)
+    if (const int rc = check_keys(*keys)) return rc;
   if (const int rc = check_range_shape(nq, d, K, nprobe)) return rc;
   const int64_t P = nq * nprobe;
   const SearchWs w(ws, nq, K, nprobe, 0);
@@ -678,8 +444,9 @@ int range_entry(bool null_arg, const void* qn, int64_t nq, int32_t d, const int3
   const int64_t units = units_bound(P, K, unit);
   const auto walk = [&](auto emit) {
     constexpr bool EMIT = decltype(emit)::value;
-    return launch_units<ivf_range_lists_kernel<IVF_BM, EMIT>, ivf_range_lists_kernel<IVF_BIG, EMIT>>(
-        unit, units, ivf_range_lds<IVF_BM>(), ivf_range_lds<IVF_BIG>(), st, (const f16*)qn, d, nprobe, threshold,
+    return launch_units_keyed<ivf_range_lists_kernel<IVF_BM, EMIT>, ivf_range_lists_kernel<IVF_BIG, EMIT>,
+                              ivf_range_lists_kernel_keyed<IVF_BM, EMIT>, ivf_range_lists_kernel_keyed<IVF_BIG, EMIT>>(
+        keys, unit, units, ivf_range_lds<IVF_BM>(), ivf_range_lds<IVF_BIG>(), st, (const f16*)qn, d, nprobe, threshold,
         (const f16*)list_rows, list_ids, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
         (const int32_t*)w.pairs, pair_counts, pair_base, total, score, idx);
   };
@@ -737,6 +504,23 @@ __global__ __launch_bounds__(IVF_TB) void ivf_slot_priority_kernel(const int32_t
   if (slot >= off[K]) return;
   const int id = ids[slot];
   sprio[slot] = priority && id >= 0 && id < n ? priority[id] : 0.f;  // an id outside [0, n) breaks the contract: not read
+}
+
+// The row filter of a search, in slot order, once per filter: fid[slot] = ids[slot] where the row is visible
+// (mask null, or mask[id] != 0), else -1 -- the "effective id" array every scan runs on unchanged, since a slot whose id is
+// -1 never enters -- and skey[slot] (nullable) = keys[id].  One thread per slot of the storage: a pad slot and a slot from
+// off[K] on get id -1 and key 0; an id outside [0, n) of the given tensors is treated as masked out and never read.
+__global__ __launch_bounds__(IVF_TB) void ivf_slot_filter_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ off,
+                                                                 int K, const int32_t* __restrict__ keys,
+                                                                 const uint8_t* __restrict__ mask, int64_t n,
+                                                                 int64_t slots, int32_t* __restrict__ fid,
+                                                                 int32_t* __restrict__ skey) {
+  const int64_t slot = (int64_t)blockIdx.x * IVF_TB + threadIdx.x;
+  if (slot >= slots) return;
+  const int id = slot < off[K] ? ids[slot] : -1;
+  const bool seen = id >= 0 && id < n && (!mask || mask[id] != 0);
+  fid[slot] = seen ? id : -1;
+  if (skey) skey[slot] = seen && keys ? keys[id] : 0;
 }
 
 template <int B>
@@ -942,7 +726,6 @@ struct DedupWs : WsLayout {
 // called.  New: the product quantiser (encode, train, decode), the gather that encodes, and a scan whose fetch decodes a
 // tile's codes into the slice loop's LDS image once per tile and K slice: the loop is ivf_scan_lists_kernel's, so a score
 // has the bits smi_ivf_search returns against the decoded row.
-constexpr int PQ_CW = 256;     // codewords of every sub-quantiser: a code is one byte
 constexpr int PQ_ROWS = 2048;  // rows one block of the training update takes of one sub-quantiser
 
 int pq_check_dsub(int32_t d, int32_t dsub) {  // behind check_shape: d > 0
@@ -1226,75 +1009,7 @@ __global__ __launch_bounds__(IVF_TB) void ivf_pq_gather_kernel(const f16* __rest
 template <int B>
 constexpr int ivf_pq_residual_scan_lds(int KT) { return ivf_scan_lds<B>(KT) + B * 4; }
 
-template <int KT, int B, bool RES>
-__global__ __launch_bounds__(IVF_TB) void ivf_pq_scan_lists_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
-                                                                   const uint8_t* __restrict__ codes, int dshift,
-                                                                   const f16* __restrict__ cb, const int32_t* __restrict__ ids,
-                                                                   const int32_t* __restrict__ off, int K,
-                                                                   const int32_t* __restrict__ poff,
-                                                                   const int32_t* __restrict__ ubase,
-                                                                   const int32_t* __restrict__ pairs, int k_out,
-                                                                   float* __restrict__ ps, int32_t* __restrict__ pi,
-                                                                   const float* __restrict__ coarse) {
-  constexpr int NR = B / 32;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  unsigned long long* lists = (unsigned long long*)(smem + 4 * B * IVF_SLICE);
-  int* spair = (int*)(lists + B * KT);
-  [[maybe_unused]] float* scoarse = (float*)(spair + B);  // RES only
-  const int tid = threadIdx.x, b = blockIdx.x;
-  if (b >= ubase[K]) return;
-  const int l = ivf_unit_list(ubase, K, b);
-  const int p0 = poff[l] + (b - ubase[l]) * B;
-  const int npair = min(B, poff[l + 1] - p0);
-  const int s_begin = off[l], s_end = off[l + 1];
-  if constexpr (RES) ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [&](int pr) { scoarse[tid] = pr >= 0 ? coarse[pr] : 0.f; });
-  else ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [](int) {});
-
-  const int nk = d / IVF_BK, cc = tid & 7;
-  const int T = (s_end - s_begin + B - 1) / B * nk;  // the slices of the walk
-  const int M = d >> dshift, dsub = 1 << dshift;
-  const f16* qsrc[NR];  // this thread's query rows of a slice
-#pragma unroll
-  for (int j = 0; j < NR; ++j) {
-    const int pr = spair[(tid >> 3) + 32 * j];
-    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
-  }
-  unsigned cd[NR];  // the code bytes of this thread's chunk of the slice the next `fetch` gathers
-  auto fetch_codes = [&](int it) {
-    const int tile = it / nk, ks = it - tile * nk;
-    const int m = (ks * IVF_BK + cc * 8) >> dshift;  // < M
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
-      cd[j] = slot < s_end ? codes[(size_t)slot * M + m] : 0u;
-    }
-  };
-  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {
-    if (it == 0) fetch_codes(0);
-    const int tile = it / nk, ks = it - tile * nk;
-    const int k0 = ks * IVF_BK + cc * 8;
-    const f16* cw = cb + ((size_t)(k0 >> dshift) * PQ_CW << dshift) + (k0 & (dsub - 1));  // codeword 0 of the sub-quantiser
-#pragma unroll
-    for (int j = 0; j < NR; ++j) {
-      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
-      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
-      lv[j] = slot < s_end ? *(const u32x4*)(cw + ((size_t)cd[j] << dshift)) : u32x4{0u, 0u, 0u, 0u};
-    }
-    if (it + 1 < T) fetch_codes(it + 1);
-  };
-  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
-    if constexpr (RES) {
-      ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, [scoarse](int pr) {
-        const float c = scoarse[pr];
-        return [c](float a, int) { return a + c; };
-      });
-    } else {
-      ivf_topk_fold<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, IvfSumIsScore{});
-    }
-  };
-  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
-  ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
-}
+// (the kernel, ivf_pq_scan_lists_kernel<KT, B, RES>, and its keyed twin: ivf_list_kernels.hpp, included above)
 // training: codes uint8 [n, M] | sums int64 [M][256][dsub] | counts int32 [M][256] (one memset clears the sums and the counts)
 struct PqTrainWs : WsLayout {
   uint8_t* codes;
@@ -1410,17 +1125,55 @@ template <bool RES>
 int pq_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes, const float* coarse, int32_t nprobe,
                     const void* list_codes, int32_t dsub, const void* codebooks, const int32_t* list_ids,
                     const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
-                    void* stream) {
+                    void* stream, const IvfKeys* keys = nullptr) {
   return search_entry(
-      !qn || !list_codes || (RES && !coarse), nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      !qn || !list_codes || (RES && !coarse), keys, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
       "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)", 0, [&] { return pq_check_codebooks(d, dsub, codebooks); },
       no_prepare, [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
         constexpr int KT = decltype(kt)::value;
         constexpr int lds_small = RES ? ivf_pq_residual_scan_lds<IVF_BM>(KT) : ivf_scan_lds<IVF_BM>(KT);
         constexpr int lds_big = RES ? ivf_pq_residual_scan_lds<IVF_BIG>(KT) : ivf_scan_lds<IVF_BIG>(KT);
-        return launch_units<ivf_pq_scan_lists_kernel<KT, IVF_BM, RES>, ivf_pq_scan_lists_kernel<KT, IVF_BIG, RES>>(
-            unit, units, lds_small, lds_big, st, (const f16*)qn, d, (int)nq, nprobe, (const uint8_t*)list_codes, pq_shift(dsub),
-            (const f16*)codebooks, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi, coarse);
+        return launch_units_keyed<ivf_pq_scan_lists_kernel<KT, IVF_BM, RES>, ivf_pq_scan_lists_kernel<KT, IVF_BIG, RES>,
+                                  ivf_pq_scan_lists_kernel_keyed<KT, IVF_BM, RES>, ivf_pq_scan_lists_kernel_keyed<KT, IVF_BIG, RES>>(
+            keys, unit, units, lds_small, lds_big, st, (const f16*)qn, d, (int)nq, nprobe, (const uint8_t*)list_codes, pq_shift(dsub),
+            (const f16*)codebooks, list_ids, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
+            (const int32_t*)w.pairs, k, w.ps, w.pi, coarse);
+      });
+}
+
+// smi_ivf_search / smi_ivf_i8_search and their keyed twins, stated once each
+int flat_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                      const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
+                      void* ws, int64_t ws_bytes, void* stream, const IvfKeys* keys) {
+  return search_entry(
+      !qn || !list_rows, keys, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)", 0, no_refusals, no_prepare,
+      [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
+        constexpr int KT = decltype(kt)::value;
+        return launch_units_keyed<ivf_scan_lists_kernel<KT, IVF_BM>, ivf_scan_lists_kernel<KT, IVF_BIG>,
+                                  ivf_scan_lists_kernel_keyed<KT, IVF_BM>, ivf_scan_lists_kernel_keyed<KT, IVF_BIG>>(
+            keys, unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
+            (const f16*)list_rows, list_ids, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
+            (const int32_t*)w.pairs, k, w.ps, w.pi);
+      });
+}
+int i8_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
+                    const float* list_scales, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
+                    int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream, const IvfKeys* keys) {
+  return search_entry(
+      !qn || !list_codes || !list_scales, keys, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes,
+      stream, "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)", d, [&] { return i8_check_dim(d); },
+      [&](const SearchWs& w, hipStream_t st) {  // the queries, encoded like the rows
+        hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, w.qc,
+                           w.qscale);
+      },
+      [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
+        constexpr int KT = decltype(kt)::value;
+        return launch_units_keyed<ivf_i8_scan_lists_kernel<KT, IVF_BM>, ivf_i8_scan_lists_kernel<KT, IVF_BIG>,
+                                  ivf_i8_scan_lists_kernel_keyed<KT, IVF_BM>, ivf_i8_scan_lists_kernel_keyed<KT, IVF_BIG>>(
+            keys, unit, units, ivf_i8_scan_lds<IVF_BM>(KT), ivf_i8_scan_lds<IVF_BIG>(KT), st, (const int8_t*)w.qc,
+            (const float*)w.qscale, d, (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets, (int)K,
+            (const int32_t*)w.poff, (const int32_t*)w.ubase, (const int32_t*)w.pairs, k, w.ps, w.pi);
       });
 }
 
@@ -1461,15 +1214,8 @@ int64_t smi_ivf_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, in
 int smi_ivf_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
                    const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                    void* ws, int64_t ws_bytes, void* stream) {
-  return search_entry(
-      !qn || !list_rows, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
-      "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)", 0, no_refusals, no_prepare,
-      [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
-        constexpr int KT = decltype(kt)::value;
-        return launch_units<ivf_scan_lists_kernel<KT, IVF_BM>, ivf_scan_lists_kernel<KT, IVF_BIG>>(
-            unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
-            (const f16*)list_rows, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k, w.ps, w.pi);
-      });
+  return flat_search_entry(qn, nq, d, probes, nprobe, list_rows, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+                           nullptr);
 }
 
 // ---------------------------------------------------------------- range search
@@ -1481,7 +1227,7 @@ int64_t smi_range_search_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t
 int smi_range_search_count(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const float* threshold,
                            const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
                            int32_t* pair_counts, void* ws, int64_t ws_bytes, void* stream) {
-  return range_entry(!pair_counts, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets, K, pair_counts,
+  return range_entry(!pair_counts, nullptr, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets, K, pair_counts,
                      nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
 }
 
@@ -1489,7 +1235,7 @@ int smi_range_search_emit(const void* qn, int64_t nq, int32_t d, const int32_t* 
                           const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
                           const int64_t* pair_base, int64_t total, float* score, int32_t* idx, void* ws, int64_t ws_bytes,
                           void* stream) {
-  return range_entry(!pair_base || !score || !idx, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets, K,
+  return range_entry(!pair_base || !score || !idx, nullptr, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets, K,
                      nullptr, pair_base, total, score, idx, ws, ws_bytes, stream);
 }
 
@@ -1560,20 +1306,8 @@ int64_t smi_ivf_i8_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe,
 int smi_ivf_i8_search(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
                       const float* list_scales, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
                       int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
-  return search_entry(
-      !qn || !list_codes || !list_scales, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
-      "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)", d, [&] { return i8_check_dim(d); },
-      [&](const SearchWs& w, hipStream_t st) {  // the queries, encoded like the rows
-        hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, w.qc,
-                           w.qscale);
-      },
-      [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
-        constexpr int KT = decltype(kt)::value;
-        return launch_units<ivf_i8_scan_lists_kernel<KT, IVF_BM>, ivf_i8_scan_lists_kernel<KT, IVF_BIG>>(
-            unit, units, ivf_i8_scan_lds<IVF_BM>(KT), ivf_i8_scan_lds<IVF_BIG>(KT), st, (const int8_t*)w.qc, (const float*)w.qscale,
-            d, (int)nq, nprobe, (const int8_t*)list_codes, list_scales, list_ids, list_offsets, (int)K, w.poff, w.ubase, w.pairs, k,
-            w.ps, w.pi);
-      });
+  return i8_search_entry(qn, nq, d, probes, nprobe, list_codes, list_scales, list_ids, list_offsets, K, k, idx, score, ws,
+                         ws_bytes, stream, nullptr);
 }
 
 // ---------------------------------------------------------------- product quantiser and product-quantised lists
@@ -1669,6 +1403,86 @@ int smi_ivf_pq_search_residual(const void* qn, int64_t nq, int32_t d, const int3
                                int64_t ws_bytes, void* stream) {
   return pq_search_entry<true>(qn, nq, d, probes, coarse, nprobe, list_codes, dsub, codebooks, list_ids, list_offsets, K, k, idx,
                                score, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- filtered search
+int smi_slot_filter(const int32_t* list_ids, const int32_t* list_offsets, int64_t K, const int32_t* row_keys,
+                    const uint8_t* row_mask, int64_t n, int32_t* slot_ids_out, int32_t* slot_keys_out, int64_t slots,
+                    void* stream) {
+  if (!list_ids || !list_offsets || !slot_ids_out) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (!row_keys && !row_mask) return fail(SMI_ERR_INVALID_ARG, "null row_keys and null row_mask: nothing to filter by");
+  if (!row_keys != !slot_keys_out)
+    return fail(SMI_ERR_INVALID_ARG, "row_keys and slot_keys_out go together: both, or neither");
+  if ((uintptr_t)slot_ids_out % 16 || (uintptr_t)slot_keys_out % 16)
+    return fail(SMI_ERR_INVALID_ARG, "slot_ids_out and slot_keys_out must be 16-byte aligned");
+  if (K < 1) return fail(SMI_ERR_INVALID_ARG, "K=%lld: at least one list", (long long)K);
+  if (n < 1) return fail(SMI_ERR_INVALID_ARG, "n=%lld: empty input", (long long)n);
+  if (slots < 1) return fail(SMI_ERR_INVALID_ARG, "slots=%lld: empty storage", (long long)slots);
+  if (n > IVF_MAX || K > IVF_MAX || slots > IVF_MAX)
+    return fail(SMI_ERR_UNSUPPORTED, "n=%lld, K=%lld, slots=%lld: row, list and slot numbers must fit int32", (long long)n,
+                (long long)K, (long long)slots);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  // one thread per slot the storage holds
+  hipLaunchKernelGGL(ivf_slot_filter_kernel, grid_for(slots, IVF_TB), dim3(IVF_TB), 0, (hipStream_t)stream, list_ids, list_offsets,
+                     (int)K, row_keys, row_mask, n, slots, slot_ids_out, slot_keys_out);
+  HIP_TRY(hipGetLastError());
+  return SMI_OK;
+}
+
+int smi_ivf_search_keyed(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                         const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
+                         void* ws, int64_t ws_bytes, void* stream, const int32_t* slot_keys, const int32_t* query_keys,
+                         int32_t accept) {
+  const IvfKeys keys{slot_keys, query_keys, accept};
+  return flat_search_entry(qn, nq, d, probes, nprobe, list_rows, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+                           &keys);
+}
+
+int smi_ivf_i8_search_keyed(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
+                            const float* list_scales, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
+                            int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream, const int32_t* slot_keys,
+                            const int32_t* query_keys, int32_t accept) {
+  const IvfKeys keys{slot_keys, query_keys, accept};
+  return i8_search_entry(qn, nq, d, probes, nprobe, list_codes, list_scales, list_ids, list_offsets, K, k, idx, score, ws,
+                         ws_bytes, stream, &keys);
+}
+
+int smi_ivf_pq_search_keyed(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
+                            int32_t dsub, const void* codebooks, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
+                            int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream,
+                            const int32_t* slot_keys, const int32_t* query_keys, int32_t accept) {
+  const IvfKeys keys{slot_keys, query_keys, accept};
+  return pq_search_entry<false>(qn, nq, d, probes, nullptr, nprobe, list_codes, dsub, codebooks, list_ids, list_offsets, K, k, idx,
+                                score, ws, ws_bytes, stream, &keys);
+}
+
+int smi_ivf_pq_search_residual_keyed(const void* qn, int64_t nq, int32_t d, const int32_t* probes, const float* coarse,
+                                     int32_t nprobe, const void* list_codes, int32_t dsub, const void* codebooks,
+                                     const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx,
+                                     float* score, void* ws, int64_t ws_bytes, void* stream, const int32_t* slot_keys,
+                                     const int32_t* query_keys, int32_t accept) {
+  const IvfKeys keys{slot_keys, query_keys, accept};
+  return pq_search_entry<true>(qn, nq, d, probes, coarse, nprobe, list_codes, dsub, codebooks, list_ids, list_offsets, K, k, idx,
+                               score, ws, ws_bytes, stream, &keys);
+}
+
+int smi_range_search_count_keyed(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                                 const float* threshold, const void* list_rows, const int32_t* list_ids,
+                                 const int32_t* list_offsets, int64_t K, int32_t* pair_counts, void* ws, int64_t ws_bytes,
+                                 void* stream, const int32_t* slot_keys, const int32_t* query_keys, int32_t accept) {
+  const IvfKeys keys{slot_keys, query_keys, accept};
+  return range_entry(!pair_counts, &keys, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets, K, pair_counts,
+                     nullptr, 0, nullptr, nullptr, ws, ws_bytes, stream);
+}
+
+int smi_range_search_emit_keyed(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                                const float* threshold, const void* list_rows, const int32_t* list_ids,
+                                const int32_t* list_offsets, int64_t K, const int64_t* pair_base, int64_t total, float* score,
+                                int32_t* idx, void* ws, int64_t ws_bytes, void* stream, const int32_t* slot_keys,
+                                const int32_t* query_keys, int32_t accept) {
+  const IvfKeys keys{slot_keys, query_keys, accept};
+  return range_entry(!pair_base || !score || !idx, &keys, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets,
+                     K, nullptr, pair_base, total, score, idx, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

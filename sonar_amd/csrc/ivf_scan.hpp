@@ -3,7 +3,8 @@
 // that a PQ score is the flat score on the decoded row because both run the one loop below; each kernel adds its prologue,
 // where a slice comes from (`fetch`) and what happens to a finished tile (`fold`).  ivf_selfjoin_kernel (whose score is the
 // search score) and ivf_i8_scan_lists_kernel (the same byte geometry on int8) follow this text in copies of their own,
-// for the reasons at the head of ivf.hip: a change here is made there too.
+// for the reasons at the head of ivf.hip: a change here is made there too.  IvfKeyTest is the key predicate of the filtered
+// search: what a kernel keeps of its keys, and the test its fold asks behind `id >= 0`.
 //
 // Workgroup b = unit b - ubase[l] of the list l with ubase[l] <= b < ubase[l + 1]: B rows of the unit's own (the pairs'
 // query rows of a search, the own slots of the self-join: the MFMA B operand, columns of D) against the slots
@@ -58,6 +59,59 @@ template <int B>
 __device__ __forceinline__ int ivf_live_blocks(int nrow) {
   return min(B / 32, max(0, (nrow - (int)(threadIdx.x >> 6 & 1) * (B / 2) + 15) / 16));
 }
+
+// ---------------------------------------------------------------- the key predicate of a filtered scan
+// Every slot has a signed int32 key (slot_keys, in slot order beside the ids; a pad slot's is unspecified), every query one
+// (query_keys [nq]); a candidate passes iff bit cmp + 1 of `accept` is set, cmp = the sign of (slot key - query key) as ONE
+// signed compare: bit 0 less, bit 1 equal, bit 2 greater (== 2, != 5, < 1, <= 3, > 4, >= 6; 0 nothing, 7 everything).  accept
+// is a kernel argument, uniform over the launch: one instantiation serves every relation.
+struct IvfNoKeys {};  // the arguments of an unkeyed scan: none
+struct IvfKeys {
+  const int32_t* slot_keys;
+  const int32_t* query_keys;
+  int accept;
+};
+// What a list-walking kernel keeps of its Keys.  IvfNoKeys: nothing, and every candidate passes -- the kernel is the text
+// without it.  IvfKeys: B ints of LDS at `lds` (the query key of every unit row, written by pair() in the unit prologue, by
+// the threads tid < B, in front of the prologue's barrier); rows() behind that barrier takes the keys of this lane's unit rows
+// wc * B / 2 + bi * 16 + l15 into registers, as the range kernel holds thr[B / 32]; slots(slot0) loads the four slot keys
+// of a fold beside the int4 of ids (slot0 % 4 == 0: 16-byte aligned); (bi, r) is the test.  It is to be asked behind id >= 0.
+template <int B, class Keys>
+struct IvfKeyTest;
+template <int B>
+struct IvfKeyTest<B, IvfNoKeys> {
+  static constexpr int LDS = 0;
+  __device__ __forceinline__ IvfKeyTest(IvfNoKeys, void*) {}
+  __device__ __forceinline__ void pair(int, int) const {}
+  __device__ __forceinline__ void rows() const {}
+  __device__ __forceinline__ void slots(int) const {}
+  __device__ __forceinline__ bool operator()(int, int) const { return true; }
+};
+template <int B>
+struct IvfKeyTest<B, IvfKeys> {
+  static constexpr int LDS = B * 4;
+  const int32_t* __restrict__ slot_keys;
+  const int32_t* __restrict__ query_keys;
+  int accept;
+  int* sqk;
+  int qk[B / 32], rk[4];
+  __device__ __forceinline__ IvfKeyTest(IvfKeys k, void* lds)
+      : slot_keys(k.slot_keys), query_keys(k.query_keys), accept(k.accept), sqk((int*)lds) {}
+  __device__ __forceinline__ void pair(int pr, int nprobe) { sqk[threadIdx.x] = pr >= 0 ? query_keys[pr / nprobe] : 0; }
+  __device__ __forceinline__ void rows() {
+    const int row0 = (threadIdx.x >> 6 & 1) * (B / 2) + (threadIdx.x & 15);
+#pragma unroll
+    for (int bi = 0; bi < B / 32; ++bi) qk[bi] = sqk[row0 + bi * 16];
+  }
+  __device__ __forceinline__ void slots(int slot0) {
+    const int4 k4 = *(const int4*)(slot_keys + slot0);
+    rk[0] = k4.x, rk[1] = k4.y, rk[2] = k4.z, rk[3] = k4.w;
+  }
+  __device__ __forceinline__ bool operator()(int bi, int r) const {
+    const int cmp = (int)(rk[r] > qk[bi]) - (int)(rk[r] < qk[bi]);
+    return accept >> (cmp + 1) & 1;
+  }
+};
 
 // LDS of a search unit behind the slice buffers: the key lists [B][KT] and the pair numbers [B] (-1: no pair).  `extra(pr)`
 // is what else a thread keeps of its pair; a barrier follows.
@@ -168,9 +222,11 @@ __device__ __forceinline__ void ivf_slice_walk(char* smem, int s_begin, int s_en
 
 // The fold of a search: this wave's scores of four slots (ids id4; -1: a pad slot) into the pairs' key lists.  A candidate
 // must beat the pair's current k-th key's score or tie it (the id decides then); a stale threshold is a valid lower bound.
-// score(pr)(a, r) is the score of sum `a` of the r-th slot against pair pr.
-template <int KT, int B, class Acc, class Score>
-__device__ __forceinline__ void ivf_topk_fold(unsigned long long* lists, int npair, int4 id4, const Acc (&acc)[B / 32], Score score) {
+// score(pr)(a, r) is the score of sum `a` of the r-th slot against pair pr.  pass(bi, r): the key predicate of slot r against
+// this lane's unit row bi (IvfKeyTest; asked behind id >= 0: a pad slot's key is unspecified).
+template <int KT, int B, class Acc, class Score, class Pass>
+__device__ __forceinline__ void ivf_topk_fold(unsigned long long* lists, int npair, int4 id4, const Acc (&acc)[B / 32], Score score,
+                                              const Pass& pass) {
   const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
   const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
 #pragma unroll
@@ -184,7 +240,7 @@ __device__ __forceinline__ void ivf_topk_fold(unsigned long long* lists, int npa
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float v = of(acc[bi][r], r);
-        if (idr[r] >= 0 && v >= thr) xs_insert<KT>(lst, v, idr[r]);
+        if (idr[r] >= 0 && pass(bi, r) && v >= thr) xs_insert<KT>(lst, v, idr[r]);
       }
     }
   }
@@ -217,16 +273,18 @@ __device__ __forceinline__ void ivf_lists_readout(const unsigned long long* list
 
 // ---------------------------------------------------------------- the range scan
 // LDS of a range unit behind the slice buffers, in place of the key lists: per unit row its pair number [B] (-1: no pair),
-// the threshold of the pair's query [B] (fp32) and one 32-bit counter [B] (zero).  A barrier follows.
-template <int B>
+// the threshold of the pair's query [B] (fp32) and one 32-bit counter [B] (zero).  `extra(pr)` is ivf_pairs_init's.  A barrier
+// follows.
+template <int B, class Extra>
 __device__ __forceinline__ void ivf_range_init(int* spair, float* sthr, unsigned* scnt, const int32_t* __restrict__ pairs, int p0,
-                                               int npair, int nprobe, const float* __restrict__ threshold) {
+                                               int npair, int nprobe, const float* __restrict__ threshold, Extra extra) {
   const int tid = threadIdx.x;
   if (tid < B) {
     const int pr = tid < npair ? pairs[p0 + tid] : -1;
     spair[tid] = pr;
     sthr[tid] = pr >= 0 ? threshold[pr / nprobe] : __builtin_nanf("");
     scnt[tid] = 0u;
+    extra(pr);
   }
   __syncthreads();
 }
@@ -236,10 +294,11 @@ __device__ __forceinline__ void ivf_range_init(int* spair, float* sthr, unsigned
 // threshold <= 0) and acc >= the pair's threshold, an fp32 compare (a NaN threshold gives no hit).  thr[bi]: the threshold of
 // this lane's unit row bi, NaN where the row holds no pair -- that is how `pr < npair` is stated here.  Most tiles hold no hit:
 // the ids are loaded and the slots are looked at one by one only where some lane of the wave has a sum at its threshold.
-// hit(bi, mask, idr): the slots r of `mask` (bits 0 .. 3), whose ids are idr[r], are hits of unit row bi.
-template <int B, class Acc, class Hit>
+// hit(bi, mask, idr): the slots r of `mask` (bits 0 .. 3), whose ids are idr[r], are hits of unit row bi.  keys: the key
+// predicate (IvfKeyTest), loaded and asked behind the wave-uniform exit only: a tile without a hit costs what it did.
+template <int B, class Acc, class KeyTest, class Hit>
 __device__ __forceinline__ void ivf_range_fold(const int32_t* __restrict__ ids, int slot0, const float (&thr)[B / 32],
-                                               const Acc (&acc)[B / 32], Hit hit) {
+                                               const Acc (&acc)[B / 32], KeyTest& keys, Hit hit) {
   bool some = false;
 #pragma unroll
   for (int bi = 0; bi < B / 32; ++bi)
@@ -248,11 +307,12 @@ __device__ __forceinline__ void ivf_range_fold(const int32_t* __restrict__ ids, 
   if (!__any(some)) return;  // wave-uniform
   const int4 id4 = *(const int4*)(ids + slot0);
   const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
+  keys.slots(slot0);
 #pragma unroll
   for (int bi = 0; bi < B / 32; ++bi) {
     unsigned mask = 0u;
 #pragma unroll
-    for (int r = 0; r < 4; ++r) mask |= (unsigned)(idr[r] >= 0 && acc[bi][r] >= thr[bi]) << r;
+    for (int r = 0; r < 4; ++r) mask |= (unsigned)(idr[r] >= 0 && keys(bi, r) && acc[bi][r] >= thr[bi]) << r;
     if (mask) hit(bi, mask, idr);
   }
 }

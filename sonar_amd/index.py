@@ -33,9 +33,22 @@ was measured on synthetic planted data only, whose noise is isotropic and does n
 FAISS's `by_residual`): the same bytes, a lower quantisation error, and one fp32 add per score -- the query's score against
 the list's centroid, which the probe has already computed (tests/ivf_pq_residual_ref.py).
 
+Filtered search (FAISS's `IDSelector`): `index.row_filter(keys=, mask=)` gives a `RowFilter`, and
+`search(..., rows=, query_keys=, match=)` of all four classes and `IVFFlatIndex.range_search` count a candidate (query q, row i)
+only where the row is visible (`mask[i]`, shared by all queries) and `keys[i] match query_keys[q]` holds, `match` one of
+== != < <= > >= over signed int32 keys.  It happens inside the scan, so k results come back wherever k rows qualify: a
+query's filtered result is, bit for bit, its unfiltered result over an index that holds only the rows it may see.  Recipes:
+  a language-restricted search     keys = the rows' language numbers, query_keys = the wanted language, match "=="
+  excluding the query itself       keys = arange(n), query_keys = the queries' own row numbers, match "!="  (k-NN of a corpus
+                                   against its own index, where every query finds itself first)
+  excluding the query's document   keys = document numbers, match "!="
+  a cut-off date                   keys = dates, query_keys = the query's cut-off, match "<"
+  rows to be ignored               mask = False for them: the only removal there is, as the index is built once
+
 Not here: an OPQ rotation, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, nprobe or
 k above 8, de-duplication or range search over quantised lists, incremental add and removal, 64-bit ids, splitting of long
-lists, multi-GPU sharding.
+lists, multi-GPU sharding; of filtering: skipping whole tiles or lists by key, per-query bitmaps or id lists, keys wider than
+32 bits, more than one key per row, a filter on the coarse probe.
 """
 from __future__ import annotations
 
@@ -53,6 +66,9 @@ UNIT_QUERIES = 64  # SMI_IVF_UNIT_QUERIES: queries of one list that one work uni
 INT8_MAX_DIM = 131072  # SMI_IVF_I8_MAX_DIM: above it the int32 sum of int8 products could overflow
 PQ_CODEWORDS = 256  # codewords of every sub-quantiser: a code is one byte
 PQ_DSUBS = (8, 16, 32, 64)  # dimensions per sub-quantiser
+# the relations of a key predicate as the C ABI's `accept`: a 3-bit mask over the outcome of one signed compare of the row's key
+# with the query's, bit 0 less, bit 1 equal, bit 2 greater (0: nothing passes, 7: everything)
+MATCH_ACCEPT = {"==": 2, "!=": 5, "<": 1, "<=": 3, ">": 4, ">=": 6}
 
 
 def _check_device_tensor(t, name: str, hint: str = "") -> None:
@@ -143,11 +159,69 @@ def _check_search_args(qn, probes, k) -> None:
     _check_table(probes, "probes", *(probes.shape if isinstance(probes, torch.Tensor) else (-1, 1)))
 
 
-def _search(entry: str, sizing: str, qn, probes, k: int, extras, storage, ids, offsets, dsub=()):
+class RowFilter(NamedTuple):
+    """Which rows of an index's lists count, in slot order (`row_filter`): ids int32 [slots], the row of every
+    slot or -1 where it is masked out (or holds none), and keys int32 [slots] or None, the rows' keys.  Reusable across calls;
+    not part of `state_dict`; tied to the storage it was made from by its length."""
+
+    ids: torch.Tensor
+    keys: Optional[torch.Tensor]
+
+
+def slot_filter(ids: torch.Tensor, offsets: torch.Tensor, keys: Optional[torch.Tensor] = None,
+                mask: Optional[torch.Tensor] = None) -> RowFilter:
+    """smi_slot_filter: the row filter of the storage (ids int32 [slots], offsets int32 [K + 1]) a `build_lists*` returned.
+    keys: device int32 [n], one key per row, or None; mask: device bool [n], True = visible, or None; at least one of them.
+    A row whose id is not below the length of a given tensor (the shorter, where both are given) is left out.  One small
+    gather kernel, enqueued; nothing is read back."""
+    if keys is None and mask is None:
+        raise ValueError("row_filter: give keys, mask or both")
+    for t, name, dtype in ((keys, "keys", torch.int32), (mask, "mask", torch.bool)):
+        if t is not None:
+            _check_device_tensor(t, name)
+            if t.dtype != dtype or t.dim() != 1 or t.shape[0] < 1:
+                raise ValueError(f"{name} must be {str(dtype).replace('torch.', '')} [n], got {t.dtype} {list(t.shape)}")
+    n = min(t.shape[0] for t in (keys, mask) if t is not None)
+    lib = _lib.load()
+    slots = ids.shape[0]
+    out_ids = torch.empty((slots,), dtype=torch.int32, device=ids.device)
+    out_keys = None if keys is None else torch.empty((slots,), dtype=torch.int32, device=ids.device)
+    keys = None if keys is None else keys.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    with torch.cuda.device(ids.device):
+        _lib.check(lib.smi_slot_filter(ids.data_ptr(), offsets.data_ptr(), offsets.shape[0] - 1,
+                                       None if keys is None else keys.data_ptr(), None if mask is None else mask.data_ptr(), n,
+                                       out_ids.data_ptr(), None if out_keys is None else out_keys.data_ptr(), slots,
+                                       _lib.current_stream_ptr()))
+    return RowFilter(out_ids, out_keys)
+
+
+def _check_keyed(slot_keys, query_keys, accept, slots: int, nq: int):
+    """The optional trailing arguments of the list functions: () without them, else the three a `_keyed` entry takes behind
+    its twin's (the tensors themselves, to be held until the call is enqueued)."""
+    if slot_keys is None and query_keys is None and accept is None:
+        return ()
+    if slot_keys is None or query_keys is None or accept is None:
+        raise ValueError("slot_keys, query_keys and accept go together: all three, or none")
+    if isinstance(accept, bool) or not isinstance(accept, int) or not 0 <= accept <= 7:
+        raise ValueError(f"accept = {accept!r}: a 3-bit mask in [0, 7] (bit 0 less, bit 1 equal, bit 2 greater)")
+    _check_table(slot_keys, "slot_keys", slots, None)
+    _check_table(query_keys, "query_keys", nq, None)
+    return (slot_keys.contiguous(), query_keys.contiguous(), accept)
+
+
+def _keyed_args(keyed):
+    return (keyed[0].data_ptr(), keyed[1].data_ptr(), keyed[2]) if keyed else ()
+
+
+def _search(entry: str, sizing: str, qn, probes, k: int, extras, storage, ids, offsets, dsub=(), keyed=()):
     """A search entry of the C ABI and its sizing call, as in `_build`: `head + extras + nprobe + storage + tail`, storage the
-    arguments that describe the lists (pointers of tensors the caller holds).  Returns (scores, ids)."""
+    arguments that describe the lists (pointers of tensors the caller holds).  keyed: `_check_keyed`'s result; with it the
+    entry is its `_keyed` twin.  Returns (scores, ids)."""
     lib = _lib.load()
     (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
+    if keyed:
+        entry += "_keyed"
     ws_bytes = int(getattr(lib, sizing)(nq, n_lists, nprobe, k, d, *dsub))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
     idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
@@ -156,7 +230,7 @@ def _search(entry: str, sizing: str, qn, probes, k: int, extras, storage, ids, o
     with torch.cuda.device(qn.device):
         _lib.check(getattr(lib, entry)(qn.data_ptr(), nq, d, probes.data_ptr(), *extras, nprobe, *storage, ids.data_ptr(),
                                        offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes,
-                                       _lib.current_stream_ptr()))
+                                       _lib.current_stream_ptr(), *_keyed_args(keyed)))
     return score, idx
 
 
@@ -175,12 +249,19 @@ def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
 
 
 def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
-                 k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+                 k: int = 1, slot_keys: Optional[torch.Tensor] = None, query_keys: Optional[torch.Tensor] = None,
+                 accept: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_ivf_search: the k best rows of the lists probes (device int32 [nq, 1..8]) names, for the first nq rows of qn
-    (contiguous fp16 [>= nq, d]) against the storage `build_lists` returned: (scores fp32 [nq, k], ids int32 [nq, k])."""
+    (contiguous fp16 [>= nq, d]) against the storage `build_lists` returned: (scores fp32 [nq, k], ids int32 [nq, k]).
+
+    slot_keys (device int32 [slots]), query_keys (device int32 [nq]) and accept (`MATCH_ACCEPT`, or any mask in [0, 7]), all
+    three or none: smi_ivf_search_keyed, where a row counts only if its key passes against the query's.
+    ids may be a `RowFilter`'s: a slot whose id is -1 never counts.  The other `search_lists_*` take the same three."""
     _check_search_args(qn, probes, k)
     _check_lists_dim(qn, rows)
-    return _search("smi_ivf_search", "smi_ivf_search_workspace_bytes", qn, probes, k, (), (rows.data_ptr(),), ids, offsets)
+    keyed = _check_keyed(slot_keys, query_keys, accept, ids.shape[0], probes.shape[0])
+    return _search("smi_ivf_search", "smi_ivf_search_workspace_bytes", qn, probes, k, (), (rows.data_ptr(),), ids, offsets,
+                   keyed=keyed)
 
 
 class RangeResult(NamedTuple):
@@ -216,8 +297,9 @@ def _check_max_total(max_total) -> None:
 
 
 def range_search_lists(qn: torch.Tensor, probes: torch.Tensor, thresholds: Union[float, torch.Tensor], rows: torch.Tensor,
-                       ids: torch.Tensor, offsets: torch.Tensor, sort: bool = True,
-                       max_total: Optional[int] = None) -> RangeResult:
+                       ids: torch.Tensor, offsets: torch.Tensor, sort: bool = True, max_total: Optional[int] = None,
+                       slot_keys: Optional[torch.Tensor] = None, query_keys: Optional[torch.Tensor] = None,
+                       accept: Optional[int] = None) -> RangeResult:
     """smi_range_search_count / smi_range_search_emit: every row of the lists probes (device int32 [nq, 1..8]) names whose
     score against query q is >= thresholds[q] (device fp32 [nq], or one Python float for all; an fp32 compare, so NaN hits
     nothing and -inf everything probed), for the first nq rows of qn against the storage `build_lists` returned.  A score
@@ -229,10 +311,13 @@ def range_search_lists(qn: torch.Tensor, probes: torch.Tensor, thresholds: Union
 
     sort: every query's segment in `xsim.topk`'s total order, score descending and ties to the lower id (three stable
     `torch.sort`s); the result then has the same bits whatever the batch or the run.  sort=False leaves the order inside a
-    segment unspecified (it differs from run to run)."""
+    segment unspecified (it differs from run to run).
+
+    slot_keys, query_keys, accept: as for `search_lists`; the `_keyed` twins of both entries."""
     _check_search_args(qn, probes, 1)
     _check_lists_dim(qn, rows)
     _check_max_total(max_total)
+    keyed = _check_keyed(slot_keys, query_keys, accept, ids.shape[0], probes.shape[0])
     (nq, nprobe), d, n_lists, dev = probes.shape, qn.shape[1], offsets.shape[0] - 1, qn.device
     thresholds = _check_thresholds(thresholds, nq, qn)
     lib = _lib.load()
@@ -242,8 +327,10 @@ def range_search_lists(qn: torch.Tensor, probes: torch.Tensor, thresholds: Union
     probes = probes.contiguous()
     inputs = (qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, thresholds.data_ptr(), rows.data_ptr(), ids.data_ptr(),
               offsets.data_ptr(), n_lists)
+    count, emit = (getattr(lib, name + ("_keyed" if keyed else "")) for name in ("smi_range_search_count", "smi_range_search_emit"))
+    keys = _keyed_args(keyed)
     with torch.cuda.device(dev):
-        _lib.check(lib.smi_range_search_count(*inputs, pair_counts.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+        _lib.check(count(*inputs, pair_counts.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr(), *keys))
         base = torch.zeros((nq * nprobe + 1,), dtype=torch.int64, device=dev)
         torch.cumsum(pair_counts, 0, dtype=torch.int64, out=base[1:])
         total = int(base[-1].item())  # the read-back
@@ -252,8 +339,8 @@ def range_search_lists(qn: torch.Tensor, probes: torch.Tensor, thresholds: Union
         score = torch.empty((total,), dtype=torch.float32, device=dev)
         idx = torch.empty((total,), dtype=torch.int32, device=dev)
         if total:
-            _lib.check(lib.smi_range_search_emit(*inputs, base.data_ptr(), total, score.data_ptr(), idx.data_ptr(), ws.data_ptr(),
-                                                 ws_bytes, _lib.current_stream_ptr()))
+            _lib.check(emit(*inputs, base.data_ptr(), total, score.data_ptr(), idx.data_ptr(), ws.data_ptr(), ws_bytes,
+                            _lib.current_stream_ptr(), *keys))
     lims = base[::nprobe].contiguous()
     if sort and total:
         score, idx = _sort_segments(lims, score, idx)
@@ -295,15 +382,17 @@ def build_lists_int8(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
 
 
 def search_lists_int8(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, ids: torch.Tensor,
-                      offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+                      offsets: torch.Tensor, k: int = 1, slot_keys: Optional[torch.Tensor] = None,
+                      query_keys: Optional[torch.Tensor] = None, accept: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_ivf_i8_search: `search_lists` against the storage `build_lists_int8` returned; the queries are encoded like the
     rows.  score = fl32(fl32((float)(integer dot product) * scale_row) * scale_query)."""
     _check_device_tensor(scales, "scales")
     _check_search_args(qn, probes, k)
     _check_int8_dim(qn.shape[1])
     _check_lists_dim(qn, codes)
+    keyed = _check_keyed(slot_keys, query_keys, accept, ids.shape[0], probes.shape[0])
     return _search("smi_ivf_i8_search", "smi_ivf_i8_search_workspace_bytes", qn, probes, k, (),
-                   (codes.data_ptr(), scales.data_ptr()), ids, offsets)
+                   (codes.data_ptr(), scales.data_ptr()), ids, offsets, keyed=keyed)
 
 
 def _check_codebooks(codebooks, d: Optional[int] = None) -> Tuple[int, int]:
@@ -413,9 +502,11 @@ def _check_coarse(coarse, shape) -> None:
         raise ValueError(f"coarse must be fp32 {list(shape)}, got {coarse.dtype} {list(coarse.shape)}")
 
 
-def _search_pq(qn, probes, codes, codebooks, ids, offsets, k: int, coarse=None):
-    """smi_ivf_pq_search, or smi_ivf_pq_search_residual with coarse (fp32, the shape of probes)."""
+def _search_pq(qn, probes, codes, codebooks, ids, offsets, k: int, coarse=None, keys=(None, None, None)):
+    """smi_ivf_pq_search, or smi_ivf_pq_search_residual with coarse (fp32, the shape of probes); keys: (slot_keys,
+    query_keys, accept) of `search_lists`."""
     _check_search_args(qn, probes, k)
+    keyed = _check_keyed(*keys, ids.shape[0], probes.shape[0])
     if coarse is not None:
         _check_coarse(coarse, probes.shape)
     m, dsub = _check_codebooks(codebooks, qn.shape[1])
@@ -425,14 +516,15 @@ def _search_pq(qn, probes, codes, codebooks, ids, offsets, k: int, coarse=None):
         coarse = coarse.contiguous()  # (held until the call is enqueued)
         entry, extra = "smi_ivf_pq_search_residual", (coarse.data_ptr(),)
     return _search(entry, "smi_ivf_pq_search_workspace_bytes", qn, probes, k, extra, (codes.data_ptr(), dsub, codebooks.data_ptr()),
-                   ids, offsets, (dsub,))
+                   ids, offsets, (dsub,), keyed)
 
 
 def search_lists_pq(qn: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, codebooks: torch.Tensor, ids: torch.Tensor,
-                    offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+                    offsets: torch.Tensor, k: int = 1, slot_keys: Optional[torch.Tensor] = None,
+                    query_keys: Optional[torch.Tensor] = None, accept: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_ivf_pq_search: `search_lists` against the storage `build_lists_pq` returned.  A score has the bits `search_lists`
     returns for the query against `pq_decode` of the row."""
-    return _search_pq(qn, probes, codes, codebooks, ids, offsets, k)
+    return _search_pq(qn, probes, codes, codebooks, ids, offsets, k, None, (slot_keys, query_keys, accept))
 
 
 def _check_centroids(centroids, d: int) -> int:
@@ -495,14 +587,15 @@ def build_lists_pq_residual(xn: torch.Tensor, labels: torch.Tensor, centroids: t
 
 
 def search_lists_pq_residual(qn: torch.Tensor, probes: torch.Tensor, coarse: torch.Tensor, codes: torch.Tensor,
-                             codebooks: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
-                             k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+                             codebooks: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor, k: int = 1,
+                             slot_keys: Optional[torch.Tensor] = None, query_keys: Optional[torch.Tensor] = None,
+                             accept: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_ivf_pq_search_residual: `search_lists_pq` against the storage `build_lists_pq_residual` returned, with
     coarse (device fp32 [nq, nprobe]: the score of query q against the centroid of the list probes[q, p]) added to every score
     of that pair in fp32.  The entry of a probe that names no list is not read."""
     if coarse is None:
         raise TypeError("coarse must be a torch.Tensor")
-    return _search_pq(qn, probes, codes, codebooks, ids, offsets, k, coarse)
+    return _search_pq(qn, probes, codes, codebooks, ids, offsets, k, coarse, (slot_keys, query_keys, accept))
 
 
 class ProductQuantizer:
@@ -684,12 +777,44 @@ class _IVFIndex:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
         return topk_normalized(qn, q.shape[0], self._c16, self._k, nprobe)[1]
 
-    def _checked_search(self, q, k, nprobe, probes, refine=None, coarse=None):
+    def row_filter(self, keys: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> RowFilter:
+        """The `RowFilter` of `search(..., rows=)`.  keys: device int32 [n], the key of every row `add` was
+        given (row number = id), for `query_keys=` / `match=`; mask: device bool [n], False = the row does not exist for any
+        query.  At least one of them.  A row beyond the end of a given tensor is left out.  Enqueued, no read-back; make it
+        once and reuse it."""
+        self._need_add("row_filter")
+        return slot_filter(self._ids, self._offsets, keys, mask)
+
+    def _filter(self, rows, query_keys, match, nq: int):
+        """The filter arguments of `search` / `range_search`: (the ids the scan runs on, None for the index's own,
+        (slot_keys, query_keys, accept) of the list function or three Nones)."""
+        if match not in MATCH_ACCEPT:
+            raise ValueError(f"match = {match!r}: one of {' '.join(MATCH_ACCEPT)}")
+        if rows is None:
+            if query_keys is not None:
+                raise ValueError("query_keys needs rows=, a RowFilter that index.row_filter(keys=...) built")
+            return None, (None, None, None)
+        if not isinstance(rows, RowFilter):
+            raise TypeError("rows must be a RowFilter (index.row_filter)")
+        _check_device_tensor(rows.ids, "rows.ids")
+        if rows.ids.dtype != torch.int32 or tuple(rows.ids.shape) != tuple(self._ids.shape):
+            raise ValueError(f"rows: a RowFilter of {list(rows.ids.shape)} slots, this index has {list(self._ids.shape)} "
+                             "(it belongs to another index, or to this one before load_state_dict)")
+        if query_keys is None:
+            return rows.ids, (None, None, None)  # the mask alone: the existing scan on the filter's ids
+        if rows.keys is None:
+            raise ValueError("query_keys needs a RowFilter built with keys: index.row_filter(keys=...)")
+        _check_table(query_keys, "query_keys", nq, None)
+        return rows.ids, (rows.keys, query_keys, MATCH_ACCEPT[match])
+
+    def _checked_search(self, q, k, nprobe, probes, refine=None, coarse=None, rows=None, query_keys=None, match="=="):
         """`search` of every kind: the argument checks, the probe, the subclass's scan and, with refine, the re-scoring.
         coarse: the scores that belong to probes (`IVFPQResidualIndex` alone passes them on); where the index probes by
-        itself they are the probe's own, so `_search_lists` is handed them either way."""
+        itself they are the probe's own, so `_search_lists` is handed them either way.  rows, query_keys, match: the filter
+        (`IVFFlatIndex.search`)."""
         _check_refine(refine, self._d)
         nq = self._check_search(q, k, nprobe, probes)
+        ids, keys = self._filter(rows, query_keys, match, nq)
         if coarse is not None:
             if probes is None:
                 raise ValueError("coarse belongs to probes: give both, or neither")
@@ -697,7 +822,7 @@ class _IVFIndex:
         qn = normalize_rows(q)
         if probes is None:
             coarse, probes = topk_normalized(qn, nq, self._c16, self._k, nprobe)
-        score, idx = self._search_lists(qn, probes, k, coarse)
+        score, idx = self._search_lists(qn, probes, k, coarse, ids, keys)
         return (score, idx) if refine is None else refine_candidates(qn, nq, refine, idx)
 
     def self_join(self, *args, **kwargs):
@@ -790,20 +915,30 @@ class IVFFlatIndex(_IVFIndex):
     def _build_lists(self, xn, labels):
         return build_lists(xn, labels, self._k)
 
-    def _search_lists(self, qn, probes, k, coarse):
-        return search_lists(qn, probes, self._rows, self._ids, self._offsets, k)
+    def _search_lists(self, qn, probes, k, coarse, ids, keys):
+        return search_lists(qn, probes, self._rows, self._ids if ids is None else ids, self._offsets, k, *keys)
 
-    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1,
-               probes: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None, *,
+               rows: Optional[RowFilter] = None, query_keys: Optional[torch.Tensor] = None,
+               match: str = "==") -> Tuple[torch.Tensor, torch.Tensor]:
         """The k best rows of the probed lists for every row of q (fp16 / fp32 [nq, d] on the device): (scores fp32
         [nq, k], ids int32 [nq, k]), the layout and order of `xsim.topk`.
 
         probes: None (the nprobe nearest lists by the quantiser) or device int32 [nq, 1..8]; an entry outside [0, K) names
-        no list.  A row of probes that names a list twice may return that list's rows twice."""
-        return self._checked_search(q, k, nprobe, probes)
+        no list.  A row of probes that names a list twice may return that list's rows twice.
+
+        Filtering (the recipes are in the module text), on every index class alike.  rows: a `RowFilter` of
+        this index (`row_filter`): only its visible rows count.  query_keys: device int32 [nq], with a filter built with
+        keys: row i counts for query j only if `keys[i] match query_keys[j]`, match one of == != < <= > >= (signed).  The
+        result is what `search` would return over an index of the rows that count for the query: k results wherever k of the
+        probed rows qualify, (-inf, -1) behind them, the same bits alone and in any batch.  Nothing more is read back; the
+        call stays capturable."""
+        return self._checked_search(q, k, nprobe, probes, rows=rows, query_keys=query_keys, match=match)
 
     def range_search(self, q: torch.Tensor, threshold: Union[float, torch.Tensor], nprobe: int = 1,
-                     probes: Optional[torch.Tensor] = None, sort: bool = True, max_total: Optional[int] = None) -> RangeResult:
+                     probes: Optional[torch.Tensor] = None, sort: bool = True, max_total: Optional[int] = None, *,
+                     rows: Optional[RowFilter] = None, query_keys: Optional[torch.Tensor] = None,
+                     match: str = "==") -> RangeResult:
         """EVERY row of the probed lists whose score is >= threshold, for every row of q (fp16 / fp32 [nq, d] on the device):
         `RangeResult(lims int64 [nq + 1], scores fp32 [total], ids int32 [total])`, FAISS's layout -- the hits of query i are
         the entries lims[i] .. lims[i + 1].  A score has the bits `search` returns for the same two rows.
@@ -814,15 +949,19 @@ class IVFFlatIndex(_IVFIndex):
         id); with sort=False the order inside a segment is unspecified.  max_total: raise ValueError, the total named, where
         more hits than this would be allocated.
 
+        rows, query_keys, match: the filter of `search`; only the rows that count for a query can be its hits.
+
         The lists are walked twice, to count and to write, and the total is READ BACK once in between to size the result:
         the call synchronises with the host and is not capturable."""
         nq = self._check_search(q, 1, nprobe, probes, "range_search")
         _check_max_total(max_total)
         threshold = _check_thresholds(threshold, nq, q)
+        ids, keys = self._filter(rows, query_keys, match, nq)
         qn = normalize_rows(q)
         if probes is None:
             probes = topk_normalized(qn, nq, self._c16, self._k, nprobe)[1]
-        return range_search_lists(qn, probes, threshold, self._rows, self._ids, self._offsets, sort, max_total)
+        return range_search_lists(qn, probes, threshold, self._rows, self._ids if ids is None else ids, self._offsets, sort,
+                                  max_total, *keys)
 
     def self_join(self, priority: Optional[torch.Tensor] = None, n: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """`dedup.self_join` over this index's own lists: (max_sim fp32 [n], nearest int32 [n]), for every
@@ -855,17 +994,19 @@ class IVFInt8Index(_IVFIndex):
     def _build_lists(self, xn, labels):
         return build_lists_int8(xn, labels, self._k)
 
-    def _search_lists(self, qn, probes, k, coarse):
-        return search_lists_int8(qn, probes, self._rows, self._scales, self._ids, self._offsets, k)
+    def _search_lists(self, qn, probes, k, coarse, ids, keys):
+        return search_lists_int8(qn, probes, self._rows, self._scales, self._ids if ids is None else ids, self._offsets, k, *keys)
 
     def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
-               refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               refine: Optional[torch.Tensor] = None, *, rows: Optional[RowFilter] = None,
+               query_keys: Optional[torch.Tensor] = None, match: str = "==") -> Tuple[torch.Tensor, torch.Tensor]:
         """`IVFFlatIndex.search` on the quantised rows: the scores are the quantised dot products of tests/ivf_i8_ref.py.
 
         refine: None, or the normalised fp16 corpus the index was built from (`normalize_rows(x)`, row number = id).  The k
         candidates of every query are then re-scored with their fp16 cosines (`mining.pair_scores`, cosine mode) and each
-        row is re-ordered into the same total order; (-inf, -1) entries stay what they are.  No host synchronisation."""
-        return self._checked_search(q, k, nprobe, probes, refine)
+        row is re-ordered into the same total order; (-inf, -1) entries stay what they are.  No host synchronisation.
+        rows, query_keys, match: the filter of `IVFFlatIndex.search`; refine re-scores the filtered candidates."""
+        return self._checked_search(q, k, nprobe, probes, refine, rows=rows, query_keys=query_keys, match=match)
 
 
 class IVFPQIndex(_IVFIndex):
@@ -907,8 +1048,8 @@ class IVFPQIndex(_IVFIndex):
     def _build_lists(self, xn, labels):
         return build_lists_pq(xn, labels, self._k, self._codebooks)
 
-    def _search_lists(self, qn, probes, k, coarse):
-        return search_lists_pq(qn, probes, self._rows, self._codebooks, self._ids, self._offsets, k)
+    def _search_lists(self, qn, probes, k, coarse, ids, keys):
+        return search_lists_pq(qn, probes, self._rows, self._codebooks, self._ids if ids is None else ids, self._offsets, k, *keys)
 
     _BY_RESIDUAL = False  # the codes are of the rows themselves; `IVFPQResidualIndex`: of their residuals
 
@@ -922,10 +1063,12 @@ class IVFPQIndex(_IVFIndex):
         return m, {"_codebooks": codebooks.clone()}
 
     def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
-               refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               refine: Optional[torch.Tensor] = None, *, rows: Optional[RowFilter] = None,
+               query_keys: Optional[torch.Tensor] = None, match: str = "==") -> Tuple[torch.Tensor, torch.Tensor]:
         """`IVFFlatIndex.search` on the reconstructed rows.  refine: as for `IVFInt8Index.search`, the normalised fp16 corpus
-        the index was built from; the k candidates are re-scored with their fp16 cosines and re-ordered."""
-        return self._checked_search(q, k, nprobe, probes, refine)
+        the index was built from; the k candidates are re-scored with their fp16 cosines and re-ordered.  rows, query_keys,
+        match: the filter of `IVFFlatIndex.search`."""
+        return self._checked_search(q, k, nprobe, probes, refine, rows=rows, query_keys=query_keys, match=match)
 
 
 class IVFPQResidualIndex(IVFPQIndex):
@@ -960,10 +1103,11 @@ class IVFPQResidualIndex(IVFPQIndex):
     def _build_lists(self, xn, labels):
         return build_lists_pq_residual(xn, labels, self._c16[: self._k], self._codebooks)
 
-    def _search_lists(self, qn, probes, k, coarse):
+    def _search_lists(self, qn, probes, k, coarse, ids, keys):
         if coarse is None:
             coarse = self.coarse_scores(qn, probes.shape[0], probes)
-        return search_lists_pq_residual(qn, probes, coarse, self._rows, self._codebooks, self._ids, self._offsets, k)
+        return search_lists_pq_residual(qn, probes, coarse, self._rows, self._codebooks, self._ids if ids is None else ids,
+                                        self._offsets, k, *keys)
 
     def coarse_scores(self, qn: torch.Tensor, nq: int, probes: torch.Tensor) -> torch.Tensor:
         """fp32 [nq, nprobe]: the cosines of the first nq rows of qn (`normalize_rows`) against the centroids probes names,
@@ -975,12 +1119,15 @@ class IVFPQResidualIndex(IVFPQIndex):
         return pair_scores(qn, nq, self._c16, self._k, src, trg, None, None, "cosine").reshape(nq, probes.shape[1])
 
     def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
-               coarse: Optional[torch.Tensor] = None, refine: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+               coarse: Optional[torch.Tensor] = None, refine: Optional[torch.Tensor] = None, *,
+               rows: Optional[RowFilter] = None, query_keys: Optional[torch.Tensor] = None,
+               match: str = "==") -> Tuple[torch.Tensor, torch.Tensor]:
         """`IVFPQIndex.search`.  With probes None the index probes by itself and the coarse term is the score
         `xsim.topk_normalized` returns beside every list number: no extra work.  With probes given, coarse is None (computed
         by `coarse_scores`; its bits may differ from the probe's own in the last place) or device fp32 [nq, nprobe], the
-        query's score against the centroid of every probed list.  refine: re-scores against the original rows, unchanged."""
-        return self._checked_search(q, k, nprobe, probes, refine, coarse)
+        query's score against the centroid of every probed list.  refine: re-scores against the original rows, unchanged.
+        rows, query_keys, match: the filter of `IVFFlatIndex.search`."""
+        return self._checked_search(q, k, nprobe, probes, refine, coarse, rows, query_keys, match)
 
     def state_dict(self) -> Dict[str, torch.Tensor]:
         state = super().state_dict()
