@@ -1278,6 +1278,49 @@ int smi_relpos_attention(const void* qkv_f16, const int32_t* cu_seqlens, const v
                          const float* u_bias, const float* v_bias, void* ctx_f16, int32_t n, int32_t max_len, int32_t d,
                          int32_t heads, int32_t tile_major, void* stream);
 
+/* The row kernels of the speech encoder and the text decoder, one call each (exported for the kernel-level parity tests,
+ * tests/test_gpu_row_kernels.py).  All pointers are device memory; cu: int32 [n+1] row offsets of the packed clips.  Widths: d in
+ * {256, 512, 768, 1024, 2048} for the LayerNorms, d % 256 == 0 for the conv, head_dim = 64 for the attentions;
+ * anything else is SMI_ERR_UNSUPPORTED.  Rows that no clip owns are neither read nor written. */
+/* Frame stacking + LayerNorm: out[cu[i] + j][0 .. 2nb) = f16(LN(fbank[i][2j][:] | fbank[i][2j+1][:]) * w + b) for j < cu[i+1] - cu[i],
+ * columns 2nb .. ldo-1 zero; fbank fp32 [n][t][nb], w / b fp32 [2nb], out f16 [rows][ldo]; 2nb <= ldo <= 192, max_len >= the longest
+ * stacked clip. */
+int smi_stack_ln(const float* fbank, int32_t n, int32_t t, int32_t nb, const int32_t* cu, int32_t max_len, const float* w,
+                 const float* b, float eps, void* out_f16, int32_t ldo, void* stream);
+/* x <- LN(x) * w1 + b1 in place (x_dtype SMI_F32 or SMI_F16); h = f16(w2 ? LN(x) * w2 + b2 : x), or nothing with h NULL.  With an
+ * fp16 stream the second LayerNorm sees the rounded values the stream holds.  layout bit 0: h tile-major, bit 1: x tile-major
+ * (fp16 stream, d % 512 == 0; (rows+255)/256*256 rows allocated for a tile-major buffer). */
+int smi_ln2(void* x, int32_t x_dtype, const float* w1, const float* b1, const float* w2_or_null, const float* b2_or_null, float eps,
+            void* h_f16_or_null, int32_t rows, int32_t d, int32_t layout, void* stream);
+/* The conformer's depthwise convolution + BatchNorm (folded to scale / shift) + SiLU over packed clips:
+ * y[t][c] = f16(silu(scale[c] * sum_k w16[c][k] * x[t + k - (ktaps-1)/2][c] + shift[c])), frames outside the clip are zero.
+ * PRECISION CONTRACT: the taps w (fp32 [d][ktaps]) are rounded to fp16 (w16) whatever the model dtype, like every GEMM weight of the
+ * engine; the products w16 * x are exact and accumulate in fp32.  x, y: f16 [rows][d]; ktaps 7 or 31; d % 256 == 0;
+ * layout bit 0: y tile-major, bit 1: x tile-major. */
+int smi_dwconv_bn_silu(const void* x_f16, const int32_t* cu, const float* w, const float* scale, const float* shift, void* y_f16,
+                       int32_t n, int32_t max_len, int32_t d, int32_t ktaps, int32_t layout, void* stream);
+/* The attention pooler: one query per clip and head over the clip's frames, scores / 8.  q: f16 [n][d]; kv: f16 [rows][2d] (k | v);
+ * ctx: f16 [n][d]; a clip of length 0 yields zeros. */
+int smi_pool_attention(const void* q_f16, const void* kv_f16, const int32_t* cu, void* ctx_f16, int32_t n, int32_t d, int32_t heads,
+                       void* stream);
+/* x <- x + sum_z parts[z] (+ c[row / group]) in fp32, in that order, ONE rounding for an fp16 stream; h = f16(LN(x) * w + b) of the
+ * stored row.  parts: nparts slabs of x's shape, part_stride ELEMENTS apart (parts_dtype SMI_F32 or SMI_F16), or NULL with
+ * nparts == 0; c: fp32 [ceil(rows / group)][d] or NULL; prefetch: prefetch_bytes of device memory that surplus workgroups pull into
+ * the cache (no effect on x or h), or NULL. */
+int smi_sum_layernorm(void* x, int32_t x_dtype, const void* parts_or_null, int32_t parts_dtype, int32_t nparts, int64_t part_stride,
+                      const float* c_or_null, int32_t group, const float* w, const float* b, float eps, void* h_f16, int32_t rows,
+                      int32_t d, int32_t h_tile_major, const void* prefetch_or_null, int64_t prefetch_bytes, void* stream);
+/* Single-query attention of the decode step at position pos.  kv: f16 [pos+1][rows_pad][3d] (q | k | v slabs, one per position);
+ * anc: int32 [rows][anc_stride], anc[r][j] = the row of slab j that holds hypothesis r's position j < pos (anc_stride >= pos);
+ * the query is q of slab pos, row r; key / value j < pos are row anc[r][j] of slab j, key / value pos row r of slab pos;
+ * scores / 8; ctx: f16 [rows][d]. */
+int smi_dec_attention(const void* kv_f16, const int32_t* anc, int32_t anc_stride, void* ctx_f16, int32_t rows, int32_t rows_pad,
+                      int32_t d, int32_t heads, int32_t pos, void* stream);
+/* Causal self-attention of the teacher-forced rows: nseq sequences of seq rows each (cu = [0, seq, 2 seq, ...]), query i of a
+ * sequence sees its keys 0..i; qkv: f16 [nseq*seq][3d]; ctx: f16 [nseq*seq][d], both row-major. */
+int smi_causal_attention(const void* qkv_f16, const int32_t* cu, void* ctx_f16, int32_t nseq, int32_t seq, int32_t d, int32_t heads,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -453,6 +453,14 @@ SYMBOLS = {
     "smi_layernorm": (C.c_int, [_vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
     "smi_attention": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "smi_relpos_attention": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "smi_stack_ln": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _f32, _vp, _i32, _vp]),
+    "smi_ln2": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp]),
+    "smi_dwconv_bn_silu": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "smi_pool_attention": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "smi_sum_layernorm": (C.c_int, [_vp, _i32, _vp, _i32, _i32, _i64, _vp, _i32, _vp, _vp, _f32, _vp, _i32, _i32, _i32, _vp, _i64,
+                                    _vp]),
+    "smi_dec_attention": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
+    "smi_causal_attention": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

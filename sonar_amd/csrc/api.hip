@@ -954,5 +954,95 @@ int smi_relpos_attention(const void* qkv, const int32_t* cu, const void* rp, int
   return SMI_OK;
 }
 
+// The row kernels of the speech encoder and the decoder as building blocks.  Everything a launcher would refuse with
+// hipErrorInvalidValue -- and what launch_dec_attention does not look at -- is decided here, before the device is asked for.
+static bool ln_width_ok(int d) { return d == 256 || d == 512 || d == 768 || d == 1024 || d == 2048; }  // ln_core.hpp: dispatch_nv
+static bool row_dtype_ok(int dt) { return dt == SMI_F32 || dt == SMI_F16; }
+
+int smi_stack_ln(const float* fbank, int32_t n, int32_t t, int32_t nb, const int32_t* cu, int32_t max_len, const float* w,
+                 const float* b, float eps, void* out, int32_t ldo, void* stream) {
+  if (!fbank || !cu || !w || !b || !out) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (n <= 0 || t <= 0 || nb <= 0 || max_len <= 0 || ldo < 2 * nb)
+    return fail(SMI_ERR_INVALID_ARG, "stack_ln n=%d t=%d nb=%d max_len=%d ldo=%d", n, t, nb, max_len, ldo);
+  if (2 * nb > 192 || ldo > 192) return fail(SMI_ERR_UNSUPPORTED, "stack_ln takes 2 nb <= ldo <= 192 (nb=%d ldo=%d)", nb, ldo);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_stack_ln(fbank, n, t, nb, cu, max_len, w, b, eps, (f16*)out, ldo, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_ln2(void* x, int32_t x_dtype, const float* w1, const float* b1, const float* w2, const float* b2, float eps, void* h,
+            int32_t rows, int32_t d, int32_t layout, void* stream) {
+  if (!x || !w1 || !b1 || (!w2) != (!b2)) return fail(SMI_ERR_INVALID_ARG, "null argument (w2 and b2 come together)");
+  if (!row_dtype_ok(x_dtype) || rows <= 0 || layout < 0 || layout > 3)
+    return fail(SMI_ERR_INVALID_ARG, "ln2 x_dtype=%d rows=%d layout=%d", x_dtype, rows, layout);
+  if (!ln_width_ok(d)) return fail(SMI_ERR_UNSUPPORTED, "ln2 d=%d unsupported", d);
+  if ((layout & 2) && (x_dtype != SMI_F16 || d % 512))
+    return fail(SMI_ERR_UNSUPPORTED, "ln2: a tile-major stream is fp16 with d %% 512 == 0 (x_dtype=%d d=%d)", x_dtype, d);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_ln2(x, w1, b1, w2, b2, eps, (f16*)h, rows, d, (hipStream_t)stream, layout & 1, x_dtype == SMI_F16, (layout >> 1) & 1));
+  return SMI_OK;
+}
+
+int smi_dwconv_bn_silu(const void* x, const int32_t* cu, const float* w, const float* scale, const float* shift, void* y, int32_t n,
+                       int32_t max_len, int32_t d, int32_t ktaps, int32_t layout, void* stream) {
+  if (!x || !cu || !w || !scale || !shift || !y) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (n <= 0 || max_len <= 0 || layout < 0 || layout > 3)
+    return fail(SMI_ERR_INVALID_ARG, "dwconv n=%d max_len=%d layout=%d", n, max_len, layout);
+  if (d <= 0 || d % 256 || (ktaps != 7 && ktaps != 31))
+    return fail(SMI_ERR_UNSUPPORTED, "dwconv takes d %% 256 == 0 and 7 or 31 taps (d=%d ktaps=%d)", d, ktaps);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_dwconv_bn_silu((const f16*)x, cu, w, scale, shift, (f16*)y, n, max_len, d, ktaps, (hipStream_t)stream, layout & 1,
+                                (layout >> 1) & 1));
+  return SMI_OK;
+}
+
+int smi_pool_attention(const void* q, const void* kv, const int32_t* cu, void* ctx, int32_t n, int32_t d, int32_t heads,
+                       void* stream) {
+  if (!q || !kv || !cu || !ctx) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (n <= 0) return fail(SMI_ERR_INVALID_ARG, "pool_attention n=%d", n);
+  if (heads <= 0 || d != heads * 64) return fail(SMI_ERR_UNSUPPORTED, "head_dim must be 64");
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_pool_attention((const f16*)q, (const f16*)kv, cu, (f16*)ctx, n, d, heads, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_sum_layernorm(void* x, int32_t x_dtype, const void* parts, int32_t parts_dtype, int32_t nparts, int64_t part_stride,
+                      const float* c, int32_t group, const float* w, const float* b, float eps, void* h, int32_t rows, int32_t d,
+                      int32_t h_tile_major, const void* prefetch, int64_t prefetch_bytes, void* stream) {
+  if (!x || !w || !b || !h) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (!row_dtype_ok(x_dtype) || !row_dtype_ok(parts_dtype) || rows <= 0 || nparts < 0 || (nparts > 0 && !parts) ||
+      (c && group < 1) || prefetch_bytes < 0 || (prefetch_bytes > 0 && !prefetch))
+    return fail(SMI_ERR_INVALID_ARG, "sum_layernorm x_dtype=%d parts_dtype=%d rows=%d nparts=%d (parts %s) group=%d prefetch_bytes=%lld",
+                x_dtype, parts_dtype, rows, nparts, parts ? "given" : "null", group, (long long)prefetch_bytes);
+  if (!ln_width_ok(d)) return fail(SMI_ERR_UNSUPPORTED, "sum_layernorm d=%d unsupported", d);
+  if (nparts > 1 && part_stride < (int64_t)rows * d)
+    return fail(SMI_ERR_INVALID_ARG, "sum_layernorm: slabs %lld elements apart overlap (rows=%d d=%d)", (long long)part_stride, rows, d);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_sum_layernorm(x, parts, nparts, (size_t)part_stride, c, c ? group : 1, w, b, eps, (f16*)h, rows, d, (hipStream_t)stream,
+                               h_tile_major != 0, x_dtype == SMI_F16, prefetch, (size_t)prefetch_bytes, parts_dtype == SMI_F16));
+  return SMI_OK;
+}
+
+int smi_dec_attention(const void* kv, const int32_t* anc, int32_t anc_stride, void* ctx, int32_t rows, int32_t rows_pad, int32_t d,
+                      int32_t heads, int32_t pos, void* stream) {
+  if (!kv || !ctx || (!anc && pos > 0)) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (heads <= 0 || d != heads * 64) return fail(SMI_ERR_UNSUPPORTED, "head_dim must be 64");
+  if (pos < 0 || rows < 1 || rows > rows_pad || anc_stride < pos)
+    return fail(SMI_ERR_INVALID_ARG, "dec_attention rows=%d rows_pad=%d pos=%d anc_stride=%d", rows, rows_pad, pos, anc_stride);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_dec_attention((const f16*)kv, anc, anc_stride, (f16*)ctx, rows, rows_pad, d, heads, pos, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_causal_attention(const void* qkv, const int32_t* cu, void* ctx, int32_t nseq, int32_t seq, int32_t d, int32_t heads,
+                         void* stream) {
+  if (!qkv || !cu || !ctx) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (nseq <= 0 || seq <= 0) return fail(SMI_ERR_INVALID_ARG, "causal_attention nseq=%d seq=%d", nseq, seq);
+  if (heads <= 0 || d != heads * 64) return fail(SMI_ERR_UNSUPPORTED, "head_dim must be 64");
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_causal_attention((const f16*)qkv, cu, (f16*)ctx, nseq, seq, d, heads, (hipStream_t)stream));
+  return SMI_OK;
+}
+
 
 }  // extern "C"

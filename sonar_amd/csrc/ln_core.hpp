@@ -5,6 +5,10 @@
 //   mean = sum / d;  v -= mean in place;  var = sum(v * v) / d  (biased, of the CENTRED values: two passes over registers)
 //   rstd = 1 / sqrt(var + eps);  y = v * rstd * w + b
 // row_sum is the cross-lane sum of the lanes that share a row: wave_sum, half_sum (common.hpp) or pair_sum (rowops.hip).
+// Accuracy: the fp32 mean is off by a few ulp of mean_i |x_i|, and that offset shifts EVERY centred value, so
+//   |y - exact| <~ 2^-20 (|w| (|x - mean| + mean_i |x_i|) rstd + |b|)
+// -- not 2^-20 (|w| |x - mean| rstd + |b|): where x ~ mean and b ~ 0 the offset of the mean is all there is.  Under an fp16
+// rounding of y the difference does not show (tests/test_gpu_row_kernels.py: rule T, and the fp32 stream of ln2).
 #pragma once
 #include <type_traits>
 

@@ -323,7 +323,8 @@ hipError_t launch_stack_ln(const float* fb, int n, int t, int nb, const int32_t*
 }
 
 // =============================================================== LayerNorm variants (fp32 stream)
-// x = LN1(x) in place (fp32); h = f16(w2 ? LN2(x) : x).  One wave per row.
+// x = LN1(x) in place (fp32); h = f16(w2 ? LN2(x) : x).  One wave per row.  (The fp32 x written back carries the accuracy
+// stated in ln_core.hpp -- the mean's rounding included; an fp16 x is that rounded once.)
 template <int NV, bool TM, typename XT>
 __global__ __launch_bounds__(256) void ln2_kernel(XT* __restrict__ x, const float* __restrict__ w1,
                                                   const float* __restrict__ b1,
