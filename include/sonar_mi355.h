@@ -991,6 +991,30 @@ int smi_ivf_pq_search_residual(const void* qn_f16, int64_t nq, int32_t d, const 
                                const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx,
                                float* score, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Gram / cross-moment matrix of fp16 rows in fp64 (restated in tests/transforms_ref.py): what a PCA
+ * diagonalises and what an OPQ Procrustes step decomposes (sonar_amd/transforms.py), contracted over the rows of a corpus.
+ *
+ * smi_gram: out[i][j] = sum over r < n of x[r][i] * y[r][j].  x contiguous fp16 [>= n, d1], y contiguous fp16 [>= n, d2] or
+ *   NULL (y = x, d2 == d1), out device fp64 [d1, d2], overwritten.  Nothing is read back or allocated.
+ * Numerics: the rows are cut into chunks of SMI_GRAM_CHUNK_ROWS consecutive rows.  Inside a chunk every product is exact (a
+ *   product of two fp16 values is exact in fp32) and the sums are the fp32 accumulation of v_mfma_f32_16x16x32_f16 over the
+ *   chunk's 32-row steps in ascending order.  A chunk's result is widened to fp64; the chunks of a span (a run of consecutive
+ *   chunks whose length is a function of n alone) are added in ascending order and then the spans in ascending order.  The
+ *   bits of out depend on (x, y, n) and the constant only: not on the CU count, the grid, the run, or the rows beyond n in
+ *   the allocation.  No atomics.  Inf and NaN propagate; nothing is read at or beyond row n.  With y == NULL only the tiles on
+ *   or above the diagonal are computed and an element below it is a copy of its mirror image: out is bitwise symmetric.
+ *   Integer-valued operands whose chunk sums stay below 2^24 give the exact integer result.
+ * workspace: device memory, 16-byte aligned, smi_gram_ws_bytes(n, d1, d2) bytes (one fp64 128 x 128 partial per span and tile;
+ *   at most 32 spans).  The symmetric form fills only the T (T + 1) / 2 tile slots of the upper triangle, T = ceil(d / 128), and
+ *   is content with smi_gram_ws_bytes(n, d, d) / T^2 * T (T + 1) / 2 bytes (an exact division).
+ * Refused before any launch: null x, out or workspace, n < 1, y == NULL with d1 != d2, a small or misaligned workspace
+ *   (SMI_ERR_INVALID_ARG); d1 or d2 below 64, not a multiple of 64 or above 8192, n above 2^31 - 256 (SMI_ERR_UNSUPPORTED).
+ *   For these shapes smi_gram_ws_bytes returns 0. */
+#define SMI_GRAM_CHUNK_ROWS 2048
+int64_t smi_gram_ws_bytes(int64_t n, int32_t d1, int32_t d2);
+int smi_gram(const void* x_f16, const void* y_f16, int64_t n, int32_t d1, int32_t d2, double* out, void* workspace,
+             int64_t workspace_bytes, void* stream);
+
 /* Embedding heads: BLASER / MuTox ---------------------------------------------
  * A small MLP over (features of) sentence embeddings.  Replaces
  *   BlaserModel.forward = F.normalize -> featurize_input -> mlp   sonar/models/blaser/model.py:82-125

@@ -412,6 +412,8 @@ SYMBOLS = {
                                             _vp]),
     "smi_ivf_pq_search_residual": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
                                              _vp, _i64, _vp]),
+    "smi_gram_ws_bytes": (_i64, [_i64, _i32, _i32]),
+    "smi_gram": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
     "smi_gemm_tn": (C.c_int, [_i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "smi_gemm_tn_tile_stats": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, C.c_float, _i32, _vp, _vp, _vp]),
     "smi_gemm_tn_splitk": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),

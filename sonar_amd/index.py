@@ -45,7 +45,10 @@ query's filtered result is, bit for bit, its unfiltered result over an index tha
   a cut-off date                   keys = dates, query_keys = the query's cut-off, match "<"
   rows to be ignored               mask = False for them: the only removal there is, as the index is built once
 
-Not here: an OPQ rotation, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, nprobe or
+`PreTransformIndex` puts a learned linear transform (`sonar_amd.transforms`: a PCA that cuts the dimension, an OPQ rotation in
+front of the sub-quantisers) in front of any of the four classes, FAISS's `IndexPreTransform`.
+
+Not here: a look-up-table scan for a handful of queries, codes of fewer than 8 bits, nprobe or
 k above 8, de-duplication or range search over quantised lists, incremental add and removal, 64-bit ids, splitting of long
 lists, multi-GPU sharding; of filtering: skipping whole tiles or lists by key, per-query bitmaps or id lists, keys wider than
 32 bits, more than one key per row, a filter on the coarse probe.
@@ -1150,3 +1153,92 @@ def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Te
     cos, idx = torch.gather(cos, 1, by_id), torch.gather(idx, 1, by_id)
     order = torch.sort(cos, dim=1, descending=True, stable=True)[1]
     return torch.gather(cos, 1, order), torch.gather(idx, 1, order)
+
+
+class PreTransformIndex:
+    """An index behind a linear transform (FAISS's `IndexPreTransform`): `add` stores
+    `transform.apply(x)`, every query is transformed once, and the wrapped index does the rest, unchanged -- a wrapped search
+    equals `index.search(transform.apply(q), ...)` bit for bit, and every argument of the wrapped class passes through.
+
+    transform: a `sonar_amd.transforms.LinearTransform` (`PCA`, `OPQ`) whose d_out is the index's dim; index: one of the four
+    IVF classes, before or after its `add`."""
+
+    def __init__(self, transform, index: _IVFIndex):
+        from .transforms import LinearTransform
+
+        if not isinstance(transform, LinearTransform):
+            raise TypeError("transform must be a sonar_amd.transforms.LinearTransform")
+        if not isinstance(index, _IVFIndex):
+            raise TypeError("index must be an IVFFlatIndex, IVFInt8Index, IVFPQIndex or IVFPQResidualIndex")
+        if transform.d_out != index.dim:
+            raise ValueError(f"the transform gives dim {transform.d_out}, the index takes {index.dim}")
+        self.transform, self.index = transform, index
+
+    @property
+    def dim(self) -> int:
+        """The dimension of the rows and queries this index takes: the transform's d_in."""
+        return self.transform.d_in
+
+    @property
+    def n_lists(self) -> int:
+        return self.index.n_lists
+
+    @property
+    def ntotal(self) -> int:
+        return self.index.ntotal
+
+    @property
+    def list_sizes(self) -> torch.Tensor:
+        return self.index.list_sizes
+
+    @property
+    def list_offsets(self) -> torch.Tensor:
+        return self.index.list_offsets
+
+    def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None):
+        """`index.add(transform.apply(x), labels)`; x fp16 / fp32 [n, d_in] on the device."""
+        self.index.add(self.transform.apply(x), labels)
+        return self
+
+    def probe(self, q: torch.Tensor, nprobe: int = 1) -> torch.Tensor:
+        return self.index.probe(self.transform.apply(q), nprobe)
+
+    def row_filter(self, keys: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> RowFilter:
+        return self.index.row_filter(keys, mask)
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None, *,
+               refine: Optional[torch.Tensor] = None, **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`index.search(transform.apply(q), k, nprobe, probes, **kwargs)`; q fp16 / fp32 [nq, d_in] on the device.  Whatever
+        the wrapped class takes behind probes (coarse, rows, query_keys, match) goes by keyword.
+
+        refine (by keyword, on every wrapped class): None, or the normalised fp16 corpus in the ORIGINAL space
+        (`normalize_rows(x)` of the x `add` was given, [rows, d_in]): the candidates of the wrapped search are re-scored with
+        the cosines of the untransformed q against those rows and re-ordered (`refine_candidates`), so the scores are what
+        `xsim.topk` would return for the pair, whatever the transform lost.  The wrapped class's own `refine` (re-scoring in
+        the transformed space, against the transformed corpus) is not reachable through the wrapper: call
+        `index.search(transform.apply(q), ..., refine=)` for that."""
+        if refine is not None:
+            _check_refine(refine, self.dim)
+        qt = self.transform.apply(q)
+        score, idx = self.index.search(qt, k, nprobe, probes, **kwargs)
+        return (score, idx) if refine is None else refine_candidates(normalize_rows(q), q.shape[0], refine, idx)
+
+    def range_search(self, q: torch.Tensor, *args, **kwargs) -> RangeResult:
+        """`index.range_search(transform.apply(q), ...)`: the thresholds are cosines in the transformed space."""
+        return self.index.range_search(self.transform.apply(q), *args, **kwargs)
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """The transform's state under `transform.*` and the index's under `index.*`."""
+        return {**{"transform." + k: v for k, v in self.transform.state_dict().items()},
+                **{"index." + k: v for k, v in self.index.state_dict().items()}}
+
+    @classmethod
+    def from_state_dict(cls, state: Dict[str, torch.Tensor], index_cls):
+        """index_cls: the class of the wrapped index (its state does not name it).  The transform comes back as a plain
+        `LinearTransform` with the same bits."""
+        from .transforms import LinearTransform
+
+        if not (isinstance(index_cls, type) and issubclass(index_cls, _IVFIndex)):
+            raise TypeError("index_cls must be one of the IVF index classes")
+        part = lambda prefix: {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)}
+        return cls(LinearTransform.from_state_dict(part("transform.")), index_cls.from_state_dict(part("index.")))
