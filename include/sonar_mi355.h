@@ -229,7 +229,8 @@ typedef struct smi_text_decoder_config {
   int32_t input_dim;     /* conditioning vector dimension (config.py input_dim; model_dim when unset) */
   float embed_scale;     /* sqrt(model_dim) */
   float ln_eps;          /* 1e-5 */
-  int32_t pad_idx, unk_idx, bos_idx, eos_idx; /* TOKENIZER ids: 0, 1, 2, 3 */
+  int32_t pad_idx, unk_idx, bos_idx, eos_idx; /* TOKENIZER ids: 0, 1, 2, 3.  pad / unk (-1 = none) and eos must be below 256 and
+                                               * below vocab_size (SPECIAL IDS at smi_vocab_select), else SMI_ERR_UNSUPPORTED */
 } smi_text_decoder_config;
 
 /* encoder_decoder_attn q/k projections and its LayerNorm are not needed: the encoder output is
@@ -379,7 +380,8 @@ int smi_text_decoder_set_step_processors(smi_text_decoder* dec, const smi_step_p
 /* The beam search's vocabulary selection under step processors on given logits, for the parity tests: logits device fp32
  * [rows, ldl] row-major, or (logits_f16_tm) fp16 in the tile-major layout with K = ldl; tile_max / tile_sum device fp32
  * [ldl / 256][rows] (per 256-column tile: maximum and sum of exp(v - maximum)); hist device int32 [rows, hist_stride], row r's
- * sequence so far hist[r][0 .. hist_len); pad_idx (-1 = none) is never a candidate.  Outputs (device): pval fp32 / pidx
+ * sequence so far hist[r][0 .. hist_len); pad_idx (-1 = none, else below 256 and below vocab: SPECIAL IDS at smi_vocab_select) is
+ * never a candidate.  Outputs (device): pval fp32 / pidx
  * int32 [rows, 16], the first k2 (<= 16) entries = the top-k2 of the masked row (value desc, token asc; -inf / INT32_MAX
  * when fewer remain), and pmax / psum fp32 [rows], the untouched row's softmax normaliser.  With no processor active the
  * engine's default selection runs, as in smi_text_decoder_generate. */
@@ -1344,6 +1346,122 @@ int smi_dec_attention(const void* kv_f16, const int32_t* anc, int32_t anc_stride
  * sequence sees its keys 0..i; qkv: f16 [nseq*seq][3d]; ctx: f16 [nseq*seq][d], both row-major. */
 int smi_causal_attention(const void* qkv_f16, const int32_t* cu, void* ctx_f16, int32_t nseq, int32_t seq, int32_t d, int32_t heads,
                          void* stream);
+
+/* The beam search's state kernels on caller-owned device arrays, one call each (exported for the kernel-level tests,
+ * tests/test_gpu_beam_kernels.py; the launchers are those of smi_text_decoder_generate).  Every pointer is device memory.
+ *
+ * SPECIAL IDS.  The selection reads tile 0 (ids 0..255) and the k2 tiles of largest raw maximum.  That holds every candidate only
+ * when the ids the masks touch -- PAD, EOS (blocked before min_seq_len), UNK (penalised) -- live in tile 0: a masked id that is the
+ * maximum of a later tile would take a slot from a tile that holds a real candidate.  So pad_idx, eos_idx and unk_idx must be below
+ * 256 (-1 = none, where an entry allows it); smi_text_decoder_create, smi_vocab_select and smi_vocab_select_banned refuse anything
+ * else with SMI_ERR_UNSUPPORTED before the device is asked for.
+ *
+ * A per-sentence prompt table (tok NULL = none, the scalar arguments hold): sentence s has prompt tok[s][0 .. len[s]), len[s] >= 1,
+ * its cap max_len_s = min(len[s] + gen_cap, model_max) and min_len_s = min(len[s] + min_gen, max_len_s).  At the step that chooses
+ * token step_nr it is forced to tok[s][step_nr] while step_nr < len[s], forced to EOS at step_nr == max_len_s - 1, free before that
+ * (EOS blocked while step_nr < min_len_s), and past its cap it does nothing.  The caller keeps len[s] <= stride and the prompt ids
+ * inside the vocabulary: the table is device memory and is not read on the host. */
+typedef struct smi_prompt_table {
+  const int32_t* tok; /* [n][stride], left-aligned */
+  const int32_t* len; /* [n] */
+  int32_t stride, gen_cap, min_gen, model_max;
+} smi_prompt_table;
+
+/* The selection of one step.  logits: fp32 [rows][ldl] row-major, or (logits_f16_tm) fp16 tile-major with K = ldl in a buffer of
+ * (rows + 255) / 256 * 256 rows; ldl a multiple of 256 >= vocab, at most 2048 tiles.  tile_max / tile_sum: fp32 [ldl / 256][stat_rows], per 256-column tile
+ * of logits * inv_temp the maximum and the sum of exp(v - maximum) (columns >= vocab excluded).  Outputs: pmax / psum [rows], the
+ * row's softmax normaliser (pmax = the row maximum, bit for bit); pval / pidx [rows][16], the first k2 entries = the row's best
+ * candidates (value desc, token asc), value = logits * inv_temp (- unk_penalty for unk_idx) in fp32, where pad_idx, columns >= vocab,
+ * -inf and -- block_eos -- eos_idx are no candidates; (-inf, INT32_MAX) fills a shorter list.  k2 = 0 writes pmax / psum only.  With
+ * a table, row r belongs to sentence r / group: block_eos is its sentence's at step_nr (the argument is not read), and a row whose
+ * sentence is not free there gets pmax / psum only. */
+typedef struct smi_vocab_select_args {
+  const void* logits;
+  int32_t ldl, logits_f16_tm, rows, vocab;
+  const float* tile_max;
+  const float* tile_sum;
+  int32_t stat_rows; /* >= rows */
+  int32_t k2;        /* 0..16 */
+  float inv_temp;    /* > 0 */
+  int32_t pad_idx, eos_idx, unk_idx; /* -1 = none; below 256 and below vocab */
+  float unk_penalty;
+  int32_t block_eos;
+  float* pmax;
+  float* psum;
+  float* pval;
+  int32_t* pidx;
+  smi_prompt_table table;
+  int32_t group, step_nr; /* read with a table: group >= 1, step_nr >= 1 */
+} smi_vocab_select_args;
+int smi_vocab_select(const smi_vocab_select_args* args, void* stream);
+
+/* The state of a search over n sentences x beam rows (row r = sentence r / beam), stride int32 per row of history.
+ *   tok / cum [n*beam]: the token fed at the current position and the cumulative log-probability of each row;
+ *   nactive / done / fin_count [n], ndone [1]: live rows (rows >= nactive[s] of a sentence are never read), finished flag,
+ *     finished hypotheses, number of finished sentences;
+ *   parent / new_tok / new_cum [n*beam]: what a step decides, consumed by the reorder;
+ *   fin_tok [n*beam][stride], fin_len / fin_score [n*beam]: finished hypotheses in the order they finished (generated tokens + EOS);
+ *   margins [n][2] or NULL: smallest gap between neighbours of a step's sorted candidate list up to the first one not consumed,
+ *     and (written by the output, for >= 2 hypotheses) best minus second finished score;
+ *   anc[2] / hist[2] [n*beam][stride]: ancestry (row of position j's slab) and tokens; position pos reads buffer pos & 1 and the
+ *     reorder writes the other one. */
+typedef struct smi_beam_state {
+  int32_t* tok;
+  float* cum;
+  int32_t* nactive;
+  int32_t* done;
+  int32_t* ndone;
+  int32_t* parent;
+  int32_t* new_tok;
+  float* new_cum;
+  int32_t* fin_tok;
+  int32_t* fin_len;
+  float* fin_score;
+  int32_t* fin_count;
+  float* margins;
+  int32_t* anc[2];
+  int32_t* hist[2];
+  int32_t n, beam, stride; /* beam 1..8 */
+} smi_beam_state;
+
+/* tok = hist[0][r][0] = first_tok (or first_toks[(r / beam) * first_stride] when given), cum = 0, anc[0][r][0] = r, nactive = 1,
+ * done = fin_count = ndone = 0, margins = +inf. */
+int smi_beam_init(const smi_beam_state* st, int32_t first_tok, const int32_t* first_toks_or_null, int32_t first_stride, void* stream);
+
+/* One beam step at position pos (it chooses token step_nr = pos + 1) from what smi_vocab_select left.  Per sentence:
+ *   done: parent = the row itself, new_tok = tok, new_cum = cum (the rows are inert), nothing else is written;
+ *   forced prompt token (step_nr < prompt_len): every live row takes forced_tok, new_cum = cum + logit * inv_temp - lse;
+ *   forced EOS (step_nr == max_len - 1): the live rows finish in order (score desc, row asc) until `beam` have, the sentence is done;
+ *   free: the candidates cum + pval - lse of the live rows' lists, ordered score desc, row asc, token asc (-inf is none).  An EOS among
+ *     the first `beam` of them finishes its row (in that order; the `beam`-th finished hypothesis ends the sentence at once, inert
+ *     rows as above); otherwise the first `beam` non-EOS candidates of the first 2 beam continue, nactive = their number, and a
+ *     spare slot keeps parent = itself, new_tok = tok, new_cum = -inf.
+ * lse = pmax + log(psum) (fast log); fin_score = score / (step_nr ^ len_penalty) with normalize, else the score.
+ * k2 must be 2 * beam; stride >= pos + 2; eos_idx (and forced_tok on a forced step) inside [0, vocab).  With a table, prompt_len /
+ * forced_tok / max_len are the sentence's own and the scalars are not read. */
+typedef struct smi_beam_step_args {
+  const void* logits;
+  int32_t ldl, logits_f16_tm, vocab;
+  const float* pmax;
+  const float* psum;
+  const float* pval;
+  const int32_t* pidx;
+  int32_t k2, pos, prompt_len, forced_tok, max_len;
+  float inv_temp, len_penalty;
+  int32_t normalize, eos_idx;
+  smi_prompt_table table;
+} smi_beam_step_args;
+int smi_beam_step(const smi_beam_state* st, const smi_beam_step_args* args, void* stream);
+
+/* The reorder after the step at pos, from buffer c = pos & 1 to the other: anc'[r][j] = anc[parent[r]][j] (j < pos), anc'[r][pos] =
+ * parent[r]; hist'[r][j] = hist[parent[r]][j] (j <= pos), hist'[r][pos + 1] = new_tok[r]; tok = new_tok, cum = new_cum.  Positions
+ * beyond pos + 1 of the destination are not written.  stride >= pos + 2; parent must hold row numbers (a step wrote them). */
+int smi_beam_reorder(const smi_beam_state* st, int32_t pos, void* stream);
+
+/* The finished hypotheses of each sentence, best first (stable: equal scores keep the order they finished in): out_tok
+ * [n*beam][out_stride] (-1 beyond the length; fin_len <= out_stride), out_len / out_score [n*beam]; a slot past fin_count is -1 /
+ * length 0 / score -inf.  margins[s][1] is written when the sentence has >= 2 hypotheses. */
+int smi_beam_output(const smi_beam_state* st, int32_t out_stride, int32_t* out_tok, int32_t* out_len, float* out_score, void* stream);
 
 #ifdef __cplusplus
 }

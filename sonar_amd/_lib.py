@@ -198,6 +198,78 @@ class smi_step_processors(C.Structure):
     ]
 
 
+class smi_prompt_table(C.Structure):
+    _fields_ = [
+        ("tok", C.c_void_p),
+        ("len", C.c_void_p),
+        ("stride", C.c_int32),
+        ("gen_cap", C.c_int32),
+        ("min_gen", C.c_int32),
+        ("model_max", C.c_int32),
+    ]
+
+
+class smi_vocab_select_args(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p),
+        ("ldl", C.c_int32),
+        ("logits_f16_tm", C.c_int32),
+        ("rows", C.c_int32),
+        ("vocab", C.c_int32),
+        ("tile_max", C.c_void_p),
+        ("tile_sum", C.c_void_p),
+        ("stat_rows", C.c_int32),
+        ("k2", C.c_int32),
+        ("inv_temp", C.c_float),
+        ("pad_idx", C.c_int32),
+        ("eos_idx", C.c_int32),
+        ("unk_idx", C.c_int32),
+        ("unk_penalty", C.c_float),
+        ("block_eos", C.c_int32),
+        ("pmax", C.c_void_p),
+        ("psum", C.c_void_p),
+        ("pval", C.c_void_p),
+        ("pidx", C.c_void_p),
+        ("table", smi_prompt_table),
+        ("group", C.c_int32),
+        ("step_nr", C.c_int32),
+    ]
+
+
+class smi_beam_state(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in ("tok", "cum", "nactive", "done", "ndone", "parent", "new_tok", "new_cum", "fin_tok",
+                                                "fin_len", "fin_score", "fin_count", "margins")] + [
+        ("anc", C.c_void_p * 2),
+        ("hist", C.c_void_p * 2),
+        ("n", C.c_int32),
+        ("beam", C.c_int32),
+        ("stride", C.c_int32),
+    ]
+
+
+class smi_beam_step_args(C.Structure):
+    _fields_ = [
+        ("logits", C.c_void_p),
+        ("ldl", C.c_int32),
+        ("logits_f16_tm", C.c_int32),
+        ("vocab", C.c_int32),
+        ("pmax", C.c_void_p),
+        ("psum", C.c_void_p),
+        ("pval", C.c_void_p),
+        ("pidx", C.c_void_p),
+        ("k2", C.c_int32),
+        ("pos", C.c_int32),
+        ("prompt_len", C.c_int32),
+        ("forced_tok", C.c_int32),
+        ("max_len", C.c_int32),
+        ("inv_temp", C.c_float),
+        ("len_penalty", C.c_float),
+        ("normalize", C.c_int32),
+        ("eos_idx", C.c_int32),
+        ("table", smi_prompt_table),
+    ]
+
+
 def step_processors_struct(ngram_size: int, banned_seqs) -> Tuple["smi_step_processors", list]:
     """-> (smi_step_processors, keep-alive list of its host arrays) for an n-gram size (0 = off) and banned sequences."""
     seqs = [list(map(int, b)) for b in banned_seqs]
@@ -463,6 +535,11 @@ SYMBOLS = {
                                     _vp]),
     "smi_dec_attention": (C.c_int, [_vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp]),
     "smi_causal_attention": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "smi_vocab_select": (C.c_int, [C.POINTER(smi_vocab_select_args), _vp]),
+    "smi_beam_init": (C.c_int, [C.POINTER(smi_beam_state), _i32, _vp, _i32, _vp]),
+    "smi_beam_step": (C.c_int, [C.POINTER(smi_beam_state), C.POINTER(smi_beam_step_args), _vp]),
+    "smi_beam_reorder": (C.c_int, [C.POINTER(smi_beam_state), _i32, _vp]),
+    "smi_beam_output": (C.c_int, [C.POINTER(smi_beam_state), _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -102,6 +102,19 @@ struct smi_text_decoder {
 
 namespace {
 
+// The ids the selection masks (PAD, blocked EOS, penalised UNK) must live in tile 0, ids 0..255: the tile argument of
+// vocab_select_kernel ranks the later tiles by their RAW maximum, and a masked id that is a later tile's maximum would take a
+// slot from a tile that holds a real candidate (decoder.hip).  -1 = none; the EOS of a search always exists.
+int check_special_ids(int pad_idx, int eos_idx, int unk_idx, int64_t vocab, bool need_eos) {
+  const int64_t lim = vocab < 256 ? vocab : 256;
+  if (pad_idx < -1 || eos_idx < (need_eos ? 0 : -1) || unk_idx < -1)
+    return fail(SMI_ERR_INVALID_ARG, "bad special ids: pad_idx=%d eos_idx=%d unk_idx=%d", pad_idx, eos_idx, unk_idx);
+  if (pad_idx >= lim || eos_idx >= lim || unk_idx >= lim)
+    return fail(SMI_ERR_UNSUPPORTED, "special ids must be below 256 and the vocabulary: pad_idx=%d eos_idx=%d unk_idx=%d", pad_idx,
+                eos_idx, unk_idx);
+  return SMI_OK;
+}
+
 // SMI_OK and *flex = false: the MFMA engines cover the shape; *flex = true: the generic-dimension kernels do
 int check_dec_cfg(const smi_text_decoder_config& c, bool* flex) {
   if (c.model_dim <= 0 || c.num_heads <= 0 || c.model_dim % c.num_heads)
@@ -114,6 +127,7 @@ int check_dec_cfg(const smi_text_decoder_config& c, bool* flex) {
                     (c.model_dim / 256 <= 4 || c.model_dim == 2048) && c.ffn_inner_dim % 128 == 0 && c.input_dim % 64 == 0;
   if (!fast && c.model_dim / c.num_heads > 256)
     return fail(SMI_ERR_UNSUPPORTED, "head_dim %d > 256 is not covered", c.model_dim / c.num_heads);
+  if (int rc = check_special_ids(c.pad_idx, c.eos_idx, c.unk_idx, c.vocab_size, true)) return rc;
   *flex = !fast;
   return SMI_OK;
 }
@@ -1270,6 +1284,7 @@ int smi_vocab_select_banned(const void* logits, int32_t ldl, int32_t logits_f16_
     return fail(SMI_ERR_INVALID_ARG, "hist_len %d outside [1, %d] or above hist_stride %d", hist_len, kStepProcMaxLen - 1,
                 hist_stride);
   if (logits_f16_tm && rows % 256) return fail(SMI_ERR_INVALID_ARG, "tile-major logits need rows padded to 256");
+  if (int rc = check_special_ids(pad_idx, -1, -1, vocab, false)) return rc;
   if (int rc = check_step_processors(procs, vocab, kStepProcMaxLen - 1)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   StepProcTable st;
@@ -1284,6 +1299,123 @@ int smi_vocab_select_banned(const void* logits, int32_t ldl, int32_t logits_f16_
   HIP_TRY(launch_vocab_select(v, (hipStream_t)stream));
   // the CSR copies are freed on return: finish with them first
   HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  return SMI_OK;
+}
+
+// ---- the beam search's state kernels on caller-owned arrays (tests/test_gpu_beam_kernels.py): the launchers of generate_chain
+namespace {
+PromptTableDev table_dev(const smi_prompt_table& t) { return PromptTableDev{t.tok, t.len, t.stride, t.gen_cap, t.min_gen, t.model_max}; }
+int check_prompt_table(const smi_prompt_table& t) {
+  if (!t.tok) return SMI_OK;
+  if (!t.len) return fail(SMI_ERR_INVALID_ARG, "prompt table without lengths");
+  if (t.stride < 1 || t.gen_cap < 1 || t.min_gen < 0 || t.model_max < 2)
+    return fail(SMI_ERR_INVALID_ARG, "prompt table: stride=%d gen_cap=%d min_gen=%d model_max=%d", t.stride, t.gen_cap, t.min_gen,
+                t.model_max);
+  return SMI_OK;
+}
+int check_beam_state(const smi_beam_state* st) {
+  if (!st) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (!st->tok || !st->cum || !st->nactive || !st->done || !st->ndone || !st->parent || !st->new_tok || !st->new_cum || !st->fin_tok ||
+      !st->fin_len || !st->fin_score || !st->fin_count || !st->anc[0] || !st->anc[1] || !st->hist[0] || !st->hist[1])
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (st->n < 1 || st->beam < 1 || st->beam > 8 || st->stride < 2 || (int64_t)st->n * st->beam > (1 << 24))
+    return fail(SMI_ERR_INVALID_ARG, "n=%d beam=%d (1..8) stride=%d", st->n, st->beam, st->stride);
+  return SMI_OK;
+}
+// (a tile-major buffer holds (rows + 255) / 256 * 256 rows: the caller's allocation, as in generate_chain)
+int check_logits_shape(int ldl, int64_t rows, int vocab) {
+  if (rows <= 0 || vocab <= 0 || ldl % 256 || ldl < vocab || ldl / 256 > 2048)
+    return fail(SMI_ERR_INVALID_ARG, "ldl %d must be a multiple of 256 >= vocab %d, at most 2048 tiles", ldl, vocab);
+  return SMI_OK;
+}
+}  // namespace
+
+int smi_vocab_select(const smi_vocab_select_args* a, void* stream) {
+  if (!a || !a->logits || !a->tile_max || !a->tile_sum || !a->pmax || !a->psum || !a->pval || !a->pidx)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (int rc = check_logits_shape(a->ldl, a->rows, a->vocab)) return rc;
+  if (a->stat_rows < a->rows) return fail(SMI_ERR_INVALID_ARG, "stat_rows %d below rows %d", a->stat_rows, a->rows);
+  if (a->k2 < 0 || a->k2 > kVocabScanK2Max) return fail(SMI_ERR_INVALID_ARG, "k2 %d outside [0, %d]", a->k2, kVocabScanK2Max);
+  if (!(a->inv_temp > 0.f) || !std::isfinite(a->inv_temp) || !std::isfinite(a->unk_penalty))
+    return fail(SMI_ERR_INVALID_ARG, "inv_temp must be positive and finite, unk_penalty finite");
+  if (int rc = check_special_ids(a->pad_idx, a->eos_idx, a->unk_idx, a->vocab, false)) return rc;
+  if (int rc = check_prompt_table(a->table)) return rc;
+  if (a->table.tok && (a->group < 1 || a->step_nr < 1 || a->rows % a->group))
+    return fail(SMI_ERR_INVALID_ARG, "prompt table: group=%d must divide rows=%d, step_nr=%d >= 1", a->group, a->rows, a->step_nr);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  VocabSelectArgs v{};
+  v.logits = (const float*)a->logits; v.ldl = a->ldl; v.f16_tm = a->logits_f16_tm ? 1 : 0; v.rows = a->rows; v.vocab = a->vocab;
+  v.tile_max = a->tile_max; v.tile_sum = a->tile_sum; v.ntiles = a->ldl / 256; v.stat_rows = a->stat_rows;
+  v.k2 = a->k2; v.inv_temp = a->inv_temp; v.pad_idx = a->pad_idx; v.eos_idx = a->eos_idx; v.unk_idx = a->unk_idx;
+  v.unk_penalty = a->unk_penalty; v.block_eos = a->block_eos ? 1 : 0;
+  v.pmax = a->pmax; v.psum = a->psum; v.pval = a->pval; v.pidx = a->pidx;
+  if (a->table.tok) v.table = table_dev(a->table);
+  v.group = a->group; v.step_nr = a->step_nr;
+  HIP_TRY(launch_vocab_select(v, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_beam_init(const smi_beam_state* st, int32_t first_tok, const int32_t* first_toks, int32_t first_stride, void* stream) {
+  if (int rc = check_beam_state(st)) return rc;
+  if (first_toks ? first_stride < 1 : first_tok < 0)
+    return fail(SMI_ERR_INVALID_ARG, "first_tok=%d first_stride=%d", first_tok, first_stride);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_beam_init(st->tok, st->cum, st->nactive, st->done, st->ndone, st->fin_count, st->hist[0], st->anc[0], st->margins,
+                           st->n * st->beam, st->n, st->stride, first_tok, (hipStream_t)stream, first_toks, first_stride, st->beam));
+  return SMI_OK;
+}
+
+int smi_beam_step(const smi_beam_state* st, const smi_beam_step_args* a, void* stream) {
+  if (int rc = check_beam_state(st)) return rc;
+  if (!a || !a->logits || !a->pmax || !a->psum || !a->pval || !a->pidx) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  const int64_t rows = (int64_t)st->n * st->beam;
+  if (int rc = check_logits_shape(a->ldl, rows, a->vocab)) return rc;
+  if (a->k2 != 2 * st->beam) return fail(SMI_ERR_INVALID_ARG, "k2=%d must be 2 * beam=%d", a->k2, st->beam);
+  if (a->pos < 0 || a->pos + 2 > st->stride) return fail(SMI_ERR_INVALID_ARG, "pos=%d needs stride=%d >= pos + 2", a->pos, st->stride);
+  if (!(a->inv_temp > 0.f) || !std::isfinite(a->inv_temp) || !std::isfinite(a->len_penalty))
+    return fail(SMI_ERR_INVALID_ARG, "inv_temp must be positive and finite, len_penalty finite");
+  if (a->eos_idx < 0 || a->eos_idx >= a->vocab) return fail(SMI_ERR_INVALID_ARG, "eos_idx=%d outside the vocabulary", a->eos_idx);
+  if (int rc = check_prompt_table(a->table)) return rc;
+  if (!a->table.tok) {
+    if (a->prompt_len < 1 || a->max_len < 2) return fail(SMI_ERR_INVALID_ARG, "prompt_len=%d max_len=%d", a->prompt_len, a->max_len);
+    if (a->pos + 1 < a->prompt_len && (a->forced_tok < 0 || a->forced_tok >= a->vocab))
+      return fail(SMI_ERR_INVALID_ARG, "forced_tok=%d outside the vocabulary", a->forced_tok);
+    if (a->pos + 1 > a->max_len - 1) return fail(SMI_ERR_INVALID_ARG, "pos=%d is past the forced EOS of max_len=%d", a->pos, a->max_len);
+  }
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  const int cur = a->pos & 1;
+  BeamStepArgs b{};
+  b.tok = st->tok; b.cum = st->cum; b.nactive = st->nactive; b.done = st->done; b.ndone = st->ndone;
+  b.parent = st->parent; b.new_tok = st->new_tok; b.new_cum = st->new_cum;
+  b.hist = st->hist[cur]; b.fin_tok = st->fin_tok; b.fin_len = st->fin_len; b.fin_score = st->fin_score; b.fin_count = st->fin_count;
+  b.margins = st->margins;
+  b.logits = (const float*)a->logits; b.ldl = a->ldl; b.logits_f16_tm = a->logits_f16_tm ? 1 : 0;
+  b.pmax = a->pmax; b.psum = a->psum; b.pval = a->pval; b.pidx = a->pidx;
+  b.n = st->n; b.beam = st->beam; b.k2 = a->k2; b.pos = a->pos; b.prompt_len = a->prompt_len; b.forced_tok = a->forced_tok;
+  b.max_len = a->max_len; b.inv_temp = a->inv_temp; b.len_penalty = a->len_penalty; b.normalize = a->normalize ? 1 : 0;
+  b.eos_idx = a->eos_idx; b.hist_stride = st->stride;
+  if (a->table.tok) b.table = table_dev(a->table);
+  HIP_TRY(launch_beam_step(b, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_beam_reorder(const smi_beam_state* st, int32_t pos, void* stream) {
+  if (int rc = check_beam_state(st)) return rc;
+  if (pos < 0 || pos + 2 > st->stride) return fail(SMI_ERR_INVALID_ARG, "pos=%d needs stride=%d >= pos + 2", pos, st->stride);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  const int cur = pos & 1;
+  HIP_TRY(launch_beam_reorder(st->parent, st->new_tok, st->new_cum, st->anc[cur], st->anc[cur ^ 1], st->hist[cur], st->hist[cur ^ 1],
+                              st->tok, st->cum, st->n * st->beam, st->stride, pos, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int smi_beam_output(const smi_beam_state* st, int32_t out_stride, int32_t* out_tok, int32_t* out_len, float* out_score, void* stream) {
+  if (int rc = check_beam_state(st)) return rc;
+  if (!out_tok || !out_len || !out_score) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (out_stride < 1) return fail(SMI_ERR_INVALID_ARG, "out_stride=%d", out_stride);
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_beam_output(st->fin_tok, st->fin_len, st->fin_score, st->fin_count, st->n, st->beam, st->stride, out_stride, out_tok,
+                             out_len, out_score, st->margins, (hipStream_t)stream));
   return SMI_OK;
 }
 
