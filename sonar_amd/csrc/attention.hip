@@ -7,16 +7,14 @@
 // gfx950 mapping: one workgroup = 128 queries of one (sentence, head); each of
 // the 4 waves owns 32 queries.  Scores are computed TRANSPOSED
 // (S^T = K.Q^T on v_mfma_f32_32x32x16_f16), so a lane holds 16 scores of ONE
-// query: the online softmax is lane-local (+1 cross-half shuffle), and the
-// fp32 scores convert in-register straight into the B operand of
-// O^T = V^T.P^T -- the 16-wide MFMA K-slot order is a free permutation as long
-// as V^T is fetched in the same order, so P never moves between lanes or
-// through LDS.  K is staged row-major with the 16-B XOR swizzle (conflict-free
-// ds_read_b128), V row-major too and read through the LDS transpose read
-// (ds_read_b64_tr_b16, common.hpp lds_tr_read_b64); both arrive by double-buffered global->LDS DMA.  S <= 514 in SONAR, so the
+// query and P never moves between lanes or through LDS: the register -> key
+// map, the lane-local online softmax with its lazy rescale, the V^T transpose
+// reads and the PV step are attn_core.hpp, shared with relpos_attention.hip.
+// K and V arrive by double-buffered global->LDS DMA.  S <= 514 in SONAR, so the
 // kernel is HBM-bound (~64 flop/B); the score matrix never leaves registers.
 #include <cstdlib>
 
+#include "attn_core.hpp"
 #include "common.hpp"
 #include "kernels.hpp"
 
@@ -32,10 +30,7 @@ constexpr int AT_KB = 64;   // keys per K/V tile
 //
 // K and V tiles (64 keys x 128 B) go global -> LDS by DMA into two buffers: tile t+1 is in flight while
 // tile t is consumed, one barrier per tile, no staging registers.  Both are row-major [key][128 B] with
-// 16-B chunk c of key r at slot c ^ swz(r): K swz = (r>>1)&7 (conflict-free ds_read_b128 of the K
-// fragments), V swz = ((r>>1)&1)<<2, read with ds_read_b64_tr_b16 -- a 16-lane group fetches a
-// [4 keys][16 dims] block and every lane receives the 4 keys of its dim, i.e. the V^T fragment without
-// a transposed copy (keys r, r+2 of a group sit in different halves of the 128-B row: all 64 banks).
+// 16-B chunk c of key r at slot c ^ swz(r), the K and V swizzles of attn_core.hpp.
 // NTL: the K / V tiles are loaded non-temporally (launcher: every sentence fits ONE 128-query block, so each qkv line
 // is read by exactly one workgroup, once)
 // CAUSAL (the decoder's teacher-forced scoring, launch_causal_attention): query i sees keys 0..i only.  The key loop of a
@@ -96,27 +91,12 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
       }
     }
   };
-  // V^T fragments: lane p of a 16-lane group feeds row (p>>2) of its [4 keys][16 dims] block and gets
-  // the 4 keys of dim p.  MFMA (db, kb, u), half `part`: keys 32 kb + 16 u + 4 hi + 8 part + (0..3),
-  // dims 32 db + 16 (l31>>4) + (0..15); 32 kb + 16 u + 8 part never changes the swizzle bit, so it is
-  // an immediate offset.  (k slot e of the MFMA <-> key 16u + 4hi + 8(e>>2) + (e&3): the S^T layout.)
-  unsigned vaddr[2];
-  {
-    const int p16 = lane & 15, g16 = (lane >> 4) & 1;
-    const int key = 4 * hi + (p16 >> 2);
-#pragma unroll
-    for (int db = 0; db < 2; ++db) {
-      const int chunk = db * 4 + g16 * 2 + ((p16 & 3) >> 1);
-      vaddr[db] = (unsigned)(size_t)(lds + TILE + key * 128 + ((chunk ^ (((key >> 1) & 1) << 2)) << 4) + (p16 & 1) * 8);
-    }
-  }
+  unsigned vaddr[2];  // V^T fragments of buffer 0, block 0
+  attn_vt_addr(vaddr, lds + TILE, lane, 4 * hi);
 
   float m = -1e30f, lsum = 0.f;  // m: running reference of the SCALED scores (log2 domain)
   f32x16 o[2];
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o[db][r] = 0.f;
+  attn_zero(o);
 
   stage(0, 0);
   for (int kv0 = 0, t = 0; kv0 < kend; kv0 += AT_KB, ++t) {
@@ -130,93 +110,24 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
     // 3 workgroups per CU; the kernel is a short latency chain per workgroup, so resident workgroups are what pays).
 #pragma unroll
     for (int kb = 0; kb < 2; ++kb) {
-      // ---- S^T = K . Q^T, 32 keys ----
-      f32x16 sc;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sc[r] = 0.f;
-      const int krow = kb * 32 + l31;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        const half8 kf = *(const half8*)(Ks + krow * 128 + (((ks * 2 + hi) ^ ((krow >> 1) & 7)) << 4));
-        sc = __builtin_amdgcn_mfma_f32_32x32x16_f16(kf, qf[ks], sc, 0, 0, 0);
-      }
-      // ---- online softmax (per query = per lane, halves joined by one shuffle) ----
-      if (kv0 + AT_KB > len) {  // only the last tile of a sentence has keys to mask
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-          if (kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi >= len) sc[r] = -INFINITY;
-      }
+      f32x16 sc = attn_k_scores(Ks, kb * 32 + l31, hi, qf);  // S^T = K . Q^T, 32 keys
+      // ---- online softmax (per query = per lane), then O^T += V^T . P^T: attn_core.hpp ----
+      if (kv0 + AT_KB > len) sc = attn_mask_tail(sc, kv0 + kb * 32, 4 * hi, len);  // only a sentence's last tile has keys to mask
       if constexpr (CAUSAL) {
         if (kv0 + AT_KB > q0) {  // the tile reaches past the block's first query: keys after the lane's query are out
 #pragma unroll
           for (int r = 0; r < 16; ++r)
-            if (kv0 + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi > qi) sc[r] = -INFINITY;
+            if (kv0 + kb * 32 + attn_key(r) + 4 * hi > qi) sc[r] = -INFINITY;
         }
       }
-      float mx = sc[0];
-#pragma unroll
-      for (int r = 1; r < 16; ++r) mx = fmaxf(mx, sc[r]);
-      {  // the other half of the keys sits 32 lanes away: v_permlane32_swap (VALU) instead of __shfl_xor (an LDS round trip in
-         // the middle of the softmax chain, once per key block)
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(mx), __float_as_uint(mx), false, false);
-        mx = fmaxf(__uint_as_float(sw[0]), __uint_as_float(sw[1])) * sl2e;  // sl2e > 0: the scaled maximum
-      }
-      // Lazy rescale: the reference m only moves when some query's block maximum exceeds it by more than
-      // 2^8; until then p = exp2(x - m) <= 256 (fine in fp32 and for the fp16 P operand) and the 32
-      // output accumulators are left alone.
-      if (__any(mx > m + 8.0f)) {
-        const float m_new = fmaxf(m, mx);
-        const float alpha = __builtin_amdgcn_exp2f(m - m_new);
-        m = m_new;
-        lsum *= alpha;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[db][r] *= alpha;
-      }
-      float psum = 0.f;
-      half8 pf[2];
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float p = __builtin_amdgcn_exp2f(__builtin_fmaf(sc[r], sl2e, -m));
-        psum += p;
-        pf[r >> 3][r & 7] = (f16)p;
-      }
-      lsum += psum;
-
-      // ---- O^T += V^T . P^T ----
-      half4 va[2][2][2];  // [db][u][part]
-#pragma unroll
-      for (int db = 0; db < 2; ++db) {
-        const unsigned a = vaddr[db] + (t & 1) * 2 * TILE + kb * 4096;
-        va[db][0][0] = lds_tr_read_b64<0>(a);
-        va[db][0][1] = lds_tr_read_b64<1024>(a);
-        va[db][1][0] = lds_tr_read_b64<2048>(a);
-        va[db][1][1] = lds_tr_read_b64<3072>(a);
-      }
-      // the wait carries the results as operands: the MFMAs below depend on IT, not just on the reads
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(va[0][0][0]), "+v"(va[0][0][1]), "+v"(va[0][1][0]), "+v"(va[0][1][1]),
-                     "+v"(va[1][0][0]), "+v"(va[1][0][1]), "+v"(va[1][1][0]), "+v"(va[1][1][1])
-                   :
-                   : "memory");
-#pragma unroll
-      for (int db = 0; db < 2; ++db)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          half8 vf;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            vf[e] = va[db][u][0][e];
-            vf[e + 4] = va[db][u][1][e];
-          }
-          o[db] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vf, pf[u], o[db], 0, 0, 0);
-        }
+      attn_lazy_rescale(attn_block_max(sc, sl2e), m, lsum, o);
+      const AttnP p = attn_exp_p(sc, sl2e, m);
+      lsum += p.sum;
+      attn_pv(o, p.pf, vaddr, (t & 1) * 2 * TILE + kb * 4096);
     }
   }
 
-  const float ltot = lsum + __shfl_xor(lsum, 32, 64);
-  const float inv = 1.0f / ltot;
+  const float inv = attn_finish(lsum);
   if constexpr (TM) {
     // Tile-major context: a lane holds 8-B pieces of ONE row, so a direct store scatters 16-B pieces over 16 lines per
     // instruction.  The wave parks its 32 rows x 128 B in LDS (the K / V buffers, free after the barrier) and writes
@@ -244,16 +155,7 @@ __global__ __launch_bounds__(256, 4) void attention_kernel(const f16* __restrict
       if (qr < len) store_nt((f32x4*)(ctx + tm_offset(start + qr, h * 64 + hb * 32 + c4 * 8, d)), v);
     }
   } else if (qi < len) {
-    f16* op = ctx + (size_t)(start + qi) * d + h * 64;
-#pragma unroll
-    for (int db = 0; db < 2; ++db)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        half4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = (f16)(o[db][q * 4 + e] * inv);
-        *(half4*)(op + db * 32 + 8 * q + 4 * hi) = v;
-      }
+    attn_store_row(o, inv, ctx, start + qi, h * 64, d, hi, 0);
   }
 }
 

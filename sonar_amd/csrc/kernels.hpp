@@ -324,7 +324,7 @@ hipError_t launch_head_featurize(int form, const void* src, const void* mt, cons
 hipError_t launch_head_output(const f16* h, int ldh, const float* w, const float* b, int rows, int K, int out_dim,
                               int act, float* out, hipStream_t stream);
 
-// ---- speech path (speech.hip) ----
+// ---- speech path (speech.hip, relpos_attention.hip) ----
 hipError_t launch_fbank(const float* wave, int64_t nsamples, float scale, int standardize, const float* window,
                         const float* mel_w, const int* mel_range, float* out, hipStream_t stream);
 hipError_t launch_stack_ln(const float* fb, int n, int t, int nb, const int32_t* cu, int max_len, const float* w,

@@ -116,6 +116,16 @@ def test_swapped_scalar_and_integer_operands_are_commuted(tmp_path):
         assert rc == 1 and "DIFF k_a" in out
 
 
+def test_swapped_packed_multiply_sources_are_commuted_only_with_their_op_sel_hi_bits(tmp_path):
+    line = "\tv_pk_mul_f32 v[30:31], v[32:33], v[30:31] op_sel_hi:[0,1]\n"
+    both = "\tv_pk_mul_f32 v[30:31], v[30:31], v[32:33] op_sel_hi:[1,0]\n"     # sources and bits swapped together: the same product
+    srcs = "\tv_pk_mul_f32 v[30:31], v[30:31], v[32:33] op_sel_hi:[0,1]\n"     # only the sources: another high half
+    rc, out = run(tmp_path, unit([kernel("k_a", BODY_A + line, 0)], "0"), unit([kernel("k_a", BODY_A + both, 0)], "0"))
+    assert rc == 0 and "COMMUTED k_a" in out
+    rc, out = run(tmp_path, unit([kernel("k_a", BODY_A + line, 0)], "0"), unit([kernel("k_a", BODY_A + srcs, 0)], "0"))
+    assert rc == 1 and "DIFF k_a" in out
+
+
 # a K-loop-like body: address arithmetic between memory operations, counted waits, MFMAs
 BODY_C = ("\ts_lshl_b32 s4, s2, 8\n\tv_lshlrev_b32_e32 v9, 4, v0\n\tglobal_load_dwordx4 v[2:5], v1, s[0:1]\n"
           "\tds_read_b128 v[10:13], v9\n\ts_waitcnt vmcnt(0) lgkmcnt(0)\n\tv_mfma_f32_16x16x32_f16 a[0:3], v[2:5], v[10:13], a[0:3]\n"

@@ -8,8 +8,9 @@ Compares function bodies (from the `name:` label line, with or without its `; @n
 and .amdhsa_kernel descriptors; the per-file __hip_cuid_<hash> symbol is masked, local labels are renumbered per
 function and the padding in front of a label line's comment is ignored.  OLD=NEW pairs a kernel of the base with its new mangled name (a template parameter that went).
 Every kernel of the base is IDENTICAL, COMMUTED (equal once the two source operands of every v_add/mul/max/min_f32_e32,
-s_add_i32/u32, s_mul_i32, s_and/or/xor_b32, s_min/max_i32/u32 and v_add_u32_e32 line are sorted -- IEEE add, mul, max and
-min and the integer operations commute exactly, SCC and carry included; nothing else is normalised), RESCHEDULED, DIFF or
+s_add_i32/u32, s_mul_i32, s_and/or/xor_b32, s_min/max_i32/u32 and v_add_u32_e32 line are sorted, and those of a v_pk_mul_f32
+whose only modifier is op_sel_hi:[x,y] together with the two bits -- IEEE add, mul, max and min and the integer operations
+commute exactly, SCC and carry included; nothing else is normalised), RESCHEDULED, DIFF or
 REMOVED; kernels only in the tree are ADDED.  Under a DIFF line: whether the ordered sequence (next sentence) is the base's all the
 same, every descriptor resource that differs as `field base -> tree`, and the count of changed lines (the larger side of a
 line diff, descriptor included) -- what a refactor that renumbers registers is judged by.  RESCHEDULED: the sequence of v_mfma*, ds_*, global_* / buffer_*, s_waitcnt*,
@@ -26,6 +27,8 @@ import sys
 
 COMMUTATIVE = re.compile(r"^(\s*(?:v_(?:add|mul|max|min)_f32_e32|s_add_[iu]32|s_mul_i32|s_(?:and|or|xor)_b32|s_(?:min|max)_[iu]32|v_add_u32_e32)"
                          r" [^,]+), ([^,;]+), ([^,;]+?)(\s*(?:;.*)?)$", re.M)
+# v_pk_mul_f32 d, a, b op_sel_hi:[x,y] (no other modifier): the two sources swapped TOGETHER with their op_sel_hi bits
+PK_MUL = re.compile(r"^(\s*v_pk_mul_f32 [^,]+), ([^,;]+), ([^,; ]+) op_sel_hi:\[([01]),([01])\](\s*(?:;.*)?)$", re.M)
 ORDERED = re.compile(r"^\s*(v_mfma\w*|ds_\w+|global_\w+|buffer_\w+|s_barrier|s_setprio|s_waitcnt\w*[^;\n]*)", re.M)  # s_waitcnt: the whole operand text
 RESOURCES = re.compile(r"^\s*\.amdhsa_(?:next_free_vgpr|next_free_sgpr|accum_offset|private_segment_fixed_size|group_segment_fixed_size) .*$", re.M)
 
@@ -57,6 +60,7 @@ def norm(s):  # local labels are numbered per file: renumber per function (comme
 
 
 def commute(s):
+    s = PK_MUL.sub(lambda m: "%s, %s, %s op_sel_hi:[%s,%s]%s" % (m.group(1), *sum(zip(*sorted(zip(m.group(2, 3), m.group(4, 5)))), ()), m.group(6)), s)
     return COMMUTATIVE.sub(lambda m: "%s, %s, %s%s" % (m.group(1), *sorted(m.group(2, 3)), m.group(4)), s)
 
 
