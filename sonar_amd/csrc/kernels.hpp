@@ -159,13 +159,18 @@ hipError_t launch_fold_residual(void* x, int x_f16, const void* parts, int npart
 // dst_f32[i] = float(src_f16[i])
 hipError_t launch_f16_to_f32(const f16* src, float* dst, size_t n, hipStream_t stream);
 
-// xsim: row-normalise then mine top-k cosine neighbours of each X row among Y rows.
+// xsim: row-normalise then mine top-k cosine neighbours of each X row among Y rows.  The tile walk, its workspace layout and
+// the host side of a pass are xsim_walk.hpp's, shared with the int8 pass (xsim_i8.hip).
 hipError_t launch_l2_normalize(const void* src, int src_is_f32, f16* dst, int64_t rows, int d,
                                hipStream_t stream);
 size_t xsim_workspace_bytes(int64_t nx_pad, int64_t ny_pad, int k, int d);
 hipError_t launch_xsim_topk(const f16* Xn, int64_t nx, int64_t nx_pad, const f16* Yn, int64_t ny,
                             int64_t ny_pad, int d, int k, int64_t y_index_offset, int32_t* idx,
                             float* score, void* workspace, hipStream_t stream);
+// final merge over the chunk-partial lists ps / pi [nchunks][nx_pad][K] of a walk, K = k rounded up to 1, 2, 4 or 8: the k
+// best of every row in `better`'s order on the fp32 scores, index + y_index_offset, -1 where a list ran short
+hipError_t launch_xsim_merge(const float* ps, const int* pi, int nchunks, int64_t nx, int nx_pad, int k,
+                             int64_t y_index_offset, int32_t* idx, float* score, hipStream_t stream);
 hipError_t launch_topk_merge(const float* part_scores, const int32_t* part_idx, int parts, int64_t n, int k,
                              float* out_scores, int32_t* out_idx, hipStream_t stream);
 hipError_t launch_margin_select(const float* fwd_scores, const int32_t* fwd_idx, int64_t nx, int k,

@@ -1,6 +1,7 @@
-// The total order "value descending, index ascending" and its packed form, stated once.  Users: xsim.hip (brute-force top-k
-// lists), ivf.hip / ivf_scan.hpp (the IVF scans and the self-join), mining.hip (the max-strategy walk), decoder.hip (tile and
-// token selection, the beam step) and sampling.hip (the radix descent and the most-probable-token draw).
+// The total order "value descending, index ascending" and its packed form, stated once.  Users: xsim_walk.hpp (the brute-force
+// top-k lists of xsim.hip and xsim_i8.hip, and TopK, the sorted register list over `better`), ivf.hip / ivf_scan.hpp (the IVF
+// scans and the self-join), mining.hip (the max-strategy walk), decoder.hip (tile and token selection, the beam step) and
+// sampling.hip (the radix descent and the most-probable-token draw).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -13,7 +14,7 @@ __device__ __forceinline__ bool better(float s, int i, float s2, int i2) {
   return s > s2 || (s == s2 && i < i2);
 }
 
-// The same order as ONE unsigned compare (the running top-k lists in LDS, xsim.hip): key = order-preserving(score) << 32 |
+// The same order as ONE unsigned compare (the running top-k lists in LDS, xsim_walk.hpp): key = order-preserving(score) << 32 |
 // (0xffffffff - index); a larger key is a better candidate.  A key built from a value other than NaN is never 0.
 constexpr unsigned long long XS_EMPTY = (0x007fffffull << 32) | 0x80000000ull;  // (-inf, index 0x7fffffff)
 __device__ __forceinline__ uint32_t xs_ord(float v) {

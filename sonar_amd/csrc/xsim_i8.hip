@@ -4,12 +4,9 @@
 // codes and scales from smi_ivf_i8_encode over the padded output of smi_xsim_normalize.  The bits of a score depend on the two
 // fp16 rows alone, so they are the bits IVFInt8Index.search returns for the same pair.
 //
-// Why the tile engine of xsim.hip holds byte for byte: a K slice of the 256x256 engine is 64 B of a row (gemm_tile256.hpp), 32
-// fp16 or 64 int8, and a lane of v_mfma_i32_16x16x64_i8 feeds the 16 consecutive bytes at 16 * kg of its row, of BOTH operands --
-// exactly the chunk v_mfma_f32_16x16x32_f16 reads.  The tile-major layout, the tm_swz swizzle, the 4-slot ring, the glds16 stream
-// and every ds_read_b128 offset of xsim_tile256_kernel are therefore unchanged, and launch_pack_tile_major packs an int8
-// [rows, d] matrix when it is told fp16 [rows, d / 2].  The C/D layout is the 16x16 fp16 one.  What differs: the MFMA, nt = d / 64
-// slices per tile instead of d / 32, and the fold, which turns the int32 sums into scores.
+// The tile kernel is the walk of xsim_walk.hpp (why one byte geometry serves fp16 and int8 is said there) over the policy XsI8
+// below.  What differs from the fp16 pass: the MFMA, nt = d / 64 slices per tile instead of d / 32, and the fold, which turns
+// the int32 sums into scores.
 //
 // The fold.  A lane holds 8 x rows (wr * 128 + mi * 16 + l15; their scales sx[8] are loaded once per workgroup) against 16 y
 // columns (wc * 64 + ni * 16 + 4 kg + r; the 256 scales of a y tile travel in the DMA stream with the tile's first slice into a
@@ -26,12 +23,9 @@
 // smallest scale of an fp16 row is 2^-24 / 127, so no row smi_ivf_i8_encode writes produces one (tests/ivf_i8_ref.edge_rows:
 // zero rows score +0 against everything).  Columns n >= ny never enter a list: a pad row (codes 0, scale 0) scores +0 and would
 // beat every negative score.
-#include <algorithm>
-
 #include "api_common.hpp"
-#include "gemm_tile256.hpp"
 #include "kernels.hpp"
-#include "topk_order.hpp"
+#include "xsim_walk.hpp"
 
 using namespace smi;
 using namespace smi_host;
@@ -39,33 +33,11 @@ using namespace smi_host;
 namespace smi {
 namespace {
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-constexpr int XI8_BK = 64;                 // elements = bytes of a row in a K slice
-constexpr int XI8_BLOCK = G2_BM * XI8_BK;  // bytes of one operand's K slice: a tile-major block
-static_assert(XI8_BK == G2_BK * (int)sizeof(f16) && XI8_BLOCK == TM_BLOCK * (int)sizeof(f16), "the byte geometry of the fp16 engine");
 constexpr int XI8_MAX_DIM = SMI_IVF_I8_MAX_DIM;
 static_assert((int64_t)127 * 127 * XI8_MAX_DIM < (1LL << 31), "the int32 sum of a row pair cannot overflow");
 
-// (xsim.hip's xs_thresholds and TopK, in copies: sharing them would move text of xsim.hip into a header)
-// the 8 row thresholds of a lane: score word of the last key of each list.  Issue and wait in ONE asm statement, or every load
-// would get `s_waitcnt vmcnt(0)` from hipcc's LDS-DMA alias tracking.  A stale value is a valid lower bound.
-template <int K>
-__device__ __forceinline__ void xi8_thresholds(unsigned lds_addr, float (&t)[8]) {
-  uint32_t o[8];
-  asm volatile(
-      "ds_read_b32 %0, %8 offset:%9\n\tds_read_b32 %1, %8 offset:%10\n\tds_read_b32 %2, %8 offset:%11\n\t"
-      "ds_read_b32 %3, %8 offset:%12\n\tds_read_b32 %4, %8 offset:%13\n\tds_read_b32 %5, %8 offset:%14\n\t"
-      "ds_read_b32 %6, %8 offset:%15\n\tds_read_b32 %7, %8 offset:%16\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(o[0]), "=&v"(o[1]), "=&v"(o[2]), "=&v"(o[3]), "=&v"(o[4]), "=&v"(o[5]), "=&v"(o[6]), "=&v"(o[7])
-      : "v"(lds_addr), "n"(0 * 128 * K), "n"(1 * 128 * K), "n"(2 * 128 * K), "n"(3 * 128 * K), "n"(4 * 128 * K),
-        "n"(5 * 128 * K), "n"(6 * 128 * K), "n"(7 * 128 * K)
-      : "memory");
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi) t[mi] = xs_unord(o[mi]);
-}
-
 // the 16 y-column scales of a lane (columns wc * 64 + ni * 16 + 4 kg + r of the tile) from the tile's scale slot in LDS, in
-// one asm statement for the same reason
+// one asm statement for the reason given at xs_thresholds
 __device__ __forceinline__ void xi8_read_scales(unsigned lds_addr, f32x4 (&sy)[4]) {
   asm volatile(
       "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\t"
@@ -75,310 +47,101 @@ __device__ __forceinline__ void xi8_read_scales(unsigned lds_addr, f32x4 (&sy)[4
       : "memory");
 }
 
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+
+// The int8 operand policy of the walk (xsim_walk.hpp).  xs / ys: the scales of the x and y rows, row order.
+// The y scales of a tile ride the DMA stream (issue_tile, first in the group of the tile's first slice: the walk's counted
+// waits hold as they are): waves 0 .. 3 copy its 256 scales (4 B per lane) into scale slot (tile & 7) above the lists.  A
+// group of waves 0 .. 3 so holds 5 operations at every tile start (every group at nt = 1, every second one at nt = 2); what
+// the earlier retirement costs at d <= 128 is unmeasured.  8 slots: the deferred fold of tile T reads its slot while, at one
+// slice per tile, the scales of T + 4 are already on their way; T + 8's are issued after T + 4's first slice was read.
 template <int K>
-struct Xi8TopK {
-  float s[K];
-  int i[K];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      s[j] = -INFINITY;
-      i[j] = 0x7fffffff;
-    }
+struct XsI8 {
+  typedef int8_t elem_t;
+  typedef i32x4 frag_t;  // 16 codes
+  typedef i32x4 acc_t;
+  static constexpr int BK = 64;
+  static constexpr bool LISTS = true;          // K = 1 too: one path
+  static constexpr int SCALES = 256 * K * 8;   // above the ring, behind the lists: [8 slots][256] fp32
+  static constexpr int LDS_ABOVE = SCALES + 8 * 1024;
+  static constexpr bool TRACED = false;
+  static __device__ __forceinline__ acc_t mfma(frag_t w, frag_t x, acc_t c) {
+    return __builtin_amdgcn_mfma_i32_16x16x64_i8(w, x, c, 0, 0, 0);
   }
-  __device__ __forceinline__ void push(float v, int idx) {
-    if (better(v, idx, s[K - 1], i[K - 1])) {
-      s[K - 1] = v;
-      i[K - 1] = idx;
+
+  struct tile_t {
+    f32x4 sy[4];  // sy[ni][r]: the scales of the lane's y columns in the tile being folded
+  };
+  const float *xs, *ys;
+  float sx[8];      // the scales of this lane's x rows
+  const float* ysg;
+  unsigned sc_addr;
+  int it, t_begin;
+  __device__ __forceinline__ XsI8(const float* xs_, const float* ys_) : xs(xs_), ys(ys_) {}
+
+  __device__ __forceinline__ void init(const XsLane& L, char* above, int m0, int t_begin_) {
 #pragma unroll
-      for (int j = K - 1; j > 0; --j) {
-        if (better(s[j], i[j], s[j - 1], i[j - 1])) {
-          const float ts = s[j];
-          s[j] = s[j - 1];
-          s[j - 1] = ts;
-          const int ti = i[j];
-          i[j] = i[j - 1];
-          i[j - 1] = ti;
-        }
-      }
-    }
+    for (int mi = 0; mi < 8; ++mi) sx[mi] = xs[L.row(mi, m0)];
+    sc_addr = (unsigned)(size_t)(above + SCALES) + L.col(0, 0) * 4;
+    ysg = ys + (size_t)t_begin_ * G2_BN + (L.wave & 3) * 64 + L.lane;
+    it = 0;
+    t_begin = t_begin_;
+  }
+  __device__ __forceinline__ void issue_tile(char* above, int wave) {
+    if (wave < 4)
+      __builtin_amdgcn_global_load_lds(SMI_GLOBAL_PTR(ysg), SMI_LDS_PTR(above + SCALES + (it & 7) * 1024 + wave * 256), 4, 0, 0);
+    ysg += G2_BN;
+    ++it;
+  }
+  __device__ __forceinline__ void fold_begin(int n0f, tile_t& ts) { xi8_read_scales(sc_addr + ((n0f / G2_BN - t_begin) & 7) * 1024, ts.sy); }
+  // the largest score of the row's 16: s_x >= 0 and a rounded product is monotone in t = fl32(sum * s_y)
+  __device__ __forceinline__ float row_max(const acc_t (&acc)[4][8], int mi, const tile_t& ts) const {
+    float tmax = -INFINITY;
+#pragma unroll
+    for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, __fmul_rn((float)acc[ni][mi][r], ts.sy[ni][r]));
+    return __fmul_rn(tmax, sx[mi]);
+  }
+  __device__ __forceinline__ float score(const acc_t (&acc)[4][8], int ni, int mi, int r, const tile_t& ts) const {
+    // (an opaque copy of the sum: or hipcc keeps the 128 products of row_max alive for the insertion path and spills)
+    int a = acc[ni][mi][r];
+    asm volatile("" : "+v"(a));
+    return __fmul_rn(__fmul_rn((float)a, ts.sy[ni][r]), sx[mi]);
   }
 };
 
-// Xc / Yc: tile-major copies of the codes (block (tile, slice) = XI8_BLOCK bytes, the LDS image); xs / ys: the scales, row order.
-// Partial results ps / pi [nchunks][nx_pad][K], a chunk without tiles leaves (-inf, 0x7fffffff).
+// Xc / Yc: tile-major copies of the codes
 template <int K>
 __global__ __launch_bounds__(G2_THREADS) void xsim_i8_tile256_kernel(const int8_t* __restrict__ Xc, const float* __restrict__ xs,
                                                                      const int8_t* __restrict__ Yc, const float* __restrict__ ys,
                                                                      int d, int ntx, int nty, int nchunks, int tiles_per_chunk,
                                                                      int ny, int nx_pad, float* __restrict__ ps,
                                                                      int* __restrict__ pi) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  int tile_m, chunk;
-  g2_tile_coords(ntx, nchunks, tile_m, chunk);
-  const int m0 = tile_m * G2_BM;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // lane -> x row l15 of a 16-row block, 4 consecutive y columns at 4 * kg of a 16-column block
-  const int l15 = lane & 15, kg = lane >> 4, wr = wave >> 2, wc = wave & 3;
-
-  const int t_begin = chunk * tiles_per_chunk;
-  const int ntiles = min(nty, t_begin + tiles_per_chunk) - t_begin;
-  const int nt = d / XI8_BK;
-  const int S = max(ntiles, 0) * nt;
-
-  unsigned long long* lists = (unsigned long long*)(smem + G2_LDS_BYTES);  // [256 rows][K] keys
-  const unsigned thr_addr = (unsigned)(size_t)(smem + G2_LDS_BYTES) + ((wr * 128 + l15) * K + (K - 1)) * 8 + 4;
-  char* scales = smem + G2_LDS_BYTES + 256 * K * 8;  // [8 slots][256] fp32: the y scales of the tiles in flight
-  const unsigned sc_addr = (unsigned)(size_t)scales + (wc * 64 + 4 * kg) * 4;
-  if (tid < 256) {
-#pragma unroll
-    for (int j = 0; j < K; ++j) lists[tid * K + j] = XS_EMPTY;
-  }
-  float sx[8];  // the scales of this lane's x rows
-#pragma unroll
-  for (int mi = 0; mi < 8; ++mi) sx[mi] = xs[m0 + wr * 128 + mi * 16 + l15];
-  __syncthreads();  // (before any LDS-DMA is in flight)
-
-  if (S > 0) {
-    // DMA stream state: slice s = (tile s / nt, k = s % nt)
-    const int8_t* xg[2];
-    const int8_t* yg[2];
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      // piece (wave * 2 + q) of a 16 KiB block: 16 rows x 64 B = 1 KiB, linear
-      xg[q] = Xc + (size_t)tile_m * nt * XI8_BLOCK + (wave * 2 + q) * 1024 + lane * 16;
-      yg[q] = Yc + (size_t)t_begin * nt * XI8_BLOCK + (wave * 2 + q) * 1024 + lane * 16;
-    }
-    // The y scales of a tile ride the stream: with the tile's first slice, waves 0 .. 3 copy its 256 scales (4 B per lane)
-    // into scale slot (tile & 7) above the lists, FIRST in the group, so the counted waits hold as they are -- a wait leaves the
-    // newest 8 (4, 0) operations in flight, the groups of the slices behind the awaited one hold at least 4 each, and what is
-    // older than them has landed, the awaited slice's scales included.  Where a group of waves 0 .. 3 holds 5 operations (every
-    // group at nt = 1, every second one at nt = 2, one in nt otherwise) the same wait retires up to two operations of the next
-    // slice as well: correct, a little earlier than needed; what that costs at d <= 128 is unmeasured.  8 slots: the deferred fold of tile T reads its slot
-    // while, at one slice per tile, the scales of T + 4 are already on their way; T + 8's are issued after T + 4's first slice
-    // was read.
-    const float* ysg = ys + (size_t)t_begin * G2_BN + (wave & 3) * 64 + lane;
-    int ik = 0, is = 0, it = 0;
-    auto issue = [&]() {
-      char* slot = smem + (is & 3) * G2_SLOT_BYTES + wave * 2048;
-      const size_t koff = (size_t)ik * XI8_BLOCK;
-      if (ik == 0) {
-        if (wave < 4) __builtin_amdgcn_global_load_lds(SMI_GLOBAL_PTR(ysg), SMI_LDS_PTR(scales + (it & 7) * 1024 + wave * 256), 4, 0, 0);
-        ysg += G2_BN;
-        ++it;
-      }
-      glds16(xg[0] + koff, slot);
-      glds16(xg[1] + koff, slot + 1024);
-      // block (tile, k) of Y sits at (tile * nt + k) * XI8_BLOCK: the chunk's slices are consecutive
-      glds16(yg[0], slot + XI8_BLOCK);
-      glds16(yg[1], slot + XI8_BLOCK + 1024);
-      yg[0] += XI8_BLOCK;
-      yg[1] += XI8_BLOCK;
-      ++is;
-      if (++ik == nt) ik = 0;
-    };
-    const int t_sw = (kg ^ tm_swz(l15)) << 4;
-    const int xoff = (wr * 128 + l15) * 64 + t_sw;
-    const int woff = XI8_BLOCK + (wc * 64 + l15) * 64 + t_sw;
-
-    i32x4 acc[4][8];  // [ni][mi]: 16x16 blocks of the wave's 64(n) x 128(m) tile
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[i][j] = i32x4{0, 0, 0, 0};
-
-    issue();
-    if (S > 1) issue();
-    if (S > 2) issue();
-    if (S > 2) SMI_WAIT_VMCNT(8);
-    else if (S > 1) SMI_WAIT_VMCNT(4);
-    else SMI_WAIT_VMCNT(0);
-    SMI_BARRIER();
-    if (wr == 1) SMI_BARRIER();
-
-    int k = 0, n0 = t_begin * G2_BN;
-    // y tile finished: fold the 128x64 sums of this wave into the row lists (n0f = first y row of that tile)
-    auto fold = [&](int n0f) {
-      float rowthr[8], vmx[8];
-      f32x4 sy[4];  // sy[ni][r]
-      xi8_thresholds<K>(thr_addr, rowthr);
-      xi8_read_scales(sc_addr + ((n0f / G2_BN - t_begin) & 7) * 1024, sy);
-      bool hit = false;
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi) {
-        float tmax = -INFINITY;
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) tmax = fmaxf(tmax, __fmul_rn((float)acc[ni][mi][r], sy[ni][r]));
-        vmx[mi] = __fmul_rn(tmax, sx[mi]);  // the largest score of the row's 16: the product is monotone in t
-        hit |= vmx[mi] >= rowthr[mi];
-      }
-      if (__any(hit)) {
-#pragma unroll
-        for (int mi = 0; mi < 8; ++mi) {
-          if (vmx[mi] >= rowthr[mi]) {
-            unsigned long long* lst = lists + (wr * 128 + mi * 16 + l15) * K;
-#pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-              for (int r = 0; r < 4; ++r) {
-                const int n = n0f + wc * 64 + ni * 16 + 4 * kg + r;
-                // (an opaque copy of the sum: or hipcc keeps the 128 products of the test above alive for this path and spills)
-                int a = acc[ni][mi][r];
-                asm volatile("" : "+v"(a));
-                const float v = __fmul_rn(__fmul_rn((float)a, sy[ni][r]), sx[mi]);
-                if (v >= rowthr[mi] && n < ny) xs_insert<K>(lst, v, n);
-              }
-          }
-        }
-      }
-    };
-    // Group 0 defers its fold by one interval, as in xsim_tile256_kernel: it first reads the next tile's first slice, then
-    // folds in front of that slice's MFMAs (which start from C = 0), so both groups fold in the same interval.
-    bool pending = false;
-    int n0_pending = 0;
-    for (int s = 0; s < S; ++s) {
-      const char* slot = smem + (s & 3) * G2_SLOT_BYTES;
-      i32x4 fx[8], fw[4];
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni) fw[ni] = *(const i32x4*)(slot + woff + ni * 1024);
-#pragma unroll
-      for (int mi = 0; mi < 8; ++mi) fx[mi] = *(const i32x4*)(slot + xoff + mi * 1024);
-      if (s + 3 < S) {
-        issue();
-        SMI_WAIT_VMCNT(8);
-      } else if (s + 2 < S) {
-        SMI_WAIT_VMCNT(4);
-      } else {
-        SMI_WAIT_VMCNT(0);
-      }
-      SMI_LGKM0_BARRIER();
-      if (pending) {  // group 0
-        fold(n0_pending);
-        pending = false;
-      }
-      __builtin_amdgcn_sched_barrier(0);
-      __builtin_amdgcn_s_setprio(1);
-      if (k == 0) {
-        // first slice of a y tile: C = 0 is an operand of the instruction
-        const i32x4 z = {0, 0, 0, 0};
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int mi = 0; mi < 8; ++mi) acc[ni][mi] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fw[ni], fx[mi], z, 0, 0, 0);
-      } else {
-#pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-          for (int mi = 0; mi < 8; ++mi)
-            acc[ni][mi] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fw[ni], fx[mi], acc[ni][mi], 0, 0, 0);
-      }
-      __builtin_amdgcn_s_setprio(0);
-      __builtin_amdgcn_sched_barrier(0);
-      SMI_BARRIER();
-      if (++k == nt) {
-        k = 0;
-        if (wr == 0) {
-          pending = true;
-          n0_pending = n0;
-        } else {
-          fold(n0);
-        }
-        n0 += G2_BN;
-      }
-    }
-    if (pending) fold(n0_pending);
-    if (wr == 0) SMI_BARRIER();
-  }
-
-  // the lists are final: one thread per row writes its chunk-partial list
-  __syncthreads();
-  if (tid < 256) {
-    const size_t o = ((size_t)chunk * nx_pad + m0 + tid) * K;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      const unsigned long long key = lists[tid * K + j];
-      ps[o + j] = xs_key_value(key);
-      pi[o + j] = xs_key_index(key);
-    }
-  }
+  XsI8<K> p(xs, ys);
+  xsim_walk<K>(p, Xc, Yc, d, ntx, nty, nchunks, tiles_per_chunk, ny, nx_pad, ps, pi);
 }
 
-// final merge over chunks, xsim_merge_kernel's: one thread per x row, `better` on the fp32 scores; k_out <= K
-template <int K>
-__global__ __launch_bounds__(256) void xsim_i8_merge_kernel(const float* __restrict__ ps, const int* __restrict__ pi, int nchunks,
-                                                            int64_t nx, int nx_pad, int k_out, int64_t y_off,
-                                                            int32_t* __restrict__ idx, float* __restrict__ score) {
-  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (row >= nx) return;
-  Xi8TopK<K> t;
-  t.init();
-  for (int c = 0; c < nchunks; ++c) {
-    const size_t o = ((size_t)c * nx_pad + row) * K;
-#pragma unroll
-    for (int j = 0; j < K; ++j) t.push(ps[o + j], pi[o + j]);
-  }
-#pragma unroll
-  for (int j = 0; j < K; ++j) {
-    if (j < k_out) {
-      const bool valid = t.i[j] != 0x7fffffff;
-      idx[row * k_out + j] = valid ? (int32_t)(t.i[j] + y_off) : -1;
-      score[row * k_out + j] = t.s[j];
-    }
-  }
-}
-
-int xi8_chunks(int64_t nty) { return (int)(nty < 8 ? nty : 8); }
-int xi8_round_k(int k) { return k <= 1 ? 1 : (k <= 2 ? 2 : (k <= 4 ? 4 : 8)); }
-
-// workspace: partial scores fp32 [chunks][nx_pad][K] | partial indices int32 [chunks][nx_pad][K] | tile-major copy of the x
-//            codes int8 [nx_pad][d] | of the y codes int8 [ny_pad][d];  chunks = min(ny_pad / 256, 8), K = k rounded up to 1, 2,
-//            4 or 8.  Every region is a multiple of 1 KiB: over a 16-byte aligned base each one is 16-byte aligned.
-// The caller sizes it with smi_xsim_workspace_bytes(nx, ny, k, d / 2), the fp16 pass's sizing call at half the dimension (no
-// sizing call of its own): an int8 [rows, d] matrix IS an fp16 [rows, d / 2] matrix to everything but the MFMA, the workspace
-// included.  XsimWs (xsim.hip) at d / 2 holds the same bytes for both copies and lists for min(ny_pad / 128, 8) >=
-// min(ny_pad / 256, 8) chunks of the same nx_pad * K entries: equal to this layout from ny_pad = 2048 on, larger by
+// The workspace is XsimWs (xsim_walk.hpp) over rows of d bytes with one chunk per G2_BN = 256 rows of y: chunks = min(ny_pad /
+// 256, 8).  The caller sizes it with smi_xsim_workspace_bytes(nx, ny, k, d / 2), the fp16 pass's sizing call at half the
+// dimension (no sizing call of its own): an int8 [rows, d] matrix IS an fp16 [rows, d / 2] matrix to everything but the MFMA,
+// the workspace included.  That call holds the same bytes for both copies and lists for min(ny_pad / 128, 8) >= min(ny_pad /
+// 256, 8) chunks of the same nx_pad * K entries: equal to this layout from ny_pad = 2048 on, larger by
 // (min(ny_pad / 128, 8) - ny_pad / 256) * nx_pad * K * 8 bytes below.
-struct XsimI8Ws : WsLayout {
-  float* ps;
-  int* pi;
-  int8_t *xtm, *ytm;
-  XsimI8Ws(void* ws, int64_t nx_pad, int64_t ny_pad, int K, int d) : WsLayout(ws) {
-    const size_t lists = (size_t)xi8_chunks(ny_pad / G2_BN) * nx_pad * K;
-    ps = take<float>(lists);
-    pi = take<int>(lists);
-    xtm = take<int8_t>((size_t)nx_pad * d);
-    ytm = take<int8_t>((size_t)ny_pad * d);
-  }
-};
+constexpr int XI8_CHUNK_ROWS = G2_BN;
 
-template <int K>
 hipError_t xsim_i8_run(const int8_t* xc, const float* xs, int64_t nx, int64_t nx_pad, const int8_t* yc, const float* ys, int64_t ny,
                        int64_t ny_pad, int d, int k, int64_t y_off, int32_t* idx, float* score, void* ws, hipStream_t stream) {
-  constexpr int lds = G2_LDS_BYTES + 256 * K * 8 + 8 * 1024;  // the ring, the row lists and 8 slots of y scales above it
-  const XsimI8Ws w(ws, nx_pad, ny_pad, K, d);
-  const int ntx = (int)(nx_pad / G2_BM), nty = (int)(ny_pad / G2_BN);
-  const int nchunks = xi8_chunks(nty);
-  const int tpc = (nty + nchunks - 1) / nchunks;
-  // an int8 [rows, d] matrix is packed as fp16 [rows, d / 2]: the same bytes
-  const int8_t* src[2] = {xc, yc};
-  int8_t* dst[2] = {w.xtm, w.ytm};
-  const int64_t rows[2] = {nx_pad, ny_pad};
-  for (int o = 0; o < 2; ++o)
-    for (int64_t r0 = 0; r0 < rows[o]; r0 += 65535LL * TM_ROWS) {  // grid.y limit of the pack kernel
-      const int64_t nr = std::min<int64_t>(rows[o] - r0, 65535LL * TM_ROWS);
-      hipError_t e = launch_pack_tile_major((const f16*)(src[o] + r0 * d), (f16*)(dst[o] + r0 * d), (int)nr, d / 2, 0, stream);
-      if (e != hipSuccess) return e;
-    }
-  hipError_t e = launch_with_lds<xsim_i8_tile256_kernel<K>>(dim3(ntx * nchunks), G2_THREADS, lds, stream, (const int8_t*)w.xtm, xs,
-                                                            (const int8_t*)w.ytm, ys, d, ntx, nty, nchunks, tpc, (int)ny,
-                                                            (int)nx_pad, w.ps, w.pi);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(xsim_i8_merge_kernel<K>, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, stream, (const float*)w.ps,
-                     (const int*)w.pi, nchunks, nx, (int)nx_pad, k, y_off, idx, score);
-  return hipGetLastError();
+  return xs_with_k(k, [&](auto K) {
+    return xsim_run(
+        xc, nx, nx_pad, yc, ny, ny_pad, d, XI8_CHUNK_ROWS, k, y_off, idx, score, ws, stream,
+        [&](dim3 grid, const XsimWs& w, int ntx, int nty, int nchunks, int tpc) {
+          constexpr int lds = G2_LDS_BYTES + XsI8<K()>::LDS_ABOVE;  // the ring, the row lists and 8 slots of y scales above it
+          return launch_with_lds<xsim_i8_tile256_kernel<K()>>(grid, G2_THREADS, lds, stream, (const int8_t*)w.xtm, xs,
+                                                              (const int8_t*)w.ytm, ys, d, ntx, nty, nchunks, tpc, (int)ny,
+                                                              (int)nx_pad, w.ps, w.pi);
+        });
+  });
 }
 
 // the refusals a shape alone decides
@@ -407,17 +170,12 @@ int smi_xsim_topk_i8(const void* x_codes, const float* x_scales, int64_t nx, con
   const int64_t nx_pad = smi_xsim_padded_rows(nx), ny_pad = smi_xsim_padded_rows(ny);
   const size_t need = (size_t)smi_xsim_workspace_bytes(nx, ny, k, d / 2);
   if (int rc = check_ws(ws, ws_bytes, need, "smi_xsim_workspace_bytes(nx, ny, k, d / 2)")) return rc;
-  if (XsimI8Ws(nullptr, nx_pad, ny_pad, xi8_round_k(k), d).bytes() > need)  // (cannot happen: see XsimI8Ws)
+  if (XsimWs(nullptr, nx_pad, ny_pad, round_k(k), d, XI8_CHUNK_ROWS).bytes() > need)  // (cannot happen: see XI8_CHUNK_ROWS)
     return fail(SMI_ERR_INVALID_ARG, "the int8 layout exceeds smi_xsim_workspace_bytes(nx, ny, k, d / 2)");
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   const int8_t *xc = (const int8_t*)x_codes, *yc = (const int8_t*)y_codes;
   hipStream_t st = (hipStream_t)stream;
-  switch (xi8_round_k(k)) {
-    case 1: HIP_TRY(xsim_i8_run<1>(xc, x_scales, nx, nx_pad, yc, y_scales, ny, ny_pad, d, k, y_off, idx, score, ws, st)); break;
-    case 2: HIP_TRY(xsim_i8_run<2>(xc, x_scales, nx, nx_pad, yc, y_scales, ny, ny_pad, d, k, y_off, idx, score, ws, st)); break;
-    case 4: HIP_TRY(xsim_i8_run<4>(xc, x_scales, nx, nx_pad, yc, y_scales, ny, ny_pad, d, k, y_off, idx, score, ws, st)); break;
-    default: HIP_TRY(xsim_i8_run<8>(xc, x_scales, nx, nx_pad, yc, y_scales, ny, ny_pad, d, k, y_off, idx, score, ws, st)); break;
-  }
+  HIP_TRY(xsim_i8_run(xc, x_scales, nx, nx_pad, yc, y_scales, ny, ny_pad, d, k, y_off, idx, score, ws, st));
   return SMI_OK;
 }
 

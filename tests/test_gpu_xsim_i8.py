@@ -122,6 +122,38 @@ def test_every_k(ny):
         assert np.isneginf(got_s[:, ny:]).all() and (got_i[:, ny:] == -1).all() and (got_i[:, :ny] >= 0).all()
 
 
+# The fp16 and the int8 kernel are two instantiations of one tile walk (csrc/xsim_walk.hpp).  On operands from {-1, 0, 1} -- fp16
+# rows for one, the same values as int8 codes with every scale exactly 1.0 for the other -- a score is a small integer, exact in
+# fp32 sums and in int32 sums times 1.0 alike, so the two passes must return the same bits, those of the stable-sorted fp64
+# reference.  300 x 513: three chunks of one tile, the last tile one valid row; 257 x 2305: chunks of two tiles, three empty.
+_WALK_PAIR = [(300, 513, 128, k, True) for k in range(1, 9)] + [(257, 2305, 64, k, False) for k in (1, 4)]
+
+
+@pytest.mark.parametrize("nx,ny,d,k,plant", _WALK_PAIR)
+def test_the_fp16_and_the_int8_walk_agree_bit_for_bit(nx, ny, d, k, plant):
+    from sonar_amd import xsim
+    from tests.test_gpu_xsim_kernels import _assert_same, _exact_case, _first_k, _mine, _pad256
+
+    x, y, vals, idx = _exact_case(nx, ny, d, plant)
+    # a condition on the INPUTS (reference alone): the k-th and (k+1)-th scores tie often enough that the tie-break matters
+    share = (vals[:, k - 1] == vals[:, k]).double().mean().item()
+    print(f"{nx} x {ny} x {d}, k = {k}: k-th / (k+1)-th tie in {share:.1%} of the rows")
+    assert share >= 0.1, share
+    want_s, want_i = _first_k(vals, idx, k)
+    f_s, f_i = _mine(x, y, k)
+    enc = [(_pad256(t).to(torch.int8).cuda(), torch.ones((t.shape[0] + 255) // 256 * 256, dtype=torch.float32, device="cuda"))
+           for t in (x, y)]
+    assert all(torch.equal(c.cpu().half()[: t.shape[0]], t) for (c, _), t in zip(enc, (x, y)))  # the codes ARE the fp16 values
+    q_s, q_i = xsim.topk_int8_normalized(None, nx, None, ny, k, refine=False, x_enc=enc[0], y_enc=enc[1])
+    torch.cuda.synchronize()
+    q_s, q_i = q_s.cpu(), q_i.cpu().long()
+    for what, s, i in (("fp16", f_s, f_i), ("int8", q_s, q_i)):
+        _assert_same(i, want_i, f"{what} indices")
+        _assert_same(s.view(torch.int32), want_s.view(torch.int32), f"{what} score bits")
+    _assert_same(q_i, f_i, "int8 against fp16 indices")
+    _assert_same(q_s.view(torch.int32), f_s.view(torch.int32), "int8 against fp16 score bits")
+
+
 def test_ties_go_by_index_within_a_tile_across_tiles_and_across_chunks():
     rng = np.random.default_rng(5)
     x, y = _unit_rows(rng, 20, 64), _unit_rows(rng, 2307, 64)
