@@ -593,6 +593,25 @@ int smi_xsim_topk_i8(const void* x_codes, const float* x_scales, int64_t nx, con
                      int64_t ny, int32_t d, int32_t k, int64_t y_index_offset, int32_t* idx, float* score, void* workspace,
                      int64_t workspace_bytes, void* stream);
 
+/* Paged top-k (restated in tests/topk_wide_ref.py): k above the list length of one pass, 16 results at a time.
+ * THE CONTRACT OF A PAGE, for this entry and smi_ivf_search_page: for every row, the k <= 16 best candidates (s, i) in the total
+ * order (score descending, ties to the lower id) that come strictly AFTER the row's exclusive ceiling (cs, ci) = (ceil_score[r],
+ * ceil_idx[r]): s < cs, or s == cs and i > ci, i being the id as returned (the y row number plus y_index_offset here, the
+ * effective id of an index).  ceil_score / ceil_idx null (both or neither): no ceiling, the first page.  A row whose ceiling
+ * id is negative is exhausted and returns only fill; fill is (-1, -inf) as everywhere.  A ceiling need not be a candidate.  A
+ * NaN ceiling score is not in the order: unspecified.  The last entry of page p is the ceiling of page p + 1 (a fill entry
+ * exhausts the row), and the pages concatenated are the top-k bit for bit: the bits of a row's result depend on the two rows
+ * and the ceiling alone, whatever the batch, the run or the split into pages.  A zero score is returned and compared as +0.
+ * smi_xsim_topk_page: the arguments of smi_xsim_topk and the ceilings, fp32 / int32 [nx].  workspace:
+ *   smi_xsim_topk_page_ws_bytes(nx, ny, k, d) bytes, 16-byte aligned (lists of 16 whatever k, the tile-major copies, one
+ *   64-bit ceiling key per padded row).  Refused before any launch: k outside [1, 16], d not a multiple of 64, empty input, rows
+ *   that do not fit int32, a null pointer, one ceiling array without the other, a short or misaligned workspace; the sizing call
+ *   returns 0 for such a shape.  Nothing is read back or allocated: the call can be captured into a graph. */
+int64_t smi_xsim_topk_page_ws_bytes(int64_t nx, int64_t ny, int32_t k, int32_t d);
+int smi_xsim_topk_page(const void* xn_f16, int64_t nx, const void* yn_f16, int64_t ny, int32_t d, int32_t k,
+                       int64_t y_index_offset, const float* ceil_score, const int32_t* ceil_idx, int32_t* idx, float* score,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 /* k-way merge of `parts` per-shard top-k lists (device fp32 / int32 [parts, n, k], each sorted as
  * smi_xsim_topk returns them) into the k best of their union, same total order (score desc, index asc).
  * Folds the per-rank partial y-side neighbour lists of the sharded margin scoring; part_idx /
@@ -774,6 +793,19 @@ int64_t smi_ivf_search_workspace_bytes(int64_t nq, int64_t K, int32_t nprobe, in
 int smi_ivf_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
                    const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                    void* workspace, int64_t workspace_bytes, void* stream);
+
+/* A page of the flat search (the contract of a page: smi_xsim_topk_page): the arguments of smi_ivf_search and,
+ * BEHIND them as the keyed twins take theirs, the ceilings ceil_score fp32 / ceil_idx int32 [nq], null for none -- ONE ceiling per query, shared by its probes: the result
+ * is the k <= 16 best rows strictly after the ceiling over all the lists the query probes, in smi_ivf_search's order, layout
+ * and score bits (a zero score as +0).  nprobe in [1, 64].  list_ids may be the effective ids of a row mask (3.24).  workspace:
+ * smi_ivf_search_page_ws_bytes(nq, K, nprobe, k, d) bytes, 16-byte aligned.  Refused before any launch: what
+ * smi_ivf_search refuses, with k outside [1, 16] and nprobe outside [1, 64] in place of its limits, and one ceiling array
+ * without the other; the sizing call returns 0 for a refused shape.  Nothing is read back or allocated. */
+int64_t smi_ivf_search_page_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d);
+int smi_ivf_search_page(const void* qn_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                        const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
+                        void* workspace, int64_t workspace_bytes, void* stream, const float* ceil_score,
+                        const int32_t* ceil_idx);
 
 /* Range search over the IVF-Flat lists (restated in tests/ivf_range_ref.py): EVERY row of the lists a query
  * probes whose score is at least the query's threshold, where smi_ivf_search returns the k <= 8 best.  How many rows that

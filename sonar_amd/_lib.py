@@ -424,6 +424,13 @@ SYMBOLS = {
     "smi_xsim_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "smi_xsim_topk": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),
     "smi_xsim_topk_i8": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _i64, _vp]),
+    # paged top-k: the pass again with (ceil_score, ceil_idx) in front of the outputs, the flat search with
+    # them behind its twin's arguments, as the keyed entries take theirs
+    "smi_xsim_topk_page_ws_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "smi_xsim_topk_page": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "smi_ivf_search_page_ws_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "smi_ivf_search_page": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp,
+                                      C.POINTER(_f32), C.POINTER(_i32)]),
     "smi_xsim_merge_topk": (C.c_int, [_vp, _vp, _i32, _i64, _i32, _vp, _vp, _vp]),
     "smi_xsim_margin_select": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     "smi_xsim_pair_scores": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _vp, _vp]),

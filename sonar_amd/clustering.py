@@ -181,6 +181,19 @@ class SphericalKMeans:
         score, idx = topk_normalized(normalize_rows(x), x.shape[0], self._c16, self.n_clusters, k)
         return (idx[:, 0], score[:, 0]) if k == 1 else (idx, score)
 
+    def predict_wide(self, x: torch.Tensor, k: int = 16) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`predict` for k up to 64, always [n, k]: the paged top-k (`xsim.topk_wide_normalized`), one pass
+        over the centroids per 16 results.  (labels -1, cosines -inf) where k exceeds the number of centroids."""
+        from .xsim import WIDE_MAX, check_count, topk_wide_normalized
+
+        check_count(k, "k", WIDE_MAX)
+        self._need_fit("predict_wide")
+        _check_matrix(x, "x")
+        if x.shape[1] != self._d:
+            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+        score, idx = topk_wide_normalized(normalize_rows(x), x.shape[0], self._c16, self.n_clusters, k)
+        return idx, score
+
 
 def update(xn: torch.Tensor, labels: torch.Tensor, n_clusters: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """smi_kmeans_update: (sums int64 [K, d] in units of 2^-24, counts int32 [K]) of the rows of xn (fp16 [>= n, d]) under

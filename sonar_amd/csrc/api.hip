@@ -637,6 +637,30 @@ int smi_xsim_topk(const void* xn, int64_t nx, const void* yn, int64_t ny, int32_
   return SMI_OK;
 }
 
+int64_t smi_xsim_topk_page_ws_bytes(int64_t nx, int64_t ny, int32_t k, int32_t d) {
+  if (nx <= 0 || ny <= 0 || k < 1 || k > 16 || d <= 0 || d % 64 || nx > 0x7fffff00LL || ny > 0x7fffff00LL) return 0;
+  return (int64_t)xsim_page_workspace_bytes(smi_xsim_padded_rows(nx), smi_xsim_padded_rows(ny), d);
+}
+
+int smi_xsim_topk_page(const void* xn, int64_t nx, const void* yn, int64_t ny, int32_t d, int32_t k, int64_t y_off,
+                       const float* ceil_score, const int32_t* ceil_idx, int32_t* idx, float* score, void* ws,
+                       int64_t ws_bytes, void* stream) {
+  if (!xn || !yn || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (!ceil_score != !ceil_idx) return fail(SMI_ERR_INVALID_ARG, "ceil_score and ceil_idx go together: both or neither");
+  if (k < 1 || k > 16) return fail(SMI_ERR_UNSUPPORTED, "k=%d outside [1,16]", k);
+  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
+  if (nx <= 0 || ny <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (nx > 0x7fffff00LL || ny > 0x7fffff00LL)
+    return fail(SMI_ERR_UNSUPPORTED, "nx=%lld, ny=%lld: row numbers must fit int32", (long long)nx, (long long)ny);
+  if (const int rc = check_ws(ws, ws_bytes, (size_t)smi_xsim_topk_page_ws_bytes(nx, ny, k, d),
+                              "smi_xsim_topk_page_ws_bytes(nx, ny, k, d)"))
+    return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(launch_xsim_topk_page((const f16*)xn, nx, smi_xsim_padded_rows(nx), (const f16*)yn, ny, smi_xsim_padded_rows(ny), d,
+                                k, y_off, ceil_score, ceil_idx, idx, score, ws, (hipStream_t)stream));
+  return SMI_OK;
+}
+
 int smi_xsim_merge_topk(const float* part_scores, const int32_t* part_idx, int32_t parts, int64_t n, int32_t k,
                         float* out_scores, int32_t* out_idx, void* stream) {
   if (!part_scores || !out_scores) return fail(SMI_ERR_INVALID_ARG, "null argument");

@@ -307,6 +307,62 @@ constexpr int PQ_CW = 256;  // codewords of every sub-quantiser of the product-q
 #undef IVF_TWIN_KEYS
 #undef IVF_TWIN_KEYARGS
 
+// ---------------------------------------------------------------- a page of the flat search
+// ivf_scan_lists_kernel with key lists of IVF_PAGE = 16 and the ceiling of the pair's query in the fold (IvfCeiling,
+// ivf_scan.hpp): the 16 best of the list strictly behind the ceiling.  The unit, the fetch and the slice loop are the flat
+// scan's, so a score has smi_ivf_search's bits.  Lists longer than 16 are not the way to more results: a row inserts about
+// K (1 + ln(n / K)) times, a quarter of a 1000-row list's candidates at K = 64, each a cascade of K dependent LDS atomics.
+// LDS behind the slice buffers: the key lists [B][16], the pair numbers [B], the ceiling keys [B].
+constexpr int IVF_PAGE = 16;
+template <int B>
+constexpr int ivf_page_scan_lds() { return ivf_scan_lds<B>(IVF_PAGE) + IvfCeiling<B>::LDS; }
+
+template <int B>
+__global__ __launch_bounds__(IVF_TB) void ivf_scan_page_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
+                                                               const f16* __restrict__ rows, const int32_t* __restrict__ ids,
+                                                               const int32_t* __restrict__ off, int K,
+                                                               const int32_t* __restrict__ poff,
+                                                               const int32_t* __restrict__ ubase,
+                                                               const int32_t* __restrict__ pairs, int k_out,
+                                                               float* __restrict__ ps, int32_t* __restrict__ pi,
+                                                               const unsigned long long* __restrict__ ceil_keys) {
+  constexpr int NR = B / 32, KT = IVF_PAGE;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* lists = (unsigned long long*)(smem + 4 * B * IVF_SLICE);
+  int* spair = (int*)(lists + B * KT);
+  IvfCeiling<B> ceil(ceil_keys, spair + B);
+  const int tid = threadIdx.x, b = blockIdx.x;
+  if (b >= ubase[K]) return;
+  const int l = ivf_unit_list(ubase, K, b);
+  const int p0 = poff[l] + (b - ubase[l]) * B;
+  const int npair = min(B, poff[l + 1] - p0);
+  const int s_begin = off[l], s_end = off[l + 1];
+  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [&](int pr) { ceil.pair(pr, nprobe); });
+  ceil.rows();
+
+  const int nk = d / IVF_BK, cc = tid & 7;
+  const f16* qsrc[NR];  // this thread's query rows of a slice
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int pr = spair[(tid >> 3) + 32 * j];
+    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
+  }
+  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {  // ivf_scan_lists_kernel's
+    const int tile = it / nk, ks = it - tile * nk;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
+      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
+      lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
+    ivf_topk_fold_page<KT, B>(lists, npair, *(const int4*)(ids + slot0), acc, ceil);
+  };
+  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
+  ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
+}
+
 int i8_check_dim(int32_t d) {
   if (d > IVF_I8_MAX_DIM)
     return fail(SMI_ERR_UNSUPPORTED, "d=%d: above %d the int32 sum of int8 products could overflow", d, IVF_I8_MAX_DIM);
@@ -1177,11 +1233,61 @@ int i8_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes
       });
 }
 
+// smi_ivf_search_page: the flat search with lists of a page, up to 64 probes and a ceiling per query.  Its
+// workspace is the search's and one 64-bit ceiling key per query behind it.
+int check_search_page_args(int64_t nq, int32_t d, int64_t K, int32_t nprobe, int32_t k) {
+  if (const int rc = check_shape(nq, "nq", d, K, "list")) return rc;
+  if (k < 1 || k > IVF_PAGE) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, %d]", k, IVF_PAGE);
+  if (nprobe < 1 || nprobe > 64) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 64]", nprobe);
+  if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
+  return SMI_OK;
+}
+struct SearchPageWs : SearchWs {
+  unsigned long long* ceil;
+  SearchPageWs(void* ws, int64_t nq, int64_t K, int nprobe, int k) : SearchWs(ws, nq, K, nprobe, k) {
+    ceil = take<unsigned long long>((size_t)nq, 16);
+  }
+};
+int flat_search_page_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                           const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, const float* ceil_score,
+                           const int32_t* ceil_idx, int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
+  if (!qn || !list_rows || !probes || !list_ids || !list_offsets || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (!ceil_score != !ceil_idx) return fail(SMI_ERR_INVALID_ARG, "ceil_score and ceil_idx go together: both or neither");
+  if (const int rc = check_search_page_args(nq, d, K, nprobe, k)) return rc;
+  const int64_t P = nq * nprobe;
+  const SearchPageWs w(ws, nq, K, nprobe, k);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_search_page_ws_bytes(nq, K, nprobe, k, d)")) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  if (ceil_idx) HIP_TRY(launch_ceiling_keys(ceil_score, ceil_idx, nq, nq, 0, w.ceil, st));
+  const int unit = unit_pairs(P, K);  // the search's rule
+  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
+  const int64_t units = units_bound(P, K, unit);
+  HIP_TRY((launch_units<ivf_scan_page_kernel<IVF_BM>, ivf_scan_page_kernel<IVF_BIG>>(
+      unit, units, ivf_page_scan_lds<IVF_BM>(), ivf_page_scan_lds<IVF_BIG>(), st, (const f16*)qn, d, (int)nq, nprobe,
+      (const f16*)list_rows, list_ids, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
+      (const int32_t*)w.pairs, k, w.ps, w.pi, (const unsigned long long*)(ceil_idx ? w.ceil : nullptr))));
+  HIP_TRY(launch_topk_merge_page(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  return SMI_OK;
+}
+
 }  // namespace
 
 }  // namespace smi
 
 extern "C" {
+
+int64_t smi_ivf_search_page_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
+  const KeepLastError keep;
+  return check_search_page_args(nq, d, K, nprobe, k) ? 0 : (int64_t)SearchPageWs(nullptr, nq, K, nprobe, k).bytes();
+}
+
+int smi_ivf_search_page(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                        const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
+                        void* ws, int64_t ws_bytes, void* stream, const float* ceil_score, const int32_t* ceil_idx) {
+  return flat_search_page_entry(qn, nq, d, probes, nprobe, list_rows, list_ids, list_offsets, K, k, ceil_score, ceil_idx, idx, score,
+                                ws, ws_bytes, stream);
+}
 
 int32_t smi_ivf_list_align(void) { return IVF_ALIGN; }
 

@@ -245,6 +245,50 @@ __device__ __forceinline__ void ivf_topk_fold(unsigned long long* lists, int npa
     }
   }
 }
+// The ceiling of a page, in the place IvfKeyTest occupies in a list-walking kernel: B 64-bit keys of LDS at
+// `lds`, the packed ceiling of the QUERY of every unit row (one per query, shared by its probes: the merged page is then the
+// best after the ceiling over all probed lists), written by pair() in the unit prologue by the threads tid < B; rows() behind
+// the prologue's barrier takes the keys of this lane's unit rows into registers; behind(bi, v, id) is the test, to be asked
+// behind id >= 0.  keys null: no ceiling (every key is below ~0).  A unit row without a pair gets 0: nothing is behind it.
+template <int B>
+struct IvfCeiling {
+  static constexpr int LDS = B * 8;
+  const unsigned long long* __restrict__ keys;
+  unsigned long long* sck;
+  unsigned long long ck[B / 32];
+  __device__ __forceinline__ IvfCeiling(const unsigned long long* k, void* lds) : keys(k), sck((unsigned long long*)lds) {}
+  __device__ __forceinline__ void pair(int pr, int nprobe) { sck[threadIdx.x] = pr < 0 ? 0ull : keys ? keys[pr / nprobe] : ~0ull; }
+  __device__ __forceinline__ void rows() {
+    const int row0 = (threadIdx.x >> 6 & 1) * (B / 2) + (threadIdx.x & 15);
+#pragma unroll
+    for (int bi = 0; bi < B / 32; ++bi) ck[bi] = sck[row0 + bi * 16];
+  }
+  __device__ __forceinline__ bool behind(int bi, float v, int id) const { return xs_key(v, id) < ck[bi]; }
+};
+
+// ivf_topk_fold of a page: the fp32 sum is the score, its zero taken as +0 (the keys order -0 below +0, `better` does not),
+// and a candidate enters only behind the ceiling of its unit row's query.
+template <int KT, int B>
+__device__ __forceinline__ void ivf_topk_fold_page(unsigned long long* lists, int npair, int4 id4, const f32x4 (&acc)[B / 32],
+                                                   const IvfCeiling<B>& ceil) {
+  const int lane = threadIdx.x & 63, wc = (threadIdx.x >> 6) & 1;
+  const int idr[4] = {id4.x, id4.y, id4.z, id4.w};
+#pragma unroll
+  for (int bi = 0; bi < B / 32; ++bi) {
+    const int pr = wc * (B / 2) + bi * 16 + (lane & 15);
+    if (pr < npair) {
+      unsigned long long* lst = lists + pr * KT;
+      const float thr =
+          xs_unord((uint32_t)(__hip_atomic_load(lst + KT - 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) >> 32));
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float v = acc[bi][r] + 0.0f;
+        if (idr[r] >= 0 && v >= thr && ceil.behind(bi, v, idr[r])) xs_list_insert<KT>(lst, v, idr[r]);
+      }
+    }
+  }
+}
+
 // the fp32 sum is the score
 struct IvfSumIsScore {
   __device__ __forceinline__ auto operator()(int) const {

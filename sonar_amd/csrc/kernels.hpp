@@ -173,6 +173,17 @@ hipError_t launch_xsim_merge(const float* ps, const int* pi, int nchunks, int64_
                              int64_t y_index_offset, int32_t* idx, float* score, hipStream_t stream);
 hipError_t launch_topk_merge(const float* part_scores, const int32_t* part_idx, int parts, int64_t n, int k,
                              float* out_scores, int32_t* out_idx, hipStream_t stream);
+// a page of the top-k: the k <= 16 best of every row strictly behind its ceiling (ceil_score, ceil_idx
+// [nx], both null: no ceiling); launch_topk_merge at the list length of a page
+size_t xsim_page_workspace_bytes(int64_t nx_pad, int64_t ny_pad, int d);
+hipError_t launch_xsim_topk_page(const f16* Xn, int64_t nx, int64_t nx_pad, const f16* Yn, int64_t ny, int64_t ny_pad, int d,
+                                 int k, int64_t y_index_offset, const float* ceil_score, const int32_t* ceil_idx, int32_t* idx,
+                                 float* score, void* workspace, hipStream_t stream);
+// keys[r] = the packed key of row r's ceiling (id - id_offset in the scan's terms), 0 for an exhausted row and for r >= n
+hipError_t launch_ceiling_keys(const float* ceil_score, const int32_t* ceil_idx, int64_t n, int64_t n_pad, int64_t id_offset,
+                               unsigned long long* keys, hipStream_t stream);
+hipError_t launch_topk_merge_page(const float* part_scores, const int32_t* part_idx, int parts, int64_t n, int k,
+                                  float* out_scores, int32_t* out_idx, hipStream_t stream);
 hipError_t launch_margin_select(const float* fwd_scores, const int32_t* fwd_idx, int64_t nx, int k,
                                 const float* bwd_scores, int64_t ny, int kind, int64_t x_off, int32_t* pred,
                                 float* pred_margin, int32_t* err_count, hipStream_t stream);

@@ -43,4 +43,22 @@ __device__ __forceinline__ void xs_insert(unsigned long long* list, float v, int
   }
 }
 
+// xs_insert for the lists of a page (K = 16), the cascade as a LOOP: unrolled, the 16 x 16 x 16 atomics of a
+// lane's insertion path made hipcc index the walk's accumulators through scratch (528 bytes a lane).  The same list for the
+// same keys: slot j keeps the larger, the smaller travels on, and an empty key has nowhere to go.
+template <int K>
+__device__ __forceinline__ void xs_insert_rolled(unsigned long long* list, float v, int n) {
+  unsigned long long key = xs_key(v, n);
+#pragma unroll 1
+  for (int j = 0; j < K && key != XS_EMPTY; ++j) {
+    const unsigned long long old = __hip_atomic_fetch_max(list + j, key, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    key = old < key ? old : key;
+  }
+}
+template <int K>
+__device__ __forceinline__ void xs_list_insert(unsigned long long* list, float v, int n) {
+  if constexpr (K > 8) xs_insert_rolled<K>(list, v, n);
+  else xs_insert<K>(list, v, n);
+}
+
 }  // namespace smi

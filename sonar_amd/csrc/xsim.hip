@@ -375,6 +375,110 @@ hipError_t launch_xsim_topk(const f16* Xn, int64_t nx, int64_t nx_pad, const f16
   });
 }
 
+// ------------------------------------------------- paged top-k
+// A page: the k <= 16 best candidates strictly BEHIND a per-row exclusive ceiling (cs, ci) in the total order.  Lists of 16
+// keys fill the LDS above the ring exactly ([256][16] x 8 B = 32 KiB: 160 KiB in all), so the ceilings stay in memory, as
+// packed keys, and are read on the insertion path (xs_fold_lists).  Without ceilings the pass is the plain K = 16 walk.
+constexpr int XS_PAGE = 16;
+static_assert(G2_LDS_BYTES + 256 * XS_PAGE * 8 == 160 * 1024, "the lists of a page fill the LDS above the ring");
+static_assert(7 * 128 * XS_PAGE < 65536, "the immediate offsets of xs_thresholds fit ds_read_b32's 16-bit field");
+
+struct XsF16Page : XsF16<XS_PAGE> {
+  static constexpr bool CEILING = true;
+  const unsigned long long* __restrict__ ceil;  // [nx_pad]; from init on, of the tile's rows
+  __device__ __forceinline__ void init(const XsLane&, char*, int m0, int) { ceil += m0; }
+  __device__ __forceinline__ unsigned long long ceiling(int row) const { return ceil[row]; }
+};
+
+__global__ __launch_bounds__(G2_THREADS) void xsim_page_tile256_kernel(const f16* __restrict__ Xn, const f16* __restrict__ Yn,
+                                                                       int d, int ntx, int nty, int nchunks,
+                                                                       int tiles_per_chunk, int ny, int nx_pad,
+                                                                       float* __restrict__ ps, int* __restrict__ pi,
+                                                                       const unsigned long long* __restrict__ ceil) {
+  XsF16Page p;
+  p.ceil = ceil;
+  xsim_walk<XS_PAGE>(p, Xn, Yn, d, ntx, nty, nchunks, tiles_per_chunk, ny, nx_pad, ps, pi);
+}
+
+// The ceiling of every row as ONE key, in the walk's terms (y row number = returned id - y_off): a candidate is behind the
+// ceiling iff its key is smaller.  ci < 0: the row is exhausted, nothing is (key 0: no key is smaller).  A ceiling need not be
+// a candidate: an id in front of the walk's first row admits every row that ties the score, one behind its last row none.
+// The score's zero is taken as +0, as the fold takes a candidate's.  Rows from nx on are pad rows: exhausted.
+__global__ __launch_bounds__(256) void xsim_ceiling_keys_kernel(const float* __restrict__ cs, const int32_t* __restrict__ ci,
+                                                                int64_t nx, int64_t nx_pad, int64_t y_off,
+                                                                unsigned long long* __restrict__ keys) {
+  const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (r >= nx_pad) return;
+  unsigned long long key = 0ull;
+  if (r < nx && ci[r] >= 0) {
+    const uint32_t o = xs_ord(cs[r] + 0.0f);
+    const int64_t n = (int64_t)ci[r] - y_off;
+    if (n < 0) key = o == 0xffffffffu ? ~0ull : (unsigned long long)(o + 1u) << 32;
+    else if (n > 0x7ffffffeLL) key = (unsigned long long)o << 32;
+    else key = xs_key_ord(o, (int)n);
+  }
+  keys[r] = key;
+}
+
+hipError_t launch_ceiling_keys(const float* ceil_score, const int32_t* ceil_idx, int64_t n, int64_t n_pad, int64_t id_offset,
+                               unsigned long long* keys, hipStream_t stream) {
+  hipLaunchKernelGGL(xsim_ceiling_keys_kernel, dim3((unsigned)((n_pad + 255) / 256)), dim3(256), 0, stream, ceil_score, ceil_idx, n,
+                     n_pad, id_offset, keys);
+  return hipGetLastError();
+}
+
+// the workspace of a page: XsimWs at lists of 16 (one chunk per 256 rows of y: what the walk fills) | ceiling keys [nx_pad]
+struct XsimPageWs : XsimWs {
+  unsigned long long* ceil;
+  XsimPageWs(void* ws, int64_t nx_pad, int64_t ny_pad, int d) : XsimWs(ws, nx_pad, ny_pad, XS_PAGE, (int64_t)d * sizeof(f16), G2_BN) {
+    ceil = take<unsigned long long>((size_t)nx_pad);
+  }
+};
+
+size_t xsim_page_workspace_bytes(int64_t nx_pad, int64_t ny_pad, int d) { return XsimPageWs(nullptr, nx_pad, ny_pad, d).bytes(); }
+
+hipError_t launch_xsim_topk_page(const f16* Xn, int64_t nx, int64_t nx_pad, const f16* Yn, int64_t ny, int64_t ny_pad, int d,
+                                 int k, int64_t y_off, const float* ceil_score, const int32_t* ceil_idx, int32_t* idx,
+                                 float* score, void* ws, hipStream_t stream) {
+  if (nx <= 0 || ny <= 0 || k < 1 || k > XS_PAGE || d % G2_BK || ny_pad > 0x7fffff00LL || nx_pad > 0x7fffff00LL ||
+      nx_pad % G2_BM || ny_pad % G2_BN || !ceil_score != !ceil_idx)
+    return hipErrorInvalidValue;
+  const XsimPageWs w(ws, nx_pad, ny_pad, d);
+  const int ntx = (int)(nx_pad / G2_BM), nty = (int)(ny_pad / G2_BN);
+  const int nchunks = xsim_chunks(nty);
+  const int tpc = (nty + nchunks - 1) / nchunks;
+  const int64_t row_bytes = (int64_t)d * sizeof(f16);
+  hipError_t e = xsim_pack((const char*)Xn, w.xtm, nx_pad, row_bytes, stream);
+  if (e != hipSuccess) return e;
+  e = xsim_pack((const char*)Yn, w.ytm, ny_pad, row_bytes, stream);
+  if (e != hipSuccess) return e;
+  constexpr int lds = G2_LDS_BYTES + XsF16<XS_PAGE>::LDS_ABOVE;
+  if (ceil_idx) {
+    e = launch_ceiling_keys(ceil_score, ceil_idx, nx, nx_pad, y_off, w.ceil, stream);
+    if (e != hipSuccess) return e;
+    e = launch_with_lds<xsim_page_tile256_kernel>(dim3(ntx * nchunks), G2_THREADS, lds, stream, (const f16*)w.xtm,
+                                                  (const f16*)w.ytm, d, ntx, nty, nchunks, tpc, (int)ny, (int)nx_pad, w.ps, w.pi,
+                                                  (const unsigned long long*)w.ceil);
+  } else {
+    e = launch_with_lds<xsim_tile256_kernel<XS_PAGE>>(dim3(ntx * nchunks), G2_THREADS, lds, stream, (const f16*)w.xtm,
+                                                      (const f16*)w.ytm, d, ntx, nty, nchunks, tpc, (int)ny, (int)nx_pad, w.ps,
+                                                      w.pi);
+  }
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(xsim_merge_kernel<XS_PAGE>, dim3((unsigned)((nx + 255) / 256)), dim3(256), 0, stream, w.ps, w.pi, nchunks, nx,
+                     (int)nx_pad, k, y_off, idx, score);
+  return hipGetLastError();
+}
+
+// launch_topk_merge for the lists of a page (k <= 16): the IVF page merges its probes' parts with it
+hipError_t launch_topk_merge_page(const float* ps, const int32_t* pi, int parts, int64_t n, int k, float* os, int32_t* oi,
+                                  hipStream_t stream) {
+  if (parts < 1 || parts > 64 || k < 1 || k > XS_PAGE || n <= 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, ps, pi, parts, n, k,
+                     os, oi);
+  return hipGetLastError();
+}
+
 }  // namespace smi
 
 #ifdef SMI_XSIM_TRACE

@@ -118,6 +118,14 @@ __device__ __forceinline__ void xs_thresholds(unsigned lds_addr, float (&t)[8]) 
 // row's 16) and score (one element, on the slow path).
 // L comes BY VALUE, here and in XsF16::top1_fold: as a reference into the walk's frame hipcc allocates 15 more VGPRs to every
 // tile kernel, 255 of 256 in the int8 ones (profiles/isa_identity_xsim_walk.txt).
+// A policy that declares `static constexpr bool CEILING = true` is a PAGE: ceiling(row) is the packed key of
+// the tile row's exclusive ceiling, and a candidate enters only with a key strictly below it.  The test sits on the insertion
+// path alone; a policy without the member compiles to the text without it.
+template <class P, class = void>
+struct xs_has_ceiling : std::false_type {};
+template <class P>
+struct xs_has_ceiling<P, std::enable_if_t<P::CEILING>> : std::true_type {};
+
 template <int K, class P>
 __device__ __forceinline__ void xs_fold_lists(P& p, const typename P::acc_t (&acc)[4][8], unsigned long long* lists,
                                               unsigned thr_addr, const XsLane L, int n0f, int ny) {
@@ -132,18 +140,42 @@ __device__ __forceinline__ void xs_fold_lists(P& p, const typename P::acc_t (&ac
     hit |= vmx[mi] >= rowthr[mi];
   }
   if (__any(hit)) {
+    if constexpr (xs_has_ceiling<P>::value) {
+      // a page: only candidates strictly behind the row's ceiling enter, one compare of keys.  The ceilings
+      // of the lane's 8 rows are loaded HERE, on the insertion path, all in front of the first use: LDS is full at K = 16, and
+      // 16 more registers per lane held across the whole walk would spill.  hipcc waits for the DMA slices in flight in
+      // front of a global load's use (vmcnt): correct, once per fold, and the ring is full behind it.
+      unsigned long long ceil[8];
 #pragma unroll
-    for (int mi = 0; mi < 8; ++mi) {
-      if (vmx[mi] >= rowthr[mi]) {
-        unsigned long long* lst = lists + L.row(mi) * K;
+      for (int mi = 0; mi < 8; ++mi) ceil[mi] = p.ceiling(L.row(mi));
 #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
+      for (int mi = 0; mi < 8; ++mi) {
+        if (vmx[mi] >= rowthr[mi]) {
+          unsigned long long* lst = lists + L.row(mi) * K;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int n = L.col(ni, r, n0f);
-            const float v = p.score(acc, ni, mi, r, ts);
-            if (v >= rowthr[mi] && n < ny) xs_insert<K>(lst, v, n);
-          }
+          for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int n = L.col(ni, r, n0f);
+              const float v = p.score(acc, ni, mi, r, ts) + 0.0f;  // -0 -> +0: the keys order them, `better` does not
+              if (v >= rowthr[mi] && n < ny && xs_key(v, n) < ceil[mi]) xs_list_insert<K>(lst, v, n);
+            }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int mi = 0; mi < 8; ++mi) {
+        if (vmx[mi] >= rowthr[mi]) {
+          unsigned long long* lst = lists + L.row(mi) * K;
+#pragma unroll
+          for (int ni = 0; ni < 4; ++ni)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              const int n = L.col(ni, r, n0f);
+              const float v = p.score(acc, ni, mi, r, ts);
+              if (v >= rowthr[mi] && n < ny) xs_list_insert<K>(lst, v, n);
+            }
+        }
       }
     }
   }

@@ -48,13 +48,21 @@ query's filtered result is, bit for bit, its unfiltered result over an index tha
 `PreTransformIndex` puts a learned linear transform (`sonar_amd.transforms`: a PCA that cuts the dimension, an OPQ rotation in
 front of the sub-quantisers) in front of any of the four classes, FAISS's `IndexPreTransform`.
 
-Not here: a look-up-table scan for a handful of queries, codes of fewer than 8 bits, nprobe or
-k above 8, de-duplication or range search over quantised lists, incremental add and removal, 64-bit ids, splitting of long
+Wide search: `probe_wide` (every class) and `IVFFlatIndex.search_wide` take nprobe and k up to 64 --
+the range real corpora are probed at -- as pages of 16 results: `search_page(..., below=)` returns the k <= 16 best rows of
+the probed lists strictly after a per-query exclusive ceiling, and `search_wide` chains ceil(k / 16) of them, each page's
+last entry the next one's ceiling.  The pages concatenated are the top-k bit for bit.  `search`, `probe` and every other
+entry keep their limit of 8.
+
+Not here: a look-up-table scan for a handful of queries, codes of fewer than 8 bits, lists of more than 16
+results in one pass, k above 64, nprobe or k above 8 on the int8 / PQ / residual indexes, in `range_search` and in `mining`,
+the key predicate on the wide search, de-duplication or range search over quantised lists, incremental add and removal, 64-bit ids, splitting of long
 lists, multi-GPU sharding; of filtering: skipping whole tiles or lists by key, per-query bitmaps or id lists, keys wider than
 32 bits, more than one key per row, a filter on the coarse probe.
 """
 from __future__ import annotations
 
+import ctypes as C
 from typing import Dict, NamedTuple, Optional, Tuple, Union
 
 import torch
@@ -62,7 +70,8 @@ import torch
 from . import _lib
 from .clustering import SphericalKMeans, init_rows
 from .mining import pair_scores
-from .xsim import normalize_rows, topk_normalized
+from .xsim import (PAGE, WIDE_MAX, check_below, check_count, last_entry, normalize_rows, page_sizes, topk_normalized,
+                   topk_wide_normalized)
 
 LIST_ALIGN = 16    # SMI_IVF_LIST_ALIGN: every list starts at a multiple of this many slots and is padded to it
 UNIT_QUERIES = 64  # SMI_IVF_UNIT_QUERIES: queries of one list that one work unit of the scan takes (128 when nq nprobe >= 256 K)
@@ -265,6 +274,36 @@ def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids
     keyed = _check_keyed(slot_keys, query_keys, accept, ids.shape[0], probes.shape[0])
     return _search("smi_ivf_search", "smi_ivf_search_workspace_bytes", qn, probes, k, (), (rows.data_ptr(),), ids, offsets,
                    keyed=keyed)
+
+
+def search_lists_page(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
+                      k: int = PAGE, below=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_ivf_search_page: `search_lists` for k <= 16 and probes int32 [nq, 1..64], and with below =
+    (scores fp32 [nq], ids int32 [nq]) the k best rows of the probed lists strictly AFTER each query's exclusive ceiling
+    in the total order (score descending, ties to the lower id) -- one ceiling per query, over all its lists.  A query
+    whose ceiling id is negative is exhausted: only fill.  ids may be a `RowFilter`'s.  Nothing is read back."""
+    check_count(k, "k", PAGE)
+    _check_rows16(qn, "qn")
+    if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= WIDE_MAX
+                                             or not 1 <= probes.shape[0] <= qn.shape[0]):
+        raise ValueError(f"probes must be [nq, 1..{WIDE_MAX}] with nq <= {qn.shape[0]} rows, got {list(probes.shape)}")
+    _check_table(probes, "probes", *(probes.shape if isinstance(probes, torch.Tensor) else (-1, 1)))
+    _check_lists_dim(qn, rows)
+    (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
+    below = check_below(below, nq, qn)
+    lib = _lib.load()
+    ws_bytes = int(lib.smi_ivf_search_page_ws_bytes(nq, n_lists, nprobe, k, d))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
+    idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
+    score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
+    probes = probes.contiguous()
+    with torch.cuda.device(qn.device):
+        ceil = (C.cast(below[0].data_ptr(), C.POINTER(C.c_float)), C.cast(below[1].data_ptr(), C.POINTER(C.c_int32))) \
+            if below else (None, None)
+        _lib.check(lib.smi_ivf_search_page(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, rows.data_ptr(), ids.data_ptr(),
+                                           offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(),
+                                           ws_bytes, _lib.current_stream_ptr(), *ceil))
+    return score, idx
 
 
 class RangeResult(NamedTuple):
@@ -780,6 +819,22 @@ class _IVFIndex:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
         return topk_normalized(qn, q.shape[0], self._c16, self._k, nprobe)[1]
 
+    def probe_wide(self, q: torch.Tensor, nprobe: int = PAGE) -> torch.Tensor:
+        """`probe` for nprobe up to 64: the paged top-k against the centroids (`xsim.topk_wide_normalized`),
+        one pass over them per 16 lists.  Like `probe`, it refuses an nprobe above the number of lists."""
+        return self._probe_wide(q, nprobe)[1]
+
+    def _probe_wide(self, q, nprobe, qn=None):
+        """(coarse scores, probes) of `probe_wide`; qn: the normalised q, where the caller has it."""
+        check_count(nprobe, "nprobe", WIDE_MAX)
+        _check_matrix(q, "q")
+        if q.shape[1] != self._d:
+            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
+        if nprobe > self._k:
+            raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
+        qn = normalize_rows(q) if qn is None else qn
+        return topk_wide_normalized(qn, q.shape[0], self._c16, self._k, nprobe)
+
     def row_filter(self, keys: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> RowFilter:
         """The `RowFilter` of `search(..., rows=)`.  keys: device int32 [n], the key of every row `add` was
         given (row number = id), for `query_keys=` / `match=`; mask: device bool [n], False = the row does not exist for any
@@ -937,6 +992,56 @@ class IVFFlatIndex(_IVFIndex):
         probed rows qualify, (-inf, -1) behind them, the same bits alone and in any batch.  Nothing more is read back; the
         call stays capturable."""
         return self._checked_search(q, k, nprobe, probes, rows=rows, query_keys=query_keys, match=match)
+
+    def _check_search_wide(self, q, k, most_k, nprobe, probes, rows, what: str):
+        """The argument checks of `search_page` / `search_wide`; returns (nq, the ids the scan runs on)."""
+        check_count(k, "k", most_k)
+        check_count(nprobe, "nprobe", WIDE_MAX)
+        self._need_add(what)
+        _check_matrix(q, "q")
+        if q.shape[1] != self._d:
+            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
+        nq = q.shape[0]
+        if probes is not None:
+            if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= WIDE_MAX):
+                raise ValueError(f"probes must be [nq, 1..{WIDE_MAX}], got {list(probes.shape)}")
+            _check_table(probes, "probes", nq, probes.shape[1] if isinstance(probes, torch.Tensor) else 1)
+        elif nprobe > self._k:
+            raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
+        ids = self._filter(rows, None, "==", nq)[0]
+        return nq, self._ids if ids is None else ids
+
+    def search_page(self, q: torch.Tensor, k: int = PAGE, nprobe: int = 1, probes: Optional[torch.Tensor] = None, *,
+                    rows: Optional[RowFilter] = None, below=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """One page of a wide search: `search` for k <= 16 and nprobe <= 64, and with below = (scores fp32
+        [nq], ids int32 [nq]) the k best rows of the probed lists strictly AFTER each query's exclusive ceiling in the total
+        order -- hand it the last entry of the page before.  A query whose ceiling id is negative (a fill entry) is
+        exhausted.  probes: None or device int32 [nq, 1..64]; give the SAME probes to every page of one search (the probe is
+        then computed once).  rows: the mask of a `RowFilter`, as for `search`; the key predicate is not available here."""
+        nq, ids = self._check_search_wide(q, k, PAGE, nprobe, probes, rows, "search_page")
+        below = check_below(below, nq, q)
+        qn = normalize_rows(q)
+        if probes is None:
+            probes = self._probe_wide(q, nprobe, qn)[1]
+        return search_lists_page(qn, probes, self._rows, ids, self._offsets, k, below)
+
+    def search_wide(self, q: torch.Tensor, k: int = PAGE, nprobe: int = PAGE, probes: Optional[torch.Tensor] = None, *,
+                    rows: Optional[RowFilter] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`search` for k and nprobe up to 64: one probe (`probe_wide`), then ceil(k / 16) pages of the
+        scan (`search_page`), each with the last entry of the one before as its ceiling, the last asking only for what is
+        left, concatenated on the device.  The result is the top-k of the probed lists in `search`'s order and layout, bit
+        for bit the same however it is split, alone or in any batch.  rows: the mask of a `RowFilter`.  No read-back."""
+        nq, ids = self._check_search_wide(q, k, WIDE_MAX, nprobe, probes, rows, "search_wide")
+        qn = normalize_rows(q)
+        if probes is None:
+            probes = self._probe_wide(q, nprobe, qn)[1]
+        pages, below = [], None
+        for kp in page_sizes(k):
+            pages.append(search_lists_page(qn, probes, self._rows, ids, self._offsets, kp, below))
+            below = last_entry(*pages[-1])
+        if len(pages) == 1:
+            return pages[0]
+        return torch.cat([p[0] for p in pages], 1), torch.cat([p[1] for p in pages], 1)
 
     def range_search(self, q: torch.Tensor, threshold: Union[float, torch.Tensor], nprobe: int = 1,
                      probes: Optional[torch.Tensor] = None, sort: bool = True, max_total: Optional[int] = None, *,
@@ -1222,6 +1327,17 @@ class PreTransformIndex:
         qt = self.transform.apply(q)
         score, idx = self.index.search(qt, k, nprobe, probes, **kwargs)
         return (score, idx) if refine is None else refine_candidates(normalize_rows(q), q.shape[0], refine, idx)
+
+    def probe_wide(self, q: torch.Tensor, nprobe: int = PAGE) -> torch.Tensor:
+        return self.index.probe_wide(self.transform.apply(q), nprobe)
+
+    def search_wide(self, q: torch.Tensor, k: int = PAGE, nprobe: int = PAGE, probes: Optional[torch.Tensor] = None,
+                    **kwargs) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`index.search_wide(transform.apply(q), k, nprobe, probes, **kwargs)`: the wrapped index must be an
+        `IVFFlatIndex`."""
+        if not hasattr(self.index, "search_wide"):
+            raise TypeError("search_wide needs the fp16 lists of an IVFFlatIndex")
+        return self.index.search_wide(self.transform.apply(q), k, nprobe, probes, **kwargs)
 
     def range_search(self, q: torch.Tensor, *args, **kwargs) -> RangeResult:
         """`index.range_search(transform.apply(q), ...)`: the thresholds are cosines in the transformed space."""

@@ -8,6 +8,10 @@ Here the similarity matrix is never materialised: `smi_xsim_topk` streams
 `topk_int8` / `topk_int8_normalized` run the same walk on int8 codes with one
 scale per row (`smi_xsim_topk_i8`): the integer MFMA on half
 the bytes, scores specified to their bits, optionally re-scored as fp16 cosines.
+`topk_wide` / `topk_wide_normalized` return up to 64 neighbours as pages of 16
+(`topk_page_normalized`, `smi_xsim_topk_page`): a page is the 16
+best candidates strictly after a per-row exclusive ceiling in the total order, and
+the pages concatenated are the top-k bit for bit; `topk` keeps its limit of 8.
 
 Multi-GPU (sharded_topk): X rows are sharded over ranks, every rank's Y shard
 is all-gathered once over RCCL/xGMI (2 GB for 1M x 1024 fp16 -- small next to
@@ -73,6 +77,93 @@ def topk(x: torch.Tensor, y: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, to
     """For every row of x: (cosine scores [nx,k] fp32, indices into y [nx,k] int32), best first."""
     xn, yn = normalize_rows(x), normalize_rows(y)
     return topk_normalized(xn, x.shape[0], yn, y.shape[0], k)
+
+
+PAGE = 16      # results of one page: the list length of the paged pass (DESIGN.md 3.27)
+WIDE_MAX = 64  # the most a wide call returns: four pages
+
+
+def check_count(v, name: str, most: int) -> None:
+    """k or nprobe of a paged call: a Python int in [1, most]."""
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= most:
+        raise ValueError(f"{name} = {v!r}: an integer in [1, {most}]")
+
+
+def check_below(below, n: int, like: Optional[torch.Tensor] = None):
+    """The ceilings of a page: None, or (scores fp32 [n], ids int32 [n]) on the device (of `like`) -> contiguous tensors."""
+    if below is None:
+        return None
+    if not isinstance(below, (tuple, list)) or len(below) != 2 or not all(isinstance(t, torch.Tensor) for t in below):
+        raise TypeError("below must be None or a (scores, ids) pair of tensors: one exclusive ceiling per row")
+    cs, ci = below
+    if cs.dtype != torch.float32 or tuple(cs.shape) != (n,):
+        raise ValueError(f"below: scores must be fp32 [{n}], got {cs.dtype} {list(cs.shape)}")
+    if ci.dtype != torch.int32 or tuple(ci.shape) != (n,):
+        raise ValueError(f"below: ids must be int32 [{n}], got {ci.dtype} {list(ci.shape)}")
+    if not cs.is_cuda or not ci.is_cuda:
+        raise RuntimeError("below: the ceilings must be on the HIP device (no CPU path)")
+    if cs.device != ci.device or (like is not None and cs.device != like.device):
+        raise ValueError(f"below: scores ({cs.device}) and ids ({ci.device}) must be on the device of the rows"
+                         + (f" ({like.device})" if like is not None else ""))
+    return cs.contiguous(), ci.contiguous()
+
+
+def page_sizes(k: int):
+    """The pages of a wide call for k results: 16, 16, ..., and what is left."""
+    return [min(PAGE, k - done) for done in range(0, k, PAGE)]
+
+
+def last_entry(score: torch.Tensor, idx: torch.Tensor):
+    """The ceiling of the next page: the last entry of every row of this one (a fill entry, id -1, exhausts the row)."""
+    return score[:, -1].contiguous(), idx[:, -1].contiguous()
+
+
+def topk_page_normalized(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, k: int = PAGE, y_index_offset: int = 0,
+                         below=None, _ws: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One page of the top-k (smi_xsim_topk_page): `topk_normalized` for k <= 16, and with below =
+    (scores fp32 [nx], ids int32 [nx]) the k best candidates strictly AFTER each row's exclusive ceiling in the total order
+    (score descending, ties to the lower id; ids as returned, y_index_offset included).  A row whose ceiling id is negative
+    is exhausted: only fill, (-inf, -1).  A ceiling need not be a candidate.  Nothing is read back."""
+    check_count(k, "k", PAGE)
+    below = check_below(below, nx, xn if isinstance(xn, torch.Tensor) and xn.is_cuda else None)
+    lib = _lib.load()
+    d = xn.shape[1]
+    if yn.shape[1] != d:
+        raise ValueError("x and y must have the same dimension")
+    ws_bytes = int(lib.smi_xsim_topk_page_ws_bytes(nx, ny, k, d))
+    ws = _ws if _ws is not None else torch.empty(ws_bytes, dtype=torch.uint8, device=xn.device)
+    idx = torch.empty((nx, k), dtype=torch.int32, device=xn.device)
+    score = torch.empty((nx, k), dtype=torch.float32, device=xn.device)
+    with torch.cuda.device(xn.device):
+        _lib.check(lib.smi_xsim_topk_page(xn.data_ptr(), nx, yn.data_ptr(), ny, d, k, y_index_offset,
+                                          below[0].data_ptr() if below else None, below[1].data_ptr() if below else None,
+                                          idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
+                                          _lib.current_stream_ptr()))
+    return score, idx
+
+
+def topk_wide_normalized(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, k: int = PAGE,
+                         y_index_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`topk_normalized` for k up to 64, in ceil(k / 16) pages (`topk_page_normalized`): every page takes the last entry of
+    the one before as its ceiling, the last page asks only for what is left, and the pages are concatenated on the device.
+    The result is the top-k in the total order, bit for bit the same however it is split; one pass over y per page."""
+    check_count(k, "k", WIDE_MAX)
+    lib = _lib.load()
+    ws = torch.empty(int(lib.smi_xsim_topk_page_ws_bytes(nx, ny, PAGE, xn.shape[1])), dtype=torch.uint8, device=xn.device)
+    pages, below = [], None
+    for kp in page_sizes(k):
+        pages.append(topk_page_normalized(xn, nx, yn, ny, kp, y_index_offset, below, _ws=ws))
+        below = last_entry(*pages[-1])
+    if len(pages) == 1:
+        return pages[0]
+    return torch.cat([p[0] for p in pages], 1), torch.cat([p[1] for p in pages], 1)
+
+
+def topk_wide(x: torch.Tensor, y: torch.Tensor, k: int = PAGE) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`topk` for k up to 64 (`topk_wide_normalized`)."""
+    check_count(k, "k", WIDE_MAX)
+    xn, yn = normalize_rows(x), normalize_rows(y)
+    return topk_wide_normalized(xn, x.shape[0], yn, y.shape[0], k)
 
 
 PRECISIONS = ("fp16", "int8")

@@ -1,5 +1,6 @@
 """Development aid: how much of the xsim mining kernel's slice stream is the per-tile fold (needs a -DSMI_XSIM_TRACE build:
-SMI_HIPCC_FLAGS=-DSMI_XSIM_TRACE python -m sonar_amd.build --force, or SMI_LIB=<variant .so>)."""
+SMI_HIPCC_FLAGS=-DSMI_XSIM_TRACE python -m sonar_amd.build --force, or SMI_LIB=<variant .so>).
+    python tools/xsim_trace.py [nx] [ny] [k] [ceiling]      k = 9 .. 16: a page; ceiling 1: the second page"""
 import ctypes as C
 import os
 import sys
@@ -19,8 +20,14 @@ def main():
     y = torch.randn(ny, 1024, device="cuda", generator=g).half()
     x = (y[torch.randint(0, ny, (nx,), device="cuda", generator=g)].float() + 0.3 * torch.randn(nx, 1024, device="cuda", generator=g)).half()
     xn, yn = xsim.normalize_rows(x), xsim.normalize_rows(y)
+    below = None
+    if k > 8 and len(sys.argv) > 4 and int(sys.argv[4]):
+        below = xsim.last_entry(*xsim.topk_page_normalized(xn, nx, yn, ny, k))
     for _ in range(2):
-        xsim.topk_normalized(xn, nx, yn, ny, k)
+        if k > 8:
+            xsim.topk_page_normalized(xn, nx, yn, ny, k, 0, below)
+        else:
+            xsim.topk_normalized(xn, nx, yn, ny, k)
     torch.cuda.synchronize()
     raw = C.CDLL(str(_lib.LIB_PATH))
     buf = np.zeros(256 * 2 * 4, dtype=np.uint64)
