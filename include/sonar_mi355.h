@@ -612,6 +612,67 @@ int smi_xsim_topk_page(const void* xn_f16, int64_t nx, const void* yn_f16, int64
                        int64_t y_index_offset, const float* ceil_score, const int32_t* ceil_idx, int32_t* idx, float* score,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Squared-Euclidean and inner-product search on rows AS THEY ARE (restated in tests/l2_ref.py).  With
+ * b[j] = -1/2 ||y_j||^2, argmax_j (x . y_j + b[j]) = argmin_j ||x - y_j||^2 and ||x - y_j||^2 = 2 (1/2 ||x||^2 - score): one
+ * additive term per y row makes the brute-force pass an L2 search.  The zero bias is maximum inner product; for that
+ * smi_xsim_topk itself serves on prepared rows (it never needed unit rows: its score is the fp32 sum of the tile).
+ * smi_l2_prepare: dst_f16 = the fp16 copy of src (round to nearest even from fp32), [smi_xsim_padded_rows(rows), d], the
+ *   rows from `rows` on zero: smi_xsim_normalize without the division.  half_norms (fp32 [padded rows], or NULL):
+ *   h[r] = fl32(1/2 S_r), S_r = the sum of the squares of the ROUNDED row, pad rows 0.  The squares are exact in fp64 and are
+ *   added in fp64 in THIS ORDER, which depends on d alone: the row is d / 8 chunks of 8 consecutive columns; for l = 0 .. 63,
+ *   p[l] = the sum, from 0, of the squares of chunks l, l + 64, l + 128, ... in that order, the 8 columns of a chunk in
+ *   ascending order; then six steps off = 32, 16, 8, 4, 2, 1, each replacing every p[l] by p[l] + p[l ^ off] at once; S_r = p[0].
+ *   A row holding a value that is not finite in fp16 (after the rounding) gives unspecified results, here and downstream.
+ *   d a multiple of 8; src and dst 16-byte aligned.
+ * smi_l2_topk: x_f16 / y_f16 are such prepared, padded matrices (or any fp16 rows in that layout), y_bias fp32
+ *   [smi_xsim_padded_rows(ny)], finite (otherwise unspecified), 16-byte aligned.  score(i, j) = fl32(acc(i, j) + y_bias[j]), acc
+ *   the fp32 sum smi_xsim_topk's tile produces for the two rows.  idx / score: smi_xsim_topk's layout, total order (score
+ *   descending, ties to the lower index) and (-1, -inf) fill; rows j >= ny never enter, whatever their bias.  A zero score is
+ *   +0.  The bits of a row's result depend on the two rows and the bias alone: the same alone or in any batch, on any run.
+ *   workspace: smi_l2_topk_ws_bytes(nx, ny, k, d) bytes, 16-byte aligned.  Refused before any launch: what smi_xsim_topk
+ *   refuses for the shape (k outside [1, 8], d not a multiple of 64, empty input, a null pointer, a short workspace), rows that
+ *   do not fit int32, a null or misaligned bias; the sizing call returns 0 for such a shape.  Nothing is read back or
+ *   allocated: the call can be captured into a graph.
+ * smi_l2_slot_bias: out[s] = -half_norms[list_ids[s]], and 0 where list_ids[s] < 0 (a pad or unused slot), for the `slots`
+ *   entries of an IVF index's list_ids: the bias of every slot, in slot order.
+ * smi_l2_flat_search: smi_ivf_search with its arguments and list_bias (fp32 [capacity_slots], 16-byte aligned,
+ *   from smi_l2_slot_bias) behind list_rows: q_f16 prepared queries, the lists built by smi_ivf_build over prepared rows, probes
+ *   from smi_l2_topk against the centroids with their bias.  score = fl32(sum + list_bias[slot]), sum what smi_ivf_search
+ *   returns for the two rows; everything else -- order, fill, unit rule, probes that name no list, pad slots (out by their id,
+ *   whatever their bias), refusals, the workspace (smi_l2_flat_search_ws_bytes = the flat search's size) -- is smi_ivf_search's.
+ *   A row mask works as there: ids of -1.  k and nprobe in [1, 8].
+ * Euclidean k-means (restated in tests/l2_ref.py).  x_f16: prepared rows.  The update is smi_kmeans_update, unchanged: its
+ *   integer sums are exact for any finite fp16 rows.
+ * smi_l2_kmeans_finalize: for a cluster with counts[c] > 0, centroids_f32[c][j] = fl32(fl64(sums[c][j]) * 2^-24 /
+ *   fl64(counts[c])) (int64 -> fp64 by round to nearest even; that expression is the contract), row c of centroids_f16 its round
+ *   to nearest even, centroid_half_norms[c] the half norm of that fp16 row in smi_l2_prepare's order.  A cluster without
+ *   members keeps all three; *empty_count (device int32, overwritten) = the number of those.  centroids_f16 has
+ *   smi_xsim_padded_rows(K) rows and centroid_half_norms as many entries; those from K on are zeroed.
+ * smi_l2_kmeans_fit: smi_kmeans_fit's loop, records and arguments, and centroid_half_norms behind centroids_f16.
+ *   resume = 0: centroids_f32 holds the K initial centroids; centroids_f16 / centroid_half_norms = smi_l2_prepare of them;
+ *   every row is assigned by smi_l2_topk's pass at k = 1 with the bias -centroid_half_norms (ties to the lower index: a
+ *   duplicate centroid stays empty); then n_iter rounds of update -> finalise -> assign.  resume = 1 continues on the same
+ *   buffers; fit(0) followed by T calls of fit(1, resume) equals fit(T) bit for bit.  scores: the score of every row against
+ *   its centroid, x . c - h_c; objective: their fp64 sum in smi_kmeans_fit's fixed order, so the inertia sum ||x - c||^2 is
+ *   2 (sum_i h_x[i] - objective).  moved / empty / sums / counts as there.  Nothing is read back: capturable.
+ *   workspace: smi_l2_kmeans_fit_ws_bytes(n, K, d) bytes, 16-byte aligned.  Refusals: smi_kmeans_fit's, and misaligned rows. */
+int smi_l2_prepare(const void* src, int32_t src_dtype, int64_t rows, int32_t d, void* dst_f16, float* half_norms, void* stream);
+int64_t smi_l2_topk_ws_bytes(int64_t nx, int64_t ny, int32_t k, int32_t d);
+int smi_l2_topk(const void* x_f16, int64_t nx, const void* y_f16, int64_t ny, int32_t d, int32_t k, int64_t y_index_offset,
+                const float* y_bias, int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, void* stream);
+int smi_l2_slot_bias(const int32_t* list_ids, int64_t slots, const float* half_norms, float* out, void* stream);
+int64_t smi_l2_flat_search_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d);
+int smi_l2_flat_search(const void* q_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                       const float* list_bias, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
+                       int32_t* idx, float* score, void* workspace, int64_t workspace_bytes, void* stream);
+int smi_l2_kmeans_finalize(const int64_t* sums, const int32_t* counts, int64_t K, int32_t d, float* centroids_f32,
+                           void* centroids_f16, float* centroid_half_norms, int32_t* empty_count, void* stream);
+int64_t smi_l2_kmeans_fit_ws_bytes(int64_t n, int64_t K, int32_t d);
+int smi_l2_kmeans_fit(const void* x_f16, int64_t n, int32_t d, int64_t K, int32_t n_iter, int32_t resume, float* centroids_f32,
+                      void* centroids_f16, float* centroid_half_norms, int32_t* labels, float* scores, int64_t* sums,
+                      int32_t* counts, double* objective, int32_t* moved, int32_t* empty, void* workspace,
+                      int64_t workspace_bytes, void* stream);
+
 /* k-way merge of `parts` per-shard top-k lists (device fp32 / int32 [parts, n, k], each sorted as
  * smi_xsim_topk returns them) into the k best of their union, same total order (score desc, index asc).
  * Folds the per-rank partial y-side neighbour lists of the sharded margin scoring; part_idx /

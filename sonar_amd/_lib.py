@@ -428,6 +428,17 @@ SYMBOLS = {
     # them behind its twin's arguments, as the keyed entries take theirs
     "smi_xsim_topk_page_ws_bytes": (_i64, [_i64, _i64, _i32, _i32]),
     "smi_xsim_topk_page": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    # L2 / inner product on rows as they are: smi_xsim_topk's arguments with y_bias in front of the outputs
+    "smi_l2_prepare": (C.c_int, [_vp, _i32, _i64, _i32, _vp, _vp, _vp]),
+    "smi_l2_topk_ws_bytes": (_i64, [_i64, _i64, _i32, _i32]),
+    "smi_l2_topk": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "smi_l2_slot_bias": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
+    "smi_l2_flat_search_ws_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
+    "smi_l2_flat_search": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    "smi_l2_kmeans_finalize": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "smi_l2_kmeans_fit_ws_bytes": (_i64, [_i64, _i64, _i32]),
+    "smi_l2_kmeans_fit": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _i64, _vp]),
     "smi_ivf_search_page_ws_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
     "smi_ivf_search_page": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp,
                                       C.POINTER(_f32), C.POINTER(_i32)]),

@@ -18,7 +18,7 @@ CSRC = ROOT / "csrc"
 OUT_DIR = ROOT / "lib"
 LIB_NAME = "libsonar_mi355.so"
 ARCH = "gfx950"
-SOURCES = ["api.hip", "gemm.hip", "gemm_v2.hip", "gemm_v2_lone.hip", "rowops.hip", "attention.hip", "xsim.hip", "xsim_i8.hip", "mining.hip", "align.hip", "kmeans.hip", "ivf.hip", "gram.hip", "decoder.hip", "decoder_api.hip", "speech.hip", "relpos_attention.hip", "speech_api.hip", "resample.hip", "host_input.cpp", "host_audio.cpp", "heads.hip", "head_train.hip", "sampling.hip", "flex.hip", "flex_encoder.hip", "laser2.hip", "score.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_v2.hip", "gemm_v2_lone.hip", "rowops.hip", "attention.hip", "xsim.hip", "xsim_i8.hip", "l2.hip", "mining.hip", "align.hip", "kmeans.hip", "ivf.hip", "gram.hip", "decoder.hip", "decoder_api.hip", "speech.hip", "relpos_attention.hip", "speech_api.hip", "resample.hip", "host_input.cpp", "host_audio.cpp", "heads.hip", "head_train.hip", "sampling.hip", "flex.hip", "flex_encoder.hip", "laser2.hip", "score.hip"]
 
 
 def hipcc() -> str:

@@ -7,8 +7,12 @@ fp16 rows, so one seed gives one run bit for bit.  `smi_kmeans_fit` enqueues eve
 nothing back; the per-round record is copied to the host only when `history` is read.  There is no CPU path.
 
 Used for semantic de-duplication, as the coarse quantiser of the IVF index (`sonar_amd.index.IVFFlatIndex`, DESIGN.md 3.18;
-`predict(x, k)` is its probe) and for codebooks over SONAR space.  Not here: Euclidean k-means, k-means++ initialisation,
-splitting of large clusters to refill empty ones (an empty cluster keeps its centroid), multi-GPU.
+`predict(x, k)` is its probe) and for codebooks over SONAR space.  Not here: k-means++ initialisation, splitting of large clusters to refill empty ones (an empty
+cluster keeps its centroid), multi-GPU.
+
+`KMeans` is ordinary (Euclidean) k-means on the rows as they are: the same update, a finalise that divides
+by the member count, and the assignment as the biased top-1 `argmax_c (x . c - ||c||^2 / 2) = argmin_c ||x - c||^2`
+(`smi_l2_kmeans_fit`).  SONAR embeddings are not unit vectors, and a product quantiser is an L2 object.
 """
 from __future__ import annotations
 
@@ -17,7 +21,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from .xsim import normalize_rows, topk_normalized
+from .xsim import normalize_rows, prepare_rows, topk_l2_prepared, topk_normalized
 
 UNIT_ROWS = 64  # SMI_KMEANS_UNIT_ROWS: members one work unit of the update sums in registers
 
@@ -193,6 +197,106 @@ class SphericalKMeans:
             raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
         score, idx = topk_wide_normalized(normalize_rows(x), x.shape[0], self._c16, self.n_clusters, k)
         return idx, score
+
+
+class KMeans(SphericalKMeans):
+    """Euclidean k-means with `SphericalKMeans`'s surface: fit / step / predict / centroids / history.  Attributes after
+    `fit`: centroids (fp32 [K, d], the means of the members), centroids_f16 (their fp16 roundings, what rows are assigned
+    against), centroid_half_norms (fp32 [K], ||c||^2 / 2 of the fp16 rows), labels (int32 [n]), scores (fp32 [n]: x . c - h_c
+    against the own centroid, so ||x - c||^2 = 2 (h_x - score)), counts, history (with `inertia`)."""
+
+    def fit(self, x: torch.Tensor, init: Optional[torch.Tensor] = None) -> "KMeans":
+        """x: fp16 / fp32 [n, d] on the device, taken as it is (rounded to fp16, not normalised).  init: None (K distinct rows
+        of x by `init_rows(n, K, seed)`) or [K, d]."""
+        _check_matrix(x, "x")
+        self._check_init(init, x.shape[0], x.shape[1])
+        start = init if init is not None else x[init_rows(x.shape[0], self.n_clusters, self.seed).to(x.device)]
+        x16, hx = prepare_rows(x)
+        return self._fit_l2(x16, hx, x.shape[0], start)
+
+    def fit_prepared(self, x16: torch.Tensor, half_norms: torch.Tensor, n: int, init: Optional[torch.Tensor] = None) -> "KMeans":
+        """As `fit`, on what `xsim.prepare_rows` returned (fp16 rows padded to a multiple of 256, their half norms) for n rows."""
+        _check_matrix(x16, "x16")
+        if x16.dtype != torch.float16 or not x16.is_contiguous():
+            raise ValueError("x16 must be the contiguous fp16 matrix prepare_rows returns")
+        if isinstance(n, bool) or not isinstance(n, int) or n < 1 or (n + 255) // 256 * 256 != x16.shape[0]:
+            raise ValueError(f"n = {n!r} does not match the {x16.shape[0]} padded rows of x16")
+        if (not isinstance(half_norms, torch.Tensor) or half_norms.dtype != torch.float32 or half_norms.device != x16.device
+                or tuple(half_norms.shape) != (x16.shape[0],)):
+            raise ValueError(f"half_norms must be the fp32 [{x16.shape[0]}] vector prepare_rows returns, on the device of x16")
+        self._check_init(init, n, x16.shape[1])
+        start = init if init is not None else x16[init_rows(n, self.n_clusters, self.seed).to(x16.device)]
+        return self._fit_l2(x16, half_norms, n, start)
+
+    def fit_normalized(self, *args, **kwargs):
+        raise TypeError("KMeans clusters rows as they are: use fit, or fit_prepared on what xsim.prepare_rows returns")
+
+    def _fit_l2(self, x16: torch.Tensor, hx: torch.Tensor, n: int, start: torch.Tensor) -> "KMeans":
+        lib = _lib.load()
+        dev, d, k = x16.device, x16.shape[1], self.n_clusters
+        self._hx = hx
+        self._ch = torch.empty((int(lib.smi_xsim_padded_rows(k)),), dtype=torch.float32, device=dev)
+        self._ws_bytes = int(lib.smi_l2_kmeans_fit_ws_bytes(n, k, d))
+        return self._fit(x16, n, start)  # the buffers and records of the spherical fit; _run below is the call
+
+    def _run(self, n_iter: int, resume: bool) -> None:
+        lib = _lib.load()
+        if self._ws.numel() < self._ws_bytes:
+            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self._xn.device)
+        a0 = self._rounds + 1 if resume else 0
+        need = a0 + n_iter + (0 if resume else 1)
+        if need > self._objective.shape[0]:
+            grow = max(need, 2 * self._objective.shape[0]) - self._objective.shape[0]
+            self._objective = torch.cat([self._objective, self._objective.new_zeros(grow)])
+            self._moved = torch.cat([self._moved, self._moved.new_zeros(grow)])
+            self._empty = torch.cat([self._empty, self._empty.new_zeros(grow)])
+        with torch.cuda.device(self._xn.device):
+            _lib.check(lib.smi_l2_kmeans_fit(
+                self._xn.data_ptr(), self._n, self._d, self.n_clusters, n_iter, int(resume), self._c32.data_ptr(),
+                self._c16.data_ptr(), self._ch.data_ptr(), self.labels.data_ptr(), self.scores.data_ptr(),
+                self._sums.data_ptr(), self.counts.data_ptr(), self._objective.data_ptr() + 8 * a0,
+                self._moved.data_ptr() + 4 * a0, self._empty.data_ptr() + 4 * self._rounds, self._ws.data_ptr(),
+                self._ws.numel(), _lib.current_stream_ptr()))
+        self._rounds += n_iter
+
+    @property
+    def centroids_f16(self) -> torch.Tensor:
+        self._need_fit("centroids_f16")
+        return self._c16[: self.n_clusters]
+
+    @property
+    def centroid_half_norms(self) -> torch.Tensor:
+        self._need_fit("centroid_half_norms")
+        return self._ch[: self.n_clusters]
+
+    @property
+    def centroids_normalized(self) -> torch.Tensor:
+        raise TypeError("KMeans keeps its centroids as they are: centroids (fp32) or centroids_f16")
+
+    @property
+    def history(self) -> Dict[str, List]:
+        """`SphericalKMeans.history`, objective being the sum of the scores x . c - h_c, and inertia = the sum of the squared
+        distances of the rows to their centroids, 2 (sum of the rows' half norms - objective), per assignment."""
+        h = SphericalKMeans.history.fget(self)
+        hx = float(self._hx[: self._n].double().sum().item())
+        h["inertia"] = [2.0 * (hx - o) for o in h["objective"]]
+        return h
+
+    def predict(self, x: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The k (<= 8) nearest centroids of every row of x, nearest first: (labels int32, squared distances fp32), [n] for
+        k = 1 and [n, k] otherwise."""
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
+            raise ValueError(f"k = {k!r}: an integer in [1, 8]")
+        self._need_fit("predict")
+        _check_matrix(x, "x")
+        if x.shape[1] != self._d:
+            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+        x16, hx = prepare_rows(x)
+        dist, idx, _ = topk_l2_prepared(x16, x.shape[0], hx, self._c16, self.n_clusters, self._ch, k)
+        return (idx[:, 0], dist[:, 0]) if k == 1 else (idx, dist)
+
+    def predict_wide(self, *args, **kwargs):
+        raise TypeError("predict_wide is the paged cosine top-k; KMeans.predict takes k <= 8")
 
 
 def update(xn: torch.Tensor, labels: torch.Tensor, n_clusters: int) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -1271,6 +1271,74 @@ int flat_search_page_entry(const void* qn, int64_t nq, int32_t d, const int32_t*
   return SMI_OK;
 }
 
+// ---------------------------------------------------------------- L2 flat search
+// ivf_scan_lists_kernel with ONE change: the fold loads the four slot biases (bias fp32 [slots], -1/2 ||row||^2 of the row a
+// slot holds, smi_l2_slot_bias) with one 16-byte load beside the four ids, and the score of a candidate is sum + bias.  The
+// sum starts from +0 and is never -0, so a zero score is +0 (l2.hip).  A pad slot stays out by id >= 0, whatever its bias.  Its
+// own kernel, outside the twice-included ivf_list_kernels.hpp: there is no keyed twin.
+template <int KT, int B>
+__global__ __launch_bounds__(IVF_TB) void ivf_l2_scan_lists_kernel(const f16* __restrict__ qn, int d, int nq, int nprobe,
+                                                                   const f16* __restrict__ rows, const int32_t* __restrict__ ids,
+                                                                   const float* __restrict__ bias, const int32_t* __restrict__ off,
+                                                                   int K, const int32_t* __restrict__ poff,
+                                                                   const int32_t* __restrict__ ubase,
+                                                                   const int32_t* __restrict__ pairs, int k_out,
+                                                                   float* __restrict__ ps, int32_t* __restrict__ pi) {
+  constexpr int NR = B / 32;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  unsigned long long* lists = (unsigned long long*)(smem + 4 * B * IVF_SLICE);
+  int* spair = (int*)(lists + B * KT);
+  const int tid = threadIdx.x, b = blockIdx.x;
+  if (b >= ubase[K]) return;
+  const int l = ivf_unit_list(ubase, K, b);
+  const int p0 = poff[l] + (b - ubase[l]) * B;
+  const int npair = min(B, poff[l + 1] - p0);
+  const int s_begin = off[l], s_end = off[l + 1];
+  ivf_pairs_init<KT, B>(lists, spair, pairs, p0, npair, [](int) {});
+
+  const int nk = d / IVF_BK, cc = tid & 7;
+  const f16* qsrc[NR];  // this thread's query rows of a slice
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    const int pr = spair[(tid >> 3) + 32 * j];
+    qsrc[j] = pr >= 0 ? qn + (size_t)(pr / nprobe) * d + cc * 8 : nullptr;
+  }
+  auto fetch = [&](int it, u32x4(&qv)[NR], u32x4(&lv)[NR]) {  // ivf_scan_lists_kernel's
+    const int tile = it / nk, ks = it - tile * nk;
+#pragma unroll
+    for (int j = 0; j < NR; ++j) {
+      const int slot = s_begin + tile * B + (tid >> 3) + 32 * j;
+      qv[j] = qsrc[j] ? *(const u32x4*)(qsrc[j] + ks * IVF_BK) : u32x4{0u, 0u, 0u, 0u};
+      lv[j] = slot < s_end ? *(const u32x4*)(rows + (size_t)slot * d + ks * IVF_BK + cc * 8) : u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  auto fold = [&](int slot0, const f32x4(&acc)[NR]) {
+    const f32x4 b4 = *(const f32x4*)(bias + slot0);
+    ivf_topk_fold<KT, B>(
+        lists, npair, *(const int4*)(ids + slot0), acc, [b4](int) { return [b4](float a, int r) { return a + b4[r]; }; },
+        IvfKeyTest<B, IvfNoKeys>(IvfNoKeys{}, nullptr));
+  };
+  ivf_slice_walk<B, IvfF16>(smem, s_begin, s_end, nk, ivf_live_blocks<B>(npair), fetch, fold);
+  ivf_lists_readout<KT>(lists, spair, npair, nprobe, nq, k_out, ps, pi);
+}
+
+// smi_l2_flat_search: smi_ivf_search's entry over the kernel above
+int l2_flat_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                         const float* list_bias, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
+                         int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
+  return search_entry(
+      !qn || !list_rows || !list_bias, nullptr, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_l2_flat_search_ws_bytes(nq, K, nprobe, k, d)", 0,
+      [&] { return (uintptr_t)list_bias % 16 ? fail(SMI_ERR_INVALID_ARG, "list_bias must be 16-byte aligned") : (int)SMI_OK; },
+      no_prepare, [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
+        constexpr int KT = decltype(kt)::value;
+        return launch_units<ivf_l2_scan_lists_kernel<KT, IVF_BM>, ivf_l2_scan_lists_kernel<KT, IVF_BIG>>(
+            unit, units, ivf_scan_lds<IVF_BM>(KT), ivf_scan_lds<IVF_BIG>(KT), st, (const f16*)qn, d, (int)nq, nprobe,
+            (const f16*)list_rows, list_ids, list_bias, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
+            (const int32_t*)w.pairs, k, w.ps, w.pi);
+      });
+}
+
 }  // namespace
 
 }  // namespace smi
@@ -1589,6 +1657,19 @@ int smi_range_search_emit_keyed(const void* qn, int64_t nq, int32_t d, const int
   const IvfKeys keys{slot_keys, query_keys, accept};
   return range_entry(!pair_base || !score || !idx, &keys, qn, nq, d, probes, nprobe, threshold, list_rows, list_ids, list_offsets,
                      K, nullptr, pair_base, total, score, idx, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- L2 flat search
+int64_t smi_l2_flat_search_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
+  const KeepLastError keep;
+  return check_search_args(nq, d, K, nprobe, k) ? 0 : (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes();
+}
+
+int smi_l2_flat_search(const void* q_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
+                       const float* list_bias, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
+                       int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
+  return l2_flat_search_entry(q_f16, nq, d, probes, nprobe, list_rows, list_bias, list_ids, list_offsets, K, k, idx, score, ws,
+                              ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -173,6 +173,15 @@ hipError_t launch_xsim_merge(const float* ps, const int* pi, int nchunks, int64_
                              int64_t y_index_offset, int32_t* idx, float* score, hipStream_t stream);
 hipError_t launch_topk_merge(const float* part_scores, const int32_t* part_idx, int parts, int64_t n, int k,
                              float* out_scores, int32_t* out_idx, hipStream_t stream);
+// L2 / inner product on rows as they are (l2.hip): the fp16 copy and the half norms (nullable) of `rows` rows,
+// padded to a multiple of 256; out[s] = -half_norms[ids[s]] (0 where ids[s] < 0; ids null: -half_norms[s]); launch_xsim_topk
+// with score = sum + y_bias[j] (y_bias fp32 [ny_pad]) and its own workspace size
+hipError_t launch_l2_prepare(const void* src, int src_is_f32, f16* dst, float* half_norms, int64_t rows, int d, hipStream_t stream);
+hipError_t launch_l2_neg_gather(const int32_t* ids, int64_t n, const float* half_norms, float* out, hipStream_t stream);
+size_t l2_topk_ws_bytes(int64_t nx_pad, int64_t ny_pad, int k, int d);
+hipError_t launch_l2_topk(const f16* X, int64_t nx, int64_t nx_pad, const f16* Y, int64_t ny, int64_t ny_pad, int d, int k,
+                          int64_t y_index_offset, const float* y_bias, int32_t* idx, float* score, void* workspace,
+                          hipStream_t stream);
 // a page of the top-k: the k <= 16 best of every row strictly behind its ceiling (ceil_score, ceil_idx
 // [nx], both null: no ceiling); launch_topk_merge at the list length of a page
 size_t xsim_page_workspace_bytes(int64_t nx_pad, int64_t ny_pad, int d);

@@ -20,6 +20,7 @@
 #include "api_common.hpp"
 #include "common.hpp"
 #include "bucket.hpp"
+#include "l2_rows.hpp"
 
 using namespace smi;
 using namespace smi_host;
@@ -323,6 +324,77 @@ hipError_t km_finalize(const long long* sums, const int32_t* counts, int K, int 
   return hipGetLastError();
 }
 
+// ---- Euclidean k-means: the update above, unchanged (its integer sums are exact for any finite fp16 rows),
+// a finalise that divides by the count, and the assignment as smi_l2_topk's pass at k = 1 with the bias -h_c.
+//
+// One wave per row of the padded centroid matrix.  A cluster with members: centroid_f32 = fl32(fl64(sum) * 2^-24 / fl64(count))
+// (int64 -> fp64 by round to nearest even, the scale exact, one correctly rounded fp64 division, one rounding to fp32), the
+// fp16 row its round to nearest even, h_c = l2_half_norm of that fp16 row.  A cluster without members keeps all three and is
+// counted.  Rows from K on: fp16 row and half norm zeroed.
+__global__ __launch_bounds__(KM_TB) void km_l2_finalize_kernel(const long long* __restrict__ sums, const int32_t* __restrict__ counts,
+                                                               int K, int64_t rows_pad, int d, float* __restrict__ cf32,
+                                                               f16* __restrict__ cf16, float* __restrict__ ch,
+                                                               int32_t* __restrict__ empty_count) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * (KM_TB / 64) + (threadIdx.x >> 6);
+  if (r >= rows_pad) return;  // wave-uniform
+  half8* o = (half8*)(cf16 + (size_t)r * d);
+  if (r >= K) {
+    for (int c = lane; c < d / 8; c += 64) o[c] = half8{0, 0, 0, 0, 0, 0, 0, 0};
+    if (lane == 0) ch[r] = 0.f;
+    return;
+  }
+  const int cnt = counts[r];
+  if (cnt <= 0) {
+    if (lane == 0) atomicAdd(empty_count, 1);
+    return;
+  }
+  const long long* s = sums + (size_t)r * d;
+  float* c32 = cf32 + (size_t)r * d;
+  const double n = (double)cnt;
+  const float h = l2_half_norm(d, lane, [&](int c) {
+    half8 v;
+    f32x4 f[2];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      f[e >> 2][e & 3] = (float)((double)s[c * 8 + e] * 0x1p-24 / n);
+      v[e] = (f16)f[e >> 2][e & 3];
+    }
+    *(f32x4*)(c32 + c * 8) = f[0];
+    *(f32x4*)(c32 + c * 8 + 4) = f[1];
+    o[c] = v;
+    return v;
+  });
+  if (lane == 0) ch[r] = h;
+}
+
+hipError_t km_l2_finalize(const long long* sums, const int32_t* counts, int K, int d, float* cf32, f16* cf16, float* ch,
+                          int32_t* empty_count, hipStream_t stream) {
+  const int64_t rows_pad = smi_xsim_padded_rows(K);
+  hipError_t e;
+  if ((e = hipMemsetAsync(empty_count, 0, 4, stream)) != hipSuccess) return e;
+  hipLaunchKernelGGL(km_l2_finalize_kernel, grid_for(rows_pad, KM_TB / 64), dim3(KM_TB), 0, stream, sums, counts, K, rows_pad, d,
+                     cf32, cf16, ch, empty_count);
+  return hipGetLastError();
+}
+
+// fit: the update's workspace | smi_l2_topk's at k = 1 | new labels int32 [n] | the centroids' bias fp32 [padded K] | partial
+//      objectives fp64 [KM_PARTS] | partial moved counts int32 [KM_PARTS]
+struct KmL2FitWs : WsLayout {
+  void *km_ws, *xs_ws;
+  int32_t *new_labels, *part_moved;
+  float* bias;
+  double* part_obj;
+  KmL2FitWs(void* ws, int64_t n, int64_t K, int d) : WsLayout(ws) {
+    km_ws = take<char>(KmUpdateWs(nullptr, n, K).bytes(), 16);
+    xs_ws = take<char>(l2_topk_ws_bytes(smi_xsim_padded_rows(n), smi_xsim_padded_rows(K), 1, d), 16);
+    new_labels = take<int32_t>(n, 16);
+    bias = take<float>(smi_xsim_padded_rows(K), 16);
+    part_obj = take<double>(KM_PARTS);
+    part_moved = take<int32_t>(KM_PARTS);
+  }
+};
+
 }  // namespace
 
 }  // namespace smi
@@ -396,6 +468,73 @@ int smi_kmeans_fit(const void* xn, int64_t n, int32_t d, int64_t K, int32_t n_it
   for (int it = 0; it < n_iter; ++it) {
     HIP_TRY(km_update((const f16*)xn, labels, (int)n, d, (int)K, (long long*)sums, counts, w.km_ws, st));
     HIP_TRY(km_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, empty + it, w.km_ws, st));
+    if (const int rc = assign(slot++)) return rc;
+  }
+  return SMI_OK;
+}
+
+// ---- Euclidean k-means
+int smi_l2_kmeans_finalize(const int64_t* sums, const int32_t* counts, int64_t K, int32_t d, float* centroids_f32,
+                           void* centroids_f16, float* centroid_half_norms, int32_t* empty_count, void* stream) {
+  if (!sums || !counts || !centroids_f32 || !centroids_f16 || !centroid_half_norms || !empty_count)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(1, nullptr, d, K, "cluster")) return rc;
+  if (((uintptr_t)centroids_f32 | (uintptr_t)centroids_f16) % 16)
+    return fail(SMI_ERR_INVALID_ARG, "centroids_f32 and centroids_f16 must be 16-byte aligned");
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  HIP_TRY(km_l2_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, centroid_half_norms,
+                         empty_count, (hipStream_t)stream));
+  return SMI_OK;
+}
+
+int64_t smi_l2_kmeans_fit_ws_bytes(int64_t n, int64_t K, int32_t d) {
+  if (n < 1 || K < 1 || d <= 0 || d % 64 || n > 0x7fffff00LL || K > 0x7fffff00LL) return 0;
+  return (int64_t)KmL2FitWs(nullptr, n, K, d).bytes();
+}
+
+int smi_l2_kmeans_fit(const void* x_f16, int64_t n, int32_t d, int64_t K, int32_t n_iter, int32_t resume, float* centroids_f32,
+                      void* centroids_f16, float* centroid_half_norms, int32_t* labels, float* scores, int64_t* sums,
+                      int32_t* counts, double* objective, int32_t* moved, int32_t* empty, void* ws, int64_t ws_bytes,
+                      void* stream) {
+  if (!x_f16 || !centroids_f32 || !centroids_f16 || !centroid_half_norms || !labels || !scores || !sums || !counts || !objective ||
+      !moved || !empty)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, nullptr, d, K, "cluster")) return rc;
+  if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d", n_iter);
+  if (resume != 0 && resume != 1) return fail(SMI_ERR_INVALID_ARG, "resume=%d (0 or 1)", resume);
+  if (((uintptr_t)x_f16 | (uintptr_t)centroids_f32 | (uintptr_t)centroids_f16) % 16)
+    return fail(SMI_ERR_INVALID_ARG, "x_f16, centroids_f32 and centroids_f16 must be 16-byte aligned");
+  const KmL2FitWs w(ws, n, K, d);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_l2_kmeans_fit_ws_bytes(n, K, d)")) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const int per = (int)((n + KM_PARTS - 1) / KM_PARTS);
+  const int64_t n_pad = smi_xsim_padded_rows(n), k_pad = smi_xsim_padded_rows(K);
+
+  // assign every row to its nearest centroid: the biased top-1 with b = -h_c (ties to the lower index), then this round's
+  // record, by the kernels of the spherical fit
+  auto assign = [&](int slot) -> int {
+    HIP_TRY(launch_l2_neg_gather(nullptr, k_pad, centroid_half_norms, w.bias, st));
+    HIP_TRY(launch_l2_topk((const f16*)x_f16, n, n_pad, (const f16*)centroids_f16, K, k_pad, d, 1, 0, w.bias, w.new_labels, scores,
+                           w.xs_ws, st));
+    hipLaunchKernelGGL(km_round_part_kernel, dim3(KM_PARTS), dim3(KM_TB), 0, st, scores, w.new_labels, labels, (int)n, per,
+                       w.part_obj, w.part_moved);
+    hipLaunchKernelGGL(km_round_sum_kernel, dim3(1), dim3(KM_PARTS), 0, st, w.part_obj, w.part_moved, objective + slot,
+                       moved + slot);
+    HIP_TRY(hipGetLastError());
+    return SMI_OK;
+  };
+
+  int slot = 0;
+  if (!resume) {
+    HIP_TRY(launch_l2_prepare(centroids_f32, 1, (f16*)centroids_f16, centroid_half_norms, K, d, st));
+    HIP_TRY(hipMemsetAsync(labels, 0xff, (size_t)n * 4, st));  // -1: every row counts as moved
+    if (const int rc = assign(slot++)) return rc;
+  }
+  for (int it = 0; it < n_iter; ++it) {
+    HIP_TRY(km_update((const f16*)x_f16, labels, (int)n, d, (int)K, (long long*)sums, counts, w.km_ws, st));
+    HIP_TRY(km_l2_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, centroid_half_norms,
+                           empty + it, st));
     if (const int rc = assign(slot++)) return rc;
   }
   return SMI_OK;

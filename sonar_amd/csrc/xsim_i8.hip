@@ -36,17 +36,6 @@ namespace {
 constexpr int XI8_MAX_DIM = SMI_IVF_I8_MAX_DIM;
 static_assert((int64_t)127 * 127 * XI8_MAX_DIM < (1LL << 31), "the int32 sum of a row pair cannot overflow");
 
-// the 16 y-column scales of a lane (columns wc * 64 + ni * 16 + 4 kg + r of the tile) from the tile's scale slot in LDS, in
-// one asm statement for the reason given at xs_thresholds
-__device__ __forceinline__ void xi8_read_scales(unsigned lds_addr, f32x4 (&sy)[4]) {
-  asm volatile(
-      "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\t"
-      "ds_read_b128 %3, %4 offset:192\n\ts_waitcnt lgkmcnt(0)"
-      : "=&v"(sy[0]), "=&v"(sy[1]), "=&v"(sy[2]), "=&v"(sy[3])
-      : "v"(lds_addr)
-      : "memory");
-}
-
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 // The int8 operand policy of the walk (xsim_walk.hpp).  xs / ys: the scales of the x and y rows, row order.
@@ -93,7 +82,7 @@ struct XsI8 {
     ysg += G2_BN;
     ++it;
   }
-  __device__ __forceinline__ void fold_begin(int n0f, tile_t& ts) { xi8_read_scales(sc_addr + ((n0f / G2_BN - t_begin) & 7) * 1024, ts.sy); }
+  __device__ __forceinline__ void fold_begin(int n0f, tile_t& ts) { xs_read_cols16(sc_addr + ((n0f / G2_BN - t_begin) & 7) * 1024, ts.sy); }
   // the largest score of the row's 16: s_x >= 0 and a rounded product is monotone in t = fl32(sum * s_y)
   __device__ __forceinline__ float row_max(const acc_t (&acc)[4][8], int mi, const tile_t& ts) const {
     float tmax = -INFINITY;

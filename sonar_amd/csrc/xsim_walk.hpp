@@ -1,6 +1,7 @@
-// The tile walk of the brute-force top-k mining kernels, stated once: xsim_tile256_kernel (xsim.hip, fp16 rows) and
-// xsim_i8_tile256_kernel (xsim_i8.hip, int8 codes) are wrappers of xsim_walk over an operand policy, and the host side of both
-// passes (workspace layout, packing, launches, the K dispatch) is xsim_run below.
+// The tile walk of the brute-force top-k mining kernels, stated once: xsim_tile256_kernel (xsim.hip, fp16 rows),
+// xsim_i8_tile256_kernel (xsim_i8.hip, int8 codes) and l2_tile256_kernel (l2.hip, fp16 rows and one additive fp32 per y row) are
+// wrappers of xsim_walk over an operand policy, and the host side of the passes (workspace layout, packing, launches, the K
+// dispatch) is xsim_run below.
 //
 // The walk runs on the 256x256 ping-pong tile engine (gemm_tile256.hpp).  The K slices of ALL y tiles of a chunk form one
 // continuous DMA stream through the 4-slot LDS ring: the pipeline is filled once per workgroup, not once per y tile; at every
@@ -110,6 +111,18 @@ __device__ __forceinline__ void xs_thresholds(unsigned lds_addr, float (&t)[8]) 
       : "memory");
 #pragma unroll
   for (int mi = 0; mi < 8; ++mi) t[mi] = xs_unord(o[mi]);
+}
+
+// the 16 per-column fp32 of a lane (columns wc * 64 + ni * 16 + 4 kg + r of the tile) from a 256-entry tile slot in LDS (what a
+// policy streams with a tile: the y scales of the int8 pass, the y biases of the biased one), in one asm statement for the
+// reason given at xs_thresholds
+__device__ __forceinline__ void xs_read_cols16(unsigned lds_addr, f32x4 (&v)[4]) {
+  asm volatile(
+      "ds_read_b128 %0, %4\n\tds_read_b128 %1, %4 offset:64\n\tds_read_b128 %2, %4 offset:128\n\t"
+      "ds_read_b128 %3, %4 offset:192\n\ts_waitcnt lgkmcnt(0)"
+      : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3])
+      : "v"(lds_addr)
+      : "memory");
 }
 
 // The fold of a finished y tile (n0f = its first y row) into the row lists: a row is tested as a whole, on the largest of the

@@ -54,7 +54,11 @@ the probed lists strictly after a per-query exclusive ceiling, and `search_wide`
 last entry the next one's ceiling.  The pages concatenated are the top-k bit for bit.  `search`, `probe` and every other
 entry keep their limit of 8.
 
-Not here: a look-up-table scan for a handful of queries, codes of fewer than 8 bits, lists of more than 16
+`IVFFlatL2Index` is the flat index under the squared Euclidean distance, on the rows as they are: the
+quantiser is `clustering.KMeans`, every slot carries the bias -||row||^2 / 2 beside its id, and `search` returns (squared
+distances ascending, ids).  SONAR embeddings are not unit vectors; this is FAISS's `METRIC_L2`.
+
+Not here: L2 on the int8 / PQ / residual lists and in the wide, keyed and range searches, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, lists of more than 16
 results in one pass, k above 64, nprobe or k above 8 on the int8 / PQ / residual indexes, in `range_search` and in `mining`,
 the key predicate on the wide search, de-duplication or range search over quantised lists, incremental add and removal, 64-bit ids, splitting of long
 lists, multi-GPU sharding; of filtering: skipping whole tiles or lists by key, per-query bitmaps or id lists, keys wider than
@@ -68,10 +72,10 @@ from typing import Dict, NamedTuple, Optional, Tuple, Union
 import torch
 
 from . import _lib
-from .clustering import SphericalKMeans, init_rows
+from .clustering import KMeans, SphericalKMeans, init_rows
 from .mining import pair_scores
-from .xsim import (PAGE, WIDE_MAX, check_below, check_count, last_entry, normalize_rows, page_sizes, topk_normalized,
-                   topk_wide_normalized)
+from .xsim import (PAGE, WIDE_MAX, check_below, check_count, last_entry, normalize_rows, page_sizes, prepare_rows,
+                   topk_bias_prepared, topk_normalized, topk_wide_normalized)
 
 LIST_ALIGN = 16    # SMI_IVF_LIST_ALIGN: every list starts at a multiple of this many slots and is padded to it
 UNIT_QUERIES = 64  # SMI_IVF_UNIT_QUERIES: queries of one list that one work unit of the scan takes (128 when nq nprobe >= 256 K)
@@ -274,6 +278,36 @@ def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids
     keyed = _check_keyed(slot_keys, query_keys, accept, ids.shape[0], probes.shape[0])
     return _search("smi_ivf_search", "smi_ivf_search_workspace_bytes", qn, probes, k, (), (rows.data_ptr(),), ids, offsets,
                    keyed=keyed)
+
+
+def slot_bias(ids: torch.Tensor, half_norms: torch.Tensor) -> torch.Tensor:
+    """smi_l2_slot_bias: fp32 [slots], -half_norms[id] for the row every slot holds and 0 where it holds none.
+    ids: int32 [slots] from `build_lists`; half_norms: fp32 [>= n] from `xsim.prepare_rows` (row number = id)."""
+    _check_table(ids, "ids", ids.shape[0] if isinstance(ids, torch.Tensor) and ids.dim() == 1 else -1, None)
+    _check_device_tensor(half_norms, "half_norms")
+    if half_norms.dtype != torch.float32 or half_norms.dim() != 1 or half_norms.device != ids.device:
+        raise ValueError(f"half_norms must be fp32 [n] on the device of ids, got {half_norms.dtype} {list(half_norms.shape)}")
+    lib = _lib.load()
+    out = torch.empty((ids.shape[0],), dtype=torch.float32, device=ids.device)
+    ids, half_norms = ids.contiguous(), half_norms.contiguous()
+    with torch.cuda.device(ids.device):
+        _lib.check(lib.smi_l2_slot_bias(ids.data_ptr(), ids.shape[0], half_norms.data_ptr(), out.data_ptr(),
+                                        _lib.current_stream_ptr()))
+    return out
+
+
+def search_lists_l2(q16: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, bias: torch.Tensor, ids: torch.Tensor,
+                    offsets: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_l2_flat_search: `search_lists` with score = sum + bias[slot] (bias: `slot_bias` of the storage, fp32 [slots]) over
+    prepared rows (`xsim.prepare_rows`): (scores fp32 [nq, k] best first, ids int32 [nq, k]).  With the bias of `slot_bias`,
+    ||q - row||^2 = 2 (h_q - score).  ids may be a `RowFilter`'s."""
+    _check_search_args(q16, probes, k)
+    _check_lists_dim(q16, rows)
+    _check_device_tensor(bias, "bias")
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (ids.shape[0],) or not bias.is_contiguous():
+        raise ValueError(f"bias must be contiguous fp32 [{ids.shape[0]}], got {bias.dtype} {list(bias.shape)}")
+    return _search("smi_l2_flat_search", "smi_l2_flat_search_ws_bytes", q16, probes, k, (), (rows.data_ptr(), bias.data_ptr()),
+                   ids, offsets)
 
 
 def search_lists_page(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
@@ -730,6 +764,8 @@ class _IVFIndex:
 
     def _check_extra(self, state, d: int, fresh: bool):
         """load_state_dict: (the columns `rows` must have, the attributes to take over from the `_EXTRA` entries)."""
+        if "metric_l2" in state:
+            raise ValueError("the state is that of an IVFFlatL2Index: its rows are not normalised and its scores carry a bias")
         return d, {}
 
     def __init__(self, quantizer: Union[SphericalKMeans, torch.Tensor]):
@@ -1083,6 +1119,124 @@ class IVFFlatIndex(_IVFIndex):
                 raise ValueError("give n, the number of rows the index was filled from, or a priority tensor of that length")
             n = priority.shape[0] if priority.dim() == 1 else -1
         return dedup.self_join(self._rows, self._ids, self._offsets, n, priority)
+
+
+class IVFFlatL2Index(_IVFIndex):
+    """`IVFFlatIndex` under the squared Euclidean distance, on the rows as they are: train / add / probe /
+    search, `state_dict` / `load_state_dict`.  The lists hold fp16 copies of the rows (rounded, not normalised) and one fp32
+    bias per slot, -||row||^2 / 2; the probe is the biased top-k against the centroids and the scan adds the slot's bias to
+    the flat scan's sum, so the best score is the nearest row.  `state_dict` adds `bias` and the marker `metric_l2`, so that
+    neither this class nor `IVFFlatIndex` loads the other's state.
+
+    quantizer: a fitted `clustering.KMeans`, or an [K, d] tensor of centroids (taken as they are, rounded to fp16)."""
+
+    _STORAGE = ("_rows", "_bias", "_ids", "_offsets", "_sizes")
+    _SLOT_VECTORS = (("_bias", torch.float32, "fp32"),)
+    _HOLDS = "an IVFFlatL2Index holds rows that are not normalised"
+
+    def __init__(self, quantizer: Union[KMeans, torch.Tensor]):
+        if isinstance(quantizer, KMeans):
+            c16 = quantizer.centroids_f16  # raises before fit
+            self._c16, self._ch = quantizer._c16.clone(), quantizer._ch.clone()
+            self._k, self._d = quantizer.n_clusters, c16.shape[1]
+        elif isinstance(quantizer, SphericalKMeans):
+            raise TypeError("an IVFFlatL2Index needs Euclidean centroids: a fitted clustering.KMeans, or a tensor")
+        else:
+            _check_matrix(quantizer, "quantizer")
+            self._k, self._d = quantizer.shape
+            self._c16, self._ch = prepare_rows(quantizer)
+        self._added = False
+
+    @classmethod
+    def train(cls, x: torch.Tensor, n_lists: int, n_iter: int = 10, seed: int = 0):
+        """Fit the coarse quantiser: Euclidean k-means with `n_lists` clusters on x (fp16 / fp32 [n, d] on the device)."""
+        return cls(KMeans(n_lists, n_iter=n_iter, seed=seed).fit(x))
+
+    @property
+    def centroids_f16(self) -> torch.Tensor:
+        return self._c16[: self._k]
+
+    @property
+    def centroids_normalized(self) -> torch.Tensor:
+        raise TypeError("an IVFFlatL2Index keeps its centroids as they are: centroids_f16")
+
+    def _nearest_lists(self, q16, nq: int, nprobe: int) -> torch.Tensor:
+        return topk_bias_prepared(q16, nq, self._c16, self._k, self._ch.neg(), nprobe)[1]
+
+    def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None):
+        """`IVFFlatIndex.add` on the rows as they are: labels None = the nearest centroid in the Euclidean sense."""
+        if self._added:
+            raise RuntimeError("add was already called: this index is built once (no incremental add)")
+        _check_matrix(x, "x")
+        if x.shape[1] != self._d:
+            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+        n = x.shape[0]
+        if labels is not None:
+            _check_table(labels, "labels", n, None)
+        x16, hx = prepare_rows(x)
+        if labels is None:
+            labels = self._nearest_lists(x16, n, 1)[:, 0]
+        self._rows, self._ids, self._offsets, self._sizes = build_lists(x16, labels, self._k)
+        self._bias = slot_bias(self._ids, hx)
+        self._added = True
+        return self
+
+    def probe(self, q: torch.Tensor, nprobe: int = 1) -> torch.Tensor:
+        """int32 [nq, nprobe]: the nprobe nearest lists of every query (squared Euclidean distance to the centroid), nearest
+        first."""
+        _check_small(nprobe, "nprobe")
+        _check_matrix(q, "q")
+        if q.shape[1] != self._d:
+            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
+        if nprobe > self._k:
+            raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
+        return self._nearest_lists(prepare_rows(q)[0], q.shape[0], nprobe)
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None, *,
+               rows: Optional[RowFilter] = None, query_keys=None, refine=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The k nearest rows of the probed lists for every row of q (fp16 / fp32 [nq, d] on the device): (squared distances
+        fp32 [nq, k] ascending, ids int32 [nq, k]), ties to the lower row number, (+inf, -1) where the probed lists hold fewer
+        than k rows.  sq_dist = clamp_min(2 (h_q - score), 0), as `xsim.topk_l2`; over all lists it IS `xsim.topk_l2` over the
+        corpus.  probes: as for `IVFFlatIndex.search`.  rows: a `RowFilter` of this index built with a mask."""
+        if query_keys is not None:
+            raise TypeError("query_keys: the keyed scan has no L2 twin (DESIGN.md 7); filter with rows=index.row_filter(mask=...)")
+        if refine is not None:
+            raise TypeError("refine re-scores quantised candidates with fp16 cosines; an IVFFlatL2Index already scores the fp16 rows")
+        nq = self._check_search(q, k, nprobe, probes)
+        ids = self._filter(rows, None, "==", nq)[0]
+        q16, hq = prepare_rows(q)
+        if probes is None:
+            probes = self._nearest_lists(q16, nq, nprobe)
+        score, idx = search_lists_l2(q16, probes, self._rows, self._bias, self._ids if ids is None else ids, self._offsets, k)
+        return (2.0 * (hq[:nq, None] - score)).clamp_min(0.0), idx
+
+    def range_search(self, *args, **kwargs):
+        raise TypeError("range_search thresholds cosines; it has no L2 variant (DESIGN.md 7)")
+
+    def probe_wide(self, *args, **kwargs):
+        raise TypeError("probe_wide is the paged cosine top-k; an IVFFlatL2Index probes at most 8 lists (DESIGN.md 7)")
+
+    def search_wide(self, *args, **kwargs):
+        raise TypeError("search_wide is the paged cosine search; an IVFFlatL2Index returns at most 8 rows (DESIGN.md 7)")
+
+    def self_join(self, *args, **kwargs):
+        raise TypeError("self_join and semdedup score cosines; they have no L2 variant (DESIGN.md 7)")
+
+    def _check_extra(self, state, d: int, fresh: bool):
+        if "metric_l2" not in state:
+            raise ValueError("state lacks ['metric_l2']: the state is that of an IVFFlatIndex, whose rows are normalised")
+        return d, {}
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """`IVFFlatIndex.state_dict` with the centroids as they are, `bias` (fp32 [slots]) and the marker `metric_l2`."""
+        state = super().state_dict()
+        state["metric_l2"] = torch.ones(1, dtype=torch.uint8, device=self._rows.device)
+        return state
+
+    def load_state_dict(self, state: Dict[str, torch.Tensor], _fresh: bool = False):
+        super().load_state_dict(state, _fresh)
+        self._ch = prepare_rows(self._c16[: self._k])[1]  # the half norms of the fp16 centroids: the same bits
+        return self
 
 
 class IVFInt8Index(_IVFIndex):

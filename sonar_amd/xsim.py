@@ -12,6 +12,9 @@ the bytes, scores specified to their bits, optionally re-scored as fp16 cosines.
 (`topk_page_normalized`, `smi_xsim_topk_page`): a page is the 16
 best candidates strictly after a per-row exclusive ceiling in the total order, and
 the pages concatenated are the top-k bit for bit; `topk` keeps its limit of 8.
+`topk_l2` / `topk_ip` search rows AS THEY ARE (SONAR embeddings are not unit vectors): squared Euclidean
+distance through one additive term per y row, -||y||^2 / 2, inside the same walk (`smi_l2_topk`), and maximum inner product
+through the existing pass, which never needed unit rows.
 
 Multi-GPU (sharded_topk): X rows are sharded over ranks, every rank's Y shard
 is all-gathered once over RCCL/xGMI (2 GB for 1M x 1024 fp16 -- small next to
@@ -77,6 +80,112 @@ def topk(x: torch.Tensor, y: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, to
     """For every row of x: (cosine scores [nx,k] fp32, indices into y [nx,k] int32), best first."""
     xn, yn = normalize_rows(x), normalize_rows(y)
     return topk_normalized(xn, x.shape[0], yn, y.shape[0], k)
+
+
+# ---- squared-Euclidean and inner-product search on rows as they are (DESIGN.md 3.28) ----
+
+def prepare_rows(t: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(fp16 copy zero-padded to a multiple of 256 rows, half norms fp32 [padded rows]): `normalize_rows` without the
+    division, and h[r] = fl32(sum of the squares of the rounded row / 2), summed in fp64 in a fixed order (smi_l2_prepare);
+    pad rows and their half norms are 0.  A value that is not finite in fp16 gives unspecified results."""
+    t = _prep(t)
+    rows, d = t.shape
+    if rows == 0:
+        raise ValueError("empty embedding matrix")
+    if d % 8:
+        raise ValueError(f"dim = {d} must be a multiple of 8")
+    lib = _lib.load()
+    pad = int(lib.smi_xsim_padded_rows(rows))
+    out = torch.empty((pad, d), dtype=torch.float16, device=t.device)
+    half_norms = torch.empty((pad,), dtype=torch.float32, device=t.device)
+    with torch.cuda.device(t.device):
+        _lib.check(lib.smi_l2_prepare(t.data_ptr(), _lib.SMI_F32 if t.dtype == torch.float32 else _lib.SMI_F16, rows, d,
+                                      out.data_ptr(), half_norms.data_ptr(), _lib.current_stream_ptr()))
+    return out, half_norms
+
+
+def _check_prepared(rows16, n, name: str) -> int:
+    """One side of a prepared call: the contiguous fp16 [padded n, dim] matrix on the device -> its padded row count."""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"n{name} = {n!r}: at least one row")
+    if not isinstance(rows16, torch.Tensor):
+        raise TypeError(f"{name}16 must be a torch.Tensor")
+    if not rows16.is_cuda:
+        raise RuntimeError("xsim runs on a HIP device only (no CPU path); move the rows to cuda")
+    pad = (n + 255) // 256 * 256
+    if rows16.dim() != 2 or rows16.dtype != torch.float16 or not rows16.is_contiguous() or rows16.shape[0] != pad:
+        raise ValueError(f"{name}16 must be the contiguous fp16 [{pad}, dim] matrix prepare_rows returns for {n} rows, got "
+                         f"{rows16.dtype} {list(rows16.shape)}")
+    return pad
+
+
+def _check_per_row(v, pad: int, like: torch.Tensor, name: str) -> None:
+    """A per-row fp32 vector of a prepared call (a bias, half norms): contiguous fp32 [pad] on the device of the rows."""
+    if not isinstance(v, torch.Tensor):
+        raise TypeError(f"{name} must be a torch.Tensor")
+    if not v.is_cuda:
+        raise RuntimeError(f"xsim runs on a HIP device only (no CPU path); move {name} to cuda")
+    if v.dtype != torch.float32 or tuple(v.shape) != (pad,) or not v.is_contiguous():
+        raise ValueError(f"{name} must be contiguous fp32 [{pad}] (one per padded row), got {v.dtype} {list(v.shape)}")
+    if v.device != like.device:
+        raise ValueError(f"{name} ({v.device}) must be on the device of the rows ({like.device})")
+
+
+def topk_bias_prepared(x16: torch.Tensor, nx: int, y16: torch.Tensor, ny: int, bias: torch.Tensor, k: int = 1,
+                       y_index_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`topk_normalized` with one additive fp32 term per y row (smi_l2_topk): score(i, j) = fl32(x_i . y_j + bias[j]) on
+    fp16 rows in the padded layout, bias fp32 [padded ny] and finite; same order and fill, a zero score is +0."""
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
+        raise ValueError("k must be in [1, 8]")
+    _check_prepared(x16, nx, "x")
+    pad_y = _check_prepared(y16, ny, "y")
+    d = x16.shape[1]
+    if y16.shape[1] != d:
+        raise ValueError("x and y must have the same dimension")
+    if y16.device != x16.device:
+        raise ValueError("x and y must be on the same device")
+    if d % 64:
+        raise ValueError(f"dim = {d} must be a multiple of 64")
+    _check_per_row(bias, pad_y, x16, "bias")
+    lib = _lib.load()
+    ws_bytes = int(lib.smi_l2_topk_ws_bytes(nx, ny, k, d))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x16.device)
+    idx = torch.empty((nx, k), dtype=torch.int32, device=x16.device)
+    score = torch.empty((nx, k), dtype=torch.float32, device=x16.device)
+    with torch.cuda.device(x16.device):
+        _lib.check(lib.smi_l2_topk(x16.data_ptr(), nx, y16.data_ptr(), ny, d, k, y_index_offset, bias.data_ptr(),
+                                   idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+    return score, idx
+
+
+def topk_l2_prepared(x16: torch.Tensor, nx: int, x_half_norms: torch.Tensor, y16: torch.Tensor, ny: int,
+                     y_half_norms: torch.Tensor, k: int = 1,
+                     y_index_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Squared-Euclidean nearest neighbours on prepared sides (`prepare_rows`) -> (sq_dist fp32 [nx, k] ascending, idx int32
+    [nx, k], the raw scores).  score(i, j) = fl32(x_i . y_j - h_y[j]) from `topk_bias_prepared`, so best first is nearest
+    first (ties to the lower index), and sq_dist = clamp_min(2 (h_x[i] - score), 0) in fp32 torch ops; fill (+inf, -1)."""
+    pad_x = _check_prepared(x16, nx, "x")
+    _check_per_row(x_half_norms, pad_x, x16, "x_half_norms")
+    _check_per_row(y_half_norms, _check_prepared(y16, ny, "y"), x16, "y_half_norms")
+    score, idx = topk_bias_prepared(x16, nx, y16, ny, y_half_norms.neg(), k, y_index_offset)
+    sq_dist = (2.0 * (x_half_norms[:nx, None] - score)).clamp_min(0.0)
+    return sq_dist, idx, score
+
+
+def topk_l2(x: torch.Tensor, y: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """For every row of x: (squared Euclidean distances [nx, k] fp32 ascending, indices into y [nx, k] int32), between the
+    fp16 roundings of the rows as they are (`topk_l2_prepared`); fill (+inf, -1)."""
+    (x16, hx), (y16, hy) = prepare_rows(x), prepare_rows(y)
+    sq_dist, idx, _ = topk_l2_prepared(x16, x.shape[0], hx, y16, y.shape[0], hy, k)
+    return sq_dist, idx
+
+
+def topk_ip(x: torch.Tensor, y: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Maximum inner product on rows as they are: (x_i . y_j [nx, k] fp32 best first, indices into y).  Prepared rows
+    (`prepare_rows`) through the existing `topk_normalized`: that pass never needed unit rows -- its score is the fp32 sum
+    of the fp16 products, whatever the rows' lengths -- so the zero-bias case takes no new kernel."""
+    (x16, _), (y16, _) = prepare_rows(x), prepare_rows(y)
+    return topk_normalized(x16, x.shape[0], y16, y.shape[0], k)
 
 
 PAGE = 16      # results of one page: the list length of the paged pass (DESIGN.md 3.27)
