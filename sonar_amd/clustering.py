@@ -21,7 +21,8 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from .xsim import normalize_rows, prepare_rows, topk_l2_prepared, topk_normalized
+from .xsim import (WIDE_MAX, check_count, normalize_rows, prepare_rows, topk_l2_prepared, topk_normalized,
+                   topk_wide_normalized)
 
 UNIT_ROWS = 64  # SMI_KMEANS_UNIT_ROWS: members one work unit of the update sums in registers
 
@@ -46,6 +47,15 @@ def _check_matrix(t, name: str) -> None:
         raise ValueError(f"{name} is empty")
     if t.shape[1] % 64:
         raise ValueError(f"{name}: dim = {t.shape[1]} must be a multiple of 64")
+
+
+def _check_padded16(t, name: str, n, source: str) -> None:
+    """The contiguous fp16 matrix `source` returns, whose first n rows are the data."""
+    _check_matrix(t, name)
+    if t.dtype != torch.float16 or not t.is_contiguous():
+        raise ValueError(f"{name} must be the contiguous fp16 matrix {source} returns")
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1 or (n + 255) // 256 * 256 != t.shape[0]:
+        raise ValueError(f"n = {n!r} does not match the {t.shape[0]} padded rows of {name}")
 
 
 def _fit_workspace_bytes(lib, n: int, k: int, d: int) -> int:
@@ -79,11 +89,7 @@ class SphericalKMeans:
 
     def fit_normalized(self, xn: torch.Tensor, n: int, init: Optional[torch.Tensor] = None) -> "SphericalKMeans":
         """As `fit`, on a matrix from `xsim.normalize_rows` (fp16, padded) whose first n rows are the data."""
-        _check_matrix(xn, "xn")
-        if xn.dtype != torch.float16 or not xn.is_contiguous():
-            raise ValueError("xn must be the contiguous fp16 matrix normalize_rows returns")
-        if isinstance(n, bool) or not isinstance(n, int) or n < 1 or (n + 255) // 256 * 256 != xn.shape[0]:
-            raise ValueError(f"n = {n!r} does not match the {xn.shape[0]} padded rows of xn")
+        _check_padded16(xn, "xn", n, "normalize_rows")
         self._check_init(init, n, xn.shape[1])
         start = init if init is not None else xn[init_rows(n, self.n_clusters, self.seed).to(xn.device)]
         return self._fit(xn, n, start)
@@ -107,7 +113,7 @@ class SphericalKMeans:
         self.scores = torch.empty((n,), dtype=torch.float32, device=dev)
         self._sums = torch.zeros((k, d), dtype=torch.int64, device=dev)
         self.counts = torch.zeros((k,), dtype=torch.int32, device=dev)
-        self._ws = torch.empty(_fit_workspace_bytes(lib, n, k, d), dtype=torch.uint8, device=dev)
+        self._ws = torch.empty(self._fit_ws_bytes(lib, n, k, d), dtype=torch.uint8, device=dev)
         cap = self.n_iter + 1
         self._objective = torch.zeros((cap,), dtype=torch.float64, device=dev)
         self._moved = torch.zeros((cap,), dtype=torch.int32, device=dev)
@@ -116,6 +122,13 @@ class SphericalKMeans:
         self._run(self.n_iter, resume=False)
         self._fitted = True
         return self
+
+    _FIT = "smi_kmeans_fit"
+    _fit_ws_bytes = staticmethod(_fit_workspace_bytes)
+
+    def _fit_extra(self) -> tuple:
+        """What the entry `_FIT` takes between the fp16 centroids and the labels."""
+        return ()
 
     def _run(self, n_iter: int, resume: bool) -> None:
         lib = _lib.load()
@@ -128,12 +141,12 @@ class SphericalKMeans:
             self._moved = torch.cat([self._moved, self._moved.new_zeros(grow)])
             self._empty = torch.cat([self._empty, self._empty.new_zeros(grow)])
         with torch.cuda.device(self._xn.device):
-            _lib.check(lib.smi_kmeans_fit(
+            _lib.check(getattr(lib, self._FIT)(
                 self._xn.data_ptr(), self._n, self._d, self.n_clusters, n_iter, int(resume), self._c32.data_ptr(),
-                self._c16.data_ptr(), self.labels.data_ptr(), self.scores.data_ptr(), self._sums.data_ptr(),
-                self.counts.data_ptr(), self._objective.data_ptr() + 8 * a0, self._moved.data_ptr() + 4 * a0,
-                self._empty.data_ptr() + 4 * self._rounds, self._ws.data_ptr(), self._ws.numel(),
-                _lib.current_stream_ptr()))
+                self._c16.data_ptr(), *self._fit_extra(), self.labels.data_ptr(), self.scores.data_ptr(),
+                self._sums.data_ptr(), self.counts.data_ptr(), self._objective.data_ptr() + 8 * a0,
+                self._moved.data_ptr() + 4 * a0, self._empty.data_ptr() + 4 * self._rounds, self._ws.data_ptr(),
+                self._ws.numel(), _lib.current_stream_ptr()))
         self._rounds += n_iter
 
     def step(self) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -173,28 +186,24 @@ class SphericalKMeans:
         return {"objective": self._objective[: r + 1].tolist(), "moved": self._moved[: r + 1].tolist(),
                 "empty": self._empty[:r].tolist()}
 
-    def predict(self, x: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The k (<= 8) nearest centroids of every row of x, best first: (labels int32, cosines fp32), [n] for k = 1 and
-        [n, k] otherwise.  k > 1 is the probe of an IVF index."""
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
-            raise ValueError(f"k = {k!r}: an integer in [1, 8]")
-        self._need_fit("predict")
+    def _check_predict(self, what: str, x, k, most: int = 8) -> None:
+        check_count(k, "k", most)
+        self._need_fit(what)
         _check_matrix(x, "x")
         if x.shape[1] != self._d:
             raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+
+    def predict(self, x: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The k (<= 8) nearest centroids of every row of x, best first: (labels int32, cosines fp32), [n] for k = 1 and
+        [n, k] otherwise.  k > 1 is the probe of an IVF index."""
+        self._check_predict("predict", x, k)
         score, idx = topk_normalized(normalize_rows(x), x.shape[0], self._c16, self.n_clusters, k)
         return (idx[:, 0], score[:, 0]) if k == 1 else (idx, score)
 
     def predict_wide(self, x: torch.Tensor, k: int = 16) -> Tuple[torch.Tensor, torch.Tensor]:
         """`predict` for k up to 64, always [n, k]: the paged top-k (`xsim.topk_wide_normalized`), one pass
         over the centroids per 16 results.  (labels -1, cosines -inf) where k exceeds the number of centroids."""
-        from .xsim import WIDE_MAX, check_count, topk_wide_normalized
-
-        check_count(k, "k", WIDE_MAX)
-        self._need_fit("predict_wide")
-        _check_matrix(x, "x")
-        if x.shape[1] != self._d:
-            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+        self._check_predict("predict_wide", x, k, WIDE_MAX)
         score, idx = topk_wide_normalized(normalize_rows(x), x.shape[0], self._c16, self.n_clusters, k)
         return idx, score
 
@@ -216,11 +225,7 @@ class KMeans(SphericalKMeans):
 
     def fit_prepared(self, x16: torch.Tensor, half_norms: torch.Tensor, n: int, init: Optional[torch.Tensor] = None) -> "KMeans":
         """As `fit`, on what `xsim.prepare_rows` returned (fp16 rows padded to a multiple of 256, their half norms) for n rows."""
-        _check_matrix(x16, "x16")
-        if x16.dtype != torch.float16 or not x16.is_contiguous():
-            raise ValueError("x16 must be the contiguous fp16 matrix prepare_rows returns")
-        if isinstance(n, bool) or not isinstance(n, int) or n < 1 or (n + 255) // 256 * 256 != x16.shape[0]:
-            raise ValueError(f"n = {n!r} does not match the {x16.shape[0]} padded rows of x16")
+        _check_padded16(x16, "x16", n, "prepare_rows")
         if (not isinstance(half_norms, torch.Tensor) or half_norms.dtype != torch.float32 or half_norms.device != x16.device
                 or tuple(half_norms.shape) != (x16.shape[0],)):
             raise ValueError(f"half_norms must be the fp32 [{x16.shape[0]}] vector prepare_rows returns, on the device of x16")
@@ -236,28 +241,16 @@ class KMeans(SphericalKMeans):
         dev, d, k = x16.device, x16.shape[1], self.n_clusters
         self._hx = hx
         self._ch = torch.empty((int(lib.smi_xsim_padded_rows(k)),), dtype=torch.float32, device=dev)
-        self._ws_bytes = int(lib.smi_l2_kmeans_fit_ws_bytes(n, k, d))
-        return self._fit(x16, n, start)  # the buffers and records of the spherical fit; _run below is the call
+        return self._fit(x16, n, start)  # the buffers, the records and the call of the spherical fit, on the entry below
 
-    def _run(self, n_iter: int, resume: bool) -> None:
-        lib = _lib.load()
-        if self._ws.numel() < self._ws_bytes:
-            self._ws = torch.empty(self._ws_bytes, dtype=torch.uint8, device=self._xn.device)
-        a0 = self._rounds + 1 if resume else 0
-        need = a0 + n_iter + (0 if resume else 1)
-        if need > self._objective.shape[0]:
-            grow = max(need, 2 * self._objective.shape[0]) - self._objective.shape[0]
-            self._objective = torch.cat([self._objective, self._objective.new_zeros(grow)])
-            self._moved = torch.cat([self._moved, self._moved.new_zeros(grow)])
-            self._empty = torch.cat([self._empty, self._empty.new_zeros(grow)])
-        with torch.cuda.device(self._xn.device):
-            _lib.check(lib.smi_l2_kmeans_fit(
-                self._xn.data_ptr(), self._n, self._d, self.n_clusters, n_iter, int(resume), self._c32.data_ptr(),
-                self._c16.data_ptr(), self._ch.data_ptr(), self.labels.data_ptr(), self.scores.data_ptr(),
-                self._sums.data_ptr(), self.counts.data_ptr(), self._objective.data_ptr() + 8 * a0,
-                self._moved.data_ptr() + 4 * a0, self._empty.data_ptr() + 4 * self._rounds, self._ws.data_ptr(),
-                self._ws.numel(), _lib.current_stream_ptr()))
-        self._rounds += n_iter
+    _FIT = "smi_l2_kmeans_fit"
+
+    @staticmethod
+    def _fit_ws_bytes(lib, n: int, k: int, d: int) -> int:
+        return int(lib.smi_l2_kmeans_fit_ws_bytes(n, k, d))
+
+    def _fit_extra(self) -> tuple:
+        return (self._ch.data_ptr(),)
 
     @property
     def centroids_f16(self) -> torch.Tensor:
@@ -285,12 +278,7 @@ class KMeans(SphericalKMeans):
     def predict(self, x: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
         """The k (<= 8) nearest centroids of every row of x, nearest first: (labels int32, squared distances fp32), [n] for
         k = 1 and [n, k] otherwise."""
-        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= 8:
-            raise ValueError(f"k = {k!r}: an integer in [1, 8]")
-        self._need_fit("predict")
-        _check_matrix(x, "x")
-        if x.shape[1] != self._d:
-            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+        self._check_predict("predict", x, k)
         x16, hx = prepare_rows(x)
         dist, idx, _ = topk_l2_prepared(x16, x.shape[0], hx, self._c16, self.n_clusters, self._ch, k)
         return (idx[:, 0], dist[:, 0]) if k == 1 else (idx, dist)

@@ -625,9 +625,7 @@ int64_t smi_xsim_workspace_bytes(int64_t nx, int64_t ny, int32_t k, int32_t d) {
 int smi_xsim_topk(const void* xn, int64_t nx, const void* yn, int64_t ny, int32_t d, int32_t k,
                   int64_t y_off, int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
   if (!xn || !yn || !idx || !score || !ws) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (k < 1 || k > 8) return fail(SMI_ERR_UNSUPPORTED, "k=%d outside [1,8]", k);
-  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
-  if (nx <= 0 || ny <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (const int rc = check_topk_shape(nx, ny, k, 8, d, false)) return rc;
   if (ws_bytes < smi_xsim_workspace_bytes(nx, ny, k, d))
     return fail(SMI_ERR_INVALID_ARG, "workspace of %lld bytes, smi_xsim_workspace_bytes(nx, ny, k, d) = %lld",
                 (long long)ws_bytes, (long long)smi_xsim_workspace_bytes(nx, ny, k, d));
@@ -638,7 +636,8 @@ int smi_xsim_topk(const void* xn, int64_t nx, const void* yn, int64_t ny, int32_
 }
 
 int64_t smi_xsim_topk_page_ws_bytes(int64_t nx, int64_t ny, int32_t k, int32_t d) {
-  if (nx <= 0 || ny <= 0 || k < 1 || k > 16 || d <= 0 || d % 64 || nx > 0x7fffff00LL || ny > 0x7fffff00LL) return 0;
+  const KeepLastError keep;
+  if (check_topk_shape(nx, ny, k, 16, d)) return 0;
   return (int64_t)xsim_page_workspace_bytes(smi_xsim_padded_rows(nx), smi_xsim_padded_rows(ny), d);
 }
 
@@ -647,11 +646,7 @@ int smi_xsim_topk_page(const void* xn, int64_t nx, const void* yn, int64_t ny, i
                        int64_t ws_bytes, void* stream) {
   if (!xn || !yn || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (!ceil_score != !ceil_idx) return fail(SMI_ERR_INVALID_ARG, "ceil_score and ceil_idx go together: both or neither");
-  if (k < 1 || k > 16) return fail(SMI_ERR_UNSUPPORTED, "k=%d outside [1,16]", k);
-  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
-  if (nx <= 0 || ny <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  if (nx > 0x7fffff00LL || ny > 0x7fffff00LL)
-    return fail(SMI_ERR_UNSUPPORTED, "nx=%lld, ny=%lld: row numbers must fit int32", (long long)nx, (long long)ny);
+  if (const int rc = check_topk_shape(nx, ny, k, 16, d)) return rc;
   if (const int rc = check_ws(ws, ws_bytes, (size_t)smi_xsim_topk_page_ws_bytes(nx, ny, k, d),
                               "smi_xsim_topk_page_ws_bytes(nx, ny, k, d)"))
     return rc;

@@ -103,6 +103,13 @@ class WsLayout {
   size_t bytes() const { return off_; }
 };
 
+// A *_workspace_bytes function runs the shape checks of its entry -- the same functions, so it returns 0 exactly where the
+// entry refuses on shape -- under this guard: a sizing call leaves smi_last_error() as it was.
+struct KeepLastError {
+  const std::string text = last_error();
+  ~KeepLastError() { last_error() = text; }
+};
+
 // The workspace checks of every entry point that takes one; `sizing` is the call that returns `need`.
 inline int check_ws(const void* ws, int64_t ws_bytes, size_t need, const char* sizing) {
   if (!ws) return fail(SMI_ERR_INVALID_ARG, "null workspace");
@@ -123,6 +130,17 @@ inline int check_shape(int64_t n, const char* n_name, int32_t d, int64_t K, cons
   if (n > kMax || K > kMax)
     return fail(SMI_ERR_UNSUPPORTED, "%s=%lld, K=%lld: row and %s numbers must fit int32", n_name ? n_name : "n", (long long)n,
                 (long long)K, bucket);
+  return SMI_OK;
+}
+
+// The shape refusals of the brute-force top-k entries over nx rows against ny: smi_xsim_topk (fit32 false: its pass refuses
+// row numbers beyond int32 itself), smi_xsim_topk_page and smi_l2_topk
+inline int check_topk_shape(int64_t nx, int64_t ny, int32_t k, int most_k, int32_t d, bool fit32 = true) {
+  if (k < 1 || k > most_k) return fail(SMI_ERR_UNSUPPORTED, "k=%d outside [1,%d]", k, most_k);
+  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
+  if (nx <= 0 || ny <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
+  if (fit32 && (nx > 0x7fffff00LL || ny > 0x7fffff00LL))
+    return fail(SMI_ERR_UNSUPPORTED, "nx=%lld, ny=%lld: row numbers must fit int32", (long long)nx, (long long)ny);
   return SMI_OK;
 }
 

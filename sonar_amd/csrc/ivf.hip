@@ -112,12 +112,7 @@ int64_t slots_bound(int64_t n, int64_t K) {
   const int64_t m = std::min(n, K);
   return m * IVF_ALIGN + (n - m) / IVF_ALIGN * IVF_ALIGN;
 }
-// A *_workspace_bytes function runs the shape checks of its entry -- the same functions, so it returns 0 exactly where the
-// entry refuses on shape -- under this guard: a sizing call leaves smi_last_error() as it was.
-struct KeepLastError {
-  const std::string text = last_error();
-  ~KeepLastError() { last_error() = text; }
-};
+// (a *_workspace_bytes function runs the shape checks of its entry under KeepLastError: api_common.hpp)
 // pairs of a scan unit = slots of its tiles: 128 where the lists are probed by 256 pairs or more on average, else 64.  (At
 // 128 pairs per list of ~61 rows, 1 M rows over 16 384 lists at nprobe = 8, the 128-slot tile is half empty and the scan took
 // 1.84 ms against 1.34; at 256 pairs per list of ~977 rows it took 1.45 ms against 2.53: profiles/ivf_experiments.txt.)
@@ -133,11 +128,13 @@ struct BuildWs : WsLayout {
 // search: pair counts [K] | pair offsets [K + 1] | unit offsets [K + 1] | cursor [K] | bucketed pairs [nq * nprobe] |
 //         partial scores fp32 [nprobe][nq][k] | partial ids int32 [nprobe][nq][k]
 //         and behind them, in the int8 search (i8_dim = its d, else 0): query codes int8 [nq, d] | query scales fp32 [nq]
+//         and, in the paged search (ceil_rows = its nq, else 0): one 64-bit ceiling key per query
 struct SearchWs : WsLayout {
   int32_t *pcount, *poff, *ubase, *cursor, *pairs, *pi;
   float *ps, *qscale;
   int8_t* qc;
-  SearchWs(void* ws, int64_t nq, int64_t K, int nprobe, int k, int i8_dim = 0) : WsLayout(ws) {
+  unsigned long long* ceil;
+  SearchWs(void* ws, int64_t nq, int64_t K, int nprobe, int k, int i8_dim = 0, int64_t ceil_rows = 0) : WsLayout(ws) {
     const size_t P = (size_t)nq * nprobe;
     pcount = take<int32_t>(K, 16);
     poff = take<int32_t>(K + 1, 16);
@@ -148,6 +145,7 @@ struct SearchWs : WsLayout {
     pi = take<int32_t>(P * k, 16);
     qc = take<int8_t>(i8_dim ? (size_t)nq * i8_dim : 0, 16);
     qscale = take<float>(i8_dim ? nq : 0, 16);
+    ceil = take<unsigned long long>((size_t)ceil_rows, 16);
   }
 };
 
@@ -172,14 +170,6 @@ int check_keys(const IvfKeys& keys) {
   if (keys.accept < 0 || keys.accept > 7)
     return fail(SMI_ERR_INVALID_ARG, "accept=%d must be in [0, 7]: bit 0 less, bit 1 equal, bit 2 greater", keys.accept);
   return SMI_OK;
-}
-// launch(KT as a std::integral_constant), KT = the key-list length of a search for k results: 1, 2, 4 or 8
-template <class Launch>
-hipError_t with_key_list(int k, Launch launch) {
-  if (k == 1) return launch(std::integral_constant<int, 1>{});
-  if (k == 2) return launch(std::integral_constant<int, 2>{});
-  if (k <= 4) return launch(std::integral_constant<int, 4>{});
-  return launch(std::integral_constant<int, 8>{});
 }
 
 // ---------------------------------------------------------------- range search
@@ -401,10 +391,40 @@ hipError_t bucket_rows(const int32_t* labels, int64_t n, int64_t K, int32_t* lis
   return hipGetLastError();
 }
 
-int check_search_args(int64_t nq, int32_t d, int64_t K, int32_t nprobe, int32_t k) {
+constexpr auto no_refusals = [] { return (int)SMI_OK; };
+inline auto keys_refusals(const IvfKeys* keys) {
+  return [keys] { return keys ? check_keys(*keys) : (int)SMI_OK; };
+}
+// How a search kind keeps the k results of a pair: the most k and nprobe it takes, with_key_list(k, launch) = launch(KT as a
+// std::integral_constant), KT the key-list length of its scan for k results, and the merge of the nprobe partial lists.
+struct ProbeLimits {
+  int k, nprobe;  // k = 0: an entry without k (the range search)
+};
+struct TopkLists {  // lists of 1, 2, 4 or 8 keys in registers
+  static constexpr ProbeLimits limits{8, 8};
+  static constexpr auto merge = launch_topk_merge;
+  template <class Launch>
+  static hipError_t with_key_list(int k, Launch launch) {
+    if (k == 1) return launch(std::integral_constant<int, 1>{});
+    if (k == 2) return launch(std::integral_constant<int, 2>{});
+    if (k <= 4) return launch(std::integral_constant<int, 4>{});
+    return launch(std::integral_constant<int, 8>{});
+  }
+};
+struct PageLists {  // a page of IVF_PAGE keys, whatever k
+  static constexpr ProbeLimits limits{IVF_PAGE, 64};
+  static constexpr auto merge = launch_topk_merge_page;
+  template <class Launch>
+  static hipError_t with_key_list(int, Launch launch) {
+    return launch(std::integral_constant<int, IVF_PAGE>{});
+  }
+};
+// the shape refusals of every entry over nq queries with nprobe probes each: the search, the page and the range search
+int check_search_args(int64_t nq, int32_t d, int64_t K, int32_t nprobe, int32_t k, ProbeLimits most = TopkLists::limits) {
   if (const int rc = check_shape(nq, "nq", d, K, "list")) return rc;
-  if (k < 1 || k > 8) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, 8]", k);
-  if (nprobe < 1 || nprobe > 8) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 8]", nprobe);
+  if (most.k && (k < 1 || k > most.k)) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, %d]", k, most.k);
+  if (nprobe < 1 || nprobe > most.nprobe)
+    return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, %d]", nprobe, most.nprobe);
   if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
   return SMI_OK;
 }
@@ -440,47 +460,42 @@ int build_entry(bool null_arg, const int32_t* labels, int64_t n, int32_t d, int6
   return SMI_OK;
 }
 
-// A search entry, stated once.  The kind gives: whether a pointer of its own is null, the name of its sizing function, the
-// i8_dim of its workspace, its own refusals (they follow check_search_args), prepare(w, st), what it enqueues in front of
-// the inversion (the int8 search encodes its queries there), and scan(kt, unit, units, w, st), the launch of its
+// A search entry, stated once.  Lists: how the kind keeps its results (above).  The kind gives: whether a pointer of its own is
+// null, the refusals of its further arguments (keys_refusals of a keyed entry, DESIGN.md 3.24, whose scan hands the keys to
+// launch_units_keyed; the ceilings of a page), the name of its sizing function, the i8_dim and ceil_rows of its workspace,
+// its own refusals on shape (they follow check_search_args), prepare(w, st), what it enqueues in front of the inversion (the
+// int8 search encodes its queries there, the page its ceiling keys), and scan(kt, unit, units, w, st), the launch of its
 // list-walking kernel with key lists of decltype(kt)::value over units for every pair count the table can have: those from
-// ubase[K] on find nothing to do.  keys: null, or the key predicate of a keyed entry, which the kind's scan
-// hands to launch_units_keyed.
-template <class Refusals, class Prepare, class Scan>
-int search_entry(bool null_arg, const IvfKeys* keys, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const int32_t* list_ids,
-                 const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
-                 void* stream, const char* sizing, int i8_dim, Refusals refusals, Prepare prepare, Scan scan) {
+// ubase[K] on find nothing to do.
+template <class Lists = TopkLists, class ArgRefusals, class Refusals, class Prepare, class Scan>
+int search_entry(bool null_arg, ArgRefusals arg_refusals, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
+                 const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws,
+                 int64_t ws_bytes, void* stream, const char* sizing, int i8_dim, int64_t ceil_rows, Refusals refusals,
+                 Prepare prepare, Scan scan) {
   if (null_arg || !probes || !list_ids || !list_offsets || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (keys)
-    if (const int rc = check_keys(*keys)) return rc;
-  if (const int rc = check_search_args(nq, d, K, nprobe, k)) return rc;
+  if (const int rc = arg_refusals()) return rc;
+  if (const int rc = check_search_args(nq, d, K, nprobe, k, Lists::limits)) return rc;
   if (const int rc = refusals()) return rc;
   const int64_t P = nq * nprobe;
-  const SearchWs w(ws, nq, K, nprobe, k, i8_dim);
+  const SearchWs w(ws, nq, K, nprobe, k, i8_dim, ceil_rows);
   if (const int rc = check_ws(ws, ws_bytes, w.bytes(), sizing)) return rc;
   if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
   hipStream_t st = (hipStream_t)stream;
-  prepare(w, st);
+  HIP_TRY(prepare(w, st));
   // one unit rule for every kind: the image and the MFMA work of a PQ unit are the flat unit's, and on int8 lists 128 won
   // from 256 pairs per list on and 64 below as well (profiles/ivf_i8_experiments.txt)
   const int unit = unit_pairs(P, K);
   HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
   const int64_t units = units_bound(P, K, unit);
-  HIP_TRY(with_key_list(k, [&](auto kt) { return scan(kt, unit, units, w, st); }));
-  HIP_TRY(launch_topk_merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
+  HIP_TRY(Lists::with_key_list(k, [&](auto kt) { return scan(kt, unit, units, w, st); }));
+  HIP_TRY(Lists::merge(w.ps, w.pi, nprobe, nq, k, score, idx, st));
   return SMI_OK;
 }
-constexpr auto no_refusals = [] { return (int)SMI_OK; };
-constexpr auto no_prepare = [](const SearchWs&, hipStream_t) {};
+constexpr auto no_prepare = [](const SearchWs&, hipStream_t) { return hipSuccess; };
 
 // The two passes of the range search, stated once.  Its workspace is the search's with k = 0: the inverted
 // probe table and no partial lists.  `emit` (pair_base non-null) trusts the workspace as `count` left it.
-int check_range_shape(int64_t nq, int32_t d, int64_t K, int32_t nprobe) {
-  if (const int rc = check_shape(nq, "nq", d, K, "list")) return rc;
-  if (nprobe < 1 || nprobe > 8) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 8]", nprobe);
-  if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
-  return SMI_OK;
-}
+int check_range_shape(int64_t nq, int32_t d, int64_t K, int32_t nprobe) { return check_search_args(nq, d, K, nprobe, 0, {0, 8}); }
 int range_entry(bool null_arg, const IvfKeys* keys, const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe,
                 const float* threshold, const void* list_rows, const int32_t* list_ids, const int32_t* list_offsets, int64_t K,
                 int32_t* pair_counts, const int64_t* pair_base, int64_t total, float* score, int32_t* idx, void* ws,
@@ -1183,8 +1198,8 @@ int pq_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes
                     const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
                     void* stream, const IvfKeys* keys = nullptr) {
   return search_entry(
-      !qn || !list_codes || (RES && !coarse), keys, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
-      "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)", 0, [&] { return pq_check_codebooks(d, dsub, codebooks); },
+      !qn || !list_codes || (RES && !coarse), keys_refusals(keys), nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_ivf_pq_search_workspace_bytes(nq, K, nprobe, k, d, dsub)", 0, 0, [&] { return pq_check_codebooks(d, dsub, codebooks); },
       no_prepare, [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
         constexpr int KT = decltype(kt)::value;
         constexpr int lds_small = RES ? ivf_pq_residual_scan_lds<IVF_BM>(KT) : ivf_scan_lds<IVF_BM>(KT);
@@ -1202,8 +1217,8 @@ int flat_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* prob
                       const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                       void* ws, int64_t ws_bytes, void* stream, const IvfKeys* keys) {
   return search_entry(
-      !qn || !list_rows, keys, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
-      "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)", 0, no_refusals, no_prepare,
+      !qn || !list_rows, keys_refusals(keys), nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_ivf_search_workspace_bytes(nq, K, nprobe, k, d)", 0, 0, no_refusals, no_prepare,
       [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
         constexpr int KT = decltype(kt)::value;
         return launch_units_keyed<ivf_scan_lists_kernel<KT, IVF_BM>, ivf_scan_lists_kernel<KT, IVF_BIG>,
@@ -1217,11 +1232,12 @@ int i8_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes
                     const float* list_scales, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
                     int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream, const IvfKeys* keys) {
   return search_entry(
-      !qn || !list_codes || !list_scales, keys, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes,
-      stream, "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)", d, [&] { return i8_check_dim(d); },
+      !qn || !list_codes || !list_scales, keys_refusals(keys), nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes,
+      stream, "smi_ivf_i8_search_workspace_bytes(nq, K, nprobe, k, d)", d, 0, [&] { return i8_check_dim(d); },
       [&](const SearchWs& w, hipStream_t st) {  // the queries, encoded like the rows
         hipLaunchKernelGGL(ivf_i8_encode_kernel, grid_for(nq, IVF_TB / 64), dim3(IVF_TB), 0, st, (const f16*)qn, nq, d, w.qc,
                            w.qscale);
+        return hipSuccess;  // (a launch that failed answers at the inversion's end)
       },
       [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
         constexpr int KT = decltype(kt)::value;
@@ -1235,40 +1251,26 @@ int i8_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes
 
 // smi_ivf_search_page: the flat search with lists of a page, up to 64 probes and a ceiling per query.  Its
 // workspace is the search's and one 64-bit ceiling key per query behind it.
-int check_search_page_args(int64_t nq, int32_t d, int64_t K, int32_t nprobe, int32_t k) {
-  if (const int rc = check_shape(nq, "nq", d, K, "list")) return rc;
-  if (k < 1 || k > IVF_PAGE) return fail(SMI_ERR_INVALID_ARG, "k=%d must be in [1, %d]", k, IVF_PAGE);
-  if (nprobe < 1 || nprobe > 64) return fail(SMI_ERR_INVALID_ARG, "nprobe=%d must be in [1, 64]", nprobe);
-  if (nq * nprobe > IVF_MAX) return fail(SMI_ERR_UNSUPPORTED, "nq * nprobe = %lld must fit int32", (long long)(nq * nprobe));
-  return SMI_OK;
-}
-struct SearchPageWs : SearchWs {
-  unsigned long long* ceil;
-  SearchPageWs(void* ws, int64_t nq, int64_t K, int nprobe, int k) : SearchWs(ws, nq, K, nprobe, k) {
-    ceil = take<unsigned long long>((size_t)nq, 16);
-  }
-};
 int flat_search_page_entry(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,
                            const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, const float* ceil_score,
                            const int32_t* ceil_idx, int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
-  if (!qn || !list_rows || !probes || !list_ids || !list_offsets || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (!ceil_score != !ceil_idx) return fail(SMI_ERR_INVALID_ARG, "ceil_score and ceil_idx go together: both or neither");
-  if (const int rc = check_search_page_args(nq, d, K, nprobe, k)) return rc;
-  const int64_t P = nq * nprobe;
-  const SearchPageWs w(ws, nq, K, nprobe, k);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_ivf_search_page_ws_bytes(nq, K, nprobe, k, d)")) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  if (ceil_idx) HIP_TRY(launch_ceiling_keys(ceil_score, ceil_idx, nq, nq, 0, w.ceil, st));
-  const int unit = unit_pairs(P, K);  // the search's rule
-  HIP_TRY(invert_probes(probes, P, K, k, unit, w, st));
-  const int64_t units = units_bound(P, K, unit);
-  HIP_TRY((launch_units<ivf_scan_page_kernel<IVF_BM>, ivf_scan_page_kernel<IVF_BIG>>(
-      unit, units, ivf_page_scan_lds<IVF_BM>(), ivf_page_scan_lds<IVF_BIG>(), st, (const f16*)qn, d, (int)nq, nprobe,
-      (const f16*)list_rows, list_ids, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
-      (const int32_t*)w.pairs, k, w.ps, w.pi, (const unsigned long long*)(ceil_idx ? w.ceil : nullptr))));
-  HIP_TRY(launch_topk_merge_page(w.ps, w.pi, nprobe, nq, k, score, idx, st));
-  return SMI_OK;
+  return search_entry<PageLists>(
+      !qn || !list_rows,
+      [&] {
+        return !ceil_score != !ceil_idx ? fail(SMI_ERR_INVALID_ARG, "ceil_score and ceil_idx go together: both or neither")
+                                        : (int)SMI_OK;
+      },
+      nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_ivf_search_page_ws_bytes(nq, K, nprobe, k, d)", 0, nq, no_refusals,
+      [&](const SearchWs& w, hipStream_t st) {
+        return ceil_idx ? launch_ceiling_keys(ceil_score, ceil_idx, nq, nq, 0, w.ceil, st) : hipSuccess;
+      },
+      [&](auto, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
+        return launch_units<ivf_scan_page_kernel<IVF_BM>, ivf_scan_page_kernel<IVF_BIG>>(
+            unit, units, ivf_page_scan_lds<IVF_BM>(), ivf_page_scan_lds<IVF_BIG>(), st, (const f16*)qn, d, (int)nq, nprobe,
+            (const f16*)list_rows, list_ids, list_offsets, (int)K, (const int32_t*)w.poff, (const int32_t*)w.ubase,
+            (const int32_t*)w.pairs, k, w.ps, w.pi, (const unsigned long long*)(ceil_idx ? w.ceil : nullptr));
+      });
 }
 
 // ---------------------------------------------------------------- L2 flat search
@@ -1327,8 +1329,8 @@ int l2_flat_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* p
                          const float* list_bias, const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k,
                          int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
   return search_entry(
-      !qn || !list_rows || !list_bias, nullptr, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
-      "smi_l2_flat_search_ws_bytes(nq, K, nprobe, k, d)", 0,
+      !qn || !list_rows || !list_bias, no_refusals, nq, d, probes, nprobe, list_ids, list_offsets, K, k, idx, score, ws, ws_bytes, stream,
+      "smi_l2_flat_search_ws_bytes(nq, K, nprobe, k, d)", 0, 0,
       [&] { return (uintptr_t)list_bias % 16 ? fail(SMI_ERR_INVALID_ARG, "list_bias must be 16-byte aligned") : (int)SMI_OK; },
       no_prepare, [&](auto kt, int unit, int64_t units, const SearchWs& w, hipStream_t st) {
         constexpr int KT = decltype(kt)::value;
@@ -1347,7 +1349,7 @@ extern "C" {
 
 int64_t smi_ivf_search_page_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d) {
   const KeepLastError keep;
-  return check_search_page_args(nq, d, K, nprobe, k) ? 0 : (int64_t)SearchPageWs(nullptr, nq, K, nprobe, k).bytes();
+  return check_search_args(nq, d, K, nprobe, k, PageLists::limits) ? 0 : (int64_t)SearchWs(nullptr, nq, K, nprobe, k, 0, nq).bytes();
 }
 
 int smi_ivf_search_page(const void* qn, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_rows,

@@ -275,20 +275,26 @@ struct KmFinalizeWs : WsLayout {
 size_t km_workspace_bytes(int64_t n, int64_t K, int d) {
   return std::max(KmUpdateWs(nullptr, n, K).bytes(), KmFinalizeWs(nullptr, K, d).bytes());
 }
-// fit: the workspace above | smi_xsim_topk's at k = 1 | new labels int32 [n] | partial objectives fp64 [KM_PARTS] | partial
-//      moved counts int32 [KM_PARTS]
+// fit: the workspace of update and finalise | the top-1 pass's | new labels int32 [n] | the centroids' bias fp32 [bias_rows] |
+//      partial objectives fp64 [KM_PARTS] | partial moved counts int32 [KM_PARTS]
 struct KmFitWs : WsLayout {
   void *km_ws, *xs_ws;
   int32_t *new_labels, *part_moved;
+  float* bias;
   double* part_obj;
-  KmFitWs(void* ws, int64_t n, int64_t K, int d) : WsLayout(ws) {
-    km_ws = take<char>(km_workspace_bytes(n, K, d), 16);
-    xs_ws = take<char>((size_t)smi_xsim_workspace_bytes(n, K, 1, d), 16);
+  KmFitWs(void* ws, int64_t n, size_t km_bytes, size_t xs_bytes, int64_t bias_rows) : WsLayout(ws) {
+    km_ws = take<char>(km_bytes, 16);
+    xs_ws = take<char>(xs_bytes, 16);
     new_labels = take<int32_t>(n, 16);
+    bias = take<float>(bias_rows, 16);
     part_obj = take<double>(KM_PARTS);
     part_moved = take<int32_t>(KM_PARTS);
   }
 };
+// the spherical fit: update and finalise share their workspace, the pass is smi_xsim_topk's at k = 1, no bias
+KmFitWs km_fit_ws(void* ws, int64_t n, int64_t K, int d) {
+  return KmFitWs(ws, n, km_workspace_bytes(n, K, d), (size_t)smi_xsim_workspace_bytes(n, K, 1, d), 0);
+}
 
 hipError_t km_update(const f16* xn, const int32_t* labels, int n, int d, int K, long long* sums, int32_t* counts, void* ws,
                      hipStream_t stream) {
@@ -378,22 +384,57 @@ hipError_t km_l2_finalize(const long long* sums, const int32_t* counts, int K, i
   return hipGetLastError();
 }
 
-// fit: the update's workspace | smi_l2_topk's at k = 1 | new labels int32 [n] | the centroids' bias fp32 [padded K] | partial
-//      objectives fp64 [KM_PARTS] | partial moved counts int32 [KM_PARTS]
-struct KmL2FitWs : WsLayout {
-  void *km_ws, *xs_ws;
-  int32_t *new_labels, *part_moved;
-  float* bias;
-  double* part_obj;
-  KmL2FitWs(void* ws, int64_t n, int64_t K, int d) : WsLayout(ws) {
-    km_ws = take<char>(KmUpdateWs(nullptr, n, K).bytes(), 16);
-    xs_ws = take<char>(l2_topk_ws_bytes(smi_xsim_padded_rows(n), smi_xsim_padded_rows(K), 1, d), 16);
-    new_labels = take<int32_t>(n, 16);
-    bias = take<float>(smi_xsim_padded_rows(K), 16);
-    part_obj = take<double>(KM_PARTS);
-    part_moved = take<int32_t>(KM_PARTS);
+// the Euclidean fit: its finalise needs no workspace, the pass is smi_l2_topk's at k = 1, one bias per padded centroid row
+KmFitWs km_l2_fit_ws(void* ws, int64_t n, int64_t K, int d) {
+  return KmFitWs(ws, n, KmUpdateWs(nullptr, n, K).bytes(), l2_topk_ws_bytes(smi_xsim_padded_rows(n), smi_xsim_padded_rows(K), 1, d),
+                 smi_xsim_padded_rows(K));
+}
+
+// A fit, stated once: `resume` = 0 starts from centroids_f32 (start(st) makes the metric's fp16 centroids of them and one
+// assignment is recorded in slot 0), then n_iter rounds of update, finalize(it, w, st) and an assignment.  An assignment is
+// nearest(w, st), the metric's top-1 pass into w.new_labels and scores (ties to the lower index), and the round's record:
+// the objective and how many rows moved.  null_arg, refusals (they follow the checks of n_iter and resume), layout and its
+// sizing call are the entry's own.
+template <class Refusals, class Start, class Finalize, class Nearest>
+int km_fit(bool null_arg, const void* x, int64_t n, int32_t d, int64_t K, int32_t n_iter, int32_t resume, int32_t* labels, float* scores,
+           int64_t* sums, int32_t* counts, double* objective, int32_t* moved, void* ws, int64_t ws_bytes, void* stream,
+           KmFitWs (*layout)(void*, int64_t, int64_t, int), const char* sizing, Refusals refusals, Start start, Finalize finalize,
+           Nearest nearest) {
+  if (null_arg || !x || !labels || !scores || !sums || !counts || !objective || !moved)
+    return fail(SMI_ERR_INVALID_ARG, "null argument");
+  if (const int rc = check_shape(n, nullptr, d, K, "cluster")) return rc;
+  if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d", n_iter);
+  if (resume != 0 && resume != 1) return fail(SMI_ERR_INVALID_ARG, "resume=%d (0 or 1)", resume);
+  if (const int rc = refusals()) return rc;
+  const KmFitWs w = layout(ws, n, K, d);
+  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), sizing)) return rc;
+  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
+  hipStream_t st = (hipStream_t)stream;
+  const int per = (int)((n + KM_PARTS - 1) / KM_PARTS);
+
+  auto assign = [&](int slot) -> int {
+    HIP_TRY(nearest(w, st));
+    hipLaunchKernelGGL(km_round_part_kernel, dim3(KM_PARTS), dim3(KM_TB), 0, st, scores, w.new_labels, labels, (int)n, per,
+                       w.part_obj, w.part_moved);
+    hipLaunchKernelGGL(km_round_sum_kernel, dim3(1), dim3(KM_PARTS), 0, st, w.part_obj, w.part_moved, objective + slot,
+                       moved + slot);
+    HIP_TRY(hipGetLastError());
+    return SMI_OK;
+  };
+
+  int slot = 0;
+  if (!resume) {
+    HIP_TRY(start(st));
+    HIP_TRY(hipMemsetAsync(labels, 0xff, (size_t)n * 4, st));  // -1: every row counts as moved
+    if (const int rc = assign(slot++)) return rc;
   }
-};
+  for (int it = 0; it < n_iter; ++it) {
+    HIP_TRY(km_update((const f16*)x, labels, (int)n, d, (int)K, (long long*)sums, counts, w.km_ws, st));
+    HIP_TRY(finalize(it, w, st));
+    if (const int rc = assign(slot++)) return rc;
+  }
+  return SMI_OK;
+}
 
 }  // namespace
 
@@ -401,9 +442,10 @@ struct KmL2FitWs : WsLayout {
 
 extern "C" {
 
+// (a sizing function asks the entries' shape check, and leaves smi_last_error() as it was)
 int64_t smi_kmeans_workspace_bytes(int64_t n, int64_t K, int32_t d) {
-  if (n < 1 || K < 1 || d <= 0 || d % 64 || n > 0x7fffff00LL || K > 0x7fffff00LL) return 0;
-  return (int64_t)km_workspace_bytes(n, K, d);
+  const KeepLastError keep;
+  return check_shape(n, nullptr, d, K, "cluster") ? 0 : (int64_t)km_workspace_bytes(n, K, d);
 }
 
 int smi_kmeans_update(const void* xn, const int32_t* labels, int64_t n, int32_t d, int64_t K, int64_t* sums,
@@ -432,45 +474,20 @@ int smi_kmeans_finalize(const int64_t* sums, const int32_t* counts, int64_t K, i
 int smi_kmeans_fit(const void* xn, int64_t n, int32_t d, int64_t K, int32_t n_iter, int32_t resume, float* centroids_f32,
                    void* centroids_f16, int32_t* labels, float* scores, int64_t* sums, int32_t* counts, double* objective,
                    int32_t* moved, int32_t* empty, void* ws, int64_t ws_bytes, void* stream) {
-  if (!xn || !centroids_f32 || !centroids_f16 || !labels || !scores || !sums || !counts || !objective || !moved || !empty)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, nullptr, d, K, "cluster")) return rc;
-  if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d", n_iter);
-  if (resume != 0 && resume != 1) return fail(SMI_ERR_INVALID_ARG, "resume=%d (0 or 1)", resume);
-  const KmFitWs w(ws, n, K, d);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(),
-                              "smi_kmeans_workspace_bytes(n, K, d) + smi_xsim_workspace_bytes(n, K, 1, d) + 4 n (each "
-                              "rounded up to 16) + 3072"))
-    return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  const int per = (int)((n + KM_PARTS - 1) / KM_PARTS);
   const int64_t n_pad = smi_xsim_padded_rows(n), k_pad = smi_xsim_padded_rows(K);
-
-  // assign every row to its nearest centroid (ties to the lower index: smi_xsim_topk's order), then this round's record
-  auto assign = [&](int slot) -> int {
-    HIP_TRY(launch_xsim_topk((const f16*)xn, n, n_pad, (const f16*)centroids_f16, K, k_pad, d, 1, 0, w.new_labels, scores,
-                             w.xs_ws, st));
-    hipLaunchKernelGGL(km_round_part_kernel, dim3(KM_PARTS), dim3(KM_TB), 0, st, scores, w.new_labels, labels, (int)n, per,
-                       w.part_obj, w.part_moved);
-    hipLaunchKernelGGL(km_round_sum_kernel, dim3(1), dim3(KM_PARTS), 0, st, w.part_obj, w.part_moved, objective + slot,
-                       moved + slot);
-    HIP_TRY(hipGetLastError());
-    return SMI_OK;
-  };
-
-  int slot = 0;
-  if (!resume) {
-    HIP_TRY(launch_l2_normalize(centroids_f32, 1, (f16*)centroids_f16, K, d, st));
-    HIP_TRY(hipMemsetAsync(labels, 0xff, (size_t)n * 4, st));  // -1: every row counts as moved
-    if (const int rc = assign(slot++)) return rc;
-  }
-  for (int it = 0; it < n_iter; ++it) {
-    HIP_TRY(km_update((const f16*)xn, labels, (int)n, d, (int)K, (long long*)sums, counts, w.km_ws, st));
-    HIP_TRY(km_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, empty + it, w.km_ws, st));
-    if (const int rc = assign(slot++)) return rc;
-  }
-  return SMI_OK;
+  return km_fit(
+      !centroids_f32 || !centroids_f16 || !empty, xn, n, d, K, n_iter, resume, labels, scores, sums, counts, objective, moved, ws,
+      ws_bytes, stream, km_fit_ws,
+      "smi_kmeans_workspace_bytes(n, K, d) + smi_xsim_workspace_bytes(n, K, 1, d) + 4 n (each rounded up to 16) + 3072",
+      [] { return (int)SMI_OK; },
+      [&](hipStream_t st) { return launch_l2_normalize(centroids_f32, 1, (f16*)centroids_f16, K, d, st); },
+      [&](int it, const KmFitWs& w, hipStream_t st) {
+        return km_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, empty + it, w.km_ws, st);
+      },
+      [&](const KmFitWs& w, hipStream_t st) {
+        return launch_xsim_topk((const f16*)xn, n, n_pad, (const f16*)centroids_f16, K, k_pad, d, 1, 0, w.new_labels, scores,
+                                w.xs_ws, st);
+      });
 }
 
 // ---- Euclidean k-means
@@ -488,56 +505,33 @@ int smi_l2_kmeans_finalize(const int64_t* sums, const int32_t* counts, int64_t K
 }
 
 int64_t smi_l2_kmeans_fit_ws_bytes(int64_t n, int64_t K, int32_t d) {
-  if (n < 1 || K < 1 || d <= 0 || d % 64 || n > 0x7fffff00LL || K > 0x7fffff00LL) return 0;
-  return (int64_t)KmL2FitWs(nullptr, n, K, d).bytes();
+  const KeepLastError keep;
+  return check_shape(n, nullptr, d, K, "cluster") ? 0 : (int64_t)km_l2_fit_ws(nullptr, n, K, d).bytes();
 }
 
 int smi_l2_kmeans_fit(const void* x_f16, int64_t n, int32_t d, int64_t K, int32_t n_iter, int32_t resume, float* centroids_f32,
                       void* centroids_f16, float* centroid_half_norms, int32_t* labels, float* scores, int64_t* sums,
                       int32_t* counts, double* objective, int32_t* moved, int32_t* empty, void* ws, int64_t ws_bytes,
                       void* stream) {
-  if (!x_f16 || !centroids_f32 || !centroids_f16 || !centroid_half_norms || !labels || !scores || !sums || !counts || !objective ||
-      !moved || !empty)
-    return fail(SMI_ERR_INVALID_ARG, "null argument");
-  if (const int rc = check_shape(n, nullptr, d, K, "cluster")) return rc;
-  if (n_iter < 0) return fail(SMI_ERR_INVALID_ARG, "n_iter=%d", n_iter);
-  if (resume != 0 && resume != 1) return fail(SMI_ERR_INVALID_ARG, "resume=%d (0 or 1)", resume);
-  if (((uintptr_t)x_f16 | (uintptr_t)centroids_f32 | (uintptr_t)centroids_f16) % 16)
-    return fail(SMI_ERR_INVALID_ARG, "x_f16, centroids_f32 and centroids_f16 must be 16-byte aligned");
-  const KmL2FitWs w(ws, n, K, d);
-  if (const int rc = check_ws(ws, ws_bytes, w.bytes(), "smi_l2_kmeans_fit_ws_bytes(n, K, d)")) return rc;
-  if (!have_device()) return fail(SMI_ERR_NO_DEVICE, "no HIP device visible");
-  hipStream_t st = (hipStream_t)stream;
-  const int per = (int)((n + KM_PARTS - 1) / KM_PARTS);
   const int64_t n_pad = smi_xsim_padded_rows(n), k_pad = smi_xsim_padded_rows(K);
-
-  // assign every row to its nearest centroid: the biased top-1 with b = -h_c (ties to the lower index), then this round's
-  // record, by the kernels of the spherical fit
-  auto assign = [&](int slot) -> int {
-    HIP_TRY(launch_l2_neg_gather(nullptr, k_pad, centroid_half_norms, w.bias, st));
-    HIP_TRY(launch_l2_topk((const f16*)x_f16, n, n_pad, (const f16*)centroids_f16, K, k_pad, d, 1, 0, w.bias, w.new_labels, scores,
-                           w.xs_ws, st));
-    hipLaunchKernelGGL(km_round_part_kernel, dim3(KM_PARTS), dim3(KM_TB), 0, st, scores, w.new_labels, labels, (int)n, per,
-                       w.part_obj, w.part_moved);
-    hipLaunchKernelGGL(km_round_sum_kernel, dim3(1), dim3(KM_PARTS), 0, st, w.part_obj, w.part_moved, objective + slot,
-                       moved + slot);
-    HIP_TRY(hipGetLastError());
-    return SMI_OK;
-  };
-
-  int slot = 0;
-  if (!resume) {
-    HIP_TRY(launch_l2_prepare(centroids_f32, 1, (f16*)centroids_f16, centroid_half_norms, K, d, st));
-    HIP_TRY(hipMemsetAsync(labels, 0xff, (size_t)n * 4, st));  // -1: every row counts as moved
-    if (const int rc = assign(slot++)) return rc;
-  }
-  for (int it = 0; it < n_iter; ++it) {
-    HIP_TRY(km_update((const f16*)x_f16, labels, (int)n, d, (int)K, (long long*)sums, counts, w.km_ws, st));
-    HIP_TRY(km_l2_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, centroid_half_norms,
-                           empty + it, st));
-    if (const int rc = assign(slot++)) return rc;
-  }
-  return SMI_OK;
+  return km_fit(
+      !centroids_f32 || !centroids_f16 || !centroid_half_norms || !empty, x_f16, n, d, K, n_iter, resume, labels, scores, sums,
+      counts, objective, moved, ws, ws_bytes, stream, km_l2_fit_ws, "smi_l2_kmeans_fit_ws_bytes(n, K, d)",
+      [&] {
+        return ((uintptr_t)x_f16 | (uintptr_t)centroids_f32 | (uintptr_t)centroids_f16) % 16
+                   ? fail(SMI_ERR_INVALID_ARG, "x_f16, centroids_f32 and centroids_f16 must be 16-byte aligned")
+                   : (int)SMI_OK;
+      },
+      [&](hipStream_t st) { return launch_l2_prepare(centroids_f32, 1, (f16*)centroids_f16, centroid_half_norms, K, d, st); },
+      [&](int it, const KmFitWs&, hipStream_t st) {
+        return km_l2_finalize((const long long*)sums, counts, (int)K, d, centroids_f32, (f16*)centroids_f16, centroid_half_norms,
+                              empty + it, st);
+      },
+      [&](const KmFitWs& w, hipStream_t st) {  // the biased top-1 with b = -h_c
+        if (hipError_t e = launch_l2_neg_gather(nullptr, k_pad, centroid_half_norms, w.bias, st); e != hipSuccess) return e;
+        return launch_l2_topk((const f16*)x_f16, n, n_pad, (const f16*)centroids_f16, K, k_pad, d, 1, 0, w.bias, w.new_labels,
+                              scores, w.xs_ws, st);
+      });
 }
 
 }  // extern "C"

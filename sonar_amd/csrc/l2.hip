@@ -171,19 +171,6 @@ hipError_t launch_l2_topk(const f16* X, int64_t nx, int64_t nx_pad, const f16* Y
   });
 }
 
-namespace {
-
-// the refusals a shape alone decides: smi_xsim_topk's, and row numbers that do not fit int32
-int l2_check_shape(int64_t nx, int64_t ny, int32_t k, int32_t d) {
-  if (k < 1 || k > 8) return fail(SMI_ERR_UNSUPPORTED, "k=%d outside [1,8]", k);
-  if (d <= 0 || d % 64) return fail(SMI_ERR_UNSUPPORTED, "d=%d must be a multiple of 64", d);
-  if (nx <= 0 || ny <= 0) return fail(SMI_ERR_INVALID_ARG, "empty input");
-  if (nx > 0x7fffff00LL || ny > 0x7fffff00LL)
-    return fail(SMI_ERR_UNSUPPORTED, "nx=%lld, ny=%lld: row numbers must fit int32", (long long)nx, (long long)ny);
-  return SMI_OK;
-}
-
-}  // namespace
 }  // namespace smi
 
 extern "C" {
@@ -202,15 +189,15 @@ int smi_l2_prepare(const void* src, int32_t src_dtype, int64_t rows, int32_t d, 
 }
 
 int64_t smi_l2_topk_ws_bytes(int64_t nx, int64_t ny, int32_t k, int32_t d) {
-  if (nx <= 0 || ny <= 0 || k < 1 || k > 8 || d <= 0 || d % 64 || nx > 0x7fffff00LL || ny > 0x7fffff00LL) return 0;
-  return (int64_t)l2_topk_ws_bytes(smi_xsim_padded_rows(nx), smi_xsim_padded_rows(ny), k, d);
+  const KeepLastError keep;
+  return check_topk_shape(nx, ny, k, 8, d) ? 0 : (int64_t)l2_topk_ws_bytes(smi_xsim_padded_rows(nx), smi_xsim_padded_rows(ny), k, d);
 }
 
 int smi_l2_topk(const void* x_f16, int64_t nx, const void* y_f16, int64_t ny, int32_t d, int32_t k, int64_t y_off,
                 const float* y_bias, int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
   if (!x_f16 || !y_f16 || !idx || !score) return fail(SMI_ERR_INVALID_ARG, "null argument");
   if (!y_bias) return fail(SMI_ERR_INVALID_ARG, "null y_bias: one fp32 per padded y row (zeros for the inner product)");
-  if (int rc = l2_check_shape(nx, ny, k, d)) return rc;
+  if (int rc = check_topk_shape(nx, ny, k, 8, d)) return rc;
   if (((uintptr_t)x_f16 | (uintptr_t)y_f16 | (uintptr_t)y_bias) % 16)
     return fail(SMI_ERR_INVALID_ARG, "rows and y_bias must be 16-byte aligned");
   if (int rc = check_ws(ws, ws_bytes, (size_t)smi_l2_topk_ws_bytes(nx, ny, k, d), "smi_l2_topk_ws_bytes(nx, ny, k, d)")) return rc;

@@ -74,8 +74,8 @@ import torch
 from . import _lib
 from .clustering import KMeans, SphericalKMeans, init_rows
 from .mining import pair_scores
-from .xsim import (PAGE, WIDE_MAX, check_below, check_count, last_entry, normalize_rows, page_sizes, prepare_rows,
-                   topk_bias_prepared, topk_normalized, topk_wide_normalized)
+from .xsim import (PAGE, WIDE_MAX, check_below, check_count, concat_pages, normalize_rows, prepare_rows, topk_bias_prepared,
+                   topk_normalized, topk_wide_normalized)
 
 LIST_ALIGN = 16    # SMI_IVF_LIST_ALIGN: every list starts at a multiple of this many slots and is padded to it
 UNIT_QUERIES = 64  # SMI_IVF_UNIT_QUERIES: queries of one list that one work unit of the scan takes (128 when nq nprobe >= 256 K)
@@ -230,10 +230,11 @@ def _keyed_args(keyed):
     return (keyed[0].data_ptr(), keyed[1].data_ptr(), keyed[2]) if keyed else ()
 
 
-def _search(entry: str, sizing: str, qn, probes, k: int, extras, storage, ids, offsets, dsub=(), keyed=()):
+def _search(entry: str, sizing: str, qn, probes, k: int, extras, storage, ids, offsets, dsub=(), keyed=(), last=()):
     """A search entry of the C ABI and its sizing call, as in `_build`: `head + extras + nprobe + storage + tail`, storage the
     arguments that describe the lists (pointers of tensors the caller holds).  keyed: `_check_keyed`'s result; with it the
-    entry is its `_keyed` twin.  Returns (scores, ids)."""
+    entry is its `_keyed` twin.  last: what the entry takes behind the stream (the ceilings of a page).  Returns (scores,
+    ids)."""
     lib = _lib.load()
     (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
     if keyed:
@@ -246,7 +247,7 @@ def _search(entry: str, sizing: str, qn, probes, k: int, extras, storage, ids, o
     with torch.cuda.device(qn.device):
         _lib.check(getattr(lib, entry)(qn.data_ptr(), nq, d, probes.data_ptr(), *extras, nprobe, *storage, ids.data_ptr(),
                                        offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes,
-                                       _lib.current_stream_ptr(), *_keyed_args(keyed)))
+                                       _lib.current_stream_ptr(), *_keyed_args(keyed), *last))
     return score, idx
 
 
@@ -323,21 +324,11 @@ def search_lists_page(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor
         raise ValueError(f"probes must be [nq, 1..{WIDE_MAX}] with nq <= {qn.shape[0]} rows, got {list(probes.shape)}")
     _check_table(probes, "probes", *(probes.shape if isinstance(probes, torch.Tensor) else (-1, 1)))
     _check_lists_dim(qn, rows)
-    (nq, nprobe), d, n_lists = probes.shape, qn.shape[1], offsets.shape[0] - 1
-    below = check_below(below, nq, qn)
-    lib = _lib.load()
-    ws_bytes = int(lib.smi_ivf_search_page_ws_bytes(nq, n_lists, nprobe, k, d))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=qn.device)
-    idx = torch.empty((nq, k), dtype=torch.int32, device=qn.device)
-    score = torch.empty((nq, k), dtype=torch.float32, device=qn.device)
-    probes = probes.contiguous()
-    with torch.cuda.device(qn.device):
-        ceil = (C.cast(below[0].data_ptr(), C.POINTER(C.c_float)), C.cast(below[1].data_ptr(), C.POINTER(C.c_int32))) \
-            if below else (None, None)
-        _lib.check(lib.smi_ivf_search_page(qn.data_ptr(), nq, d, probes.data_ptr(), nprobe, rows.data_ptr(), ids.data_ptr(),
-                                           offsets.data_ptr(), n_lists, k, idx.data_ptr(), score.data_ptr(), ws.data_ptr(),
-                                           ws_bytes, _lib.current_stream_ptr(), *ceil))
-    return score, idx
+    below = check_below(below, probes.shape[0], qn)
+    ceil = (C.cast(below[0].data_ptr(), C.POINTER(C.c_float)), C.cast(below[1].data_ptr(), C.POINTER(C.c_int32))) \
+        if below else (None, None)
+    return _search("smi_ivf_search_page", "smi_ivf_search_page_ws_bytes", qn, probes, k, (), (rows.data_ptr(),), ids, offsets,
+                   last=ceil)
 
 
 class RangeResult(NamedTuple):
@@ -819,6 +810,23 @@ class _IVFIndex:
         self._need_add("ntotal")
         return int(self._sizes.sum().item())
 
+    # ------------------------------------------------------------------------------------------------ the metric
+    def _prepare_rows(self, x) -> tuple:
+        """What the metric makes of rows, of the corpus and of queries alike: first the padded fp16 matrix that the nearest
+        lists are found for and that the lists hold, then what `_build_lists` takes beside it."""
+        return (normalize_rows(x),)
+
+    def _nearest_lists(self, x16, n: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(scores fp32, lists int32) [n, nprobe]: the nearest centroids of the first n prepared rows, nearest first."""
+        return topk_normalized(x16, n, self._c16, self._k, nprobe)
+
+    def _check_query(self, q) -> int:
+        """The queries of a probe or a search: a device matrix of the index's dimension; returns nq."""
+        _check_matrix(q, "q")
+        if q.shape[1] != self._d:
+            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
+        return q.shape[0]
+
     # ------------------------------------------------------------------------------------------------ add
     def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None):
         """Index the rows of x (fp16 / fp32 [n, d] on the device); ids are the row numbers.  Once per index.
@@ -835,10 +843,10 @@ class _IVFIndex:
         n = x.shape[0]
         if labels is not None:
             _check_table(labels, "labels", n, None)
-        xn = normalize_rows(x)
+        prepared = self._prepare_rows(x)
         if labels is None:
-            labels = topk_normalized(xn, n, self._c16, self._k, 1)[1][:, 0]
-        for name, t in zip(self._STORAGE, self._build_lists(xn, labels)):
+            labels = self._nearest_lists(prepared[0], n, 1)[1][:, 0]
+        for name, t in zip(self._STORAGE, self._build_lists(*prepared, labels)):
             setattr(self, name, t)
         self._added = True
         return self
@@ -847,13 +855,10 @@ class _IVFIndex:
     def probe(self, q: torch.Tensor, nprobe: int = 1) -> torch.Tensor:
         """int32 [nq, nprobe]: the nprobe nearest lists of every query, nearest first."""
         _check_small(nprobe, "nprobe")
-        _check_matrix(q, "q")
-        if q.shape[1] != self._d:
-            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
-        qn = normalize_rows(q)
+        nq = self._check_query(q)
         if nprobe > self._k:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
-        return topk_normalized(qn, q.shape[0], self._c16, self._k, nprobe)[1]
+        return self._nearest_lists(self._prepare_rows(q)[0], nq, nprobe)[1]
 
     def probe_wide(self, q: torch.Tensor, nprobe: int = PAGE) -> torch.Tensor:
         """`probe` for nprobe up to 64: the paged top-k against the centroids (`xsim.topk_wide_normalized`),
@@ -863,13 +868,11 @@ class _IVFIndex:
     def _probe_wide(self, q, nprobe, qn=None):
         """(coarse scores, probes) of `probe_wide`; qn: the normalised q, where the caller has it."""
         check_count(nprobe, "nprobe", WIDE_MAX)
-        _check_matrix(q, "q")
-        if q.shape[1] != self._d:
-            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
+        nq = self._check_query(q)
         if nprobe > self._k:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
         qn = normalize_rows(q) if qn is None else qn
-        return topk_wide_normalized(qn, q.shape[0], self._c16, self._k, nprobe)
+        return topk_wide_normalized(qn, nq, self._c16, self._k, nprobe)
 
     def row_filter(self, keys: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> RowFilter:
         """The `RowFilter` of `search(..., rows=)`.  keys: device int32 [n], the key of every row `add` was
@@ -925,18 +928,16 @@ class _IVFIndex:
     def range_search(self, *args, **kwargs):
         raise TypeError(f"range_search needs the fp16 lists of an IVFFlatIndex; {self._HOLDS}")
 
-    def _check_search(self, q, k, nprobe, probes, what: str = "search") -> int:
-        """The argument checks of `search` (and of `range_search`, with k = 1); returns nq."""
-        _check_small(k, "k")
-        _check_small(nprobe, "nprobe")
+    def _check_search(self, q, k, nprobe, probes, what: str = "search", most_k: int = 8, most_probes: int = 8) -> int:
+        """The argument checks of `search` (of `range_search`, with k = 1; of the paged searches, with their limits); returns
+        nq."""
+        check_count(k, "k", most_k)
+        check_count(nprobe, "nprobe", most_probes)
         self._need_add(what)
-        _check_matrix(q, "q")
-        if q.shape[1] != self._d:
-            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
-        nq = q.shape[0]
+        nq = self._check_query(q)
         if probes is not None:
-            if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= 8):
-                raise ValueError(f"probes must be [nq, 1..8], got {list(probes.shape)}")
+            if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= most_probes):
+                raise ValueError(f"probes must be [nq, 1..{most_probes}], got {list(probes.shape)}")
             _check_table(probes, "probes", nq, probes.shape[1] if isinstance(probes, torch.Tensor) else 1)
         elif nprobe > self._k:
             raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
@@ -1031,19 +1032,7 @@ class IVFFlatIndex(_IVFIndex):
 
     def _check_search_wide(self, q, k, most_k, nprobe, probes, rows, what: str):
         """The argument checks of `search_page` / `search_wide`; returns (nq, the ids the scan runs on)."""
-        check_count(k, "k", most_k)
-        check_count(nprobe, "nprobe", WIDE_MAX)
-        self._need_add(what)
-        _check_matrix(q, "q")
-        if q.shape[1] != self._d:
-            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
-        nq = q.shape[0]
-        if probes is not None:
-            if isinstance(probes, torch.Tensor) and (probes.dim() != 2 or not 1 <= probes.shape[1] <= WIDE_MAX):
-                raise ValueError(f"probes must be [nq, 1..{WIDE_MAX}], got {list(probes.shape)}")
-            _check_table(probes, "probes", nq, probes.shape[1] if isinstance(probes, torch.Tensor) else 1)
-        elif nprobe > self._k:
-            raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
+        nq = self._check_search(q, k, nprobe, probes, what, most_k, WIDE_MAX)
         ids = self._filter(rows, None, "==", nq)[0]
         return nq, self._ids if ids is None else ids
 
@@ -1071,13 +1060,7 @@ class IVFFlatIndex(_IVFIndex):
         qn = normalize_rows(q)
         if probes is None:
             probes = self._probe_wide(q, nprobe, qn)[1]
-        pages, below = [], None
-        for kp in page_sizes(k):
-            pages.append(search_lists_page(qn, probes, self._rows, ids, self._offsets, kp, below))
-            below = last_entry(*pages[-1])
-        if len(pages) == 1:
-            return pages[0]
-        return torch.cat([p[0] for p in pages], 1), torch.cat([p[1] for p in pages], 1)
+        return concat_pages(lambda kp, below: search_lists_page(qn, probes, self._rows, ids, self._offsets, kp, below), k)
 
     def range_search(self, q: torch.Tensor, threshold: Union[float, torch.Tensor], nprobe: int = 1,
                      probes: Optional[torch.Tensor] = None, sort: bool = True, max_total: Optional[int] = None, *,
@@ -1160,37 +1143,15 @@ class IVFFlatL2Index(_IVFIndex):
     def centroids_normalized(self) -> torch.Tensor:
         raise TypeError("an IVFFlatL2Index keeps its centroids as they are: centroids_f16")
 
-    def _nearest_lists(self, q16, nq: int, nprobe: int) -> torch.Tensor:
-        return topk_bias_prepared(q16, nq, self._c16, self._k, self._ch.neg(), nprobe)[1]
+    # the metric: the rows as they are with their half norms, the nearest centroid in the Euclidean sense (the biased top-k)
+    _prepare_rows = staticmethod(prepare_rows)
 
-    def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None):
-        """`IVFFlatIndex.add` on the rows as they are: labels None = the nearest centroid in the Euclidean sense."""
-        if self._added:
-            raise RuntimeError("add was already called: this index is built once (no incremental add)")
-        _check_matrix(x, "x")
-        if x.shape[1] != self._d:
-            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
-        n = x.shape[0]
-        if labels is not None:
-            _check_table(labels, "labels", n, None)
-        x16, hx = prepare_rows(x)
-        if labels is None:
-            labels = self._nearest_lists(x16, n, 1)[:, 0]
-        self._rows, self._ids, self._offsets, self._sizes = build_lists(x16, labels, self._k)
-        self._bias = slot_bias(self._ids, hx)
-        self._added = True
-        return self
+    def _nearest_lists(self, x16, n: int, nprobe: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        return topk_bias_prepared(x16, n, self._c16, self._k, self._ch.neg(), nprobe)
 
-    def probe(self, q: torch.Tensor, nprobe: int = 1) -> torch.Tensor:
-        """int32 [nq, nprobe]: the nprobe nearest lists of every query (squared Euclidean distance to the centroid), nearest
-        first."""
-        _check_small(nprobe, "nprobe")
-        _check_matrix(q, "q")
-        if q.shape[1] != self._d:
-            raise ValueError(f"q has dim {q.shape[1]}, the index {self._d}")
-        if nprobe > self._k:
-            raise ValueError(f"nprobe = {nprobe} exceeds the {self._k} lists")
-        return self._nearest_lists(prepare_rows(q)[0], q.shape[0], nprobe)
+    def _build_lists(self, x16, half_norms, labels):
+        rows, ids, offsets, sizes = build_lists(x16, labels, self._k)
+        return rows, slot_bias(ids, half_norms), ids, offsets, sizes
 
     def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None, *,
                rows: Optional[RowFilter] = None, query_keys=None, refine=None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1206,7 +1167,7 @@ class IVFFlatL2Index(_IVFIndex):
         ids = self._filter(rows, None, "==", nq)[0]
         q16, hq = prepare_rows(q)
         if probes is None:
-            probes = self._nearest_lists(q16, nq, nprobe)
+            probes = self._nearest_lists(q16, nq, nprobe)[1]
         score, idx = search_lists_l2(q16, probes, self._rows, self._bias, self._ids if ids is None else ids, self._offsets, k)
         return (2.0 * (hq[:nq, None] - score)).clamp_min(0.0), idx
 

@@ -56,24 +56,30 @@ def normalize_rows(t: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _call_topk(entry: str, sizing: str, shape, dev, nx: int, k: int, *front, ws: Optional[torch.Tensor] = None):
+    """A top-k entry of the C ABI on the current stream: `front`, its arguments up to the outputs, then idx int32 [nx, k],
+    score fp32 [nx, k] and the workspace -- `ws`, or a fresh one of `sizing(*shape)` bytes.  Returns (score, idx)."""
+    lib = _lib.load()
+    if ws is None:
+        ws = torch.empty(int(getattr(lib, sizing)(*shape)), dtype=torch.uint8, device=dev)
+    idx = torch.empty((nx, k), dtype=torch.int32, device=dev)
+    score = torch.empty((nx, k), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(getattr(lib, entry)(*front, idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
+                                       _lib.current_stream_ptr()))
+    return score, idx
+
+
 def topk_normalized(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, k: int = 1,
                     y_index_offset: int = 0) -> Tuple[torch.Tensor, torch.Tensor]:
     """Mine on already normalised + padded matrices (see normalize_rows)."""
-    lib = _lib.load()
     d = xn.shape[1]
     if yn.shape[1] != d:
         raise ValueError("x and y must have the same dimension")
     if not 1 <= k <= 8:
         raise ValueError("k must be in [1, 8]")
-    ws_bytes = int(lib.smi_xsim_workspace_bytes(nx, ny, k, d))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=xn.device)
-    idx = torch.empty((nx, k), dtype=torch.int32, device=xn.device)
-    score = torch.empty((nx, k), dtype=torch.float32, device=xn.device)
-    with torch.cuda.device(xn.device):
-        _lib.check(lib.smi_xsim_topk(xn.data_ptr(), nx, yn.data_ptr(), ny, d, k, y_index_offset,
-                                     idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes,
-                                     _lib.current_stream_ptr()))
-    return score, idx
+    return _call_topk("smi_xsim_topk", "smi_xsim_workspace_bytes", (nx, ny, k, d), xn.device, nx, k,
+                      xn.data_ptr(), nx, yn.data_ptr(), ny, d, k, y_index_offset)
 
 
 def topk(x: torch.Tensor, y: torch.Tensor, k: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -147,15 +153,8 @@ def topk_bias_prepared(x16: torch.Tensor, nx: int, y16: torch.Tensor, ny: int, b
     if d % 64:
         raise ValueError(f"dim = {d} must be a multiple of 64")
     _check_per_row(bias, pad_y, x16, "bias")
-    lib = _lib.load()
-    ws_bytes = int(lib.smi_l2_topk_ws_bytes(nx, ny, k, d))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x16.device)
-    idx = torch.empty((nx, k), dtype=torch.int32, device=x16.device)
-    score = torch.empty((nx, k), dtype=torch.float32, device=x16.device)
-    with torch.cuda.device(x16.device):
-        _lib.check(lib.smi_l2_topk(x16.data_ptr(), nx, y16.data_ptr(), ny, d, k, y_index_offset, bias.data_ptr(),
-                                   idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
-    return score, idx
+    return _call_topk("smi_l2_topk", "smi_l2_topk_ws_bytes", (nx, ny, k, d), x16.device, nx, k,
+                      x16.data_ptr(), nx, y16.data_ptr(), ny, d, k, y_index_offset, bias.data_ptr())
 
 
 def topk_l2_prepared(x16: torch.Tensor, nx: int, x_half_norms: torch.Tensor, y16: torch.Tensor, ny: int,
@@ -235,20 +234,24 @@ def topk_page_normalized(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, k
     is exhausted: only fill, (-inf, -1).  A ceiling need not be a candidate.  Nothing is read back."""
     check_count(k, "k", PAGE)
     below = check_below(below, nx, xn if isinstance(xn, torch.Tensor) and xn.is_cuda else None)
-    lib = _lib.load()
     d = xn.shape[1]
     if yn.shape[1] != d:
         raise ValueError("x and y must have the same dimension")
-    ws_bytes = int(lib.smi_xsim_topk_page_ws_bytes(nx, ny, k, d))
-    ws = _ws if _ws is not None else torch.empty(ws_bytes, dtype=torch.uint8, device=xn.device)
-    idx = torch.empty((nx, k), dtype=torch.int32, device=xn.device)
-    score = torch.empty((nx, k), dtype=torch.float32, device=xn.device)
-    with torch.cuda.device(xn.device):
-        _lib.check(lib.smi_xsim_topk_page(xn.data_ptr(), nx, yn.data_ptr(), ny, d, k, y_index_offset,
-                                          below[0].data_ptr() if below else None, below[1].data_ptr() if below else None,
-                                          idx.data_ptr(), score.data_ptr(), ws.data_ptr(), ws.numel(),
-                                          _lib.current_stream_ptr()))
-    return score, idx
+    return _call_topk("smi_xsim_topk_page", "smi_xsim_topk_page_ws_bytes", (nx, ny, k, d), xn.device, nx, k,
+                      xn.data_ptr(), nx, yn.data_ptr(), ny, d, k, y_index_offset,
+                      below[0].data_ptr() if below else None, below[1].data_ptr() if below else None, ws=_ws)
+
+
+def concat_pages(page, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A wide call for k results: page(kp, below) -> (score, idx) over `page_sizes(k)`, every page under the last entry of
+    the one before as its ceiling (the first under None), concatenated on the device."""
+    pages, below = [], None
+    for kp in page_sizes(k):
+        pages.append(page(kp, below))
+        below = last_entry(*pages[-1])
+    if len(pages) == 1:
+        return pages[0]
+    return torch.cat([p[0] for p in pages], 1), torch.cat([p[1] for p in pages], 1)
 
 
 def topk_wide_normalized(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, k: int = PAGE,
@@ -259,13 +262,7 @@ def topk_wide_normalized(xn: torch.Tensor, nx: int, yn: torch.Tensor, ny: int, k
     check_count(k, "k", WIDE_MAX)
     lib = _lib.load()
     ws = torch.empty(int(lib.smi_xsim_topk_page_ws_bytes(nx, ny, PAGE, xn.shape[1])), dtype=torch.uint8, device=xn.device)
-    pages, below = [], None
-    for kp in page_sizes(k):
-        pages.append(topk_page_normalized(xn, nx, yn, ny, kp, y_index_offset, below, _ws=ws))
-        below = last_entry(*pages[-1])
-    if len(pages) == 1:
-        return pages[0]
-    return torch.cat([p[0] for p in pages], 1), torch.cat([p[1] for p in pages], 1)
+    return concat_pages(lambda kp, below: topk_page_normalized(xn, nx, yn, ny, kp, y_index_offset, below, _ws=ws), k)
 
 
 def topk_wide(x: torch.Tensor, y: torch.Tensor, k: int = PAGE) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -345,18 +342,13 @@ def topk_int8_normalized(xn: Optional[torch.Tensor], nx: int, yn: Optional[torch
     from . import index  # (index imports this module)
 
     index._check_int8_dim(d)
-    lib = _lib.load()
     xc, xs = x_enc if x_enc is not None else index.encode_rows_int8(xn)
     yc, ys = y_enc if y_enc is not None else index.encode_rows_int8(yn)
     kk = candidates if refine else k
-    ws_bytes = int(lib.smi_xsim_workspace_bytes(nx, ny, kk, d // 2))  # int8 [rows, d] is fp16 [rows, d / 2] in bytes
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    idx = torch.empty((nx, kk), dtype=torch.int32, device=dev)
-    score = torch.empty((nx, kk), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(lib.smi_xsim_topk_i8(xc.data_ptr(), xs.data_ptr(), nx, yc.data_ptr(), ys.data_ptr(), ny, d, kk,
-                                        0 if refine else y_index_offset, idx.data_ptr(), score.data_ptr(), ws.data_ptr(),
-                                        ws_bytes, _lib.current_stream_ptr()))
+    # (the workspace: int8 [rows, d] is fp16 [rows, d / 2] in bytes)
+    score, idx = _call_topk("smi_xsim_topk_i8", "smi_xsim_workspace_bytes", (nx, ny, kk, d // 2), dev, nx, kk,
+                            xc.data_ptr(), xs.data_ptr(), nx, yc.data_ptr(), ys.data_ptr(), ny, d, kk,
+                            0 if refine else y_index_offset)
     if not refine:
         return score, idx
     score, idx = index.refine_candidates(xn, nx, yn, idx)

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
 """Record tests/golden/ivf_refusals.json: what every IVF / PQ entry of csrc/ivf.hip answers to calls it refuses on their
-arguments -- the return code and the smi_last_error() text -- and what its sizing function returns for the same shape.
+arguments -- the return code and the smi_last_error() text -- and what its sizing function returns for the same shape --
+and tests/golden/metric_refusals.json: the same for the paged and Euclidean entries that came after (METRIC_ENTRIES).
 
-    python tests/golden/make_golden_ivf_refusals.py          (on a machine without a HIP device, library built)
+    python tests/golden/make_golden_ivf_refusals.py [ivf] [metric]     (on a machine without a HIP device, library built)
 
 Per entry: its arguments with values it accepts, and its refusals IN THE ORDER THE ENTRY CHECKS THEM, each as the arguments
 to replace.  A case is one refusal, or two neighbours of that order at once (the first one must answer: that fixes the
 order), or one of a few pairs given by hand.  Pointers are made-up aligned integers and are never dereferenced: the
 recorder asserts that no call got as far as looking for a device.  tests/test_ivf_refusals_cpu.py replays the file.
 """
+import ctypes
 import json
 import os
 import sys
@@ -128,9 +130,83 @@ ENTRIES = {
 }
 
 
-def main():
+def ceil_pair():  # the ceilings of a page: both or neither
+    return [("ceil_score alone", {"ceil_score": P}, ARG), ("ceil_idx alone", {"ceil_score": None, "ceil_idx": P}, ARG)]
+
+
+def topk_shape(kmax, big=True):  # the shape refusals of a brute-force top-k, in its order
+    return ([("k 0", {"k": 0}, SHAPE), (f"k {kmax + 1}", {"k": kmax + 1}, SHAPE), ("d", {"d": 96}, SHAPE), ("d 0", {"d": 0}, SHAPE),
+             ("nx 0", {"nx": 0}, SHAPE), ("ny 0", {"ny": 0}, SHAPE)]
+            + ([("big nx", {"nx": I31}, SHAPE), ("big ny", {"ny": I31}, SHAPE)] if big else []))
+
+
+def misaligned(*names):
+    return [(f"misaligned {n}", {n: P + 8}, ARG) for n in names]
+
+
+KM_NULLS = ("centroids_f32", "centroids_f16", "labels", "scores", "sums", "counts", "objective", "moved", "empty")
+KM_SHAPE = [("d", {"d": 96}, SHAPE), ("d 0", {"d": 0}, SHAPE), ("K 0", {"K": 0}, SHAPE), ("n 0", {"n": 0}, SHAPE),
+            ("big n", {"n": I31}, SHAPE), ("big K", {"K": I31}, SHAPE), ("n_iter", {"n_iter": -1}, ARG),
+            ("resume", {"resume": 2}, ARG)]
+
+
+def km_fit(x, extra=()):
+    return [(x, P), ("n", 1000), ("d", 64), ("K", 7), ("n_iter", 3), ("resume", 0), ("centroids_f32", P), ("centroids_f16", P),
+            *extra, ("labels", P), ("scores", P), ("sums", P), ("counts", P), ("objective", P), ("moved", P), ("empty", P),
+            ("ws", P), ("ws_bytes", BIG), ("stream", None)]
+
+
+def topk(extra):
+    return [("x", P), ("nx", 100), ("y", P), ("ny", 300), ("d", 64), ("k", 5), ("y_off", 0), *extra, ("idx", P), ("score", P),
+            ("ws", P), ("ws_bytes", BIG), ("stream", None)]
+
+
+PAGE_TAIL = [("k 0", {"k": 0}, SHAPE), ("k 17", {"k": 17}, SHAPE), ("nprobe 0", {"nprobe": 0}, SHAPE),
+             ("nprobe 65", {"nprobe": 65}, SHAPE), ("big pairs", {"nq": 1 << 29, "nprobe": 8}, SHAPE)]
+CEIL = [("ceil_score", None), ("ceil_idx", None)]
+TW = ("nx", "ny", "k", "d")
+
+# The entries whose host halves were stated once after ivf_refusals.json was recorded.  smi_kmeans_fit has no sizing function
+# of its own: the shape predicate it shares is smi_kmeans_workspace_bytes', and any workspace of 16 bytes is short.
+# smi_xsim_topk's sizing function does not look at d % 64: none is recorded for it.
+METRIC_ENTRIES = {
+    "smi_ivf_search_page": (search([("rows", P)]) + CEIL, ("smi_ivf_search_page_ws_bytes", SW),
+                            nulls("qn", "probes", "rows", "ids", "offsets", "idx", "score") + ceil_pair() + shape_k("nq")
+                            + PAGE_TAIL + ws("smi_ivf_search_page_ws_bytes", 100, 7, 4, 5, 64)
+                            + [("search-sized ws", {"ws_bytes": lib.smi_ivf_search_workspace_bytes(100, 7, 4, 5, 64)}, ARG)],
+                            [("k 16 + nprobe 64 + short ws", {"k": 16, "nprobe": 64, "ws_bytes": 16}, ARG)]),
+    "smi_l2_flat_search": (search([("rows", P), ("bias", P)]), ("smi_l2_flat_search_ws_bytes", SW),
+                           nulls("qn", "probes", "rows", "bias", "ids", "offsets", "idx", "score") + shape_k("nq") + SEARCH_TAIL
+                           + misaligned("bias") + ws("smi_l2_flat_search_ws_bytes", 100, 7, 4, 5, 64), []),
+    "smi_kmeans_fit": (km_fit("xn"), ("smi_kmeans_workspace_bytes", ("n", "K", "d")),
+                       nulls("xn", *KM_NULLS) + KM_SHAPE
+                       + [("null ws", {"ws": None}, ARG), ("misaligned ws", {"ws": P + 8}, ARG), ("short ws", {"ws_bytes": 16}, ARG)],
+                       [("short ws, K 300", {"K": 300, "ws_bytes": 16}, ARG), ("short ws, d 1024", {"d": 1024, "ws_bytes": 16}, ARG)]),
+    "smi_l2_kmeans_fit": (km_fit("x", [("half_norms", P)]), ("smi_l2_kmeans_fit_ws_bytes", ("n", "K", "d")),
+                          nulls("x", "half_norms", *KM_NULLS) + KM_SHAPE + misaligned("x", "centroids_f32", "centroids_f16")
+                          + ws("smi_l2_kmeans_fit_ws_bytes", 1000, 7, 64),
+                          [("short ws, K 300", {"K": 300, "ws_bytes": 16}, ARG), ("short ws, d 1024", {"d": 1024, "ws_bytes": 16}, ARG)]),
+    "smi_l2_topk": (topk([("y_bias", P)]), ("smi_l2_topk_ws_bytes", TW),
+                    nulls("x", "y", "idx", "score", "y_bias") + topk_shape(8) + misaligned("x", "y", "y_bias")
+                    + ws("smi_l2_topk_ws_bytes", 100, 300, 5, 64), []),
+    "smi_xsim_topk_page": (topk(CEIL), ("smi_xsim_topk_page_ws_bytes", TW),
+                           nulls("x", "y", "idx", "score") + ceil_pair() + topk_shape(16)
+                           + ws("smi_xsim_topk_page_ws_bytes", 100, 300, 5, 64), []),
+    "smi_xsim_topk": (topk([]), None,
+                      nulls("x", "y", "idx", "score", "ws") + topk_shape(8, big=False)
+                      + [("short ws", {"ws_bytes": lib.smi_xsim_workspace_bytes(100, 300, 5, 64) - 1}, ARG)], []),
+}
+FILES = {"ivf": (ENTRIES, "ivf_refusals.json"), "metric": (METRIC_ENTRIES, "metric_refusals.json")}
+
+
+def c_args(fn, values):  # a made-up address for an argument declared as a typed pointer
+    return [ctypes.cast(v, t) if isinstance(v, int) and issubclass(t, ctypes._Pointer) else v
+            for t, v in zip(_lib.SYMBOLS[fn][1], values)]
+
+
+def record(entries, file):
     out, odd = {}, []
-    for fn, (args, sizing, refusals, pairs) in ENTRIES.items():
+    for fn, (args, sizing, refusals, pairs) in entries.items():
         names, good = [a for a, _ in args], dict(args)
         assert len(names) == len(_lib.SYMBOLS[fn][1]), fn
         cases, single = [], {}
@@ -142,7 +218,7 @@ def main():
         for label, change, is_shape, first in todo:
             assert set(change) <= set(names), (fn, label)
             call = {**good, **change}
-            rc = getattr(lib, fn)(*(call[a] for a in names))
+            rc = getattr(lib, fn)(*c_args(fn, [call[a] for a in names]))
             text = lib.smi_last_error().decode()
             assert rc not in (0, -3), (fn, label, rc, text)  # neither accepted nor refused for want of a device
             case = {"case": label, "change": change, "rc": rc, "error": text}
@@ -158,7 +234,7 @@ def main():
                    "cases": cases}
     for o in odd:
         print("the pair does not answer as its first refusal alone:", *o)
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "ivf_refusals.json")
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), file)
     with open(path, "w") as f:
         f.write("{\n" + ",\n".join(
             f' {json.dumps(fn)}: {{"args": {json.dumps(e["args"])}, "good": {json.dumps(e["good"])}, '
@@ -168,4 +244,5 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    for which in sys.argv[1:] or FILES:
+        record(*FILES[which])

@@ -5,32 +5,59 @@ refusals one at a time and two neighbouring ones at once (the first one answers:
 what the entry's sizing function returns for the same shape -- 0 exactly where the entry refuses on shape -- which also
 must leave smi_last_error() alone.  Pointers are made-up aligned integers, never dereferenced as long as the calls are
 refused; where a HIP device is visible a regression that stopped refusing would launch kernels on them, so the test is for
-the machine without one."""
+the machine without one.
+
+tests/golden/metric_refusals.json holds the same for the entries whose host halves were stated once after that: the paged
+and the L2 flat search, the two k-means fits and the brute-force top-k entries beside them (METRIC_ENTRIES of the
+recorder), from the library built at commit 9098134, the parent of that change."""
+import ctypes
 import json
 import os
 
 import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ivf_refusals.json")
+GOLDEN_METRIC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "metric_refusals.json")
+METRIC = {"smi_ivf_search_page", "smi_l2_flat_search", "smi_kmeans_fit", "smi_l2_kmeans_fit", "smi_l2_topk", "smi_xsim_topk_page",
+          "smi_xsim_topk"}
 
 
-def test_refusals_are_the_recorded_ones():
+def _library():
     from sonar_amd import _lib, build
 
     build.build(verbose=False)
     lib = _lib.load()
     if lib.smi_device_count() > 0:
         pytest.skip("a HIP device is visible: the made-up pointers must never reach a kernel")
+    return _lib, lib
+
+
+def test_refusals_are_the_recorded_ones():
+    _lib, lib = _library()
     entries = json.load(open(GOLDEN))
     ivf = {s for s in _lib.SYMBOLS if s.startswith(("smi_ivf_", "smi_pq_")) and _lib.SYMBOLS[s][1][-1:] == [_lib.C.c_void_p]}
     assert ivf == set(entries), ivf ^ set(entries)
     assert sum(len(e["cases"]) for e in entries.values()) >= 400
+    _replay(_lib, lib, entries)
+
+
+def test_metric_refusals_are_the_recorded_ones():
+    _lib, lib = _library()
+    entries = json.load(open(GOLDEN_METRIC))
+    assert METRIC == set(entries), METRIC ^ set(entries)
+    assert sum(len(e["cases"]) for e in entries.values()) >= 250
+    _replay(_lib, lib, entries)
+
+
+def _replay(_lib, lib, entries):
     wrong = []
     for fn, e in entries.items():
         names, sizing = e["args"], e["sizing"]
         for c in e["cases"]:
             call = {**dict(zip(names, e["good"])), **c["change"]}
-            rc = getattr(lib, fn)(*(call[a] for a in names))
+            # (a made-up address for an argument declared as a typed pointer goes through a cast)
+            rc = getattr(lib, fn)(*(ctypes.cast(call[a], t) if isinstance(call[a], int) and issubclass(t, ctypes._Pointer)
+                                    else call[a] for a, t in zip(names, _lib.SYMBOLS[fn][1])))
             got = {"rc": rc, "error": lib.smi_last_error().decode()}
             if sizing:
                 got["bytes"] = getattr(lib, sizing["fn"])(*(call[a] for a in sizing["args"]))
