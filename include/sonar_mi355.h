@@ -855,6 +855,41 @@ int smi_ivf_search(const void* qn_f16, int64_t nq, int32_t d, const int32_t* pro
                    const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score,
                    void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Regrouping of IVF storage: extend, remove and merge on the device (restated in tests/ivf_regroup_ref.py).
+ * All five index kinds keep the storage of smi_ivf_build: payload rows of row_bytes bytes (fp16 rows, int8 codes, PQ codes),
+ * one int32 id per slot and at most one 32-bit aux value per slot (the scales of the int8 lists, the bias of the L2 lists).
+ * smi_lists_regroup writes FRESH storage of that layout from the surviving slots of a filled index and a set of new rows that
+ * are already encoded (smi_ivf_i8_encode, smi_pq_encode, smi_pq_encode_residual; fp16 rows as they are).
+ *
+ * Survivors: old slot s survives iff old_ids[s] >= 0 (and s < old_offsets[K]).  old_ids may be the effective ids smi_slot_filter
+ *   writes for a row mask: that is how rows are removed.  old_rows_bound = the caller's upper bound on the number of survivors,
+ *   at most old_slots.
+ * New rows: row i goes to list new_labels[i]; a label outside [0, K) leaves it out (smi_ivf_build's convention).  Its id is
+ *   new_ids[i] where new_ids is given -- a given id below 0 leaves the row out too -- else new_id_base + i.
+ * Output: list c holds the survivors of old list c and the new rows labelled c, each with its row_bytes payload bytes, its
+ *   aux value (where the aux pointers are given) and its id, unchanged.  The layout is smi_ivf_build's: every list starts at a
+ *   multiple of SMI_IVF_LIST_ALIGN, pad slots are zero bytes with aux 0 and id -1, list_sizes[c] = the rows of list c, and
+ *   list_ids is -1 from list_offsets[K] to capacity_slots.  The order inside a list is unspecified, as in the build.
+ *   capacity_slots >= smi_ivf_slots_bound(old_rows_bound + n_new, K): the host checks it without seeing device data.
+ * No store leaves the caller's buffers whatever the device data say: destination slots are bounded by that slots bound and
+ *   list numbers by K; were there more survivors than old_rows_bound, the rows beyond the bound are dropped.
+ * row_bytes: any value from 1 up.  16-byte accesses where row_bytes % 16 == 0 and old_rows, new_rows and list_rows are
+ *   16-byte aligned; byte accesses otherwise.
+ * Empty sides: n_new = 0 (null new_*) is a pure compaction; old_slots = 0 (null old_*) is a build from encoded rows.
+ * workspace: device memory, 16-byte aligned, smi_lists_regroup_ws_bytes(old_slots, n_new, K) bytes.  Nothing is read back or
+ *   allocated: the call can be captured in a graph.
+ * Refused before any launch: a null output pointer, a null input on a side that has rows, K < 1, both sides empty, a negative
+ *   count, row_bytes < 1, old_rows_bound outside [0, old_slots], aux pointers given on some sides that have rows and not on
+ *   others (list_aux counts as a side), an output pointer equal to an input pointer, capacity_slots below the bound, a small
+ *   or misaligned workspace (SMI_ERR_INVALID_ARG); old_slots + n_new, K, new_id_base + n_new or the slots bound above
+ *   2^31 - 256, new_id_base < 0 (SMI_ERR_UNSUPPORTED).  The sizing function returns 0 for a refused shape. */
+int64_t smi_lists_regroup_ws_bytes(int64_t old_slots, int64_t n_new, int64_t K);
+int smi_lists_regroup(const void* old_rows, const float* old_aux, const int32_t* old_ids, const int32_t* old_offsets,
+                    int64_t old_slots, int64_t old_rows_bound, const void* new_rows, const float* new_aux,
+                    const int32_t* new_labels, const int32_t* new_ids, int32_t new_id_base, int64_t n_new, int32_t row_bytes,
+                    int64_t K, void* list_rows, float* list_aux, int32_t* list_ids, int64_t capacity_slots,
+                    int32_t* list_offsets, int32_t* list_sizes, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* A page of the flat search (the contract of a page: smi_xsim_topk_page): the arguments of smi_ivf_search and,
  * BEHIND them as the keyed twins take theirs, the ceilings ceil_score fp32 / ceil_idx int32 [nq], null for none -- ONE ceiling per query, shared by its probes: the result
  * is the k <= 16 best rows strictly after the ceiling over all the lists the query probes, in smi_ivf_search's order, layout

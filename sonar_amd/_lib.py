@@ -461,6 +461,11 @@ SYMBOLS = {
     "smi_ivf_slots_bound": (_i64, [_i64, _i64]),
     "smi_ivf_build_workspace_bytes": (_i64, [_i64, _i64, _i32]),
     "smi_ivf_build": (C.c_int, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp]),
+    # regrouping: the old storage (rows, aux, ids, offsets, slots, rows bound), the new rows (rows, aux, labels,
+    # ids, id base, n), row_bytes, K, then the build's storage arguments with aux behind the rows
+    "smi_lists_regroup_ws_bytes": (_i64, [_i64, _i64, _i64]),
+    "smi_lists_regroup": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i64, _vp, _vp, _vp,
+                                  _i64, _vp, _vp, _vp, _i64, _vp]),
     "smi_ivf_search_workspace_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
     "smi_ivf_search": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
     "smi_range_search_ws_bytes": (_i64, [_i64, _i64, _i32, _i32]),

@@ -1341,6 +1341,9 @@ int l2_flat_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* p
       });
 }
 
+// ---------------------------------------------------------------- regrouping: extend, remove, merge
+#include "ivf_regroup.hpp"
+
 }  // namespace
 
 }  // namespace smi
@@ -1672,6 +1675,22 @@ int smi_l2_flat_search(const void* q_f16, int64_t nq, int32_t d, const int32_t* 
                        int32_t* idx, float* score, void* ws, int64_t ws_bytes, void* stream) {
   return l2_flat_search_entry(q_f16, nq, d, probes, nprobe, list_rows, list_bias, list_ids, list_offsets, K, k, idx, score, ws,
                               ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- regrouping
+int64_t smi_lists_regroup_ws_bytes(int64_t old_slots, int64_t n_new, int64_t K) {
+  const KeepLastError keep;
+  return check_regroup_shape(old_slots, n_new, K) ? 0 : (int64_t)RegroupWs(nullptr, old_slots + n_new, K).bytes();
+}
+
+int smi_lists_regroup(const void* old_rows, const float* old_aux, const int32_t* old_ids, const int32_t* old_offsets,
+                    int64_t old_slots, int64_t old_rows_bound, const void* new_rows, const float* new_aux,
+                    const int32_t* new_labels, const int32_t* new_ids, int32_t new_id_base, int64_t n_new, int32_t row_bytes,
+                    int64_t K, void* list_rows, float* list_aux, int32_t* list_ids, int64_t capacity_slots, int32_t* list_offsets,
+                    int32_t* list_sizes, void* ws, int64_t ws_bytes, void* stream) {
+  return regroup_entry(old_rows, old_aux, old_ids, old_offsets, old_slots, old_rows_bound, new_rows, new_aux, new_labels, new_ids,
+                       new_id_base, n_new, row_bytes, K, list_rows, list_aux, list_ids, capacity_slots, list_offsets, list_sizes, ws,
+                       ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -43,7 +43,7 @@ query's filtered result is, bit for bit, its unfiltered result over an index tha
                                    against its own index, where every query finds itself first)
   excluding the query's document   keys = document numbers, match "!="
   a cut-off date                   keys = dates, query_keys = the query's cut-off, match "<"
-  rows to be ignored               mask = False for them: the only removal there is, as the index is built once
+  rows to be ignored               mask = False for them: they stay in the lists and are scanned; `remove` takes them out
 
 `PreTransformIndex` puts a learned linear transform (`sonar_amd.transforms`: a PCA that cuts the dimension, an OPQ rotation in
 front of the sub-quantisers) in front of any of the four classes, FAISS's `IndexPreTransform`.
@@ -58,10 +58,17 @@ entry keep their limit of 8.
 quantiser is `clustering.KMeans`, every slot carries the bias -||row||^2 / 2 beside its id, and `search` returns (squared
 distances ascending, ids).  SONAR embeddings are not unit vectors; this is FAISS's `METRIC_L2`.
 
+The storage life-cycle, on every class: `add` fills an empty index once; `extend(x)` takes further rows
+(`add(x1).extend(x2)` is the index `add(cat(x1, x2))` builds), `remove(ids= | mask=)` takes rows out, bytes and scan cost
+included, and `merge_from(other)` takes over the rows of an index of the same class over the same quantiser.  All three run
+one device operation, `regroup_lists` (smi_lists_regroup): the surviving slots and the new, already-encoded rows are regrouped
+into fresh list-contiguous storage, so a call costs about one build of the union -- feed chunks, not rows.  A `RowFilter`
+belongs to the storage it was made from: after any of the three, make a new one (an old one is refused).
+
 Not here: L2 on the int8 / PQ / residual lists and in the wide, keyed and range searches, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, lists of more than 16
 results in one pass, k above 64, nprobe or k above 8 on the int8 / PQ / residual indexes, in `range_search` and in `mining`,
-the key predicate on the wide search, de-duplication or range search over quantised lists, incremental add and removal, 64-bit ids, splitting of long
-lists, multi-GPU sharding; of filtering: skipping whole tiles or lists by key, per-query bitmaps or id lists, keys wider than
+the key predicate on the wide search, de-duplication or range search over quantised lists, in-place growth with spare capacity per list (an `extend` that costs
+O(new rows), not O(all rows), bytes), 64-bit ids, splitting of long lists, multi-GPU sharding; of filtering: skipping whole tiles or lists by key, per-query bitmaps or id lists, keys wider than
 32 bits, more than one key per row, a filter on the coarse probe.
 """
 from __future__ import annotations
@@ -85,6 +92,7 @@ PQ_DSUBS = (8, 16, 32, 64)  # dimensions per sub-quantiser
 # the relations of a key predicate as the C ABI's `accept`: a 3-bit mask over the outcome of one signed compare of the row's key
 # with the query's, bit 0 less, bit 1 equal, bit 2 greater (0: nothing passes, 7: everything)
 MATCH_ACCEPT = {"==": 2, "!=": 5, "<": 1, "<=": 3, ">": 4, ">=": 6}
+ID_MAX = 0x7FFFFF00  # 2^31 - 256: the largest row count, and so one more than the largest row id, of every entry
 
 
 def _check_device_tensor(t, name: str, hint: str = "") -> None:
@@ -178,10 +186,12 @@ def _check_search_args(qn, probes, k) -> None:
 class RowFilter(NamedTuple):
     """Which rows of an index's lists count, in slot order (`row_filter`): ids int32 [slots], the row of every
     slot or -1 where it is masked out (or holds none), and keys int32 [slots] or None, the rows' keys.  Reusable across calls;
-    not part of `state_dict`; tied to the storage it was made from by its length."""
+    not part of `state_dict`; tied to the storage it was made from by its length and by `generation`, the number of
+    `extend` / `remove` / `merge_from` calls the index had seen when `row_filter` made it (0: none)."""
 
     ids: torch.Tensor
     keys: Optional[torch.Tensor]
+    generation: int = 0
 
 
 def slot_filter(ids: torch.Tensor, offsets: torch.Tensor, keys: Optional[torch.Tensor] = None,
@@ -263,6 +273,102 @@ def build_lists(xn: torch.Tensor, labels: torch.Tensor, n_lists: int):
     labels, so the storage is sized for any labelling.  Slots from offsets[n_lists] on are unused (ids -1, rows unwritten)."""
     _check_build_args(xn, labels, n_lists)
     return _build("smi_ivf_build", "smi_ivf_build_workspace_bytes", xn, labels, n_lists, (), [(torch.float16, xn.shape[1:])])
+
+
+def _check_regroup_side(side, name: str, rows_like, want_aux):
+    """One side of `regroup_lists`: (rows, aux, third, fourth) -> the four tensors, contiguous; rows_like / want_aux: the rows
+    and whether there is an aux vector on the side checked before (None: this is the first)."""
+    if not isinstance(side, (tuple, list)) or len(side) != 4:
+        raise TypeError(f"{name} must be None or a tuple of four: rows, aux or None, and its two int32 vectors")
+    rows, aux = side[0], side[1]
+    _check_device_tensor(rows, f"{name} rows")
+    if rows.dim() != 2 or rows.shape[1] < 1 or not rows.is_contiguous():
+        raise ValueError(f"{name} rows must be a contiguous [slots, width] matrix, got {list(rows.shape)}")
+    if rows_like is not None and (rows.dtype != rows_like.dtype or rows.shape[1] != rows_like.shape[1]
+                                  or rows.device != rows_like.device):
+        raise ValueError(f"{name} rows are {rows.dtype} [., {rows.shape[1]}] on {rows.device}, the old rows "
+                         f"{rows_like.dtype} [., {rows_like.shape[1]}] on {rows_like.device}")
+    if want_aux is not None and (aux is not None) != want_aux:
+        raise ValueError("aux goes with both sides or with neither: the storage holds one value per slot, or none")
+    if aux is not None:
+        _check_device_tensor(aux, f"{name} aux")
+        if aux.dtype != torch.float32 or aux.dim() != 1 or not aux.is_contiguous():
+            raise ValueError(f"{name} aux must be contiguous fp32 [slots], got {aux.dtype} {list(aux.shape)}")
+    return rows, aux, side[2], side[3]
+
+
+def regroup_lists(n_lists: int, old=None, new=None, old_rows_bound: Optional[int] = None, new_id_base: int = 0,
+                  capacity: Optional[int] = None):
+    """smi_lists_regroup: fresh list-contiguous storage from the surviving slots of a filled storage and a set
+    of new rows that are already encoded.  What `extend`, `remove` and `merge_from` of every index class run on.
+
+    old: None, or (rows [slots, w], aux fp32 [slots] or None, ids int32 [slots], offsets int32 [n_lists + 1]) as a
+         `build_lists*` or an earlier regroup returned them; a slot survives iff its id is >= 0, so ids may be a `RowFilter`'s.
+    new: None, or (rows [>= n, w], aux fp32 [>= n] or None, labels int32 [n], ids int32 [n] or None): row i goes to list
+         labels[i] (outside [0, n_lists): left out) with the id ids[i] (below 0: left out), or new_id_base + i without ids.
+    rows are of any dtype, the same on both sides: fp16 rows, int8 or uint8 codes.  old_rows_bound: an upper bound on the
+    survivors (default: the old slots).  capacity: the slots of the result, at least (and by default)
+    smi_ivf_slots_bound(old_rows_bound + n, n_lists).  Returns (rows, aux or None, ids, offsets, sizes) in `build_lists`'s
+    layout: pad slots are zero with aux 0 and id -1.  Enqueued on the current stream; nothing is read back."""
+    if isinstance(n_lists, bool) or not isinstance(n_lists, int) or n_lists < 1:
+        raise ValueError(f"n_lists = {n_lists!r}: at least one list")
+    if old is None and new is None:
+        raise ValueError("regroup_lists: give old, new or both")
+    rows_like = want_aux = None
+    old_slots = n_new = 0
+    o_rows = o_aux = o_ids = o_off = n_rows = n_aux = n_labels = n_ids = None
+    if old is not None:
+        o_rows, o_aux, o_ids, o_off = _check_regroup_side(old, "old", None, None)
+        old_slots = o_rows.shape[0]
+        _check_table(o_ids, "old ids", old_slots, None)
+        _check_table(o_off, "old offsets", n_lists + 1, None)
+        if o_aux is not None and o_aux.shape[0] != old_slots:
+            raise ValueError(f"old aux has {o_aux.shape[0]} entries for {old_slots} slots")
+        o_ids, o_off = o_ids.contiguous(), o_off.contiguous()
+        rows_like, want_aux = o_rows, o_aux is not None
+    if new is not None:
+        n_rows, n_aux, n_labels, n_ids = _check_regroup_side(new, "new", rows_like, want_aux)
+        _check_table(n_labels, "labels", n_labels.shape[0] if isinstance(n_labels, torch.Tensor) and n_labels.dim() == 1 else -1,
+                     None)
+        n_new = n_labels.shape[0]
+        if n_new > n_rows.shape[0] or (n_aux is not None and n_new > n_aux.shape[0]):
+            raise ValueError(f"{n_new} labels for {n_rows.shape[0]} new rows")
+        if n_ids is not None:
+            _check_table(n_ids, "new ids", n_new, None)
+            n_ids = n_ids.contiguous()
+        n_labels = n_labels.contiguous()
+        rows_like, want_aux = n_rows, n_aux is not None
+    if old_slots + n_new < 1:
+        raise ValueError("regroup_lists: no old slots and no new rows")
+    if old_rows_bound is None:
+        old_rows_bound = old_slots
+    if isinstance(old_rows_bound, bool) or not isinstance(old_rows_bound, int) or not 0 <= old_rows_bound <= old_slots:
+        raise ValueError(f"old_rows_bound = {old_rows_bound!r}: between 0 and the {old_slots} old slots")
+    if isinstance(new_id_base, bool) or not isinstance(new_id_base, int) or new_id_base < 0 or new_id_base + n_new > ID_MAX:
+        raise ValueError(f"new_id_base = {new_id_base!r} with {n_new} new rows: row ids must lie in [0, {ID_MAX}]")
+    lib = _lib.load()
+    need = int(lib.smi_ivf_slots_bound(old_rows_bound + n_new, n_lists)) if old_rows_bound + n_new else 0
+    ws_bytes = int(lib.smi_lists_regroup_ws_bytes(old_slots, n_new, n_lists))
+    if (old_rows_bound + n_new and need < 1) or ws_bytes < 1:
+        raise ValueError(f"{old_slots} slots and {n_new} rows over {n_lists} lists: slot numbers must fit int32")
+    if capacity is None:
+        capacity = max(need, LIST_ALIGN)
+    if isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < max(need, 1):
+        raise ValueError(f"capacity = {capacity!r}: at least smi_ivf_slots_bound({old_rows_bound + n_new}, {n_lists}) = {need}")
+    dev, width = rows_like.device, rows_like.shape[1]
+    rows = torch.empty((capacity, width), dtype=rows_like.dtype, device=dev)
+    aux = torch.empty((capacity,), dtype=torch.float32, device=dev) if want_aux else None
+    ids = torch.empty((capacity,), dtype=torch.int32, device=dev)
+    offsets = torch.empty((n_lists + 1,), dtype=torch.int32, device=dev)
+    sizes = torch.empty((n_lists,), dtype=torch.int32, device=dev)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    with torch.cuda.device(dev):
+        _lib.check(lib.smi_lists_regroup(ptr(o_rows), ptr(o_aux), ptr(o_ids), ptr(o_off), old_slots, old_rows_bound, ptr(n_rows),
+                                       ptr(n_aux), ptr(n_labels), ptr(n_ids), new_id_base, n_new, width * rows_like.element_size(),
+                                       n_lists, rows.data_ptr(), ptr(aux), ids.data_ptr(), capacity, offsets.data_ptr(),
+                                       sizes.data_ptr(), ws.data_ptr(), ws_bytes, _lib.current_stream_ptr()))
+    return rows, aux, ids, offsets, sizes
 
 
 def search_lists(qn: torch.Tensor, probes: torch.Tensor, rows: torch.Tensor, ids: torch.Tensor, offsets: torch.Tensor,
@@ -752,6 +858,10 @@ class _IVFIndex:
     _SLOT_VECTORS = ()
     _EXTRA = ()
     _HOLDS = None  # the sentence that ends the refusal of `self_join`
+    # the storage life-cycle, as class defaults so that an index made any way has them
+    _generation = 0  # the `extend` / `remove` / `merge_from` calls so far: a `RowFilter` of another generation is refused
+    _next_id = None  # the running id, one more than any id handed out; None: not known (a loaded state), read back on demand
+    _rows_bound = None  # an upper bound on the rows the storage holds, known without a read-back
 
     def _check_extra(self, state, d: int, fresh: bool):
         """load_state_dict: (the columns `rows` must have, the attributes to take over from the `_EXTRA` entries)."""
@@ -836,7 +946,7 @@ class _IVFIndex:
         the list counts, the storage is sized for any labelling, `smi_ivf_slots_bound(n, K)` slots, at most
         (LIST_ALIGN - 1) * min(n, K) more than n; `state_dict` cuts it to the slots in use."""
         if self._added:
-            raise RuntimeError("add was already called: this index is built once (no incremental add)")
+            raise RuntimeError("add was already called: `add` fills an empty index once; `extend` takes further rows")
         _check_matrix(x, "x")
         if x.shape[1] != self._d:
             raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
@@ -849,6 +959,166 @@ class _IVFIndex:
         for name, t in zip(self._STORAGE, self._build_lists(*prepared, labels)):
             setattr(self, name, t)
         self._added = True
+        self._next_id = self._rows_bound = n
+        return self
+
+    # ------------------------------------------------------------------------------------------------ extend, remove, merge
+    def _encode_rows(self, prepared: tuple, labels: torch.Tensor, n: int):
+        """(rows, aux or None) of the first n prepared rows as the lists hold them: what the build's gather writes for a
+        row, by the class's stand-alone encoder."""
+        return prepared[0], None
+
+    @property
+    def _aux_name(self) -> Optional[str]:
+        """The attribute of the one value per slot the class keeps beside its rows (`_scales`, `_bias`), or None."""
+        return self._SLOT_VECTORS[0][0] if self._SLOT_VECTORS else None
+
+    def _running_id(self) -> int:
+        """One more than the largest id handed out.  After `load_state_dict` it is max(ids) + 1: one read-back, once."""
+        if self._next_id is None:
+            self._next_id = int(self._ids.max().item()) + 1 if self._ids.shape[0] else 0
+        return self._next_id
+
+    def _old_storage(self, ids: Optional[torch.Tensor] = None):
+        """This index's storage as the `old` of `regroup_lists` (ids: effective ids in place of its own), None if it has no
+        slot."""
+        if not self._ids.shape[0]:
+            return None
+        aux = self._aux_name
+        return (self._rows, getattr(self, aux) if aux else None, self._ids if ids is None else ids, self._offsets)
+
+    def _take_regrouped(self, old, new, n_new_bound: int, id_base: int = 0) -> None:
+        """Run the regroup and take its storage over; n_new_bound: the most rows `new` adds."""
+        slots = self._ids.shape[0]
+        bound = slots if self._rows_bound is None else min(self._rows_bound, slots)
+        rows, aux, ids, offsets, sizes = regroup_lists(self._k, old, new, bound if old is not None else None, id_base)
+        self._rows, self._ids, self._offsets, self._sizes = rows, ids, offsets, sizes
+        if self._aux_name:
+            setattr(self, self._aux_name, aux)
+        self._rows_bound = bound + n_new_bound
+        self._generation += 1
+
+    def _check_id_range(self, first: int, count: int, what: str) -> None:
+        if first + count > ID_MAX:
+            raise ValueError(f"{what}: ids {first} .. {first + count} exceed {ID_MAX} (row ids are int32)")
+
+    def extend(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None, first_id: Optional[int] = None):
+        """Add the rows of x (fp16 / fp32 [n, d] on the device) to a filled index: `add(x1).extend(x2)` is the
+        index `add(cat(x1, x2))` builds -- the same lists, ids, rows or codes and aux values, hence the same search results
+        bit for bit.  The order of the slots inside a list is unspecified, as after `add`.
+
+        labels: as for `add`.  first_id: the id of x[0] (the ids are first_id .. first_id + n); None continues at the running
+        id, the number of rows handed to `add` / `extend` so far -- after `load_state_dict`, max(ids) + 1, read back once.
+        The rows are encoded by the class's stand-alone encoder and regrouped with the old storage into fresh storage of
+        `smi_ivf_slots_bound(rows so far + n, K)` slots (`regroup_lists`): one call costs about one build of the union, so
+        feed chunks, not single rows.  Enqueued on the current stream, no read-back.  A `RowFilter` made before is refused
+        afterwards: make a new one."""
+        self._need_add("extend")
+        _check_matrix(x, "x")
+        if x.shape[1] != self._d:
+            raise ValueError(f"x has dim {x.shape[1]}, the centroids {self._d}")
+        if x.dtype not in (torch.float16, torch.float32):
+            raise ValueError(f"x must be fp16 or fp32, got {x.dtype}")
+        if x.device != self._ids.device:
+            raise ValueError(f"x is on {x.device}, the index on {self._ids.device}")
+        n = x.shape[0]
+        if labels is not None:
+            _check_table(labels, "labels", n, None)
+        if first_id is not None and (isinstance(first_id, bool) or not isinstance(first_id, int) or first_id < 0):
+            raise ValueError(f"first_id = {first_id!r}: None or a non-negative integer")
+        base = self._running_id() if first_id is None else first_id
+        self._check_id_range(base, n, "extend")
+        prepared = self._prepare_rows(x)
+        if labels is None:
+            labels = self._nearest_lists(prepared[0], n, 1)[1][:, 0]
+        labels = labels.contiguous()
+        rows, aux = self._encode_rows(prepared, labels, n)
+        self._take_regrouped(self._old_storage(), (rows, aux, labels, None), n, base)
+        if self._next_id is not None:  # (unknown after load_state_dict and a first_id: max(ids) + 1 will cover these rows)
+            self._next_id = max(self._next_id, base + n)
+        return self
+
+    def remove(self, ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+        """Drop rows from the index: their bytes and their scan cost go, where a `RowFilter` mask only hides
+        them.  Exactly one of
+          ids   a 1-D device int32 / int64 tensor of row ids (an id the index does not hold is ignored);
+          mask  a device bool tensor, True = the row leaves, covering every id handed out so far.
+        The rows that stay keep their ids.  The index is compacted into fresh storage on the effective ids `slot_filter`
+        makes from the complement; the storage keeps its bound (`from_state_dict(state_dict())` cuts it to the slots in
+        use).  Enqueued, no read-back (after `load_state_dict`: the one of the running id).  A `RowFilter` made before is
+        refused afterwards."""
+        self._need_add("remove")
+        if (ids is None) == (mask is None):
+            raise ValueError("remove: give ids or mask, one of the two")
+        total = self._running_id()
+        if mask is not None:
+            _check_device_tensor(mask, "mask")
+            if mask.dtype != torch.bool or mask.dim() != 1:
+                raise ValueError(f"mask must be bool [n], got {mask.dtype} {list(mask.shape)}")
+            if mask.shape[0] < max(total, 1):
+                raise ValueError(f"mask has {mask.shape[0]} entries, the ids handed out so far go up to {total}")
+            keep = mask.logical_not()
+        else:
+            _check_device_tensor(ids, "ids")
+            if ids.dtype not in (torch.int32, torch.int64) or ids.dim() != 1:
+                raise ValueError(f"ids must be int32 or int64 [m], got {ids.dtype} {list(ids.shape)}")
+            # an id outside [0, total) lands in the spare entry: nothing is indexed out of range, nothing is read back
+            keep = torch.ones((total + 1,), dtype=torch.bool, device=self._ids.device)
+            if ids.shape[0]:
+                inside = (ids >= 0) & (ids < total)
+                keep[torch.where(inside, ids, torch.full_like(ids, total)).long()] = False
+            keep = keep[: max(total, 1)]
+        if keep.device != self._ids.device:
+            raise ValueError(f"the rows to remove are named on {keep.device}, the index is on {self._ids.device}")
+        old = self._old_storage()
+        if old is None:
+            return self  # no slots: nothing to remove
+        effective = slot_filter(self._ids, self._offsets, mask=keep).ids
+        self._take_regrouped(self._old_storage(effective), None, 0)
+        return self
+
+    def _check_same_lists(self, other) -> None:
+        """merge_from: the two indexes must quantise alike, bit for bit (`torch.equal` reads back)."""
+        if type(other) is not type(self):
+            raise TypeError(f"merge_from: a {type(self).__name__} takes a {type(self).__name__}, got {type(other).__name__}")
+        if other is self:
+            raise ValueError("merge_from: an index cannot be merged into itself")
+        other._need_add("merge_from (the other index)")
+        if (other._k, other._d) != (self._k, self._d) or other._ids.device != self._ids.device:
+            raise ValueError(f"merge_from: the other index has {other._k} lists of dim {other._d} on {other._ids.device}, this "
+                             f"one {self._k} of dim {self._d} on {self._ids.device}")
+        for name in ("_c16", *self._EXTRA):
+            a, b = getattr(self, name), getattr(other, name)
+            if name == "_c16":
+                a, b = a[: self._k], b[: self._k]
+            if a.shape != b.shape or not torch.equal(a, b):
+                raise ValueError(f"merge_from: the other index has other {name[1:].replace('c16', 'centroids')}; merged lists "
+                                 "need the same quantiser, bit for bit")
+
+    def merge_from(self, other, add_id: Optional[int] = None):
+        """Take over the rows of `other`, an index of the same class over the same centroids (and codebooks), bitwise
+        (DESIGN.md 3.29): shards embedded separately become one index.  `other`'s slots are the new rows of a regroup, their
+        labels their list numbers and their ids shifted by add_id (default: this index's running id, so that
+        `a.add(x1); b.add(x2); a.merge_from(b)` is `add(cat(x1, x2))`).  `other` is left as it is.  The comparison of the
+        quantisers reads back; the merge itself is enqueued."""
+        self._need_add("merge_from")
+        if not isinstance(other, _IVFIndex):
+            raise TypeError(f"merge_from: a {type(self).__name__} takes a {type(self).__name__}, got {type(other).__name__}")
+        self._check_same_lists(other)
+        if add_id is not None and (isinstance(add_id, bool) or not isinstance(add_id, int) or add_id < 0):
+            raise ValueError(f"add_id = {add_id!r}: None or a non-negative integer")
+        shift = self._running_id() if add_id is None else add_id
+        self._check_id_range(shift, other._running_id(), "merge_from")
+        new = other._old_storage()
+        if new is not None:
+            slots = other._ids.shape[0]
+            # the list of every slot from the offsets, without a read-back: the offsets at or below the slot, less one
+            # (slots from offsets[K] on get K, which names no list)
+            labels = torch.searchsorted(other._offsets[1:].contiguous(), torch.arange(slots, dtype=torch.int32, device=other._ids.device),
+                                        right=True).to(torch.int32)
+            ids = torch.where(other._ids >= 0, other._ids + shift, other._ids)
+            self._take_regrouped(self._old_storage(), (new[0], new[1], labels, ids), min(other._rows_bound, slots))
+        self._next_id = max(self._running_id(), shift + other._running_id())
         return self
 
     # ------------------------------------------------------------------------------------------------ search
@@ -880,7 +1150,7 @@ class _IVFIndex:
         query.  At least one of them.  A row beyond the end of a given tensor is left out.  Enqueued, no read-back; make it
         once and reuse it."""
         self._need_add("row_filter")
-        return slot_filter(self._ids, self._offsets, keys, mask)
+        return slot_filter(self._ids, self._offsets, keys, mask)._replace(generation=self._generation)
 
     def _filter(self, rows, query_keys, match, nq: int):
         """The filter arguments of `search` / `range_search`: (the ids the scan runs on, None for the index's own,
@@ -897,6 +1167,9 @@ class _IVFIndex:
         if rows.ids.dtype != torch.int32 or tuple(rows.ids.shape) != tuple(self._ids.shape):
             raise ValueError(f"rows: a RowFilter of {list(rows.ids.shape)} slots, this index has {list(self._ids.shape)} "
                              "(it belongs to another index, or to this one before load_state_dict)")
+        if rows.generation != self._generation:
+            raise ValueError(f"rows: a RowFilter of generation {rows.generation}, this index is at {self._generation}: extend, "
+                             "remove and merge_from regroup the slots, so make a new one with index.row_filter")
         if query_keys is None:
             return rows.ids, (None, None, None)  # the mask alone: the existing scan on the filter's ids
         if rows.keys is None:
@@ -999,6 +1272,7 @@ class _IVFIndex:
         for name, t in extra.items():
             setattr(self, name, t)
         self._added = True
+        self._next_id, self._rows_bound = None, rows.shape[0]  # the running id: max(ids) + 1, read back when first needed
         return self
 
 
@@ -1153,6 +1427,9 @@ class IVFFlatL2Index(_IVFIndex):
         rows, ids, offsets, sizes = build_lists(x16, labels, self._k)
         return rows, slot_bias(ids, half_norms), ids, offsets, sizes
 
+    def _encode_rows(self, prepared, labels, n):
+        return prepared[0], prepared[1][:n].neg()  # `slot_bias`'s value for the row
+
     def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None, *,
                rows: Optional[RowFilter] = None, query_keys=None, refine=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The k nearest rows of the probed lists for every row of q (fp16 / fp32 [nq, d] on the device): (squared distances
@@ -1217,6 +1494,9 @@ class IVFInt8Index(_IVFIndex):
     def _build_lists(self, xn, labels):
         return build_lists_int8(xn, labels, self._k)
 
+    def _encode_rows(self, prepared, labels, n):
+        return encode_rows_int8(prepared[0], n)
+
     def _search_lists(self, qn, probes, k, coarse, ids, keys):
         return search_lists_int8(qn, probes, self._rows, self._scales, self._ids if ids is None else ids, self._offsets, k, *keys)
 
@@ -1270,6 +1550,9 @@ class IVFPQIndex(_IVFIndex):
 
     def _build_lists(self, xn, labels):
         return build_lists_pq(xn, labels, self._k, self._codebooks)
+
+    def _encode_rows(self, prepared, labels, n):
+        return pq_encode(prepared[0], self._codebooks, n), None
 
     def _search_lists(self, qn, probes, k, coarse, ids, keys):
         return search_lists_pq(qn, probes, self._rows, self._codebooks, self._ids if ids is None else ids, self._offsets, k, *keys)
@@ -1325,6 +1608,9 @@ class IVFPQResidualIndex(IVFPQIndex):
 
     def _build_lists(self, xn, labels):
         return build_lists_pq_residual(xn, labels, self._c16[: self._k], self._codebooks)
+
+    def _encode_rows(self, prepared, labels, n):
+        return pq_encode_residual(prepared[0], labels, self._c16[: self._k], self._codebooks), None
 
     def _search_lists(self, qn, probes, k, coarse, ids, keys):
         if coarse is None:
@@ -1418,6 +1704,28 @@ class PreTransformIndex:
     def add(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None):
         """`index.add(transform.apply(x), labels)`; x fp16 / fp32 [n, d_in] on the device."""
         self.index.add(self.transform.apply(x), labels)
+        return self
+
+    def extend(self, x: torch.Tensor, labels: Optional[torch.Tensor] = None, first_id: Optional[int] = None):
+        """`index.extend(transform.apply(x), labels, first_id)`."""
+        self.index.extend(self.transform.apply(x), labels, first_id)
+        return self
+
+    def remove(self, ids: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None):
+        self.index.remove(ids, mask)
+        return self
+
+    def merge_from(self, other, add_id: Optional[int] = None):
+        """`index.merge_from(other.index, add_id)`; other: a `PreTransformIndex` with the same transform matrix and offset,
+        bit for bit (`torch.equal` reads back)."""
+        if not isinstance(other, PreTransformIndex):
+            raise TypeError(f"merge_from: a PreTransformIndex takes a PreTransformIndex, got {type(other).__name__}")
+        if other is self:
+            raise ValueError("merge_from: an index cannot be merged into itself")
+        mine, theirs = self.transform.state_dict(), other.transform.state_dict()
+        if set(mine) != set(theirs) or any(mine[k].shape != theirs[k].shape or not torch.equal(mine[k], theirs[k]) for k in mine):
+            raise ValueError("merge_from: the other index has another transform; merged lists need the same one, bit for bit")
+        self.index.merge_from(other.index, add_id)
         return self
 
     def probe(self, q: torch.Tensor, nprobe: int = 1) -> torch.Tensor:
