@@ -673,6 +673,50 @@ int smi_l2_kmeans_fit(const void* x_f16, int64_t n, int32_t d, int64_t K, int32_
                       int32_t* counts, double* objective, int32_t* moved, int32_t* empty, void* workspace,
                       int64_t workspace_bytes, void* stream);
 
+/* L2 search over the product-quantised lists, plain and residual (restated in tests/ivf_pq_l2_ref.py).  The
+ * row a slot stands for is what its codes decode to: y^ = smi_pq_decode of the codes (plain), or y^ = c + r^ with c the fp16
+ * Euclidean centroid of the slot's list and r^ the decoded fp16 residual (residual; FAISS's IVFx,PQy with METRIC_L2 and
+ * by_residual).  The nearest row has the largest q . y^ - 1/2 ||y^||^2, and
+ *   q . y^ - 1/2 ||y^||^2 = (q . c - 1/2 ||c||^2) + q . r^ - (c . r^ + 1/2 ||r^||^2).
+ * THE SCORE CONTRACT.  acc = the fp32 sum smi_ivf_pq_search produces for (query, decoded codes): the bits of smi_ivf_search
+ * on the decoded row.
+ *   plain     bias = -fl32(1/2 ||y^||^2): the half norm of the decoded row in smi_l2_prepare's fp64 order, negated -- the bits
+ *             of -half_norms of smi_l2_prepare(smi_pq_decode(codes)).             score = fl32(acc + bias)
+ *   residual  bias = -fl32(S1 + S2), S1 = sum_j c_j r^_j, S2 = 1/2 sum_j r^_j r^_j: each an fp64 sum of exact products in
+ *             smi_l2_prepare's lane, chunk and xor order (S2 halved exactly), joined by ONE fp64 add, rounded to fp32 once.
+ *             coarse = the biased score smi_l2_topk returns for the query against the list's centroid, q . c - 1/2 ||c||^2.
+ *                                                                                 score = fl32(fl32(acc + bias) + coarse)
+ *   both      ||q - y^||^2 = 2 (1/2 ||q||^2 - score).  A zero score is +0.  A pad slot has bias 0 and stays out by its id < 0,
+ *             whatever its bias.  On integer-valued operands every term is a multiple of 1/2 and, while below 2^24, exact:
+ *             the score is then exact and the distance the exact squared distance to the reconstructed row.
+ * smi_l2_pq_bias: out[i] (fp32 [n]) = the bias of item i of codes (uint8 [n, d / dsub]) against codebooks (fp16
+ *   [d / dsub][256][dsub], 16-byte aligned), one wave per item, no n x d temporary.  slot_ids (int32 [n], or NULL): the items
+ *   are the slots of a storage and an item whose id is below 0 gets 0 (its codes are not read).  centroids NULL: the plain
+ *   bias (labels and list_offsets must be NULL).  centroids (fp16 [K, d], 16-byte aligned): the residual bias against the
+ *   centroid of the item's list, which is labels[i] (int32 [n]: the stand-alone form over encoded rows) or the list whose
+ *   range of list_offsets (int32 [K + 1], with slot_ids) holds slot i -- exactly one of the two; a list number outside [0, K)
+ *   means no centroid (c = 0).  One device function serves both forms, so the bias of a row does not depend on the form.
+ *   Refusals: null codes / out, empty n, d not a multiple of 64, dsub, null or misaligned codebooks or centroids, K, labels
+ *   or list_offsets without centroids, neither or both of them with centroids, list_offsets without slot_ids.
+ * smi_l2_pq_search / smi_l2_pq_search_residual: smi_ivf_pq_search / smi_ivf_pq_search_residual with list_bias (fp32
+ *   [capacity_slots], 16-byte aligned, from smi_l2_pq_bias) behind codebooks, on prepared queries (smi_l2_prepare) and the
+ *   score above; everything else -- order, fill, unit rule, probes that name no list (their coarse entry is not read), pad
+ *   slots, a row mask as ids of -1, the workspace (smi_l2_pq_search_ws_bytes = smi_ivf_pq_search_workspace_bytes) -- is
+ *   theirs.  There are no keyed twins.  Refusals: smi_l2_flat_search's, and dsub, null or misaligned codebooks, a null or
+ *   misaligned list_bias, a null coarse.  Nothing is read back or allocated: capturable. */
+int smi_l2_pq_bias(const void* codes, int64_t n, int32_t d, int32_t dsub, const void* codebooks, const int32_t* slot_ids,
+                   const int32_t* list_offsets, const int32_t* labels, const void* centroids, int64_t K, float* out,
+                   void* stream);
+int64_t smi_l2_pq_search_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d, int32_t dsub);
+int smi_l2_pq_search(const void* q_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
+                     int32_t dsub, const void* codebooks, const float* list_bias, const int32_t* list_ids,
+                     const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* workspace,
+                     int64_t workspace_bytes, void* stream);
+int smi_l2_pq_search_residual(const void* q_f16, int64_t nq, int32_t d, const int32_t* probes, const float* coarse,
+                              int32_t nprobe, const void* list_codes, int32_t dsub, const void* codebooks, const float* list_bias,
+                              const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx,
+                              float* score, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* k-way merge of `parts` per-shard top-k lists (device fp32 / int32 [parts, n, k], each sorted as
  * smi_xsim_topk returns them) into the k best of their union, same total order (score desc, index asc).
  * Folds the per-rank partial y-side neighbour lists of the sharded margin scoring; part_idx /

@@ -435,6 +435,13 @@ SYMBOLS = {
     "smi_l2_slot_bias": (C.c_int, [_vp, _i64, _vp, _vp, _vp]),
     "smi_l2_flat_search_ws_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32]),
     "smi_l2_flat_search": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp]),
+    # L2 over the product-quantised lists: the PQ search entries' arguments with list_bias behind codebooks
+    "smi_l2_pq_bias": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "smi_l2_pq_search_ws_bytes": (_i64, [_i64, _i64, _i32, _i32, _i32, _i32]),
+    "smi_l2_pq_search": (C.c_int, [_vp, _i64, _i32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64,
+                                   _vp]),
+    "smi_l2_pq_search_residual": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp,
+                                            _vp, _i64, _vp]),
     "smi_l2_kmeans_finalize": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp]),
     "smi_l2_kmeans_fit_ws_bytes": (_i64, [_i64, _i64, _i32]),
     "smi_l2_kmeans_fit": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

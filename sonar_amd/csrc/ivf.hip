@@ -32,6 +32,7 @@
 #include "api_common.hpp"
 #include "ivf_scan.hpp"
 #include "bucket.hpp"
+#include "l2_rows.hpp"
 
 #include <type_traits>
 
@@ -1344,6 +1345,9 @@ int l2_flat_search_entry(const void* qn, int64_t nq, int32_t d, const int32_t* p
 // ---------------------------------------------------------------- regrouping: extend, remove, merge
 #include "ivf_regroup.hpp"
 
+// ---------------------------------------------------------------- L2 over the product-quantised lists
+#include "ivf_pq_l2.hpp"
+
 }  // namespace
 
 }  // namespace smi
@@ -1691,6 +1695,35 @@ int smi_lists_regroup(const void* old_rows, const float* old_aux, const int32_t*
   return regroup_entry(old_rows, old_aux, old_ids, old_offsets, old_slots, old_rows_bound, new_rows, new_aux, new_labels, new_ids,
                        new_id_base, n_new, row_bytes, K, list_rows, list_aux, list_ids, capacity_slots, list_offsets, list_sizes, ws,
                        ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- L2 over the product-quantised lists
+int smi_l2_pq_bias(const void* codes, int64_t n, int32_t d, int32_t dsub, const void* codebooks, const int32_t* slot_ids,
+                   const int32_t* list_offsets, const int32_t* labels, const void* centroids, int64_t K, float* out,
+                   void* stream) {
+  return pq_l2_bias_entry(codes, n, d, dsub, codebooks, slot_ids, list_offsets, labels, centroids, K, out, stream);
+}
+
+int64_t smi_l2_pq_search_ws_bytes(int64_t nq, int64_t K, int32_t nprobe, int32_t k, int32_t d, int32_t dsub) {
+  const KeepLastError keep;
+  const bool refused = check_search_args(nq, d, K, nprobe, k) || pq_check_dsub(d, dsub);
+  return refused ? 0 : (int64_t)SearchWs(nullptr, nq, K, nprobe, k).bytes();
+}
+
+int smi_l2_pq_search(const void* q_f16, int64_t nq, int32_t d, const int32_t* probes, int32_t nprobe, const void* list_codes,
+                     int32_t dsub, const void* codebooks, const float* list_bias, const int32_t* list_ids,
+                     const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx, float* score, void* ws, int64_t ws_bytes,
+                     void* stream) {
+  return pq_l2_search_entry<false>(q_f16, nq, d, probes, nullptr, nprobe, list_codes, dsub, codebooks, list_bias, list_ids,
+                                   list_offsets, K, k, idx, score, ws, ws_bytes, stream);
+}
+
+int smi_l2_pq_search_residual(const void* q_f16, int64_t nq, int32_t d, const int32_t* probes, const float* coarse,
+                              int32_t nprobe, const void* list_codes, int32_t dsub, const void* codebooks, const float* list_bias,
+                              const int32_t* list_ids, const int32_t* list_offsets, int64_t K, int32_t k, int32_t* idx,
+                              float* score, void* ws, int64_t ws_bytes, void* stream) {
+  return pq_l2_search_entry<true>(q_f16, nq, d, probes, coarse, nprobe, list_codes, dsub, codebooks, list_bias, list_ids,
+                                  list_offsets, K, k, idx, score, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 """IVF indexes over sentence embeddings on the MI355X engine: flat fp16 lists, int8 scalar-quantised
-lists and product-quantised lists, plain or of residuals.
+lists and product-quantised lists, plain or of residuals, under the cosine
+or, for the flat and the product-quantised lists, the squared Euclidean distance.
 
 Brute-force `xsim.topk` scores every query against every row.  An inverted-file index scores a query against the rows of the
 `nprobe` nearest of K clusters only, about nprobe / K of the work, which is what repeated search of one corpus (LASER-style
@@ -58,6 +59,12 @@ entry keep their limit of 8.
 quantiser is `clustering.KMeans`, every slot carries the bias -||row||^2 / 2 beside its id, and `search` returns (squared
 distances ascending, ids).  SONAR embeddings are not unit vectors; this is FAISS's `METRIC_L2`.
 
+`IVFPQL2Index` and `IVFPQResidualL2Index` are the product-quantised indexes under the squared Euclidean distance (DESIGN.md
+3.30; FAISS's `IVFx,PQy` with `METRIC_L2`, the second with `by_residual`): a Euclidean `KMeans`, codebooks trained on the rows
+as they are, and one fp32 bias per slot -- -1/2 ||y^||^2 of the decoded row, or -(c . r^ + 1/2 ||r^||^2) of the decoded residual
+against its list's centroid (`pq_l2_bias`) -- that the scan adds to the PQ scan's sum (`search_lists_pq_l2`).  `search` returns
+squared distances to the RECONSTRUCTED rows, ascending; `refine=prepare_rows(x)` re-scores the candidates against the fp16 rows.
+
 The storage life-cycle, on every class: `add` fills an empty index once; `extend(x)` takes further rows
 (`add(x1).extend(x2)` is the index `add(cat(x1, x2))` builds), `remove(ids= | mask=)` takes rows out, bytes and scan cost
 included, and `merge_from(other)` takes over the rows of an index of the same class over the same quantiser.  All three run
@@ -65,7 +72,7 @@ one device operation, `regroup_lists` (smi_lists_regroup): the surviving slots a
 into fresh list-contiguous storage, so a call costs about one build of the union -- feed chunks, not rows.  A `RowFilter`
 belongs to the storage it was made from: after any of the three, make a new one (an old one is refused).
 
-Not here: L2 on the int8 / PQ / residual lists and in the wide, keyed and range searches, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, lists of more than 16
+Not here: L2 on the int8 lists (a scale AND a bias per slot) and in the wide, keyed and range searches, an OPQ fitted on rows that are not normalised, a look-up-table scan for a handful of queries, codes of fewer than 8 bits, lists of more than 16
 results in one pass, k above 64, nprobe or k above 8 on the int8 / PQ / residual indexes, in `range_search` and in `mining`,
 the key predicate on the wide search, de-duplication or range search over quantised lists, in-place growth with spare capacity per list (an `extend` that costs
 O(new rows), not O(all rows), bytes), 64-bit ids, splitting of long lists, multi-GPU sharding; of filtering: skipping whole tiles or lists by key, per-query bitmaps or id lists, keys wider than
@@ -622,8 +629,9 @@ def _pq_train(xn, n: int, dsub, init, n_iter, residual=None) -> torch.Tensor:
 
 def pq_train(xn: torch.Tensor, dsub: int, init: torch.Tensor, n_iter: int = 10, n: Optional[int] = None) -> torch.Tensor:
     """smi_pq_train: codebooks fp16 [d / dsub, 256, dsub] after n_iter Lloyd rounds on the first n rows (default: all) of xn
-    (contiguous fp16 [>= n, d], rows of `normalize_rows`), started from the subvectors of the rows init names (device int32
-    [256], values in [0, n): not checked here).  No read-back; one init gives one result bit for bit."""
+    (contiguous fp16 [>= n, d]: rows of `normalize_rows`, or of `prepare_rows` for the L2 classes -- the quantiser is
+    Euclidean and never needed unit rows), started from the subvectors of the rows init names (device int32 [256], values in
+    [0, n): not checked here).  No read-back; one init gives one result bit for bit."""
     return _pq_train(xn, _check_rows16(xn, "xn", n), dsub, init, n_iter)
 
 
@@ -771,8 +779,75 @@ def search_lists_pq_residual(qn: torch.Tensor, probes: torch.Tensor, coarse: tor
     return _search_pq(qn, probes, codes, codebooks, ids, offsets, k, coarse, (slot_keys, query_keys, accept))
 
 
+def pq_l2_bias(codes: torch.Tensor, codebooks: torch.Tensor, labels: Optional[torch.Tensor] = None,
+               centroids: Optional[torch.Tensor] = None, *, ids: Optional[torch.Tensor] = None,
+               offsets: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """smi_l2_pq_bias: fp32 [n], the L2 bias of every row of codes (uint8 [n, M]) against codebooks (fp16
+    [M, 256, dsub]); one wave per row, nothing of size n x d is allocated.
+
+    Plain (centroids None): -fl32(1/2 ||y^||^2) of the decoded row y^, the bits of `prepare_rows(pq_decode(codes,
+    codebooks))[1].neg()`.  Residual (centroids: contiguous fp16 [K, d], the lists' Euclidean centroids): -fl32(sum c r^ +
+    1/2 sum r^ r^) against the centroid c of the row's list, r^ the decoded residual -- two fp64 sums in `prepare_rows`' order,
+    one fp64 add, one rounding.  The list of row i is labels[i] (device int32 [n]; the form `extend` encodes new rows with),
+    or, over the slots of a storage, the list whose range of offsets (int32 [K + 1]) holds slot i: exactly one of the two.
+    ids (int32 [n]): the rows are slots, and one whose id is below 0 (a pad, an unused slot) gets 0.  Both forms run one
+    device function: the bias of a row does not depend on the form."""
+    m, dsub = _check_codebooks(codebooks)
+    _check_codes(codes, "codes", m)
+    n, d = codes.shape[0], m * dsub
+    if ids is not None:
+        _check_table(ids, "ids", n, None)
+    k = 0
+    if centroids is None:
+        if labels is not None or offsets is not None:
+            raise ValueError("labels and offsets name the lists of centroids: give centroids, or neither")
+    else:
+        k = _check_centroids(centroids, d)
+        if (labels is None) == (offsets is None):
+            raise ValueError("with centroids, give labels or offsets: one of the two")
+        if labels is not None:
+            _check_table(labels, "labels", n, None)
+        else:
+            if ids is None:
+                raise ValueError("offsets describe slots: give ids with them")
+            _check_table(offsets, "offsets", k + 1, None)
+    lib = _lib.load()
+    out = torch.empty((n,), dtype=torch.float32, device=codes.device)
+    held = [None if t is None else t.contiguous() for t in (ids, offsets, labels)]  # (until the call is enqueued)
+    with torch.cuda.device(codes.device):
+        _lib.check(lib.smi_l2_pq_bias(codes.data_ptr(), n, d, dsub, codebooks.data_ptr(), *(None if t is None else t.data_ptr() for t in held),
+                                      None if centroids is None else centroids.data_ptr(), k, out.data_ptr(),
+                                      _lib.current_stream_ptr()))
+    return out
+
+
+def search_lists_pq_l2(q16: torch.Tensor, probes: torch.Tensor, codes: torch.Tensor, codebooks: torch.Tensor, bias: torch.Tensor,
+                       ids: torch.Tensor, offsets: torch.Tensor, k: int = 1,
+                       coarse: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """smi_l2_pq_search, or with coarse smi_l2_pq_search_residual: `search_lists_pq` on prepared queries
+    (`xsim.prepare_rows`) with score = fl32(sum + bias[slot]), bias fp32 [slots] from `pq_l2_bias`; with coarse (device fp32,
+    the shape of probes: the biased score of query q against the centroid of the list probes[q, p], `topk_bias_prepared`'s)
+    over residual codes, score = fl32(fl32(sum + bias[slot]) + coarse[q, p]).  (scores fp32 [nq, k] best first, ids int32
+    [nq, k]); ||q - row||^2 = 2 (h_q - score) for the reconstructed row.  ids may be a `RowFilter`'s.  No keyed form."""
+    _check_search_args(q16, probes, k)
+    if coarse is not None:
+        _check_coarse(coarse, probes.shape)
+    m, dsub = _check_codebooks(codebooks, q16.shape[1])
+    _check_codes(codes, "codes", m)
+    _check_device_tensor(bias, "bias")
+    if bias.dtype != torch.float32 or tuple(bias.shape) != (ids.shape[0],) or not bias.is_contiguous():
+        raise ValueError(f"bias must be contiguous fp32 [{ids.shape[0]}], got {bias.dtype} {list(bias.shape)}")
+    entry, extra = "smi_l2_pq_search", ()
+    if coarse is not None:
+        coarse = coarse.contiguous()  # (held until the call is enqueued)
+        entry, extra = "smi_l2_pq_search_residual", (coarse.data_ptr(),)
+    return _search(entry, "smi_l2_pq_search_ws_bytes", q16, probes, k, extra,
+                   (codes.data_ptr(), dsub, codebooks.data_ptr(), bias.data_ptr()), ids, offsets, (dsub,))
+
+
 class ProductQuantizer:
-    """M = d / dsub sub-quantisers of 256 codewords each over rows of `normalize_rows`.
+    """M = d / dsub sub-quantisers of 256 codewords each over rows of `normalize_rows`.  `train` and `encode`
+    normalise; the L2 classes train their codebooks on the rows as they are (`pq_train`) and hand them over.
 
     codebooks: fp16 [M, 256, dsub] on the device, dsub in {8, 16, 32, 64}, M * dsub a multiple of 64 (copied)."""
 
@@ -1560,6 +1635,9 @@ class IVFPQIndex(_IVFIndex):
     _BY_RESIDUAL = False  # the codes are of the rows themselves; `IVFPQResidualIndex`: of their residuals
 
     def _check_extra(self, state, d: int, fresh: bool):
+        if "metric_l2" in state:
+            raise ValueError("the state is that of an IVFPQL2Index or IVFPQResidualL2Index: its codes are of rows that are not "
+                             "normalised and its scores carry a bias")
         if ("by_residual" in state) != self._BY_RESIDUAL:
             raise ValueError("the state is that of an IVFPQResidualIndex: its codes are residuals against the list centroids"
                              if "by_residual" in state else
@@ -1644,6 +1722,208 @@ class IVFPQResidualIndex(IVFPQIndex):
         return state
 
 
+def _check_refine_l2(refine, d: int) -> None:
+    """`refine` of an L2 quantised index's search: None, or (x16, h) as `prepare_rows` of the original corpus returns it."""
+    if refine is None:
+        return
+    if not isinstance(refine, (tuple, list)) or len(refine) != 2:
+        raise TypeError("refine must be None or the pair (rows fp16, half norms fp32) prepare_rows returned for the corpus")
+    x16, h = refine
+    _check_matrix(x16, "refine")
+    if x16.dtype != torch.float16 or not x16.is_contiguous() or x16.shape[1] != d:
+        raise ValueError(f"refine must hold the contiguous fp16 [rows, {d}] matrix prepare_rows returned")
+    _check_device_tensor(h, "refine half norms")
+    if h.dtype != torch.float32 or tuple(h.shape) != (x16.shape[0],) or h.device != x16.device:
+        raise ValueError(f"refine must hold the fp32 [{x16.shape[0]}] half norms prepare_rows returned beside the rows")
+
+
+class IVFPQL2Index(IVFFlatL2Index):
+    """`IVFPQIndex` under the squared Euclidean distance, on the rows as they are (FAISS's `IVFx,PQy` with
+    `METRIC_L2`): the quantiser, the probe and the results are `IVFFlatL2Index`'s, the lists hold product-quantiser codes and
+    one fp32 bias per slot, -1/2 ||decoded row||^2 (`pq_l2_bias`).  A score is the flat L2 index's score against the
+    reconstructed row, bit for bit, so a distance is the squared distance to that row.  `state_dict` holds `bias`,
+    `codebooks` and the marker `metric_l2`; each of the four PQ classes refuses the states of the other three.
+
+    quantizer: a fitted `clustering.KMeans`, or an [K, d] tensor of centroids (rounded to fp16, not normalised); pq: a
+    `ProductQuantizer` of the same dim, or its fp16 [M, 256, dsub] codebooks (trained on rows that are not normalised)."""
+
+    _ROWS_DTYPE = torch.uint8
+    _ROWS_NAME = "uint8"
+    _EXTRA = ("_codebooks",)
+    _HOLDS = "an IVFPQL2Index holds product-quantiser codes of rows that are not normalised"
+    _BY_RESIDUAL = False
+
+    def __init__(self, quantizer: Union[KMeans, torch.Tensor], pq: Union[ProductQuantizer, torch.Tensor]):
+        if isinstance(quantizer, SphericalKMeans) and not isinstance(quantizer, KMeans):
+            raise TypeError(f"an {type(self).__name__} needs Euclidean centroids: a fitted clustering.KMeans, or a tensor")
+        super().__init__(quantizer)
+        if not isinstance(pq, ProductQuantizer):
+            pq = ProductQuantizer(pq)
+        if pq.dim != self._d:
+            raise ValueError(f"the product quantiser has dim {pq.dim}, the centroids {self._d}")
+        self._codebooks = pq.codebooks.clone()
+
+    @classmethod
+    def _train_codebooks(cls, x16, n: int, km: KMeans, dsub: int, init: torch.Tensor, pq_iter: int) -> torch.Tensor:
+        return pq_train(x16, dsub, init, pq_iter, n)
+
+    @classmethod
+    def train(cls, x: torch.Tensor, n_lists: int, dsub: int = 16, n_iter: int = 10, pq_iter: int = 8, seed: int = 0):
+        """Fit the coarse quantiser (Euclidean k-means, `n_lists` clusters, n_iter rounds) and the product quantiser (dsub
+        dimensions per sub-quantiser, pq_iter Lloyd rounds from the rows `clustering.init_rows(n, 256, seed)` names) on the
+        rows of x as they are (fp16 / fp32 [n, d] on the device, n >= 256).  The residual class labels the rows with their
+        Euclidean nearest centroid, as `add` will, and fits the codebooks on the residuals."""
+        _check_matrix(x, "x")
+        n, d = x.shape
+        _check_dsub(dsub, d)
+        init = init_rows(n, PQ_CODEWORDS, seed).to(device=x.device, dtype=torch.int32)
+        km = KMeans(n_lists, n_iter=n_iter, seed=seed).fit(x)
+        return cls(km, cls._train_codebooks(prepare_rows(x)[0], n, km, dsub, init, pq_iter))
+
+    @property
+    def codebooks(self) -> torch.Tensor:
+        return self._codebooks
+
+    @property
+    def dsub(self) -> int:
+        return self._codebooks.shape[2]
+
+    def _list_centroids(self) -> Optional[torch.Tensor]:
+        """The centroids the codes are residuals against; None: the codes are of the rows themselves."""
+        return None
+
+    def _build_lists(self, x16, half_norms, labels):
+        cent = self._list_centroids()
+        codes, ids, offsets, sizes = (build_lists_pq(x16, labels, self._k, self._codebooks) if cent is None else
+                                      build_lists_pq_residual(x16, labels, cent, self._codebooks))
+        bias = pq_l2_bias(codes, self._codebooks, None, cent, ids=ids, offsets=None if cent is None else offsets)
+        return codes, bias, ids, offsets, sizes
+
+    def _encode_rows(self, prepared, labels, n):
+        cent = self._list_centroids()
+        if cent is None:
+            codes = pq_encode(prepared[0], self._codebooks, n)
+            return codes, pq_l2_bias(codes, self._codebooks)
+        codes = pq_encode_residual(prepared[0], labels, cent, self._codebooks)
+        return codes, pq_l2_bias(codes, self._codebooks, labels, cent)
+
+    def _scan(self, q16, nq: int, probes, k: int, coarse, ids):
+        return search_lists_pq_l2(q16, probes, self._rows, self._codebooks, self._bias, self._ids if ids is None else ids,
+                                  self._offsets, k)
+
+    def _search_l2(self, q, k, nprobe, probes, coarse, rows, query_keys, refine):
+        if query_keys is not None:
+            raise TypeError("query_keys: the keyed scan has no L2 twin (DESIGN.md 7); filter with rows=index.row_filter(mask=...)")
+        _check_refine_l2(refine, self._d)
+        nq = self._check_search(q, k, nprobe, probes)
+        ids = self._filter(rows, None, "==", nq)[0]
+        if coarse is not None:
+            if probes is None:
+                raise ValueError("coarse belongs to probes: give both, or neither")
+            _check_coarse(coarse, probes.shape)
+        q16, hq = prepare_rows(q)
+        if probes is None:
+            coarse, probes = self._nearest_lists(q16, nq, nprobe)
+        score, idx = self._scan(q16, nq, probes, k, coarse, ids)
+        if refine is not None:
+            score, idx = refine_candidates_l2(q16, nq, refine[0], refine[1], idx)
+        return (2.0 * (hq[:nq, None] - score)).clamp_min(0.0), idx
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None, refine=None, *,
+               rows: Optional[RowFilter] = None, query_keys=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`IVFFlatL2Index.search` on the reconstructed rows: (squared distances fp32 [nq, k] ascending, ids int32 [nq, k]),
+        ties to the lower row number, (+inf, -1) where the probed lists hold fewer than k rows; sq_dist = clamp_min(2 (h_q -
+        score), 0), score the flat L2 scan's against the decoded row, bit for bit.  k, nprobe <= 8; probes and rows (a
+        `RowFilter` built with a mask) as there.
+
+        refine: None, or `prepare_rows(x)` of the corpus the index was built from -- the pair (rows fp16, half norms fp32),
+        row number = id.  The k candidates are re-scored as fl32(q . x[id] - h[id]) (`mining.pair_scores` in cosine mode,
+        which on prepared rows is a plain dot product) and re-ordered by the two stable sorts of `refine_candidates`; the
+        distances returned are then those to the fp16 rows.  No kernel of its own, no host synchronisation."""
+        return self._search_l2(q, k, nprobe, probes, None, rows, query_keys, refine)
+
+    @property
+    def centroids_normalized(self) -> torch.Tensor:
+        raise TypeError(f"an {type(self).__name__} keeps its centroids as they are: centroids_f16")
+
+    def range_search(self, *args, **kwargs):
+        raise TypeError(f"range_search needs the fp16 lists of an IVFFlatIndex; {self._HOLDS}")
+
+    def probe_wide(self, *args, **kwargs):
+        raise TypeError(f"probe_wide is the paged cosine top-k; an {type(self).__name__} probes at most 8 lists (DESIGN.md 7)")
+
+    def search_wide(self, *args, **kwargs):
+        raise TypeError(f"search_wide needs the fp16 lists of an IVFFlatIndex; {self._HOLDS}")
+
+    def self_join(self, *args, **kwargs):
+        raise TypeError(f"self_join and semdedup need the fp16 lists of an IVFFlatIndex; {self._HOLDS}")
+
+    def _check_extra(self, state, d: int, fresh: bool):
+        if "metric_l2" not in state:
+            raise ValueError("state lacks ['metric_l2']: the state is that of an IVFPQIndex or IVFPQResidualIndex, whose rows "
+                             "are normalised")
+        if ("by_residual" in state) != self._BY_RESIDUAL:
+            raise ValueError("the state is that of an IVFPQResidualL2Index: its codes are residuals against the list centroids"
+                             if "by_residual" in state else
+                             "state lacks ['by_residual']: the state is that of a plain IVFPQL2Index")
+        codebooks = state["codebooks"]
+        m, _ = _check_codebooks(codebooks, d)
+        return m, {"_codebooks": codebooks.clone()}
+
+    def state_dict(self) -> Dict[str, torch.Tensor]:
+        """`IVFPQIndex.state_dict` (rows: the uint8 codes; codebooks) with the centroids as they are, `bias` (fp32 [slots]),
+        the marker `metric_l2` and, for the residual class, the marker `by_residual`."""
+        state = super().state_dict()
+        if self._BY_RESIDUAL:
+            state["by_residual"] = torch.ones(1, dtype=torch.uint8, device=self._rows.device)
+        return state
+
+
+class IVFPQResidualL2Index(IVFPQL2Index):
+    """`IVFPQL2Index` with every row encoded as its residual against the Euclidean centroid of its list (DESIGN.md 3.30;
+    FAISS's `IVFx,PQy` with `METRIC_L2` and `by_residual`, its default): the row a slot stands for is c + r^, the slot's bias
+    is -(c . r^ + 1/2 ||r^||^2), and a score is fl32(fl32(sum + bias) + coarse), coarse the biased score of the query against
+    the list's centroid that the L2 probe has already computed.  The same storage as the plain class, byte for byte in its
+    layout.  The codes and the bias hang on the bits of the fp16 centroids."""
+
+    _BY_RESIDUAL = True
+    _HOLDS = "an IVFPQResidualL2Index holds product-quantiser codes of residuals of rows that are not normalised"
+
+    @classmethod
+    def _train_codebooks(cls, x16, n: int, km: KMeans, dsub: int, init: torch.Tensor, pq_iter: int) -> torch.Tensor:
+        k = km.n_clusters
+        labels = topk_bias_prepared(x16, n, km._c16, k, km._ch.neg(), 1)[1][:, 0].contiguous()
+        return pq_train_residual(x16, labels, km._c16[:k], dsub, init, pq_iter)
+
+    def _list_centroids(self) -> torch.Tensor:
+        return self._c16[: self._k]
+
+    def coarse_scores(self, q16: torch.Tensor, nq: int, probes: torch.Tensor) -> torch.Tensor:
+        """fp32 [nq, nprobe]: fl32(q . c - h_c) of the first nq rows of q16 (`prepare_rows`) against the centroids probes
+        names, the dot products by `mining.pair_scores` in cosine mode; an entry outside [0, K) is clamped into range first
+        (the scan does not read its value).  The probe's own scores (`xsim.topk_bias_prepared`) are the tiled kernel's and
+        may differ from these in the last place."""
+        src = torch.arange(nq, device=probes.device).repeat_interleave(probes.shape[1])
+        trg = probes.clamp(0, self._k - 1).reshape(-1)
+        dots = pair_scores(q16, nq, self._c16, self._k, src, trg, None, None, "cosine")
+        return (dots - self._ch[trg.long()]).reshape(nq, probes.shape[1])
+
+    def _scan(self, q16, nq: int, probes, k: int, coarse, ids):
+        if coarse is None:
+            coarse = self.coarse_scores(q16, nq, probes)
+        return search_lists_pq_l2(q16, probes, self._rows, self._codebooks, self._bias, self._ids if ids is None else ids,
+                                  self._offsets, k, coarse)
+
+    def search(self, q: torch.Tensor, k: int = 1, nprobe: int = 1, probes: Optional[torch.Tensor] = None,
+               coarse: Optional[torch.Tensor] = None, refine=None, *, rows: Optional[RowFilter] = None,
+               query_keys=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """`IVFPQL2Index.search`; a distance is the squared distance to c + r^.  With probes None the index probes by itself
+        and the coarse term is the biased score `xsim.topk_bias_prepared` returns beside every list number: no extra work.
+        With probes given, coarse is None (computed by `coarse_scores`; its bits may differ from the probe's own in the last
+        place) or device fp32 [nq, nprobe], fl32(q . c - h_c) for the centroid of every probed list."""
+        return self._search_l2(q, k, nprobe, probes, coarse, rows, query_keys, refine)
+
+
 def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """The candidates idx (int32 [nq, k], -1 = none) of the first nq rows of qn re-scored with their fp16 cosines against the
     rows of xn (both from `normalize_rows`) and every row re-ordered into the total order: (scores fp32 [nq, k], ids int32
@@ -1654,11 +1934,30 @@ def refine_candidates(qn: torch.Tensor, nq: int, xn: torch.Tensor, idx: torch.Te
     src = torch.arange(nq, device=idx.device).repeat_interleave(k)
     trg = torch.where(have, idx, torch.zeros_like(idx)).reshape(-1)
     cos = pair_scores(qn, nq, xn, xn.shape[0], src, trg, None, None, "cosine").reshape(nq, k)
-    cos = torch.where(have, cos, torch.full_like(cos, float("-inf")))
+    return _total_order(torch.where(have, cos, torch.full_like(cos, float("-inf"))), idx)
+
+
+def _total_order(score: torch.Tensor, idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Every row of (score, idx) [nq, k] in the total order, score descending and ties to the lower id: two stable sorts."""
     by_id = torch.sort(idx, dim=1, stable=True)[1]  # then a stable sort by score: ties go to the lower id
-    cos, idx = torch.gather(cos, 1, by_id), torch.gather(idx, 1, by_id)
-    order = torch.sort(cos, dim=1, descending=True, stable=True)[1]
-    return torch.gather(cos, 1, order), torch.gather(idx, 1, order)
+    score, idx = torch.gather(score, 1, by_id), torch.gather(idx, 1, by_id)
+    order = torch.sort(score, dim=1, descending=True, stable=True)[1]
+    return torch.gather(score, 1, order), torch.gather(idx, 1, order)
+
+
+def refine_candidates_l2(q16: torch.Tensor, nq: int, x16: torch.Tensor, half_norms: torch.Tensor,
+                         idx: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """`refine_candidates` under L2: the candidates idx (int32 [nq, k], -1 = none) of the first nq rows of q16
+    re-scored as fl32(q . x[id] - half_norms[id]) against the prepared corpus (x16, half_norms of `prepare_rows`) and every
+    row re-ordered into the total order: (scores fp32 [nq, k], ids int32 [nq, k]); ||q - x||^2 = 2 (h_q - score).  The dot
+    product is `mining.pair_scores` in cosine mode, which on prepared rows divides by nothing."""
+    k = idx.shape[1]
+    have = idx >= 0
+    src = torch.arange(nq, device=idx.device).repeat_interleave(k)
+    trg = torch.where(have, idx, torch.zeros_like(idx)).reshape(-1)
+    dot = pair_scores(q16, nq, x16, x16.shape[0], src, trg, None, None, "cosine").reshape(nq, k)
+    score = dot - half_norms[trg.long()].reshape(nq, k)
+    return _total_order(torch.where(have, score, torch.full_like(score, float("-inf"))), idx)
 
 
 class PreTransformIndex:
@@ -1667,7 +1966,7 @@ class PreTransformIndex:
     equals `index.search(transform.apply(q), ...)` bit for bit, and every argument of the wrapped class passes through.
 
     transform: a `sonar_amd.transforms.LinearTransform` (`PCA`, `OPQ`) whose d_out is the index's dim; index: one of the four
-    IVF classes, before or after its `add`."""
+    IVF classes or of their L2 counterparts, before or after its `add`."""
 
     def __init__(self, transform, index: _IVFIndex):
         from .transforms import LinearTransform
@@ -1746,6 +2045,9 @@ class PreTransformIndex:
         the transformed space, against the transformed corpus) is not reachable through the wrapper: call
         `index.search(transform.apply(q), ..., refine=)` for that."""
         if refine is not None:
+            if isinstance(self.index, IVFFlatL2Index):
+                raise TypeError("refine re-scores with cosines in the original space; the wrapped index scores squared "
+                                "distances: call index.search(transform.apply(q), refine=prepare_rows(transform.apply(x)))")
             _check_refine(refine, self.dim)
         qt = self.transform.apply(q)
         score, idx = self.index.search(qt, k, nprobe, probes, **kwargs)
